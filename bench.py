@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — refined action chunks / s on MI355X for the VLA-Touch action-refinement path.
 
-    python bench.py [--gpus N --steps K --warmup W]            (N=1)
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]            (N=1)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One "step" = one `DiffusionController.predict` over a batch of `--batch` (32) episodes per GPU: 2 camera batches of
@@ -10,9 +10,11 @@ denormalised refined chunks [B, T, 10].  Inputs are resident in HBM before the t
 noise is drawn on device inside the step (as the reference does).  Episodes are independent: ranks take disjoint
 batches (weak scaling), frozen weights are broadcast once from rank 0 over RCCL, no collective in the step loop.
 
-Prints ONE JSON line (rank 0) with the BASELINE.json metric plus `roofline` (dominant kernel class = the 256-square ping-pong MFMA GEMM tile,
+Prints ONE JSON line (rank 0) with the BASELINE.json metric.  A plain run only sets up, warms up, times the --steps steps and
+prints that line (plus the outputs of the last timed step with --dump-outputs DIR).  With --full the line also carries the side
+measurements: `latency_mode` (one batch at a time), `roofline` (dominant kernel class = the 256-square ping-pong MFMA GEMM tile,
 gemm_pt_kernel / gemm_pp256d_kernel, timed live with HIP events on its launch stream; `roofline_other` carries the same
-figures for the 128-column GEMM kernel) and `cpu_baseline` (the oracle on the host cores).
+figures for the 128-column GEMM kernel), `alt_rdt_compute`, `onbox_peaks` and `cpu_baseline` (the oracle on the host cores).
 """
 from __future__ import annotations
 
@@ -38,6 +40,7 @@ import torch
 
 PEAK_BF16_TFLOPS = 2500.0     # MI355X dense bf16 MFMA peak (MI355X_MICROARCH.md)
 PEAK_HBM_GBS = 8000.0
+DUMP_MAX_ELEMS = 1 << 22      # per dumped array (16 MB of float32); the largest step output (siglip tokens) is sampled down to it
 
 
 def parse():
@@ -83,7 +86,16 @@ def parse():
                          "same weights, its own graphs; workloads with an RDT chunk only; 0 = skip)")
     ap.add_argument("--latency-steps", type=int, default=6,
                     help="steps of the extra ONE-batch-at-a-time pass run after the timed region (reported as `latency_mode`; 0 = skip)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements after the timed region: latency mode, roofline legs, the other 16-bit activation type "
+                         "of RDT-1B, on-box peaks and the CPU baseline with its parity checks (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (the arrays its caller receives) as DIR/<name>.npy in float32; "
+                         "an output above %d elements is replaced by a fixed seeded sample of that many" % DUMP_MAX_ELEMS)
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def synth_inputs(B, T, res, seed, device, force_dim=3):
@@ -101,9 +113,34 @@ def synth_inputs(B, T, res, seed, device, force_dim=3):
     )
 
 
+def step_outputs(holder, workload):
+    """What one step handed its caller (`holder` of the slot that ran it) as host arrays: name -> float32 ndarray (float64 for integer
+    outputs).  An output above DUMP_MAX_ELEMS elements becomes a fixed seeded sample of its flattened values, drawn on the device."""
+    names = {"chunk": ("rdt_chunk",),
+             "out": {"dino_mlp": ("obs_cond",), "siglip": ("image_tokens",),
+                     "marker": ("marker_displacement", "force_magnitude", "force_direction")}.get(workload, ("a_hat",))}
+    arrays = {}
+    for key, val in holder.items():
+        parts = val if isinstance(val, (tuple, list)) else (val,)
+        for i, part in enumerate(parts):
+            nm = names[key][i] if key in names and i < len(names[key]) else f"{key}_{i}"
+            t = part if torch.is_tensor(part) else torch.from_numpy(np.ascontiguousarray(part))
+            wide = t.dtype == torch.float64 or not t.is_floating_point()
+            flat = t.detach().reshape(-1)
+            if flat.numel() > DUMP_MAX_ELEMS:
+                idx = np.sort(np.random.default_rng(0).integers(0, flat.numel(), DUMP_MAX_ELEMS))
+                flat = flat[torch.from_numpy(idx).to(flat.device)]
+                arrays[nm] = flat.to(torch.float64 if wide else torch.float32).cpu().numpy()
+            else:
+                arrays[nm] = flat.to(torch.float64 if wide else torch.float32).cpu().numpy().reshape(tuple(t.shape))
+    return arrays
+
+
 def main():
     args = parse()
     if args.workload in ("train", "train_lstm"):     # SURVEY 8f-4: the controller training step (one JSON line, tools/train_bench.py; 1 GPU)
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs: the training workloads keep their outputs inside tools/train_bench.py (not supported)")
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         import train_bench
         B = args.batch if args.batch != 32 else 128                   # the reference's training default (bridge_train.py:698)
@@ -114,8 +151,8 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
-        # `python bench.py --gpus N` launches its own ranks: re-exec under torch.distributed.run, one process per GPU, rendezvous on
-        # 127.0.0.1 (the container hostname may not resolve).  Rank 0 of the relaunched job prints the ONE JSON line.
+        # `python bench.py --gpus N` launches its own ranks: a child torch.distributed.run, one process per GPU, rendezvous on
+        # 127.0.0.1 (the container hostname may not resolve).  Rank 0 of the child job prints the ONE JSON line; this process only waits.
         import socket
         with socket.socket() as s_:
             s_.bind(("127.0.0.1", 0))
@@ -125,7 +162,8 @@ def main():
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
                "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
         sys.stdout.flush()
-        os.execv(sys.executable, cmd)
+        import subprocess
+        raise SystemExit(subprocess.run(cmd).returncode)
     if world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: launch one process per GPU (python bench.py --gpus N does it itself)")
     assert torch.cuda.is_available(), "bench.py needs an MI355X (no CPU path in the product)"
@@ -180,7 +218,9 @@ def main():
     vla_bufs = [torch.empty(B, T, 10, dtype=torch.float32, device=dev) for _ in range(n_streams)]
     xinit_bufs = [torch.empty(B, 64, 128, dtype=torch.float32, device=dev) for _ in range(n_streams)]
     from vlatouch import ops as _ops
-    rng = _ops.DeviceRng(20250928 + rank, dev)
+    # one device RNG state per batch in flight: the graphs of different slots run concurrently, and a shared Philox counter would hand
+    # each slot whichever draws it reached first (outputs different from run to run); per slot, the draws depend on its own step count only
+    rngs = [_ops.DeviceRng(20250928 + rank + 1000 * si, dev) for si in range(n_streams)]
 
     # ---- RDT-1B chunk generator (config NOT in the reference: upstream RDT-1B values, SURVEY §8a-8 [assumed-upstream])
     rdt = rin = None
@@ -226,7 +266,8 @@ def main():
             getattr(lstm, name).load_state_dict(synth.torch_state_dict(shp, prefix=f"lstm_ctrl.{name}."))
         lstm.to(dev)
         lstm.stats = {k: v.to(dev) for k, v in synth.unit_stats().items()}
-        lstm_ins = [dict(forces=torch.randn(B, T, 3, device=dev)) for _ in range(n_streams)]
+        gl = torch.Generator(device=dev).manual_seed(5678 + rank)          # seeded: the same inputs on every run (--dump-outputs compares runs)
+        lstm_ins = [dict(forces=torch.randn(B, T, 3, device=dev, generator=gl)) for _ in range(n_streams)]
         lstm_in = lstm_ins[0]
     mk = mk_frames = None
     if args.workload == "marker":       # GelSight frames -> marker displacements + force estimate, a 256-frame stream per step
@@ -245,7 +286,8 @@ def main():
         ssd = synth.fill_state_dict_device(synth.siglip_shapes(**c), dev, wdt, seed=9)
         sig = SiglipEngine({k: v.cpu() for k, v in ssd.items()}, heads=c["heads"], precision="fp16" if args.precision == "bf16" else "fp32", device=dev)
         del ssd
-        sig_pxs = [(2.0 * torch.rand(6 * B, 3, 384, 384, device=dev) - 1.0) for _ in range(n_streams)]
+        gs = torch.Generator(device=dev).manual_seed(8765 + rank)          # seeded: the same frames on every run
+        sig_pxs = [(2.0 * torch.rand(6 * B, 3, 384, 384, device=dev, generator=gs) - 1.0) for _ in range(n_streams)]
         sig_px = sig_pxs[0]
         if args.workload == "robot":
             tok_bufs = [torch.empty(6 * B, 729, 1152, dtype=rdt.compute_dtype, device=dev) for _ in range(n_streams)]
@@ -257,6 +299,7 @@ def main():
         out_holder, noise_buf = out_holders[slot], noise_bufs[slot]
         inp = inps[slot]
         rdt = ctx["rdt"]
+        rng = rngs[slot]
         rin = ctx["rins"][slot] if rdt is not None else None
         lstm_in = lstm_ins[slot] if lstm is not None else None
         sig_px = sig_pxs[slot] if sig is not None else None
@@ -363,12 +406,16 @@ def main():
         elapsed = time.perf_counter() - t_start
         lat = sorted(ev0[i].elapsed_time(ev1[i]) for i in range(args.steps))
         p50 = lat[len(lat) // 2]
-        out_holder = out_holders[0]
+        # what the LAST timed step handed over (its slot's buffers), copied out before anything below reuses them
+        if args.dump_outputs and rank == 0:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for nm, a in step_outputs(out_holders[(args.steps - 1) % n_streams], args.workload).items():
+                np.save(os.path.join(args.dump_outputs, nm + ".npy"), a)
 
-        # ---- latency mode inside the same run: ONE batch at a time (slot 0's graph back to back on its stream) — what a caller that waits for
-        #      each refined batch sees; same barrier + synchronize bracket, same max over ranks
+        # ---- latency mode inside the same run (--full): ONE batch at a time (slot 0's graph back to back on its stream) — what a caller that
+        #      waits for each refined batch sees; same barrier + synchronize bracket, same max over ranks
         lat_elapsed = None
-        if args.latency_steps > 0 and n_streams > 1:
+        if args.full and args.latency_steps > 0 and n_streams > 1:
             barrier()
             t1 = time.perf_counter()
             for _ in range(args.latency_steps):
@@ -376,10 +423,10 @@ def main():
             barrier()
             lat_elapsed = time.perf_counter() - t1
 
-        # ---- roofline leg: one eager step with HIP events around every launch of the dominant GEMM kernel
+        # ---- roofline leg (--full): one eager step with HIP events around every launch of the dominant GEMM kernel
         lib = L.lib()
         prof = {}
-        for mode in (2, 3, 4, 6):    # 2 = 256-square GEMM tile, 3 = 160 / 128-column GEMM tiles, 4 = cached cross-attention, 6 = fused U-Net convolution (one eager step each)
+        for mode in ((2, 3, 4, 6) if args.full else ()):    # 2 = 256-square GEMM tile, 3 = 160 / 128-column GEMM tiles, 4 = cached cross-attention, 6 = fused U-Net convolution (one eager step each)
             lib.vt_prof_enable(mode)
             step()
             stream.synchronize()
@@ -398,7 +445,7 @@ def main():
         range_guard = {"rdt_compute_requested": args.rdt_compute, "rdt_compute_used": rdt_used, "rdt_flag": bits, "rdt_flag_names": L.range_names(bits),
                        "note": "sticky device word OR-ed by the kernels of every step of this run (warm-up, graph replays, timed region): 0 = no value left the compute type's range"}
     alt_elapsed = None
-    if rdt is not None and args.precision == "bf16" and args.alt_compute_steps > 0 and args.workload in ("full", "rdt"):
+    if args.full and rdt is not None and args.precision == "bf16" and args.alt_compute_steps > 0 and args.workload in ("full", "rdt"):
         try:                                            # a side measurement: it must never take the headline line down with it
             from models.rdt_runner import RDTRunner as _RR
             alt_mode = "bf16" if rdt_used == "f16" else "f16"
@@ -531,7 +578,8 @@ def main():
     # the last such run is attached when present (null otherwise: counters cannot be read from inside this process)
     pmc = {}
     try:
-        pmc = json.load(open(os.path.join(ROOT, "profiles", "pmc_traffic.json")))
+        if prof:
+            pmc = json.load(open(os.path.join(ROOT, "profiles", "pmc_traffic.json")))
     except Exception:
         pass
     # the counters are a BUILDER-side measurement (separate rocprofv3 --pmc passes, tools/profile_round.sh) read from a committed file, not taken in this run:
@@ -540,7 +588,7 @@ def main():
                       "csrc_sha16_of_this_tree": L.csrc_sha16(), "same_kernel_sources": pmc.get("csrc_sha16") == L.csrc_sha16()} if pmc else None
 
     def roof(mode, name, pmc_key):
-        ms_, fl_, by_, n_ = prof[mode]
+        ms_, fl_, by_, n_ = prof.get(mode, (0, 0, 0, 0))
         if n_ <= 0 or ms_ <= 0:
             return None
         tf = fl_ / (ms_ * 1e-3) / 1e12
@@ -555,7 +603,7 @@ def main():
     # on-box measured peaks (report fractions of the nominal AND of a measured peak): a large square bf16 GEMM on the
     # same kernel family and a device-to-device copy (read + write bytes)
     onbox = None
-    if rank == 0:
+    if rank == 0 and args.full:
         from vlatouch import ops as _ops
         with torch.cuda.stream(stream):
             a8 = torch.randn(8192, 8192, device=dev).to(torch.bfloat16)
@@ -636,7 +684,7 @@ def main():
     #      chunks/s = 1 / (t_pi / CB + t_rdt).  Round 6: the thread count is SWEPT (--cpu-threads 32,64,128, passive OpenMP waits — set at the top of this
     #      file, before torch loads its OpenMP runtime) on the pi_I leg and on a one-denoise-step probe of the RDT leg; the timed legs run at the best count of
     #      each, `cores` = the count of the dominant (RDT) leg, the rest of the sweep is in `cores_sweep`.
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload in ("pi_refine", "full"):
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload in ("pi_refine", "full"):
         from oracle import controller as oc
         avail = len(os.sched_getaffinity(0))
         cand = sorted({max(1, min(avail, int(c))) for c in str(args.cpu_threads).split(",") if c.strip()})

@@ -3,7 +3,7 @@
 # Each line carries roofline_other[gemm_pw].frac and latency_mode.  Output: gpurun_out/rows/*.json
 set -u
 out=gpurun_out/rows; mkdir -p $out
-run() { name=$1; shift; timeout 600 python bench.py --no-cpu-baseline --alt-compute-steps 0 "$@" > $out/$name.json 2> $out/$name.err; echo "$name rc=$? $(head -c 300 $out/$name.json)"; }
+run() { name=$1; shift; timeout 600 python bench.py --full --no-cpu-baseline --alt-compute-steps 0 "$@" > $out/$name.json 2> $out/$name.err; echo "$name rc=$? $(head -c 300 $out/$name.json)"; }
 run b32_s1 --batch 32 --streams 1 --latency-steps 0
 run b32_s3 --batch 32 --streams 3
 run b64_s1 --batch 64 --streams 1 --latency-steps 0

@@ -1,7 +1,7 @@
 #!/bin/bash
 # every workload of bench.py once -> gpurun_out/rNN_bench_*.json (copy into profiles/)
 R=${1:-r02}; O=gpurun_out
-run() { name=$1; shift; python bench.py "$@" > $O/${R}_bench_$name.json 2> $O/${R}_bench_$name.err; python - <<P
+run() { name=$1; shift; python bench.py --full "$@" > $O/${R}_bench_$name.json 2> $O/${R}_bench_$name.err; python - <<P
 import json
 try:
     d=json.loads(open("$O/${R}_bench_$name.json").read().strip().splitlines()[-1]); print("$name", d["value"], d["unit"], d["ms_per_step"], "p50", d["p50_step_latency_ms"])

@@ -7,5 +7,5 @@ cd $GRAFT_REPO_ROOT
 python -m pytest tests/test_gpu_rdt.py -q -m gpu -k "cross_attention or wide or predict_action" 2>&1 | tail -1
 for r in 1 2; do for lib in "" /tmp/libvlatouch_shfl.so; do
   echo "== online softmax (rms var), lib=${lib:-product(permlane)}"
-  VLATOUCH_LIB=$lib python bench.py --no-cpu-baseline --alt-compute-steps 0 --rms-mode var 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.readline()); r=[x for x in d['roofline_other'] if 'attn_kvt' in x['kernel']][0]; print(d['value'], d['latency_mode']['chunks_per_s'], 'kvt avg us', r['avg_launch_us'])"
+  VLATOUCH_LIB=$lib python bench.py --full --no-cpu-baseline --alt-compute-steps 0 --rms-mode var 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.readline()); r=[x for x in d['roofline_other'] if 'attn_kvt' in x['kernel']][0]; print(d['value'], d['latency_mode']['chunks_per_s'], 'kvt avg us', r['avg_launch_us'])"
 done; done

@@ -8,7 +8,7 @@ cd $GRAFT_REPO_ROOT
 O=gpurun_out
 mkdir -p $O/pmc
 # 1. per-kernel time of the headline command line (2 batches in flight, hipGraph)
-rocprofv3 --kernel-trace --stats -d $O/prof_full -o full -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline --alt-compute-steps 0 > $O/${R}_prof_bench.json 2> $O/${R}_prof_bench.err
+rocprofv3 --kernel-trace --stats -d $O/prof_full -o full -- python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --alt-compute-steps 0 > $O/${R}_prof_bench.json 2> $O/${R}_prof_bench.err
 python tools/prof_summary.py $(find $O/prof_full -name "*.db" | head -1) 10 > $O/${R}_full_kernel_stats.txt
 rm -rf $O/prof_full
 # 2. the same with one batch in flight (kernel durations without co-running kernels)
