@@ -28,6 +28,7 @@ typedef struct vt_unet_s* vt_unet_t;
 typedef struct vt_dino_s* vt_dino_t;
 typedef struct vt_lstm_s* vt_lstm_t;
 typedef struct vt_rdt_s* vt_rdt_t;
+typedef struct vt_t5_s* vt_t5_t;
 
 const char* vt_last_error(void);
 int vt_version(void);
@@ -183,6 +184,30 @@ int vt_dino_set_range_flag(vt_dino_t h, unsigned* word);      /* see vt_rdt_set_
 int vt_dino_forward(vt_dino_t h, const void* const* imgs, int ncams, int is_u8, int nhwc, float pre_scale,
                     int norm_mode, int B, int res, const float* pos_patch, float* out, float* flags_out,
                     void* workspace, vt_stream_t stream);
+
+/* ---------------------------------------------------------------- T5 v1.1 text encoder (csrc/vt_t5.hip)
+ * Replaces HF T5EncoderModel (feed_forward_proj "gated-gelu") of models/multimodal_encoder/t5_encoder.py::T5Embedder, used by
+ * scripts/encode_lang*.py and franka_model_eef.py (encode_instruction): instruction tokens -> last_hidden_state = RDT's lang_tokens.
+ * d_kv must be 64; cdt = adt = 0 (fp32) or 1 (bf16 weights and GEMM operands; fp32 residual stream and accumulation).  There is no fp16 mode.
+ * Weights (vt_t5_num_weights of them): shared [vocab][d_model] cdt, relative_attention_bias of layer 0 [num_buckets][heads] fp32, per layer
+ * {layer_norm [d_model] fp32, q|k|v [3 heads*64][d_model] cdt, o [d_model][heads*64] cdt, layer_norm [d_model] fp32, wi_0|wi_1 [2 d_ff][d_model] cdt,
+ * wo [d_model][d_ff] cdt}, final_layer_norm [d_model] fp32. */
+typedef struct {
+  int vocab, d_model, heads, d_kv, d_ff, layers;
+  int num_buckets, max_distance;     /* relative_attention_num_buckets / relative_attention_max_distance (used by the host's bucket table) */
+  float eps;                         /* layer_norm_epsilon */
+  int cdt, adt;
+} vt_t5_desc;
+int vt_t5_create(const vt_t5_desc* desc, const void* const* weights, int n_weights, vt_t5_t* out);
+void vt_t5_destroy(vt_t5_t h);
+int vt_t5_num_weights(const vt_t5_desc* desc);
+size_t vt_t5_workspace_bytes(vt_t5_t h, int B, int L);
+/* ids: HOST int32 [B][L] token ids; mask_or_null: HOST uint8 [B][L] attention_mask (1 = token, 0 = padding; null = all tokens) — both are
+ * validated on the host (an id outside [0, vocab) or a row with no valid token is -22) and copied into the workspace on `stream`.
+ * L <= 1024.  bucket_tab: device int8 [2047], the relative-position bucket of rel = -1023 .. 1023 at index rel + 1023 (HF
+ * T5Attention._relative_position_bucket, bidirectional, computed on the host in fp32).  out: [B][L][d_model] of out_dt (0 fp32, 1 bf16). */
+int vt_t5_forward(vt_t5_t h, const int32_t* ids, const uint8_t* mask_or_null, int B, int L, const int8_t* bucket_tab, void* out, int out_dt,
+                  void* workspace, vt_stream_t stream);
 
 /* ---------------------------------------------------------------- small MLP chain (state encoder / force encoder / heads)
  * y = L_n(...act(L_1(x))): replaces the nn.Sequential MLPs of bridge_controller.py:42-48 and

@@ -674,6 +674,12 @@ inline dim3 g1(long n, int bs = 256) { return dim3((unsigned)((n + bs - 1) / bs)
 
 int vt_k_rownorm(const void* x, int xdt, long ldx, void* y, int ydt, long ldy, const float* w, const float* b, int rows, int D,
                  float eps, int mode, hipStream_t s, unsigned* range_flag) {
+  if (xdt == VT_F32 && D > 2048 && D <= 4096 && D % 4 == 0 && rows > 0 && (ldx % 4) == 0 && (ldy % 4) == 0) {   // T5-XXL width: block per row, 4 float4 per thread
+    if (ydt == VT_F32) hipLaunchKernelGGL((rownorm_block_kernel<float, 4>), dim3(rows), dim3(256), 0, s, (const float*)x, ldx, (float*)y, ldy, w, b, D, eps, mode, range_flag);
+    else if (ydt == VT_F16) hipLaunchKernelGGL((rownorm_block_kernel<half_t, 4>), dim3(rows), dim3(256), 0, s, (const float*)x, ldx, (half_t*)y, ldy, w, b, D, eps, mode, range_flag);
+    else hipLaunchKernelGGL((rownorm_block_kernel<bf16_t, 4>), dim3(rows), dim3(256), 0, s, (const float*)x, ldx, (bf16_t*)y, ldy, w, b, D, eps, mode, range_flag);
+    return vt_check_launch();
+  }
   if (D % 4 || D > 64 * 4 * 8 || rows <= 0) return VT_ERR_ARG;
   static const int wave_rows = [] { const char* e = getenv("VLATOUCH_ROWNORM_WAVE"); return e ? atoi(e) : 8192; }();   // rows from which the wave-per-row kernel takes over (0 = never)
   if (xdt == VT_F32 && D >= 512 && wave_rows > 0 && rows >= wave_rows && (ldx % 4) == 0 && (ldy % 4) == 0) {

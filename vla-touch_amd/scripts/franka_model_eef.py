@@ -8,7 +8,9 @@ policy are the HIP-backed mirrors.  Differences, all forced by what is absent he
   * no torchvision: `transforms.Resize` / `ColorJitter(brightness=1.75)` are done with PIL (same resampling / the same
     ImageEnhance.Brightness torchvision itself uses for PIL images); the SiglipImageProcessor arithmetic (bicubic resize to
     image_size, x/255, (x-0.5)/0.5) is restated in `SiglipPreprocessor` and pinned against HF's PIL processor in tests;
-  * the T5 text encoder is not loaded (the reference comments it out as well): `encode_instruction` raises."""
+  * the T5 text encoder is optional, as in the reference (which comments it out "due to limited GPU memory"): with `text_model=` /
+    `text_tokenizer=` or `pretrained_text_encoder_name_or_path=` it runs on the card (vlatouch.t5) and `encode_instruction` works;
+    without one, `encode_instruction` raises NotImplementedError."""
 from __future__ import annotations
 
 import os
@@ -51,7 +53,8 @@ def create_model(args, **kwargs):
 class RoboticDiffusionTransformerModel(object):
     def __init__(self, args, device="cuda", dtype=torch.bfloat16, image_size=None, control_frequency=25, pretrained=None,
                  pretrained_vision_encoder_name_or_path=None, *, vision_model=None, policy=None,
-                 state_indices: Optional[Sequence[int]] = None):
+                 state_indices: Optional[Sequence[int]] = None, text_model=None, text_tokenizer=None,
+                 pretrained_text_encoder_name_or_path=None):
         self.args = args
         self.dtype = dtype
         self.image_size = image_size
@@ -63,6 +66,11 @@ class RoboticDiffusionTransformerModel(object):
         else:
             self.vision_model = SiglipVisionTower(vision_tower=pretrained_vision_encoder_name_or_path, args=None, device=device,
                                                   precision="bf16" if dtype == torch.bfloat16 else "fp32")
+        self.text_tokenizer, self.text_model = text_tokenizer, text_model
+        if text_model is None and pretrained_text_encoder_name_or_path is not None:
+            self.text_tokenizer, self.text_model = self.get_text_encoder(pretrained_text_encoder_name_or_path)
+            if text_tokenizer is not None:
+                self.text_tokenizer = text_tokenizer
         self.image_processor = SiglipPreprocessor(self.vision_model.config.image_size)
         self.policy = policy if policy is not None else self.get_policy(pretrained)
         self.reset()
@@ -98,8 +106,23 @@ class RoboticDiffusionTransformerModel(object):
         else:
             raise NotImplementedError(f"Unknown checkpoint format: {pretrained}")
 
+    def get_text_encoder(self, pretrained_text_encoder_name_or_path):
+        """franka_model_eef.py:115-121: (tokenizer, model) of a T5Embedder; the encoder runs on the card (vlatouch.t5)."""
+        from models.multimodal_encoder.t5_encoder import T5Embedder
+        embedder = T5Embedder(from_pretrained=pretrained_text_encoder_name_or_path, model_max_length=self.args["dataset"]["tokenizer_max_length"],
+                              device=self.device, torch_dtype=self.dtype)
+        return embedder.tokenizer, embedder.model
+
     def encode_instruction(self, instruction, device="cuda"):
-        raise NotImplementedError("the T5-XXL text encoder is not part of this build: pass cached instruction embeddings to step()")
+        """franka_model_eef.py:145-165: instruction string -> [1, L, d_model] T5 embeddings."""
+        if self.text_model is None or self.text_tokenizer is None:
+            raise NotImplementedError("no T5 text encoder was given (text_model= / text_tokenizer= or pretrained_text_encoder_name_or_path=): "
+                                      "pass cached instruction embeddings to step()")
+        tokens = self.text_tokenizer(instruction, return_tensors="pt", padding="longest", truncation=True)["input_ids"].to(device)
+        tokens = tokens.view(1, -1)
+        with torch.no_grad():
+            pred = self.text_model(tokens).last_hidden_state.detach()
+        return pred
 
     def _format_joint_to_state(self, joints):
         """[B, N, 10] EEF proprioception (gripper 0..255) -> unified state [B, N, state_token_dim] and its element mask [B, dim]."""

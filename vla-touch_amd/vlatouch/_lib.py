@@ -39,7 +39,7 @@ def range_names(bits: int):
 
 
 F32, BF16, F32X3, F16 = 0, 1, 2, 3   # F32X3: fp32 storage, split-bf16 3-MFMA compute (GEMM weights only); F16: IEEE half
-ACT_NONE, ACT_GELU_ERF, ACT_GELU_TANH, ACT_SILU, ACT_MISH, ACT_SWIGLU = 0, 1, 2, 3, 4, 5
+ACT_NONE, ACT_GELU_ERF, ACT_GELU_TANH, ACT_SILU, ACT_MISH, ACT_SWIGLU, ACT_GEGLU = 0, 1, 2, 3, 4, 5, 6
 NORM_LAYER, NORM_RMS_MEANSQ, NORM_RMS_VAR = 0, 1, 2
 IMGNORM_AUTO, IMGNORM_ON, IMGNORM_OFF = 0, 1, 2
 
@@ -112,6 +112,11 @@ class DinoDesc(C.Structure):
                 ("attn_scale", C.c_float)]
 
 
+class T5Desc(C.Structure):
+    _fields_ = [("vocab", C.c_int), ("d_model", C.c_int), ("heads", C.c_int), ("d_kv", C.c_int), ("d_ff", C.c_int), ("layers", C.c_int),
+                ("num_buckets", C.c_int), ("max_distance", C.c_int), ("eps", C.c_float), ("cdt", C.c_int), ("adt", C.c_int)]
+
+
 class LstmDesc(C.Structure):
     _fields_ = [("state_dim", C.c_int), ("hidden", C.c_int), ("layers", C.c_int), ("force_dim", C.c_int),
                 ("force_pad", C.c_int), ("in_pad", C.c_int), ("cdt", C.c_int)]
@@ -177,6 +182,11 @@ SIGNATURES = {
     "vt_dino_set_packed": (_I, [_P, _P, _P]),
     "vt_dino_set_range_flag": (_I, [_P, _P]),
     "vt_dino_forward": (_I, [_P, _P, _I, _I, _I, _F, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "vt_t5_create": (_I, [_P, _P, _I, _P]),
+    "vt_t5_destroy": (None, [_P]),
+    "vt_t5_num_weights": (_I, [_P]),
+    "vt_t5_workspace_bytes": (_Z, [_P, _I, _I]),
+    "vt_t5_forward": (_I, [_P, _P, _P, _I, _I, _P, _P, _I, _P, _P]),
     "vt_mlp": (_I, [_P, _L, _I, _I, _P, _P, _P, _I, _P, _I, _L, _I, _I, _P, _P]),
     "vt_concat_obs": (_I, [_P, _P, _I, _P, _I, _P, _I, _P, _I, _L, _I, _P]),
     "vt_lstm_create": (_I, [_P, _P, _I, _P]),

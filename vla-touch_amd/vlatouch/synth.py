@@ -408,3 +408,41 @@ def synth_gel_frame(rng, shift=(0.0, 0.0), bulge: float = 0.0, H: int = 240, W: 
             k += 1
     img += rng.normal(0, 3.0, img.shape)
     return np.clip(np.rint(img), 0, 255).astype(np.uint8)
+
+
+# ------------------------------------------------------------------ T5 v1.1 text encoder (vlatouch/t5.py)
+T5_CONFIGS = {
+    # HF T5Config fields of the encoder; every variant is v1.1 (gated-gelu, d_kv 64, 32 buckets up to distance 128, eps 1e-6)
+    "tiny": dict(vocab_size=384, d_model=128, num_heads=4, d_kv=64, d_ff=256, num_layers=2),
+    "small_like": dict(vocab_size=512, d_model=512, num_heads=6, d_kv=64, d_ff=1024, num_layers=2),     # inner 384 != d_model 512, as t5-v1_1-small
+    "xxl": dict(vocab_size=32128, d_model=4096, num_heads=64, d_kv=64, d_ff=10240, num_layers=24),       # google/t5-v1_1-xxl: shapes only
+}
+
+
+def t5_config(name: str, **over) -> Dict:
+    c = dict(T5_CONFIGS[name], relative_attention_num_buckets=32, relative_attention_max_distance=128, layer_norm_epsilon=1e-6,
+             feed_forward_proj="gated-gelu", is_gated_act=True, dense_act_fn="gelu_new")
+    c.update(over)
+    return c
+
+
+def t5_shapes(vocab_size: int, d_model: int, num_heads: int, d_ff: int, num_layers: int, d_kv: int = 64, num_buckets: int = 32,
+              **_) -> Dict[str, Tuple[int, ...]]:
+    """HF T5EncoderModel key map (gated-gelu).  The relative-attention bias exists in block 0 only."""
+    D, I = d_model, num_heads * d_kv
+    d: Dict[str, Tuple[int, ...]] = {"shared.weight": (vocab_size, D)}
+    for i in range(num_layers):
+        a = f"encoder.block.{i}.layer.0."
+        for n in ("q", "k", "v"):
+            d[a + f"SelfAttention.{n}.weight"] = (I, D)
+        d[a + "SelfAttention.o.weight"] = (D, I)
+        if i == 0:
+            d[a + "SelfAttention.relative_attention_bias.weight"] = (num_buckets, num_heads)
+        d[a + "layer_norm.weight"] = (D,)
+        f = f"encoder.block.{i}.layer.1."
+        d[f + "DenseReluDense.wi_0.weight"] = (d_ff, D)
+        d[f + "DenseReluDense.wi_1.weight"] = (d_ff, D)
+        d[f + "DenseReluDense.wo.weight"] = (D, d_ff)
+        d[f + "layer_norm.weight"] = (D,)
+    d["encoder.final_layer_norm.weight"] = (D,)
+    return d
