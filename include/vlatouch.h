@@ -35,9 +35,10 @@ int vt_version(void);
 /* MFMA fragment-layout self test (A = I with asymmetric B, both dtypes); out_err[2] device floats. */
 int vt_selftest_mfma(float* out_err, vt_stream_t stream);
 
-/* Live timing of the LDS-DMA MFMA GEMM kernels: while enabled, every launch of the selected kernel is bracketed by HIP
- * events on its launch stream.  on = 0 off, 1 both kernels, 2 only gemm_pp256_kernel (256-square ping-pong tile),
- * 3 only gemm_glds_kernel (128-column tiles).  vt_prof_collect (after the caller synchronised the stream) returns the
+/* Live timing of the LDS-DMA MFMA GEMM kernels: while enabled, every launch of the selected kernel class is bracketed by HIP
+ * events on its launch stream.  on = 0 off, 1 every GEMM class, 2 only the 256-square ping-pong tiles (gemm_pp256d_kernel,
+ * gemm_pt_kernel), 3 only the 128- / 160-column tiles (gemm_glds_kernel, gemm_ppk_kernel, gemm_pw_kernel, gemm_pws_kernel),
+ * 4 only the cached cross-attention, 5 only the register-staged GEMMs, 6 only the fused U-Net convolution.  vt_prof_collect (after the caller synchronised the stream) returns the
  * summed duration, the algorithmic FLOPs / bytes of those launches and their count. */
 int vt_prof_enable(int on);
 int vt_prof_collect(double* total_ms, double* flops, double* bytes, long* launches);
@@ -51,15 +52,14 @@ int vt_gemm(const void* params, vt_stream_t stream);
  * K % 16 == 0; same byte count): VtGemmParams.Wp of the weights-in-registers GEMM tile (csrc/vt_gemm_pw.hip).  Replaces nothing in
  * the reference (torch.nn.Linear keeps one layout, models/rdt/blocks.py:144-183); it is the load-time packing of this engine. */
 int vt_pack_w32(const void* W, long ldw, void* out, int N, int K, vt_stream_t stream);
-/* A/B tuning knobs of the GEMM dispatcher (tools/, tests): knob 1 = ring depth of the weights-in-registers tile (0 default, 4, 8);
- * knob 2 = that tile on (1) / off (0); knob 3 = the small-M tile (csrc/vt_gemm_pws.hip) on / off; knob 4 = its k-split factor (0 = choose);
- * knob 5 = timing-only ablation of the weights-in-registers tile (results are garbage: exists only in a build with -DVLATOUCH_BENCH_BUILD,
- *          tools/gemm_bench_pw.py --abl; the shipped library rejects any value but 0);
+/* Kernel selection knobs of the dispatcher (tests, tools/): knob 1 = ring depth of the weights-in-registers tile (0 default, 4, 8);
+ * knob 2 = that tile on (1) / off (0); knob 4 = k-split factor of the small-M tile (csrc/vt_gemm_pws.hip; 0 = none, -1 = choose);
  * knob 6 = fixed-maximum softmax of the cached cross-attention on (1) / off (0: always the online form);
  * knob 7 = fused U-Net sampler path (vt_unet_fused_pack) on (1) / off (0: the launch-per-op driver);
  * knob 8 = persistent 256-square GEMM tile with the in-loop epilogue (csrc/vt_gemm_pt.hip) on (1) / off (0: gemm_pp256d_kernel);
  * knob 9 = grouped-query ViT self-attention (csrc/vt_attn.hip, attn16g_kernel: a block walks the keys once for G x 16 query rows per wave):
- *          0 off (attn16u_kernel), 1 = 64-wide heads with at most 384 query rows (DINOv2 @224; default), 3 / 6 = every 16-bit unmasked call, G pinned. */
+ *          0 off (attn16u_kernel), 1 = 64-wide heads with at most 384 query rows (DINOv2 @224; default), 3 / 6 = every 16-bit unmasked call, G pinned.
+ * Any other knob (or value) returns VT_ERR_ARG. */
 int vt_tune(int knob, int value);
 
 /* Flash attention, head_dim 64 (or 96: params.hd): params = struct VtAttnParams (csrc/vt_kernels.h), host pointer.

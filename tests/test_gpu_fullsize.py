@@ -214,8 +214,8 @@ def _oracle_episode_uncached(r, d, b, steps):
 
 
 def test_rdt_1b_batch32_rows_vs_oracle(rdt1b):
-    """BASELINE configs[3]'s RDT leg exactly as bench.py times it: B=32 (M = 2144 rows / 139 968 condition rows -> gemm_ppk_kernel,
-    gemm_pp256_kernel<..,1|2> and the un-split attn_kvt_kernel), 5 DPM-Solver++ steps; rows 0 and 31 against the oracle run on those
+    """BASELINE configs[3]'s RDT leg exactly as bench.py times it: B=32 (M = 2144 rows / 139 968 condition rows -> gemm_pw_kernel,
+    gemm_pt_kernel (fused K|V projection) and attn_kvt_ring_kernel), 5 DPM-Solver++ steps; rows 0 and 31 against the oracle run on those
     single episodes.  Bar: the north star's FLAT 1e-2 on the chunk (round 6; the product default = fp16 activations under the range guard; models/rdt_runner.py:122-165,225-250)."""
     d = rdt_inputs(32, seed=17)
     rdt1b.num_inference_timesteps = 5

@@ -1,5 +1,4 @@
-"""ViT self-attention (attn16_kernel) at the SigLIP-so400m and DINOv2-B shapes of the bench: time per layer and MFMA rate; with a bench build, the
-timing-only ablations of tools/attn_abl.sh (VLATOUCH_ATTN_ABL)."""
+"""ViT self-attention (attn16u_kernel / attn16g_kernel) at the SigLIP-so400m and DINOv2-B shapes of the bench: time per layer and MFMA rate."""
 import os
 import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

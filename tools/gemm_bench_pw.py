@@ -102,7 +102,6 @@ def check_small(M, N, odt, act, res, hn):
         ref = torch.nn.functional.gelu(ref, approximate="tanh")
     if res:
         ref = ref + r.float()
-    lib.vt_tune(3, 1)
     errs = {}
     outs = {}
     for S in (1, 2, 4, 8):
@@ -119,12 +118,9 @@ def check_small(M, N, odt, act, res, hn):
     for S in (2, 8):
         sl = ops.gemm(a, w, None, wp=wp, splitk=S)
         slab_err[S] = float((sl.sum(0) - pre).abs().max())
-    lib.vt_tune(3, 0)
-    sl_old = ops.gemm(a, w, None, wp=wp, splitk=8)
-    lib.vt_tune(3, 1)
     print(f"  small M={M} N={N} out={str(odt)[6:]} act={act} res={int(res)} hn={int(hn)}: " + " ".join(f"S{S} {e:.2e}{'' if same else ' NONDET'}" for S, (e, same) in errs.items()) +
           f" | no-scratch==S1 {bool(torch.equal(noscratch, outs[1]))} | slabs " + " ".join(f"S{S} {e:.2e}" for S, e in slab_err.items()) +
-          f" (generic S8 {float((sl_old.sum(0) - pre).abs().max()):.2e}) | counters zero {int(cnt.abs().sum()) == 0}", flush=True)
+          f" | counters zero {int(cnt.abs().sum()) == 0}", flush=True)
 
 
 def bench_small(M, N, odt):
@@ -135,7 +131,6 @@ def bench_small(M, N, odt):
     out = torch.empty(M, N, device=dev, dtype=odt)
     ws = torch.empty(8 * M * N, dtype=torch.float32, device=dev)
     cnt = torch.zeros(4096, dtype=torch.int32, device=dev)
-    lib.vt_tune(3, 1)
     for S in (0, 1, 2, 4, 8):
         lib.vt_tune(4, S)
         cold = graph_time(lambda i: ops.gemm(a, wts[i % nw], out=out, out_dtype=odt, wp=wps[i % nw], sk_ws=ws, sk_cnt=cnt), nw)
@@ -143,11 +138,8 @@ def bench_small(M, N, odt):
     lib.vt_tune(4, 0)
     slab = torch.empty(8, M, N, device=dev, dtype=torch.float32)
     for S in (2, 4, 8):
-        for on in (1, 0):
-            lib.vt_tune(3, on)
-            cold = graph_time(lambda i: ops.gemm(a, wts[i % nw], out=slab[:S], wp=wps[i % nw], splitk=S), nw)
-            print(f"  small M={M} N={N} slab mode S={S} {'pws    ' if on else 'generic'}: cold {cold:6.2f} us  ({N * K * 2 / cold / 1e6:5.2f} TB/s of weights)", flush=True)
-    lib.vt_tune(3, 1)
+        cold = graph_time(lambda i: ops.gemm(a, wts[i % nw], out=slab[:S], wp=wps[i % nw], splitk=S), nw)
+        print(f"  small M={M} N={N} slab mode S={S}: cold {cold:6.2f} us  ({N * K * 2 / cold / 1e6:5.2f} TB/s of weights)", flush=True)
 
 
 if __name__ == "__main__":
@@ -161,18 +153,6 @@ if __name__ == "__main__":
     bench_small(67, 6144, torch.bfloat16)
     bench_small(134, 2048, torch.bfloat16)
     bench_small(268, 2048, torch.bfloat16)
-    if "--abl" in sys.argv:      # timing-only ablations of gemm_pw_kernel<bf16, bf16, 4> (what bounds the k-loop?)
-        M, N = 2144, 2048
-        a = torch.randn(M, K, device=dev).to(torch.bfloat16)
-        ws_ = [(torch.randn(N, K, device=dev) * K ** -0.5).to(torch.bfloat16) for _ in range(NW)]
-        wps = [ops.pack_w32(w) for w in ws_]
-        out = torch.empty(M, N, device=dev, dtype=torch.bfloat16)
-        lib.vt_tune(2, 1); lib.vt_tune(1, 4)
-        for k, name in ((0, "full kernel"), (1, "no fragment reads"), (2, "no weight loads"), (3, "no MFMAs"), (4, "no activation DMA"), (5, "no epilogue")):
-            lib.vt_tune(5, k)
-            t = graph_time(lambda i: ops.gemm(a, ws_[i % NW], out=out, out_dtype=torch.bfloat16, wp=wps[i % NW]), NW)
-            print(f"  ablation {k} ({name:18s}): {t:6.2f} us", flush=True)
-        lib.vt_tune(5, 0)
     if "--big" not in sys.argv:
         sys.exit(0)
     print("correctness (bf16 operands, fp32 torch product as yardstick)")

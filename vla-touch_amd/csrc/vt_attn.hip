@@ -7,7 +7,6 @@
 // The k-index -> key assignment inside a 32-key block is (j>>2)*16 + g*4 + (j&3), which makes the P fragment
 // exactly the lane's own S registers (no cross-lane movement); Vt is read with the same assignment.
 // Online softmax state (m, l) lives per q row, replicated over the 4 lanes sharing lane&15.
-#include <stdlib.h>
 #include "vt_common.h"
 #include "vt_kernels.h"
 
@@ -215,15 +214,6 @@ __global__ __launch_bounds__(512) void attn_kernel(const VtAttnParams p) {
   }
 }
 
-// ---- 16-bit self-attention with DMA-staged, double-buffered K / V tiles (DINOv2 257 tokens, SigLIP 729 tokens x 72-wide heads padded to 96, RDT
-// self-attention).  Same arithmetic and fragment conventions as attn_kernel above; what changes is how the tiles reach the MFMAs:
-//   * K and V tiles (64 keys) go HBM/L2 -> LDS by DMA (16 B per lane, 8 rows x 128 B per wave instruction, XOR swizzle on the SOURCE address),
-//     BOTH row-major [key][d] — attn_kernel transposed V through registers with eight 2-byte LDS stores per 16-byte chunk, which alone cost
-//     more LDS instructions than everything else in the tile;
-//   * the Vt fragment (4 consecutive keys of one d column) is read from the row-major V tile with ds_read_b64_tr_b16: the 16 lanes of a lane
-//     group address a [4 keys][16 d] block (lane i: key i/4, d columns (i%4)*4 .. +3) and the hardware hands lane i the 4 keys of column i;
-//   * a ring of three LDS stages: two tiles are in flight behind the one being consumed, waits are counted (vmcnt), ONE raw barrier per tile.
-// No key mask here (masked calls keep attn_kernel).  Keys past Nk in the last tile are clamped loads, masked in the softmax.
 typedef __attribute__((address_space(3))) void lds_void_a;
 typedef const __attribute__((address_space(1))) void glb_void_a;
 typedef __attribute__((ext_vector_type(4))) short short4_t;
@@ -239,226 +229,24 @@ template <> __device__ __forceinline__ void mma16_k16<half_t>(float4_t& acc, con
   acc = __builtin_amdgcn_mfma_f32_16x16x16f16(__builtin_bit_cast(half4v_t, a), __builtin_bit_cast(half4v_t, b), acc, 0, 0, 0);
 }
 
-#ifdef VLATOUCH_BENCH_BUILD      // timing-only ablations of attn16_kernel (tools/attn_abl.sh; garbage results): 1 = no softmax arithmetic, 2 = no P V, 4 = no Q K^T, 8 = no K / V staging after the first tiles
-__device__ int d_attn_abl = 0;
-__device__ long long* d_attn_tbuf = nullptr;   // optional phase time stamps of attn16u_kernel (tools/attn_phases.py): 4 x s_memrealtime per block
-#define VT_ATTN_ABL(bit) (d_attn_abl & (bit))
-#else
-#define VT_ATTN_ABL(bit) 0
-#endif
-
-template <typename T, int HD>
-__global__ __launch_bounds__(512) void attn16_kernel(const VtAttnParams p) {
-  static_assert(sizeof(T) == 2, "16-bit types only");
-  constexpr int KT = 64;
-  constexpr int NKS = HD / 32, NDT = HD / 16;
-  constexpr bool TAIL16 = (HD % 32) == 16;            // one 16-deep step behind the NKS 32-deep ones
-  static_assert(HD >= 64 && HD <= 128 && HD % 16 == 0 && (HD % 32 == 0 || HD % 32 == 16), "head dimension: 64 .. 128, multiple of 16");
-  // LDS image of a K (or V) tile: MAIN = [64 keys][128 B] for d 0..63 (16-byte chunks XOR-swizzled by the row) followed by a compact TAIL =
-  // [64 keys][TW bytes] for d 64.. (linear: its reads are contiguous as they are) — 8 / 10 / 12 KiB for 64 / 80 / 96-wide heads, so THREE stages
-  // (K + V each) still leave two blocks per CU
-  constexpr int TW = (HD - 64) * 2;                   // tail bytes per key row: 0, 32, 64
-  constexpr int MAINB = KT * 128;
-  constexpr int TILE = MAINB + KT * TW;
-  constexpr int STAGE = 2 * TILE;                     // K then V
-  constexpr int NST = 3;
-  constexpr int TP = KT * TW / 1024;                  // tail DMA pieces per tile (a piece = 1 KiB = 1024 / TW rows)
-  constexpr int PT = 8 + TP;                          // pieces per tile
-  constexpr int PIECES = 2 * PT;                      // per stage
-  __shared__ __attribute__((aligned(16))) char smem[NST * STAGE];
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int nw = blockDim.x >> 6;
-  const int g = lane >> 4, l15 = lane & 15;
-  const int b = blockIdx.z, h = blockIdx.y;
-  const int q = blockIdx.x * (nw * 16) + wave * 16 + l15;
-  const T* Q = reinterpret_cast<const T*>(p.Q) + (long)b * p.q_bs + (long)h * p.q_hs;
-  const T* K = reinterpret_cast<const T*>(p.K) + (long)b * p.k_bs + (long)h * p.k_hs;
-  const T* V = reinterpret_cast<const T*>(p.V) + (long)b * p.v_bs + (long)h * p.v_hs;
-
-  Frag<T> qf[NKS];
-#pragma unroll
-  for (int ks = 0; ks < NKS; ++ks) QLoad<T>::ld(qf[ks], Q + (long)q * p.q_rs + ks * 32 + g * 8, q < p.Nq);
-  short4_t q16 = {0, 0, 0, 0};
-  if constexpr (TAIL16) { if (q < p.Nq) q16 = *reinterpret_cast<const short4_t*>(Q + (long)q * p.q_rs + NKS * 32 + g * 4); }
-  // retire the Q loads before the first DMA (an ordinary load pending beside LDS-DMA makes hipcc drain the whole queue at its first use)
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-  for (int ks = 0; ks < NKS; ++ks) asm volatile("" : "+v"(qf[ks].v));
-  asm volatile("" : "+v"(q16));
-
-  // DMA plan: the PIECES 1-KiB pieces of a stage are dealt round-robin over the waves (the counted wait uses the per-wave count).  Main
-  // pieces: 8 rows x 128 B, lane -> (row, chunk position), it fetches the chunk whose swizzled position is its own; tail pieces: 1024 / TW
-  // rows x TW bytes, linear.
-  const int my_pieces = (PIECES - wave + nw - 1) / nw;                 // pieces i = wave, wave + nw, ...
-  auto stage = [&](const int slot, const int tile) {
-    const int key0 = tile * KT;
-    for (int i = wave; i < PIECES; i += nw) {
-      const bool isv = i >= PT;
-      const int j = isv ? i - PT : i;
-      const T* base = isv ? V : K;
-      const long rs = isv ? p.v_rs : p.k_rs;
-      char* dst = smem + slot * STAGE + (isv ? TILE : 0);
-      if (TP == 0 || j < 8) {
-        const int r = j * 8 + (lane >> 3);
-        const int c = (lane & 7) ^ ((r >> 1) & 7);
-        __builtin_amdgcn_global_load_lds((glb_void_a*)(base + (long)min(key0 + r, p.Nk - 1) * rs + c * 8), (lds_void_a*)(dst + j * 1024), 16, 0, 0);
-      } else if constexpr (TP > 0) {
-        constexpr int CPR = TW / 16;                  // 16-byte chunks per tail row: 2 or 4
-        const int r = (j - 8) * (64 / CPR) + lane / CPR;
-        const int c = lane % CPR;
-        __builtin_amdgcn_global_load_lds((glb_void_a*)(base + (long)min(key0 + r, p.Nk - 1) * rs + 64 + c * 8), (lds_void_a*)(dst + MAINB + (j - 8) * 1024), 16, 0, 0);
-      }
-    }
-  };
-  auto wait_own = [&](const bool younger_in_flight) {   // this wave's pieces of the oldest outstanding stage have landed
-    if (!younger_in_flight) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if (my_pieces == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-    else if (my_pieces == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    else if (my_pieces == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-    else if (my_pieces == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else if (my_pieces == 5) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-    else if (my_pieces == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  };
-
-  float4_t o[NDT];
-#pragma unroll
-  for (int i = 0; i < NDT; ++i) o[i] = (float4_t){0.f, 0.f, 0.f, 0.f};
-  float m_run = -INFINITY, l_run = 0.f;
-  const float cscale = p.scale * 1.4426950408889634f;
-  const int ntiles = (p.Nk + KT - 1) / KT;
-
-  // ring of NST = 3 stages, two tiles in flight behind the one being consumed; ONE barrier per tile: it publishes tile t (every wave waited
-  // for its own pieces) and proves that everybody is done with tile t-1, whose slot the DMA of tile t+2 then takes
-  stage(0, 0);
-  if (ntiles > 1) stage(1, 1);
-  int slot = 0;
-  for (int tile = 0; tile < ntiles; ++tile) {
-    const int key0 = tile * KT;
-    wait_own(tile + 1 < ntiles);
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    if (tile + 2 < ntiles && !VT_ATTN_ABL(8)) stage(slot == 0 ? 2 : slot - 1, tile + 2);
-    const char* Ks = smem + slot * STAGE;
-    const char* Vs = Ks + TILE;
-    slot = slot == NST - 1 ? 0 : slot + 1;
-
-    float4_t sacc[4], tacc[4];
-#pragma unroll
-    for (int kt = 0; kt < 4; ++kt) {
-      sacc[kt] = (float4_t){0.f, 0.f, 0.f, 0.f};
-      tacc[kt] = (float4_t){0.f, 0.f, 0.f, 0.f};
-      if (VT_ATTN_ABL(4)) continue;
-      const int row = kt * 16 + l15;
-#pragma unroll
-      for (int ks = 0; ks < NKS; ++ks) {
-        Frag<T> kf;
-        if (ks < 2) lds_frag(kf, Ks, row, ks * 4 + g);                                                  // d 0..63: the swizzled main image
-        else kf.v = *reinterpret_cast<const short8_t*>(Ks + MAINB + row * TW + (ks - 2) * 64 + g * 16);  // d 64..: the linear tail
-        mma16(sacc[kt], kf, qf[ks]);
-      }
-      if constexpr (TAIL16) {
-        // into its OWN accumulator, added on the VALU below: chained straight behind the 8-pass 16x16x32 MFMAs on the same accumulator, the
-        // 4-pass 16x16x16 read registers 0..1 of the last key tile before they were written (scores of keys 48 + 4g + {0, 1} lost their d < 64
-        // part; tools/_dbg pinpointed it) — hipcc 7.2 does not pad that SrcC hazard between the two instruction lengths
-        const short4_t k16 = *reinterpret_cast<const short4_t*>(Ks + MAINB + row * TW + (NKS - 2) * 64 + g * 8);
-        tacc[kt] = (float4_t){0.f, 0.f, 0.f, 0.f};
-        mma16_k16<T>(tacc[kt], k16, q16);
-      }
-    }
-    float sv[16];
-#pragma unroll
-    for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) sv[kt * 4 + r] = TAIL16 ? sacc[kt][r] + tacc[kt][r] : sacc[kt][r];
-    if (key0 + KT > p.Nk) {
-#pragma unroll
-      for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          if (key0 + kt * 16 + g * 4 + r >= p.Nk) sv[kt * 4 + r] = -INFINITY;
-    }
-    if (!VT_ATTN_ABL(1)) {
-    float mx = sv[0];
-#pragma unroll
-    for (int i = 1; i < 16; ++i) mx = fmaxf(mx, sv[i]);
-    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    const float m_new = fmaxf(m_run, mx);
-    if (__any(m_new != m_run)) {
-      const float alpha = (m_run == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f((m_run - m_new) * cscale);
-      l_run *= alpha;
-#pragma unroll
-      for (int dt = 0; dt < NDT; ++dt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) o[dt][r] *= alpha;
-      m_run = m_new;
-    }
-    const float mc = (m_run == -INFINITY) ? 0.f : m_run * cscale;
-    float psum = 0.f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) { sv[i] = __builtin_amdgcn_exp2f(fmaf(sv[i], cscale, -mc)); psum += sv[i]; }
-    l_run += psum;
-    } else { l_run = 1.f; }
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb) {
-      if (VT_ATTN_ABL(2)) break;
-      float pj[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) pj[j] = sv[(kb * 2 + (j >> 2)) * 4 + (j & 3)];
-      Frag<T> pf;
-      PackP<T>::pack(pf, pj);
-#pragma unroll
-      for (int dt = 0; dt < NDT; ++dt) {
-        // lane i of group g addresses key (kb*32 [+16] + g*4 + i/4), d columns dt*16 + (i%4)*4 .. +3 of the row-major V tile and receives
-        // the 4 keys kb*32 [+16] + g*4 .. +3 of column dt*16 + i
-        const int dcol = dt * 16 + (l15 & 3) * 4;
-        Frag<T> vf;
-#pragma unroll
-        for (int hh = 0; hh < 2; ++hh) {
-          const int key = kb * 32 + hh * 16 + g * 4 + (l15 >> 2);
-          const char* a = dt < 4 ? Vs + key * 128 + (((dcol >> 3) ^ ((key >> 1) & 7)) * 16) + (dcol & 7) * 2
-                                 : Vs + MAINB + key * TW + (dcol - 64) * 2;
-          const short4_t t = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4_t*)a);
-          vf.v[hh * 4 + 0] = t[0]; vf.v[hh * 4 + 1] = t[1]; vf.v[hh * 4 + 2] = t[2]; vf.v[hh * 4 + 3] = t[3];
-        }
-        mma16(o[dt], vf, pf);
-      }
-    }
-  }
-  float l = l_run;
-  l += __shfl_xor(l, 16, 64);
-  l += __shfl_xor(l, 32, 64);
-  const float inv = 1.0f / l;
-  if (q < p.Nq) {
-    T* O = reinterpret_cast<T*>(p.O) + (long)b * p.o_bs + (long)q * p.o_rs + h * HD;
-#pragma unroll
-    for (int dt = 0; dt < NDT; ++dt) {
-      T ov[4] = {Elem<T>::from_f(o[dt][0] * inv), Elem<T>::from_f(o[dt][1] * inv), Elem<T>::from_f(o[dt][2] * inv), Elem<T>::from_f(o[dt][3] * inv)};
-      *reinterpret_cast<uint2*>(O + dt * 16 + g * 4) = *reinterpret_cast<const uint2*>(ov);
-    }
-  }
-}
-
-
-// ---- attn16u_kernel: attn16_kernel with the tile loop unrolled over the three ring slots.  With the slot a compile-time constant every LDS
-// address of the tile is (per-lane offset computed ONCE before the loop) + (immediate): the 60 address instructions per tile of attn16_kernel
-// (a third of its VALU issue slots; the kernel is VALU-issue-bound in its arithmetic, tools/attn_abl.sh) disappear.  The DMA source addresses
-// are (uniform tile base, SALU) + (per-lane piece offset, computed once) except in the last, clamped tile, and the first two stages are issued
-// BEFORE the Q fragments are loaded so that a block pays one memory round trip before its first MFMA, not two.
+// ---- attn16u_kernel: 16-bit self-attention with DMA-staged K / V tiles (DINOv2 257 tokens, SigLIP 729 tokens x 72-wide heads padded to 80, RDT
+// self-attention).  Same arithmetic and fragment conventions as attn_kernel above; what changes is how the tiles reach the MFMAs:
+//   * K and V tiles (64 keys) go HBM/L2 -> LDS by DMA (16 B per lane, 8 rows x 128 B per wave instruction, XOR swizzle on the SOURCE address),
+//     BOTH row-major [key][d] — attn_kernel transposed V through registers with eight 2-byte LDS stores per 16-byte chunk, which alone cost
+//     more LDS instructions than everything else in the tile;
+//   * the Vt fragment (4 consecutive keys of one d column) is read from the row-major V tile with ds_read_b64_tr_b16: the 16 lanes of a lane
+//     group address a [4 keys][16 d] block (lane i: key i/4, d columns (i%4)*4 .. +3) and the hardware hands lane i the 4 keys of column i;
+//   * a ring of three LDS stages: two tiles are in flight behind the one being consumed, waits are counted (vmcnt), ONE raw barrier per tile;
+//   * the tile loop is unrolled over the three ring slots.  With the slot a compile-time constant every LDS address of the tile is (per-lane
+//     offset computed ONCE before the loop) + (immediate): the 60 address instructions per tile of the rolled loop (a third of its VALU issue
+//     slots; the kernel is VALU-issue-bound in its arithmetic) disappear.  The DMA source addresses are (uniform tile base, SALU) + (per-lane
+//     piece offset, computed once) except in the last, clamped tile, and the first two stages are issued BEFORE the Q fragments are loaded so
+//     that a block pays one memory round trip before its first MFMA, not two.
+// No key mask here (masked calls keep attn_kernel).  Keys past Nk in the last tile are clamped loads, masked in the softmax.
 
 // max / sum over the four 16-lane rows of a wave (lanes that differ in bits 4 and 5), result in every lane, on v_permlane16_swap / v_permlane32_swap
 // (VALU) instead of two __shfl_xor = ds_bpermute round trips (round 5: the same change took the cached cross-attention's online softmax from 114 to 104 us)
 template <bool MAX> __device__ __forceinline__ float rows4_reduce(float v) {
-#ifdef VLATOUCH_ATTN_SHFL
-  const float a = __shfl_xor(v, 16, 64);
-  v = MAX ? fmaxf(v, a) : v + a;
-  const float b = __shfl_xor(v, 32, 64);
-  return MAX ? fmaxf(v, b) : v + b;
-#else
   const unsigned u = __builtin_bit_cast(unsigned, v);
   const auto a = __builtin_amdgcn_permlane16_swap(u, u, false, false);
   const float a0 = __builtin_bit_cast(float, (unsigned)a[0]), a1 = __builtin_bit_cast(float, (unsigned)a[1]);
@@ -467,7 +255,6 @@ template <bool MAX> __device__ __forceinline__ float rows4_reduce(float v) {
   const auto b = __builtin_amdgcn_permlane32_swap(x, x, false, false);
   const float b0 = __builtin_bit_cast(float, (unsigned)b[0]), b1 = __builtin_bit_cast(float, (unsigned)b[1]);
   return MAX ? fmaxf(b0, b1) : b0 + b1;
-#endif
 }
 template <int I> struct IC { static constexpr int value = I; };
 
@@ -499,14 +286,10 @@ __global__ __launch_bounds__(512) void attn16u_kernel(const VtAttnParams p) {
   const T* K = reinterpret_cast<const T*>(p.K) + (long)b * p.k_bs + (long)h * p.k_hs;
   const T* V = reinterpret_cast<const T*>(p.V) + (long)b * p.v_bs + (long)h * p.v_hs;
   const int ntiles = (p.Nk + KT - 1) / KT;
-#ifdef VLATOUCH_BENCH_BUILD
-  const int lin_blk = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-  long long* tb = (d_attn_tbuf && lin_blk < 4096 && tid == 0) ? d_attn_tbuf + (long)lin_blk * 4 : nullptr;
-  if (tb) tb[0] = wall_clock64();
-#endif
 
-  // DMA plan (as attn16_kernel): the PIECES 1-KiB pieces of a stage are dealt round-robin over the waves.  poff[n] = this lane's element offset
-  // inside the K (or V) rows of a tile for the wave's n-th piece.
+  // DMA plan: the PIECES 1-KiB pieces of a stage are dealt round-robin over the waves (the counted wait uses the per-wave count).  Main
+  // pieces: 8 rows x 128 B, lane -> (row, chunk position), it fetches the chunk whose swizzled position is its own; tail pieces: 1024 / TW
+  // rows x TW bytes, linear.  poff[n] = this lane's element offset inside the K (or V) rows of a tile for the wave's n-th piece.
   const int my_pieces = (PIECES - wave + nw - 1) / nw;
   unsigned poff[MAXP];
 #pragma unroll
@@ -581,11 +364,9 @@ __global__ __launch_bounds__(512) void attn16u_kernel(const VtAttnParams p) {
 #pragma unroll
   for (int ks = 0; ks < NKS; ++ks) asm volatile("" : "+v"(qf[ks].v));
   asm volatile("" : "+v"(q16));
-#ifdef VLATOUCH_BENCH_BUILD
-  if (tb) tb[1] = wall_clock64();
-#endif
 
-  // per-lane LDS offsets inside a tile (see attn16_kernel for the fragment conventions)
+  // per-lane LDS offsets inside a tile (fragment conventions: the K fragment as lds_frag; lane i of group g addresses key (kb*32 [+16] + g*4 + i/4),
+  // d columns dt*16 + (i%4)*4 .. +3 of the row-major V tile and receives the 4 keys kb*32 [+16] + g*4 .. +3 of column dt*16 + i)
   //   K fragment (key row kt*16 + l15, 16-byte chunk ks*4 + g, swizzled by (row >> 1) & 7 = (l15 >> 1) & 7):  kt*2048 + koff[ks]
   //   V fragment (key kb*32 + hh*16 + vkey, d columns dt*16 + (l15 & 3)*4 ..):  (kb*32 + hh*16)*128 + voff[dt]   (dt < 4)
   const int ksw = (l15 >> 1) & 7;
@@ -619,7 +400,7 @@ __global__ __launch_bounds__(512) void attn16u_kernel(const VtAttnParams p) {
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
-    if (tile + 2 < ntiles && !VT_ATTN_ABL(8)) stage(NEXT, tile + 2);
+    if (tile + 2 < ntiles) stage(NEXT, tile + 2);
     const char* Ks = smem + SLOT * STAGE;
     const char* Vs = Ks + TILE;
 
@@ -628,7 +409,6 @@ __global__ __launch_bounds__(512) void attn16u_kernel(const VtAttnParams p) {
     for (int kt = 0; kt < 4; ++kt) {
       sacc[kt] = (float4_t){0.f, 0.f, 0.f, 0.f};
       tacc[kt] = (float4_t){0.f, 0.f, 0.f, 0.f};
-      if (VT_ATTN_ABL(4)) continue;
 #pragma unroll
       for (int ks = 0; ks < NKS; ++ks) {
         Frag<T> kf;
@@ -637,7 +417,9 @@ __global__ __launch_bounds__(512) void attn16u_kernel(const VtAttnParams p) {
         mma16(sacc[kt], kf, qf[ks]);
       }
       if constexpr (TAIL16) {
-        // own accumulator, added on the VALU below (the SrcC hazard between the 8-pass and 4-pass MFMAs, see attn16_kernel)
+        // into its OWN accumulator, added on the VALU below: chained straight behind the 8-pass 16x16x32 MFMAs on the same accumulator, the
+        // 4-pass 16x16x16 read registers 0..1 of the last key tile before they were written (scores of keys 48 + 4g + {0, 1} lost their d < 64
+        // part) — hipcc 7.2 does not pad that SrcC hazard between the two instruction lengths
         const short4_t k16 = *reinterpret_cast<const short4_t*>(Ks + kt * 16 * TW + ktail16);
         mma16_k16<T>(tacc[kt], k16, q16);
       }
@@ -654,30 +436,27 @@ __global__ __launch_bounds__(512) void attn16u_kernel(const VtAttnParams p) {
         for (int r = 0; r < 4; ++r)
           if (key0 + kt * 16 + g * 4 + r >= p.Nk) sv[kt * 4 + r] = -INFINITY;
     }
-    if (!VT_ATTN_ABL(1)) {
-      float mx = sv[0];
+    float mx = sv[0];
 #pragma unroll
-      for (int i = 1; i < 16; ++i) mx = fmaxf(mx, sv[i]);
-      mx = rows4_reduce<true>(mx);
-      const float m_new = fmaxf(m_run, mx);
-      if (__any(m_new != m_run)) {
-        const float alpha = (m_run == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f((m_run - m_new) * cscale);
-        l_run *= alpha;
+    for (int i = 1; i < 16; ++i) mx = fmaxf(mx, sv[i]);
+    mx = rows4_reduce<true>(mx);
+    const float m_new = fmaxf(m_run, mx);
+    if (__any(m_new != m_run)) {
+      const float alpha = (m_run == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f((m_run - m_new) * cscale);
+      l_run *= alpha;
 #pragma unroll
-        for (int dt = 0; dt < NDT; ++dt)
+      for (int dt = 0; dt < NDT; ++dt)
 #pragma unroll
-          for (int r = 0; r < 4; ++r) o[dt][r] *= alpha;
-        m_run = m_new;
-      }
-      const float mc = (m_run == -INFINITY) ? 0.f : m_run * cscale;
-      float psum = 0.f;
+        for (int r = 0; r < 4; ++r) o[dt][r] *= alpha;
+      m_run = m_new;
+    }
+    const float mc = (m_run == -INFINITY) ? 0.f : m_run * cscale;
+    float psum = 0.f;
 #pragma unroll
-      for (int i = 0; i < 16; ++i) { sv[i] = __builtin_amdgcn_exp2f(fmaf(sv[i], cscale, -mc)); psum += sv[i]; }
-      l_run += psum;
-    } else { l_run = 1.f; }
+    for (int i = 0; i < 16; ++i) { sv[i] = __builtin_amdgcn_exp2f(fmaf(sv[i], cscale, -mc)); psum += sv[i]; }
+    l_run += psum;
 #pragma unroll
     for (int kb = 0; kb < 2; ++kb) {
-      if (VT_ATTN_ABL(2)) break;
       float pj[8];
 #pragma unroll
       for (int j = 0; j < 8; ++j) pj[j] = sv[(kb * 2 + (j >> 2)) * 4 + (j & 3)];
@@ -706,9 +485,6 @@ __global__ __launch_bounds__(512) void attn16u_kernel(const VtAttnParams p) {
     body(IC<2>{}, tile + 2);
   }
 
-#ifdef VLATOUCH_BENCH_BUILD
-  if (tb) { asm volatile("" : "+v"(o[0])); tb[2] = wall_clock64(); }
-#endif
   float l = l_run;
   l = rows4_reduce<false>(l);
   const float inv = 1.0f / l;
@@ -720,14 +496,11 @@ __global__ __launch_bounds__(512) void attn16u_kernel(const VtAttnParams p) {
       *reinterpret_cast<uint2*>(O + dt * 16 + g * 4) = *reinterpret_cast<const uint2*>(ov);
     }
   }
-#ifdef VLATOUCH_BENCH_BUILD
-  if (tb) tb[3] = wall_clock64();
-#endif
 }
 
 
 // ---- attn16g_kernel (round 5): the ViT self-attention loop nest turned inside out.  attn16u_kernel gives a block 16 query rows per wave and walks the
-// whole key sequence for them: a SigLIP (image, head) is 6 blocks, each staging the same 233 KB of K / V (tools/attn_abl.sh: a third of the launch is
+// whole key sequence for them: a SigLIP (image, head) is 6 blocks, each staging the same 233 KB of K / V (timing ablations, round 5: a third of the launch is
 // re-staging, another third the per-block fixed cost — dispatch, Q loads, first DMA round trip, 12 barriers, O stores).  Here a wave owns G query
 // groups of 16 rows (G sets of Q fragments, running (m, l) and O accumulators in registers) and a block walks the key tiles ONCE for all of its
 // 16 * nw * G rows: one block per (image, head) for SigLIP (8 waves x 6 groups = 768 >= 729 rows) and DINOv2 @224 (6 x 3 = 288 >= 257).  Inside a
@@ -907,7 +680,7 @@ __global__ __launch_bounds__(512) void attn16g_kernel(const VtAttnParams p) {
           else kf.v = *reinterpret_cast<const short8_t*>(kt_ + kt * 16 * TW + (ks - 2) * 64);
           mma16(sacc[kt], kf, qf[gi][ks]);
         }
-        if constexpr (TAIL16) {      // own accumulator (the SrcC hazard between the 8-pass and 4-pass MFMAs, see attn16_kernel)
+        if constexpr (TAIL16) {      // own accumulator (the SrcC hazard between the 8-pass and 4-pass MFMAs, see attn16u_kernel)
           const short4_t k16 = *reinterpret_cast<const short4_t*>(kt16 + kt * 16 * TW);
           mma16_k16<T>(tacc[kt], k16, q16[gi]);
         }
@@ -985,20 +758,11 @@ __global__ __launch_bounds__(512) void attn16g_kernel(const VtAttnParams p) {
 
 }  // namespace
 
-#ifdef VLATOUCH_BENCH_BUILD
-extern "C" int vt_attn_set_timing(long long* buf) {      // bench build only: device buffer of 4096 x 4 stamps (null = off)
-  return hipMemcpyToSymbol(HIP_SYMBOL(d_attn_tbuf), &buf, sizeof(buf)) == hipSuccess ? VT_OK : VT_ERR_LAUNCH;
-}
-#endif
-
-static int g_vt_attn16g = -1;     // -1 = read VLATOUCH_ATTN16G at the first launch; 0 = attn16u_kernel everywhere, 1 = grouped-query kernel with G chosen per shape, 3 / 6 = pinned
+static int g_vt_attn16g = 1;      // 0 = attn16u_kernel everywhere, 1 = grouped-query kernel with G chosen per shape, 3 / 6 = pinned
 void vt_attn16g_tune(int value) { g_vt_attn16g = value; }
 
 int vt_attn_launch(const VtAttnParams& p, hipStream_t s) {
   if (p.B <= 0 || p.H <= 0 || p.Nq <= 0 || p.Nk <= 0) return VT_ERR_ARG;
-#ifdef VLATOUCH_BENCH_BUILD
-  { const char* e = getenv("VLATOUCH_ATTN_ABL"); const int v = e ? atoi(e) : 0; (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(d_attn_abl), &v, sizeof(int), 0, hipMemcpyHostToDevice, s); }
-#endif
   if (p.dtype != VT_F32 && p.dtype != VT_BF16 && p.dtype != VT_F16) return VT_ERR_UNSUPPORTED;
   const int epc = p.dtype == VT_F32 ? 4 : 8;
   if (p.q_rs % epc || p.k_rs % epc || p.v_rs % epc || p.q_hs % epc || p.k_hs % epc || p.v_hs % epc) return VT_ERR_ARG;
@@ -1010,18 +774,14 @@ int vt_attn_launch(const VtAttnParams& p, hipStream_t s) {
   const int rows = nw * 16;
   dim3 grid((p.Nq + rows - 1) / rows, p.H, p.B);
   if (p.hd != 0 && p.hd != 64 && p.hd != 96 && p.hd != 80) return VT_ERR_UNSUPPORTED;
-  // 16-bit, unmasked, 16-byte-aligned rows: DMA-staged double-buffered tiles (VLATOUCH_ATTN16=0 keeps attn_kernel for A/B)
-  static const int a16 = [] { const char* e = getenv("VLATOUCH_ATTN16"); return e ? atoi(e) : 2; }();
   // Grouped-query kernel (attn16g_kernel, G = 6 query groups per wave, the key tiles walked once per block).  Measured (round 5, tools/attn_bench.py,
   // EXPERIMENTS.md): DINOv2-B's 257 tokens as ONE block of 4 waves per (image, head): 48.8 us per layer against 54.4 for attn16u_kernel's three blocks
   // (the six independent groups of a wave overlap their MFMA and softmax streams); the SAME nest on SigLIP's 729 tokens x 80-wide heads is SLOWER
   // (G = 6: 1 459 us against 1 279 — 256 VGPRs + 23 spilled; G = 3, no spills, two blocks per (image, head): 1 308): staging K / V once is not what
   // that launch is short of.  So: 64-wide heads and at most 24 query groups (Nq <= 384) take it, everything else stays on attn16u_kernel.
-  // vt_tune(9, v) / VLATOUCH_ATTN16G: 0 = never, 1 = that policy (default), 3 / 6 = every 16-bit unmasked call with G pinned (tests, A/B).
-  if (g_vt_attn16g < 0) { const char* e = getenv("VLATOUCH_ATTN16G"); g_vt_attn16g = e ? atoi(e) : 1; }
+  // vt_tune(9, v): 0 = never, 1 = that policy (default), 3 / 6 = every 16-bit unmasked call with G pinned (tests).
   const int a16g = g_vt_attn16g;
-  // (only under the default variant selection: VLATOUCH_ATTN16=1, the A/B switch for the rolled attn16_kernel, must reach the kernel it names — ADVICE r5)
-  if (a16 == 2 && a16g && p.dtype != VT_F32 && !p.kmask && p.o_rs % 4 == 0 && p.Nq >= 128 && (p.hd == 0 || p.hd == 64 || p.hd == 80)) {
+  if (a16g && p.dtype != VT_F32 && !p.kmask && p.o_rs % 4 == 0 && p.Nq >= 128 && (p.hd == 0 || p.hd == 64 || p.hd == 80)) {
     const int need = (p.Nq + 15) / 16;
     int bG = 0, bW = 0;
     if (a16g == 3 || a16g == 6) {                     // pinned: fewest blocks per (image, head), then fewest groups in them, then more waves
@@ -1044,12 +804,12 @@ int vt_attn_launch(const VtAttnParams& p, hipStream_t s) {
       return vt_check_launch();
     }
   }
-  if (a16 && p.dtype != VT_F32 && !p.kmask && p.o_rs % 4 == 0 && p.Nk >= 1) {
-#define VT_A16(KERN, T) do { if (p.hd == 96) hipLaunchKernelGGL((KERN<T, 96>), grid, dim3(64 * nw), 0, s, p); \
-                       else if (p.hd == 80) hipLaunchKernelGGL((KERN<T, 80>), grid, dim3(64 * nw), 0, s, p); \
-                       else hipLaunchKernelGGL((KERN<T, 64>), grid, dim3(64 * nw), 0, s, p); } while (0)
-    if (a16 == 2) { if (p.dtype == VT_BF16) VT_A16(attn16u_kernel, bf16_t); else VT_A16(attn16u_kernel, half_t); }
-    else { if (p.dtype == VT_BF16) VT_A16(attn16_kernel, bf16_t); else VT_A16(attn16_kernel, half_t); }
+  // 16-bit, unmasked, 16-byte-aligned rows: DMA-staged tiles
+  if (p.dtype != VT_F32 && !p.kmask && p.o_rs % 4 == 0 && p.Nk >= 1) {
+#define VT_A16(T) do { if (p.hd == 96) hipLaunchKernelGGL((attn16u_kernel<T, 96>), grid, dim3(64 * nw), 0, s, p); \
+                       else if (p.hd == 80) hipLaunchKernelGGL((attn16u_kernel<T, 80>), grid, dim3(64 * nw), 0, s, p); \
+                       else hipLaunchKernelGGL((attn16u_kernel<T, 64>), grid, dim3(64 * nw), 0, s, p); } while (0)
+    if (p.dtype == VT_BF16) VT_A16(bf16_t); else VT_A16(half_t);
 #undef VT_A16
     return vt_check_launch();
   }

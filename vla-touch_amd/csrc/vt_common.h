@@ -125,7 +125,7 @@ __device__ __forceinline__ float act_apply(float x, int act) {
 }
 
 // sum / max over the 64 lanes, result in every lane.  Round 5: inside a row of 16 on DPP lane permutes, across the four rows on v_permlane16_swap /
-// v_permlane32_swap — all VALU — instead of six __shfl_xor = ds_bpermute round trips through the LDS crossbar (-DVLATOUCH_WAVE_SHFL keeps the butterfly for A/B).
+// v_permlane32_swap — all VALU — instead of six __shfl_xor = ds_bpermute round trips through the LDS crossbar.
 __device__ __forceinline__ float rows4_sum(float v) {
   const unsigned u = __builtin_bit_cast(unsigned, v);
   const auto a = __builtin_amdgcn_permlane16_swap(u, u, false, false);
@@ -141,11 +141,6 @@ __device__ __forceinline__ float rows4_max(float v) {
   const unsigned x = __builtin_bit_cast(unsigned, w);
   const auto b = __builtin_amdgcn_permlane32_swap(x, x, false, false);
   return fmaxf(__builtin_bit_cast(float, (unsigned)b[0]), __builtin_bit_cast(float, (unsigned)b[1]));
-}
-__device__ __forceinline__ float wave_sum_shfl(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 // sum over each aligned group of 16 lanes, result in every lane, on DPP lane permutes only (no LDS crossbar round trips as
 // __shfl_xor would take): pairs inside quads, quads inside 8s (row_half_mirror pairs quad 0 <-> quad 1), 8s inside the row of 16
@@ -170,17 +165,8 @@ __device__ __forceinline__ float row16_max(float v) {
   v = fmaxf(v, dpp(v, std::integral_constant<int, 0x140>{}));
   return v;
 }
-#ifdef VLATOUCH_WAVE_SHFL
-__device__ __forceinline__ float wave_sum(float v) { return wave_sum_shfl(v); }
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-#else
 __device__ __forceinline__ float wave_sum(float v) { return rows4_sum(row16_sum(v)); }
 __device__ __forceinline__ float wave_max(float v) { return rows4_max(row16_max(v)); }
-#endif
 
 // generic typed load/store as float
 template <typename T> __device__ __forceinline__ float ldf(const T* p, size_t i);

@@ -10,37 +10,9 @@
 #include "vt_gemm.h"
 #include "vt_kernels.h"
 
-// global stores of the row-segment epilogue.  VT_EPI_ST_POLICY (set by a translation unit before including this header; A/B only): 1 = nt, 2 = sc0 sc1
-// (write-through): a short kernel that stores its whole output in its last microsecond leaves it dirty in L2 for the kernel boundary to write back
-#ifndef VT_EPI_ST_POLICY
-#define VT_EPI_ST_POLICY 0
-#endif
-__device__ __forceinline__ void vt_epi_st128(void* ptr, const float4 v) {
-#if VT_EPI_ST_POLICY == 1
-  typedef __attribute__((ext_vector_type(4))) float f4v;
-  __builtin_nontemporal_store((f4v){v.x, v.y, v.z, v.w}, reinterpret_cast<f4v*>(ptr));
-#elif VT_EPI_ST_POLICY == 2
-  typedef __attribute__((ext_vector_type(4))) float f4v;
-  const f4v t = {v.x, v.y, v.z, v.w};
-  // s_nop: a > 8-byte store reads its data registers a few cycles after issue; hipcc inserts that wait state behind its own stores but does not look inside inline
-  // asm (tools/ubench/band_seam.hip, round 6: without it the next VALU write corrupted 20 % of the stored words)
-  asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 2" ::"v"(ptr), "v"(t) : "memory");
-#else
-  *reinterpret_cast<float4*>(ptr) = v;
-#endif
-}
-__device__ __forceinline__ void vt_epi_st64(void* ptr, const uint2 v) {
-#if VT_EPI_ST_POLICY == 1
-  typedef __attribute__((ext_vector_type(2))) unsigned u2v;
-  __builtin_nontemporal_store((u2v){v.x, v.y}, reinterpret_cast<u2v*>(ptr));
-#elif VT_EPI_ST_POLICY == 2
-  typedef __attribute__((ext_vector_type(2))) unsigned u2v;
-  const u2v t = {v.x, v.y};
-  asm volatile("global_store_dwordx2 %0, %1, off sc0 sc1" ::"v"(ptr), "v"(t) : "memory");
-#else
-  *reinterpret_cast<uint2*>(ptr) = v;
-#endif
-}
+// global stores of the row-segment epilogue
+__device__ __forceinline__ void vt_epi_st128(void* ptr, const float4 v) { *reinterpret_cast<float4*>(ptr) = v; }
+__device__ __forceinline__ void vt_epi_st64(void* ptr, const uint2 v) { *reinterpret_cast<uint2*>(ptr) = v; }
 
 constexpr int EP_LD = 68;                      // floats per row of the epilogue patch (64 + 4 pad, keeps 16-B alignment)
 constexpr int EPT_LD = 36;                     // transposed patch (cmap 2): 64 d-rows x 32 keys + 4 pad

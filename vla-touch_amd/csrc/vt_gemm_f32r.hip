@@ -12,7 +12,6 @@
 // Conv mode (taps > 0, cin % 32 == 0): a k-tile lies inside one tap; rows whose tap falls outside [0, tin) read a zero page.
 // Epilogue: + bias, fp32 row-major C (or the raw split-K slab).  Anything else (activation, column scale, residual, 16-bit types,
 // K % 32 != 0) stays on gemm_kernel.
-#include <stdlib.h>
 #include "vt_common.h"
 #include "vt_gemm.h"
 #include "vt_prof.h"
@@ -218,13 +217,9 @@ __global__ __launch_bounds__(256, 2) void gemm_f32r_kernel(const VtGemmParams p)
 
 }  // namespace
 
-// VLATOUCH_F32_RING=0 keeps every fp32 product on the register-staged kernel (A/B)
-static int f32r_mode() { static const int m = [] { const char* e = getenv("VLATOUCH_F32_RING"); return e ? atoi(e) : -1; }(); return m; }
-
 bool vt_gemm_f32r_eligible(const VtGemmParams& p) {
-  if (f32r_mode() == 0) return false;
   if (p.a_dtype != VT_F32 || (p.w_dtype != VT_F32 && p.w_dtype != VT_F32X3) || p.c_dtype != VT_F32) return false;
-  if (p.w_dtype == VT_F32X3 && (f32r_mode() == 1 || p.K % 64)) return false;     // VLATOUCH_F32_RING=1: ring for exact fp32 only (A/B); K % 64: gemm_kernel's slices
+  if (p.w_dtype == VT_F32X3 && p.K % 64) return false;          // K % 64: gemm_kernel's slices
   if (p.act != VT_ACT_NONE || p.colscale || p.residual || p.hn_w0 || p.hn_w1 || p.cmap) return false;
   if (p.K % BK || p.K < 2 * BK || p.lda % 4 || p.ldw % 4) return false;
   if (p.taps && (p.cin % BK || p.K != p.taps * p.cin)) return false;

@@ -13,13 +13,10 @@
 // Operands are swapped (D = W_tile A_tile^T) so a lane ends with 4 consecutive n of one row m.
 // Epilogue: vt_gemm_epilogue.h (shared with the ping-pong kernels vt_gemm_pp.hip / vt_gemm_ppk.hip, which take the shapes
 // their tiles fit: this kernel is the fallback for every other large 16-bit GEMM).
-#include <stdlib.h>
 #include "vt_common.h"
 #include "vt_gemm.h"
 #include "vt_gemm_epilogue.h"
 #include "vt_prof.h"
-
-int g_vt_gm = 0;         // m-tiles per super-row (VLATOUCH_GEMM_GM; 0 = choose per launch)
 
 namespace {
 
@@ -131,12 +128,7 @@ __global__ __launch_bounds__(2 * BN, MINW * (BN / 128)) void gemm_glds_kernel(co
 
 }  // namespace
 
-int g_vt_force_bm = 0;   // tuning hooks: VLATOUCH_GEMM_BM=64|128, VLATOUCH_GEMM_VARIANT=22|14
-int g_vt_variant = 0;    // 0 = choose per launch; 22 = two LDS stages at 2 blocks/CU, 14 = one stage at 4 blocks/CU
-
 bool vt_gemm_fast_eligible(const VtGemmParams& p) {
-  static const bool init = [] { const char* e = getenv("VLATOUCH_GEMM_BM"); if (e) g_vt_force_bm = atoi(e); e = getenv("VLATOUCH_GEMM_VARIANT"); if (e) g_vt_variant = atoi(e); e = getenv("VLATOUCH_GEMM_GM"); if (e) g_vt_gm = atoi(e); return true; }();
-  (void)init;
   if ((p.a_dtype != VT_BF16 && p.a_dtype != VT_F16) || p.w_dtype != p.a_dtype || p.taps != 0 || p.splitk != 1) return false;
   if (p.c_dtype != p.a_dtype && p.c_dtype != VT_F32) return false;
   if (p.K % BK || p.lda % 8 || p.ldw % 8 || p.N % 4 || p.ldc % 4 || (p.residual && p.ldr % 4)) return false;
@@ -153,7 +145,7 @@ template <typename T16, typename TC, int BM, int CMAP>
 static void launch_variant(int variant, dim3 grid, hipStream_t s, const VtGemmParams& p, int tiles_n, int per_group, int total) {
   // super-row height (measured): tall-skinny outputs (few n-tiles, many m-tiles: the condition K/V projections) like 16,
   // everything else 4
-  const int gm = g_vt_gm > 0 ? g_vt_gm : ((tiles_n <= 16 && per_group / tiles_n >= 128) ? 16 : 4);
+  const int gm = (tiles_n <= 16 && per_group / tiles_n >= 128) ? 16 : 4;
   if (variant == 14) hipLaunchKernelGGL((gemm_glds_kernel<T16, TC, BM, 128, 1, 4, CMAP>), grid, dim3(256), 0, s, p, tiles_n, per_group, total, gm);
   else hipLaunchKernelGGL((gemm_glds_kernel<T16, TC, BM, 128, 2, 2, CMAP>), grid, dim3(256), 0, s, p, tiles_n, per_group, total, gm);
 }
@@ -167,14 +159,13 @@ int vt_gemm_fast_launch(const VtGemmParams& p, hipStream_t s) {
   // ping-pong kernel of vt_gemm_pp.hip (half the L2 -> LDS bytes per flop).
   // A ragged last row block that costs a whole extra round of 256-square tiles (DINOv2-base: 64 images x 257 tokens = 64 x 256 + 64
   // rows; fc1's 65 x 12 = 780 tiles are 3.05 rounds of the 256 CUs): the full row blocks go to the ping-pong kernel, the <= 64 remaining
-  // rows to a second small launch (rows are independent: an exact row split).  VLATOUCH_GEMM_ROWSPLIT=0 for A/B.
-  if (g_vt_force_bm == 0 && vt_gemm_pw_eligible(p)) return vt_gemm_pw_launch(p, s);     // frozen, fragment-packed weights: W never touches LDS
-  if (g_vt_force_bm == 0 && p.cmap == 0 && p.groups == 1 && !p.hn_w0 && !p.hn_w1 && p.M % 256 != 0 && p.M % 256 <= 64 && vt_gemm_pp_eligible(p)) {
-    static const bool on = [] { const char* e = getenv("VLATOUCH_GEMM_ROWSPLIT"); return !e || atoi(e) != 0; }();
+  // rows to a second small launch (rows are independent: an exact row split).
+  if (vt_gemm_pw_eligible(p)) return vt_gemm_pw_launch(p, s);     // frozen, fragment-packed weights: W never touches LDS
+  if (p.cmap == 0 && p.groups == 1 && !p.hn_w0 && !p.hn_w1 && p.M % 256 != 0 && p.M % 256 <= 64 && vt_gemm_pp_eligible(p)) {
     const long tm = (p.M + 255) / 256, tn = (p.N + 255) / 256;
     VtGemmParams a = p;
     a.M = (int)((tm - 1) * 256);
-    if (on && tm > 1 && (tm * tn + 255) / 256 > ((tm - 1) * tn + 255) / 256 && vt_gemm_pp_eligible(a)) {
+    if (tm > 1 && (tm * tn + 255) / 256 > ((tm - 1) * tn + 255) / 256 && vt_gemm_pp_eligible(a)) {
       VtGemmParams b = p;
       const size_t ea = p.a_dtype == VT_F32 ? 4 : 2, ec = p.c_dtype == VT_F32 ? 4 : 2;
       b.M = p.M - a.M;
@@ -185,14 +176,13 @@ int vt_gemm_fast_launch(const VtGemmParams& p, hipStream_t s) {
       return rc != VT_OK ? rc : vt_gemm_launch(b, s);
     }
   }
-  if (g_vt_force_bm == 256 || (g_vt_force_bm == 0 && vt_gemm_pp_eligible(p))) return vt_gemm_pp_launch(p, s);
-  if ((g_vt_force_bm == 160 || g_vt_force_bm == 0) && vt_gemm_ppk_eligible(p)) return vt_gemm_ppk_launch(p, s);
-  int bm = tiles128 < 1024 ? 64 : 128;
-  if (g_vt_force_bm == 64 || g_vt_force_bm == 128) bm = g_vt_force_bm;
+  if (vt_gemm_pp_eligible(p)) return vt_gemm_pp_launch(p, s);
+  if (vt_gemm_ppk_eligible(p)) return vt_gemm_ppk_launch(p, s);
+  const int bm = tiles128 < 1024 ? 64 : 128;
   const int bn = 128;
   const int tiles_n = (p.N + bn - 1) / bn, tiles_m = (p.M + bm - 1) / bm;
   const int per_group = tiles_n * tiles_m, total = per_group * p.groups;
-  const int variant = g_vt_variant ? g_vt_variant : (total < 768 ? 22 : 14);   // 22 = two stages, 2 blocks/CU; 14 = one stage, 4 blocks/CU
+  const int variant = total < 768 ? 22 : 14;   // 22 = two stages, 2 blocks/CU; 14 = one stage, 4 blocks/CU
   VtProfScope prof(3, p, s);
 #define VT_FAST_GO(T16, TC, BMv) launch_variant<T16, TC, BMv, 0>(variant, dim3(total), s, p, tiles_n, per_group, total)
 #define VT_FAST_GO3(T16, TC) \

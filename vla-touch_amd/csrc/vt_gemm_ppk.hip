@@ -13,13 +13,10 @@
 //   * at the end the groups swap halves of their accumulators through LDS (80 KiB, lane-contiguous): group 0 finishes row tiles
 //     0..2 of every wave tile, group 1 row tiles 3..4 (a + b is commutative: the result does not depend on timing), and both
 //     run the shared epilogue on their part.
-#include <stdlib.h>
 #include "vt_common.h"
 #include "vt_gemm.h"
 #include "vt_gemm_epilogue.h"
 #include "vt_prof.h"
-
-extern int g_vt_gm;
 
 namespace {
 
@@ -177,7 +174,7 @@ bool vt_gemm_ppk_eligible(const VtGemmParams& p) {
 int vt_gemm_ppk_launch(const VtGemmParams& p, hipStream_t s) {
   const int tiles_n = (p.N + BN - 1) / BN, tiles_m = (p.M + BM - 1) / BM;
   const int per_group = tiles_n * tiles_m, total = per_group * p.groups;
-  const int gm = g_vt_gm > 0 ? g_vt_gm : 4;
+  const int gm = 4;
   VtProfScope prof(3, p, s);
 #define VT_PPK_GO(T16, TC) hipLaunchKernelGGL((gemm_ppk_kernel<T16, TC>), dim3(total), dim3(512), 0, s, p, tiles_n, per_group, total, gm)
   const bool c16 = p.c_dtype != VT_F32;

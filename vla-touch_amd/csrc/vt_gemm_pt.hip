@@ -32,13 +32,10 @@
 //   KV   cmap 3: fused condition K|V projection of RDT (bias; K half: per-head RMSNorm + K tiles; V half: Vt tiles — the V-half waves
 //        run their MFMAs with the operands SWAPPED, so a lane owns 4 consecutive keys of one d row, which is the Vt tile's order)
 //   P16  bias (+ GELU erf / tanh) -> row-major 16-bit C  (ViT qkv / fc1, adaptor first layers)
-#include <stdlib.h>
 #include "vt_common.h"
 #include "vt_gemm.h"
 #include "vt_kernels.h"
 #include "vt_prof.h"
-
-extern int g_vt_gm;
 
 namespace {
 
@@ -56,16 +53,8 @@ constexpr int SMEM_BYTES = HN_OFF + 256;
 enum { KIND_KV = 0, KIND_P16 = 1, KIND_R32 = 2 };
 enum { MODE_STEADY = 0, MODE_FIRST = 1, MODE_SECOND = 2, MODE_SWITCH = 3, MODE_LAST = 4 };
 
-// the epilogue's store; bench builds can turn it into a register sink (VLATOUCH_PT_ABL & 8: what do the stores themselves cost?)
-__device__ __forceinline__ void pt_store(const uint4_t d, const __amdgpu_buffer_rsrc_t rc, const int off, const int abl) {
-#ifdef VLATOUCH_BENCH_BUILD
-  if (abl & 8) { asm volatile("" :: "v"(d), "v"(off)); return; }
-#endif
-#ifdef VLATOUCH_BENCH_BUILD      // A/B of the store's cache policy bits (VLATOUCH_PT_ABL bits 4..6 -> aux: 1 = sc0, 2 = nt, 3 = sc0 nt)
-  if ((abl >> 4) & 1) { __builtin_amdgcn_raw_buffer_store_b128(d, rc, off, 0, 2); return; }
-  if ((abl >> 5) & 1) { __builtin_amdgcn_raw_buffer_store_b128(d, rc, off, 0, 3); return; }
-  if ((abl >> 6) & 1) { __builtin_amdgcn_raw_buffer_store_b128(d, rc, off, 0, 1); return; }
-#endif
+// the epilogue's store
+__device__ __forceinline__ void pt_store(const uint4_t d, const __amdgpu_buffer_rsrc_t rc, const int off) {
   __builtin_amdgcn_raw_buffer_store_b128(d, rc, off, 0, 0);
 }
 
@@ -160,8 +149,7 @@ struct TileId { int m0, n0; };
 // SWAP (KV kind only): this block walks V-half tiles (columns >= N/2) and runs its MFMAs with the operands exchanged.  `tiles_n`, `total_tiles`
 // count the tiles of ONE role (KV: one half of the columns); `nroles` = 2 for the KV kind: blocks with ((blockIdx.x >> 3) & 1) == 1 are the V role.
 template <typename T16, int KIND, int ACT, bool SWAP>
-__device__ __forceinline__ void pt_body(const VtGemmParams& p, char* smem, const int tiles_n, const int tiles_m, const int total_tiles, const int GM, const int nroles,
-                                        const int abl, const bool rev = false) {
+__device__ __forceinline__ void pt_body(const VtGemmParams& p, char* smem, const int tiles_n, const int tiles_m, const int total_tiles, const int GM, const int nroles) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 2, wn = wave & 3;          // group (row half), column quarter
@@ -171,8 +159,8 @@ __device__ __forceinline__ void pt_body(const VtGemmParams& p, char* smem, const
   // ---- persistent tile walk: block b = (XCD x = b & 7, slot s = b >> 3) takes entries s, s + S, s + 2S, ... of XCD x's contiguous band of the tile
   //      order (the order itself — super-rows of GM m-tiles, n-major inside — is gemm_pp256d_kernel's), so the S blocks of an XCD work on neighbouring tiles
   const int G = gridDim.x / nroles;                                  // blocks of this role
-  // this block's index among them: blockIdx.x with the role bit (bit rb >= 3, the XCD bits stay) squeezed out
-  const int rb = (abl >> 8) & 15;
+  // this block's index among them: blockIdx.x with the role bit (bit rb = 3, the XCD bits stay) squeezed out
+  constexpr int rb = 3;
   const int bx = nroles == 2 ? (int)(((blockIdx.x >> (rb + 1)) << rb) | (blockIdx.x & ((1u << rb) - 1))) : (int)blockIdx.x;
   const int n_base = SWAP ? (p.N >> 1) : 0;
   const bool banded = (G & 7) == 0;
@@ -181,12 +169,7 @@ __device__ __forceinline__ void pt_body(const VtGemmParams& p, char* smem, const
   const int band0 = banded ? (bx & 7) * band : 0;
   const int bandn = min(band, total_tiles - band0);                 // may be <= 0 for the last XCDs of a tiny grid
   int idx = banded ? (bx >> 3) : bx;
-  if (rev) idx = S - 1 - idx;       // second phase of a two-phase walk: the blocks that had one tile more in the first phase get one less here
   if (idx >= bandn) return;
-#ifdef VLATOUCH_BENCH_BUILD      // 2 = only the K-role blocks run, 4 = only the V-role blocks (KV kind: how long does each role take alone?)
-  if ((abl & 2) && SWAP) return;
-  if ((abl & 4) && !SWAP && KIND == KIND_KV) return;
-#endif
   auto decode = [&](int id) __attribute__((always_inline)) -> TileId {
     const int sr = id / (GM * tiles_n);
     const int gmr = min(GM, tiles_m - sr * GM);
@@ -212,12 +195,7 @@ __device__ __forceinline__ void pt_body(const VtGemmParams& p, char* smem, const
     }
   const float* bias = p.bias;
   auto set_stage_ctx = [&](const TileId t) __attribute__((always_inline)) {
-#ifdef VLATOUCH_BENCH_BUILD      // timing only (VLATOUCH_PT_ABL & 128, garbage results): every tile stages the A rows of m-tile (tm & 1) — the A panel becomes
-    // L2-resident (2 MB per XCD), the fabric reads of the launch drop to the W stream: does the time follow the traffic?
-    const uint16_t* A = reinterpret_cast<const uint16_t*>(p.A) + (long)((abl & 128) ? (t.m0 & BM) : t.m0) * p.lda;
-#else
     const uint16_t* A = reinterpret_cast<const uint16_t*>(p.A) + (long)t.m0 * p.lda;
-#endif
     const uint16_t* W = reinterpret_cast<const uint16_t*>(p.W) + (long)t.n0 * p.ldw;
     rsA = __builtin_amdgcn_make_buffer_rsrc((void*)A, 0, 0x7fffffff, 0x00020000);
     rsW = __builtin_amdgcn_make_buffer_rsrc((void*)W, 0, 0x7fffffff, 0x00020000);
@@ -338,7 +316,7 @@ __device__ __forceinline__ void pt_body(const VtGemmParams& p, char* smem, const
           const auto s1 = __builtin_amdgcn_permlane16_swap(d[0][1], d[1][1], false, false);
           const int m = mrow0 + j * 16 + fl15;
           const int off = lb + ((j >> 2) * 16384 + (j & 3) * 2048 + IB * 32);
-          pt_store((uint4_t){s0[0], s1[0], s0[1], s1[1]}, rc, m < p.M ? off : 0x7ffffff0, abl);
+          pt_store((uint4_t){s0[0], s1[0], s0[1], s1[1]}, rc, m < p.M ? off : 0x7ffffff0);
         });
       } else {
         // V half (swapped operands): lane = d row i*16 + l15, keys j*16 + g*4 + r; Vt position of key kk: vt_kpos -> (j&2)*16 + g*8 + (j&1)*4 + r,
@@ -367,7 +345,7 @@ __device__ __forceinline__ void pt_body(const VtGemmParams& p, char* smem, const
             // a row block past the last tile of the stream (the second of the two tiles when only one is left) must not be written: the range
             // check covers voffset only up to num_records, which is per WAVE here -> send it out of range by hand
             pt_store((uint4_t){pack16<T16>(lo[0], lo[1]), pack16<T16>(lo[2], lo[3]), pack16<T16>(hi[0], hi[1]), pack16<T16>(hi[2], hi[3])},
-                     rc, (mg + j * 16) < p.cmap_T * 64 ? off : 0x7ffffff0, abl);
+                     rc, (mg + j * 16) < p.cmap_T * 64 ? off : 0x7ffffff0);
           });
         });
       }
@@ -398,7 +376,7 @@ __device__ __forceinline__ void pt_body(const VtGemmParams& p, char* smem, const
         const auto s0 = __builtin_amdgcn_permlane16_swap(d[0][0], d[1][0], false, false);
         const auto s1 = __builtin_amdgcn_permlane16_swap(d[0][1], d[1][1], false, false);
         const int off = lb + j * 16 * rowb + IB * 32;                            // rows >= M land past num_records: dropped by the range check
-        pt_store((uint4_t){s0[0], s1[0], s0[1], s1[1]}, rc, off, abl);
+        pt_store((uint4_t){s0[0], s1[0], s0[1], s1[1]}, rc, off);
       });
     }
   };
@@ -444,7 +422,7 @@ __device__ __forceinline__ void pt_body(const VtGemmParams& p, char* smem, const
             float4_t x = acc[i][j];
             const float4_t r = __builtin_bit_cast(float4_t, rv[jj][i]);
             x = (x + b4[i]) * c4[i] + r;
-            pt_store(__builtin_bit_cast(uint4_t, x), rc, clane + j * 16 * crow + i * 64, abl);
+            pt_store(__builtin_bit_cast(uint4_t, x), rc, clane + j * 16 * crow + i * 64);
           });
         });
       });
@@ -453,9 +431,6 @@ __device__ __forceinline__ void pt_body(const VtGemmParams& p, char* smem, const
   auto slot_run = [&](auto s_tag) __attribute__((always_inline)) {
     constexpr int SL = decltype(s_tag)::value;
     if constexpr (KIND == KIND_R32) return;
-#ifdef VLATOUCH_BENCH_BUILD      // timing-only ablations (tools/gemm_bench_pt.py --abl; garbage results): 1 = no epilogue slots at all
-    if (abl & 1) return;
-#endif
     if constexpr (SL == 0) epi_stats(I0{}, rstd[0]);
     else if constexpr (SL == 1) epi_store(I0{}, I0{}, rstd[0]);       // (A0, B0)
     else if constexpr (SL == 2) epi_stats(I4{}, rstd[1]);
@@ -490,34 +465,27 @@ __device__ __forceinline__ void pt_body(const VtGemmParams& p, char* smem, const
     const char* As = smem + cur_b * BUF_BYTES;
     const char* Bs = As + BM * 128;
     Frag<T16> a0[4][2], a1[4][2], b0[2][2], b1[2][2];
-    // head of a phase, BEFORE its fragment reads (fewest fragments live: the slot's temporaries fit beside the 128 accumulators): the epilogue slot
-    // of this phase and, in SWITCH phase 2, the move of the staging context to the next tile
+    // head of a phase, BEFORE its fragment reads: in SWITCH phase 2, the move of the staging context to the next tile
     auto head = [&](auto ph_tag) __attribute__((always_inline)) {
       constexpr int ph = decltype(ph_tag)::value;
-#ifdef VLATOUCH_PT_SLOT_HEAD      // A/B: the first placement of the slots (head of the phase, before its fragment reads)
-      if constexpr (MODE == MODE_LAST && ph == 2) slot_run(std::integral_constant<int, 0>{});
-      if constexpr (MODE == MODE_LAST && ph == 3) slot_run(std::integral_constant<int, 1>{});
-      if constexpr (MODE == MODE_FIRST) slot_run(std::integral_constant<int, 2 + ph>{});
-#endif
       if constexpr (MODE == MODE_SWITCH && ph == 2) {           // from here on the stream belongs to the next tile (or, past the last one, re-reads this one)
         set_stage_ctx(nxt);
         stage_params(nxt, (tseq + 1) & 1);
       }
       __builtin_amdgcn_sched_barrier(0);
     };
-    // tail of a phase = right behind its 16 MFMAs, before the barrier that ends the compute half: the epilogue slot that the FIRST placement ran at the
-    // head of the NEXT phase.  Same position in the wave's vector-memory queue (after this phase's unit, before the next one: the wait table is
-    // unchanged) and the same live fragments, but the phase's own fragment reads were issued long ago and the slot's VALU starts while the cluster's last
-    // MFMAs still execute.  At the head the slot sat between the other group's MFMA cluster and this group's fragment reads, so every slot phase
-    // cost slot + exposed LDS latency, twice (once per group): measured 8 % of the K|V projection for the arithmetic alone (tools/pt_abl.sh).
+    // tail of a phase = right behind its 16 MFMAs, before the barrier that ends the compute half: the epilogue slot of the NEXT phase (S_k of the
+    // table above runs at the tail of the phase before it).  Same position in the wave's vector-memory queue as at the head of the next phase
+    // (after this phase's unit, before the next one: the wait table holds either way) and the same live fragments, but the phase's own fragment
+    // reads were issued long ago and the slot's VALU starts while the cluster's last MFMAs still execute.  At the head of the phase the slot sat
+    // between the other group's MFMA cluster and this group's fragment reads, so every slot phase cost slot + exposed LDS latency, twice (once
+    // per group): measured 8 % of the K|V projection for the arithmetic alone.
     auto tail = [&](auto ph_tag) __attribute__((always_inline)) {
       constexpr int ph = decltype(ph_tag)::value;
-#ifndef VLATOUCH_PT_SLOT_HEAD
       if constexpr (MODE == MODE_LAST && ph == 1) slot_run(std::integral_constant<int, 0>{});
       if constexpr (MODE == MODE_LAST && ph == 2) slot_run(std::integral_constant<int, 1>{});
       if constexpr (MODE == MODE_LAST && ph == 3) slot_run(std::integral_constant<int, 2>{});
       if constexpr (MODE == MODE_FIRST && ph < 3) slot_run(std::integral_constant<int, 3 + ph>{});
-#endif
     };
     auto mem_end = [&](auto ph_tag) __attribute__((always_inline)) {
       constexpr int ph = decltype(ph_tag)::value;
@@ -605,9 +573,6 @@ __device__ __forceinline__ void pt_body(const VtGemmParams& p, char* smem, const
   }
   if (wm == 0) __builtin_amdgcn_s_barrier();       // pay back the stagger
   // the last tile's remaining slots, back to back; then drain the (never consumed) trailing units before the wave ends
-#ifdef VLATOUCH_PT_SLOT_HEAD
-  slot_run(std::integral_constant<int, 2>{});
-#endif
   slot_run(std::integral_constant<int, 3>{});
   slot_run(std::integral_constant<int, 4>{});
   slot_run(std::integral_constant<int, 5>{});
@@ -618,27 +583,17 @@ __device__ __forceinline__ void pt_body(const VtGemmParams& p, char* smem, const
 // V half runs its MFMAs with exchanged operands and that choice has to be compile time for the register allocator: the same 16 (of 32) blocks of an
 // XCD walk the same band of m-tiles in both roles, so the A panel they stream is shared in that XCD's L2.
 template <typename T16, int KIND, int ACT>
-__global__ __launch_bounds__(512, 2) void gemm_pt_kernel(const VtGemmParams p, const int tiles_n, const int tiles_m, const int total_tiles, const int GM, const int abl) {
+__global__ __launch_bounds__(512, 2) void gemm_pt_kernel(const VtGemmParams p, const int tiles_n, const int tiles_m, const int total_tiles, const int GM) {
   __shared__ __attribute__((aligned(16))) char smem[SMEM_BYTES];
   if constexpr (KIND == KIND_KV) {
-    if (abl & (1 << 12)) {        // A/B (VLATOUCH_PT_KV_SPLIT=1): the first form — K-half and V-half tiles walked by DIFFERENT blocks (alternate groups of 8)
-      if ((blockIdx.x >> ((abl >> 8) & 15)) & 1) pt_body<T16, KIND, ACT, true>(p, smem, tiles_n, tiles_m, total_tiles, GM, 2, abl);
-      else pt_body<T16, KIND, ACT, false>(p, smem, tiles_n, tiles_m, total_tiles, GM, 2, abl);
-    } else {
-      // every block walks its share of the K-half tiles, then of the V-half tiles (the operand swap is compile time, so the two walks are two copies
-      // of the loop nest): all blocks of an XCD are in the same half at the same time and at the same pace, so the A panel and the W band they share stay
-      // shared, and no CU idles while the slower half finishes.  The second walk takes the slots in reverse, which evens out the odd tile.
-      pt_body<T16, KIND, ACT, false>(p, smem, tiles_n, tiles_m, total_tiles, GM, 1, abl, false);
-      __syncthreads();            // (LDS of the first walk is dead: its last parameter reads are behind this barrier)
-      pt_body<T16, KIND, ACT, true>(p, smem, tiles_n, tiles_m, total_tiles, GM, 1, abl, true);
-    }
+    if ((blockIdx.x >> 3) & 1) pt_body<T16, KIND, ACT, true>(p, smem, tiles_n, tiles_m, total_tiles, GM, 2);
+    else pt_body<T16, KIND, ACT, false>(p, smem, tiles_n, tiles_m, total_tiles, GM, 2);
   } else {
-    pt_body<T16, KIND, ACT, false>(p, smem, tiles_n, tiles_m, total_tiles, GM, 1, abl);
+    pt_body<T16, KIND, ACT, false>(p, smem, tiles_n, tiles_m, total_tiles, GM, 1);
   }
 }
 
-int g_pt_on = -1;
-int g_pt_abl = 0;                // bench builds only (VLATOUCH_PT_ABL): see the #ifdef VLATOUCH_BENCH_BUILD blocks above
+int g_pt_on = 1;                 // vt_tune(8, .): 0 = gemm_pp256d_kernel takes these launches
 int g_pt_cus = 0;
 
 }  // namespace
@@ -656,28 +611,19 @@ static bool pt_kind_ok(const VtGemmParams& p) {
   if ((long)p.ldc * 2 * 128 >= (1L << 31)) return false;
   return p.act == VT_ACT_NONE || p.act == VT_ACT_GELU_ERF || p.act == VT_ACT_GELU_TANH;
 }
-static bool pt_enabled() {
-  if (g_pt_on < 0) { const char* e = getenv("VLATOUCH_PT"); g_pt_on = e ? atoi(e) : 1; }
-  return g_pt_on != 0;
-}
-
-void vt_gemm_pt_tune(int value) {
-  (void)pt_enabled();                        // the environment default is read before the first explicit setting
-  g_pt_on = value != 0;
-}
+void vt_gemm_pt_tune(int value) { g_pt_on = value != 0; }
 
 // One round of 160 .. 256 tiles at K >= 512 (DINOv2-B out-projection: 64 x 3 tiles, K = 768): too short for gemm_pp256d_kernel to beat the 128-column
 // tiles (its 64-KiB prologue fill and LDS-patch epilogue are a third of such a launch), fine for this kernel (continuous operand stream is moot with one
-// tile per block, but the in-register epilogue is not).  VLATOUCH_PT_EXTRA=0 for A/B.
+// tile per block, but the in-register epilogue is not).
 bool vt_gemm_pt_extra_shape(const VtGemmParams& p) {
-  static const bool on = [] { const char* e = getenv("VLATOUCH_PT_EXTRA"); return !e || atoi(e) != 0; }();
-  if (!on || !pt_enabled() || p.cmap != 0 || !vt_gemm_fast_eligible(p) || !pt_kind_ok(p)) return false;
+  if (!g_pt_on || p.cmap != 0 || !vt_gemm_fast_eligible(p) || !pt_kind_ok(p)) return false;
   const long tiles256 = (long)((p.M + 255) / 256) * ((p.N + 255) / 256);
   return tiles256 >= 160 && tiles256 <= 256 && p.K >= 512;
 }
 
 // which launches take the persistent kernel
-bool vt_gemm_pt_eligible(const VtGemmParams& p) { return pt_enabled() && pt_kind_ok(p) && (vt_gemm_pp_shape(p) || vt_gemm_pt_extra_shape(p)); }
+bool vt_gemm_pt_eligible(const VtGemmParams& p) { return g_pt_on && pt_kind_ok(p) && (vt_gemm_pp_shape(p) || vt_gemm_pt_extra_shape(p)); }
 
 int vt_gemm_pt_launch(const VtGemmParams& p, hipStream_t s) {
   if (!g_pt_cus) {
@@ -690,32 +636,19 @@ int vt_gemm_pt_launch(const VtGemmParams& p, hipStream_t s) {
   const int total = tiles_n * tiles_m;
   // super-row height of the tile order: the 16 blocks of one role on an XCD then cover 4 m-tiles x 4 n-tiles at a time (KV kind: 8 n-tiles per role;
   // measured 1 812 us at 4, 1 831 at 8, 1 864 at 16 on the K|V shape); the other kinds keep 8
-  const int gm = g_vt_gm > 0 ? g_vt_gm : (kv ? 4 : 8);
+  const int gm = kv ? 4 : 8;
   int grid;
-  // bits 8..11 of the last argument: which bit of blockIdx.x selects the role of a KV-kind block (3 .. 7; VLATOUCH_PT_ROLE_BIT for A/B)
-  static const int role_bit = [] { const char* e = getenv("VLATOUCH_PT_ROLE_BIT"); const int v = e ? atoi(e) : 3; return v >= 3 && v <= 7 ? v : 3; }();
-  static const int kv_split = [] { const char* e = getenv("VLATOUCH_PT_KV_SPLIT"); return e ? atoi(e) : 1; }();
-  if (kv) {
-    static const int kv_grid = [] { const char* e = getenv("VLATOUCH_PT_KV_GRID"); return e ? atoi(e) : 0; }();   // A/B: leave CUs to a co-running stream
-    const int cap = kv_grid > 0 && kv_grid < g_pt_cus ? kv_grid : g_pt_cus;
-    if (kv_split) {                                    // two roles: whole groups of 256 blocks (role bit up to 7)
-      grid = 2 * total < cap ? 2 * total : cap;
-      grid &= ~((2 << role_bit) - 1);                  // whole groups of 2^(role_bit + 1) blocks: 16 for the default bit 3
-      if (grid < (2 << role_bit)) return VT_ERR_UNSUPPORTED;
-    } else {                                           // every block walks both halves: one block per CU, XCD-banded
-      grid = total < cap ? total : cap;
-      if (grid >= 8) grid &= ~7;
-    }
+  if (kv) {                                          // two roles (bit 3 of blockIdx.x): whole groups of 16 blocks
+    grid = 2 * total < g_pt_cus ? 2 * total : g_pt_cus;
+    grid &= ~15;
+    if (grid < 16) return VT_ERR_UNSUPPORTED;
   } else {
     // one block per tile when the tiles fit the chip (195 tiles must not become 192 blocks + a second round for 3 of them: the kernel falls back to the
     // plain tile order when the grid is not a multiple of 8); otherwise one block per CU, XCD-banded
     grid = total <= g_pt_cus ? total : (g_pt_cus & ~7);
   }
   VtProfScope prof(2, p, s);
-#ifdef VLATOUCH_BENCH_BUILD
-  { const char* e = getenv("VLATOUCH_PT_ABL"); g_pt_abl = e ? atoi(e) : 0; }
-#endif
-#define VT_PT_GO(T16, KIND, ACT) hipLaunchKernelGGL((gemm_pt_kernel<T16, KIND, ACT>), dim3(grid), dim3(512), 0, s, p, tiles_n, tiles_m, total, gm, g_pt_abl | (role_bit << 8) | (kv_split ? (1 << 12) : 0))
+#define VT_PT_GO(T16, KIND, ACT) hipLaunchKernelGGL((gemm_pt_kernel<T16, KIND, ACT>), dim3(grid), dim3(512), 0, s, p, tiles_n, tiles_m, total, gm)
   if (p.cmap == 3) { if (p.a_dtype == VT_BF16) VT_PT_GO(bf16_t, KIND_KV, VT_ACT_NONE); else VT_PT_GO(half_t, KIND_KV, VT_ACT_NONE); }
   else if (p.c_dtype == VT_F32) { if (p.a_dtype == VT_BF16) VT_PT_GO(bf16_t, KIND_R32, VT_ACT_NONE); else VT_PT_GO(half_t, KIND_R32, VT_ACT_NONE); }
   else if (p.a_dtype == VT_BF16) {

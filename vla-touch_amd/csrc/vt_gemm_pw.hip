@@ -22,10 +22,6 @@
 //   * epilogue: the block's 160 x 128 fp32 tile goes through LDS (the ring, XOR-swizzled instead of padded: exactly 80 KiB) and is
 //     read back as whole row segments by vt_epi_segment (bias / per-head RMSNorm / activation / column scale / residual), the same
 //     arithmetic in the same order as vt_gemm_epilogue.h.
-#include <stdlib.h>
-#ifdef VLATOUCH_PW_ST
-#define VT_EPI_ST_POLICY VLATOUCH_PW_ST
-#endif
 #include "vt_common.h"
 #include "vt_gemm.h"
 #include "vt_gemm_epilogue.h"
@@ -33,8 +29,6 @@
 #include "vt_host.h"
 #include "vt_kernels.h"
 #include "../../include/vlatouch.h"
-
-extern int g_vt_gm;
 
 namespace {
 
@@ -76,10 +70,8 @@ template <int N, typename F> __device__ __forceinline__ void static_for(F&& f) {
   if constexpr (N > 0) { static_for<N - 1>(f); f(std::integral_constant<int, N - 1>{}); }
 }
 
-// ABL (timing-only ablations, tools/gemm_bench_pw.py --abl; results are garbage): 1 = no fragment reads after the prologue, 2 = no weight
-// loads after the prologue, 3 = no MFMAs, 4 = no activation DMA after the prologue
 // FUSE: 0 = plain, 1 = producer of a fused RMSNorm hand-off (xn_out / xn_part), 2 = its consumer (rs_part) — own instantiations: the plain kernels keep their registers
-template <typename T16, typename TC, int NB, int ABL = 0, int FUSE = 0>
+template <typename T16, typename TC, int NB, int FUSE = 0>
 __global__ __launch_bounds__(256, 1) void gemm_pw_kernel(const VtGemmParams p, const int tiles_n, const int tiles_per_group, const int total_tiles, const int GM) {
   constexpr int SMEM = NB * A_TILE > BM * BN * 4 ? NB * A_TILE : BM * BN * 4;
   __shared__ __attribute__((aligned(16))) char smem[SMEM];                  // ring of A k-tiles; later the block's fp32 output tile
@@ -121,18 +113,14 @@ __global__ __launch_bounds__(256, 1) void gemm_pw_kernel(const VtGemmParams p, c
   int4_t wb[NB][4];
   auto issue = [&](const int kt, auto bc) {
     constexpr int b = decltype(bc)::value;
-    if (ABL != 4 || kt < NB - 1) {
 #pragma unroll
-      for (int e = 0; e < 5; ++e)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_void*)(smem + b * A_TILE + (wave + 4 * e) * 1024), 16, asrc[e], kt * (BK * 2), 0, 0);
-    }
-    if (ABL != 2 || kt < NB - 1) {
-      const char* sb = wbase + (long)kt * 4096;
-      pw_wload<0, true>(wb[b][0], wvoff, sb);
-      pw_wload<1024, false>(wb[b][1], wvoff, sb);
-      pw_wload<2048, false>(wb[b][2], wvoff, sb);
-      pw_wload<3072, false>(wb[b][3], wvoff, sb);
-    }
+    for (int e = 0; e < 5; ++e)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_void*)(smem + b * A_TILE + (wave + 4 * e) * 1024), 16, asrc[e], kt * (BK * 2), 0, 0);
+    const char* sb = wbase + (long)kt * 4096;
+    pw_wload<0, true>(wb[b][0], wvoff, sb);
+    pw_wload<1024, false>(wb[b][1], wvoff, sb);
+    pw_wload<2048, false>(wb[b][2], wvoff, sb);
+    pw_wload<3072, false>(wb[b][3], wvoff, sb);
   };
 
   // fragment (32 rows x 16 k) of k-step s of the tile in slot b: lane reads row j*32 + l31, chunk s*2 + hk (swizzled by the row)
@@ -160,7 +148,6 @@ __global__ __launch_bounds__(256, 1) void gemm_pw_kernel(const VtGemmParams p, c
   __builtin_amdgcn_sched_barrier(0);
   int4_t af[2][TMW];
   frags(af[0], 0, 0);
-  if constexpr (ABL == 1) frags(af[1], 0, 1);
 
   // consumer of a fused RMSNorm: the block's 160 rows x rs_n (sum x^2, sum x) pairs = 160 * rs_n / 2 float4, dealt flat over the 256 threads
   // (float4 q = tid + 256 i: row q / (rs_n / 2), two pairs of that row) — 10 loads per thread at rs_n = 32 instead of 16 on 160 of the threads
@@ -183,17 +170,10 @@ __global__ __launch_bounds__(256, 1) void gemm_pw_kernel(const VtGemmParams p, c
     }
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
-      if constexpr (ABL != 1) {
-        if (s < 3) frags(af[(s + 1) & 1], U, s + 1);
-        else if (!TAIL || U < NB - 1) frags(af[0], (U + 1) % NB, 0);
-      }
-      if constexpr (ABL != 3) {
+      if (s < 3) frags(af[(s + 1) & 1], U, s + 1);
+      else if (!TAIL || U < NB - 1) frags(af[0], (U + 1) % NB, 0);
 #pragma unroll
-        for (int j = 0; j < TMW; ++j) acc[j] = mma32<T16>(wb[U][s], af[s & 1][j], acc[j]);
-      } else {
-#pragma unroll
-        for (int j = 0; j < TMW; ++j) asm volatile("" : "+v"(af[s & 1][j]), "+v"(wb[U][s]));
-      }
+      for (int j = 0; j < TMW; ++j) acc[j] = mma32<T16>(wb[U][s], af[s & 1][j], acc[j]);
     }
     // issue order of the k-tile: MFMA, fragment read, MFMA, ... — every read of step s+1 has five MFMAs (160 clk) to land before its
     // consumer (left alone, hipcc keeps only two reads in flight and a lone wave per SIMD stalls on lgkmcnt before every MFMA)
@@ -213,11 +193,6 @@ __global__ __launch_bounds__(256, 1) void gemm_pw_kernel(const VtGemmParams p, c
   for (; t + NB < nk; t += NB) static_for<NB>([&](auto uc) { sub(t + decltype(uc)::value, uc, std::false_type{}); });
   static_for<NB>([&](auto uc) { sub(t + decltype(uc)::value, uc, std::true_type{}); });
 
-  if constexpr (ABL == 5) {      // timing only: no epilogue (the accumulators are kept alive, nothing is stored)
-#pragma unroll
-    for (int j = 0; j < TMW; ++j) asm volatile("" :: "v"(acc[j]));
-    return;
-  }
   // ---------------- epilogue: accumulators -> the block's fp32 tile in LDS [160][128], 16-byte columns XOR-swizzled by the row; read back as
   // row segments: 16 lanes cover 64 columns (= one head) of one row, 4 rows per instruction; wave w takes column half w & 1 of rows (w >> 1) * 80 ..
   float* tile = reinterpret_cast<float*>(smem);
@@ -409,15 +384,10 @@ __global__ void pack_w32_kernel(const uint16_t* __restrict__ W, const long ldw, 
 
 }  // namespace
 
-#ifdef VLATOUCH_BENCH_BUILD
-static int g_vt_pw_abl = 0;     // vt_tune(5, k): timing-only ablation k of gemm_pw_kernel<bf16, bf16, 4> (0 = off)
-#endif
-static int g_vt_pw_nb = 0;      // ring depth 4 | 8 (VLATOUCH_PW_NB, vt_tune(1, .)); 0 = default
-static int g_vt_pw_on = 1;      // VLATOUCH_PW=0 / vt_tune(2, 0) disables the kernel (A/B against gemm_ppk_kernel / gemm_pp256d_kernel)
+static int g_vt_pw_nb = 0;      // ring depth 4 | 8 (vt_tune(1, .)); 0 = default
+static int g_vt_pw_on = 1;      // vt_tune(2, 0) disables the kernel (against gemm_ppk_kernel / gemm_pp256d_kernel)
 
 bool vt_gemm_pw_eligible(const VtGemmParams& p) {
-  static const bool init = [] { const char* e = getenv("VLATOUCH_PW"); const char* nb = getenv("VLATOUCH_PW_NB"); if (nb) g_vt_pw_nb = atoi(nb); if (e) g_vt_pw_on = atoi(e) != 0; return true; }();
-  (void)init;
   if (!g_vt_pw_on || !p.Wp || !vt_gemm_fast_eligible(p) || p.cmap || p.groups != 1) return false;
   if (p.N % BN || p.K % (8 * BK) || p.lda >= (1 << 21)) return false;
   const long tiles = (long)((p.M + BM - 1) / BM) * (p.N / BN) * p.groups;
@@ -429,35 +399,24 @@ bool vt_gemm_pw_eligible(const VtGemmParams& p) {
 int vt_gemm_pw_launch(const VtGemmParams& p, hipStream_t s) {
   const int tiles_n = p.N / BN, tiles_m = (p.M + BM - 1) / BM;
   const int per_group = tiles_n * tiles_m, total = per_group * p.groups;
-  const int gm = g_vt_gm > 0 ? g_vt_gm : 4;
+  const int gm = 4;
   VtProfScope prof(3, p, s);
   const bool c16 = p.c_dtype != VT_F32;
 #define VT_PW_GO(T16, TC) do { if (g_vt_pw_nb == 8) hipLaunchKernelGGL((gemm_pw_kernel<T16, TC, 8>), dim3(total), dim3(256), 0, s, p, tiles_n, per_group, total, gm); \
                                else hipLaunchKernelGGL((gemm_pw_kernel<T16, TC, 4>), dim3(total), dim3(256), 0, s, p, tiles_n, per_group, total, gm); } while (0)
-#ifdef VLATOUCH_BENCH_BUILD      // timing-only ablations (garbage results): compiled only into a bench build (make DEFS=-DVLATOUCH_BENCH_BUILD)
-  if (g_vt_pw_abl && p.a_dtype == VT_BF16 && c16) {
-    const dim3 g(total), b(256);
-    if (g_vt_pw_abl == 1) hipLaunchKernelGGL((gemm_pw_kernel<bf16_t, bf16_t, 4, 1>), g, b, 0, s, p, tiles_n, per_group, total, gm);
-    else if (g_vt_pw_abl == 2) hipLaunchKernelGGL((gemm_pw_kernel<bf16_t, bf16_t, 4, 2>), g, b, 0, s, p, tiles_n, per_group, total, gm);
-    else if (g_vt_pw_abl == 3) hipLaunchKernelGGL((gemm_pw_kernel<bf16_t, bf16_t, 4, 3>), g, b, 0, s, p, tiles_n, per_group, total, gm);
-    else if (g_vt_pw_abl == 4) hipLaunchKernelGGL((gemm_pw_kernel<bf16_t, bf16_t, 4, 4>), g, b, 0, s, p, tiles_n, per_group, total, gm);
-    else hipLaunchKernelGGL((gemm_pw_kernel<bf16_t, bf16_t, 4, 5>), g, b, 0, s, p, tiles_n, per_group, total, gm);
-    return vt_check_launch();
-  }
-#endif
   if (p.xn_out || p.rs_part) {        // fused RMSNorm hand-off (vt_gemm.h): ring depth 4 only
     const dim3 g(total), b(256);
     if (p.xn_out && (c16 || !p.residual || p.act != VT_ACT_NONE || p.hn_w0 || p.hn_w1)) return VT_ERR_UNSUPPORTED;
     if (p.xn_out && p.rs_part) return VT_ERR_UNSUPPORTED;
     if (p.xn_out) {
-      if (p.a_dtype == VT_BF16) hipLaunchKernelGGL((gemm_pw_kernel<bf16_t, float, 4, 0, 1>), g, b, 0, s, p, tiles_n, per_group, total, gm);
-      else hipLaunchKernelGGL((gemm_pw_kernel<half_t, float, 4, 0, 1>), g, b, 0, s, p, tiles_n, per_group, total, gm);
+      if (p.a_dtype == VT_BF16) hipLaunchKernelGGL((gemm_pw_kernel<bf16_t, float, 4, 1>), g, b, 0, s, p, tiles_n, per_group, total, gm);
+      else hipLaunchKernelGGL((gemm_pw_kernel<half_t, float, 4, 1>), g, b, 0, s, p, tiles_n, per_group, total, gm);
     } else if (!c16) {
       return VT_ERR_UNSUPPORTED;        // consumers are the 16-bit-output Linears (qkv, cross q, fc1); an fp32-output consumer would need 260 VGPRs (no second block per CU)
     } else if (p.a_dtype == VT_BF16) {
-      hipLaunchKernelGGL((gemm_pw_kernel<bf16_t, bf16_t, 4, 0, 2>), g, b, 0, s, p, tiles_n, per_group, total, gm);
+      hipLaunchKernelGGL((gemm_pw_kernel<bf16_t, bf16_t, 4, 2>), g, b, 0, s, p, tiles_n, per_group, total, gm);
     } else {
-      hipLaunchKernelGGL((gemm_pw_kernel<half_t, half_t, 4, 0, 2>), g, b, 0, s, p, tiles_n, per_group, total, gm);
+      hipLaunchKernelGGL((gemm_pw_kernel<half_t, half_t, 4, 2>), g, b, 0, s, p, tiles_n, per_group, total, gm);
     }
     return vt_check_launch();
   }
@@ -470,20 +429,13 @@ int vt_gemm_pw_launch(const VtGemmParams& p, hipStream_t s) {
 void vt_unet_fused_tune(int on);
 
 extern "C" int vt_tune(int knob, int value) {
-  VtGemmParams dummy{};
-  (void)vt_gemm_pw_eligible(dummy);          // environment defaults are read before the first explicit setting
   if (knob == 1 && (value == 0 || value == 4 || value == 8)) { g_vt_pw_nb = value; return VT_OK; }
   if (knob == 2) { g_vt_pw_on = value != 0; return VT_OK; }
-#ifdef VLATOUCH_BENCH_BUILD
-  if (knob == 5 && value >= 0 && value <= 5) { g_vt_pw_abl = value; return VT_OK; }
-#else
-  if (knob == 5) return value == 0 ? VT_OK : vt_fail(VT_ERR_UNSUPPORTED, "vt_tune(5, .): the timing-only ablations exist only in a bench build (make DEFS=-DVLATOUCH_BENCH_BUILD)");
-#endif
   if (knob == 6) { vt_attn_kvt_tune(value); return VT_OK; }
   if (knob == 7) { vt_unet_fused_tune(value); return VT_OK; }
   if (knob == 8) { vt_gemm_pt_tune(value); return VT_OK; }
   if (knob == 9 && (value == 0 || value == 1 || value == 3 || value == 6)) { vt_attn16g_tune(value); return VT_OK; }
-  if (knob == 3 || knob == 4) { vt_gemm_pws_tune(knob, value); return VT_OK; }
+  if (knob == 4) { vt_gemm_pws_tune(value); return VT_OK; }
   return vt_fail(VT_ERR_ARG, "vt_tune: unknown knob %d / value %d", knob, value);
 }
 

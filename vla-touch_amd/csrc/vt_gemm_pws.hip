@@ -14,7 +14,6 @@
 //     scope release, ticket); the LAST block of a tile to arrive sums the S slabs in slice order (deterministic: independent of arrival order)
 //     and runs the shared epilogue (bias / per-head RMSNorm / activation / column scale / residual) — no second kernel, no extra boundary.
 //     The ticket counters are self-resetting; the RDT driver zeroes them once per call.
-#include <stdlib.h>
 #include "vt_common.h"
 #include "vt_gemm.h"
 #include "vt_gemm_epilogue.h"
@@ -42,16 +41,10 @@ template <> __device__ __forceinline__ float16_t mma32s<bf16_t>(const int4_t w, 
 template <> __device__ __forceinline__ float16_t mma32s<half_t>(const int4_t w, const int4_t a, const float16_t c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, w), __builtin_bit_cast(f16x8_t, a), c, 0, 0, 0);
 }
-// (A/B: -DVLATOUCH_PWS_NT puts the nt cache policy on the weight stream — every fragment is read by ONE block per launch)
-#ifdef VLATOUCH_PWS_NT
-#define VT_PWS_POL " nt"
-#else
-#define VT_PWS_POL ""
-#endif
 template <int OFF, bool FIRST>
 __device__ __forceinline__ void pws_wload(int4_t& d, const unsigned voff, const char* sbase) {
-  if constexpr (FIRST) asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2 offset:%3" VT_PWS_POL : "=v"(d) : "v"(voff), "s"(sbase), "i"(OFF) : "memory");
-  else asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" VT_PWS_POL : "=v"(d) : "v"(voff), "s"(sbase), "i"(OFF) : "memory");
+  if constexpr (FIRST) asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(d) : "v"(voff), "s"(sbase), "i"(OFF) : "memory");
+  else asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(d) : "v"(voff), "s"(sbase), "i"(OFF) : "memory");
 }
 template <int N>
 __device__ __forceinline__ void pws_wait(int4_t (&w)[8]) {
@@ -260,13 +253,9 @@ __global__ __launch_bounds__(256, 1) void gemm_pws_kernel(const VtGemmParams p, 
 
 }  // namespace
 
-static int g_vt_pws_on = 1;      // VLATOUCH_PWS=0 / vt_tune(3, 0) disables the kernel; vt_tune(4, S) forces the split factor (0 = choose)
-static int g_vt_pws_s = 0;
+static int g_vt_pws_s = 0;       // vt_tune(4, S): forces the split factor (0 = none, -1 = choose)
 
-void vt_gemm_pws_tune(int knob, int value) {
-  if (knob == 3) g_vt_pws_on = value != 0;
-  if (knob == 4) g_vt_pws_s = value;
-}
+void vt_gemm_pws_tune(int split) { g_vt_pws_s = split; }
 
 static int pws_split(const VtGemmParams& p) {
   if (p.splitk > 1) return p.splitk;
@@ -279,9 +268,7 @@ static int pws_split(const VtGemmParams& p) {
 }
 
 bool vt_gemm_pws_eligible(const VtGemmParams& p) {
-  static const bool init = [] { const char* e = getenv("VLATOUCH_PWS"); if (e) g_vt_pws_on = atoi(e) != 0; return true; }();
-  (void)init;
-  if (!g_vt_pws_on || !p.Wp || p.cmap || p.groups != 1 || p.taps != 0 || p.splitk < 1) return false;
+  if (!p.Wp || p.cmap || p.groups != 1 || p.taps != 0 || p.splitk < 1) return false;
   if (p.splitk > 1 && (p.c_dtype != VT_F32 || (p.K / BK) % (p.splitk * CH) || p.ldc % 4)) return false;     // slab mode: whole chunks per slice
   if ((p.a_dtype != VT_BF16 && p.a_dtype != VT_F16) || p.w_dtype != p.a_dtype) return false;
   if (p.c_dtype != p.a_dtype && p.c_dtype != VT_F32) return false;

@@ -3,7 +3,6 @@
 // over split-K partial slabs (one wave per (sample, group), group staged in LDS), per-head q/k RMSNorm,
 // image statistics + patchify (one HBM read of the frames), the SDE update, action (de)normalisation
 // and the small glue kernels of the U-Net / LSTM drivers.
-#include <stdlib.h>
 #include <type_traits>
 #include "vt_common.h"
 #include "vt_kernels.h"
@@ -681,8 +680,8 @@ int vt_k_rownorm(const void* x, int xdt, long ldx, void* y, int ydt, long ldy, c
     return vt_check_launch();
   }
   if (D % 4 || D > 64 * 4 * 8 || rows <= 0) return VT_ERR_ARG;
-  static const int wave_rows = [] { const char* e = getenv("VLATOUCH_ROWNORM_WAVE"); return e ? atoi(e) : 8192; }();   // rows from which the wave-per-row kernel takes over (0 = never)
-  if (xdt == VT_F32 && D >= 512 && wave_rows > 0 && rows >= wave_rows && (ldx % 4) == 0 && (ldy % 4) == 0) {
+  constexpr int wave_rows = 8192;                 // rows from which the wave-per-row kernel takes over
+  if (xdt == VT_F32 && D >= 512 && rows >= wave_rows && (ldx % 4) == 0 && (ldy % 4) == 0) {
     const dim3 grid((unsigned)((rows + 3) / 4));
 #define VT_RNW(TO, NV) hipLaunchKernelGGL((rownorm_wave_kernel<TO, NV>), grid, dim3(256), 0, s, (const float*)x, ldx, (TO*)y, ldy, w, b, rows, D, eps, mode, range_flag)
 #define VT_RNW_T(TO) do { if (D <= 1024) VT_RNW(TO, 4); else if (D <= 1280) VT_RNW(TO, 5); else VT_RNW(TO, 8); } while (0)

@@ -162,7 +162,7 @@ int vt_dino_forward(vt_dino_t h, const void* const* imgs, int ncams, int is_u8, 
   const int M = Bt * N;
   // The reference consumes only pooler_output = the CLS row of the last layer (visual_encoder.py:88-93): in the LAST block every token still feeds
   // K and V, but only the CLS row needs a query, the output projection, the MLP and the residual updates (SURVEY 2.1 "last layer prunes to the CLS
-  // query").  VLATOUCH_DINO_CLS_LAST=0 runs the last block on all tokens (A/B; same CLS row up to the summation order of the small-M GEMM tiles).
+  // query").
   // the FFN of a block on `rows` rows of xn (row stride D) -> tok rows (row stride tstride_out): fc1 (+ activation, or the SwiGLU gate) -> fc2 + LayerScale + residual
   const bool swiglu = act == VT_ACT_SWIGLU;
   auto ffn = [&](const DinoLayer& L, int rows, long tok_stride) -> int {
@@ -189,10 +189,9 @@ int vt_dino_forward(vt_dino_t h, const void* const* imgs, int ncams, int is_u8, 
       } }
     return VT_OK;
   };
-  static const bool cls_last_on = [] { const char* e = getenv("VLATOUCH_DINO_CLS_LAST"); return !e || atoi(e) != 0; }();
   for (int l = 0; l < d.layers; ++l) {
     const DinoLayer& L = h->L[l];
-    const bool cls_only = cls_last_on && cls && !d.out_all && l == d.layers - 1;
+    const bool cls_only = cls && !d.out_all && l == d.layers - 1;
     CK(vt_k_rownorm(tok, VT_F32, D, ws + w.xn, d.adt, D, L.ln1_w, L.ln1_b, M, D, d.eps, VT_NORM_LAYER, s));
     if (cls_only) {
       const long tstride = (long)N * D;                 // CLS row of image b = row b * N of the token matrix

@@ -269,8 +269,8 @@ int rgemm(RCtx& c, VtGemmParams p, const char* what, const float* hn_w0 = nullpt
   const long tiles64 = (long)((p.M + 63) / 64) * ((p.N + 63) / 64);
   const int nk = p.K / 64;
   // slices per tile on the fragment-packed small-M kernel: at most 4 (8 slices of a K = 2048 Linear finish the GEMM 1 us sooner and cost the
-  // slab reduction 2 us more: batch 1 21.6 -> 21.0 ms; VLATOUCH_RDT_SPLIT_CAP for A/B)
-  static const int split_cap = [] { const char* e = getenv("VLATOUCH_RDT_SPLIT_CAP"); return e && atoi(e) > 0 ? atoi(e) : 4; }();
+  // slab reduction 2 us more: batch 1 21.6 -> 21.0 ms)
+  constexpr int split_cap = 4;
   int S = (int)(512 / (tiles64 > 0 ? tiles64 : 1));
   if (S > RDT_MAX_SPLITK) S = RDT_MAX_SPLITK;
   if (S > nk / 2) S = nk / 2;
@@ -457,15 +457,14 @@ int run_blocks(RCtx& c, const uint8_t* lang_mask) {
   // RMSNorm hand-off (VtGemmParams::xn_out / rs_part): when every Linear of a block runs on the weights-in-registers tile (batch 32: M = 2144) the three
   // norm launches of a block disappear — the residual Linear writes x * gain + sums of squares, the next Linear scales its rows by rstd.
   // Both RmsNorm forms (round 5: the producer hands over the row sums beside the sums of squares, which is what the variance form of
-  // timm <= 1.0.8 needs); VLATOUCH_RDT_FUSE_NORM=0 for A/B.
+  // timm <= 1.0.8 needs).
   {
-    static const bool on = [] { const char* e = getenv("VLATOUCH_RDT_FUSE_NORM"); return !e || atoi(e) != 0; }();
     const Blk& b0 = c.h->blk[0];
     VtGemmParams pr = lin(c.ws + c.w.att, d.adt, D, b0.proj_w, d.cdt, D, b0.proj_b, x, VT_F32, D, M, D, D, VT_ACT_NONE, b0.proj_wp);
     pr.residual = x; pr.ldr = D;
     VtGemmParams c1 = lin(c.ws + c.w.xn, d.adt, D, b0.qkv_w, d.cdt, D, b0.qkv_b, c.ws + c.w.qkv, d.adt, 3 * D, M, 3 * D, D, VT_ACT_NONE, b0.qkv_wp);
     VtGemmParams c2 = lin(c.ws + c.w.xn, d.adt, D, b0.cq_w, d.cdt, D, b0.cq_b, c.ws + c.w.q, d.adt, D, M, D, D, VT_ACT_NONE, b0.cq_wp);
-    c.fuse_norm = on && (d.rms_mode == VT_NORM_RMS_MEANSQ || d.rms_mode == VT_NORM_RMS_VAR) && c.w.slab_bytes == 0 && D % 128 == 0 && 2 * (D / 128) <= 32 && vt_gemm_fast_eligible(pr) &&
+    c.fuse_norm = (d.rms_mode == VT_NORM_RMS_MEANSQ || d.rms_mode == VT_NORM_RMS_VAR) && c.w.slab_bytes == 0 && D % 128 == 0 && 2 * (D / 128) <= 32 && vt_gemm_fast_eligible(pr) &&
                   vt_gemm_pw_eligible(pr) && vt_gemm_fast_eligible(c1) && vt_gemm_pw_eligible(c1) && vt_gemm_fast_eligible(c2) && vt_gemm_pw_eligible(c2);
     c.rs_pending = false;
   }

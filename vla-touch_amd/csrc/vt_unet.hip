@@ -16,7 +16,6 @@
 //   per up-sample (levels-1):    w_even [C][2*C] (taps k=1,k=3)   w_odd [C][2*C] (taps k=0,k=2)   b
 //   final:  fc_w [C0][k*C0]  fc_b  fgn_g  fgn_b  out_w [input_dim][C0]  out_b
 #include <math.h>
-#include <stdlib.h>
 #include <string.h>
 #include <new>
 #include "vt_common.h"
@@ -335,16 +334,12 @@ int make_ctx(Ctx& c, vt_unet_t h, int B, int T, void* ws, vt_stream_t s) {
 
 }  // namespace
 
-// VLATOUCH_UNET_FUSED=0 / vt_tune(7, 0) keeps the sampler on the launch-per-op driver below (A/B)
-static int g_unet_fused = -1;
-static bool fused_enabled() {
-  if (g_unet_fused < 0) { const char* e = getenv("VLATOUCH_UNET_FUSED"); g_unet_fused = (!e || atoi(e) != 0) ? 1 : 0; }
-  return g_unet_fused != 0;
-}
-void vt_unet_fused_tune(int on) { g_unet_fused = on ? 1 : 0; }
+// vt_tune(7, 0) keeps the sampler on the launch-per-op driver below
+static bool g_unet_fused = true;
+void vt_unet_fused_tune(int on) { g_unet_fused = on != 0; }
 
 size_t vt_unet_fused_plan_bytes(vt_unet_t h, int B, int T, int n_steps) { return h ? vt_unet_fused_workspace_bytes(h, B, T, n_steps) : 0; }
-int vt_unet_fused_covers(vt_unet_t h, int B, int T, int n_steps) { return (h && fused_enabled() && vt_unet_fused_ok(h, B, T, n_steps)) ? 1 : 0; }
+int vt_unet_fused_covers(vt_unet_t h, int B, int T, int n_steps) { return (h && g_unet_fused && vt_unet_fused_ok(h, B, T, n_steps)) ? 1 : 0; }
 
 // the larger of the two drivers' needs; the fused plan is sized whenever the CONFIGURATION supports it, packed or not (a caller may size first and
 // pack afterwards)
@@ -358,7 +353,7 @@ int vt_unet_forward(vt_unet_t h, const float* x, const float* t_dev, float t_hos
                     int B, int T, void* workspace, vt_stream_t stream) {
   Ctx c;
   CK(make_ctx(c, h, B, T, workspace, stream));
-  if (!t_dev && fused_enabled() && vt_unet_fused_ok(h, B, T, 1))
+  if (!t_dev && g_unet_fused && vt_unet_fused_ok(h, B, T, 1))
     return vt_unet_fused_run(h, const_cast<float*>(x), cond, &t_host, nullptr, 1, nullptr, nullptr, out, B, T, workspace, (hipStream_t)stream);
   CK(vt_wrap(film_tables(c, t_dev, t_host, false, cond), "unet film tables"));
   CK(vt_wrap(trunk(c, x, out), "unet trunk"));
@@ -411,7 +406,7 @@ int vt_si_sample_ex(vt_unet_t h, float* x, const float* cond, const float* noise
   if (traj) { if (hipMemcpyAsync(traj, x, n * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return vt_fail(VT_ERR_LAUNCH, "traj copy"); }
   // delta_t = float(1/diffuse_step); n_steps = int(1/delta_t)  (bridge_model.py:335)
   const float dt = (float)(1.0 / (double)n_steps);
-  const bool fused = fused_enabled() && vt_unet_fused_ok(h, B, T, n_steps);
+  const bool fused = g_unet_fused && vt_unet_fused_ok(h, B, T, n_steps);
   float ts[64];
   VtSdeCoef coef[64];
   for (int k = 1; k <= n_steps; ++k) {

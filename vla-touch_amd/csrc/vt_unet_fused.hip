@@ -9,7 +9,6 @@
 //   * final_conv.1 (1x1 to the action dims) of both nets and the Euler-Maruyama update are one small kernel (vt_ufinal).
 // Res-block outputs that a later launch needs as a plain tensor (identity residuals, skip connections) are written by the first consumer.
 #include <math.h>
-#include <stdlib.h>
 #include <string.h>
 #include "vt_common.h"
 #include "vt_kernels.h"
@@ -28,9 +27,7 @@ struct Tile { int J, cs, S, nsamp, mtiles; size_t lds; int l_r, l_st, l_par, l_h
 // the number of rounds grows with the slices this launch writes; more than two blocks per CU run in waves.
 // cpg_min: the smallest GroupNorm group width among the sources (0 = no GroupNorm): bounds the statistics units of a block.
 bool pick_tile(int B, int Tin, int Tq, int Ntiles, int ntaps, int Ctot, int cmin, int unit, int cpg_min, int groups, bool has_res_in, Tile* out) {
-  static const double t_step = [] { const char* e = getenv("VLATOUCH_UC_TSTEP"); return e ? atof(e) : 0.1; }();
-  static const double t_round = [] { const char* e = getenv("VLATOUCH_UC_TROUND"); return e ? atof(e) : 1.5; }();
-  static const double blk_cap = [] { const char* e = getenv("VLATOUCH_UC_BLOCKS"); return e ? atof(e) : 512.0; }();
+  constexpr double t_step = 0.1, t_round = 1.5, blk_cap = 512.0;
   double best_cost = 1e30;
   Tile bt;
   bool found = false;

@@ -18,8 +18,6 @@ loop: a training step is a few thousand small launches (this is the f-4 row "bui
 """
 from __future__ import annotations
 
-import os
-
 import ctypes as C
 from collections import OrderedDict
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -105,7 +103,7 @@ def _splits(M: int, N: int, K: int) -> int:
     one 4-wave block per tile leaves most of the 256 CUs idle.  Aim at >= 512 blocks of 64x64 (two per CU, what the LDS ring of
     csrc/vt_gemm_f32r.hip is sized for) while a slice keeps >= 256 of the reduction (tools/gemm_bench_f32.py: within 5 % of the best
     factor on every shape of the step; more splits only add slab traffic)."""
-    if N % 4 or os.environ.get("VLATOUCH_TRAIN_SPLITK", "1") == "0":
+    if N % 4:
         return 1
     blocks = ((M + 63) // 64) * ((N + 63) // 64)
     s = 1
