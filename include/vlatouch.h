@@ -65,6 +65,14 @@ int vt_tune(int knob, int value);
 /* Flash attention, head_dim 64 (or 96: params.hd): params = struct VtAttnParams (csrc/vt_kernels.h), host pointer.
  * Replaces F.scaled_dot_product_attention (models/rdt/blocks.py:116-123) and HF Dinov2SelfAttention. */
 int vt_attention(const void* params, vt_stream_t stream);
+/* Cross-attention against a cached condition, head_dim 64, bf16 or fp16: params = struct VtAttnKvtParams (csrc/vt_kernels.h), host pointer.
+ * K / V come as the per-head tile stream documented in csrc/vt_attn_kvt.hip; params.parts > 1 splits every sample's keys over that many
+ * blocks and needs params.part_ws of vt_attention_kvt_part_bytes(B, H, Nq, parts) bytes.  Replaces the SDPA call of CrossAttention.forward
+ * (models/rdt/blocks.py:102-123) against the image / language condition. */
+int vt_attention_kvt(const void* params, vt_stream_t stream);
+size_t vt_attention_kvt_part_bytes(int B, int H, int Nq, int parts);
+/* Row-major K and V [M][ld] (head h at columns h*64..) -> that tile stream KV, T tiles per head (T * 64 >= M, rows >= M zero). */
+int vt_retile_kv(const void* K, const void* V, long ld, void* KV, int M, int T, int H, vt_stream_t stream);
 /* GroupNorm(+Mish, FiLM, residual) over fp32 split-K slabs: params = struct VtGnParams. */
 int vt_groupnorm(const void* params, vt_stream_t stream);
 /* Row norm: mode 0 LayerNorm, 1 RMSNorm(mean-square), 2 RMSNorm(timm<=1.0.8 unbiased-variance form). */

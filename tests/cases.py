@@ -181,6 +181,26 @@ def lstm_inputs(B: int, Tlen: int, seed: int = 5, hidden: int = 256):
                 forces=T(g.standard_normal((B, Tlen, 3), dtype=np.float32)))
 
 
+def vt_kpos() -> torch.Tensor:
+    """Position of key kk (0..63) inside a Vt row of the cached-condition tile stream (csrc/vt_kernels.h, vt_kpos)."""
+    kk = torch.arange(64)
+    return (kk & 32) | (((kk >> 2) & 3) << 3) | (((kk >> 4) & 1) << 2) | (kk & 3)
+
+
+def kv_tile_stream(k: torch.Tensor, v: torch.Tensor, T: int, fill: float = 0.0) -> torch.Tensor:
+    """The cached-condition tile stream of csrc/vt_attn_kvt.hip built in torch from row-major k, v [M, H, 64]: [H, T, 2, 64, 64] where
+    tile(h, t) = [K: 64 rows x 64 d][Vt: 64 d x 64 rows, row kk at column vt_kpos(kk)] over the rows m = t * 64 + r; rows >= M hold `fill`."""
+    M, H, D = k.shape
+    assert v.shape == k.shape and D == 64 and T * 64 >= M
+    pk = torch.full((T * 64, H, 64), fill, dtype=k.dtype, device=k.device)
+    pv = torch.full((T * 64, H, 64), fill, dtype=v.dtype, device=v.device)
+    pk[:M], pv[:M] = k, v
+    kt = pk.reshape(T, 64, H, 64).permute(2, 0, 1, 3)                # [h, t, r, d]
+    vt = torch.empty(H, T, 64, 64, dtype=v.dtype, device=v.device)  # [h, t, d, position]
+    vt[..., vt_kpos().to(v.device)] = pv.reshape(T, 64, H, 64).permute(2, 0, 3, 1)
+    return torch.stack([kt, vt], dim=2).contiguous()
+
+
 def rdt_inputs(cfg: dict, B: int, lang_len: int, seed: int = 6, dtype=torch.float32):
     g = synth.inputs_rng(seed)
     D = cfg["hidden"]

@@ -56,8 +56,8 @@ def test_ctypes_structs_match_c_layout():
 #include "vt_kernels.h"
 #include "../../include/vlatouch.h"
 int main() {
-  printf("%zu %zu %zu %zu %zu %zu %zu\n", sizeof(VtGemmParams), offsetof(VtGemmParams, cmap_T), sizeof(VtGnParams), sizeof(VtAttnParams),
-         sizeof(vt_unet_desc), sizeof(vt_dino_desc), sizeof(vt_rdt_desc));
+  printf("%zu %zu %zu %zu %zu %zu %zu %zu\n", sizeof(VtGemmParams), offsetof(VtGemmParams, cmap_T), sizeof(VtGnParams), sizeof(VtAttnParams),
+         sizeof(vt_unet_desc), sizeof(vt_dino_desc), sizeof(vt_rdt_desc), sizeof(VtAttnKvtParams));
   return 0;
 }'''
     d = os.path.join(ROOT, "vla-touch_amd", "csrc")
@@ -71,7 +71,7 @@ int main() {
     out = subprocess.run([exe], capture_output=True, text=True).stdout.split()
     got = [int(x) for x in out]
     want = [C.sizeof(_lib.GemmParams), _lib.GemmParams.cmap_T.offset, C.sizeof(_lib.GnParams), C.sizeof(_lib.AttnParams), C.sizeof(_lib.UnetDesc),
-            C.sizeof(_lib.DinoDesc), C.sizeof(_lib.RdtDesc)]
+            C.sizeof(_lib.DinoDesc), C.sizeof(_lib.RdtDesc), C.sizeof(_lib.AttnKvtParams)]
     assert got == want, (got, want)
 
 

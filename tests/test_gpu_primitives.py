@@ -223,20 +223,15 @@ def test_gemm_condition_tile_stream_outputs(dev, M, K):
     w = rnd((N, K), 2, dev, torch.bfloat16, K ** -0.5)
     bias = rnd((N,), 3, dev)
     ref = ops.gemm(a, w, bias, out_dtype=torch.bfloat16)                       # [M, N] bf16, same kernels, plain layout
-    pad = torch.zeros(T * 64, N, dtype=torch.bfloat16, device=dev)
-    pad[:M] = ref
-    rows = pad.reshape(T, 64, H, 64)                                           # [t, r, h, d]
-    kk = torch.arange(64)
-    pos = (kk & 32) | (((kk >> 2) & 3) << 3) | (((kk >> 4) & 1) << 2) | (kk & 3)   # vt_kpos
     kv = torch.full((H, T, 2, 64, 64), 7.0, dtype=torch.bfloat16, device=dev)
     ops.gemm(a, w, bias, out=kv, out_dtype=torch.bfloat16, cmap=(1, T))
     ops.gemm(a, w, bias, out=kv, out_dtype=torch.bfloat16, cmap=(2, T))
-    valid = (torch.arange(T * 64, device=dev) < M).reshape(T, 64)
-    got_k = kv[:, :, 0].permute(1, 2, 0, 3)                                    # [t, r, h, d]
-    assert torch.equal(got_k[valid], rows[valid])
-    got_v = torch.empty(T, 64, H, 64, dtype=torch.bfloat16, device=dev)        # undo the k order: row kk sits at pos[kk]
-    got_v[:, kk] = kv[:, :, 1][:, :, :, pos.to(dev)].permute(1, 3, 0, 2)       # [h,t,d,kk] -> [t,kk,h,d]
-    assert torch.equal(got_v[valid], rows[valid])
+    rows = ref.reshape(M, H, 64)
+    want = cases.kv_tile_stream(rows, rows, T)
+    ones = torch.ones(M, H, 64, dtype=torch.bool, device=dev)
+    valid = cases.kv_tile_stream(ones, ones, T, fill=False)                    # stream positions of the rows < M
+    assert torch.equal(kv[:, :, 0][valid[:, :, 0]], want[:, :, 0][valid[:, :, 0]])
+    assert torch.equal(kv[:, :, 1][valid[:, :, 1]], want[:, :, 1][valid[:, :, 1]])
 
 
 @pytest.mark.parametrize("mode", ["f32", "bf16", "f16"])

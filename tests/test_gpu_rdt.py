@@ -245,6 +245,46 @@ def test_rdt_forward_edge_language_lengths(dname, dtype, B, L, valid):
     assert e < (2e-4 if dname == "f32" else 3e-2) * scale, (dname, B, L, valid, e)
 
 
+@pytest.mark.parametrize("dname,dtype", [("bf16", torch.bfloat16), ("f16", torch.float16)])
+@pytest.mark.parametrize("horizon", [8, 64, 125])
+@pytest.mark.parametrize("B", [1, 3])
+def test_rdt_forward_image_cross_attention_key_split(dname, dtype, horizon, B):
+    """2100 image tokens with 4 heads: the image layers' cross-attention splits every sample's keys over 16 parts at B = 1 and 3 (vt_rdt.hip, rcarve /
+    cross_attn), against the oracle run live.  N = horizon + 3 = 11 query rows run on 4 waves, whose split writes 64 partial rows per part: the part
+    buffer, the last region of the workspace, must be sized for them.  N = 128, the largest N the driver splits, must be one query block of 8 waves.
+    The engine's scratch is pre-filled with vt_rdt_workspace_bytes + 8 MiB of sentinel (the engine reuses a large enough buffer); no byte past the
+    workspace may change."""
+    from oracle import rdt as orr
+    from vlatouch import _lib as L
+    cfg = dict(cases.RDT_TINY, img_cond_len=2100, horizon=horizon)
+    Llang = 12
+    m = make_rdt(cfg, dtype)
+    ri = cases.rdt_inputs(cfg, B, Llang, seed=40 + B, dtype=dtype)
+    eng = m._standalone_engine(torch.device("cuda"))
+    nb = L.lib().vt_rdt_workspace_bytes(eng._h, B, Llang)
+    buf = torch.full((nb + (8 << 20),), 0xA5, dtype=torch.uint8, device="cuda")
+    eng._ws.bufs[torch.cuda.current_stream().cuda_stream] = buf
+    y = m(ri["x"], ri["freq"], ri["t"], ri["lang_c"], ri["img_c"], lang_mask=ri["lang_mask"])
+    assert eng._ws_for(B, Llang) is buf
+    hit = int((buf[nb:] != 0xA5).sum())
+    assert hit == 0, f"{hit} bytes written past the {nb}-byte workspace"
+    sd = cases.rdt_sd(cfg, dtype)                              # the weights as the engine holds them
+    f32 = {k: v.float() for k, v in sd.items()}
+    rf = {k: (v.float() if v.is_floating_point() else v) for k, v in ri.items()}
+    exact = orr.rdt_forward(f32, rf["x"], rf["freq"], rf["t"], rf["lang_c"], rf["img_c"], lang_mask=rf["lang_mask"], heads=cfg["heads"], horizon=horizon)
+    sd16 = cases.rdt_sd(cfg, torch.bfloat16)                  # the reference's own execution dtype
+    r16 = {k: (v.to(torch.bfloat16) if v.is_floating_point() else v) for k, v in rf.items()}
+    ref16 = orr.rdt_forward(sd16, r16["x"], rf["freq"], rf["t"], r16["lang_c"], r16["img_c"], lang_mask=rf["lang_mask"], heads=cfg["heads"],
+                            horizon=horizon)
+    exact16 = orr.rdt_forward({k: v.float() for k, v in sd16.items()}, r16["x"].float(), rf["freq"], rf["t"], r16["lang_c"].float(), r16["img_c"].float(),
+                              lang_mask=rf["lang_mask"], heads=cfg["heads"], horizon=horizon)
+    scale = float(exact.abs().max())
+    e_hip, e_ref = err(y, exact.numpy()), err(ref16.float(), exact16.numpy())
+    print(f"[split {dname} B{B} horizon {horizon}] scale {scale:.2f}: |hip16-exact| {e_hip:.3e}  |ref16-exact| {e_ref:.3e}")
+    assert torch.isfinite(y.float()).all()
+    assert e_hip <= max(1e-2 * scale, 1.5 * e_ref), (e_hip, e_ref)
+
+
 @pytest.mark.parametrize("dname,dtype", [("f32", torch.float32), ("bf16", torch.bfloat16)])
 def test_rdt_wide_var_rmsnorm(dname, dtype):
     """timm==1.0.3 `RmsNorm` (rsqrt(var_unbiased + eps), the upstream-checkpoint setting; models/rdt/blocks.py:22) at D=2048, B=4:
@@ -300,10 +340,11 @@ def test_engine_rejects_wrong_shapes():
 @pytest.mark.parametrize("B", [1, 4])
 def test_cross_attention_fixed_maximum_matches_online_softmax(B):
     """The cached cross-attention with the load-time score bound (softmax against a FIXED maximum, vt_attn_kvt.hip) against its online form
-    (vt_tune(6, 0)): same chunk within bf16 rounding of the attention output; B = 1 also takes the key-range-parts + combine path.  With the
-    q / k norm gains scaled so that the bound exceeds 40 the launcher must fall back to the online form (bit-equal to it)."""
+    (vt_tune(6, 0)): same chunk within bf16 rounding of the attention output.  2048 image tokens: the image layers take the key-range-parts +
+    combine path at both batches (16 parts at B = 1, 4 at B = 4; cross_attn in vt_rdt.hip splits when the condition has 128 keys per part).  With
+    the q / k norm gains scaled so that the bound exceeds 40 the launcher must fall back to the online form (bit-equal to it)."""
     from vlatouch import _lib as L
-    cfg = cases.RDT_WIDE
+    cfg = dict(cases.RDT_WIDE, img_cond_len=2048)
     r = make_runner(cfg, torch.bfloat16, compute="bf16")        # bf16 probabilities: bounds up to 40 (fp16 ones: up to 10, tests/test_gpu_range_guard.py)
     ri = {k: v.to("cuda:0") for k, v in cases.rdt_inputs(cfg, B, 20, seed=5, dtype=torch.bfloat16).items()}
     args = (ri["lang_tokens"], ri["lang_mask"], ri["img_tokens"], ri["state_tokens"], ri["action_mask"], ri["freq"])

@@ -22,6 +22,19 @@ int vt_attention(const void* params, vt_stream_t stream) {
   if (r) vt_fail(r, "vt_attention: bad strides/sizes or launch failure");
   return r;
 }
+int vt_attention_kvt(const void* params, vt_stream_t stream) {
+  if (!params) return vt_fail(VT_ERR_ARG, "vt_attention_kvt: null params");
+  const int r = vt_attn_kvt_launch(*reinterpret_cast<const VtAttnKvtParams*>(params), (hipStream_t)stream);
+  if (r) vt_fail(r, "vt_attention_kvt: bad sizes / strides (T * 64 >= B * Nk, q_rs % 8), parts without part_ws or > 16, or launch failure");
+  return r;
+}
+size_t vt_attention_kvt_part_bytes(int B, int H, int Nq, int parts) { return vt_attn_kvt_part_bytes(B, H, Nq, parts); }
+int vt_retile_kv(const void* K, const void* V, long ld, void* KV, int M, int T, int H, vt_stream_t stream) {
+  if (!K || !V || !KV || M < 1 || H < 1) return vt_fail(VT_ERR_ARG, "vt_retile_kv: null source / destination or empty shape");
+  const int r = vt_k_retile_kv(K, V, ld, KV, M, T, H, (hipStream_t)stream);
+  if (r) vt_fail(r, "vt_retile_kv: T * 64 < M, ld % 8 or launch failure");
+  return r;
+}
 int vt_groupnorm(const void* params, vt_stream_t stream) {
   if (!params) return vt_fail(VT_ERR_ARG, "vt_groupnorm: null params");
   const int r = vt_k_groupnorm(*reinterpret_cast<const VtGnParams*>(params), (hipStream_t)stream);

@@ -398,11 +398,7 @@ int vt_attn_kvt_launch(const VtAttnKvtParams& p, hipStream_t s) {
   if (p.B <= 0 || p.H <= 0 || p.Nq <= 0 || p.Nk <= 0 || (long)p.T * 64 < (long)p.B * p.Nk || p.q_rs % 8) return VT_ERR_ARG;
   if (p.dtype != 0 && p.dtype != VT_BF16 && p.dtype != VT_F16) return VT_ERR_UNSUPPORTED;
   const bool f16 = p.dtype == VT_F16;             // 0 (unset) = bf16
-  int nw = 4, best = 1 << 30;
-  for (int w = 4; w <= 8; ++w) {
-    const int rows = w * 16, padded = (p.Nq + rows - 1) / rows * rows;
-    if (padded < best) { best = padded; nw = w; }
-  }
+  const int nw = vt_attn_kvt_waves(p.Nq);
   const int qblocks = (p.Nq + nw * 16 - 1) / (nw * 16);
   // algorithmic work of one call: every (batch, head) streams its sample's K and Vt tiles once (16 KiB per 64 keys) + Q in, O out
   const double kv_bytes = (double)p.B * p.H * (((long)p.Nk + 63) / 64) * 16384.0, qo_bytes = 2.0 * p.B * p.H * p.Nq * 64 * 2.0;

@@ -30,7 +30,7 @@ struct VtAttnParams {
   int hd;                     // head dimension: 0 or 64 -> 64; 96
 };
 
-// cross-attention against the cached condition (bf16 only): KV = per-head tile stream over the rows b*Nk + l, see vt_attn_kvt.hip
+// cross-attention against the cached condition (bf16 or IEEE fp16, `dtype`): KV = per-head tile stream over the rows b*Nk + l, see vt_attn_kvt.hip
 struct VtAttnKvtParams {
   const void* Q; const void* KV; void* O;
   long q_bs, q_rs;            // Q element strides: batch, row (head h at +h*64)
@@ -44,8 +44,21 @@ struct VtAttnKvtParams {
   int dtype;                  // VT_BF16 (or 0) / VT_F16: the 16-bit type of Q, the tile stream and O
   unsigned* range_flag;       // range guard word (include/vlatouch.h): VT_RANGE_ATTN_EMPTY when a row's probabilities sum to 0 / inf (the row is written as zeros); null = none
 };
+// waves per block of vt_attn_kvt_launch (4..8).  Nq <= 128: ONE query block of the fewest waves that hold every row, which the split form needs
+// (the RDT driver splits for every N <= 128; the padding rule below ties 4 and 8 waves at 113..128 rows and would take two blocks of 4).  Larger
+// Nq: the fewest padding rows of 16*NW, the smallest NW on ties.  In the split form every lane of a block writes its partial row, so a part of
+// part_ws holds 16*NW rows however many of them are < Nq.
+inline int vt_attn_kvt_waves(int Nq) {
+  if (Nq <= 128) return Nq <= 64 ? 4 : (Nq + 15) / 16;
+  int nw = 4, best = 1 << 30;
+  for (int w = 4; w <= 8; ++w) {
+    const int rows = w * 16, padded = (Nq + rows - 1) / rows * rows;
+    if (padded < best) { best = padded; nw = w; }
+  }
+  return nw;
+}
 // bytes of part_ws for vt_attn_kvt_launch with `parts` parts
-inline size_t vt_attn_kvt_part_bytes(int B, int H, int Nq, int parts) { return parts > 1 ? (size_t)B * H * parts * ((Nq + 15) / 16 * 16 + 16) * 66 * 4 : 0; }
+inline size_t vt_attn_kvt_part_bytes(int B, int H, int Nq, int parts) { return parts > 1 ? (size_t)B * H * parts * (16 * vt_attn_kvt_waves(Nq)) * 66 * 4 : 0; }
 // position of key kk (0..63) inside a Vt tile row: within each 32-key half the keys are stored in the k order of the
 // P fragment (k index g*8 + j <-> key (j>>2)*16 + g*4 + (j&3)), so an A fragment of Vt is one 16-byte chunk.  Aligned pairs
 // and aligned groups of 4 keys stay contiguous.

@@ -99,6 +99,22 @@ class AttnParams(C.Structure):
     ]
 
 
+class AttnKvtParams(C.Structure):
+    _fields_ = [
+        ("Q", C.c_void_p), ("KV", C.c_void_p), ("O", C.c_void_p),
+        ("q_bs", C.c_long), ("q_rs", C.c_long),
+        ("o_bs", C.c_long), ("o_rs", C.c_long),
+        ("kmask", C.c_void_p),
+        ("B", C.c_int), ("H", C.c_int), ("Nq", C.c_int), ("Nk", C.c_int), ("T", C.c_int),
+        ("scale", C.c_float),
+        ("parts", C.c_int),
+        ("part_ws", C.c_void_p),
+        ("fixed_max", C.c_float),
+        ("dtype", C.c_int),
+        ("range_flag", C.c_void_p),
+    ]
+
+
 class UnetDesc(C.Structure):
     _fields_ = [("nets", C.c_int), ("input_dim", C.c_int), ("input_pad", C.c_int), ("cond_dim", C.c_int),
                 ("dsed", C.c_int), ("n_groups", C.c_int), ("ksize", C.c_int), ("n_levels", C.c_int),
@@ -159,6 +175,9 @@ SIGNATURES = {
     "vt_pack_w32": (_I, [_P, _L, _P, _I, _I, _P]),
     "vt_tune": (_I, [_I, _I]),
     "vt_attention": (_I, [_P, _P]),
+    "vt_attention_kvt": (_I, [_P, _P]),
+    "vt_attention_kvt_part_bytes": (_Z, [_I, _I, _I, _I]),
+    "vt_retile_kv": (_I, [_P, _P, _L, _P, _I, _I, _I, _P]),
     "vt_groupnorm": (_I, [_P, _P]),
     "vt_rownorm": (_I, [_P, _I, _L, _P, _I, _L, _P, _P, _I, _I, _F, _I, _P]),
     "vt_headnorm": (_I, [_P, _I, _L, _I, _L, _P, _F, _I, _P]),
