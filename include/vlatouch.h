@@ -399,6 +399,45 @@ int vt_sum_mid(const float* src, long lds, int off, float* out, int B, int T, in
 int vt_mul_(float* a, const float* b, long n, vt_stream_t stream);
 int vt_mse_residual(const float* base, const float* delta, const float* target, float* pred, float* ddelta, float* loss, long n, vt_stream_t stream);
 
+/* ---- camera frames -> SigLIP pixel_values (scripts/franka_model_eef.py:242-288: RoboticDiffusionTransformerModel.preprocess_images + the
+ * `.to(device, dtype)` of step(); SiglipImageProcessor.preprocess).  Bit-identical to that PIL path: optional brightness lift
+ * (v' = min(255, (int)(1.75f * v)) when sum / (h * w * 255.0 * 3) <= 0.15, decided on the device), pad to a square with `fill_rgb` (never
+ * materialised; the fill is not lifted), PIL's 8-bit antialiased resampler (horizontal pass, uint8 intermediate, vertical pass), then the
+ * normalise table.  One frame = one record of the table below; the caller passes the table twice, as host memory (checked here, sizes the
+ * launches) and as the same bytes in device memory (read by the kernels).
+ * Coefficient table of one axis (device int32, built by the host in double for (in, out, filter); vlatouch/imgprep.py):
+ *   [out][2] = (first input index, tap count), then [out][ksize] taps in 22-bit fixed point; a null table = the axis is already at its
+ *   output size and the pass is skipped, as PIL skips it.
+ * flags: VT_IMGPREP_PAD, VT_IMGPREP_BRIGHT, output VT_IMGPREP_OUT_BF16 (default fp32) -> out [n][3][S][S] through `lut` ([3][256] of the
+ *   output dtype; out 16-byte aligned); VT_IMGPREP_OUT_U8 -> plain resample to uint8 HWC, frame i at out + out_off (the `image_size`
+ *   pre-resize; no pad / brightness / missing frames, lut unused, S ignored); VT_IMGPREP_TWO_PASS forces the two-launch form.
+ * A missing frame (src null) becomes the S x S image of fill_rgb.  fill_rgb = r | g << 8 | b << 16.
+ * The fused kernel holds at most 128 intermediate rows per 16-row output tile (rows_max): calls with a larger frame, and the uint8 mode,
+ * run horizontal and vertical passes as two launches through a uint8 scratch in `ws`.
+ * vt_imgprep_workspace_bytes checks the table, WRITES every record's ws_off and returns the bytes vt_imgprep needs (0 on a bad table,
+ * see vt_last_error); copy the table to the device after it. */
+typedef struct {
+  const void* src;      /* uint8 HWC RGB, device; null = missing frame */
+  const void* coef_h;   /* coefficient table of the horizontal pass (input = padded width), or null */
+  const void* coef_v;   /* ... of the vertical pass (input = padded height), or null */
+  long pitch;           /* bytes between rows of src, >= 3 * w */
+  int h, w;             /* frame size */
+  int out_h, out_w;     /* output size (= S unless VT_IMGPREP_OUT_U8) */
+  int ksize_h, ksize_v; /* taps per output index in the tables */
+  int rows_max;         /* most input rows any 16-row output tile reads: max over y0 = 0, 16, .. of first[y1] + count[y1] - first[y0], y1 = min(y0 + 15, out_h - 1); 16 without a vertical table */
+  int reserved;
+  long out_off;         /* VT_IMGPREP_OUT_U8: byte offset of this frame's output */
+  long ws_off;          /* written by vt_imgprep_workspace_bytes */
+} vt_imgprep_frame;
+#define VT_IMGPREP_PAD 1
+#define VT_IMGPREP_BRIGHT 2
+#define VT_IMGPREP_OUT_BF16 4
+#define VT_IMGPREP_OUT_U8 8
+#define VT_IMGPREP_TWO_PASS 16
+size_t vt_imgprep_workspace_bytes(vt_imgprep_frame* frames_host, int n, int S, int flags);
+int vt_imgprep(const vt_imgprep_frame* frames_host, const void* frames_dev, int n, int S, const void* lut, unsigned fill_rgb, int flags,
+               void* out, void* ws, size_t ws_bytes, vt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,7 +10,9 @@ policy are the HIP-backed mirrors.  Differences, all forced by what is absent he
     image_size, x/255, (x-0.5)/0.5) is restated in `SiglipPreprocessor` and pinned against HF's PIL processor in tests;
   * the T5 text encoder is optional, as in the reference (which comments it out "due to limited GPU memory"): with `text_model=` /
     `text_tokenizer=` or `pretrained_text_encoder_name_or_path=` it runs on the card (vlatouch.t5) and `encode_instruction` works;
-    without one, `encode_instruction` raises NotImplementedError."""
+    without one, `encode_instruction` raises NotImplementedError;
+  * `step` turns the camera frames into `pixel_values` on the card (`preprocess_images_device`, vlatouch.imgprep): bit-identical to
+    `preprocess_images(...).to(device, dtype)`, which stays as the CPU statement and runs when `device_preprocess=False`."""
 from __future__ import annotations
 
 import os
@@ -54,8 +56,10 @@ class RoboticDiffusionTransformerModel(object):
     def __init__(self, args, device="cuda", dtype=torch.bfloat16, image_size=None, control_frequency=25, pretrained=None,
                  pretrained_vision_encoder_name_or_path=None, *, vision_model=None, policy=None,
                  state_indices: Optional[Sequence[int]] = None, text_model=None, text_tokenizer=None,
-                 pretrained_text_encoder_name_or_path=None):
+                 pretrained_text_encoder_name_or_path=None, device_preprocess: bool = True):
         self.args = args
+        self.device_preprocess = device_preprocess      # frames -> pixel_values on the card (vlatouch.imgprep); False: the PIL path
+        self._imgprep = {}
         self.dtype = dtype
         self.image_size = image_size
         self.device = device
@@ -172,12 +176,34 @@ class RoboticDiffusionTransformerModel(object):
             out.append(self.image_processor.preprocess(image, return_tensors="pt")["pixel_values"][0])
         return torch.stack(out, dim=0)
 
+    def preprocess_images_device(self, images, out=None):
+        """`preprocess_images(images).to(self.device, self.dtype)`, bit for bit, computed on the card (csrc/vt_imgprep.hip): frames go up
+        as raw bytes in one copy; device-resident uint8 [H, W, 3] tensors are used in place.  Per frame: PIL image, HxWx3 uint8 array,
+        uint8 tensor (host or device) or None."""
+        from vlatouch.imgprep import DevicePreprocessor
+        p, d = self.image_processor, self.args["dataset"]
+        size = p.size["height"]
+        if p.size["width"] != size:
+            raise NotImplementedError("device preprocessing takes a square processor size; use preprocess_images")
+        sz = self.image_size if self.image_size is None or isinstance(self.image_size, int) else tuple(int(v) for v in self.image_size)
+        key = (size, tuple(p.image_mean), tuple(p.image_std), p.rescale_factor, str(self.device), self.dtype,
+               d.get("image_aspect_ratio", "pad") == "pad", bool(d.get("auto_adjust_image_brightness", False)), sz)
+        pp = self._imgprep.get(key)
+        if pp is None:
+            pp = DevicePreprocessor(size, p.image_mean, p.image_std, self.device, self.dtype, pad=key[6], brightness=key[7], image_size=sz,
+                                    rescale_factor=p.rescale_factor)
+            self._imgprep = {key: pp}
+        return pp(list(images), out=out)
+
     @torch.no_grad()
     def step(self, proprio, images, text_embeds):
         """proprio [1, 10]; images: [ext_{t-1}, right_wrist_{t-1}, left_wrist_{t-1}, ext_t, right_wrist_t, left_wrist_t] (PIL or
         None); text_embeds [1, L, lang_token_dim].  Returns the action chunk [1, horizon, 10] fp32 (gripper back in 0..255)."""
         device, dtype = self.device, self.dtype
-        image_tensor = self.preprocess_images(images).to(device, dtype=dtype)
+        if self.device_preprocess:
+            image_tensor = self.preprocess_images_device(images)
+        else:
+            image_tensor = self.preprocess_images(images).to(device, dtype=dtype)
         image_embeds = self.vision_model(image_tensor).detach()
         image_embeds = image_embeds.reshape(-1, self.vision_model.hidden_size).unsqueeze(0)
         joints = proprio.to(device).unsqueeze(0)

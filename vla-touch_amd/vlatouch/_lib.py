@@ -133,6 +133,15 @@ class T5Desc(C.Structure):
                 ("num_buckets", C.c_int), ("max_distance", C.c_int), ("eps", C.c_float), ("cdt", C.c_int), ("adt", C.c_int)]
 
 
+class ImgprepFrame(C.Structure):     # vt_imgprep_frame
+    _fields_ = [("src", C.c_void_p), ("coef_h", C.c_void_p), ("coef_v", C.c_void_p), ("pitch", C.c_long),
+                ("h", C.c_int), ("w", C.c_int), ("out_h", C.c_int), ("out_w", C.c_int), ("ksize_h", C.c_int), ("ksize_v", C.c_int),
+                ("rows_max", C.c_int), ("reserved", C.c_int), ("out_off", C.c_long), ("ws_off", C.c_long)]
+
+
+IMGPREP_PAD, IMGPREP_BRIGHT, IMGPREP_OUT_BF16, IMGPREP_OUT_U8, IMGPREP_TWO_PASS = 1, 2, 4, 8, 16
+
+
 class LstmDesc(C.Structure):
     _fields_ = [("state_dim", C.c_int), ("hidden", C.c_int), ("layers", C.c_int), ("force_dim", C.c_int),
                 ("force_pad", C.c_int), ("in_pad", C.c_int), ("cdt", C.c_int)]
@@ -254,6 +263,8 @@ SIGNATURES = {
     "vt_sum_mid": (_I, [_P, _L, _I, _P, _I, _I, _I, _P]),
     "vt_mul_": (_I, [_P, _P, _L, _P]),
     "vt_mse_residual": (_I, [_P, _P, _P, _P, _P, _P, _L, _P]),
+    "vt_imgprep_workspace_bytes": (_Z, [_P, _I, _I, _I]),
+    "vt_imgprep": (_I, [_P, _P, _I, _I, _P, C.c_uint, _I, _P, _P, _Z, _P]),
     "vt_marker_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     "vt_marker_detect": (_I, [_P, _I, _I, _I, _I, _I, C.c_double, C.c_double, _I, _P, _P, _I, _P, _P, _P]),
     "vt_marker_displacement": (_I, [_P, _P, _I, _I, _P, _I, _P, _P, _P]),

@@ -1,0 +1,313 @@
+"""Camera frames -> SigLIP `pixel_values` on the device (csrc/vt_imgprep.hip), bit-identical to the PIL path of
+`scripts.franka_model_eef.RoboticDiffusionTransformerModel.preprocess_images(...).to(device, dtype)`.
+
+Host side of the feature:
+  * `resample_coeffs(in, out, filter)`: PIL's 8-bit resampler restated — per output index the first input index, the tap count and
+    the taps in 22-bit fixed point, computed in double exactly as Pillow's `precompute_coeffs` / `normalize_coeffs_8bpc` do
+    (src/libImaging/Resample.c).  Cached per geometry, on the host and on the device.
+  * `norm_table(mean, std, dtype)`: the 256 possible outputs of a channel, built with the very expressions of
+    `SiglipPreprocessor.preprocess` and torch's own cast, so the kernel only looks up.
+  * `DevicePreprocessor`: frames of any accepted kind -> one pinned staging buffer -> one host-to-device copy of raw bytes ->
+    `vt_imgprep`.  Device-resident frames (pitched views included) are used in place; with frames of an already-seen geometry at
+    already-seen addresses the call allocates nothing (given `out=`), copies nothing and never synchronises, so it can be captured in
+    a graph together with the tower.
+
+All launches go to the current stream; the staging buffers are reused from call to call on the assumption that calls are issued in
+stream order (the pinned buffer itself is guarded by an event).
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+
+BILINEAR, BICUBIC = 1, 2
+_SUPPORT = {BILINEAR: 1.0, BICUBIC: 2.0}
+PRECISION_BITS = 22
+TILE_ROWS = 16          # output rows of a kernel tile (kTR in csrc/vt_imgprep.hip)
+FUSED_ROWS = 128        # most intermediate rows the fused kernel holds; beyond it the two-launch form runs
+
+
+def _filter(x: np.ndarray, filt: int) -> np.ndarray:
+    x = np.abs(x)
+    if filt == BILINEAR:
+        return np.where(x < 1.0, 1.0 - x, 0.0)
+    a = -0.5
+    return np.where(x < 1.0, ((a + 2.0) * x - (a + 3.0)) * x * x + 1, np.where(x < 2.0, (((x - 5) * x + 8) * x - 4) * a, 0.0))
+
+
+_coeff_cache: dict = {}
+
+
+def resample_coeffs(in_size: int, out_size: int, filt: int = BICUBIC) -> Tuple[np.ndarray, np.ndarray]:
+    """(bounds [out, 2] int32 = (xmin, count), taps [out, ksize] int32) of PIL's resize of an 8-bit axis from in_size to out_size."""
+    key = (int(in_size), int(out_size), int(filt))
+    hit = _coeff_cache.get(key)
+    if hit is not None:
+        return hit
+    in_size, out_size = key[0], key[1]
+    if in_size < 1 or out_size < 1:
+        raise ValueError(f"resample_coeffs: sizes must be positive, got {in_size} -> {out_size}")
+    scale = in_size / out_size
+    fs = max(scale, 1.0)
+    support = _SUPPORT[filt] * fs
+    ksize = int(math.ceil(support)) * 2 + 1
+    ss = 1.0 / fs
+    center = (np.arange(out_size, dtype=np.float64) + 0.5) * scale
+    xmin = np.maximum((center - support + 0.5).astype(np.int64), 0)          # C's (int) truncates toward zero, as astype does
+    xmax = np.minimum((center + support + 0.5).astype(np.int64), in_size) - xmin
+    w = np.zeros((out_size, ksize), dtype=np.float64)
+    ww = np.zeros(out_size, dtype=np.float64)
+    for t in range(ksize):                                                     # the sum runs over the taps in order, as in C
+        valid = t < xmax
+        wt = np.where(valid, _filter((t + xmin - center + 0.5) * ss, filt), 0.0)
+        w[:, t] = wt
+        ww = ww + wt
+    w = np.where(ww[:, None] != 0.0, w / np.where(ww == 0.0, 1.0, ww)[:, None], w)
+    kk = np.where(w < 0, (-0.5 + w * (1 << PRECISION_BITS)).astype(np.int64), (0.5 + w * (1 << PRECISION_BITS)).astype(np.int64)).astype(np.int32)
+    bounds = np.stack([xmin, xmax], axis=1).astype(np.int32)
+    _coeff_cache[key] = (bounds, kk)
+    return bounds, kk
+
+
+def tile_rows_max(bounds: np.ndarray) -> int:
+    """Most input rows a TILE_ROWS-row output tile reads (the LDS rows of the fused kernel)."""
+    out = bounds.shape[0]
+    y0 = np.arange(0, out, TILE_ROWS)
+    y1 = np.minimum(y0 + TILE_ROWS - 1, out - 1)
+    return int((bounds[y1, 0] + bounds[y1, 1] - bounds[y0, 0]).max())
+
+
+def norm_table(image_mean, image_std, dtype: torch.dtype = torch.float32, rescale_factor: float = 1 / 255.0) -> torch.Tensor:
+    """[3, 256]: channel c of a byte v after SiglipPreprocessor.preprocess and `.to(dtype)`."""
+    x = np.arange(256, dtype=np.uint8).reshape(256, 1).repeat(3, axis=1)
+    x = np.asarray(x, dtype=np.float32) * np.float32(rescale_factor)
+    x = (x - np.asarray(image_mean, dtype=np.float32)) / np.asarray(image_std, dtype=np.float32)
+    return torch.from_numpy(np.ascontiguousarray(x.T)).to(dtype)
+
+
+def _align(v: int, a: int) -> int:
+    return (v + a - 1) // a * a
+
+
+class DevicePreprocessor:
+    """`preprocess_images` of one model configuration on one device.  image_size / pad / brightness as in the wrapper."""
+
+    def __init__(self, size: int, image_mean, image_std, device, dtype: torch.dtype = torch.float32, *, pad: bool = True,
+                 brightness: bool = False, image_size=None, rescale_factor: float = 1 / 255.0):
+        self.device = _lib.require_gpu(device)
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise _lib.VtError(f"DevicePreprocessor: fp32 or bf16 output, got {dtype}")
+        self.S, self.dtype, self.pad, self.brightness, self.image_size = int(size), dtype, bool(pad), bool(brightness), image_size
+        self.mean255 = tuple(int(x * 255) for x in image_mean)
+        self.fill = self.mean255[0] | self.mean255[1] << 8 | self.mean255[2] << 16
+        self.lut = norm_table(image_mean, image_std, dtype, rescale_factor).to(self.device)
+        self.flags = (_lib.IMGPREP_PAD if self.pad else 0) | (_lib.IMGPREP_BRIGHT if self.brightness else 0) | \
+                     (_lib.IMGPREP_OUT_BF16 if dtype == torch.bfloat16 else 0)
+        self.force_two_pass = False           # tests: run the two-launch form where the fused one would do
+        # a missing frame is the S x S fill image; the kernel writes it directly unless a pre-resize or a brightness lift could touch it
+        bg_dark = self.brightness and sum(self.mean255) / (255.0 * 3) <= 0.15
+        self._bg_as_frame = image_size is not None or bg_dark
+        self._bg: Optional[torch.Tensor] = None
+        self._tables: dict = {}               # (in, out, filter) -> (device int32 table, ksize, rows_max)
+        self._plans: dict = {}
+        self._pinned: Optional[torch.Tensor] = None
+        self._pinned_free: Optional[torch.cuda.Event] = None
+        self._upload: Optional[torch.Tensor] = None
+        self._ws: Optional[torch.Tensor] = None
+        self._keepalive: list = []
+
+    # ---- tables
+    def _table(self, in_size: int, out_size: int, filt: int):
+        if in_size == out_size:
+            return None, 0, TILE_ROWS
+        key = (in_size, out_size, filt)
+        hit = self._tables.get(key)
+        if hit is None:
+            b, k = resample_coeffs(in_size, out_size, filt)
+            flat = np.concatenate([b.reshape(-1), k.reshape(-1)]).astype(np.int32)
+            hit = (torch.from_numpy(flat).to(self.device), int(k.shape[1]), tile_rows_max(b))
+            self._tables[key] = hit
+        return hit
+
+    def _background(self) -> torch.Tensor:
+        if self._bg is None:
+            bg = np.ones((self.S, self.S, 3), dtype=np.uint8) * np.array(self.mean255, dtype=np.uint8).reshape(1, 1, 3)
+            self._bg = torch.from_numpy(bg).to(self.device)
+        return self._bg
+
+    # ---- frames
+    def _gather(self, images: Sequence):
+        """-> list of (ptr, h, w, pitch) or None per frame, plus the tensors that must stay alive; host frames go up in one copy."""
+        from PIL import Image
+        items, host, keep = [], [], []
+        for im in images:
+            if im is None:
+                if self._bg_as_frame:
+                    bg = self._background()
+                    items.append((bg.data_ptr(), self.S, self.S, 3 * self.S))
+                else:
+                    items.append(None)
+                continue
+            if isinstance(im, torch.Tensor) and im.is_cuda:
+                if im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3:
+                    raise _lib.VtError(f"device frame must be uint8 [H, W, 3], got {im.dtype} {tuple(im.shape)}")
+                if im.device != self.device:
+                    raise _lib.VtError(f"device frame lives on {im.device}, the preprocessor on {self.device}")
+                h, w = int(im.shape[0]), int(im.shape[1])
+                if not (im.stride(2) == 1 and im.stride(1) == 3 and (h == 1 or im.stride(0) >= 3 * w)):
+                    im = im.contiguous()          # an exotic view: one device copy (allocates)
+                keep.append(im)
+                items.append((im.data_ptr(), h, w, int(im.stride(0)) if h > 1 else 3 * w))
+                continue
+            if isinstance(im, Image.Image):
+                a = np.asarray(im if im.mode == "RGB" else im.convert("RGB"))
+            elif isinstance(im, torch.Tensor):
+                a = im.numpy()
+            else:
+                a = np.asarray(im)
+            if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
+                raise _lib.VtError(f"frame must be uint8 [H, W, 3], got {a.dtype} {a.shape}")
+            host.append((len(items), a))
+            items.append(None)
+        if host:
+            offs, total = [], 0
+            for _, a in host:
+                offs.append(total)
+                total = _align(total + a.size, 16)
+            if self._pinned is None or self._pinned.numel() < total:
+                self._pinned = torch.empty(_align(total * 3 // 2, 4096), dtype=torch.uint8).pin_memory()
+                self._upload = torch.empty(self._pinned.numel(), dtype=torch.uint8, device=self.device)
+                self._pinned_free = None
+            if self._pinned_free is not None:
+                self._pinned_free.synchronize()           # the previous call's copy has left the pinned buffer (waits for that copy only)
+            pin = self._pinned.numpy()
+            for (_, a), o in zip(host, offs):
+                pin[o:o + a.size] = a.reshape(-1)
+            self._upload[:total].copy_(self._pinned[:total], non_blocking=True)
+            self._pinned_free = torch.cuda.Event()
+            self._pinned_free.record(torch.cuda.current_stream(self.device))
+            base = self._upload.data_ptr()
+            for (i, a), o in zip(host, offs):
+                items[i] = (base + o, int(a.shape[0]), int(a.shape[1]), 3 * int(a.shape[1]))
+        return items, keep
+
+    def _resized(self, h: int, w: int) -> Tuple[int, int]:
+        sz = self.image_size
+        if isinstance(sz, int):                           # transforms.Resize(int): shorter side -> sz
+            return (max(1, int(sz * h / w)), sz) if w <= h else (sz, max(1, int(sz * w / h)))
+        return int(sz[0]), int(sz[1])
+
+    # ---- planning: everything that depends only on geometry and addresses
+    def _stage(self, items, flags: int, S: int, out_sizes, filt: int):
+        n = len(items)
+        arr = (_lib.ImgprepFrame * n)()
+        off = 0
+        for i, it in enumerate(items):
+            if it is None:
+                continue
+            ptr, h, w, pitch = it
+            oh, ow = out_sizes[i]
+            ih, iw = (max(h, w), max(h, w)) if flags & _lib.IMGPREP_PAD else (h, w)
+            if ih > 100 * iw and oh < ih:
+                # recent Pillow resizes such a sliver vertically first (Image.resize), older ones do not: there is no single result to match
+                raise _lib.VtError(f"frame of {h} x {w} resized without padding: more than 100 times taller than wide is not supported "
+                                   "on the device (use preprocess_images)")
+            th, kh, _ = self._table(iw, ow, filt)
+            tv, kv, rows = self._table(ih, oh, filt)
+            f = arr[i]
+            f.src, f.pitch, f.h, f.w, f.out_h, f.out_w = ptr, pitch, h, w, oh, ow
+            f.coef_h = th.data_ptr() if th is not None else None
+            f.coef_v = tv.data_ptr() if tv is not None else None
+            f.ksize_h, f.ksize_v, f.rows_max = kh, kv, rows
+            f.out_off = off
+            off += _align(oh * ow * 3, 16)
+        L = _lib.lib()
+        ws_bytes = int(L.vt_imgprep_workspace_bytes(arr, n, S, flags))
+        if ws_bytes == 0:
+            raise _lib.VtError("vt_imgprep_workspace_bytes: " + L.vt_last_error().decode())
+        return arr, ws_bytes, off
+
+    def _plan(self, items, ws_ptr: Optional[int]):
+        key = (tuple(items), ws_ptr, self.force_two_pass)
+        plan = self._plans.get(key)
+        if plan is not None:
+            return plan
+        if len(self._plans) >= 64:                        # plans a captured graph reads (their device tables) are never dropped
+            self._plans = {k: v for k, v in self._plans.items() if v.get("captured")}
+        n = len(items)
+        flags = self.flags | (_lib.IMGPREP_TWO_PASS if self.force_two_pass else 0)
+        plan = {"pre": None}
+        total = 0
+        if self.image_size is not None:                   # step 1: bilinear pre-resize into uint8 frames at the head of the workspace
+            sizes = [self._resized(it[1], it[2]) for it in items]
+            arr1, ws1, out1 = self._stage(items, _lib.IMGPREP_OUT_U8, 0, sizes, BILINEAR)
+            plan["pre"] = {"arr": arr1, "out_off": 0, "ws_off": _align(out1, 256), "ws_bytes": ws1}
+            total = _align(out1, 256) + _align(ws1, 256)
+            mid = [(None, sizes[i][0], sizes[i][1], 3 * sizes[i][1], arr1[i].out_off) for i in range(n)]
+        else:
+            mid = None
+        plan["flags"], plan["main_off"] = flags, total
+        # the main stage's table needs the addresses of the pre-resized frames, i.e. the workspace: sized first with a placeholder base
+        base = ws_ptr if ws_ptr is not None else 4096
+        main_items = items if mid is None else [(base + m[4], m[1], m[2], m[3]) for m in mid]
+        arr2, ws2, _ = self._stage(main_items, flags, self.S, [(self.S, self.S)] * n, BICUBIC)
+        plan["arr"], plan["ws_bytes_main"], plan["ws_bytes"] = arr2, ws2, total + ws2
+        if ws_ptr is not None:
+            plan["dev"] = self._to_device(arr2)
+            if plan["pre"] is not None:
+                plan["pre"]["dev"] = self._to_device(plan["pre"]["arr"])
+        self._plans[key] = plan
+        return plan
+
+    def _to_device(self, arr) -> torch.Tensor:
+        raw = np.frombuffer(bytes(memoryview(arr)), dtype=np.uint8).copy()
+        return torch.from_numpy(raw).to(self.device)
+
+    def workspace_bytes(self, images: Sequence) -> int:
+        """Bytes of workspace a call on these frames needs (geometry only)."""
+        items, _ = self._gather(images)
+        return self._plan(items, None)["ws_bytes"]
+
+    @torch.no_grad()
+    def __call__(self, images: Sequence, out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+        n = len(images)
+        if n < 1:
+            raise _lib.VtError("DevicePreprocessor: no frames")
+        S = self.S
+        with torch.cuda.device(self.device):
+            items, keep = self._gather(images)
+            if workspace is None:
+                need = self._plan(items, None)["ws_bytes"]
+                if self._ws is None or self._ws.numel() < need:
+                    if self._ws is not None and any(v.get("captured") for v in self._plans.values()):
+                        self._keepalive.append(self._ws)          # a captured graph still works in the old one
+                    self._ws = torch.empty(_align(need * 3 // 2, 4096), dtype=torch.uint8, device=self.device)
+                workspace = self._ws
+            elif workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.device != self.device:
+                raise _lib.VtError("workspace must be a contiguous uint8 tensor on the preprocessor's device")
+            plan = self._plan(items, workspace.data_ptr())
+            if torch.cuda.is_current_stream_capturing():
+                plan["captured"] = True
+            if workspace.numel() < plan["ws_bytes"]:
+                raise _lib.VtError(f"workspace of {workspace.numel()} bytes, {plan['ws_bytes']} needed")
+            if out is None:
+                out = torch.empty((n, 3, S, S), dtype=self.dtype, device=self.device)
+            elif out.shape != (n, 3, S, S) or out.dtype != self.dtype or not out.is_contiguous() or out.device != self.device:
+                raise _lib.VtError(f"out must be a contiguous {self.dtype} [{n}, 3, {S}, {S}] tensor on {self.device}")
+            L, st = _lib.lib(), _lib.stream_ptr(self.device)
+            wp = workspace.data_ptr()
+            pre = plan["pre"]
+            if pre is not None:
+                _lib.check(L.vt_imgprep(pre["arr"], _lib.ptr(pre["dev"]), n, 0, None, 0, _lib.IMGPREP_OUT_U8, C.c_void_p(wp + pre["out_off"]),
+                                        C.c_void_p(wp + pre["ws_off"]), pre["ws_bytes"], st), "vt_imgprep (pre-resize)")
+            _lib.check(L.vt_imgprep(plan["arr"], _lib.ptr(plan["dev"]), n, S, _lib.ptr(self.lut), self.fill, plan["flags"], _lib.ptr(out),
+                                    C.c_void_p(wp + plan["main_off"]), plan["ws_bytes_main"], st), "vt_imgprep")
+        return out

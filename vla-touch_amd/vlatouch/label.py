@@ -24,8 +24,11 @@ def encode_frames(model, frames: Sequence, batch: int = 48) -> torch.Tensor:
     from PIL import Image
     out = []
     for i in range(0, len(frames), batch):
-        pil = [None if f is None else (f if isinstance(f, Image.Image) else Image.fromarray(np.asarray(f))) for f in frames[i:i + batch]]
-        px = model.preprocess_images(pil).to(model.device, dtype=model.dtype)
+        if getattr(model, "device_preprocess", False):
+            px = model.preprocess_images_device(list(frames[i:i + batch]))       # raw bytes up in one copy, resized and normalised on the card
+        else:
+            pil = [None if f is None else (f if isinstance(f, Image.Image) else Image.fromarray(np.asarray(f))) for f in frames[i:i + batch]]
+            px = model.preprocess_images(pil).to(model.device, dtype=model.dtype)
         out.append(model.vision_model(px))
     return torch.cat(out, dim=0)
 
