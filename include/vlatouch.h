@@ -399,6 +399,56 @@ int vt_sum_mid(const float* src, long lds, int off, float* out, int B, int T, in
 int vt_mul_(float* a, const float* b, long n, vt_stream_t stream);
 int vt_mse_residual(const float* base, const float* delta, const float* target, float* pred, float* ddelta, float* loss, long n, vt_stream_t stream);
 
+/* ---- RDT fine-tuning step (csrc/vt_train_rdt.hip; vlatouch/rdt_train.py): the backward arithmetic of RDTRunner.compute_loss
+ * (models/rdt_runner.py:168-222) through RDT.forward (models/rdt/model.py:126-165, blocks.py:72-202) and the clip of train/train.py:440-442.
+ * Linears stay vt_gemm calls (data / weight gradients on transposed operands).
+ * vt_attention_bwd: dQ, dK, dV of softmax(q k^T scale [+ key mask]) v (timm Attention / blocks.py:102-138 under autograd), head_dim 64,
+ *   fp32 or bf16 operands with fp32 accumulation.  Q, dO, dQ are [B, Nq, H, 64] and K, V, dK, dV [B, Nk, H, 64] views given by element
+ *   strides (batch, row, head; unit inner stride); kmask [B][km_bs] bytes (0 = key masked) or null.  The probabilities are recomputed; `ws`
+ *   (B * H * Nq * 3 floats, device) receives the row statistics (max, 1 / sum, sum_j P dP).  No atomics: two calls give the same bits.  A query
+ *   row with every key masked gets zero gradients, as a masked key does.
+ * vt_rmsnorm_bwd: backward of vt_rownorm modes 1 / 2 (no bias), x, dy, dx, dyxr [rows][D] fp32; the column sums of dyxr (vt_colsum) are d w.
+ * vt_headnorm_bwd: backward of vt_headnorm: x = the PRE-norm values, dy is overwritten by dx, both at [token * stride + head * 64 + 0..63];
+ *   part [ceil(tokens * heads / 64)][64] partial sums of d w (vt_colsum finishes).
+ * vt_act_bwd: act 2 = GELU(approximate="tanh") (timm Mlp, the adaptors), 3 = SiLU (TimestepEmbedder); dy null: act(x), else dy * act'(x).
+ * vt_ddpm_qsample: DDPMScheduler.add_noise + the token layout of rdt_runner.py:197-204: out [B][horizon + 1][2A] = row 0: state ‖ mask,
+ *   row 1 + r: sqrt(ab_t) action_r + sqrt(1 - ab_t) noise_r ‖ mask; alphas_cumprod [num_train_timesteps] fp32, timesteps [B] int64 (device).
+ * vt_timestep_embed: blocks.py:41-61, out [B][dim] = cos(t f) | sin(t f) over the host's table f [dim / 2] = exp(-ln(10000) j / (dim / 2)).   vt_add_rowvec_: a[r][c] += v[c] (position embeddings).
+ * vt_transpose_pad: [M][N] -> [N][Mp >= M], the padding columns zero (vt_gemm wants its reduction length as a multiple of 4).
+ * vt_grad_clip_multi: torch.nn.utils.clip_grad_norm_ over the table of vt_adamw_ema_multi: chunk_part [total_chunks] scratch,
+ *   norm_coef[0] = the global L2 norm of the gradients before clipping, norm_coef[1] = min(1, max_norm / (norm + 1e-6)), every gradient
+ *   multiplied by it in place.  Nothing is read back by the host.
+ * Activations (x, dy, dx, out, pred, a ...) are of dtype `dt` / `odt`: 0 = fp32, 1 = bf16 storage with fp32 arithmetic; gains, targets and every
+ *   sum (dyxr, part, loss, norm) are fp32.
+ * vt_mse_loss: F.mse_loss and its gradient: loss[0] = mean((pred - target)^2), dpred = 2 (pred - target) / n. */
+typedef struct {
+  const void *Q, *K, *V, *dO;
+  void *dQ, *dK, *dV;
+  float* ws;
+  const unsigned char* kmask;
+  long km_bs;
+  long q_bs, q_rs, q_hs, k_bs, k_rs, k_hs, v_bs, v_rs, v_hs, do_bs, do_rs, do_hs;
+  long dq_bs, dq_rs, dq_hs, dk_bs, dk_rs, dk_hs, dv_bs, dv_rs, dv_hs;
+  int B, H, Nq, Nk, hd, dtype;
+  float scale;
+} VtAttnBwdParams;
+int vt_attention_bwd(const VtAttnBwdParams* params, vt_stream_t stream);
+int vt_rmsnorm_bwd(const void* x, const float* w, const void* dy, void* dx, float* dyxr, int rows, int D, float eps, int mode, int dt, vt_stream_t stream);
+int vt_headnorm_bwd(const void* x, long x_stride, void* dy, long dy_stride, int heads, long tokens, const float* w, float* part, float eps,
+                    int mode, int dt, vt_stream_t stream);
+int vt_act_bwd(const void* x, const void* dy, void* out, long n, int act, int dt, vt_stream_t stream);
+int vt_ddpm_qsample(const float* state, const float* action, const float* noise, const float* mask, const long* timesteps,
+                    const float* alphas_cumprod, int num_train_timesteps, void* out, int odt, int B, int horizon, int action_dim, vt_stream_t stream);
+int vt_timestep_embed(const float* t, const float* freqs, void* out, int odt, int B, int dim, vt_stream_t stream);
+int vt_add_rowvec_(void* a, int dt, const float* v, long rows, long cols, vt_stream_t stream);
+int vt_transpose_pad(const void* in, void* out, int dt, int M, int N, int Mp, vt_stream_t stream);
+/* vt_colsum / vt_add_ / vt_copy_cols (fp32 only, above) for an activation dtype `dt` (0 fp32, 1 bf16): column sums in fp32, a += b, dst[:, doff..] = src[:, off..] */
+int vt_colsum_dt(const void* x, int dt, long ld, float* out, int M, int N, vt_stream_t stream);
+int vt_add_dt(void* a, const void* b, long n, int dt, vt_stream_t stream);
+int vt_copy_cols_dt(const void* src, long lds, long off, void* dst, long ldd, long doff, long rows, long cols, int dt, vt_stream_t stream);
+int vt_grad_clip_multi(const void* table, int ntensors, long total_chunks, float max_norm, float* chunk_part, float* norm_coef, vt_stream_t stream);
+int vt_mse_loss(const void* pred, const float* target, void* dpred, float* loss, long n, int dt, vt_stream_t stream);
+
 /* ---- camera frames -> SigLIP pixel_values (scripts/franka_model_eef.py:242-288: RoboticDiffusionTransformerModel.preprocess_images + the
  * `.to(device, dtype)` of step(); SiglipImageProcessor.preprocess).  Bit-identical to that PIL path: optional brightness lift
  * (v' = min(255, (int)(1.75f * v)) when sum / (h * w * 255.0 * 3) <= 0.15, decided on the device), pad to a square with `fill_rgb` (never

@@ -1,0 +1,140 @@
+#!/usr/bin/env python
+"""Wall time and memory of the RDT fine-tuning step (vlatouch/rdt_train.py) at RDT-1B dimensions (bench.py's RDT config: hidden 2048, depth 28,
+32 heads, horizon 64, 4 374 image tokens, 32 language tokens, synthetic weights) -> profiles/rdt_train_bench.json.
+
+Default: `precision="bf16"` (the reference's execution dtype), batch 4 (main.py:54) and batch 32, 3 warm-up + 10 timed steps on one repeated
+batch, device-synchronised wall time split into forward (get_loss without backward), backward, and clip + AdamW + EMA; peak device memory; the
+loss of every timed step (it must fall on a repeated batch); algorithmic FLOPs per step from the shapes (3 x the forward's 2 x MAC count of the
+Linears and attention products, no K/V cache credit) and the share of the bf16 MFMA peak they give as a WHOLE-STEP rate, not a kernel's.
+Yardstick only: `loss.backward()` of the oracle (tests/rdt_train_ref.loss_fn, plain torch) on the same GPU in bf16 at the first batch size, and
+the ratio; if it does not run, the field says "not measured" and why.
+    python tools/rdt_train_bench.py [--precision bf16] [--batch 4 32] [--depth 28] [--steps 10] [--out profiles/rdt_train_bench.json]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "vla-touch_amd")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+from vlatouch import synth  # noqa: E402
+
+
+def forward_macs(c: dict, B: int, lang_len: int) -> float:
+    """Multiply-accumulates of one forward of compute_loss (Linears + attention products), from the shapes."""
+    D, N, Li, A = c["hidden"], c["horizon"] + 3, c["img_cond_len"], c["action_dim"]
+    M = B * N
+    macs = B * lang_len * (c["lang_token_dim"] * D + D * D) + B * Li * (c["img_token_dim"] * D + D * D)
+    macs += B * (c["horizon"] + 1) * (2 * A * D + 2 * D * D) + 2 * B * (256 * D + D * D)
+    for i in range(c["depth"]):
+        Lc = lang_len if i % 2 == 0 else Li
+        macs += M * D * 3 * D + 2 * B * N * N * D + M * D * D                      # self-attention
+        macs += M * D * D + B * Lc * D * 2 * D + 2 * B * N * Lc * D + M * D * D    # cross-attention
+        macs += 2 * M * D * D                                                      # FFN
+    return float(macs + M * D * D + M * D * A)
+
+
+PEAK_BF16_FLOPS = 16 * 157.3e12   # MI355X dense bf16 MFMA peak (16 x the 157.3 TFLOP/s fp32 matrix rate), for the whole-step share only
+
+
+def yardstick(sd, c, args, kw, dev):
+    """forward + loss.backward() of the oracle under torch autograd on this GPU in bf16 (1 warm-up + 3 timed) -> dict, or "not measured: why"."""
+    try:
+        from tests import rdt_train_ref as R
+        keys = ("lang_tokens", "lang_attn_mask", "img_tokens", "state_tokens", "action_gt", "action_mask", "ctrl_freqs")
+        b = dict(zip(keys, args), **kw)
+        cfg = dict(heads=c["heads"], horizon=c["horizon"])
+        leaves = R.leaf_sd(sd, torch.bfloat16)
+        ts = []
+        with torch.device(dev), torch.enable_grad():
+            for n in range(4):
+                for v in leaves.values():
+                    v.grad = None
+                torch.cuda.synchronize(dev); t0 = time.perf_counter()
+                loss = R.loss_fn(leaves, b, cfg, dtype=torch.bfloat16)
+                loss.backward()
+                torch.cuda.synchronize(dev); ts.append(time.perf_counter() - t0)
+        return {"what": "oracle forward + loss.backward() under torch autograd, bf16, same GPU", "fwd_bwd_ms": 1e3 * min(ts[1:]), "loss": float(loss.detach())}
+    except Exception as e:                       # a yardstick only: record why it did not run
+        return f"not measured: {type(e).__name__}: {str(e)[:200]}"
+    finally:
+        torch.cuda.empty_cache()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, nargs="+", default=[4, 32])
+    ap.add_argument("--precision", default="bf16", choices=["fp32", "bf16"])
+    ap.add_argument("--no-yardstick", action="store_true")
+    ap.add_argument("--depth", type=int, default=28)
+    ap.add_argument("--hidden", type=int, default=2048)
+    ap.add_argument("--img-len", type=int, default=4374)
+    ap.add_argument("--lang-len", type=int, default=32)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--lr", type=float, default=1e-4)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rdt_train_bench.json"))
+    a = ap.parse_args()
+    from vlatouch.rdt_train import RdtTrainer
+    dev = torch.device("cuda:0")
+    c = dict(hidden=a.hidden, depth=a.depth, heads=a.hidden // 64, horizon=64, action_dim=128, lang_token_dim=4096, img_token_dim=1152,
+             state_token_dim=128, max_lang_cond_len=1024, img_cond_len=a.img_len)
+    sd = synth.fill_state_dict_device(synth.rdt_runner_shapes(**c), dev, torch.float32, seed=7)
+    params = sum(v.numel() for v in sd.values())
+    rec = {"config": c, "precision": a.precision, "parameters": params, "lang_len": a.lang_len, "warmup": a.warmup, "steps": a.steps, "lr": a.lr,
+           "device": torch.cuda.get_device_name(dev), "runs": []}
+    sync = lambda: torch.cuda.synchronize(dev)
+    for B in a.batch:
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats(dev)
+        tr = RdtTrainer(sd, heads=c["heads"], horizon=64, action_dim=128, lr=a.lr, precision=a.precision, device=dev)
+        g = torch.Generator(device=dev).manual_seed(99)
+        rn = lambda *s: torch.randn(*s, generator=g, device=dev)
+        amask = torch.zeros(B, 1, 128, device=dev)
+        amask[:, :, :10] = 1.0
+        args = (rn(B, a.lang_len, 4096), torch.ones(B, a.lang_len, dtype=torch.bool, device=dev), rn(B, a.img_len, 1152), rn(B, 1, 128),
+                torch.tanh(rn(B, 64, 128)) * amask, amask, torch.full((B,), 10.0, device=dev))
+        kw = dict(noise=rn(B, 64, 128), timesteps=torch.randint(0, 1000, (B,), generator=g, device=dev))
+        t_f = t_fb = t_o = 0.0
+        losses = []
+        for n in range(a.warmup + a.steps):
+            sync(); t0 = time.perf_counter()
+            tr.get_loss(*args, backward=False, **kw)
+            sync(); t1 = time.perf_counter()
+            loss = tr.get_loss(*args, **kw)
+            sync(); t2 = time.perf_counter()
+            tr.optimizer_step()
+            sync(); t3 = time.perf_counter()
+            if n >= a.warmup:
+                t_f, t_fb, t_o = t_f + t1 - t0, t_fb + t2 - t1, t_o + t3 - t2
+                losses.append(float(loss))
+        k = 1e3 / a.steps
+        flops = 3 * 2 * forward_macs(c, B, a.lang_len)
+        step_ms = (t_fb + t_o) * k
+        run = {"batch": B, "forward_ms": t_f * k, "backward_ms": (t_fb - t_f) * k, "clip_adamw_ema_ms": t_o * k, "step_ms": step_ms,
+               "samples_per_s": B / (step_ms / 1e3), "peak_memory_gib": torch.cuda.max_memory_allocated(dev) / 2 ** 30,
+               "algorithmic_tflop_per_step": flops / 1e12, "whole_step_tflops": flops / (step_ms / 1e3) / 1e12,
+               "losses": losses, "loss_decreases": bool(losses[-1] < losses[0]), "grad_norm_last": float(tr.grad_norm),
+               "share_of_bf16_mfma_peak": flops / (step_ms / 1e3) / PEAK_BF16_FLOPS if a.precision == "bf16" else None}
+        del tr
+        if B == a.batch[0]:
+            run["torch_autograd_yardstick"] = "not measured: --no-yardstick" if a.no_yardstick else yardstick(sd, c, args, kw, dev)
+            if isinstance(run["torch_autograd_yardstick"], dict):
+                run["torch_autograd_yardstick"]["ratio_torch_over_this"] = run["torch_autograd_yardstick"]["fwd_bwd_ms"] / ((t_fb) * k)
+        print(json.dumps(run))
+        rec["runs"].append(run)
+    with open(a.out, "w") as f:
+        json.dump(rec, f, indent=1)
+    print("wrote", a.out)
+
+
+if __name__ == "__main__":
+    main()

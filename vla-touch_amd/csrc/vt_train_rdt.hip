@@ -1,0 +1,459 @@
+// vt_train_rdt.hip — backward arithmetic of the RDT fine-tuning step (VLA/train/train.py:404-448, RDTRunner.compute_loss
+// models/rdt_runner.py:168-222): what the forward primitives and csrc/vt_train.hip do not already provide to differentiate an RDT block
+// and to clip its gradients.  Every Linear of the step (forward, data gradient, weight gradient) stays a vt_gemm call; the kernels here are
+//   * attention backward with recomputed probabilities (no stored P, no floating-point atomics: bit-reproducible),
+//   * RMSNorm / per-head RMSNorm backward in both timm forms (vt_rownorm modes 1 and 2),
+//   * tanh-GELU / SiLU and their derivatives on libm functions (gradients are not the place for the ~1 ulp shortcuts of the epilogues),
+//   * the DDPM forward process written into the state ‖ noisy-action ‖ mask token layout, the sinusoidal timestep embedding,
+//   * global-norm gradient clipping over the multi-tensor table vt_adamw_ema_multi reads,
+//   * a zero-padding transpose (the weight-gradient products reduce over the token count, which vt_gemm wants as a multiple of 4 / 8),
+//   * dtype-typed column sum / add / column copy for the bf16 mode (the helpers of vt_train.hip are fp32 only).
+// A wave owns one query row (dQ) or one key row (dK, dV) with lane = head-dim element (head_dim 64 = the wave width), so every sum has a
+// fixed order.  These are fp32 VALU kernels with one wave reduction per (query, key) pair: correct and reproducible, not fast — at RDT-1B size
+// the two attention-backward kernels are 40 % of the fp32 step's kernel time and 65 % of the bf16 step's (profiles/rdt_train_kernels*.txt), almost all of it the 4 374-key image
+// cross-attention, so an MFMA tile for that case is the first thing to build next.
+#include <math.h>
+#include "vt_common.h"
+#include "vt_host.h"
+#include "../../include/vlatouch.h"
+
+namespace {
+
+inline dim3 g1(long n) { return dim3((unsigned)((n + 255) / 256)); }
+
+// ------------------------------------------------------------------------------------------------ attention backward
+// Pass 1 + dQ: one wave per (b, h, query row i).  Online softmax statistics over the keys give m_i (row max), 1 / l_i and
+// delta_i = sum_j P_ij dP_ij (dP_ij = dO_i . v_j); they are written to ws[(b, h, i)][3] for the dK / dV kernel, then a second walk over
+// the keys accumulates dQ_i = scale * sum_j P_ij (dP_ij - delta_i) k_j.  A row whose keys are all masked gets m = 0, 1 / l = 0: P = 0.
+template <typename T>
+__global__ __launch_bounds__(256) void attn_bwd_dq_kernel(VtAttnBwdParams p) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const long row = (long)blockIdx.x * 4 + wv;                 // (b * H + h) * Nq + i
+  const long rows = (long)p.B * p.H * p.Nq;
+  if (row >= rows) return;                                     // whole wave leaves together
+  const int i = (int)(row % p.Nq);
+  const long bh = row / p.Nq;
+  const int h = (int)(bh % p.H), b = (int)(bh / p.H);
+  const T* q = (const T*)p.Q + (long)b * p.q_bs + (long)i * p.q_rs + (long)h * p.q_hs;
+  const T* go = (const T*)p.dO + (long)b * p.do_bs + (long)i * p.do_rs + (long)h * p.do_hs;
+  const T* kb = (const T*)p.K + (long)b * p.k_bs + (long)h * p.k_hs;
+  const T* vb = (const T*)p.V + (long)b * p.v_bs + (long)h * p.v_hs;
+  const unsigned char* km = p.kmask ? p.kmask + (long)b * p.km_bs : nullptr;
+  const float qd = ldf<T>(q, lane) * p.scale, gd = ldf<T>(go, lane);
+  float m = -INFINITY, l = 0.f, acc = 0.f;
+  for (int j = 0; j < p.Nk; ++j) {
+    if (km && !km[j]) continue;                                // uniform over the wave
+    const float s = wave_sum(qd * ldf<T>(kb + (long)j * p.k_rs, lane));
+    const float dp = wave_sum(gd * ldf<T>(vb + (long)j * p.v_rs, lane));
+    const float mn = fmaxf(m, s);
+    const float c = expf(m - mn), e = expf(s - mn);            // first key: m = -inf -> c = 0
+    l = l * c + e;
+    acc = acc * c + e * dp;
+    m = mn;
+  }
+  const float inv_l = l > 0.f ? 1.0f / l : 0.f;
+  if (!(l > 0.f)) m = 0.f;
+  const float delta = acc * inv_l;
+  if (lane == 0) { float* w = p.ws + row * 3; w[0] = m; w[1] = inv_l; w[2] = delta; }
+  float dq = 0.f;
+  for (int j = 0; j < p.Nk; ++j) {
+    if (km && !km[j]) continue;
+    const float kd = ldf<T>(kb + (long)j * p.k_rs, lane);
+    const float s = wave_sum(qd * kd);
+    const float dp = wave_sum(gd * ldf<T>(vb + (long)j * p.v_rs, lane));
+    const float pr = expf(s - m) * inv_l;
+    dq += pr * (dp - delta) * kd;
+  }
+  stf<T>((T*)p.dQ + (long)b * p.dq_bs + (long)i * p.dq_rs + (long)h * p.dq_hs, lane, dq * p.scale);
+}
+
+// dK, dV: one wave per (b, h, key j), walking the query rows with the statistics of the kernel above:
+//   dV_j = sum_i P_ij dO_i,  dK_j = scale * sum_i P_ij (dP_ij - delta_i) q_i.   A masked key gets zeros.
+template <typename T>
+__global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(VtAttnBwdParams p) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int j = blockIdx.x * 4 + wv;
+  if (j >= p.Nk) return;
+  const int h = blockIdx.y % p.H, b = blockIdx.y / p.H;
+  const bool live = !(p.kmask && !p.kmask[(long)b * p.km_bs + j]);
+  const float kd = ldf<T>((const T*)p.K + (long)b * p.k_bs + (long)j * p.k_rs + (long)h * p.k_hs, lane);
+  const float vd = ldf<T>((const T*)p.V + (long)b * p.v_bs + (long)j * p.v_rs + (long)h * p.v_hs, lane);
+  const T* qb = (const T*)p.Q + (long)b * p.q_bs + (long)h * p.q_hs;
+  const T* gb = (const T*)p.dO + (long)b * p.do_bs + (long)h * p.do_hs;
+  const float* ws = p.ws + ((long)b * p.H + h) * p.Nq * 3;
+  float dk = 0.f, dv = 0.f;
+  if (live) {
+    for (int i = 0; i < p.Nq; ++i) {
+      const float qd = ldf<T>(qb + (long)i * p.q_rs, lane), gd = ldf<T>(gb + (long)i * p.do_rs, lane);
+      const float s = wave_sum(qd * kd) * p.scale;
+      const float dp = wave_sum(gd * vd);
+      const float pr = expf(s - ws[i * 3]) * ws[i * 3 + 1];
+      dv += pr * gd;
+      dk += pr * (dp - ws[i * 3 + 2]) * qd;
+    }
+  }
+  stf<T>((T*)p.dK + (long)b * p.dk_bs + (long)j * p.dk_rs + (long)h * p.dk_hs, lane, dk * p.scale);
+  stf<T>((T*)p.dV + (long)b * p.dv_bs + (long)j * p.dv_rs + (long)h * p.dv_hs, lane, dv);
+}
+
+// ------------------------------------------------------------------------------------------------ RMSNorm backward
+// y = x r w with r = rsqrt(v + eps); mode 1: v = mean(x^2); mode 2: v = sum (x - mean)^2 / (D - 1)  (timm <= 1.0.8).  With g = dy w:
+//   mode 1: dx = r g - r^3 <g, x> x / D          mode 2: dx = r g - r^3 <g, x> (x - mean) / (D - 1)
+// One block per row.  dyxr (fp32) = dy x r, whose column sums are d w (vt_colsum finishes, as after vt_ln_bwd).
+// Every element-wise kernel below is typed on the activation type T (fp32, or bf16 storage with fp32 arithmetic and one rounding at the store).
+__device__ __forceinline__ float block_sum4(float t, float* red) {
+  t = wave_sum(t);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = t;
+  __syncthreads();
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
+template <typename T>
+__global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const T* __restrict__ x, const float* __restrict__ w, const T* __restrict__ dy,
+                                                          T* __restrict__ dx, float* __restrict__ dyxr, int D, float eps, int mode) {
+  __shared__ float red[4];
+  const long base = (long)blockIdx.x * D;
+  float s1 = 0.f, s2 = 0.f;
+  for (int c = threadIdx.x; c < D; c += 256) { const float v = ldf<T>(x, base + c); s1 += v; s2 += v * v; }
+  float mean = 0.f, var;
+  if (mode == 2) {
+    mean = block_sum4(s1, red) / (float)D;
+    float q = 0.f;
+    for (int c = threadIdx.x; c < D; c += 256) { const float d = ldf<T>(x, base + c) - mean; q += d * d; }
+    var = block_sum4(q, red) / (float)(D - 1);
+  } else {
+    var = block_sum4(s2, red) / (float)D;
+  }
+  const float r = rsqrtf(var + eps);
+  float gx = 0.f;
+  for (int c = threadIdx.x; c < D; c += 256) gx += ldf<T>(dy, base + c) * w[c] * ldf<T>(x, base + c);
+  const float k = block_sum4(gx, red) * r * r * r / (float)(mode == 2 ? D - 1 : D);
+  for (int c = threadIdx.x; c < D; c += 256) {
+    const float xv = ldf<T>(x, base + c), dv = ldf<T>(dy, base + c);
+    stf<T>(dx, base + c, r * dv * w[c] - k * (xv - mean));
+    dyxr[base + c] = dv * xv * r;
+  }
+}
+
+// The same over 64-wide head slices: x (pre-norm) and dy (overwritten by dx) live at [token * stride + head * 64 + lane].  A block takes 64
+// consecutive (token, head) pairs, 16 per wave; lane d keeps d w[d] of its pairs, the four waves are added in a fixed order into
+// part[block][64] (vt_colsum finishes).
+template <typename T>
+__global__ __launch_bounds__(256) void headnorm_bwd_kernel(const T* __restrict__ x, long x_stride, T* __restrict__ dy, long dy_stride, int heads,
+                                                           long pairs, const float* __restrict__ w, float* __restrict__ part, float eps, int mode) {
+  __shared__ float red[4][64];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const float wd = w[lane];
+  float dw = 0.f;
+  for (int it = 0; it < 16; ++it) {
+    const long pr = (long)blockIdx.x * 64 + wv * 16 + it;
+    if (pr >= pairs) break;
+    const long tok = pr / heads;
+    const int hh = (int)(pr - tok * heads);
+    const float xv = ldf<T>(x, tok * x_stride + hh * 64 + lane);
+    const long di = tok * dy_stride + hh * 64 + lane;
+    const float dv = ldf<T>(dy, di);
+    float mean = 0.f, var;
+    if (mode == 2) {
+      mean = wave_sum(xv) * (1.0f / 64.0f);
+      const float d = xv - mean;
+      var = wave_sum(d * d) * (1.0f / 63.0f);
+    } else {
+      var = wave_sum(xv * xv) * (1.0f / 64.0f);
+    }
+    const float r = rsqrtf(var + eps);
+    const float k = wave_sum(dv * wd * xv) * r * r * r * (mode == 2 ? 1.0f / 63.0f : 1.0f / 64.0f);
+    stf<T>(dy, di, r * dv * wd - k * (xv - mean));
+    dw += dv * xv * r;
+  }
+  red[wv][lane] = dw;
+  __syncthreads();
+  if (wv == 0) part[(long)blockIdx.x * 64 + lane] = (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]);
+}
+
+// ------------------------------------------------------------------------------------------------ activations
+__device__ __forceinline__ void gelu_tanh_fd(float x, float& y, float& d) {     // timm Mlp / adaptor GELU(approximate="tanh")
+  const float c = 0.7978845608028654f, a = 0.044715f;
+  const float t = tanhf(c * (x + a * x * x * x));
+  y = 0.5f * x * (1.0f + t);
+  d = 0.5f * (1.0f + t) + 0.5f * x * (1.0f - t * t) * c * (1.0f + 3.0f * a * x * x);
+}
+__device__ __forceinline__ void silu_fd(float x, float& y, float& d) {          // TimestepEmbedder nn.SiLU
+  const float s = 1.0f / (1.0f + expf(-x));
+  y = x * s;
+  d = s * (1.0f + x * (1.0f - s));
+}
+template <typename T>
+__global__ void act_kernel(const T* __restrict__ x, const T* __restrict__ dy, T* __restrict__ out, long n, int act) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  float y, d;
+  if (act == VT_ACT_SILU) silu_fd(ldf<T>(x, i), y, d); else gelu_tanh_fd(ldf<T>(x, i), y, d);
+  stf<T>(out, i, dy ? ldf<T>(dy, i) * d : y);
+}
+
+// ------------------------------------------------------------------------------------------------ DDPM forward process + token layout
+// out [B][horizon + 1][2A]: row 0 = state ‖ mask, row 1 + r = (sqrt(ab_t) a_r + sqrt(1 - ab_t) eps_r) ‖ mask   (rdt_runner.py:197-204,
+// DDPMScheduler.add_noise); ab = alphas_cumprod [T] fp32, t [B] int64 (clamped into the table).
+template <typename T>
+__global__ void ddpm_qsample_kernel(const float* __restrict__ state, const float* __restrict__ action, const float* __restrict__ noise,
+                                    const float* __restrict__ mask, const long* __restrict__ t, const float* __restrict__ ab, int Tn,
+                                    T* __restrict__ out, int B, int horizon, int A) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  const long per = (long)(horizon + 1) * 2 * A;
+  if (i >= (long)B * per) return;
+  const int b = (int)(i / per);
+  const long e = i - (long)b * per;
+  const int r = (int)(e / (2 * A)), c = (int)(e - (long)r * 2 * A);
+  float v;
+  if (c >= A) v = mask[(long)b * A + c - A];
+  else if (r == 0) v = state[(long)b * A + c];
+  else {
+    long tt = t[b];
+    tt = tt < 0 ? 0 : (tt >= Tn ? Tn - 1 : tt);
+    const float a = ab[tt];
+    const long k = ((long)b * horizon + r - 1) * A + c;
+    v = sqrtf(a) * action[k] + sqrtf(1.0f - a) * noise[k];
+  }
+  stf<T>(out, i, v);
+}
+
+// TimestepEmbedder.timestep_embedding (blocks.py:41-61): out[b] = [cos(t_b f_j) | sin(t_b f_j)], f_j = exp(-ln(max_period) j / half) from the
+// host's table (an angle of up to 1000 rad turns one ulp of f_j into 6e-5 of the embedding, so the table is the one torch computes)
+template <typename T>
+__global__ void timestep_embed_kernel(const float* __restrict__ t, const float* __restrict__ freqs, T* __restrict__ out, int B, int dim) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= B * dim) return;
+  const int b = i / dim, j = i - b * dim, half = dim / 2;
+  const int jj = j < half ? j : j - half;
+  const float a = t[b] * freqs[jj];
+  stf<T>(out, i, j < half ? cosf(a) : sinf(a));
+}
+
+// a[r][c] += v[c]: a position embedding (fp32 parameter) added to every sample
+template <typename T>
+__global__ void add_rowvec_kernel(T* __restrict__ a, const float* __restrict__ v, long rows, long cols) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i < rows * cols) stf<T>(a, i, ldf<T>(a, i) + v[i % cols]);
+}
+
+// [M][N] -> [N][Mp], columns M .. Mp-1 zero
+template <typename T>
+__global__ void transpose_pad_kernel(const T* __restrict__ in, T* __restrict__ out, int M, int N, int Mp) {
+  __shared__ float tile[32][33];
+  const int n0 = blockIdx.x * 32, m0 = blockIdx.y * 32;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  for (int r = ty; r < 32; r += 8) { const int m = m0 + r, n = n0 + tx; tile[r][tx] = (m < M && n < N) ? ldf<T>(in, (long)m * N + n) : 0.f; }
+  __syncthreads();
+  for (int r = ty; r < 32; r += 8) { const int n = n0 + r, m = m0 + tx; if (n < N && m < Mp) stf<T>(out, (long)n * Mp + m, tile[tx][r]); }
+}
+
+// 16-bit-capable forms of vt_colsum / vt_add_ / vt_copy_cols (csrc/vt_train.hip, fp32 only): same orders of summation, typed loads
+template <typename T>
+__global__ __launch_bounds__(1024) void colsum_t_kernel(const T* __restrict__ x, long ld, float* __restrict__ out, int M, int N) {
+  __shared__ float part[32][33];
+  const int c = threadIdx.x & 31, r = threadIdx.x >> 5;
+  const int n = blockIdx.x * 32 + c;
+  float s0 = 0.f, s1 = 0.f;
+  if (n < N) {
+    int m = r;
+    for (; m + 32 < M; m += 64) { s0 += ldf<T>(x, (long)m * ld + n); s1 += ldf<T>(x, (long)(m + 32) * ld + n); }
+    if (m < M) s0 += ldf<T>(x, (long)m * ld + n);
+  }
+  part[r][c] = s0 + s1;
+  __syncthreads();
+  for (int h = 16; h > 0; h >>= 1) {
+    if (r < h) part[r][c] += part[r + h][c];
+    __syncthreads();
+  }
+  if (r == 0 && n < N) out[n] = part[0][c];
+}
+template <typename T>
+__global__ void add_t_kernel(T* __restrict__ a, const T* __restrict__ b, long n) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) stf<T>(a, i, ldf<T>(a, i) + ldf<T>(b, i));
+}
+template <typename T>
+__global__ void copy_cols_t_kernel(const T* __restrict__ src, long lds_, long off, T* __restrict__ dst, long ldd, long doff, long rows, long cols) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= rows * cols) return;
+  const long c = i % cols, m = i / cols;
+  dst[m * ldd + doff + c] = src[m * lds_ + off + c];
+}
+
+// ------------------------------------------------------------------------------------------------ global-norm clipping
+// The table is vt_adamw_ema_multi's: tab[k] = {p, g, m, v, shadow, n, first_chunk}; a block takes one 4096-element chunk of one gradient.
+struct MtEntry { float* p; float* g; float* m; float* v; float* shadow; long n; long first_chunk; };
+__device__ __forceinline__ MtEntry mt_find(const MtEntry* tab, int ntensors, long chunk) {
+  int lo = 0, hi = ntensors - 1;
+  while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (tab[mid].first_chunk <= chunk) lo = mid; else hi = mid - 1; }
+  return tab[lo];
+}
+__global__ __launch_bounds__(256) void sumsq_mt_kernel(const MtEntry* __restrict__ tab, int ntensors, float* __restrict__ part) {
+  __shared__ float red[4];
+  const MtEntry e = mt_find(tab, ntensors, blockIdx.x);
+  const long base = ((long)blockIdx.x - e.first_chunk) * 4096;
+  float s = 0.f;
+  for (int it = 0; it < 16; ++it) {
+    const long i = base + it * 256 + threadIdx.x;
+    if (i < e.n) { const float v = e.g[i]; s += v * v; }
+  }
+  s = block_sum4(s, red);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+// one block: norm = sqrt(sum of the chunk partials, fixed order), coef = min(1, max_norm / (norm + 1e-6))  (torch clip_grad_norm_)
+__global__ __launch_bounds__(256) void clip_coef_kernel(const float* __restrict__ part, long nchunks, float max_norm, float* __restrict__ out2) {
+  __shared__ float red[4];
+  float s = 0.f;
+  for (long i = threadIdx.x; i < nchunks; i += 256) s += part[i];
+  s = block_sum4(s, red);
+  if (threadIdx.x == 0) {
+    const float norm = sqrtf(s);
+    out2[0] = norm;
+    out2[1] = fminf(1.0f, max_norm / (norm + 1e-6f));
+  }
+}
+__global__ __launch_bounds__(256) void scale_mt_kernel(const MtEntry* __restrict__ tab, int ntensors, const float* __restrict__ norm_coef) {
+  const MtEntry e = mt_find(tab, ntensors, blockIdx.x);
+  const long base = ((long)blockIdx.x - e.first_chunk) * 4096;
+  const float c = norm_coef[1];
+  if (c >= 1.0f) return;                                       // torch multiplies by a coefficient clamped to 1: the same values
+  for (int it = 0; it < 16; ++it) {
+    const long i = base + it * 256 + threadIdx.x;
+    if (i < e.n) e.g[i] *= c;
+  }
+}
+
+// mean squared error of pred against target (fp32) and its gradient: loss = mean((pred - target)^2), dpred = 2 (pred - target) / n; one block
+template <typename T>
+__global__ __launch_bounds__(256) void mse_kernel(const T* __restrict__ pred, const float* __restrict__ tgt, T* __restrict__ dpred,
+                                                  float* __restrict__ loss, long n) {
+  __shared__ float red[4];
+  float s = 0.f;
+  const float k = 2.0f / (float)n;
+  for (long i = threadIdx.x; i < n; i += 256) {
+    const float d = ldf<T>(pred, i) - tgt[i];
+    s += d * d;
+    stf<T>(dpred, i, k * d);
+  }
+  s = block_sum4(s, red);
+  if (threadIdx.x == 0) loss[0] = s / (float)n;
+}
+
+}  // namespace
+
+#define LAUNCH_OK() (vt_check_launch())
+// launch KERNEL<float> or KERNEL<bf16_t> by the activation dtype code `dt` (void* arguments are cast by the CAST macro at the call site)
+#define BAD_DT(name) vt_fail(VT_ERR_UNSUPPORTED, name ": activation dtype must be fp32 (0) or bf16 (1)")
+
+int vt_attention_bwd(const VtAttnBwdParams* p, vt_stream_t s) {
+  if (!p) return vt_fail(VT_ERR_ARG, "vt_attention_bwd: null params");
+  if (!p->Q || !p->K || !p->V || !p->dO || !p->dQ || !p->dK || !p->dV || !p->ws) return vt_fail(VT_ERR_ARG, "vt_attention_bwd: null pointer");
+  if (p->B < 1 || p->H < 1 || p->Nq < 1 || p->Nk < 1 || p->hd != 64) return vt_fail(VT_ERR_ARG, "vt_attention_bwd: bad shape (head_dim must be 64)");
+  if ((long)p->B * p->H > 65535) return vt_fail(VT_ERR_ARG, "vt_attention_bwd: B * H > 65535");
+  if (p->kmask && p->km_bs < p->Nk) return vt_fail(VT_ERR_ARG, "vt_attention_bwd: key mask row shorter than Nk");
+  const long rows = (long)p->B * p->H * p->Nq;
+  const dim3 gq((unsigned)((rows + 3) / 4)), gk((unsigned)((p->Nk + 3) / 4), (unsigned)(p->B * p->H));
+  if (p->dtype == VT_F32) {
+    hipLaunchKernelGGL(attn_bwd_dq_kernel<float>, gq, dim3(256), 0, (hipStream_t)s, *p);
+    hipLaunchKernelGGL(attn_bwd_dkv_kernel<float>, gk, dim3(256), 0, (hipStream_t)s, *p);
+  } else if (p->dtype == VT_BF16) {
+    hipLaunchKernelGGL(attn_bwd_dq_kernel<bf16_t>, gq, dim3(256), 0, (hipStream_t)s, *p);
+    hipLaunchKernelGGL(attn_bwd_dkv_kernel<bf16_t>, gk, dim3(256), 0, (hipStream_t)s, *p);
+  } else {
+    return vt_fail(VT_ERR_UNSUPPORTED, "vt_attention_bwd: fp32 or bf16 operands");
+  }
+  return LAUNCH_OK();
+}
+int vt_rmsnorm_bwd(const void* x, const float* w, const void* dy, void* dx, float* dyxr, int rows, int D, float eps, int mode, int dt, vt_stream_t s) {
+  if (!x || !w || !dy || !dx || !dyxr || rows < 1 || D < 2 || (mode != 1 && mode != 2)) return vt_fail(VT_ERR_ARG, "vt_rmsnorm_bwd: bad argument");
+  if (dt == VT_F32) hipLaunchKernelGGL(rmsnorm_bwd_kernel<float>, dim3(rows), dim3(256), 0, (hipStream_t)s, (const float*)x, w, (const float*)dy, (float*)dx, dyxr, D, eps, mode);
+  else if (dt == VT_BF16) hipLaunchKernelGGL(rmsnorm_bwd_kernel<bf16_t>, dim3(rows), dim3(256), 0, (hipStream_t)s, (const bf16_t*)x, w, (const bf16_t*)dy, (bf16_t*)dx, dyxr, D, eps, mode);
+  else return BAD_DT("vt_rmsnorm_bwd");
+  return LAUNCH_OK();
+}
+int vt_headnorm_bwd(const void* x, long x_stride, void* dy, long dy_stride, int heads, long tokens, const float* w, float* part, float eps, int mode,
+                    int dt, vt_stream_t s) {
+  if (!x || !dy || !w || !part || heads < 1 || tokens < 1 || x_stride < (long)heads * 64 || dy_stride < (long)heads * 64 || (mode != 1 && mode != 2))
+    return vt_fail(VT_ERR_ARG, "vt_headnorm_bwd: bad argument");
+  const long pairs = tokens * heads;
+  const dim3 g((unsigned)((pairs + 63) / 64));
+  if (dt == VT_F32) hipLaunchKernelGGL(headnorm_bwd_kernel<float>, g, dim3(256), 0, (hipStream_t)s, (const float*)x, x_stride, (float*)dy, dy_stride, heads, pairs, w, part, eps, mode);
+  else if (dt == VT_BF16) hipLaunchKernelGGL(headnorm_bwd_kernel<bf16_t>, g, dim3(256), 0, (hipStream_t)s, (const bf16_t*)x, x_stride, (bf16_t*)dy, dy_stride, heads, pairs, w, part, eps, mode);
+  else return BAD_DT("vt_headnorm_bwd");
+  return LAUNCH_OK();
+}
+int vt_act_bwd(const void* x, const void* dy, void* out, long n, int act, int dt, vt_stream_t s) {
+  if (!x || !out || n < 1 || (act != VT_ACT_GELU_TANH && act != VT_ACT_SILU)) return vt_fail(VT_ERR_ARG, "vt_act_bwd: bad argument (act 2 = tanh-GELU, 3 = SiLU)");
+  if (dt == VT_F32) hipLaunchKernelGGL(act_kernel<float>, g1(n), dim3(256), 0, (hipStream_t)s, (const float*)x, (const float*)dy, (float*)out, n, act);
+  else if (dt == VT_BF16) hipLaunchKernelGGL(act_kernel<bf16_t>, g1(n), dim3(256), 0, (hipStream_t)s, (const bf16_t*)x, (const bf16_t*)dy, (bf16_t*)out, n, act);
+  else return BAD_DT("vt_act_bwd");
+  return LAUNCH_OK();
+}
+int vt_ddpm_qsample(const float* state, const float* action, const float* noise, const float* mask, const long* timesteps, const float* alphas_cumprod,
+                    int num_train_timesteps, void* out, int odt, int B, int horizon, int action_dim, vt_stream_t s) {
+  if (!state || !action || !noise || !mask || !timesteps || !alphas_cumprod || !out || num_train_timesteps < 1 || B < 1 || horizon < 1 || action_dim < 1)
+    return vt_fail(VT_ERR_ARG, "vt_ddpm_qsample: bad argument");
+  const dim3 g = g1((long)B * (horizon + 1) * 2 * action_dim);
+  if (odt == VT_F32) hipLaunchKernelGGL(ddpm_qsample_kernel<float>, g, dim3(256), 0, (hipStream_t)s, state, action, noise, mask, timesteps, alphas_cumprod, num_train_timesteps, (float*)out, B, horizon, action_dim);
+  else if (odt == VT_BF16) hipLaunchKernelGGL(ddpm_qsample_kernel<bf16_t>, g, dim3(256), 0, (hipStream_t)s, state, action, noise, mask, timesteps, alphas_cumprod, num_train_timesteps, (bf16_t*)out, B, horizon, action_dim);
+  else return BAD_DT("vt_ddpm_qsample");
+  return LAUNCH_OK();
+}
+int vt_timestep_embed(const float* t, const float* freqs, void* out, int odt, int B, int dim, vt_stream_t s) {
+  if (!t || !freqs || !out || B < 1 || dim < 2 || dim % 2) return vt_fail(VT_ERR_ARG, "vt_timestep_embed: bad argument");
+  if (odt == VT_F32) hipLaunchKernelGGL(timestep_embed_kernel<float>, g1((long)B * dim), dim3(256), 0, (hipStream_t)s, t, freqs, (float*)out, B, dim);
+  else if (odt == VT_BF16) hipLaunchKernelGGL(timestep_embed_kernel<bf16_t>, g1((long)B * dim), dim3(256), 0, (hipStream_t)s, t, freqs, (bf16_t*)out, B, dim);
+  else return BAD_DT("vt_timestep_embed");
+  return LAUNCH_OK();
+}
+int vt_add_rowvec_(void* a, int dt, const float* v, long rows, long cols, vt_stream_t s) {
+  if (!a || !v || rows < 1 || cols < 1) return vt_fail(VT_ERR_ARG, "vt_add_rowvec_: bad argument");
+  if (dt == VT_F32) hipLaunchKernelGGL(add_rowvec_kernel<float>, g1(rows * cols), dim3(256), 0, (hipStream_t)s, (float*)a, v, rows, cols);
+  else if (dt == VT_BF16) hipLaunchKernelGGL(add_rowvec_kernel<bf16_t>, g1(rows * cols), dim3(256), 0, (hipStream_t)s, (bf16_t*)a, v, rows, cols);
+  else return BAD_DT("vt_add_rowvec_");
+  return LAUNCH_OK();
+}
+int vt_transpose_pad(const void* in, void* out, int dt, int M, int N, int Mp, vt_stream_t s) {
+  if (!in || !out || M < 1 || N < 1 || Mp < M) return vt_fail(VT_ERR_ARG, "vt_transpose_pad: bad argument");
+  const dim3 g((N + 31) / 32, (Mp + 31) / 32);
+  if (dt == VT_F32) hipLaunchKernelGGL(transpose_pad_kernel<float>, g, dim3(256), 0, (hipStream_t)s, (const float*)in, (float*)out, M, N, Mp);
+  else if (dt == VT_BF16) hipLaunchKernelGGL(transpose_pad_kernel<bf16_t>, g, dim3(256), 0, (hipStream_t)s, (const bf16_t*)in, (bf16_t*)out, M, N, Mp);
+  else return BAD_DT("vt_transpose_pad");
+  return LAUNCH_OK();
+}
+int vt_colsum_dt(const void* x, int dt, long ld, float* out, int M, int N, vt_stream_t s) {
+  if (!x || !out || M < 1 || N < 1) return vt_fail(VT_ERR_ARG, "vt_colsum_dt: bad argument");
+  if (dt == VT_F32) hipLaunchKernelGGL(colsum_t_kernel<float>, dim3((N + 31) / 32), dim3(1024), 0, (hipStream_t)s, (const float*)x, ld, out, M, N);
+  else if (dt == VT_BF16) hipLaunchKernelGGL(colsum_t_kernel<bf16_t>, dim3((N + 31) / 32), dim3(1024), 0, (hipStream_t)s, (const bf16_t*)x, ld, out, M, N);
+  else return BAD_DT("vt_colsum_dt");
+  return LAUNCH_OK();
+}
+int vt_add_dt(void* a, const void* b, long n, int dt, vt_stream_t s) {
+  if (!a || !b || n < 1) return vt_fail(VT_ERR_ARG, "vt_add_dt: bad argument");
+  if (dt == VT_F32) hipLaunchKernelGGL(add_t_kernel<float>, g1(n), dim3(256), 0, (hipStream_t)s, (float*)a, (const float*)b, n);
+  else if (dt == VT_BF16) hipLaunchKernelGGL(add_t_kernel<bf16_t>, g1(n), dim3(256), 0, (hipStream_t)s, (bf16_t*)a, (const bf16_t*)b, n);
+  else return BAD_DT("vt_add_dt");
+  return LAUNCH_OK();
+}
+int vt_copy_cols_dt(const void* src, long lds_, long off, void* dst, long ldd, long doff, long rows, long cols, int dt, vt_stream_t s) {
+  if (!src || !dst || rows < 1 || cols < 1) return vt_fail(VT_ERR_ARG, "vt_copy_cols_dt: bad argument");
+  if (dt == VT_F32) hipLaunchKernelGGL(copy_cols_t_kernel<float>, g1(rows * cols), dim3(256), 0, (hipStream_t)s, (const float*)src, lds_, off, (float*)dst, ldd, doff, rows, cols);
+  else if (dt == VT_BF16) hipLaunchKernelGGL(copy_cols_t_kernel<bf16_t>, g1(rows * cols), dim3(256), 0, (hipStream_t)s, (const bf16_t*)src, lds_, off, (bf16_t*)dst, ldd, doff, rows, cols);
+  else return BAD_DT("vt_copy_cols_dt");
+  return LAUNCH_OK();
+}
+int vt_grad_clip_multi(const void* table, int ntensors, long total_chunks, float max_norm, float* chunk_part, float* norm_coef, vt_stream_t s) {
+  if (!table || !chunk_part || !norm_coef || ntensors < 1 || total_chunks < 1 || !(max_norm > 0.f)) return vt_fail(VT_ERR_ARG, "vt_grad_clip_multi: bad argument");
+  hipLaunchKernelGGL(sumsq_mt_kernel, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)s, (const MtEntry*)table, ntensors, chunk_part);
+  hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(256), 0, (hipStream_t)s, chunk_part, total_chunks, max_norm, norm_coef);
+  hipLaunchKernelGGL(scale_mt_kernel, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)s, (const MtEntry*)table, ntensors, norm_coef);
+  return LAUNCH_OK();
+}
+int vt_mse_loss(const void* pred, const float* target, void* dpred, float* loss, long n, int dt, vt_stream_t s) {
+  if (!pred || !target || !dpred || !loss || n < 1) return vt_fail(VT_ERR_ARG, "vt_mse_loss: bad argument");
+  if (dt == VT_F32) hipLaunchKernelGGL(mse_kernel<float>, dim3(1), dim3(256), 0, (hipStream_t)s, (const float*)pred, target, (float*)dpred, loss, n);
+  else if (dt == VT_BF16) hipLaunchKernelGGL(mse_kernel<bf16_t>, dim3(1), dim3(256), 0, (hipStream_t)s, (const bf16_t*)pred, target, (bf16_t*)dpred, loss, n);
+  else return BAD_DT("vt_mse_loss");
+  return LAUNCH_OK();
+}

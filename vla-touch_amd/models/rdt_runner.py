@@ -4,8 +4,8 @@ Same keyword-only constructor, `config` dict layout (`config['rdt']`, `config['l
 sub-module names and state-dict keys (`model.*`, `lang_adaptor.*`, `img_adaptor.*`, `state_adaptor.*`), projector types
 (`linear`, `mlpNx_gelu`; ValueError otherwise), and `predict_action` / `conditional_sample` / `adapt_conditions`
 signatures.  `from_pretrained(path)` reads a local HF-style directory (config.json + model.safetensors / pytorch_model.bin)
-like the hub mixin (models/hub_mixin.py:26-75) — there is no network here.  Training (`compute_loss`, the DDPM scheduler)
-is out of scope.
+like the hub mixin (models/hub_mixin.py:26-75) — there is no network here.  `compute_loss` (rdt_runner.py:168-222) and `trainer()`
+run the fine-tuning step of vlatouch/rdt_train.py.
 
 predict_action is ONE call into the HIP driver (vt_rdt_sample): adaptors, per-chunk cross-attention K/V caches,
 num_inference_timesteps x depth blocks and the DPM-Solver++ updates.  The N(0,1) start of the reverse process is drawn
@@ -75,6 +75,9 @@ class RDTRunner:
                  img_cond_len, lang_pos_embed_config=None, img_pos_embed_config=None, dtype=torch.bfloat16, device="cuda",
                  rms_mode: Optional[str] = None, init_weights: bool = True, solver_state: Optional[str] = None, compute_dtype=None):
         hidden_size = config['rdt']['hidden_size']
+        self._ctor = dict(action_dim=action_dim, pred_horizon=pred_horizon, config=config, lang_token_dim=lang_token_dim, img_token_dim=img_token_dim,
+                          state_token_dim=state_token_dim, max_lang_cond_len=max_lang_cond_len, img_cond_len=img_cond_len,
+                          lang_pos_embed_config=lang_pos_embed_config, img_pos_embed_config=img_pos_embed_config)
         # compute_dtype (extension): the engine's 16-bit activation / MFMA operand type for a bf16 model — torch.float16 (default: the bf16 weights convert
         # exactly, same width and MFMA rate, 3 more mantissa bits: |chunk - fp32 reference| 1e-2 -> 1.2e-3 at RDT-1B) or torch.bfloat16
         # (the reference's own execution dtype, rounding after every op).  config['rdt']['compute_dtype'] / VLATOUCH_RDT_COMPUTE = "f16" | "bf16".
@@ -267,8 +270,46 @@ class RDTRunner:
                                                     beta_schedule=self.beta_schedule, prediction_type=self.prediction_type, adapted=False,
                                                     return_fp32=return_fp32))
 
-    def compute_loss(self, *a, **k):
-        raise NotImplementedError("training is outside this build's scope (inference-only hot path)")
+    # ---- training
+    def trainer(self, **kw):
+        """An `RdtTrainer` (vlatouch/rdt_train.py) on a copy of this runner's weights: get_loss / optimizer_step / train_step on the device.
+        `trainer.sync_to(runner)` (or `runner.load_state_dict(trainer.state_dict())`) brings the trained weights back; the engine rebuilds."""
+        from vlatouch.rdt_train import RdtTrainer
+        cfg = dict(self._ctor, dtype=str(self.dtype).replace("torch.", ""), rms_mode=self.rms_mode)
+        args = dict(heads=self.model.num_heads, horizon=self.pred_horizon, action_dim=self.action_dim, rms_mode=self.rms_mode,
+                    prediction_type=self.prediction_type, num_train_timesteps=self.num_train_timesteps, beta_schedule=self.beta_schedule,
+                    config=cfg, device=self.device)
+        args.update(kw)
+        return RdtTrainer(self.state_dict(), **args)
+
+    def release_loss_trainer(self) -> None:
+        """Drop the trainer `compute_loss` keeps between calls (its copy of the weights)."""
+        self._loss_trainer = self._loss_trainer_key = None
+
+    def compute_loss(self, lang_tokens, lang_attn_mask, img_tokens, state_tokens, action_gt, action_mask, ctrl_freqs, *, noise=None, timesteps=None):
+        """The diffusion training loss (rdt_runner.py:168-222) -> 0-d fp32 tensor on the device.  `noise` [B, horizon, action_dim] and `timesteps` [B]
+        replace the reference's `torch.randn` / `torch.randint` draws (:187-194), which are made here in the same order when they are not given.
+        Evaluated by the fp32 trainer's forward on this runner's weights (no gradients are formed: use `trainer()` to train).  That trainer — one
+        more fp32 copy of every weight on the device, 4.9 GB at RDT-1B size, no optimizer state — is kept for the next call and rebuilt when the
+        weights change; `release_loss_trainer()` frees it."""
+        for name, t, nd in (("lang_tokens", lang_tokens, 3), ("img_tokens", img_tokens, 3), ("state_tokens", state_tokens, 3), ("action_gt", action_gt, 3),
+                            ("action_mask", action_mask, 3), ("lang_attn_mask", lang_attn_mask, 2), ("ctrl_freqs", ctrl_freqs, 1)):
+            if torch.as_tensor(t).dim() != nd:
+                raise ValueError(f"compute_loss: {name} must have {nd} dimensions")
+        if self.prediction_type not in ("epsilon", "sample"):
+            raise ValueError(f"Unsupported prediction type {self.prediction_type}")
+        key = tuple(getattr(self, p).version for p in self._PARTS) + (str(self.device), self.prediction_type, self.num_train_timesteps, self.beta_schedule)
+        if getattr(self, "_loss_trainer_key", None) != key:
+            self._loss_trainer, self._loss_trainer_key = self.trainer(), key
+        tr = self._loss_trainer
+        action_gt = torch.as_tensor(action_gt)
+        B = action_gt.shape[0]
+        if noise is None:
+            noise = torch.randn(tuple(action_gt.shape), dtype=self.dtype, device=tr.device)
+        if timesteps is None:
+            timesteps = torch.randint(0, self.num_train_timesteps, (B,), device=tr.device).long()
+        return tr.get_loss(lang_tokens, lang_attn_mask, img_tokens, state_tokens, action_gt, action_mask, ctrl_freqs, noise=noise, timesteps=timesteps,
+                           backward=False)
 
     def forward(self, *args, **kwargs):
         return self.compute_loss(*args, **kwargs)

@@ -115,6 +115,12 @@ class AttnKvtParams(C.Structure):
     ]
 
 
+class AttnBwdParams(C.Structure):     # VtAttnBwdParams (include/vlatouch.h)
+    _fields_ = ([(n, C.c_void_p) for n in ("Q", "K", "V", "dO", "dQ", "dK", "dV", "ws", "kmask")] + [("km_bs", C.c_long)] +
+                [(f"{t}_{s}", C.c_long) for t in ("q", "k", "v", "do", "dq", "dk", "dv") for s in ("bs", "rs", "hs")] +
+                [(n, C.c_int) for n in ("B", "H", "Nq", "Nk", "hd", "dtype")] + [("scale", C.c_float)])
+
+
 class UnetDesc(C.Structure):
     _fields_ = [("nets", C.c_int), ("input_dim", C.c_int), ("input_pad", C.c_int), ("cond_dim", C.c_int),
                 ("dsed", C.c_int), ("n_groups", C.c_int), ("ksize", C.c_int), ("n_levels", C.c_int),
@@ -263,6 +269,19 @@ SIGNATURES = {
     "vt_sum_mid": (_I, [_P, _L, _I, _P, _I, _I, _I, _P]),
     "vt_mul_": (_I, [_P, _P, _L, _P]),
     "vt_mse_residual": (_I, [_P, _P, _P, _P, _P, _P, _L, _P]),
+    "vt_attention_bwd": (_I, [_P, _P]),
+    "vt_rmsnorm_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _F, _I, _I, _P]),
+    "vt_headnorm_bwd": (_I, [_P, _L, _P, _L, _I, _L, _P, _P, _F, _I, _I, _P]),
+    "vt_act_bwd": (_I, [_P, _P, _P, _L, _I, _I, _P]),
+    "vt_ddpm_qsample": (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _P]),
+    "vt_timestep_embed": (_I, [_P, _P, _P, _I, _I, _I, _P]),
+    "vt_add_rowvec_": (_I, [_P, _I, _P, _L, _L, _P]),
+    "vt_transpose_pad": (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    "vt_colsum_dt": (_I, [_P, _I, _L, _P, _I, _I, _P]),
+    "vt_add_dt": (_I, [_P, _P, _L, _I, _P]),
+    "vt_copy_cols_dt": (_I, [_P, _L, _L, _P, _L, _L, _L, _L, _I, _P]),
+    "vt_grad_clip_multi": (_I, [_P, _I, _L, _F, _P, _P, _P]),
+    "vt_mse_loss": (_I, [_P, _P, _P, _P, _L, _I, _P]),
     "vt_imgprep_workspace_bytes": (_Z, [_P, _I, _I, _I]),
     "vt_imgprep": (_I, [_P, _P, _I, _I, _P, C.c_uint, _I, _P, _P, _Z, _P]),
     "vt_marker_workspace_bytes": (_Z, [_I, _I, _I, _I]),

@@ -1,0 +1,559 @@
+"""RDT fine-tuning step on the MI355X: loss, backward, gradient clipping, AdamW, EMA.
+
+Replaces, for one optimisation step, what the reference does with torch autograd (VLA/train/train.py:404-448):
+  * `RDTRunner.compute_loss` (models/rdt_runner.py:168-222): DDPM forward process, state ‖ noisy-action ‖ mask tokens, the three adaptors,
+    `RDT.forward` (models/rdt/model.py:126-165) and the MSE against the action chunk (`sample`) or the noise (`epsilon`);
+  * `loss.backward()` through the final layer, `depth` blocks (self-attention, cross-attention alternating language (masked) / image, FFN, the
+    three RMSNorms, the q / k head norms), the token assembly, the timestep / frequency embedders, the position embeddings, the adaptors;
+  * `accelerator.clip_grad_norm_` (train.py:440-442), `torch.optim.AdamW` (train.py:229-237) and `EMAModel.step` (models/ema_model.py).
+
+Design: fp32 master parameters in the reference's state-dict key layout (`model.*`, `lang_adaptor.*`, `img_adaptor.*`, `state_adaptor.*`);
+every Linear — forward, data gradient, weight gradient — is a vt_gemm call in exact-fp32 MFMA mode (vlatouch.train.gemm: deterministic
+split-K for the long reductions), the attention forward is vt_attention, the norms vt_rownorm / vt_headnorm, and everything autograd would
+add is csrc/vt_train_rdt.hip.  The forward keeps what the backward reads (block inputs, pre-norm q / k, normed q / k / v, attention outputs,
+FFN pre-activations); the image K / V of the odd blocks are kept, not recomputed.  Orchestration is host Python like the reference's loop.
+`precision="fp32"` is the parity mode.  `precision="bf16"` is the reference's execution dtype: bf16 copies of the Linear weights (and of their
+transposes) refreshed after each optimizer step, bf16 activations, activation gradients and MFMA operands, fp32 accumulators, fp32 master
+weights / gradients / moments / EMA (what DeepSpeed's bf16 mode keeps); norm gains, biases and position embeddings are read in fp32.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import json
+import math
+import os
+from collections import OrderedDict
+from typing import Dict, List, Optional
+
+import torch
+
+from . import _lib as L
+from . import ops
+from . import train as T
+from .train import _Optimizer, _empty, _sp
+
+F32 = torch.float32
+LR_SCHEDULERS = ("constant", "constant_with_warmup")
+PREDICTION_TYPES = ("sample", "epsilon")
+
+
+# ---------------------------------------------------------------------------------------------- host-side schedules
+def alphas_cumprod(num_train_timesteps: int, beta_schedule: str) -> torch.Tensor:
+    """DDPMScheduler's fp32 table of prod(1 - beta) over the published beta schedules (vlatouch.dpm._betas)."""
+    from .dpm import _betas
+    return torch.cumprod(1.0 - torch.from_numpy(_betas(num_train_timesteps, beta_schedule)).to(F32), dim=0)
+
+
+def ema_decay(optimization_step: int, update_after_step: int = 0, inv_gamma: float = 1.0, power: float = 2 / 3, min_value: float = 0.0,
+              max_value: float = 0.9999) -> float:
+    """EMAModel.get_decay (models/ema_model.py:45-55)."""
+    step = max(0, optimization_step - update_after_step - 1)
+    if step <= 0:
+        return 0.0
+    return max(min_value, min(1 - (1 + step / inv_gamma) ** -power, max_value))
+
+
+def lr_at(base: float, scheduler: str, steps_done: int, warmup: int) -> float:
+    """diffusers.optimization.get_scheduler's `constant` and `constant_with_warmup` multipliers after `steps_done` scheduler steps."""
+    if scheduler == "constant":
+        return base
+    if scheduler == "constant_with_warmup":
+        return base * (min(1.0, steps_done / max(1, warmup)))
+    raise ValueError(f"lr_scheduler must be one of {LR_SCHEDULERS}, got {scheduler!r}")
+
+
+# ---------------------------------------------------------------------------------------------- primitive wrappers
+# Activations are fp32 or bf16 tensors; every wrapper takes the dtype from its operands.  Sums (weight / bias / gain gradients) are always fp32.
+def _dt(t: torch.Tensor) -> int:
+    return L.dt_code(t.dtype)
+
+
+def transpose_pad(x2d: torch.Tensor) -> torch.Tensor:
+    """[M, N] -> [N, Mp] with zero padding, Mp = M rounded up to the GEMM's reduction alignment (4 fp32, 8 bf16): the operand form of a
+    weight-gradient product (reduction over the M token rows) and of a data-gradient product (W -> W^T)."""
+    M, N = x2d.shape
+    al = 4 if x2d.dtype == F32 else 8
+    Mp = (M + al - 1) // al * al
+    out = torch.empty((N, Mp), dtype=x2d.dtype, device=x2d.device)
+    L.check(L.lib().vt_transpose_pad(L.ptr(x2d), L.ptr(out), _dt(x2d), M, N, Mp, _sp(x2d.device)), "vt_transpose_pad")
+    return out
+
+
+def colsum(x2d: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    M, N = x2d.shape
+    if out is None:
+        out = _empty((N,), x2d.device)
+    if x2d.dtype == F32:
+        L.check(L.lib().vt_colsum(L.ptr(x2d), x2d.stride(0), L.ptr(out), M, N, 0, _sp(x2d.device)), "vt_colsum")
+    else:
+        L.check(L.lib().vt_colsum_dt(L.ptr(x2d), _dt(x2d), x2d.stride(0), L.ptr(out), M, N, _sp(x2d.device)), "vt_colsum_dt")
+    return out
+
+
+def add_(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    if a.dtype == F32:
+        return T.add_(a, b)
+    assert a.shape == b.shape and a.dtype == b.dtype and a.is_contiguous() and b.is_contiguous()
+    L.check(L.lib().vt_add_dt(L.ptr(a), L.ptr(b), a.numel(), _dt(a), _sp(a.device)), "vt_add_dt")
+    return a
+
+
+def copy_cols(src: torch.Tensor, off: int, dst: torch.Tensor, doff: int, cols: int) -> None:
+    """dst[:, doff:doff+cols] = src[:, off:off+cols] on 2-D views of row-contiguous buffers of one dtype."""
+    if src.dtype == F32:
+        return T.copy_cols(src, off, dst, doff, cols)
+    assert src.dtype == dst.dtype
+    L.check(L.lib().vt_copy_cols_dt(L.ptr(src), src.stride(0), off, L.ptr(dst), dst.stride(0), doff, src.shape[0], cols, _dt(src), _sp(src.device)),
+            "vt_copy_cols_dt")
+
+
+def linear_bwd(x: torch.Tensor, w: torch.Tensor, dy: torch.Tensor, need_dx: bool = True, wt: Optional[torch.Tensor] = None):
+    """y = x w^T + b -> (dx | None, dw fp32, db fp32).  fp32: exact-fp32 MFMA with the deterministic split-K of vlatouch.train.gemm;
+    bf16 operands (w, or its cached transpose wt, in bf16): bf16 MFMA with fp32 accumulation, dx rounded to bf16, dw written in fp32."""
+    if x.dtype == F32:
+        dx = T.gemm(dy, T.transpose(w)) if need_dx else None
+        return dx, T.gemm(transpose_pad(dy), transpose_pad(x)), colsum(dy)
+    dx = ops.gemm(dy, wt if wt is not None else transpose_pad(w)) if need_dx else None
+    return dx, ops.gemm(transpose_pad(dy), transpose_pad(x), out_dtype=F32), colsum(dy)
+
+
+def act(x: torch.Tensor, kind: int, dy: Optional[torch.Tensor] = None) -> torch.Tensor:
+    out = torch.empty_like(x)
+    L.check(L.lib().vt_act_bwd(L.ptr(x), L.ptr(dy), L.ptr(out), x.numel(), kind, _dt(x), _sp(x.device)), "vt_act_bwd")
+    return out
+
+
+def rmsnorm_bwd(x: torch.Tensor, w: torch.Tensor, dy: torch.Tensor, eps: float, mode: int):
+    M, D = x.shape
+    dx, dyxr = torch.empty_like(x), _empty((M, D), x.device)
+    L.check(L.lib().vt_rmsnorm_bwd(L.ptr(x), L.ptr(w), L.ptr(dy), L.ptr(dx), L.ptr(dyxr), M, D, eps, mode, _dt(x), _sp(x.device)), "vt_rmsnorm_bwd")
+    return dx, T.colsum(dyxr)
+
+
+def headnorm_bwd_(x: torch.Tensor, dy: torch.Tensor, heads: int, w: torch.Tensor, eps: float, mode: int) -> torch.Tensor:
+    """x (pre-norm), dy: 2-D views [tokens, heads * 64] of row-strided buffers; dy becomes dx; -> d w [64]."""
+    tokens = x.shape[0]
+    assert x.shape == dy.shape == (tokens, heads * 64) and x.stride(1) == 1 and dy.stride(1) == 1 and x.dtype == dy.dtype
+    part = _empty(((tokens * heads + 63) // 64, 64), x.device)
+    L.check(L.lib().vt_headnorm_bwd(L.ptr(x), x.stride(0), L.ptr(dy), dy.stride(0), heads, tokens, L.ptr(w), L.ptr(part), eps, mode, _dt(x),
+                                    _sp(x.device)), "vt_headnorm_bwd")
+    return T.colsum(part)
+
+
+def attention_bwd(q, k, v, do, dq, dk, dv, *, kmask: Optional[torch.Tensor] = None, scale: Optional[float] = None) -> None:
+    """q, do, dq [B, Nq, H, 64]; k, v, dk, dv [B, Nk, H, 64] (any strides with unit inner stride, one dtype: fp32 or bf16); kmask [B, Nk] uint8."""
+    B, Nq, H, hd = q.shape
+    Nk = k.shape[1]
+    assert hd == 64 and k.shape == v.shape == dk.shape == dv.shape == (B, Nk, H, 64) and do.shape == dq.shape == q.shape
+    p = L.AttnBwdParams()
+    for name, t in (("q", q), ("k", k), ("v", v), ("do", do), ("dq", dq), ("dk", dk), ("dv", dv)):
+        assert t.stride(3) == 1 and t.dtype == q.dtype
+        setattr(p, {"q": "Q", "k": "K", "v": "V", "do": "dO", "dq": "dQ", "dk": "dK", "dv": "dV"}[name], t.data_ptr())
+        setattr(p, f"{name}_bs", t.stride(0)), setattr(p, f"{name}_rs", t.stride(1)), setattr(p, f"{name}_hs", t.stride(2))
+    ws = _empty((B * H * Nq * 3,), q.device)
+    p.ws = ws.data_ptr()
+    if kmask is not None:
+        assert kmask.dtype == torch.uint8 and kmask.shape == (B, Nk) and kmask.is_contiguous()
+        p.kmask, p.km_bs = kmask.data_ptr(), Nk
+    p.B, p.H, p.Nq, p.Nk, p.hd, p.dtype = B, H, Nq, Nk, 64, L.dt_code(q.dtype)
+    p.scale = scale if scale is not None else hd ** -0.5
+    L.check(L.lib().vt_attention_bwd(C.byref(p), _sp(q.device)), "vt_attention_bwd")
+
+
+def ddpm_qsample(state, action, noise, mask, timesteps, ab, dtype=F32) -> torch.Tensor:
+    """state [B,1,A], action / noise [B,H,A], mask [B,1,A] fp32, timesteps [B] int64, ab [T] -> [B, H+1, 2A] in `dtype` (rdt_runner.py:197-204)."""
+    B, H, A = action.shape
+    out = torch.empty((B, H + 1, 2 * A), dtype=dtype, device=action.device)
+    L.check(L.lib().vt_ddpm_qsample(L.ptr(state), L.ptr(action), L.ptr(noise), L.ptr(mask), L.ptr(timesteps), L.ptr(ab), ab.numel(), L.ptr(out), _dt(out),
+                                    B, H, A, _sp(action.device)), "vt_ddpm_qsample")
+    return out
+
+
+def timestep_freqs(dim: int = 256, max_period: float = 10000.0) -> torch.Tensor:
+    """The fp32 frequency table exactly as blocks.py:53-56 computes it."""
+    half = dim // 2
+    return torch.exp(-math.log(max_period) * torch.arange(start=0, end=half, dtype=F32) / half)
+
+
+def timestep_embed(t: torch.Tensor, freqs: torch.Tensor, dtype=F32) -> torch.Tensor:
+    dim = 2 * freqs.numel()
+    out = torch.empty((t.shape[0], dim), dtype=dtype, device=t.device)
+    L.check(L.lib().vt_timestep_embed(L.ptr(t), L.ptr(freqs), L.ptr(out), _dt(out), t.shape[0], dim, _sp(t.device)), "vt_timestep_embed")
+    return out
+
+
+def add_rowvec_(a2d: torch.Tensor, v: torch.Tensor) -> None:
+    rows, cols = a2d.shape
+    assert a2d.is_contiguous() and v.is_contiguous() and v.dtype == F32 and v.numel() >= cols
+    L.check(L.lib().vt_add_rowvec_(L.ptr(a2d), _dt(a2d), L.ptr(v), rows, cols, _sp(a2d.device)), "vt_add_rowvec_")
+
+
+def mse_loss(pred: torch.Tensor, target: torch.Tensor):
+    """pred (activation dtype), target fp32 -> (loss [1] fp32, d pred in pred's dtype)."""
+    dpred, loss = torch.empty_like(pred), _empty((1,), pred.device)
+    L.check(L.lib().vt_mse_loss(L.ptr(pred), L.ptr(target), L.ptr(dpred), L.ptr(loss), pred.numel(), _dt(pred), _sp(pred.device)), "vt_mse_loss")
+    return loss, dpred
+
+
+def _cols(src2d: torch.Tensor, off: int, cols: int) -> torch.Tensor:
+    out = torch.empty((src2d.shape[0], cols), dtype=src2d.dtype, device=src2d.device)
+    copy_cols(src2d, off, out, 0, cols)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------- the trainer
+class RdtTrainer(_Optimizer):
+    """get_loss + backward + clip + AdamW + EMA for `RDTRunner` (all of its parameters train, the three position embeddings included).
+
+    sd: the runner's state dict (reference keys).  Hyper-parameters default to main.py:125-210 (lr 5e-6, betas 0.9 / 0.999, eps 1e-8, weight decay
+    1e-2, max_grad_norm 1.0) and EMAModel's constructor."""
+
+    def __init__(self, sd, *, heads: int, horizon: int, action_dim: int, rms_mode: str = "meansq", prediction_type: str = "sample",
+                 num_train_timesteps: int = 1000, beta_schedule: str = "squaredcos_cap_v2", precision: str = "fp32", lr: float = 5e-6,
+                 betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, max_grad_norm: float = 1.0, lr_scheduler: str = "constant",
+                 lr_warmup_steps: int = 500, ema: Optional[dict] = None, config: Optional[dict] = None, device="cuda"):
+        if precision not in ("fp32", "bf16"):
+            raise ValueError(f"precision must be 'fp32' or 'bf16', got {precision!r} (no fp16 training mode: its gradients underflow without loss scaling)")
+        if prediction_type not in PREDICTION_TYPES:
+            raise ValueError(f"Unsupported prediction type {prediction_type}")
+        if rms_mode not in ("meansq", "var"):
+            raise ValueError(f"rms_mode must be 'meansq' or 'var', got {rms_mode!r}")
+        lr_at(lr, lr_scheduler, 0, lr_warmup_steps)                       # raises on an unknown scheduler
+        self.device = dev = L.require_gpu(device)
+        self.p: "OrderedDict[str, torch.Tensor]" = OrderedDict((k, v.detach().to(dev, F32).contiguous().clone()) for k, v in sd.items())
+        self.g: Dict[str, torch.Tensor] = {}
+        self.depth = 0
+        while f"model.blocks.{self.depth}.norm1.weight" in self.p:
+            self.depth += 1
+        self.hidden = self.p["model.x_pos_embed"].shape[2]
+        self.heads, self.horizon, self.action_dim = heads, horizon, action_dim
+        if self.hidden != heads * 64:
+            raise ValueError("RdtTrainer: head_dim must be 64")
+        if self.p["model.x_pos_embed"].shape[1] != horizon + 3:
+            raise ValueError("RdtTrainer: x_pos_embed does not match horizon + 3 tokens")
+        self.rms_mode, self.norm_mode = rms_mode, (L.NORM_RMS_MEANSQ if rms_mode == "meansq" else L.NORM_RMS_VAR)
+        self.prediction_type, self.num_train_timesteps, self.beta_schedule = prediction_type, num_train_timesteps, beta_schedule
+        self.ab = alphas_cumprod(num_train_timesteps, beta_schedule).to(dev)
+        self.freqs = timestep_freqs(256).to(dev)
+        self.adaptors = {n: self._adaptor_layers(n) for n in ("lang_adaptor", "img_adaptor", "state_adaptor")}
+        self.precision = precision
+        self.adt = F32 if precision == "fp32" else torch.bfloat16     # dtype of activations, activation gradients and MFMA operands
+        self.w16: Dict[str, torch.Tensor] = {}                        # bf16 mode: copies of the Linear weights and of their transposes,
+        self.w16t: Dict[str, torch.Tensor] = {}                       # refreshed after every optimizer step
+        self._refresh16()
+        self.base_lr, self.lr, self.wd, self.betas, self.eps, self.max_grad_norm = lr, lr, weight_decay, betas, eps, max_grad_norm
+        self.lr_scheduler, self.lr_warmup_steps = lr_scheduler, lr_warmup_steps
+        self.ema_cfg = dict(update_after_step=0, inv_gamma=1.0, power=2 / 3, min_value=0.0, max_value=0.9999)
+        self.ema_cfg.update(ema or {})
+        self.config = config
+        self.step_count = 0
+        self.ema_updates = 0
+        self._m: Dict[str, torch.Tensor] = {}                 # AdamW moments and the EMA copy appear with the first optimizer step (the parameters are
+        self._v: Dict[str, torch.Tensor] = {}                 # still the initial ones then), so a trainer that only evaluates the loss holds one copy
+        self.shadow: Dict[str, torch.Tensor] = {}
+        self._norm_coef = torch.zeros(2, dtype=F32, device=dev)
+        self._table_key = None
+        self.last_loss: Optional[torch.Tensor] = None
+
+    def _adaptor_layers(self, name: str) -> List[str]:
+        if f"{name}.weight" in self.p:
+            return [name]
+        out, i = [], 0
+        while f"{name}.{i}.weight" in self.p:
+            out.append(f"{name}.{i}")
+            i += 2
+        if not out:
+            raise ValueError(f"no weights for {name}")
+        return out
+
+    # ---- _Optimizer plumbing
+    def _all_params(self):
+        for k, v in self.p.items():
+            yield k, v, self.g.get(k)
+
+    def _ema_decay(self, step: int) -> float:
+        """`step` = number of EMA updates including this one; EMAModel.step evaluates get_decay at the count before it."""
+        return ema_decay(step - 1, **self.ema_cfg)
+
+    def _shadow_source(self, name: str) -> torch.Tensor:
+        return self.p[name]
+
+    @property
+    def grad_norm(self) -> torch.Tensor:
+        """Global L2 norm of the gradients before clipping at the last optimizer_step (0-d device tensor; reading it synchronises)."""
+        return self._norm_coef[0]
+
+    def _refresh16(self) -> None:
+        if self.adt == F32:
+            return
+        for k, v in self.p.items():
+            if k.endswith(".weight") and v.dim() == 2:
+                self.w16[k] = ops.cast(v, self.adt, out=self.w16.get(k))
+                self.w16t[k] = transpose_pad(self.w16[k])
+
+    # ---- layers
+    def _linear(self, name, x, residual=None):
+        b = self.p[f"{name}.bias"]
+        if self.adt != F32:
+            return ops.gemm(x, self.w16[f"{name}.weight"], b, residual=residual)
+        w = self.p[f"{name}.weight"]
+        return ops.gemm(x, w, b, residual=residual) if residual is not None else T.gemm(x, w, b)
+
+    def _linear_bwd(self, name, x, dy, need_dx=True):
+        k = f"{name}.weight"
+        dx, self.g[k], self.g[f"{name}.bias"] = linear_bwd(x, self.w16.get(k, self.p[k]), dy, need_dx, self.w16t.get(k))
+        return dx
+
+    def _norm(self, name, x):
+        return ops.rownorm(x, self.p[f"{name}.weight"], None, 1e-6, self.norm_mode)
+
+    def _norm_bwd(self, name, x, dy):
+        dx, self.g[f"{name}.weight"] = rmsnorm_bwd(x, self.p[f"{name}.weight"], dy, 1e-6, self.norm_mode)
+        return dx
+
+    def _mlp_fwd(self, layers, x, kind):
+        """Linear (act Linear)*: -> (output, tape of (layer input, layer output))."""
+        tape, h = [], x
+        for j, name in enumerate(layers):
+            if j > 0:
+                h = act(tape[-1][1], kind)
+            a = self._linear(name, h)
+            tape.append((h, a))
+        return tape[-1][1], tape
+
+    def _mlp_bwd(self, layers, tape, d, kind, need_dx=False):
+        for j in range(len(layers) - 1, -1, -1):
+            d = self._linear_bwd(layers[j], tape[j][0], d, need_dx or j > 0)
+            if j > 0:
+                d = act(tape[j - 1][1], kind, d)
+        return d
+
+    def _embed_fwd(self, name, t):
+        return self._mlp_fwd([f"{name}.mlp.0", f"{name}.mlp.2"], timestep_embed(t, self.freqs, self.adt), L.ACT_SILU)
+
+    def _heads4(self, buf2d, B, N, col0, row_width):
+        """[B*N, row_width] buffer -> the [B, N, H, 64] view of its columns col0 .. col0 + hidden."""
+        return buf2d.view(B, N, row_width)[:, :, col0:col0 + self.hidden].unflatten(2, (self.heads, 64))
+
+    # ---- forward with the tape, loss, backward
+    def get_loss(self, lang_tokens, lang_attn_mask, img_tokens, state_tokens, action_gt, action_mask, ctrl_freqs, *, noise, timesteps,
+                 backward: bool = True) -> torch.Tensor:
+        """compute_loss's arguments (rdt_runner.py:168-182) plus the two random draws it makes: noise [B, horizon, action_dim] and timesteps [B]
+        (integers in [0, num_train_timesteps)).  -> the loss as a 0-d fp32 device tensor; with backward=True the gradients are left in `self.g`."""
+        dev, D, Hh, hor, A = self.device, self.hidden, self.heads, self.horizon, self.action_dim
+        f = lambda a: torch.as_tensor(a).to(dev, F32).contiguous()
+        lang, img, state, act_gt, amask, noise = f(lang_tokens), f(img_tokens), f(state_tokens), f(action_gt), f(action_mask), f(noise)
+        B, Ll, Li = lang.shape[0], lang.shape[1], img.shape[1]
+        N = hor + 3
+        if act_gt.shape != (B, hor, A) or noise.shape != act_gt.shape or state.shape != (B, 1, A) or amask.shape != (B, 1, A):
+            raise ValueError("get_loss: state_tokens / action_mask must be [B, 1, action_dim], action_gt / noise [B, horizon, action_dim]")
+        if Ll > self.p["model.lang_cond_pos_embed"].shape[1] or Li != self.p["model.img_cond_pos_embed"].shape[1]:
+            raise ValueError("get_loss: language longer than max_lang_cond_len, or image token count != img_cond_len")
+        ts = torch.as_tensor(timesteps)
+        if ts.numel() != B:
+            raise ValueError("get_loss: timesteps must hold one integer per sample")
+        ts = ts.reshape(B).to(dev, torch.int64).contiguous()
+        freqs = f(ctrl_freqs).reshape(B)
+        kmask = torch.as_tensor(lang_attn_mask).to(dev).to(torch.uint8).contiguous()
+        if kmask.shape != (B, Ll):
+            raise ValueError("get_loss: lang_attn_mask must be [B, lang_len]")
+        gelu, mode = L.ACT_GELU_TANH, self.norm_mode
+        p = self.p
+
+        # tokens: DDPM forward process + layout, the three adaptors, the two embedders, position embeddings
+        adt = self.adt
+        new = lambda *shape: torch.empty(shape, dtype=adt, device=dev)
+        if adt != F32:
+            lang, img = ops.cast(lang, adt), ops.cast(img, adt)
+        sa_in = ddpm_qsample(state, act_gt, noise, amask, ts, self.ab, adt).view(B * (hor + 1), 2 * A)
+        sa, tp_state = self._mlp_fwd(self.adaptors["state_adaptor"], sa_in, gelu)
+        lang_c, tp_lang = self._mlp_fwd(self.adaptors["lang_adaptor"], lang.view(B * Ll, -1), gelu)
+        img_c, tp_img = self._mlp_fwd(self.adaptors["img_adaptor"], img.view(B * Li, -1), gelu)
+        te, tp_t = self._embed_fwd("model.t_embedder", ts.to(F32))
+        fe, tp_f = self._embed_fwd("model.freq_embedder", freqs)
+        x = new(B, N * D)
+        copy_cols(te, 0, x, 0, D)
+        copy_cols(fe, 0, x, D, D)
+        copy_cols(sa.view(B, (hor + 1) * D), 0, x, 2 * D, (hor + 1) * D)
+        add_rowvec_(x, p["model.x_pos_embed"])
+        add_rowvec_(lang_c.view(B, Ll * D), p["model.lang_cond_pos_embed"])
+        add_rowvec_(img_c.view(B, Li * D), p["model.img_cond_pos_embed"])
+        x = x.view(B * N, D)
+        conds = ((lang_c, Ll, kmask), (img_c, Li, None))
+
+        blocks = []
+        for i in range(self.depth):
+            b = f"model.blocks.{i}"
+            c, Lc, km = conds[i % 2]
+            tb = {"x0": x}
+            # self-attention (timm Attention with q / k RmsNorm)
+            h1 = self._norm(f"{b}.norm1", x)
+            qkv = self._linear(f"{b}.attn.qkv", h1)
+            tb["h1"], tb["qkv_raw"] = h1, qkv.clone()
+            ops.headnorm_(qkv[:, :D], Hh, p[f"{b}.attn.q_norm.weight"], 1e-6, mode, tok_stride=3 * D, tokens=B * N)
+            ops.headnorm_(qkv[:, D:2 * D], Hh, p[f"{b}.attn.k_norm.weight"], 1e-6, mode, tok_stride=3 * D, tokens=B * N)
+            o = ops.attention(self._heads4(qkv, B, N, 0, 3 * D), self._heads4(qkv, B, N, D, 3 * D), self._heads4(qkv, B, N, 2 * D, 3 * D)).view(B * N, D)
+            tb["qkv"], tb["o1"] = qkv, o
+            x = self._linear(f"{b}.attn.proj", o, residual=x)
+            tb["x1"] = x
+            # cross-attention (blocks.py:102-138)
+            h2 = self._norm(f"{b}.norm2", x)
+            q = self._linear(f"{b}.cross_attn.q", h2)
+            kv = self._linear(f"{b}.cross_attn.kv", c)
+            tb["h2"], tb["q_raw"], tb["k_raw"] = h2, q.clone(), kv[:, :D].clone()
+            ops.headnorm_(q, Hh, p[f"{b}.cross_attn.q_norm.weight"], 1e-6, mode, tok_stride=D, tokens=B * N)
+            ops.headnorm_(kv[:, :D], Hh, p[f"{b}.cross_attn.k_norm.weight"], 1e-6, mode, tok_stride=2 * D, tokens=B * Lc)
+            o = ops.attention(self._heads4(q, B, N, 0, D), self._heads4(kv, B, Lc, 0, 2 * D), self._heads4(kv, B, Lc, D, 2 * D), kmask=km).view(B * N, D)
+            tb["q"], tb["kv"], tb["o2"] = q, kv, o
+            x = self._linear(f"{b}.cross_attn.proj", o, residual=x)
+            tb["x2"] = x
+            # FFN (timm Mlp, tanh-GELU)
+            h3 = self._norm(f"{b}.norm3", x)
+            a = self._linear(f"{b}.ffn.fc1", h3)
+            gl = act(a, gelu)
+            x = self._linear(f"{b}.ffn.fc2", gl, residual=x)
+            tb["h3"], tb["a"], tb["gl"] = h3, a, gl
+            blocks.append(tb)
+
+        fl = "model.final_layer"
+        hf = self._norm(f"{fl}.norm_final", x)
+        af = self._linear(f"{fl}.ffn_final.fc1", hf)
+        gf = act(af, gelu)
+        out = self._linear(f"{fl}.ffn_final.fc2", gf)                                 # [B*N, A]
+        pred = _cols(out.view(B, N * A), 3 * A, hor * A)                               # x[:, -horizon:]
+        target = (act_gt if self.prediction_type == "sample" else noise).view(B, hor * A)
+        loss, dpred = mse_loss(pred, target)
+        self.last_loss = loss.reshape(())
+        self.last_pred = pred.view(B, hor, A)
+        if not backward:
+            return self.last_loss
+
+        # ---------------- backward
+        g = self.g
+        dout = torch.zeros(B, N * A, dtype=adt, device=dev)
+        copy_cols(dpred, 0, dout, 3 * A, hor * A)
+        d = self._linear_bwd(f"{fl}.ffn_final.fc2", gf, dout.view(B * N, A))
+        d = self._linear_bwd(f"{fl}.ffn_final.fc1", hf, act(af, gelu, d))
+        d = self._norm_bwd(f"{fl}.norm_final", x, d)                                   # d loss / d x after the last block
+        dconds = [None, None]
+        for i in range(self.depth - 1, -1, -1):
+            b, tb = f"model.blocks.{i}", blocks[i]
+            c, Lc, km = conds[i % 2]
+            # FFN
+            dg = self._linear_bwd(f"{b}.ffn.fc2", tb["gl"], d)
+            dh = self._linear_bwd(f"{b}.ffn.fc1", tb["h3"], act(tb["a"], gelu, dg))
+            d = add_(self._norm_bwd(f"{b}.norm3", tb["x2"], dh), d)
+            # cross-attention
+            do = self._linear_bwd(f"{b}.cross_attn.proj", tb["o2"], d)
+            dq, dkv = new(B * N, D), new(B * Lc, 2 * D)
+            attention_bwd(self._heads4(tb["q"], B, N, 0, D), self._heads4(tb["kv"], B, Lc, 0, 2 * D), self._heads4(tb["kv"], B, Lc, D, 2 * D),
+                          self._heads4(do, B, N, 0, D), self._heads4(dq, B, N, 0, D), self._heads4(dkv, B, Lc, 0, 2 * D), self._heads4(dkv, B, Lc, D, 2 * D),
+                          kmask=km)
+            g[f"{b}.cross_attn.q_norm.weight"] = headnorm_bwd_(tb["q_raw"], dq, Hh, p[f"{b}.cross_attn.q_norm.weight"], 1e-6, mode)
+            g[f"{b}.cross_attn.k_norm.weight"] = headnorm_bwd_(tb["k_raw"], dkv[:, :D], Hh, p[f"{b}.cross_attn.k_norm.weight"], 1e-6, mode)
+            dc = self._linear_bwd(f"{b}.cross_attn.kv", c, dkv)
+            dconds[i % 2] = dc if dconds[i % 2] is None else add_(dconds[i % 2], dc)
+            dh = self._linear_bwd(f"{b}.cross_attn.q", tb["h2"], dq)
+            d = add_(self._norm_bwd(f"{b}.norm2", tb["x1"], dh), d)
+            # self-attention
+            do = self._linear_bwd(f"{b}.attn.proj", tb["o1"], d)
+            dqkv, qkv = new(B * N, 3 * D), tb["qkv"]
+            attention_bwd(self._heads4(qkv, B, N, 0, 3 * D), self._heads4(qkv, B, N, D, 3 * D), self._heads4(qkv, B, N, 2 * D, 3 * D),
+                          self._heads4(do, B, N, 0, D), self._heads4(dqkv, B, N, 0, 3 * D), self._heads4(dqkv, B, N, D, 3 * D),
+                          self._heads4(dqkv, B, N, 2 * D, 3 * D))
+            raw = tb["qkv_raw"]
+            g[f"{b}.attn.q_norm.weight"] = headnorm_bwd_(raw[:, :D], dqkv[:, :D], Hh, p[f"{b}.attn.q_norm.weight"], 1e-6, mode)
+            g[f"{b}.attn.k_norm.weight"] = headnorm_bwd_(raw[:, D:2 * D], dqkv[:, D:2 * D], Hh, p[f"{b}.attn.k_norm.weight"], 1e-6, mode)
+            dh = self._linear_bwd(f"{b}.attn.qkv", tb["h1"], dqkv)
+            d = add_(self._norm_bwd(f"{b}.norm1", tb["x0"], dh), d)
+        # token assembly, position embeddings, embedders, adaptors
+        dx = d.view(B, N * D)
+        g["model.x_pos_embed"] = colsum(dx).view(1, N, D)
+        self._mlp_bwd(["model.t_embedder.mlp.0", "model.t_embedder.mlp.2"], tp_t, _cols(dx, 0, D), L.ACT_SILU)
+        self._mlp_bwd(["model.freq_embedder.mlp.0", "model.freq_embedder.mlp.2"], tp_f, _cols(dx, D, D), L.ACT_SILU)
+        self._mlp_bwd(self.adaptors["state_adaptor"], tp_state, _cols(dx, 2 * D, (hor + 1) * D).view(B * (hor + 1), D), gelu)
+        for name, dc, Lc, tp_, key in (("lang_adaptor", dconds[0], Ll, tp_lang, "model.lang_cond_pos_embed"),
+                                       ("img_adaptor", dconds[1], Li, tp_img, "model.img_cond_pos_embed")):
+            gp = torch.zeros_like(p[key])
+            if dc is None:                                        # depth 1: no block attends to the image tokens
+                for k in self.p:
+                    if k.startswith(name + "."):
+                        g[k] = torch.zeros_like(p[k])
+            else:
+                colsum(dc.view(B, Lc * D), gp)
+                self._mlp_bwd(self.adaptors[name], tp_, dc, gelu)
+            g[key] = gp
+        return self.last_loss
+
+    # ---- optimizer
+    def _table(self):
+        """The multi-tensor table vt_grad_clip_multi / vt_adamw_ema_multi read: {p, g, m, v, shadow, n, first_chunk} per tensor, on the device."""
+        rows, chunk0 = [], 0
+        if not self.shadow:
+            self._m = {k: torch.zeros_like(v) for k, v in self.p.items()}
+            self._v = {k: torch.zeros_like(v) for k, v in self.p.items()}
+            self.shadow = {k: v.clone() for k, v in self.p.items()}
+        for name, pt, gt in self._all_params():
+            if gt is None:
+                raise RuntimeError(f"no gradient for {name}: call get_loss first")
+            if not gt.is_contiguous():
+                gt = self.g[name] = gt.contiguous()
+            rows.append([pt.data_ptr(), gt.data_ptr(), self._m[name].data_ptr(), self._v[name].data_ptr(), self.shadow[name].data_ptr(), pt.numel(), chunk0])
+            chunk0 += (pt.numel() + 4095) // 4096
+        key = tuple(r[1] for r in rows)
+        if key != self._table_key:                                # gradients are fresh allocations each step: their addresses usually repeat, not always
+            self._mt_dev = torch.tensor(rows, dtype=torch.int64).to(self.device)
+            self._chunk_part = _empty((chunk0,), self.device)
+            self._table_key, self._chunks = key, chunk0
+        return self._mt_dev, len(rows), self._chunks
+
+    def optimizer_step(self, hyper: Optional[torch.Tensor] = None):
+        """clip_grad_norm_(max_grad_norm) -> AdamW -> EMA (train.py:440-448), three launches over one table; no host read."""
+        if hyper is not None:
+            raise NotImplementedError("RdtTrainer: hipGraph capture of the step is not built")
+        lib, dev = L.lib(), self.device
+        tab, n, chunks = self._table()
+        self.lr = lr_at(self.base_lr, self.lr_scheduler, self.step_count, self.lr_warmup_steps)
+        self.step_count += 1
+        self.ema_updates += 1
+        host = torch.zeros(4, dtype=F32)
+        L.check(lib.vt_train_hyper(self.lr, self.betas[0], self.betas[1], self.step_count, self._ema_decay(self.ema_updates), L.ptr(host)), "vt_train_hyper")
+        hy = host.to(dev)
+        L.check(lib.vt_grad_clip_multi(L.ptr(tab), n, chunks, self.max_grad_norm, L.ptr(self._chunk_part), L.ptr(self._norm_coef), _sp(dev)), "vt_grad_clip_multi")
+        L.check(lib.vt_adamw_ema_multi(L.ptr(tab), n, chunks, L.ptr(hy), self.betas[0], self.betas[1], self.eps, self.wd, _sp(dev)), "vt_adamw_ema_multi")
+        self._refresh16()
+
+    def train_step(self, lang_tokens, lang_attn_mask, img_tokens, state_tokens, action_gt, action_mask, ctrl_freqs, *, noise=None, timesteps=None):
+        B = torch.as_tensor(action_gt).shape[0]
+        if noise is None:
+            noise = torch.randn(tuple(torch.as_tensor(action_gt).shape), dtype=F32, device=self.device)
+        if timesteps is None:
+            timesteps = torch.randint(0, self.num_train_timesteps, (B,), device=self.device)
+        loss = self.get_loss(lang_tokens, lang_attn_mask, img_tokens, state_tokens, action_gt, action_mask, ctrl_freqs, noise=noise, timesteps=timesteps)
+        self.optimizer_step()
+        return loss
+
+    # ---- state
+    def grads(self):
+        return OrderedDict((k, self.g[k].detach().cpu().reshape(self.p[k].shape)) for k in self.p)
+
+    def state_dict(self):
+        return OrderedDict((k, v.detach().cpu().clone()) for k, v in self.p.items())
+
+    def ema_state_dict(self):
+        return OrderedDict((k, self.shadow.get(k, self.p[k]).detach().cpu().clone()) for k in self.p)
+
+    def sync_to(self, runner, ema: bool = False):
+        """Hand the trained (or the averaged) weights to an RDTRunner: its engine rebuilds on the next call."""
+        runner.load_state_dict(self.ema_state_dict() if ema else self.state_dict())
+        return runner
+
+    def save_pretrained(self, path: str, ema: bool = False) -> None:
+        """config.json (the runner's constructor arguments) + model.safetensors, as RDTRunner.from_pretrained reads them."""
+        if self.config is None:
+            raise RuntimeError("save_pretrained needs the runner's constructor arguments: build the trainer with RDTRunner.trainer()")
+        from safetensors.torch import save_file
+        os.makedirs(path, exist_ok=True)
+        with open(os.path.join(path, "config.json"), "w") as fjs:
+            json.dump(self.config, fjs, indent=2)
+        save_file({k: v.contiguous() for k, v in (self.ema_state_dict() if ema else self.state_dict()).items()}, os.path.join(path, "model.safetensors"))
