@@ -349,7 +349,8 @@ int vt_add_(float* a, const float* b, long n, vt_stream_t stream);
 int vt_copy_cols(const float* src, long lds, int off, float* dst, long ldd, int doff, int rows, int cols, int accumulate, vt_stream_t stream);
 int vt_mish(const float* x, const float* dy, float* out, long n, vt_stream_t stream);             /* dy NULL: mish(x); else dy * mish'(x) */
 /* backward of out = film_scale * mish(GroupNorm(c)) + film_bias: c, dout, dc [B*T][C]; film, dfilm [B][2C] (scale | bias) or NULL;
- * dgamma_part, dbeta_part [B][C] per-sample partials (sum over B with vt_colsum). */
+ * dgamma_part, dbeta_part [B][C] per-sample partials (sum over B with vt_colsum).  C / ngroups <= 256; a group (C / ngroups) * T of more than
+ * 8188 elements (2 floats each + 32 bytes of static LDS past 64 KiB) returns VT_ERR_UNSUPPORTED. */
 int vt_gn_mish_bwd(const float* c, const float* gamma, const float* beta, const float* film, const float* dout, float* dc,
                    float* dgamma_part, float* dbeta_part, float* dfilm, int B, int T, int C, int ngroups, float eps, vt_stream_t stream);
 int vt_gelu(const float* x, const float* dy, float* out, long n, vt_stream_t stream);             /* erf GELU / its backward */

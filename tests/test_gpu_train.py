@@ -417,3 +417,134 @@ def test_training_step_at_bench_batch_is_the_mean_of_its_sub_batches():
     assert abs(lb - lsum / 8) < 2e-6 * abs(lb), (lb, lsum / 8)
     worst = max(float((gb[k].double() - acc[k] / 8).norm() / (acc[k].norm() / 8 + 1e-30)) for k in gb)
     assert worst < 5e-5, worst
+
+
+# ------------------------------------------------------------------------------------------------ element-wise against the fp64 statement
+# tests/train_ref.py restates both training losses in plain torch (pinned on the CPU to the same goldens by tests/test_train_host.py); here
+# EVERY gradient tensor of the HIP step is compared with its fp64 autograd run element by element, at horizons / widths other than the goldens'.
+# Bars: losses 1e-5 relative; every gradient and d loss / d obs_cond within 1e-4 of the tensor's norm AND max element error <= 1e-4 of its max-abs.
+def _si_inputs(B, T, seed, t_extra=()):
+    from vlatouch import synth
+    g = synth.inputs_rng(seed)
+    t = g.uniform(0, 1, B).astype(np.float32)
+    t[0], t[1] = 0.0002, 0.9999                       # both clipped to [t_min, 1 - t_min]
+    for i, v in enumerate(t_extra):
+        t[2 + i] = v
+    return dict(obs_in=cases.T(g.standard_normal((B, 781), dtype=np.float32)), vla_n=cases.T(g.uniform(-1, 1, (B, T, 10)).astype(np.float32)),
+                expert_n=cases.T(g.uniform(-1, 1, (B, T, 10)).astype(np.float32)), t=cases.T(t), z=cases.T(g.standard_normal((B, T, 10), dtype=np.float32)))
+
+
+def _worst_elementwise(got, ref):
+    from tests import train_ref as R
+    assert set(got) == set(ref), set(got) ^ set(ref)
+    wn = max((R.rel_err(got[k], ref[k]), k) for k in ref)
+    wm = max((R.max_err(got[k], ref[k]), k) for k in ref)
+    return wn, wm
+
+
+def _si_against_fp64(B, T, gamma, kind, t_extra=()):
+    from tests import train_ref as R
+    from vlatouch.train import SITrainer
+    net, enc = cases.si_net_sd(""), cases.state_encoder_sd(781)
+    inp = _si_inputs(B, T, 900 + 10 * B + T, t_extra)
+    tr = SITrainer(net, enc, gamma_type=gamma, interpolant_type=kind, device="cuda:0")
+    loss, info = tr.get_loss(inp["obs_in"], inp["vla_n"], inp["expert_n"], inp["t"], inp["z"])
+    l64, i64, g64, dc64 = R.si_loss_and_grads(net, enc, inp, gamma_type=gamma, interpolant_type=kind)
+    grads = dict(tr.net_grads())
+    grads.update({"state_encoder." + k: v for k, v in tr.mlp.grads().items()})
+    got, want = np.array([loss] + [info[k] for k in ("v_loss", "s_loss", "b_loss")]), np.array([l64] + [i64[k] for k in ("v_loss", "s_loss", "b_loss")])
+    el = float(np.abs(got - want).max() / np.abs(want).max())
+    (wn, kn), (wm, km) = _worst_elementwise(grads, g64)
+    dn, dm = R.rel_err(tr.last_dcond.cpu(), dc64), R.max_err(tr.last_dcond.cpu(), dc64)
+    print(f"[si_train {kind} / {gamma} B{B} T{T}] loss {loss:.6f} (fp64 {l64:.6f}): losses {el:.2e}; worst gradient {wn:.2e} of the norm ({kn}), "
+          f"{wm:.2e} of max-abs ({km}); dcond {dn:.2e} / {dm:.2e}")
+    assert tr.last_dcond.shape == (B, 256)
+    assert el < 1e-5 and wn <= 1e-4 and wm <= 1e-4 and dn <= 1e-4 and dm <= 1e-4, (el, wn, kn, wm, km, dn, dm)
+
+
+SI_GRID = [(16, 16, 0), (4, 8, 1), (8, 32, 2), (4, 48, 0), (4, 64, 1), (8, 12, 2), (5, 24, 0)]           # (5, 24): the ragged batch at a new horizon
+
+
+@pytest.mark.parametrize("B,T,gamma", SI_GRID)
+def test_si_gradients_elementwise_against_fp64_autograd(B, T, gamma):
+    """SITrainer.get_loss at horizons 8 .. 64 (other split-K factors, other padding edges of the strided / transposed convolutions, GroupNorm groups
+    of 2 .. 64 ticks), linear interpolant, every gamma schedule at least twice.  Measured on an MI355X over the grid: losses <= 9.5e-8 relative;
+    worst gradient 1.9e-6 of its norm, 3.0e-6 of its max-abs; d loss / d obs_cond 1.5e-6 / 1.8e-6 (bars 1e-5, 1e-4, 1e-4)."""
+    from tests import train_ref as R
+    _si_against_fp64(B, T, R.GAMMAS[gamma], "linear")
+
+
+def test_si_gradients_elementwise_nonlinear_interpolant():
+    _si_against_fp64(8, 32, "(2t(t-1))^0.5", "gaussian_encode_decode", t_extra=(0.5, 0.5000001, 0.31, 0.77))
+
+
+def _lstm_inputs(B, T, seed):
+    from vlatouch import synth
+    g = synth.inputs_rng(seed)
+    return dict(obs_in=cases.T(g.standard_normal((B, 778), dtype=np.float32)), vla_n=cases.T(g.uniform(-1, 1, (B, T, 10)).astype(np.float32)),
+                forces=cases.T(g.standard_normal((B, T, 3), dtype=np.float32)), expert_n=cases.T(g.uniform(-1, 1, (B, T, 10)).astype(np.float32)))
+
+
+@pytest.mark.parametrize("with_masks", [False, True])
+@pytest.mark.parametrize("B,T", [(8, 16), (4, 1), (3, 7)])
+@pytest.mark.parametrize("hidden,layers", [(256, 2), (128, 2), (384, 3)])
+def test_lstm_gradients_elementwise_against_fp64_autograd(hidden, layers, B, T, with_masks):
+    """LstmTrainer.get_loss at the widths / depths the forward kernels are tested at (tools/make_golden_lstm_widths.py: latent 384 for every width, so
+    obs_encoder reads 778 columns), one tick, a ragged batch; eval-mode arithmetic and injected keep-masks (three layers: two different inter-layer masks).
+    Measured on an MI355X over the 18 cases: prediction <= 2.3e-6 absolute; worst gradient 1.4e-6 of its norm, 1.8e-6 of its max-abs; dcond 1.0e-6 / 1.4e-6."""
+    from tests import train_ref as R
+    from vlatouch.train import LstmTrainer
+    mods = cases.lstm_mods(384, hidden, layers)
+    inp = _lstm_inputs(B, T, 1000 + hidden + 10 * B + T)
+    masks = None
+    if with_masks:
+        gen, p = torch.Generator().manual_seed(hidden + T), 0.1
+        keep = lambda: (torch.rand(B, T, hidden, generator=gen) >= p).float() / (1 - p)
+        masks = {"head": keep()}
+        masks.update({"lstm": keep()} if layers == 2 else {f"lstm{l}": keep() for l in range(layers - 1)})
+        assert layers == 2 or not torch.equal(masks["lstm0"], masks["lstm1"])
+    tr = LstmTrainer(mods, device="cuda:0")
+    loss, pred = tr.get_loss(inp["obs_in"], inp["vla_n"], inp["forces"], inp["expert_n"], masks=masks)
+    l64, p64, g64, dc64 = R.lstm_loss_and_grads(mods, inp, masks=masks)
+    grads = {f"{m}.{k}": v for m, sd in tr.modules_grads().items() for k, v in sd.items()}
+    (wn, kn), (wm, km) = _worst_elementwise(grads, g64)
+    ep = float((pred.cpu().double() - p64).abs().max())
+    dn, dm = R.rel_err(tr.last_dcond.cpu(), dc64), R.max_err(tr.last_dcond.cpu(), dc64)
+    print(f"[lstm_train h{hidden} l{layers} B{B} T{T} masks{int(with_masks)}] loss {loss:.6f} (fp64 {l64:.6f}), pred {ep:.2e} abs; worst gradient {wn:.2e} of the "
+          f"norm ({kn}), {wm:.2e} of max-abs ({km}); dcond {dn:.2e} / {dm:.2e}")
+    assert pred.shape == (B, T, 10) and tr.last_dcond.shape == (B, hidden)
+    with pytest.raises(ValueError):              # a mask that covers neither the B T real rows nor the padded batch is refused, not padded
+        tr.get_loss(inp["obs_in"], inp["vla_n"], inp["forces"], inp["expert_n"], masks={"head": torch.ones(B, T + 1, hidden)}, backward=False)
+    assert abs(loss - l64) < 1e-5 * abs(l64) and ep < 2e-5 and wn <= 1e-4 and wm <= 1e-4 and dn <= 1e-4 and dm <= 1e-4, (loss, l64, ep, wn, kn, wm, km, dn, dm)
+
+
+def test_three_si_train_steps_against_fp64_adamw_ema():
+    """Three eager SITrainer.train_step calls at (8, 32): the update p_k - p_0 and the EMA's ema_k - p_0 per tensor, relative to the fp64 run's update
+    norm (tests/train_ref.adamw_ema_steps fed with the fp64 gradients).  Bar: the worst tensor of the HIP run at most 5 x the worst tensor of the same
+    three steps in fp32 torch on the CPU against fp64 (Adam's division by sqrt(v) amplifies gradient rounding where the gradient is near zero).
+    Measured on an MI355X: 3.5e-3 / 2.2e-3 / 1.7e-3 where fp32 torch has 4.2e-3 / 2.6e-3 / 2.1e-3 (the same tensor, a FiLM Linear); EMA alike."""
+    from tests import train_ref as R
+    from vlatouch.train import SITrainer
+    B, T, hp = 8, 32, dict(lr=1e-3, wd=1e-2, betas=(0.9, 0.999), eps=1e-8, ema_decay=0.75)
+    net, enc = cases.si_net_sd(""), cases.state_encoder_sd(781)
+    params = dict(net)
+    params.update({"state_encoder." + k: v for k, v in enc.items()})
+    batches = [_si_inputs(B, T, 1200 + n) for n in range(3)]
+
+    def grads_of(inp, dtype):
+        split = lambda p: ({k: v for k, v in p.items() if not k.startswith("state_encoder.")},
+                           {k[len("state_encoder."):]: v for k, v in p.items() if k.startswith("state_encoder.")})
+        return lambda p: R.si_loss_and_grads(*split(p), inp, dtype=dtype)[2]
+    r64 = R.adamw_ema_steps(params, [grads_of(b, torch.float64) for b in batches], dtype=torch.float64, ema_keys=list(net), **hp)
+    r32 = R.adamw_ema_steps(params, [grads_of(b, torch.float32) for b in batches], dtype=torch.float32, ema_keys=list(net), **hp)
+    p0 = {k: v.double() for k, v in params.items()}
+    worst = lambda got, ref: max((R.rel_err(got[k].double() - p0[k], ref[k] - p0[k]), k) for k in ref)
+    tr = SITrainer(net, enc, lr=hp["lr"], weight_decay=hp["wd"], betas=hp["betas"], eps=hp["eps"], ema_decay=hp["ema_decay"], device="cuda:0")
+    for n, b in enumerate(batches):
+        tr.train_step(b["obs_in"], b["vla_n"], b["expert_n"], b["t"], b["z"])
+        got = dict(tr.net_state_dict())
+        got.update({"state_encoder." + k: v for k, v in tr.mlp.state_dict().items()})
+        (wp, kp), (we, ke) = worst(got, r64[n]["params"]), worst(dict(tr.ema_state_dict()), r64[n]["ema"])
+        (bp, _), (be, _) = worst(r32[n]["params"], r64[n]["params"]), worst(r32[n]["ema"], r64[n]["ema"])
+        print(f"[si_train step {n + 1}] worst update error HIP {wp:.2e} ({kp}) / fp32 torch {bp:.2e}; EMA HIP {we:.2e} ({ke}) / fp32 torch {be:.2e}")
+        assert wp <= 5 * bp and we <= 5 * be, (n, wp, kp, bp, we, ke, be)

@@ -70,15 +70,18 @@ __global__ void wflip_kernel(const float* __restrict__ W, float* __restrict__ WT
 
 // column sums of [M][N] (row pitch ld) -> out[N] (bias gradients; the [B][C] partials of the GroupNorm gains).  A block owns 32 columns
 // (128-B row segments) with 32 row lanes; each lane adds its rows in order, the lanes are combined by a fixed LDS tree: deterministic.
+// The sums are carried in fp64 and rounded once at the store: a 2048-row fp32 tree lost up to 2.6 ulp of the result (1.5 x the bar of
+// tests/test_gpu_train_kernels.py::test_colsum, three times fp32 torch's own error).  Expected to cost nothing (one strided load per add);
+// the kernel was not timed on its own.
 __global__ __launch_bounds__(1024) void colsum_kernel(const float* __restrict__ x, long ld, float* __restrict__ out, int M, int N, int accumulate) {
-  __shared__ float part[32][33];
+  __shared__ double part[32][33];
   const int c = threadIdx.x & 31, r = threadIdx.x >> 5;
   const int n = blockIdx.x * 32 + c;
-  float s0 = 0.f, s1 = 0.f;
+  double s0 = 0.0, s1 = 0.0;
   if (n < N) {
     int m = r;
-    for (; m + 32 < M; m += 64) { s0 += x[(long)m * ld + n]; s1 += x[(long)(m + 32) * ld + n]; }
-    if (m < M) s0 += x[(long)m * ld + n];
+    for (; m + 32 < M; m += 64) { s0 += (double)x[(long)m * ld + n]; s1 += (double)x[(long)(m + 32) * ld + n]; }
+    if (m < M) s0 += (double)x[(long)m * ld + n];
   }
   part[r][c] = s0 + s1;
   __syncthreads();
@@ -86,7 +89,7 @@ __global__ __launch_bounds__(1024) void colsum_kernel(const float* __restrict__ 
     if (r < h) part[r][c] += part[r + h][c];
     __syncthreads();
   }
-  if (r == 0 && n < N) out[n] = accumulate ? out[n] + part[0][c] : part[0][c];
+  if (r == 0 && n < N) out[n] = accumulate ? out[n] + (float)part[0][c] : (float)part[0][c];
 }
 
 // out[i] = sum_s slabs[s][i] (+ bias[i % N]), slabs summed in order: the reduction of a split-K GEMM's fp32 partial products
@@ -342,13 +345,16 @@ __global__ void ema_kernel(float* __restrict__ shadow, const float* __restrict__
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i < n) shadow[i] = ema_elem(shadow[i], p[i], one_minus_decay);
 }
-// SinusoidalPosEmb (conditional_unet_1D.py:7-19): emb[b] = [sin(t_b f_j) | cos(t_b f_j)], f_j = exp(-j log(10000) / (half - 1))
+// SinusoidalPosEmb (conditional_unet_1D.py:7-19): emb[b] = [sin(t_b f_j) | cos(t_b f_j)], f_j = exp(-j log(10000) / (half - 1)).
+// f_j is evaluated in fp64 and rounded once: the fp32 expf / logf chain was up to 2 ulp off, which at t ~ 1000 is 5e-5 of the embedding
+// (tests/test_gpu_train_kernels.py::test_posemb).  The reference builds its table with torch's fp32 exp, itself within an ulp of these
+// correctly rounded values; the product t f and the sinusoid are fp32 here as they are there.
 __global__ void posemb_kernel(const float* __restrict__ t, float* __restrict__ out, int B, int dim) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= B * dim) return;
   const int b = i / dim, j = i - b * dim, half = dim / 2;
   const int jj = j < half ? j : j - half;
-  const float f = expf(-(float)jj * (logf(10000.0f) / (float)(half - 1)));
+  const float f = (float)exp(-(double)jj * (log(10000.0) / (double)(half - 1)));
   const float a = t[b] * f;
   out[i] = j < half ? sinf(a) : cosf(a);
 }
@@ -409,7 +415,8 @@ int vt_gn_mish_bwd(const float* c, const float* gamma, const float* beta, const 
   if (!c || !gamma || !beta || !dout || !dc || !dgamma_part || !dbeta_part || (film && !dfilm)) return vt_fail(VT_ERR_ARG, "vt_gn_mish_bwd: null argument");
   if (B < 1 || T < 1 || ngroups < 1 || C % ngroups || C / ngroups > 256) return vt_fail(VT_ERR_ARG, "vt_gn_mish_bwd: bad shape");
   const size_t smem = (size_t)2 * (C / ngroups) * T * sizeof(float);
-  if (smem > 64 * 1024) return vt_fail(VT_ERR_UNSUPPORTED, "vt_gn_mish_bwd: group too large for LDS");
+  // the kernel's static `red[8]` counts against the same 64 KiB a block gets without hipFuncAttributeMaxDynamicSharedMemorySize
+  if (smem + 8 * sizeof(float) > 64 * 1024) return vt_fail(VT_ERR_UNSUPPORTED, "vt_gn_mish_bwd: group too large for LDS");
   hipLaunchKernelGGL(gn_mish_bwd_kernel, dim3(B * ngroups), dim3(256), smem, (hipStream_t)s, c, gamma, beta, film, dout, dc, dgamma_part, dbeta_part, dfilm, B, T, C,
                      ngroups, eps);
   return LAUNCH_OK();

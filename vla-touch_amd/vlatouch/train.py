@@ -226,7 +226,9 @@ def _unpack_convT(wc: torch.Tensor, cin: int) -> torch.Tensor:
 
 class TrainUNet:
     """One DiffusionConditionalUnet1D (input_dim 10, cond 256, dsed 256, down_dims [256, 512, 512], k 5, 8 groups) with packed fp32
-    parameters `self.p`, a forward that records what the backward needs, and the backward filling `self.g` (same keys as `self.p`)."""
+    parameters `self.p`, a forward that records what the backward needs, and the backward filling `self.g` (same keys as `self.p`).
+    Any horizon T % 4 == 0 and batch B % 4 == 0; the shapes it is tested at element-wise against fp64 autograd are `SI_GRID` of
+    tests/test_gpu_train.py (whole net, horizons 8 .. 64) and `CONV_CASES` of tests/test_gpu_train_kernels.py (each convolution's backward)."""
 
     def __init__(self, sd: Dict[str, torch.Tensor], device):
         self.device = torch.device(device)
@@ -782,7 +784,9 @@ class LstmTrainer(_Optimizer):
         self.gl[f"bias_ih_l{l}"], self.gl[f"bias_hh_l{l}"] = db, db
         return dX
 
-    def _mask(self, masks, key, shape, p):
+    def _mask(self, masks, key, shape, p, real_rows=None):
+        """-> the [M, H] keep-mask for `key` or None.  An injected mask covers either all M = B T rows or the `real_rows` = Breal T rows of a ragged
+        batch (then the zero-weight padding samples behind them keep everything: nothing of theirs reaches a gradient); any other size raises."""
         if masks is None or p <= 0:
             return None
         if isinstance(masks, str):
@@ -790,7 +794,15 @@ class LstmTrainer(_Optimizer):
                 raise ValueError("masks must be None, 'draw' or a dict of tensors")
             return (torch.rand(shape, device=self.device) >= p).to(F32) / (1.0 - p)
         m = masks.get(key)
-        return None if m is None else m.to(self.device, F32).contiguous().reshape(shape)
+        if m is None:
+            return None
+        m = m.to(self.device, F32).contiguous()
+        if m.numel() == shape[0] * shape[1]:
+            return m.reshape(shape)
+        if real_rows is None or m.numel() != real_rows * shape[1]:
+            raise ValueError(f"mask '{key}' has {m.numel()} elements; expected {shape[0]} x {shape[1]}"
+                             + ("" if real_rows is None else f" or {real_rows} x {shape[1]}"))
+        return torch.cat([m.reshape(real_rows, shape[1]), torch.ones(shape[0] - real_rows, shape[1], dtype=F32, device=self.device)])
 
     def get_loss(self, obs, vla_n, forces, expert_n, *, masks=None, backward: bool = True, sync: bool = True):
         """obs: obs_cond [B,H], or the obs_encoder's input [B, 2*Dv+state] when the trainer owns that MLP; vla_n / expert_n [B,T,D]
@@ -814,7 +826,7 @@ class LstmTrainer(_Optimizer):
             hseq, sv = self._layer_fwd(l, X, B, T)
             saved.append(sv)
             if l + 1 < self.nl:
-                m = self._mask(masks, "lstm" if self.nl == 2 else f"lstm{l}", (M, H), self.p_lstm)
+                m = self._mask(masks, "lstm" if self.nl == 2 else f"lstm{l}", (M, H), self.p_lstm, Breal * T)
                 lmasks.append(m)
                 X = hseq
                 if m is not None:
@@ -826,7 +838,7 @@ class LstmTrainer(_Optimizer):
         a1 = gemm(comb, self.head["0.weight"], self.head["0.bias"])
         n1 = ops.rownorm(a1, self.head["1.weight"], self.head["1.bias"], 1e-5)
         g1_ = gelu(n1)
-        hm = self._mask(masks, "head", (M, H), self.p_head)
+        hm = self._mask(masks, "head", (M, H), self.p_head, Breal * T)
         if hm is not None:
             L.check(lib.vt_mul_(L.ptr(g1_), L.ptr(hm), g1_.numel(), sp), "vt_mul_")
         delta = ops.gemm(g1_, self.head["4.weight"], self.head["4.bias"])
