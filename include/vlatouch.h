@@ -449,6 +449,13 @@ int vt_add_dt(void* a, const void* b, long n, int dt, vt_stream_t stream);
 int vt_copy_cols_dt(const void* src, long lds, long off, void* dst, long ldd, long doff, long rows, long cols, int dt, vt_stream_t stream);
 int vt_grad_clip_multi(const void* table, int ntensors, long total_chunks, float max_norm, float* chunk_part, float* norm_coef, vt_stream_t stream);
 int vt_mse_loss(const void* pred, const float* target, void* dpred, float* loss, long n, int dt, vt_stream_t stream);
+/* Gradient accumulation over the table of vt_adamw_ema_multi, whose g column holds the persistent fp32 accumulators.
+ * vt_grad_accum_multi: fresh = device array of ntensors `const float*`, the micro-batch's gradients in table order.  accumulate = 0:
+ *   acc = g * scale (the accumulator is not read); otherwise acc = fma(g, scale, acc).  scale = 1 / gradient_accumulation_steps.
+ * vt_ema_multi: the EMA half of vt_adamw_ema_multi alone (records without a shadow are skipped), 1 - decay read from hyper[3]: the bits of
+ *   vt_ema_update_dev per tensor. */
+int vt_grad_accum_multi(const void* table, const void* fresh, int ntensors, long total_chunks, float scale, int accumulate, vt_stream_t stream);
+int vt_ema_multi(const void* table, int ntensors, long total_chunks, const float* hyper, vt_stream_t stream);
 
 /* ---- camera frames -> SigLIP pixel_values (scripts/franka_model_eef.py:242-288: RoboticDiffusionTransformerModel.preprocess_images + the
  * `.to(device, dtype)` of step(); SiglipImageProcessor.preprocess).  Bit-identical to that PIL path: optional brightness lift

@@ -9,6 +9,13 @@ Linears and attention products, no K/V cache credit) and the share of the bf16 M
 Yardstick only: `loss.backward()` of the oracle (tests/rdt_train_ref.loss_fn, plain torch) on the same GPU in bf16 at the first batch size, and
 the ratio; if it does not run, the field says "not measured" and why.
     python tools/rdt_train_bench.py [--precision bf16] [--batch 4 32] [--depth 28] [--steps 10] [--out profiles/rdt_train_bench.json]
+
+`--accum K` (K > 1) measures the accumulated step instead (the reference's finetune.sh: batch 4, K = 4) at the first batch size: `--steps` windows
+of K micro-batches after `--warmup` windows, every phase device-synchronised: forward, backward, vt_grad_accum_multi, and vt_ema_multi (the
+K - 1 micro-batches without an optimizer step) or clip + AdamW + EMA (the K-th); median and min / max over the timed windows; samples/s over a
+whole window; peak memory; the bytes the accumulate and EMA-only launches move (12 B per parameter each) against the HBM roof; and, from a K = 1
+trainer in the same process, the clip + AdamW + EMA phase the two launches together are held against.  Added to `--out` under the key
+`accumulation`; the other keys of the file stay as they are.
 """
 from __future__ import annotations
 
@@ -42,6 +49,8 @@ def forward_macs(c: dict, B: int, lang_len: int) -> float:
     return float(macs + M * D * D + M * D * A)
 
 
+HBM_SPEC_BYTES_PER_S = 8.0e12    # MI355X HBM3E specification; a float4 copy reaches about 6.3e12 of it
+HBM_COPY_BYTES_PER_S = 6.3e12
 PEAK_BF16_FLOPS = 16 * 157.3e12   # MI355X dense bf16 MFMA peak (16 x the 157.3 TFLOP/s fp32 matrix rate), for the whole-step share only
 
 
@@ -69,6 +78,85 @@ def yardstick(sd, c, args, kw, dev):
         torch.cuda.empty_cache()
 
 
+def _stats(ms):
+    """median, min, max of a list of millisecond samples."""
+    t = sorted(ms)
+    n = len(t)
+    return {"median": t[n // 2] if n % 2 else 0.5 * (t[n // 2 - 1] + t[n // 2]), "min": t[0], "max": t[-1], "n": n}
+
+
+def inputs(a, B, dev):
+    g = torch.Generator(device=dev).manual_seed(99)
+    rn = lambda *s: torch.randn(*s, generator=g, device=dev)
+    amask = torch.zeros(B, 1, 128, device=dev)
+    amask[:, :, :10] = 1.0
+    args = (rn(B, a.lang_len, 4096), torch.ones(B, a.lang_len, dtype=torch.bool, device=dev), rn(B, a.img_len, 1152), rn(B, 1, 128),
+            torch.tanh(rn(B, 64, 128)) * amask, amask, torch.full((B,), 10.0, device=dev))
+    kw = dict(noise=rn(B, 64, 128), timesteps=torch.randint(0, 1000, (B,), generator=g, device=dev))
+    return args, kw
+
+
+def accum_run(a, c, sd, params, dev):
+    """The accumulated step at batch a.batch[0], K = a.accum, and the K = 1 optimizer phase in the same process -> dict."""
+    from vlatouch.rdt_train import RdtTrainer
+    B, K = a.batch[0], a.accum
+    sync = lambda: torch.cuda.synchronize(dev)
+    args, kw = inputs(a, B, dev)
+    # K = 1 first: the phase the two new launches are held against
+    tr = RdtTrainer(sd, heads=c["heads"], horizon=64, action_dim=128, lr=a.lr, precision=a.precision, device=dev)
+    k1 = []
+    for n in range(a.warmup + a.steps):
+        tr.get_loss(*args, **kw)
+        sync(); t0 = time.perf_counter()
+        tr.optimizer_step()
+        sync(); t1 = time.perf_counter()
+        if n >= a.warmup:
+            k1.append(1e3 * (t1 - t0))
+    del tr
+    torch.cuda.empty_cache()
+    torch.cuda.reset_peak_memory_stats(dev)
+    tr = RdtTrainer(sd, heads=c["heads"], horizon=64, action_dim=128, lr=a.lr, precision=a.precision, gradient_accumulation_steps=K, device=dev)
+    ph = {n: [] for n in ("forward_ms", "backward_ms", "accumulate_ms", "ema_only_ms", "sync_step_ms", "window_ms")}
+    losses = []
+    for n in range(a.warmup + a.steps):
+        window = 0.0
+        for j in range(K):
+            sync(); t0 = time.perf_counter()
+            tr.get_loss(*args, backward=False, **kw)
+            sync(); t1 = time.perf_counter()
+            loss = tr.get_loss(*args, **kw)
+            sync(); t2 = time.perf_counter()
+            tr.accumulate()
+            sync(); t3 = time.perf_counter()
+            if j == K - 1:
+                tr.optimizer_step()
+            else:
+                tr.ema_step()
+            sync(); t4 = time.perf_counter()
+            window += t4 - t1                                        # the forward-only pass is there for the split, not part of a step
+            if n >= a.warmup:
+                ph["forward_ms"].append(1e3 * (t1 - t0)), ph["backward_ms"].append(1e3 * ((t2 - t1) - (t1 - t0))), ph["accumulate_ms"].append(1e3 * (t3 - t2))
+                ph["sync_step_ms" if j == K - 1 else "ema_only_ms"].append(1e3 * (t4 - t3))
+        if n >= a.warmup:
+            ph["window_ms"].append(1e3 * window)
+            losses.append(float(loss))
+    out = {"batch": B, "accum": K, "precision": a.precision, "parameters": params, "warmup_windows": a.warmup, "timed_windows": a.steps}
+    out.update({n: _stats(v) for n, v in ph.items()})
+    out["samples_per_s"] = B * K / (out["window_ms"]["median"] / 1e3)
+    out["peak_memory_gib"] = torch.cuda.max_memory_allocated(dev) / 2 ** 30
+    out["losses_last_micro_batch_of_window"] = losses
+    out["grad_norm_last"] = float(tr.grad_norm)
+    out["k1_clip_adamw_ema_ms_same_session"] = _stats(k1)
+    both = out["accumulate_ms"]["median"] + out["ema_only_ms"]["median"]
+    out["accumulate_plus_ema_only_ms"] = both
+    out["no_longer_than_k1_optimizer_phase"] = bool(both <= out["k1_clip_adamw_ema_ms_same_session"]["median"])
+    for n in ("accumulate_ms", "ema_only_ms"):
+        rate = 12.0 * params / (out[n]["median"] / 1e3)
+        out[n]["bytes_per_s"] = rate
+        out[n]["share_of_hbm_spec"], out[n]["share_of_float4_copy_rate"] = rate / HBM_SPEC_BYTES_PER_S, rate / HBM_COPY_BYTES_PER_S
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, nargs="+", default=[4, 32])
@@ -81,6 +169,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--lr", type=float, default=1e-4)
+    ap.add_argument("--accum", type=int, default=1, help="gradient_accumulation_steps; > 1 measures the accumulated step and adds it to --out")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rdt_train_bench.json"))
     a = ap.parse_args()
     from vlatouch.rdt_train import RdtTrainer
@@ -89,6 +178,21 @@ def main():
              state_token_dim=128, max_lang_cond_len=1024, img_cond_len=a.img_len)
     sd = synth.fill_state_dict_device(synth.rdt_runner_shapes(**c), dev, torch.float32, seed=7)
     params = sum(v.numel() for v in sd.values())
+    if a.accum > 1:
+        rec = {}
+        if os.path.exists(a.out):
+            with open(a.out) as f:
+                rec = json.load(f)
+        rec["accumulation"] = dict(accum_run(a, c, sd, params, dev), config=c, lang_len=a.lang_len, lr=a.lr, device=torch.cuda.get_device_name(dev))
+        print(json.dumps(rec["accumulation"]))
+        with open(a.out, "w") as f:
+            json.dump(rec, f, indent=1)
+        print("wrote", a.out)
+        return
+    kept = None
+    if os.path.exists(a.out):
+        with open(a.out) as f:
+            kept = json.load(f).get("accumulation")
     rec = {"config": c, "precision": a.precision, "parameters": params, "lang_len": a.lang_len, "warmup": a.warmup, "steps": a.steps, "lr": a.lr,
            "device": torch.cuda.get_device_name(dev), "runs": []}
     sync = lambda: torch.cuda.synchronize(dev)
@@ -96,13 +200,7 @@ def main():
         torch.cuda.empty_cache()
         torch.cuda.reset_peak_memory_stats(dev)
         tr = RdtTrainer(sd, heads=c["heads"], horizon=64, action_dim=128, lr=a.lr, precision=a.precision, device=dev)
-        g = torch.Generator(device=dev).manual_seed(99)
-        rn = lambda *s: torch.randn(*s, generator=g, device=dev)
-        amask = torch.zeros(B, 1, 128, device=dev)
-        amask[:, :, :10] = 1.0
-        args = (rn(B, a.lang_len, 4096), torch.ones(B, a.lang_len, dtype=torch.bool, device=dev), rn(B, a.img_len, 1152), rn(B, 1, 128),
-                torch.tanh(rn(B, 64, 128)) * amask, amask, torch.full((B,), 10.0, device=dev))
-        kw = dict(noise=rn(B, 64, 128), timesteps=torch.randint(0, 1000, (B,), generator=g, device=dev))
+        args, kw = inputs(a, B, dev)
         t_f = t_fb = t_o = 0.0
         losses = []
         for n in range(a.warmup + a.steps):
@@ -131,6 +229,8 @@ def main():
                 run["torch_autograd_yardstick"]["ratio_torch_over_this"] = run["torch_autograd_yardstick"]["fwd_bwd_ms"] / ((t_fb) * k)
         print(json.dumps(run))
         rec["runs"].append(run)
+    if kept is not None:
+        rec["accumulation"] = kept                # measured by --accum K: not this run's to drop
     with open(a.out, "w") as f:
         json.dump(rec, f, indent=1)
     print("wrote", a.out)

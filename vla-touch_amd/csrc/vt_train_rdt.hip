@@ -324,6 +324,71 @@ __global__ __launch_bounds__(256) void scale_mt_kernel(const MtEntry* __restrict
   }
 }
 
+// ------------------------------------------------------------------------------------------------ gradient accumulation
+// Folds one micro-batch's fresh gradients (fresh[k], a second device array of pointers: they are new allocations every micro-batch) into the
+// persistent fp32 accumulators, which are the table's g column, so that the clip and AdamW kernels read the accumulated gradient from the
+// table as it stands.  accumulate = 0 stores g * scale (first micro-batch of a window: no zero pass, the accumulator is not read), otherwise
+// acc = fma(g, scale, acc): one rounding per element and micro-batch in a fixed order, no atomics.  A chunk is read and written as 128-bit
+// words where both tensors are 16-byte aligned (a chunk starts 16 KiB into its tensor, so the tensor's alignment is the chunk's); what is
+// left of n behind the last whole quad, or the whole chunk of an unaligned tensor, goes element by element.
+__global__ __launch_bounds__(256) void grad_accum_mt_kernel(const MtEntry* __restrict__ tab, const float* const* __restrict__ fresh, int ntensors,
+                                                            float scale, int accumulate) {
+  int lo = 0, hi = ntensors - 1;
+  const long chunk = blockIdx.x;
+  while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (tab[mid].first_chunk <= chunk) lo = mid; else hi = mid - 1; }
+  const MtEntry e = tab[lo];
+  const long base = (chunk - e.first_chunk) * 4096;
+  const long left = e.n - base;
+  const int cnt = left < 4096 ? (int)left : 4096;
+  float* __restrict__ acc = e.g + base;
+  const float* __restrict__ g = fresh[lo] + base;
+  const bool aligned = ((((size_t)acc) | ((size_t)g)) & 15) == 0;
+  const int quads = aligned ? cnt >> 2 : 0;
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    const int j = it * 256 + threadIdx.x;
+    if (j >= quads) break;
+    const float4 gv = reinterpret_cast<const float4*>(g)[j];
+    float4 a;
+    if (accumulate) {
+      a = reinterpret_cast<const float4*>(acc)[j];
+      a.x = fmaf(gv.x, scale, a.x); a.y = fmaf(gv.y, scale, a.y); a.z = fmaf(gv.z, scale, a.z); a.w = fmaf(gv.w, scale, a.w);
+    } else {
+      a.x = gv.x * scale; a.y = gv.y * scale; a.z = gv.z * scale; a.w = gv.w * scale;
+    }
+    reinterpret_cast<float4*>(acc)[j] = a;
+  }
+  for (int i = quads * 4 + threadIdx.x; i < cnt; i += 256) acc[i] = accumulate ? fmaf(g[i], scale, acc[i]) : g[i] * scale;
+}
+// EMAModel.step alone over the table (the micro-batches that take no optimizer step): shadow -= (1 - decay) (shadow - p), the arithmetic of
+// vt_train.hip's ema_elem with contraction off, so it gives the bits of vt_ema_update_dev per tensor.  hyper[3] = 1 - decay.
+__device__ __forceinline__ float ema_elem_rdt(float sh, float p, float one_minus_decay) {
+#pragma clang fp contract(off)
+  return sh - one_minus_decay * (sh - p);
+}
+__global__ __launch_bounds__(256) void ema_mt_kernel(const MtEntry* __restrict__ tab, int ntensors, const float* __restrict__ hyper) {
+  const MtEntry e = mt_find(tab, ntensors, blockIdx.x);
+  if (!e.shadow) return;
+  const long base = ((long)blockIdx.x - e.first_chunk) * 4096;
+  const long left = e.n - base;
+  const int cnt = left < 4096 ? (int)left : 4096;
+  const float omd = hyper[3];
+  float* __restrict__ sh = e.shadow + base;
+  const float* __restrict__ p = e.p + base;
+  const bool aligned = ((((size_t)sh) | ((size_t)p)) & 15) == 0;
+  const int quads = aligned ? cnt >> 2 : 0;
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    const int j = it * 256 + threadIdx.x;
+    if (j >= quads) break;
+    const float4 pv = reinterpret_cast<const float4*>(p)[j];
+    float4 s = reinterpret_cast<const float4*>(sh)[j];
+    s.x = ema_elem_rdt(s.x, pv.x, omd); s.y = ema_elem_rdt(s.y, pv.y, omd); s.z = ema_elem_rdt(s.z, pv.z, omd); s.w = ema_elem_rdt(s.w, pv.w, omd);
+    reinterpret_cast<float4*>(sh)[j] = s;
+  }
+  for (int i = quads * 4 + threadIdx.x; i < cnt; i += 256) sh[i] = ema_elem_rdt(sh[i], p[i], omd);
+}
+
 // mean squared error of pred against target (fp32) and its gradient: loss = mean((pred - target)^2), dpred = 2 (pred - target) / n; one block
 template <typename T>
 __global__ __launch_bounds__(256) void mse_kernel(const T* __restrict__ pred, const float* __restrict__ tgt, T* __restrict__ dpred,
@@ -448,6 +513,17 @@ int vt_grad_clip_multi(const void* table, int ntensors, long total_chunks, float
   hipLaunchKernelGGL(sumsq_mt_kernel, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)s, (const MtEntry*)table, ntensors, chunk_part);
   hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(256), 0, (hipStream_t)s, chunk_part, total_chunks, max_norm, norm_coef);
   hipLaunchKernelGGL(scale_mt_kernel, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)s, (const MtEntry*)table, ntensors, norm_coef);
+  return LAUNCH_OK();
+}
+int vt_grad_accum_multi(const void* table, const void* fresh, int ntensors, long total_chunks, float scale, int accumulate, vt_stream_t s) {
+  if (!table || !fresh || ntensors < 1 || total_chunks < 1 || !(scale > 0.f)) return vt_fail(VT_ERR_ARG, "vt_grad_accum_multi: bad argument");
+  hipLaunchKernelGGL(grad_accum_mt_kernel, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)s, (const MtEntry*)table, (const float* const*)fresh, ntensors,
+                     scale, accumulate);
+  return LAUNCH_OK();
+}
+int vt_ema_multi(const void* table, int ntensors, long total_chunks, const float* hyper, vt_stream_t s) {
+  if (!table || !hyper || ntensors < 1 || total_chunks < 1) return vt_fail(VT_ERR_ARG, "vt_ema_multi: bad argument");
+  hipLaunchKernelGGL(ema_mt_kernel, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)s, (const MtEntry*)table, ntensors, hyper);
   return LAUNCH_OK();
 }
 int vt_mse_loss(const void* pred, const float* target, void* dpred, float* loss, long n, int dt, vt_stream_t s) {

@@ -211,7 +211,8 @@ class RdtTrainer(_Optimizer):
     def __init__(self, sd, *, heads: int, horizon: int, action_dim: int, rms_mode: str = "meansq", prediction_type: str = "sample",
                  num_train_timesteps: int = 1000, beta_schedule: str = "squaredcos_cap_v2", precision: str = "fp32", lr: float = 5e-6,
                  betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, max_grad_norm: float = 1.0, lr_scheduler: str = "constant",
-                 lr_warmup_steps: int = 500, ema: Optional[dict] = None, config: Optional[dict] = None, device="cuda"):
+                 lr_warmup_steps: int = 500, ema: Optional[dict] = None, config: Optional[dict] = None, gradient_accumulation_steps: int = 1,
+                 device="cuda"):
         if precision not in ("fp32", "bf16"):
             raise ValueError(f"precision must be 'fp32' or 'bf16', got {precision!r} (no fp16 training mode: its gradients underflow without loss scaling)")
         if prediction_type not in PREDICTION_TYPES:
@@ -219,6 +220,8 @@ class RdtTrainer(_Optimizer):
         if rms_mode not in ("meansq", "var"):
             raise ValueError(f"rms_mode must be 'meansq' or 'var', got {rms_mode!r}")
         lr_at(lr, lr_scheduler, 0, lr_warmup_steps)                       # raises on an unknown scheduler
+        if int(gradient_accumulation_steps) != gradient_accumulation_steps or gradient_accumulation_steps < 1:
+            raise ValueError(f"gradient_accumulation_steps must be an integer >= 1, got {gradient_accumulation_steps!r}")
         self.device = dev = L.require_gpu(device)
         self.p: "OrderedDict[str, torch.Tensor]" = OrderedDict((k, v.detach().to(dev, F32).contiguous().clone()) for k, v in sd.items())
         self.g: Dict[str, torch.Tensor] = {}
@@ -246,8 +249,12 @@ class RdtTrainer(_Optimizer):
         self.ema_cfg = dict(update_after_step=0, inv_gamma=1.0, power=2 / 3, min_value=0.0, max_value=0.9999)
         self.ema_cfg.update(ema or {})
         self.config = config
-        self.step_count = 0
-        self.ema_updates = 0
+        self.k = int(gradient_accumulation_steps)             # micro-batches per optimizer step (accelerate's gradient_accumulation_steps)
+        self.step_count = 0                                   # optimizer steps taken: feeds the lr schedule and AdamW's bias correction
+        self.ema_updates = 0                                  # EMAModel.optimization_step: one per micro-batch
+        self.micro_step = 0                                   # micro-batches folded into the open accumulation window
+        self.sync_gradients = False                           # the last train_step took the optimizer step
+        self._acc: Dict[str, torch.Tensor] = {}               # k > 1: persistent fp32 accumulators, the table's g column
         self._m: Dict[str, torch.Tensor] = {}                 # AdamW moments and the EMA copy appear with the first optimizer step (the parameters are
         self._v: Dict[str, torch.Tensor] = {}                 # still the initial ones then), so a trainer that only evaluates the loss holds one copy
         self.shadow: Dict[str, torch.Tensor] = {}
@@ -268,8 +275,9 @@ class RdtTrainer(_Optimizer):
 
     # ---- _Optimizer plumbing
     def _all_params(self):
+        src = self._acc if self.k > 1 else self.g
         for k, v in self.p.items():
-            yield k, v, self.g.get(k)
+            yield k, v, src.get(k)
 
     def _ema_decay(self, step: int) -> float:
         """`step` = number of EMA updates including this one; EMAModel.step evaluates get_decay at the count before it."""
@@ -277,6 +285,11 @@ class RdtTrainer(_Optimizer):
 
     def _shadow_source(self, name: str) -> torch.Tensor:
         return self.p[name]
+
+    @property
+    def global_step(self) -> int:
+        """Optimizer steps taken (train.py's global_step)."""
+        return self.step_count
 
     @property
     def grad_norm(self) -> torch.Tensor:
@@ -489,6 +502,8 @@ class RdtTrainer(_Optimizer):
     def _table(self):
         """The multi-tensor table vt_grad_clip_multi / vt_adamw_ema_multi read: {p, g, m, v, shadow, n, first_chunk} per tensor, on the device."""
         rows, chunk0 = [], 0
+        if self.k > 1 and not self._acc:
+            self._acc = {k: torch.empty_like(v) for k, v in self.p.items()}          # never read before the window's first, storing, accumulate
         if not self.shadow:
             self._m = {k: torch.zeros_like(v) for k, v in self.p.items()}
             self._v = {k: torch.zeros_like(v) for k, v in self.p.items()}
@@ -502,6 +517,7 @@ class RdtTrainer(_Optimizer):
             chunk0 += (pt.numel() + 4095) // 4096
         key = tuple(r[1] for r in rows)
         if key != self._table_key:                                # gradients are fresh allocations each step: their addresses usually repeat, not always
+                                                                  # (k > 1: the g column holds the accumulators, so the table is built once)
             self._mt_dev = torch.tensor(rows, dtype=torch.int64).to(self.device)
             self._chunk_part = _empty((chunk0,), self.device)
             self._table_key, self._chunks = key, chunk0
@@ -511,9 +527,11 @@ class RdtTrainer(_Optimizer):
         """clip_grad_norm_(max_grad_norm) -> AdamW -> EMA (train.py:440-448), three launches over one table; no host read."""
         if hyper is not None:
             raise NotImplementedError("RdtTrainer: hipGraph capture of the step is not built")
+        if self.k > 1 and self.micro_step != self.k:
+            raise RuntimeError(f"optimizer_step needs a full accumulation window ({self.micro_step} of {self.k} micro-batches accumulated)")
         lib, dev = L.lib(), self.device
         tab, n, chunks = self._table()
-        self.lr = lr_at(self.base_lr, self.lr_scheduler, self.step_count, self.lr_warmup_steps)
+        self.lr = lr_at(self.base_lr, self.lr_scheduler, self.step_count, self.lr_warmup_steps * self.k)      # train.py:302 scales the warm-up by k
         self.step_count += 1
         self.ema_updates += 1
         host = torch.zeros(4, dtype=F32)
@@ -522,6 +540,40 @@ class RdtTrainer(_Optimizer):
         L.check(lib.vt_grad_clip_multi(L.ptr(tab), n, chunks, self.max_grad_norm, L.ptr(self._chunk_part), L.ptr(self._norm_coef), _sp(dev)), "vt_grad_clip_multi")
         L.check(lib.vt_adamw_ema_multi(L.ptr(tab), n, chunks, L.ptr(hy), self.betas[0], self.betas[1], self.eps, self.wd, _sp(dev)), "vt_adamw_ema_multi")
         self._refresh16()
+        self.micro_step, self.sync_gradients = 0, True
+
+    def accumulate(self) -> None:
+        """k > 1: fold the gradients get_loss left in `self.g` into the accumulators, scaled by 1 / k (accelerator.backward's loss / k); the
+        first micro-batch of a window stores, the others add.  One launch; the fresh gradients' addresses travel as a second device array."""
+        if self.k == 1:
+            raise RuntimeError("accumulate: the trainer was built with gradient_accumulation_steps=1")
+        if self.micro_step >= self.k:
+            raise RuntimeError("accumulate: the window is full, call optimizer_step")
+        tab, n, chunks = self._table()
+        ptrs = []
+        for name, pt in self.p.items():
+            gt = self.g.get(name)
+            if gt is None:
+                raise RuntimeError(f"no gradient for {name}: call get_loss first")
+            if gt.dtype != F32 or gt.numel() != pt.numel():
+                raise RuntimeError(f"gradient of {name}: fp32 with {pt.numel()} elements expected")
+            if not gt.is_contiguous():
+                gt = self.g[name] = gt.contiguous()
+            ptrs.append(gt.data_ptr())
+        fresh = torch.tensor(ptrs, dtype=torch.int64).to(self.device)
+        L.check(L.lib().vt_grad_accum_multi(L.ptr(tab), L.ptr(fresh), n, chunks, 1.0 / self.k, int(self.micro_step > 0), _sp(self.device)),
+                "vt_grad_accum_multi")
+        self.micro_step += 1
+
+    def ema_step(self) -> None:
+        """EMAModel.step alone (train.py:448 on a micro-batch without an optimizer step): the shadows move toward the unchanged parameters."""
+        tab, n, chunks = self._table()
+        self.ema_updates += 1
+        host = torch.zeros(4, dtype=F32)
+        L.check(L.lib().vt_train_hyper(self.lr, self.betas[0], self.betas[1], max(1, self.step_count), self._ema_decay(self.ema_updates), L.ptr(host)),
+                "vt_train_hyper")
+        L.check(L.lib().vt_ema_multi(L.ptr(tab), n, chunks, L.ptr(host.to(self.device)), _sp(self.device)), "vt_ema_multi")
+        self.sync_gradients = False
 
     def train_step(self, lang_tokens, lang_attn_mask, img_tokens, state_tokens, action_gt, action_mask, ctrl_freqs, *, noise=None, timesteps=None):
         B = torch.as_tensor(action_gt).shape[0]
@@ -530,12 +582,20 @@ class RdtTrainer(_Optimizer):
         if timesteps is None:
             timesteps = torch.randint(0, self.num_train_timesteps, (B,), device=self.device)
         loss = self.get_loss(lang_tokens, lang_attn_mask, img_tokens, state_tokens, action_gt, action_mask, ctrl_freqs, noise=noise, timesteps=timesteps)
-        self.optimizer_step()
+        if self.k == 1:
+            self.optimizer_step()
+            return loss
+        self.accumulate()
+        if self.micro_step == self.k:
+            self.optimizer_step()
+        else:
+            self.ema_step()
         return loss
 
     # ---- state
     def grads(self):
-        return OrderedDict((k, self.g[k].detach().cpu().reshape(self.p[k].shape)) for k in self.p)
+        src = self._acc if self.k > 1 else self.g
+        return OrderedDict((k, src[k].detach().cpu().reshape(self.p[k].shape)) for k in self.p)
 
     def state_dict(self):
         return OrderedDict((k, v.detach().cpu().clone()) for k, v in self.p.items())
@@ -557,3 +617,93 @@ class RdtTrainer(_Optimizer):
         with open(os.path.join(path, "config.json"), "w") as fjs:
             json.dump(self.config, fjs, indent=2)
         save_file({k: v.contiguous() for k, v in (self.ema_state_dict() if ema else self.state_dict()).items()}, os.path.join(path, "model.safetensors"))
+
+    # ---- checkpoints (train.py:455-460 accelerator.save_state + the ema/ directory; :377-385 on resume)
+    _HYPER = ("base_lr", "wd", "betas", "eps", "max_grad_norm", "lr_scheduler", "lr_warmup_steps", "ema_cfg")
+
+    def save_checkpoint(self, path: str) -> None:
+        """`path`/checkpoint/{model,adam_m,adam_v}.safetensors (fp32 master weights and AdamW moments), `path`/ema/ (the averaged weights as
+        RDTRunner.from_pretrained reads them: the reference's checkpoint-N/ema placement) and `path`/trainer_state.json (the counters, k,
+        precision, hyper-parameters).  Only between accumulation windows, where the reference saves."""
+        if self.micro_step != 0:
+            raise RuntimeError(f"save_checkpoint in the middle of an accumulation window ({self.micro_step} of {self.k} micro-batches): "
+                               "the partial gradient sum is not part of a checkpoint")
+        from safetensors.torch import save_file
+        cpu = lambda d: {k: (d[k] if k in d else torch.zeros_like(v)).detach().cpu().contiguous() for k, v in self.p.items()}
+        os.makedirs(os.path.join(path, "checkpoint"), exist_ok=True)
+        os.makedirs(os.path.join(path, "ema"), exist_ok=True)
+        save_file(cpu(self.p), os.path.join(path, "checkpoint", "model.safetensors"))
+        save_file(cpu(self._m), os.path.join(path, "checkpoint", "adam_m.safetensors"))
+        save_file(cpu(self._v), os.path.join(path, "checkpoint", "adam_v.safetensors"))
+        save_file({k: v.contiguous() for k, v in self.ema_state_dict().items()}, os.path.join(path, "ema", "model.safetensors"))
+        if self.config is not None:
+            with open(os.path.join(path, "ema", "config.json"), "w") as fjs:
+                json.dump(self.config, fjs, indent=2)
+        state = dict(step_count=self.step_count, ema_updates=self.ema_updates, global_step=self.global_step, gradient_accumulation_steps=self.k,
+                     precision=self.precision, hyper={n: getattr(self, n) for n in self._HYPER})
+        with open(os.path.join(path, "trainer_state.json"), "w") as fjs:
+            json.dump(state, fjs, indent=2)
+
+    def load_checkpoint(self, path: str) -> None:
+        """Restore what save_checkpoint wrote into this trainer (built on the same model with the same gradient_accumulation_steps): weights,
+        moments, EMA shadows, counters and hyper-parameters; training then continues bit for bit.  Unlike the reference, which starts its
+        EMAModel.optimization_step at 0 again, the EMA update count is restored."""
+        from safetensors.torch import load_file
+        with open(os.path.join(path, "trainer_state.json")) as fjs:
+            state = json.load(fjs)
+        if state["gradient_accumulation_steps"] != self.k:
+            raise ValueError(f"checkpoint was written with gradient_accumulation_steps={state['gradient_accumulation_steps']}, this trainer has {self.k}")
+        parts = {n: load_file(os.path.join(path, *f)) for n, f in (("p", ("checkpoint", "model.safetensors")), ("m", ("checkpoint", "adam_m.safetensors")),
+                                                                   ("v", ("checkpoint", "adam_v.safetensors")), ("ema", ("ema", "model.safetensors")))}
+        for n, d in parts.items():
+            if set(d) != set(self.p) or any(d[k].shape != v.shape or d[k].dtype != F32 for k, v in self.p.items()):
+                raise ValueError(f"checkpoint {path}: the {n} tensors do not match this trainer's parameters")
+        dev = self.device
+        for k, v in self.p.items():
+            v.copy_(parts["p"][k])
+        self._m = {k: parts["m"][k].to(dev).contiguous() for k in self.p}
+        self._v = {k: parts["v"][k].to(dev).contiguous() for k in self.p}
+        self.shadow = {k: parts["ema"][k].to(dev).contiguous() for k in self.p}
+        for n, val in state["hyper"].items():
+            setattr(self, n, tuple(val) if n == "betas" else val)
+        self.step_count, self.ema_updates = state["step_count"], state["ema_updates"]
+        self.micro_step, self.sync_gradients, self._table_key = 0, False, None
+        self.lr = lr_at(self.base_lr, self.lr_scheduler, max(0, self.step_count - 1), self.lr_warmup_steps * self.k)
+        self._refresh16()
+
+
+# ---------------------------------------------------------------------------------------------- the loop around the trainer
+def latest_checkpoint(output_dir: str) -> Optional[str]:
+    """The `checkpoint-N` entry of `output_dir` with the largest N (train.py:364-367), or None."""
+    if not os.path.isdir(output_dir):
+        return None
+    dirs = [d for d in os.listdir(output_dir) if d.startswith("checkpoint-") and d.split("-", 1)[1].isdigit()]
+    return max(dirs, key=lambda d: int(d.split("-", 1)[1])) if dirs else None
+
+
+def finetune(trainer: RdtTrainer, batches, *, max_train_steps: int, checkpointing_period: Optional[int] = None, output_dir: Optional[str] = None,
+             resume_from_checkpoint: Optional[str] = None) -> List[torch.Tensor]:
+    """The reference's loop (train.py:359-489) around `trainer.train_step`: every item of `batches` is one micro-batch, a mapping of train_step's
+    keyword arguments.  Stops when `max_train_steps` optimizer steps are taken; writes `output_dir`/checkpoint-{global_step} every
+    `checkpointing_period` optimizer steps; `resume_from_checkpoint` = a checkpoint's name under `output_dir` or "latest" (a missing one starts a
+    new run, as there); ends with save_pretrained(output_dir) and the averaged weights in `output_dir`/ema.  Like the reference's loop it does
+    not skip the batches an earlier run consumed: `batches` continues where the caller wants.  -> the micro-batch losses (device tensors)."""
+    if (checkpointing_period or resume_from_checkpoint) and output_dir is None:
+        raise ValueError("finetune: checkpointing_period / resume_from_checkpoint need output_dir")
+    if resume_from_checkpoint:
+        name = latest_checkpoint(output_dir) if resume_from_checkpoint == "latest" else os.path.basename(os.path.normpath(resume_from_checkpoint))
+        if name is not None and os.path.isdir(os.path.join(output_dir, name)):
+            trainer.load_checkpoint(os.path.join(output_dir, name))
+    losses = []
+    for batch in batches:
+        if trainer.global_step >= max_train_steps:
+            break
+        losses.append(trainer.train_step(**batch))
+        if trainer.sync_gradients and checkpointing_period and trainer.global_step % checkpointing_period == 0:
+            trainer.save_checkpoint(os.path.join(output_dir, f"checkpoint-{trainer.global_step}"))
+    if output_dir is not None:
+        if trainer.micro_step != 0:
+            raise RuntimeError("finetune: the batches ended in the middle of an accumulation window")
+        trainer.save_pretrained(output_dir)
+        trainer.save_pretrained(os.path.join(output_dir, "ema"), ema=True)
+    return losses
