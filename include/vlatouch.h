@@ -48,6 +48,22 @@ int vt_prof_collect(double* total_ms, double* flops, double* bytes, long* launch
  * Replaces torch nn.Linear / nn.Conv1d / nn.ConvTranspose1d calls of
  * bridge/networks/conditional_unet_1D.py:25,34,49,83, bridge_controller.py:42-48, HF Dinov2 linears. */
 int vt_gemm(const void* params, vt_stream_t stream);
+/* Which kernel vt_gemm runs for a parameter block (csrc/vt_gemm_route.hip: the one function that decides; host code only, nothing is launched, no
+ * GPU is needed).  VT_ROUTE_ROWSPLIT = two launches: the full 256-row blocks on the 256-square tile (head: VT_ROUTE_PT or VT_ROUTE_PP) and the
+ * remaining <= 64 rows as a launch of their own (tail: any route); vt_gemm_route_split reports both for a block that routes there (else -22). */
+enum { VT_ROUTE_UNSUPPORTED = 0,   /* vt_gemm returns -95 */
+       VT_ROUTE_BAD_ARG = 1,       /* vt_gemm returns -22 */
+       VT_ROUTE_REG = 2,           /* register-staged gemm_kernel (csrc/vt_gemm.hip) */
+       VT_ROUTE_F32R = 3,          /* exact-fp32 LDS-DMA ring, gemm_f32r_kernel */
+       VT_ROUTE_GLDS = 4,          /* 128-column LDS-DMA tile, gemm_glds_kernel */
+       VT_ROUTE_PP = 5,            /* 256-square ping-pong tile, gemm_pp256d_kernel */
+       VT_ROUTE_PT = 6,            /* its persistent form, gemm_pt_kernel */
+       VT_ROUTE_PPK = 7,           /* 160 x 128 split-K tile, gemm_ppk_kernel */
+       VT_ROUTE_PW = 8,            /* weights-in-registers tile, gemm_pw_kernel */
+       VT_ROUTE_PWS = 9,           /* small-M packed tile, gemm_pws_kernel */
+       VT_ROUTE_ROWSPLIT = 10 };
+int vt_gemm_route_of(const void* params);
+int vt_gemm_route_split(const void* params, int* head_route, int* tail_route);
 /* Frozen 16-bit weights W [N][K] (row stride ldw) -> a second copy in MFMA fragment order [N/32][K/16][64 lanes][8] (N % 32 == 0,
  * K % 16 == 0; same byte count): VtGemmParams.Wp of the weights-in-registers GEMM tile (csrc/vt_gemm_pw.hip).  Replaces nothing in
  * the reference (torch.nn.Linear keeps one layout, models/rdt/blocks.py:144-183); it is the load-time packing of this engine. */

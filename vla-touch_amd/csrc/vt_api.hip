@@ -1,9 +1,14 @@
-// vt_api.hip — C-ABI entry points for the primitives (unit-test hooks) and the MFMA layout self test.
+// vt_api.hip — C-ABI entry points for the primitives (unit-test hooks), the profiling and tuning controls, and the MFMA layout self test.
 #include <string.h>
 #include "vt_common.h"
 #include "vt_kernels.h"
 #include "vt_host.h"
+#include "vt_gemm_route.h"
+#include "vt_prof.h"
+#include "vt_unet_int.h"
 #include "../../include/vlatouch.h"
+
+VtProfState g_vt_prof;
 
 extern "C" {
 
@@ -15,6 +20,50 @@ int vt_gemm(const void* params, vt_stream_t stream) {
   const int r = vt_gemm_launch(*reinterpret_cast<const VtGemmParams*>(params), (hipStream_t)stream);
   if (r) vt_fail(r, "vt_gemm: rejected (alignment: K, lda, ldw multiples of 8 bf16 / 4 fp32; conv: cin likewise) or launch failure");
   return r;
+}
+// which kernel vt_gemm would run for this block (VT_ROUTE_*); no launch
+int vt_gemm_route_of(const void* params) {
+  if (!params) return VT_ROUTE_BAD_ARG;
+  return vt_gemm_route(*reinterpret_cast<const VtGemmParams*>(params));
+}
+int vt_gemm_route_split(const void* params, int* head_route, int* tail_route) {
+  if (!params || !head_route || !tail_route) return vt_fail(VT_ERR_ARG, "vt_gemm_route_split: null argument");
+  const VtGemmParams& p = *reinterpret_cast<const VtGemmParams*>(params);
+  if (vt_gemm_route(p) != VT_GEMM_ROWSPLIT) return vt_fail(VT_ERR_ARG, "vt_gemm_route_split: the block does not route to VT_ROUTE_ROWSPLIT");
+  VtGemmParams head, tail;
+  *head_route = vt_gemm_rowsplit(p, head, tail);
+  *tail_route = vt_gemm_route(tail);
+  return VT_OK;
+}
+int vt_tune(int knob, int value) {
+  if (knob == 1 && (value == 0 || value == 4 || value == 8)) { vt_gemm_pw_tune(value); return VT_OK; }
+  if (knob == 2 || knob == 8) { vt_gemm_route_tune(knob, value); return VT_OK; }
+  if (knob == 4) { vt_gemm_pws_tune(value); return VT_OK; }
+  if (knob == 6) { vt_attn_kvt_tune(value); return VT_OK; }
+  if (knob == 7) { vt_unet_fused_tune(value); return VT_OK; }
+  if (knob == 9 && (value == 0 || value == 1 || value == 3 || value == 6)) { vt_attn16g_tune(value); return VT_OK; }
+  return vt_fail(VT_ERR_ARG, "vt_tune: unknown knob %d / value %d", knob, value);
+}
+// ---- profiling control
+int vt_prof_enable(int on) {
+  g_vt_prof.on = on != 0;
+  g_vt_prof.mode = on > 1 ? on : 1;
+  if (on) { g_vt_prof.used = 0; g_vt_prof.flops = 0.0; g_vt_prof.bytes = 0.0; }
+  return VT_OK;
+}
+// After the stream has been synchronised by the caller: total milliseconds, algorithmic flops and bytes, launch count.
+int vt_prof_collect(double* total_ms, double* flops, double* bytes, long* launches) {
+  double ms = 0.0;
+  for (int i = 0; i < g_vt_prof.used; ++i) {
+    float t = 0.f;
+    if (hipEventElapsedTime(&t, g_vt_prof.ev[2 * i], g_vt_prof.ev[2 * i + 1]) != hipSuccess) return VT_ERR_LAUNCH;
+    ms += t;
+  }
+  if (total_ms) *total_ms = ms;
+  if (flops) *flops = g_vt_prof.flops;
+  if (bytes) *bytes = g_vt_prof.bytes;
+  if (launches) *launches = g_vt_prof.used;
+  return VT_OK;
 }
 int vt_attention(const void* params, vt_stream_t stream) {
   if (!params) return vt_fail(VT_ERR_ARG, "vt_attention: null params");
@@ -58,6 +107,10 @@ int vt_action_normalize(const float* in, float* out, const float* mins, const fl
 }
 
 }  // extern "C"
+
+static_assert(VT_ROUTE_UNSUPPORTED == VT_GEMM_UNSUPPORTED && VT_ROUTE_BAD_ARG == VT_GEMM_BAD_ARG && VT_ROUTE_REG == VT_GEMM_REG && VT_ROUTE_F32R == VT_GEMM_F32R &&
+              VT_ROUTE_GLDS == VT_GEMM_GLDS && VT_ROUTE_PP == VT_GEMM_PP && VT_ROUTE_PT == VT_GEMM_PT && VT_ROUTE_PPK == VT_GEMM_PPK && VT_ROUTE_PW == VT_GEMM_PW &&
+              VT_ROUTE_PWS == VT_GEMM_PWS && VT_ROUTE_ROWSPLIT == VT_GEMM_ROWSPLIT, "include/vlatouch.h route codes = enum VtGemmRoute");
 
 // ---------------------------------------------------------------- MFMA layout self test
 namespace {

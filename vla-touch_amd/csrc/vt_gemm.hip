@@ -1,4 +1,6 @@
-// vt_gemm.hip — generic MFMA GEMM / implicit-conv1d kernel for gfx950 (see vt_gemm.h for semantics).
+// vt_gemm.hip — generic MFMA GEMM / implicit-conv1d kernel for gfx950 (see vt_gemm.h for semantics): the register-staged kernel and its launcher.
+// It takes what no LDS-DMA kernel claims (VT_GEMM_REG in vt_gemm_route.hip, which also holds vt_gemm_launch); VLATOUCH_GEMM_TRACE=1 prints one line
+// per launch that lands here.
 //
 // Structure (v1, register-staged): 256 threads = 4 waves; block tile BM x BN x BK with BK = 128 bytes of
 // the compute type per row (64 bf16 / 32 f32).  Global -> registers (16 B per thread per pass, coalesced
@@ -9,10 +11,8 @@
 // the epilogue reads bias/colscale/residual and writes C with 16-B (f32) / 8-B (bf16) vectors.
 #include <type_traits>
 #include "vt_common.h"
-#include "vt_gemm.h"
+#include "vt_gemm_route.h"
 #include "vt_prof.h"
-
-VtProfState g_vt_prof;
 
 namespace {
 
@@ -355,25 +355,8 @@ int launch_cfg(const VtGemmParams& p, hipStream_t s) {
 
 }  // namespace
 
-// Host entry used by every driver in the library (and exported through vt_gemm in vt_api.hip).
-int vt_gemm_launch(const VtGemmParams& p, hipStream_t s) {
-  if (p.M <= 0 || p.N <= 0 || p.K <= 0) return VT_ERR_ARG;
-  const int epc = p.w_dtype == VT_F32 ? 4 : 8;   // k elements per staged chunk (bf16 and split-bf16: 8)
-  const int epa = epc;  // A chunks are loaded in units of the compute type's chunk
-  if (p.K % epc || p.ldw % epc || p.lda % epa) return VT_ERR_ARG;      // 16-B chunk granularity
-  if (p.taps && (p.cin % epc || p.K != p.taps * p.cin)) return VT_ERR_ARG;
-  if (p.splitk < 1 || p.groups < 1) return VT_ERR_ARG;
-  if (p.splitk > 1 && p.c_dtype != VT_F32) return VT_ERR_ARG;
-  if (p.pf_ptr && p.pf_bytes >= (1ul << 31)) return VT_ERR_ARG;      // prefetch hint: 32-bit byte arithmetic in the kernel
-  if (p.xn_out || p.rs_part) {        // fused RMSNorm hand-off: only the weights-in-registers tile implements it, and the caller has checked that it takes this shape
-    if (p.groups != 1 || (p.xn_out && (!p.xn_gain || !p.xn_part || p.c_dtype != VT_F32 || !p.residual || p.act != VT_ACT_NONE || p.hn_w0 || p.hn_w1 || p.xn_ld % 4)) ||
-        (p.rs_part && (p.rs_n < 4 || p.rs_n > 32 || p.rs_n % 4)) || !vt_gemm_fast_eligible(p) || !vt_gemm_pw_eligible(p))
-      return VT_ERR_UNSUPPORTED;
-    return vt_gemm_pw_launch(p, s);
-  }
-  if (vt_gemm_pws_eligible(p) && (p.M <= 192 || !vt_gemm_fast_eligible(p))) return vt_gemm_pws_launch(p, s);   // small M, frozen packed weights
-  if (vt_gemm_fast_eligible(p)) return vt_gemm_fast_launch(p, s);     // large bf16 GEMMs: LDS-DMA pipeline (vt_gemm_fast.hip)
-  if (p.hn_w0 || p.hn_w1 || p.cmap) return VT_ERR_UNSUPPORTED;         // fused head-norm / tile-stream output exist only on the fast path
+// The register-staged kernel's launcher (VT_GEMM_REG of vt_gemm_route.hip, which has checked the arguments and admits exactly these dtype triples).
+int vt_gemm_reg_launch(const VtGemmParams& p, hipStream_t s) {
   if (p.a_dtype == VT_BF16 && p.w_dtype == VT_BF16) {
     if (p.c_dtype == VT_BF16) return launch_cfg<bf16_t, bf16_t, bf16_t>(p, s);
     if (p.c_dtype == VT_F32) return launch_cfg<bf16_t, bf16_t, float>(p, s);
@@ -387,30 +370,7 @@ int vt_gemm_launch(const VtGemmParams& p, hipStream_t s) {
   if (p.a_dtype == VT_F32 && p.w_dtype == VT_BF16) {
     return p.c_dtype == VT_BF16 ? launch_cfg<float, bf16_t, bf16_t>(p, s) : launch_cfg<float, bf16_t, float>(p, s);
   }
-  if (vt_gemm_f32r_eligible(p)) return vt_gemm_f32r_launch(p, s);      // exact fp32, few blocks per CU: LDS-DMA ring (vt_gemm_f32r.hip)
   if (p.a_dtype == VT_F32 && p.w_dtype == VT_F32 && p.c_dtype == VT_F32) return launch_cfg<float, float, float>(p, s);
   if (p.a_dtype == VT_F32 && p.w_dtype == VT_F32X3 && p.c_dtype == VT_F32) return launch_cfg<float, x3_t, float>(p, s);
   return VT_ERR_UNSUPPORTED;
-}
-
-// ---- profiling control (exported through include/vlatouch.h)
-extern "C" int vt_prof_enable(int on) {
-  g_vt_prof.on = on != 0;
-  g_vt_prof.mode = on > 1 ? on : 1;
-  if (on) { g_vt_prof.used = 0; g_vt_prof.flops = 0.0; g_vt_prof.bytes = 0.0; }
-  return VT_OK;
-}
-// After the stream has been synchronised by the caller: total milliseconds, algorithmic flops and bytes, launch count.
-extern "C" int vt_prof_collect(double* total_ms, double* flops, double* bytes, long* launches) {
-  double ms = 0.0;
-  for (int i = 0; i < g_vt_prof.used; ++i) {
-    float t = 0.f;
-    if (hipEventElapsedTime(&t, g_vt_prof.ev[2 * i], g_vt_prof.ev[2 * i + 1]) != hipSuccess) return VT_ERR_LAUNCH;
-    ms += t;
-  }
-  if (total_ms) *total_ms = ms;
-  if (flops) *flops = g_vt_prof.flops;
-  if (bytes) *bytes = g_vt_prof.bytes;
-  if (launches) *launches = g_vt_prof.used;
-  return VT_OK;
 }

@@ -13,7 +13,7 @@
 // Epilogue: + bias, fp32 row-major C (or the raw split-K slab).  Anything else (activation, column scale, residual, 16-bit types,
 // K % 32 != 0) stays on gemm_kernel.
 #include "vt_common.h"
-#include "vt_gemm.h"
+#include "vt_gemm_route.h"
 #include "vt_prof.h"
 
 namespace {
@@ -217,7 +217,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32r_kernel(const VtGemmParams p)
 
 }  // namespace
 
-bool vt_gemm_f32r_eligible(const VtGemmParams& p) {
+bool vt_gemm_f32r_fits(const VtGemmParams& p) {
   if (p.a_dtype != VT_F32 || (p.w_dtype != VT_F32 && p.w_dtype != VT_F32X3) || p.c_dtype != VT_F32) return false;
   if (p.w_dtype == VT_F32X3 && p.K % 64) return false;          // K % 64: gemm_kernel's slices
   if (p.act != VT_ACT_NONE || p.colscale || p.residual || p.hn_w0 || p.hn_w1 || p.cmap) return false;

@@ -11,10 +11,11 @@
 // before the MFMAs of tile t).  Blocks are dealt to XCDs in contiguous bands of tiles, and inside a band in super-rows of
 // GM m-tiles, so neighbouring tiles share operand panels in that XCD's private L2.
 // Operands are swapped (D = W_tile A_tile^T) so a lane ends with 4 consecutive n of one row m.
-// Epilogue: vt_gemm_epilogue.h (shared with the ping-pong kernels vt_gemm_pp.hip / vt_gemm_ppk.hip, which take the shapes
-// their tiles fit: this kernel is the fallback for every other large 16-bit GEMM).
+// Epilogue: vt_gemm_epilogue.h (shared with the ping-pong kernels vt_gemm_pp.hip / vt_gemm_ppk.hip).
+// Dispatch: this file launches gemm_glds_kernel only.  Which large 16-bit GEMMs land here is decided in vt_gemm_route.hip (VT_GEMM_GLDS: what
+// none of the other tiles of the family claims); vt_gemm_lds_fits below is the contract of the whole family.
 #include "vt_common.h"
-#include "vt_gemm.h"
+#include "vt_gemm_route.h"
 #include "vt_gemm_epilogue.h"
 #include "vt_prof.h"
 
@@ -128,7 +129,8 @@ __global__ __launch_bounds__(2 * BN, MINW * (BN / 128)) void gemm_glds_kernel(co
 
 }  // namespace
 
-bool vt_gemm_fast_eligible(const VtGemmParams& p) {
+// what the LDS-DMA family (this kernel and the tiles of vt_gemm_pp / pt / ppk / pw.hip) computes, and the smallest grid worth its pipeline
+bool vt_gemm_lds_fits(const VtGemmParams& p) {
   if ((p.a_dtype != VT_BF16 && p.a_dtype != VT_F16) || p.w_dtype != p.a_dtype || p.taps != 0 || p.splitk != 1) return false;
   if (p.c_dtype != p.a_dtype && p.c_dtype != VT_F32) return false;
   if (p.K % BK || p.lda % 8 || p.ldw % 8 || p.N % 4 || p.ldc % 4 || (p.residual && p.ldr % 4)) return false;
@@ -139,7 +141,7 @@ bool vt_gemm_fast_eligible(const VtGemmParams& p) {
   return tiles >= 96;
 }
 
-bool vt_gemm_can_fuse_headnorm(const VtGemmParams& p) { return vt_gemm_fast_eligible(p) && (p.N % 64) == 0; }
+bool vt_gemm_can_fuse_headnorm(const VtGemmParams& p) { return vt_gemm_lds_fits(p) && (p.N % 64) == 0; }
 
 template <typename T16, typename TC, int BM, int CMAP>
 static void launch_variant(int variant, dim3 grid, hipStream_t s, const VtGemmParams& p, int tiles_n, int per_group, int total) {
@@ -155,29 +157,7 @@ int vt_gemm_fast_launch(const VtGemmParams& p, hipStream_t s) {
   // Measured on MI355X (tools/gemm_bench.py).  128-column tiles: one LDS stage with 4 co-resident blocks per CU (1024 block
   // slots) beats in-block double buffering at 2 blocks/CU on every shape of this path (cond-K/V 561 -> 854 TF/s, K=768 DINOv2
   // GEMMs 330 -> 490) except when the grid cannot fill the slots, where the two-stage kernel hides latency inside the block;
-  // 128-row tiles when they fill the slots, else 64-row tiles.  GEMMs with several rounds of 256-square tiles go to the
-  // ping-pong kernel of vt_gemm_pp.hip (half the L2 -> LDS bytes per flop).
-  // A ragged last row block that costs a whole extra round of 256-square tiles (DINOv2-base: 64 images x 257 tokens = 64 x 256 + 64
-  // rows; fc1's 65 x 12 = 780 tiles are 3.05 rounds of the 256 CUs): the full row blocks go to the ping-pong kernel, the <= 64 remaining
-  // rows to a second small launch (rows are independent: an exact row split).
-  if (vt_gemm_pw_eligible(p)) return vt_gemm_pw_launch(p, s);     // frozen, fragment-packed weights: W never touches LDS
-  if (p.cmap == 0 && p.groups == 1 && !p.hn_w0 && !p.hn_w1 && p.M % 256 != 0 && p.M % 256 <= 64 && vt_gemm_pp_eligible(p)) {
-    const long tm = (p.M + 255) / 256, tn = (p.N + 255) / 256;
-    VtGemmParams a = p;
-    a.M = (int)((tm - 1) * 256);
-    if (tm > 1 && (tm * tn + 255) / 256 > ((tm - 1) * tn + 255) / 256 && vt_gemm_pp_eligible(a)) {
-      VtGemmParams b = p;
-      const size_t ea = p.a_dtype == VT_F32 ? 4 : 2, ec = p.c_dtype == VT_F32 ? 4 : 2;
-      b.M = p.M - a.M;
-      b.A = (const char*)p.A + (size_t)a.M * p.lda * ea;
-      b.C = (char*)p.C + (size_t)a.M * p.ldc * ec;
-      if (p.residual) b.residual = (const char*)p.residual + (size_t)a.M * p.ldr * ec;
-      const int rc = vt_gemm_pp_launch(a, s);
-      return rc != VT_OK ? rc : vt_gemm_launch(b, s);
-    }
-  }
-  if (vt_gemm_pp_eligible(p)) return vt_gemm_pp_launch(p, s);
-  if (vt_gemm_ppk_eligible(p)) return vt_gemm_ppk_launch(p, s);
+  // 128-row tiles when they fill the slots, else 64-row tiles.
   const int bm = tiles128 < 1024 ? 64 : 128;
   const int bn = 128;
   const int tiles_n = (p.N + bn - 1) / bn, tiles_m = (p.M + bm - 1) / bm;

@@ -16,8 +16,10 @@
 //     (RAW: the wait is per wave, the barrier makes it block-wide, also across the stagger).
 // LDS: 2 buffers x (A 256 x 128 B + B 256 x 128 B) = 128 KiB, rows XOR-swizzled exactly as in vt_gemm_fast.hip (lane-linear
 // DMA image, swizzle on the source address).  Tile order, XCD banding and the epilogue are shared with that kernel.
+// Dispatch: this file launches gemm_pp256d_kernel only.  vt_gemm_route.hip sends it the grids of vt_gemm_pp_fits (below) whose epilogue the persistent
+// form of the tile (vt_gemm_pt.hip) does not have, and all of them with vt_tune(8, 0).
 #include "vt_common.h"
-#include "vt_gemm.h"
+#include "vt_gemm_route.h"
 #include "vt_gemm_epilogue.h"
 #include "vt_prof.h"
 
@@ -188,11 +190,9 @@ __global__ __launch_bounds__(512, 2) void gemm_pp256d_kernel(const VtGemmParams 
 
 }  // namespace
 
-bool vt_gemm_pp_eligible(const VtGemmParams& p) { return vt_gemm_pp_shape(p) || vt_gemm_pt_extra_shape(p); }
-
-// the shapes gemm_pp256d_kernel is good at (the persistent kernel of vt_gemm_pt.hip takes these and a few more, vt_gemm_pt_extra_shape)
-bool vt_gemm_pp_shape(const VtGemmParams& p) {
-  if (!vt_gemm_fast_eligible(p)) return false;
+// the shapes gemm_pp256d_kernel is good at, inside the LDS-DMA family (vt_gemm_lds_fits); the persistent kernel of vt_gemm_pt.hip takes these and a few
+// more (vt_gemm_pt_one_round) — which of the two runs is vt_gemm_route.hip's decision
+bool vt_gemm_pp_fits(const VtGemmParams& p) {
   const long tiles256 = (long)((p.M + 255) / 256) * ((p.N + 255) / 256) * p.groups;
   if (p.lda >= (1 << 21) || p.ldw >= (1 << 21) || p.K >= (1 << 24)) return false;   // 32-bit buffer offsets inside a 256-row block
   if (tiles256 >= 192 && tiles256 <= 256 && p.K >= 1024) return true;   // one well-filled round (RDT qkv: 9 x 24 tiles): 22 % faster than 128-col tiles
@@ -200,7 +200,6 @@ bool vt_gemm_pp_shape(const VtGemmParams& p) {
 }
 
 int vt_gemm_pp_launch(const VtGemmParams& p, hipStream_t s) {
-  if (vt_gemm_pt_eligible(p)) return vt_gemm_pt_launch(p, s);      // persistent tile walk + in-register epilogue folded into the main loop (vt_gemm_pt.hip)
   const int tiles_n = (p.N + BN - 1) / BN, tiles_m = (p.M + BM - 1) / BM;
   const int per_group = tiles_n * tiles_m, total = per_group * p.groups;
   const int gm = 8;

@@ -14,7 +14,7 @@
 //     0..2 of every wave tile, group 1 row tiles 3..4 (a + b is commutative: the result does not depend on timing), and both
 //     run the shared epilogue on their part.
 #include "vt_common.h"
-#include "vt_gemm.h"
+#include "vt_gemm_route.h"
 #include "vt_gemm_epilogue.h"
 #include "vt_prof.h"
 
@@ -165,8 +165,8 @@ __global__ __launch_bounds__(512, 2) void gemm_ppk_kernel(const VtGemmParams p, 
 
 }  // namespace
 
-bool vt_gemm_ppk_eligible(const VtGemmParams& p) {
-  if (!vt_gemm_fast_eligible(p) || p.cmap) return false;
+bool vt_gemm_ppk_fits(const VtGemmParams& p) {      // inside the LDS-DMA family (vt_gemm_lds_fits)
+  if (p.cmap) return false;
   const long tiles = (long)((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN) * p.groups;
   return tiles >= 100 && tiles <= 256 && p.K >= 512;     // one round of 160 x 128 tiles over the 256 CUs
 }

@@ -33,7 +33,7 @@
 //        run their MFMAs with the operands SWAPPED, so a lane owns 4 consecutive keys of one d row, which is the Vt tile's order)
 //   P16  bias (+ GELU erf / tanh) -> row-major 16-bit C  (ViT qkv / fc1, adaptor first layers)
 #include "vt_common.h"
-#include "vt_gemm.h"
+#include "vt_gemm_route.h"
 #include "vt_kernels.h"
 #include "vt_prof.h"
 
@@ -593,14 +593,13 @@ __global__ __launch_bounds__(512, 2) void gemm_pt_kernel(const VtGemmParams p, c
   }
 }
 
-int g_pt_on = 1;                 // vt_tune(8, .): 0 = gemm_pp256d_kernel takes these launches
 int g_pt_cus = 0;
 
 }  // namespace
 
 
 // epilogue kinds the persistent kernel has (anything else stays on gemm_pp256d_kernel)
-static bool pt_kind_ok(const VtGemmParams& p) {
+bool vt_gemm_pt_fits(const VtGemmParams& p) {
   if (p.groups != 1 || p.K < 4 * BK || !p.bias || (p.N % 64)) return false;
   if (p.lda >= (1 << 21) || p.ldw >= (1 << 21) || p.K >= (1 << 24)) return false;   // 32-bit buffer offsets inside a 256-row block
   if (p.c_dtype == VT_F32)          // R32 kind: fp32 C = residual + colscale * (acc + bias)
@@ -611,19 +610,15 @@ static bool pt_kind_ok(const VtGemmParams& p) {
   if ((long)p.ldc * 2 * 128 >= (1L << 31)) return false;
   return p.act == VT_ACT_NONE || p.act == VT_ACT_GELU_ERF || p.act == VT_ACT_GELU_TANH;
 }
-void vt_gemm_pt_tune(int value) { g_pt_on = value != 0; }
 
 // One round of 160 .. 256 tiles at K >= 512 (DINOv2-B out-projection: 64 x 3 tiles, K = 768): too short for gemm_pp256d_kernel to beat the 128-column
 // tiles (its 64-KiB prologue fill and LDS-patch epilogue are a third of such a launch), fine for this kernel (continuous operand stream is moot with one
 // tile per block, but the in-register epilogue is not).
-bool vt_gemm_pt_extra_shape(const VtGemmParams& p) {
-  if (!g_pt_on || p.cmap != 0 || !vt_gemm_fast_eligible(p) || !pt_kind_ok(p)) return false;
+bool vt_gemm_pt_one_round(const VtGemmParams& p) {
+  if (p.cmap != 0 || !vt_gemm_pt_fits(p)) return false;
   const long tiles256 = (long)((p.M + 255) / 256) * ((p.N + 255) / 256);
   return tiles256 >= 160 && tiles256 <= 256 && p.K >= 512;
 }
-
-// which launches take the persistent kernel
-bool vt_gemm_pt_eligible(const VtGemmParams& p) { return g_pt_on && pt_kind_ok(p) && (vt_gemm_pp_shape(p) || vt_gemm_pt_extra_shape(p)); }
 
 int vt_gemm_pt_launch(const VtGemmParams& p, hipStream_t s) {
   if (!g_pt_cus) {

@@ -23,7 +23,7 @@
 //     read back as whole row segments by vt_epi_segment (bias / per-head RMSNorm / activation / column scale / residual), the same
 //     arithmetic in the same order as vt_gemm_epilogue.h.
 #include "vt_common.h"
-#include "vt_gemm.h"
+#include "vt_gemm_route.h"
 #include "vt_gemm_epilogue.h"
 #include "vt_prof.h"
 #include "vt_host.h"
@@ -385,10 +385,11 @@ __global__ void pack_w32_kernel(const uint16_t* __restrict__ W, const long ldw, 
 }  // namespace
 
 static int g_vt_pw_nb = 0;      // ring depth 4 | 8 (vt_tune(1, .)); 0 = default
-static int g_vt_pw_on = 1;      // vt_tune(2, 0) disables the kernel (against gemm_ppk_kernel / gemm_pp256d_kernel)
 
-bool vt_gemm_pw_eligible(const VtGemmParams& p) {
-  if (!g_vt_pw_on || !p.Wp || !vt_gemm_fast_eligible(p) || p.cmap || p.groups != 1) return false;
+void vt_gemm_pw_tune(int ring) { g_vt_pw_nb = ring; }
+
+bool vt_gemm_pw_fits(const VtGemmParams& p) {       // inside the LDS-DMA family (vt_gemm_lds_fits)
+  if (!p.Wp || p.cmap || p.groups != 1) return false;
   if (p.N % BN || p.K % (8 * BK) || p.lda >= (1 << 21)) return false;
   const long tiles = (long)((p.M + BM - 1) / BM) * (p.N / BN) * p.groups;
   // one round of the 256 CUs, or several rounds each at least 7/8 full
@@ -424,19 +425,6 @@ int vt_gemm_pw_launch(const VtGemmParams& p, hipStream_t s) {
   else { if (c16) VT_PW_GO(half_t, half_t); else VT_PW_GO(half_t, float); }
 #undef VT_PW_GO
   return vt_check_launch();
-}
-
-void vt_unet_fused_tune(int on);
-
-extern "C" int vt_tune(int knob, int value) {
-  if (knob == 1 && (value == 0 || value == 4 || value == 8)) { g_vt_pw_nb = value; return VT_OK; }
-  if (knob == 2) { g_vt_pw_on = value != 0; return VT_OK; }
-  if (knob == 6) { vt_attn_kvt_tune(value); return VT_OK; }
-  if (knob == 7) { vt_unet_fused_tune(value); return VT_OK; }
-  if (knob == 8) { vt_gemm_pt_tune(value); return VT_OK; }
-  if (knob == 9 && (value == 0 || value == 1 || value == 3 || value == 6)) { vt_attn16g_tune(value); return VT_OK; }
-  if (knob == 4) { vt_gemm_pws_tune(value); return VT_OK; }
-  return vt_fail(VT_ERR_ARG, "vt_tune: unknown knob %d / value %d", knob, value);
 }
 
 extern "C" int vt_pack_w32(const void* W, long ldw, void* out, int N, int K, vt_stream_t stream) {

@@ -15,7 +15,7 @@
 //     and runs the shared epilogue (bias / per-head RMSNorm / activation / column scale / residual) — no second kernel, no extra boundary.
 //     The ticket counters are self-resetting; the RDT driver zeroes them once per call.
 #include "vt_common.h"
-#include "vt_gemm.h"
+#include "vt_gemm_route.h"
 #include "vt_gemm_epilogue.h"
 #include "vt_prof.h"
 #include "vt_host.h"
@@ -267,7 +267,7 @@ static int pws_split(const VtGemmParams& p) {
   return S;
 }
 
-bool vt_gemm_pws_eligible(const VtGemmParams& p) {
+bool vt_gemm_pws_fits(const VtGemmParams& p) {
   if (!p.Wp || p.cmap || p.groups != 1 || p.taps != 0 || p.splitk < 1) return false;
   if (p.splitk > 1 && (p.c_dtype != VT_F32 || (p.K / BK) % (p.splitk * CH) || p.ldc % 4)) return false;     // slab mode: whole chunks per slice
   if ((p.a_dtype != VT_BF16 && p.a_dtype != VT_F16) || p.w_dtype != p.a_dtype) return false;

@@ -15,7 +15,7 @@
 #include "vt_common.h"
 #include "vt_kernels.h"
 #include "vt_host.h"
-#include "vt_prof.h"
+#include "vt_gemm_route.h"
 #include "../../include/vlatouch.h"
 
 #define CK(x) do { int _r = (x); if (_r) return _r; } while (0)
@@ -169,7 +169,7 @@ int vt_dino_forward(vt_dino_t h, const void* const* imgs, int ncams, int is_u8, 
     const int N1 = swiglu ? 2 * Dm : Dm;
     { VtGemmParams p = lin(ws + w.xn, d.adt, D, L.fc1_w, d.cdt, D, L.fc1_b, ws + w.h1, d.adt, N1, rows, N1, D, swiglu ? VT_ACT_NONE : act);
       p.Wp = swiglu ? nullptr : L.fc1_wp;
-      if (p.Wp && vt_gemm_fast_eligible(p) && vt_gemm_pw_eligible(p)) p.Wp = nullptr;   // the 160 x 128 weights-in-registers tile is the RDT denoise loop's; ViT GEMMs stay on the persistent tile
+      if (p.Wp && vt_gemm_route(p) == VT_GEMM_PW) p.Wp = nullptr;   // the 160 x 128 weights-in-registers tile is the RDT denoise loop's; ViT GEMMs stay on the persistent tile
       CK(vt_wrap(vt_gemm_launch(p, s), "dino fc1")); }
     if (swiglu) CK(vt_wrap(vt_k_swiglu(ws + w.h1, d.adt, N1, rows, Dm, s, h->range_flag), "dino swiglu gate"));
     { VtGemmParams p = lin(ws + w.h1, d.adt, N1, L.fc2_w, d.cdt, Dm, L.fc2_b, tok, VT_F32, tok_stride, rows, D, Dm, VT_ACT_NONE);
@@ -177,7 +177,7 @@ int vt_dino_forward(vt_dino_t h, const void* const* imgs, int ncams, int is_u8, 
       // a few images (2 x 257 rows at batch 1): 108 tiles of 64 x 64 would each walk K = 3072 alone (50 us); DINO_SPLITK slices per tile into fp32
       // slabs + the slab reduction (bias, LayerScale, residual) take 17
       if (w.slab_bytes && rows > 64 && (size_t)DINO_SPLITK * rows * D * 4 <= w.slab_bytes && Dm >= 2048 && (Dm / 64) % DINO_SPLITK == 0 && D % 4 == 0 &&
-          !vt_gemm_fast_eligible(p)) {
+          !vt_gemm_lds_fits(p)) {
         VtGemmParams q = p;
         q.C = ws + w.slab; q.c_dtype = VT_F32; q.ldc = D; q.splitk = DINO_SPLITK; q.c_slab = (long)rows * D;
         q.bias = nullptr; q.colscale = nullptr; q.residual = nullptr;

@@ -24,7 +24,7 @@
 #include "vt_common.h"
 #include "vt_kernels.h"
 #include "vt_host.h"
-#include "vt_prof.h"
+#include "vt_gemm_route.h"
 #include "../../include/vlatouch.h"
 
 #define CK(x) do { int _r = (x); if (_r) return _r; } while (0)
@@ -279,7 +279,7 @@ int rgemm(RCtx& c, VtGemmParams p, const char* what, const float* hn_w0 = nullpt
     while (P * 2 <= S && P * 2 <= split_cap && nk % (P * 2 * 4) == 0) P *= 2;
     S = P;
   }
-  const bool small = c.w.slab_bytes > 0 && !vt_gemm_fast_eligible(p) && p.M <= 512 && p.K >= 512 && (p.K % 64) == 0 && (p.N % 4) == 0 && !p.hn_w0 &&
+  const bool small = c.w.slab_bytes > 0 && !vt_gemm_lds_fits(p) && p.M <= 512 && p.K >= 512 && (p.K % 64) == 0 && (p.N % 4) == 0 && !p.hn_w0 &&
                      !p.hn_w1 && p.groups == 1 && p.taps == 0 && S >= 2 && (size_t)S * p.M * p.N * 4 <= c.w.slab_bytes;
   if (!small) {
     // producer side of the RMSNorm hand-off: decided on THIS launch's parameters (the per-run switch c.fuse_norm only says that block 0 qualifies):
@@ -288,7 +288,7 @@ int rgemm(RCtx& c, VtGemmParams p, const char* what, const float* hn_w0 = nullpt
       VtGemmParams q = p;
       q.xn_out = c.ws + c.w.xn; q.xn_ld = p.N; q.xn_gain = next_norm; q.xn_part = (float*)(c.ws + c.w.rs_part);
       q.rs_mode = c.h->d.rms_mode;      // the variance form hands over centred second moments (vt_gemm.h)
-      if (vt_gemm_fast_eligible(q) && vt_gemm_pw_eligible(q)) {
+      if (vt_gemm_route(q) == VT_GEMM_PW) {
         p = q;
         *xn_done = true;
         c.rs_pending = true;
@@ -297,7 +297,7 @@ int rgemm(RCtx& c, VtGemmParams p, const char* what, const float* hn_w0 = nullpt
     // prefetch hint for the next launch's weights: measured SLOWER (round 5, EXPERIMENTS.md: one batch at a time 363 -> 359 chunks/s, batch 1 20.31 -> 20.59 ms)
     // — off unless VLATOUCH_RDT_PREFETCH=1
     static const bool pf_on = [] { const char* e = getenv("VLATOUCH_RDT_PREFETCH"); return e && atoi(e) != 0; }();
-    if (pf_on && c.pf_next && p.Wp && vt_gemm_fast_eligible(p) && vt_gemm_pw_eligible(p)) { p.pf_ptr = c.pf_next; p.pf_bytes = c.pf_bytes; }
+    if (pf_on && c.pf_next && vt_gemm_route(p) == VT_GEMM_PW) { p.pf_ptr = c.pf_next; p.pf_bytes = c.pf_bytes; }
     c.pf_next = nullptr;
     return vt_wrap(vt_gemm_launch(p, c.s), what);
   }
@@ -443,7 +443,7 @@ int take_rstd(RCtx& c, VtGemmParams& p, const float* gain) {
   VtGemmParams q = p;
   q.rs_part = (const float*)(c.ws + c.w.rs_part); q.rs_n = 2 * (c.h->d.hidden / 128); q.rs_inv_k = 1.0f / (float)c.h->d.hidden; q.rs_eps = 1e-6f;
   q.rs_mode = c.h->d.rms_mode;
-  if (q.c_dtype != VT_F32 && vt_gemm_fast_eligible(q) && vt_gemm_pw_eligible(q)) { p = q; return VT_OK; }
+  if (q.c_dtype != VT_F32 && vt_gemm_route(q) == VT_GEMM_PW) { p = q; return VT_OK; }
   const vt_rdt_desc& d = c.h->d;
   return vt_k_rownorm((const float*)(c.ws + c.w.x), VT_F32, d.hidden, c.ws + c.w.xn, d.adt, d.hidden, gain, nullptr, p.M, d.hidden, 1e-6f, d.rms_mode, c.s);
 }
@@ -464,8 +464,8 @@ int run_blocks(RCtx& c, const uint8_t* lang_mask) {
     pr.residual = x; pr.ldr = D;
     VtGemmParams c1 = lin(c.ws + c.w.xn, d.adt, D, b0.qkv_w, d.cdt, D, b0.qkv_b, c.ws + c.w.qkv, d.adt, 3 * D, M, 3 * D, D, VT_ACT_NONE, b0.qkv_wp);
     VtGemmParams c2 = lin(c.ws + c.w.xn, d.adt, D, b0.cq_w, d.cdt, D, b0.cq_b, c.ws + c.w.q, d.adt, D, M, D, D, VT_ACT_NONE, b0.cq_wp);
-    c.fuse_norm = (d.rms_mode == VT_NORM_RMS_MEANSQ || d.rms_mode == VT_NORM_RMS_VAR) && c.w.slab_bytes == 0 && D % 128 == 0 && 2 * (D / 128) <= 32 && vt_gemm_fast_eligible(pr) &&
-                  vt_gemm_pw_eligible(pr) && vt_gemm_fast_eligible(c1) && vt_gemm_pw_eligible(c1) && vt_gemm_fast_eligible(c2) && vt_gemm_pw_eligible(c2);
+    c.fuse_norm = (d.rms_mode == VT_NORM_RMS_MEANSQ || d.rms_mode == VT_NORM_RMS_VAR) && c.w.slab_bytes == 0 && D % 128 == 0 && 2 * (D / 128) <= 32 &&
+                  vt_gemm_route(pr) == VT_GEMM_PW && vt_gemm_route(c1) == VT_GEMM_PW && vt_gemm_route(c2) == VT_GEMM_PW;
     c.rs_pending = false;
   }
   for (int l = 0; l < d.depth; ++l) {

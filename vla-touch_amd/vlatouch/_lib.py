@@ -40,6 +40,8 @@ def range_names(bits: int):
 
 F32, BF16, F32X3, F16 = 0, 1, 2, 3   # F32X3: fp32 storage, split-bf16 3-MFMA compute (GEMM weights only); F16: IEEE half
 ACT_NONE, ACT_GELU_ERF, ACT_GELU_TANH, ACT_SILU, ACT_MISH, ACT_SWIGLU, ACT_GEGLU = 0, 1, 2, 3, 4, 5, 6
+# vt_gemm_route_of (include/vlatouch.h, VT_ROUTE_*)
+ROUTE_NAMES = ("UNSUPPORTED", "BAD_ARG", "REG", "F32R", "GLDS", "PP", "PT", "PPK", "PW", "PWS", "ROWSPLIT")
 NORM_LAYER, NORM_RMS_MEANSQ, NORM_RMS_VAR = 0, 1, 2
 IMGNORM_AUTO, IMGNORM_ON, IMGNORM_OFF = 0, 1, 2
 
@@ -184,6 +186,8 @@ SIGNATURES = {
     "vt_prof_enable": (_I, [_I]),
     "vt_prof_collect": (_I, [_P, _P, _P, _P]),
     "vt_gemm": (_I, [_P, _P]),
+    "vt_gemm_route_of": (_I, [_P]),
+    "vt_gemm_route_split": (_I, [_P, _P, _P]),
     "vt_randn": (_I, [_P, _L, _P, _I, _P]),
     "vt_slice_cast": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _P]),
     "vt_cast": (_I, [_P, _I, _L, _P, _I, _L, _I, _I, _P]),
