@@ -472,6 +472,16 @@ int vt_mse_loss(const void* pred, const float* target, void* dpred, float* loss,
  *   vt_ema_update_dev per tensor. */
 int vt_grad_accum_multi(const void* table, const void* fresh, int ntensors, long total_chunks, float scale, int accumulate, vt_stream_t stream);
 int vt_ema_multi(const void* table, int ntensors, long total_chunks, const float* hyper, vt_stream_t stream);
+/* Metrics of fine-tuning's periodic sampling evaluation (VLA/train/sample.py:55-86, log_sample_res), one call per evaluation batch.
+ * pred [B][H][A] of dtype `dt` (0 fp32, 1 bf16, 3 fp16), target [B][H][A], mask [B][A] (0 / 1) and state_norm [B][A] fp32, the last two
+ * broadcast over H; dataset_idx [B] int32 in [0, n_datasets).  Per element in fp32: sq = (pred - target)^2, l2 = sqrt(sq) / (state_norm + 1e-3).
+ *   per_sample [B][2] = (sum sq m / sum m, sum l2 m / sum m) over the sample's H * A elements, overall [2] = the same two ratios over the whole
+ *   batch; sums in fp64, rounded once at the fp32 store.  A sample whose mask is all zero gives NaN (0 / 0) and adds zero to the overall sums.
+ *   Running state of one evaluation, zeroed by the caller before its first batch: acc [n_datasets + 1][2] fp64 and count [n_datasets + 1]
+ *   int32.  Row dataset_idx[b] receives per_sample[b] (the fp32 values, in index order) and a count, row n_datasets the overall pair.
+ *   ws: 3 * B doubles of scratch.  Two launches, no atomics (two calls give the same bits), no host read, allocation or synchronisation. */
+int vt_sample_metrics(const void* pred, int dt, const float* target, const float* mask, const float* state_norm, const int* dataset_idx, int B,
+                      int H, int A, int n_datasets, float* per_sample, float* overall, double* acc, int* count, double* ws, vt_stream_t stream);
 
 /* ---- camera frames -> SigLIP pixel_values (scripts/franka_model_eef.py:242-288: RoboticDiffusionTransformerModel.preprocess_images + the
  * `.to(device, dtype)` of step(); SiglipImageProcessor.preprocess).  Bit-identical to that PIL path: optional brightness lift

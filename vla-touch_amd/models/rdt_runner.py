@@ -78,6 +78,15 @@ class RDTRunner:
         self._ctor = dict(action_dim=action_dim, pred_horizon=pred_horizon, config=config, lang_token_dim=lang_token_dim, img_token_dim=img_token_dim,
                           state_token_dim=state_token_dim, max_lang_cond_len=max_lang_cond_len, img_cond_len=img_cond_len,
                           lang_pos_embed_config=lang_pos_embed_config, img_pos_embed_config=img_pos_embed_config)
+        # the two execution settings, where the caller gave them as arguments, as the strings a config.json can hold: `trainer()` carries them,
+        # so a runner rebuilt from the trainer's config (RdtTrainer.sampler, from_pretrained) executes as this one does
+        self._ctor_exec = {}
+        if isinstance(compute_dtype, str):
+            self._ctor_exec["compute_dtype"] = compute_dtype
+        elif compute_dtype in (torch.bfloat16, torch.float16):               # any other dtype is no 16-bit setting: nothing to record
+            self._ctor_exec["compute_dtype"] = "bf16" if compute_dtype == torch.bfloat16 else "f16"
+        if solver_state is not None:
+            self._ctor_exec["solver_state"] = solver_state
         # compute_dtype (extension): the engine's 16-bit activation / MFMA operand type for a bf16 model — torch.float16 (default: the bf16 weights convert
         # exactly, same width and MFMA rate, 3 more mantissa bits: |chunk - fp32 reference| 1e-2 -> 1.2e-3 at RDT-1B) or torch.bfloat16
         # (the reference's own execution dtype, rounding after every op).  config['rdt']['compute_dtype'] / VLATOUCH_RDT_COMPUTE = "f16" | "bf16".
@@ -120,6 +129,7 @@ class RDTRunner:
         self.max_lang_cond_len, self.img_cond_len = max_lang_cond_len, img_cond_len
         self._engine: Optional[RdtEngine] = None
         self._engine_key = None
+        self._engine_owns_weights = False     # True (set by adopt_weights): the engine copies every weight, so it can be refreshed in place
 
     # ---- module plumbing
     _PARTS = ("model", "lang_adaptor", "img_adaptor", "state_adaptor")
@@ -177,15 +187,31 @@ class RDTRunner:
         obj.load_state_dict(sd)
         return obj
 
+    def _weights_key(self):
+        return tuple(getattr(self, p).version for p in self._PARTS) + (str(self.device),)
+
+    def adopt_weights(self, sd) -> "RDTRunner":
+        """Take over `sd` (every key, tensors on this runner's device) without a copy, like load_state_dict(sd, assign=True), and bring the
+        engine up to date with device-to-device copies: the first call builds it on copies of its own, later calls overwrite those in place
+        and re-derive the packed forms (RdtEngine.load_weights) instead of building a new engine.  Nothing passes through host memory.
+        The caller keeps `sd` alive and calls again after changing it (RdtTrainer.sampler)."""
+        self.load_state_dict(sd, assign=True)
+        self._engine_owns_weights = True
+        if self._engine is not None:
+            self._engine.load_weights(self.state_dict())
+            self._engine_key = self._weights_key()
+        return self
+
     def engine(self) -> RdtEngine:
-        key = tuple(getattr(self, p).version for p in self._PARTS) + (str(self.device),)
+        key = self._weights_key()
         if self._engine is None or self._engine_key != key:
             self._engine = RdtEngine(
                 self.state_dict(), hidden=self.model.hidden_size, depth=self.model.depth, heads=self.model.num_heads,
                 horizon=self.pred_horizon, action_dim=self.action_dim, lang_token_dim=self.lang_token_dim, img_token_dim=self.img_token_dim,
                 state_token_dim=self.state_token_dim, max_lang_cond_len=self.max_lang_cond_len, img_cond_len=self.img_cond_len,
                 lang_adaptor=self.config['lang_adaptor'], img_adaptor=self.config['img_adaptor'], state_adaptor=self.config['state_adaptor'],
-                dtype=self.compute_dtype, io_dtype=self.dtype, rms_mode=self.rms_mode, solver_state=self.solver_state, device=self.device)
+                dtype=self.compute_dtype, io_dtype=self.dtype, rms_mode=self.rms_mode, solver_state=self.solver_state, device=self.device,
+                own_weights=self._engine_owns_weights)
             self._engine_key = key
             rg = self._range
             if rg is not None and not rg.fell_back and self.compute_dtype == torch.float16 and not self._engine.fits_fp16:
@@ -275,7 +301,7 @@ class RDTRunner:
         """An `RdtTrainer` (vlatouch/rdt_train.py) on a copy of this runner's weights: get_loss / optimizer_step / train_step on the device.
         `trainer.sync_to(runner)` (or `runner.load_state_dict(trainer.state_dict())`) brings the trained weights back; the engine rebuilds."""
         from vlatouch.rdt_train import RdtTrainer
-        cfg = dict(self._ctor, dtype=str(self.dtype).replace("torch.", ""), rms_mode=self.rms_mode)
+        cfg = dict(self._ctor, dtype=str(self.dtype).replace("torch.", ""), rms_mode=self.rms_mode, **self._ctor_exec)
         args = dict(heads=self.model.num_heads, horizon=self.pred_horizon, action_dim=self.action_dim, rms_mode=self.rms_mode,
                     prediction_type=self.prediction_type, num_train_timesteps=self.num_train_timesteps, beta_schedule=self.beta_schedule,
                     config=cfg, device=self.device)

@@ -30,12 +30,14 @@ class RdtEngine(RangeGuard):
                  img_token_dim: int, state_token_dim: int, max_lang_cond_len: int, img_cond_len: int,
                  lang_adaptor: str = "mlp2x_gelu", img_adaptor: str = "mlp2x_gelu", state_adaptor: str = "mlp3x_gelu",
                  dtype: torch.dtype = torch.bfloat16, rms_mode: str = "meansq", solver_state: str = "fp32", io_dtype: Optional[torch.dtype] = None,
-                 device="cuda"):
+                 device="cuda", own_weights: bool = False):
         """dtype = the engine's storage / MFMA operand type (fp32, bf16, or IEEE fp16).  io_dtype = the MODEL's dtype when it differs: a bf16 checkpoint
         evaluated with fp16 activations (dtype=torch.float16, io_dtype=torch.bfloat16: the bf16 weights convert exactly, same width and MFMA rate, 8x
         smaller activation rounding) still rounds its start noise / returns its result on the bf16 grid.
         solver_state (16-bit mode only): "fp32" (default) keeps the DPM-Solver++ state, the x0 predictions and the final projection in fp32 between
-        network evaluations — closer to the fp32 reference; "bf16" reproduces the reference's bf16 rounding points (rdt_runner.py:137-139,160)."""
+        network evaluations — closer to the fp32 reference; "bf16" reproduces the reference's bf16 rounding points (rdt_runner.py:137-139,160).
+        own_weights: every packed weight is a copy, also where `sd` already holds it on this device in the execution dtype (by default such a
+        tensor is adopted as it is); an engine whose weights are refreshed in place (`load_weights`) must not alias its source."""
         self.device = L.require_gpu(device)
         if solver_state not in ("fp32", "bf16"):
             raise ValueError(f"solver_state must be 'fp32' or 'bf16', got {solver_state!r}")
@@ -50,8 +52,13 @@ class RdtEngine(RangeGuard):
         self.hidden, self.horizon, self.action_dim, self.img_len, self.max_lang = hidden, horizon, action_dim, img_cond_len, max_lang_cond_len
         self.state_dim, self.lang_dim, self.img_dim = state_token_dim, lang_token_dim, img_token_dim
         f32 = torch.float32
-        w = lambda k: sd[k].detach().to(dev, dtype).contiguous()
-        v = lambda k: sd[k].detach().to(dev, f32).contiguous()
+        keys: List[str] = []                        # state-dict key of every entry of W, in order (`load_weights`)
+
+        def w(k, to=dtype):
+            keys.append(k)
+            return sd[k].detach().to(dev, to, copy=own_weights).contiguous()
+
+        v = lambda k: w(k, f32)
         W: List[torch.Tensor] = []
         for e in ("t_embedder", "freq_embedder"):
             W += [w(f"model.{e}.mlp.0.weight"), v(f"model.{e}.mlp.0.bias"), w(f"model.{e}.mlp.2.weight"), v(f"model.{e}.mlp.2.bias")]
@@ -76,7 +83,7 @@ class RdtEngine(RangeGuard):
             else:
                 for j in range(n):
                     W += [w(f"{name}.{2 * j}.weight"), v(f"{name}.{2 * j}.bias")]
-        self._weights = W
+        self._weights, self._weight_keys = W, keys
         d = L.RdtDesc()
         d.hidden, d.depth, d.heads, d.horizon, d.out_dim, d.state_dim = hidden, depth, heads, horizon, action_dim, state_token_dim
         d.lang_dim, d.img_dim, d.max_lang_len, d.img_len = lang_token_dim, img_token_dim, max_lang_cond_len, img_cond_len
@@ -129,6 +136,23 @@ class RdtEngine(RangeGuard):
         self._set_score_bounds()
         if self._packed is not None:
             L.check(L.lib().vt_rdt_set_packed(self._h, L.ptr(self._packed), L.stream_ptr(self.device)), "vt_rdt_set_packed")
+
+    def load_weights(self, sd: SD) -> None:
+        """Overwrite the packed weights in place from `sd` (tensors on this device, the constructor's keys and shapes), then `repack()`:
+        device-to-device copies and casts, no allocation and nothing through host memory.  The static fp16 bounds of the constructor
+        (`fits_fp16`) are not taken again: weights that leave the 16-bit range show in the range guard's word at the next call."""
+        from . import ops
+        for dst, k in zip(self._weights, self._weight_keys):
+            src = sd[k].detach()
+            if src.dim() == dst.dim() + 1:                     # the three position tables are packed without their leading 1
+                src = src[0]
+            if src.device != dst.device or src.shape != dst.shape or not src.is_contiguous():
+                raise ValueError(f"RdtEngine.load_weights: {k} must be a contiguous tensor of shape {tuple(dst.shape)} on {dst.device}")
+            if src.dtype == dst.dtype:
+                dst.copy_(src)
+            else:
+                ops.cast(src, dst.dtype, out=dst)
+        self.repack()
 
     def update_weights(self, fn):
         """In-place change of the packed weights through `fn(self._weights)`, followed by `repack()` (the derived copies never go stale)."""

@@ -261,6 +261,11 @@ class RdtTrainer(_Optimizer):
         self._norm_coef = torch.zeros(2, dtype=F32, device=dev)
         self._table_key = None
         self.last_loss: Optional[torch.Tensor] = None
+        self.weights_version = 0                              # optimizer steps and load_checkpoint calls: changes of the master parameters
+        self.shadow_version = 0                               # the same plus EMA-only steps: changes of the shadows; `sampler` compares the one it reads
+        self._sampler = None                                  # the RDTRunner `sampler` keeps, and the (source, its version) it was last refreshed at
+        self._sampler_key = None
+        self.sampler_repacks = 0                              # times `sampler` handed weights over (the first build included)
 
     def _adaptor_layers(self, name: str) -> List[str]:
         if f"{name}.weight" in self.p:
@@ -541,6 +546,8 @@ class RdtTrainer(_Optimizer):
         L.check(lib.vt_adamw_ema_multi(L.ptr(tab), n, chunks, L.ptr(hy), self.betas[0], self.betas[1], self.eps, self.wd, _sp(dev)), "vt_adamw_ema_multi")
         self._refresh16()
         self.micro_step, self.sync_gradients = 0, True
+        self.weights_version += 1
+        self.shadow_version += 1
 
     def accumulate(self) -> None:
         """k > 1: fold the gradients get_loss left in `self.g` into the accumulators, scaled by 1 / k (accelerator.backward's loss / k); the
@@ -574,6 +581,7 @@ class RdtTrainer(_Optimizer):
                 "vt_train_hyper")
         L.check(L.lib().vt_ema_multi(L.ptr(tab), n, chunks, L.ptr(host.to(self.device)), _sp(self.device)), "vt_ema_multi")
         self.sync_gradients = False
+        self.shadow_version += 1
 
     def train_step(self, lang_tokens, lang_attn_mask, img_tokens, state_tokens, action_gt, action_mask, ctrl_freqs, *, noise=None, timesteps=None):
         B = torch.as_tensor(action_gt).shape[0]
@@ -607,6 +615,35 @@ class RdtTrainer(_Optimizer):
         """Hand the trained (or the averaged) weights to an RDTRunner: its engine rebuilds on the next call."""
         runner.load_state_dict(self.ema_state_dict() if ema else self.state_dict())
         return runner
+
+    def sampler(self, ema: bool = False):
+        """An RDTRunner on the live weights (ema=True: on the averaged ones) for sampling during training (train.py:462-475 evaluates
+        `rdt.predict_action` on the weights being trained).  Built once from the runner's constructor arguments and kept; its engine holds
+        copies of its own in the runner's execution dtype, overwritten from the fp32 master parameters (or the EMA shadows) by
+        device-to-device copies, and repacked, only when the source changed since the last hand-over (an optimizer step or load_checkpoint;
+        for the shadows also an EMA-only micro-batch) or `ema` changed (`sampler_repacks` counts the hand-overs).  No weight passes through host memory, unlike `sync_to`.
+        `release_sampler()` frees the runner and its engine."""
+        if self.config is None:
+            raise RuntimeError("sampler needs the runner's constructor arguments: build the trainer with RDTRunner.trainer()")
+        from_shadow = bool(ema) and bool(self.shadow)             # before the first optimizer step the average is the parameters
+        key = (from_shadow, self.shadow_version if from_shadow else self.weights_version)
+        if self._sampler is None:
+            from models.rdt_runner import RDTRunner
+            cfg = dict(self.config)
+            dt = cfg.pop("dtype", "bfloat16")
+            self._sampler = RDTRunner(dtype=getattr(torch, dt.replace("torch.", "")) if isinstance(dt, str) else dt, device=self.device,
+                                      init_weights=False, **cfg)
+            self._sampler_key = None
+        if self._sampler_key != key:
+            src = self.shadow if from_shadow else self.p
+            self._sampler.adopt_weights(OrderedDict((k, src[k]) for k in self.p))
+            self._sampler.engine()
+            self._sampler_key = key
+            self.sampler_repacks += 1
+        return self._sampler
+
+    def release_sampler(self) -> None:
+        self._sampler = self._sampler_key = None
 
     def save_pretrained(self, path: str, ema: bool = False) -> None:
         """config.json (the runner's constructor arguments) + model.safetensors, as RDTRunner.from_pretrained reads them."""
@@ -670,6 +707,8 @@ class RdtTrainer(_Optimizer):
         self.micro_step, self.sync_gradients, self._table_key = 0, False, None
         self.lr = lr_at(self.base_lr, self.lr_scheduler, max(0, self.step_count - 1), self.lr_warmup_steps * self.k)
         self._refresh16()
+        self.weights_version += 1
+        self.shadow_version += 1
 
 
 # ---------------------------------------------------------------------------------------------- the loop around the trainer
@@ -681,15 +720,106 @@ def latest_checkpoint(output_dir: str) -> Optional[str]:
     return max(dirs, key=lambda d: int(d.split("-", 1)[1])) if dirs else None
 
 
+def sample_eval(runner, batches, *, num_sample_batches: int, dataset_id2name, vision_encoder=None, text_encoder=None, return_raw: bool = False):
+    """`log_sample_res` (train/sample.py:7-98): sample an action chunk with `runner.predict_action` for the first `num_sample_batches` items of
+    `batches` and report, per dataset and overall, the masked MSE and the masked, state-norm-relative L2 error against the ground truth.
+
+    A batch is the reference collator's mapping: `data_indices` (a list of dataset ids), `ctrl_freqs`, `state_norm` [B, A], `states`
+    [B, T, A] (the last one is the state token), `actions` [B, horizon, A], `state_elem_mask` [B, A], `lang_attn_mask`; the language as
+    `lang_embeds` or as `input_ids` for `text_encoder`; the images as `images` [B, N, C, H, W] for `vision_encoder` (reshaped to
+    (B, -1, vision_encoder.hidden_size), sample.py:34-36) or, not in the reference, as ready `img_tokens`; an optional `x_init` replaces
+    predict_action's draw of the start noise.  `dataset_id2name`: a mapping id -> name (or a sequence of names).
+
+    One vt_sample_metrics launch per batch adds into sums on the device; they are read once, after the last batch.  -> the reference's dict:
+    `<name>_sample_mse` / `<name>_sample_l2err` = mean over that dataset's samples, for the datasets that occurred, and
+    `overall_avg_sample_mse` / `overall_avg_sample_l2err` = sum of the batches' overall values / num_sample_batches (also when `batches` ends
+    early, as there), all rounded to 4 decimals.  return_raw=True: (that dict, the same keys unrounded)."""
+    ids = list(dataset_id2name.keys()) if hasattr(dataset_id2name, "keys") else list(range(len(dataset_id2name)))
+    if not ids:
+        raise ValueError("sample_eval: dataset_id2name is empty")
+    if int(num_sample_batches) != num_sample_batches or num_sample_batches < 1:
+        raise ValueError(f"sample_eval: num_sample_batches must be an integer >= 1, got {num_sample_batches!r}")
+    row_of = {i: r for r, i in enumerate(ids)}
+    n = len(ids)
+    state = None
+    keys: "OrderedDict[str, tuple]" = OrderedDict()                      # result key -> (row, column), in the order the reference's dict gets them
+    for step, batch in enumerate(batches):
+        if step >= num_sample_batches:
+            break
+        data_indices = [int(i) for i in batch["data_indices"]]
+        for i in data_indices:
+            if i not in row_of:
+                raise ValueError(f"sample_eval: data_indices entry {i} is not a key of dataset_id2name")
+        if state is None:
+            dev, lib = L.require_gpu(runner.device), L.lib()
+            f32 = lambda t: torch.as_tensor(t).to(dev, F32).contiguous()
+            # acc [n + 1][2] fp64 followed by count [n + 1] int32 in one buffer: one copy to the host ends the evaluation
+            state = torch.zeros(2 * (n + 1) + (n + 2) // 2, dtype=torch.float64, device=dev)
+            acc, count = state[:2 * (n + 1)], state[2 * (n + 1):].view(torch.int32)
+        actions, mask, state_norm = f32(batch["actions"]), f32(batch["state_elem_mask"]), f32(batch["state_norm"])
+        B, H, A = actions.shape
+        if len(data_indices) != B or mask.shape != (B, A) or state_norm.shape != (B, A):
+            raise ValueError("sample_eval: data_indices must hold B entries, state_elem_mask and state_norm must be [B, action_dim]")
+        if "img_tokens" in batch:
+            img_tokens = batch["img_tokens"]
+        else:
+            if vision_encoder is None:
+                raise ValueError("sample_eval: a batch with `images` needs vision_encoder")
+            images = batch["images"]
+            img_tokens = vision_encoder(images.reshape(-1, *images.shape[2:])).detach().reshape(B, -1, vision_encoder.hidden_size)
+        lang_attn_mask = batch["lang_attn_mask"]
+        if "lang_embeds" in batch:
+            lang_tokens = batch["lang_embeds"]
+        else:
+            if text_encoder is None:
+                raise ValueError("sample_eval: a batch with `input_ids` needs text_encoder")
+            lang_tokens = text_encoder(input_ids=batch["input_ids"], attention_mask=lang_attn_mask)["last_hidden_state"].detach()
+        kw = {"x_init": batch["x_init"]} if batch.get("x_init") is not None else {}
+        pred = runner.predict_action(lang_tokens=lang_tokens, lang_attn_mask=lang_attn_mask, img_tokens=img_tokens,
+                                     state_tokens=torch.as_tensor(batch["states"])[:, -1:, :], action_mask=mask.unsqueeze(1),
+                                     ctrl_freqs=batch["ctrl_freqs"], **kw).contiguous()
+        if pred.shape != actions.shape or pred.device != actions.device:
+            raise ValueError(f"sample_eval: predict_action returned {tuple(pred.shape)} on {pred.device}, actions are {tuple(actions.shape)} on {actions.device}")
+        rows = torch.tensor([row_of[i] for i in data_indices], dtype=torch.int32).to(dev)
+        out = _empty((2 * B + 2,), dev)                                  # per_sample [B][2] | overall [2]
+        ws = torch.empty(3 * B, dtype=torch.float64, device=dev)
+        L.check(lib.vt_sample_metrics(L.ptr(pred), _dt(pred), L.ptr(actions), L.ptr(mask), L.ptr(state_norm), L.ptr(rows), B, H, A, n, L.ptr(out),
+                                      C.c_void_p(out.data_ptr() + 8 * B), L.ptr(acc), L.ptr(count), L.ptr(ws), _sp(dev)), "vt_sample_metrics")
+        for col, suffix in enumerate(("_sample_mse", "_sample_l2err")):
+            for i in data_indices:
+                keys.setdefault(dataset_id2name[i] + suffix, (row_of[i], col))
+        keys.setdefault("overall_avg_sample_mse", (n, 0))
+        keys.setdefault("overall_avg_sample_l2err", (n, 1))
+    if state is None:                                                    # no batch: the reference returns an empty dict
+        return ({}, {}) if return_raw else {}
+    host = state.cpu()                                                   # the evaluation's one device read
+    raw = sample_eval_means(host[:2 * (n + 1)].view(n + 1, 2), host[2 * (n + 1):].view(torch.int32), keys, num_sample_batches)
+    metrics = {name: round(v, 4) for name, v in raw.items()}
+    return (metrics, raw) if return_raw else metrics
+
+
+def sample_eval_means(acc, count, keys, num_sample_batches: int) -> dict:
+    """The divisions at the end of log_sample_res (sample.py:88-93) on the sums vt_sample_metrics left: acc [n + 1][2] fp64, count [n + 1];
+    keys: result key -> (row, column).  A dataset's sums are divided by its sample count, the overall sums (row n) by num_sample_batches."""
+    last = acc.shape[0] - 1
+    return {name: float(acc[r, c]) / (num_sample_batches if r == last else int(count[r])) for name, (r, c) in keys.items()}
+
+
 def finetune(trainer: RdtTrainer, batches, *, max_train_steps: int, checkpointing_period: Optional[int] = None, output_dir: Optional[str] = None,
-             resume_from_checkpoint: Optional[str] = None) -> List[torch.Tensor]:
+             resume_from_checkpoint: Optional[str] = None, sample_period: int = -1, sample_batches=None, num_sample_batches: int = 2,
+             dataset_id2name=None, sample_ema: bool = False, log=None, vision_encoder=None, text_encoder=None) -> List[torch.Tensor]:
     """The reference's loop (train.py:359-489) around `trainer.train_step`: every item of `batches` is one micro-batch, a mapping of train_step's
     keyword arguments.  Stops when `max_train_steps` optimizer steps are taken; writes `output_dir`/checkpoint-{global_step} every
     `checkpointing_period` optimizer steps; `resume_from_checkpoint` = a checkpoint's name under `output_dir` or "latest" (a missing one starts a
     new run, as there); ends with save_pretrained(output_dir) and the averaged weights in `output_dir`/ema.  Like the reference's loop it does
-    not skip the batches an earlier run consumed: `batches` continues where the caller wants.  -> the micro-batch losses (device tensors)."""
+    not skip the batches an earlier run consumed: `batches` continues where the caller wants.  sample_period > 0: after every optimizer step with
+    global_step % sample_period == 0, and after that step's checkpoint (train.py:455-475), `sample_eval` runs on `trainer.sampler(ema=sample_ema)`
+    over `sample_batches` (iterated afresh at each visit; `vision_encoder` / `text_encoder` go to it for batches with `images` / `input_ids`)
+    and `log(metrics, global_step)` is called if given; the evaluation reads the weights and writes none.  -> the micro-batch losses (device tensors)."""
     if (checkpointing_period or resume_from_checkpoint) and output_dir is None:
         raise ValueError("finetune: checkpointing_period / resume_from_checkpoint need output_dir")
+    if sample_period is not None and sample_period > 0 and (sample_batches is None or dataset_id2name is None):
+        raise ValueError("finetune: sample_period > 0 needs sample_batches and dataset_id2name")
     if resume_from_checkpoint:
         name = latest_checkpoint(output_dir) if resume_from_checkpoint == "latest" else os.path.basename(os.path.normpath(resume_from_checkpoint))
         if name is not None and os.path.isdir(os.path.join(output_dir, name)):
@@ -701,6 +831,11 @@ def finetune(trainer: RdtTrainer, batches, *, max_train_steps: int, checkpointin
         losses.append(trainer.train_step(**batch))
         if trainer.sync_gradients and checkpointing_period and trainer.global_step % checkpointing_period == 0:
             trainer.save_checkpoint(os.path.join(output_dir, f"checkpoint-{trainer.global_step}"))
+        if trainer.sync_gradients and sample_period is not None and sample_period > 0 and trainer.global_step % sample_period == 0:
+            metrics = sample_eval(trainer.sampler(ema=sample_ema), sample_batches, num_sample_batches=num_sample_batches,
+                                  dataset_id2name=dataset_id2name, vision_encoder=vision_encoder, text_encoder=text_encoder)
+            if log is not None:
+                log(metrics, trainer.global_step)
     if output_dir is not None:
         if trainer.micro_step != 0:
             raise RuntimeError("finetune: the batches ended in the middle of an accumulation window")
