@@ -70,6 +70,107 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, 
     return out
 
 
+def _grouped(t: torch.Tensor, grouped: bool, what: str):
+    """(data_ptr, group stride, row stride) of a [rows, cols] / [G, rows, cols] operand view with unit inner stride."""
+    assert t.dim() == (3 if grouped else 2) and t.stride(-1) == 1, f"{what}: expected a {'3' if grouped else '2'}-D view with unit inner stride"
+    return t.data_ptr(), (t.stride(0) if grouped else 0), t.stride(-2)
+
+
+def gemm_block_params(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, bias: Optional[torch.Tensor] = None, *, w_code: Optional[int] = None,
+                      act: int = L.ACT_NONE, colscale: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None, splitk: int = 1,
+                      conv: Optional[dict] = None) -> L.GemmParams:
+    """The parameter block of one vt_gemm launch as the library's own drivers fill it: groups, per-group strides and pitches come from the
+    tensors' strides, nothing is launched.
+      plain:  a [M, K] | [G, M, K],  w [N, K] | [G, N, K],  out [M, N] | [G, M, N];  splitk > 1: out [S, M, N] | [S, G, M, N] fp32 slabs
+      conv:   conv = dict(taps, cin, tout, stride=1, off0=0, tstep=1),  a [B, Tin, cin] | [G, B, Tin, cin] (samples back to back),  w [N, taps*cin] | [G, ...],
+              out rows = B * tout
+    The launch is grouped when `out` has the extra leading dimension; then EVERY operand carries it.  A shared operand is t.expand(G, ...)
+    (group stride 0), a pitched one a column slice of a wider tensor.  bias [N] | [G, N]; residual like one slab of out (dtype of out);
+    colscale [N] (the block has no per-group stride for it).  w_code overrides the W type code (L.F32X3 on fp32 storage: split-bf16)."""
+    grouped = out.dim() - (1 if splitk > 1 else 0) == 3
+    p = L.GemmParams()
+    p.W, p.w_gs, p.ldw = _grouped(w, grouped, "w")
+    if conv is None:
+        p.A, p.a_gs, p.lda = _grouped(a, grouped, "a")
+        M, K = a.shape[-2:]
+    else:
+        taps, cin, tout = conv["taps"], conv["cin"], conv["tout"]
+        assert a.dim() == (4 if grouped else 3) and a.shape[-1] == cin and a.stride(-1) == 1 and a.stride(-3) == a.shape[-2] * a.stride(-2)
+        p.A, p.a_gs, p.lda = a.data_ptr(), (a.stride(0) if grouped else 0), a.stride(-2)
+        M, K = a.shape[-3] * tout, taps * cin
+        p.taps, p.cin, p.tout, p.tin = taps, cin, tout, a.shape[-2]
+        p.stride, p.off0, p.tstep = conv.get("stride", 1), conv.get("off0", 0), conv.get("tstep", 1)
+    N = w.shape[-2]
+    assert w.shape[-1] == K and tuple(out.shape[-2:]) == (M, N)
+    G = out.shape[-3] if grouped else 1
+    assert not grouped or (a.shape[0] == G and w.shape[0] == G)
+    p.M, p.N, p.K = M, N, K
+    if splitk > 1:
+        assert out.shape[0] == splitk and out.dtype == torch.float32
+        p.c_slab = out.stride(0)
+        p.C, p.c_gs, p.ldc = _grouped(out[0], grouped, "out")
+    else:
+        p.C, p.c_gs, p.ldc = _grouped(out, grouped, "out")
+        p.c_slab = M * N
+    if bias is not None:
+        assert bias.dtype == torch.float32 and bias.dim() == (2 if grouped else 1) and bias.shape[-1] == N and bias.stride(-1) == 1
+        p.bias, p.bias_gs = bias.data_ptr(), (bias.stride(0) if grouped else 0)
+    if colscale is not None:
+        assert colscale.dtype == torch.float32 and colscale.shape == (N,) and colscale.stride(0) == 1
+        p.colscale = colscale.data_ptr()
+    if residual is not None:
+        assert residual.dtype == out.dtype and residual.shape == (out[0].shape if splitk > 1 else out.shape)
+        p.residual, p.r_gs, p.ldr = _grouped(residual, grouped, "residual")
+    p.act, p.groups, p.splitk = act, G, splitk
+    p.a_dtype, p.w_dtype, p.c_dtype = L.dt_code(a.dtype), (L.dt_code(w.dtype) if w_code is None else w_code), L.dt_code(out.dtype)
+    return p
+
+
+def gemm_route(p: L.GemmParams) -> str:
+    """The kernel vt_gemm takes for the block (vt_gemm_route_of): one of L.ROUTE_NAMES.  Host only."""
+    return L.ROUTE_NAMES[L.lib().vt_gemm_route_of(C.addressof(p))]
+
+
+def gemm_block(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, bias: Optional[torch.Tensor] = None, *, route: Optional[str] = None, **fields) -> str:
+    """Launch the block gemm_block_params() builds from the same arguments; returns its route name.  `route` names the kernel the caller holds to
+    account: checked BEFORE the launch, so a shape the dispatcher has moved elsewhere fails loudly instead of testing another kernel."""
+    p = gemm_block_params(a, w, out, bias, **fields)
+    got = gemm_route(p)
+    assert route is None or got == route, f"the dispatcher sends this block to {got}, the caller expects {route}"
+    L.check(L.lib().vt_gemm(C.byref(p), L.stream_ptr(out.device)), "vt_gemm")
+    return got
+
+
+def groupnorm_block_params(slabs: torch.Tensor, bias: Optional[torch.Tensor], gamma: torch.Tensor, beta: torch.Tensor, out: torch.Tensor, *, B: int, T: int,
+                           ngroups: int = 8, film: Optional[torch.Tensor] = None, film_off: int = 0, residual: Optional[torch.Tensor] = None,
+                           eps: float = 1e-5) -> L.GnParams:
+    """The parameter block of one vt_groupnorm launch over several nets, strides taken from the tensors:
+    slabs [S, nets, B*T, C] fp32; bias / gamma / beta [nets, C] with ONE common net stride (the block has a single vec_gs); film [nets, B, width]: sample
+    b of a net reads scale = film[net, b, film_off + c], shift = film[net, b, film_off + C + c]; residual / out [nets, B*T, C] of the output dtype."""
+    S, nets, M, Cc = slabs.shape
+    assert M == B * T and slabs.dtype == torch.float32 and slabs.stride(3) == 1 and out.shape == (nets, M, Cc) and out.stride(2) == 1
+    vecs = [v for v in (bias, gamma, beta) if v is not None]
+    assert all(v.dtype == torch.float32 and v.shape == (nets, Cc) and v.stride(1) == 1 and v.stride(0) == gamma.stride(0) for v in vecs)
+    p = L.GnParams()
+    p.P, p.nslabs, p.slab_stride, p.p_gs, p.ldp = slabs.data_ptr(), S, slabs.stride(0), slabs.stride(1), slabs.stride(2)
+    p.bias = 0 if bias is None else bias.data_ptr()
+    p.gamma, p.beta, p.vec_gs = gamma.data_ptr(), beta.data_ptr(), gamma.stride(0)
+    if film is not None:
+        assert film.dtype == torch.float32 and film.dim() == 3 and film.shape[:2] == (nets, B) and film.stride(2) == 1 and 0 <= film_off <= film.shape[2] - 2 * Cc
+        p.film, p.film_gs, p.film_ld, p.film_off = film.data_ptr(), film.stride(0), film.stride(1), film_off
+    if residual is not None:
+        assert residual.dtype == out.dtype and residual.shape == out.shape and residual.stride(2) == 1
+        p.residual, p.r_gs, p.ldr = residual.data_ptr(), residual.stride(0), residual.stride(1)
+    p.out, p.o_gs, p.ldo, p.out_dtype = out.data_ptr(), out.stride(0), out.stride(1), L.dt_code(out.dtype)
+    p.B, p.T, p.C, p.ngroups, p.nets, p.eps = B, T, Cc, ngroups, nets, eps
+    return p
+
+
+def groupnorm_block(slabs: torch.Tensor, bias, gamma, beta, out: torch.Tensor, **fields) -> None:
+    p = groupnorm_block_params(slabs, bias, gamma, beta, out, **fields)
+    L.check(L.lib().vt_groupnorm(C.byref(p), L.stream_ptr(out.device)), "vt_groupnorm")
+
+
 class DeviceRng:
     """Philox key + counter in device memory (vt_randn): N(0,1) draws without torch kernels, graph-replay safe."""
 
