@@ -522,6 +522,42 @@ size_t vt_imgprep_workspace_bytes(vt_imgprep_frame* frames_host, int n, int S, i
 int vt_imgprep(const vt_imgprep_frame* frames_host, const void* frames_dev, int n, int S, const void* lut, unsigned fill_rgb, int flags,
                void* out, void* ws, size_t ws_bytes, vt_stream_t stream);
 
+/* ---- colour jitter of camera frames (train/dataset.py:379-391: the brightness lift and transforms.ColorJitter on PIL images, i.e.
+ * PIL.ImageEnhance.Brightness / Contrast / Color and the HSV round trip of Image.convert).  Bit-identical to PIL; uint8 HWC RGB in, uint8
+ * HWC RGB out.  Per frame up to four operations in a stated order:
+ *   brightness(f) = blend(0, v, f);  saturation(f) = blend(L(pixel), v, f);  contrast(f) = blend(m, v, f) with
+ *   m = (int)((double)sum of L / (double)(h * w) + 0.5) over the frame as the operations before contrast left it;
+ *   hue(shift): RGB -> HSV, H = (H + shift) & 255, HSV -> RGB as Pillow's Convert.c;
+ *   blend(a, b, f) = Image.blend per byte: t = (float)a + f * ((float)b - (float)a) in fp32 without contraction, 0 for t <= 0, 255 for
+ *   t >= 255, else (int)t;  L = (19595 r + 38470 g + 7471 b + 0x8000) >> 16.
+ * order[k]: the operation of slot k (VT_COLORJITTER_BRIGHTNESS .. _HUE), VT_COLORJITTER_NONE skips the slot; no operation twice.  Any
+ * subset in any order can be stated, the empty one included (the frame is then copied, or only lifted).
+ * flags: VT_COLORJITTER_LIFT applies the brightness lift of vt_imgprep (v' = min(255, (int)(1.75f * v)) when sum / (h * w * 255.0 * 3) <= 0.15
+ * on the frame as given, decided on the device) before the operations.
+ * Two launches: exact integer sums (one uint64 partial per block in `ws`, every slot rewritten, no atomics; skipped when no frame needs
+ * one), then the per-pixel pass.  Frame i is written tight (pitch 3 * w) at out + out_off; source and output must not overlap.
+ * The table is passed as host memory (checked here) and as the same bytes in device memory (read by the kernels).  n < 1, a null source,
+ * an unknown or repeated operation id and a short workspace return VT_ERR_ARG without a launch. */
+typedef struct {
+  const void* src;      /* uint8 HWC RGB, device */
+  long pitch;           /* bytes between rows of src, >= 3 * w */
+  int h, w;             /* frame size */
+  long out_off;         /* byte offset of this frame's output in `out` */
+  int order[4];         /* operation ids in application order */
+  float brightness, contrast, saturation;   /* blend factors of the three enhance operations */
+  unsigned char hue_shift;                  /* byte added to H (int(hue * 255) mod 256) */
+  unsigned char reserved[3];
+} vt_colorjitter_frame;
+#define VT_COLORJITTER_BRIGHTNESS 0
+#define VT_COLORJITTER_CONTRAST 1
+#define VT_COLORJITTER_SATURATION 2
+#define VT_COLORJITTER_HUE 3
+#define VT_COLORJITTER_NONE 4
+#define VT_COLORJITTER_LIFT 1
+size_t vt_colorjitter_workspace_bytes(int n);
+int vt_colorjitter(const vt_colorjitter_frame* frames_host, const void* frames_dev, int n, int flags, void* out, void* ws, size_t ws_bytes,
+                   vt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,6 +4,9 @@ MI355X host, for (a) the robot step's 6 frames of 480 x 640 and (b) a labelling 
 pad + brightness check on).  Per case: the CPU path's ms per call (PIL + the host-to-device copy, ending in a synchronise), the device
 path from host frames (one copy of raw bytes included, ending in a synchronise), the device path from device-resident frames
 (back-to-back calls between two events: kernel time plus launch gaps) and its bytes moved against the 6.3 TB/s copy ceiling.
+Then the training-time colour jitter (`--image_aug`, tests/imgaug_ref.py / csrc/vt_colorjitter.hip) on the 6 frames, every frame jittered with all
+four operations: the PIL chain followed by `preprocess_images` against one `DevicePreprocessor` call with `jitter=`, beside the unjittered
+device call of the same run (key `c_jitter_6`).
 Then `step()` at batch 1 from PIL frames (so400m tower + RDT-1B, synthetic weights) with `device_preprocess` off and on, alternated in
 this process, with the spread of the repeats.  A machine without a GPU fails: nothing here is measured on a CPU.  One JSON line.
 
@@ -62,6 +65,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=7, help="alternated off / on repeats of step()")
+    ap.add_argument("--no-jitter", action="store_true", help="skip the colour-jitter leg")
     ap.add_argument("--no-step", action="store_true", help="skip the step() comparison (it builds the so400m tower and RDT-1B)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -101,6 +105,41 @@ def main():
              "speedup_vs_cpu_path": round(cpu[0] / hostf[0], 1)}
         res[tag] = r
         print(tag, r, file=sys.stderr, flush=True)
+    if not a.no_jitter:
+        from tests import imgaug_ref
+        from vlatouch.imgaug import color_jitter_params
+        n = 6
+        arrs = [(g.random((480, 640, 3)) * 256 * (0.2 if i % 5 == 4 else 1.0)).astype(np.uint8) for i in range(n)]
+        pil = [Image.fromarray(x) for x in arrs]
+        dev = [torch.from_numpy(x).to(DEV) for x in arrs]
+        gen = torch.Generator().manual_seed(0)
+        jit = [color_jitter_params(generator=gen) for _ in range(n)]          # all four operations on every frame
+        out = torch.empty(n, 3, 384, 384, dtype=torch.bfloat16, device=DEV)
+        proc = m.image_processor
+
+        def host_chain():
+            px = [imgaug_ref.train_image_chain(im, True, p, image_size=None, brightness=True, pad=True, processor=proc) for im, p in zip(pil, jit)]
+            return torch.stack(px).to(DEV, dtype=torch.bfloat16)
+        want = host_chain()
+        same = bool(torch.equal(m.preprocess_images_device(arrs, jitter=jit), want) and torch.equal(m.preprocess_images_device(dev, out=out, jitter=jit), want))
+        cpu = host_ms(host_chain, max(3, a.iters // 2), warmup=1)
+        hostf = host_ms(lambda: m.preprocess_images_device(arrs, out=out, jitter=jit), a.iters)
+        devf = host_ms(lambda: m.preprocess_images_device(dev, out=out, jitter=jit), a.iters)
+        plainh = host_ms(lambda: m.preprocess_images_device(arrs, out=out), a.iters)
+        plaind = host_ms(lambda: m.preprocess_images_device(dev, out=out), a.iters)
+        gpu = event_ms(lambda: m.preprocess_images_device(dev, out=out, jitter=jit), 10 * a.iters)
+        gpu_plain = event_ms(lambda: m.preprocess_images_device(dev, out=out), 10 * a.iters)
+        r = {"n": n, "operations_per_frame": 4, "bit_identical": same,
+             "host_chain_ms": {"median": cpu[0], "min": cpu[1], "max": cpu[2]},
+             "device_jitter_from_host_arrays_ms": {"median": hostf[0], "min": hostf[1], "max": hostf[2]},
+             "device_jitter_from_device_frames_ms": {"median": devf[0], "min": devf[1], "max": devf[2]},
+             "device_unjittered_from_host_arrays_ms": {"median": plainh[0], "min": plainh[1], "max": plainh[2]},
+             "device_unjittered_from_device_frames_ms": {"median": plaind[0], "min": plaind[1], "max": plaind[2]},
+             "device_frames_back_to_back_ms": {"jitter": gpu, "unjittered": gpu_plain},
+             "jitter_over_unjittered_from_host_arrays": round(hostf[0] / plainh[0], 2),
+             "speedup_vs_host_chain": round(cpu[0] / hostf[0], 1)}
+        res["c_jitter_6"] = r
+        print("c_jitter_6", r, file=sys.stderr, flush=True)
     if not a.no_step:
         from models.multimodal_encoder.siglip_encoder import SiglipVisionTower
         from models.rdt_runner import RDTRunner

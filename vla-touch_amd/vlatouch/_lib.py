@@ -150,6 +150,14 @@ class ImgprepFrame(C.Structure):     # vt_imgprep_frame
 IMGPREP_PAD, IMGPREP_BRIGHT, IMGPREP_OUT_BF16, IMGPREP_OUT_U8, IMGPREP_TWO_PASS = 1, 2, 4, 8, 16
 
 
+class ColorJitterFrame(C.Structure):     # vt_colorjitter_frame (operation ids: vlatouch/imgaug.py)
+    _fields_ = [("src", C.c_void_p), ("pitch", C.c_long), ("h", C.c_int), ("w", C.c_int), ("out_off", C.c_long), ("order", C.c_int * 4),
+                ("brightness", C.c_float), ("contrast", C.c_float), ("saturation", C.c_float), ("hue_shift", C.c_ubyte), ("reserved", C.c_ubyte * 3)]
+
+
+COLORJITTER_LIFT = 1
+
+
 class LstmDesc(C.Structure):
     _fields_ = [("state_dim", C.c_int), ("hidden", C.c_int), ("layers", C.c_int), ("force_dim", C.c_int),
                 ("force_pad", C.c_int), ("in_pad", C.c_int), ("cdt", C.c_int)]
@@ -291,6 +299,8 @@ SIGNATURES = {
     "vt_sample_metrics": (_I, [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "vt_imgprep_workspace_bytes": (_Z, [_P, _I, _I, _I]),
     "vt_imgprep": (_I, [_P, _P, _I, _I, _P, C.c_uint, _I, _P, _P, _Z, _P]),
+    "vt_colorjitter_workspace_bytes": (_Z, [_I]),
+    "vt_colorjitter": (_I, [_P, _P, _I, _I, _P, _P, _Z, _P]),
     "vt_marker_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     "vt_marker_detect": (_I, [_P, _I, _I, _I, _I, _I, C.c_double, C.c_double, _I, _P, _P, _I, _P, _P, _P]),
     "vt_marker_displacement": (_I, [_P, _P, _I, _I, _P, _I, _P, _P, _P]),

@@ -11,6 +11,8 @@ Host side of the feature:
     `vt_imgprep`.  Device-resident frames (pitched views included) are used in place; with frames of an already-seen geometry at
     already-seen addresses the call allocates nothing (given `out=`), copies nothing and never synchronises, so it can be captured in
     a graph together with the tower.
+  * `jitter=`: the training-time ColorJitter (vlatouch/imgaug.py, csrc/vt_colorjitter.hip) between the `image_size` pre-resize and the
+    pad, where the reference's dataset applies it (train/dataset.py:373-409): Resize -> lift -> jitter -> pad -> resize -> normalise.
 
 All launches go to the current stream; the staging buffers are reused from call to call on the assumption that calls are issued in
 stream order (the pinned buffer itself is guarded by an event).
@@ -25,6 +27,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .imgaug import OP_NONE, ColorJitterParams
 
 BILINEAR, BICUBIC = 1, 2
 _SUPPORT = {BILINEAR: 1.0, BICUBIC: 2.0}
@@ -235,8 +238,8 @@ class DevicePreprocessor:
             raise _lib.VtError("vt_imgprep_workspace_bytes: " + L.vt_last_error().decode())
         return arr, ws_bytes, off
 
-    def _plan(self, items, ws_ptr: Optional[int]):
-        key = (tuple(items), ws_ptr, self.force_two_pass)
+    def _plan(self, items, ws_ptr: Optional[int], jit: bool = False):
+        key = (tuple(items), ws_ptr, self.force_two_pass, jit)
         plan = self._plans.get(key)
         if plan is not None:
             return plan
@@ -258,6 +261,32 @@ class DevicePreprocessor:
         # the main stage's table needs the addresses of the pre-resized frames, i.e. the workspace: sized first with a placeholder base
         base = ws_ptr if ws_ptr is not None else 4096
         main_items = items if mid is None else [(base + m[4], m[1], m[2], m[3]) for m in mid]
+        if jit:
+            # the jitter stage: every frame that exists goes through it (an unjittered one with an empty operation list) into tight uint8
+            # frames of the workspace, which the main stage reads; the stage also takes the lift decision, on the frame before the jitter,
+            # so the main stage runs without VT_IMGPREP_BRIGHT and no frame is lifted twice
+            idx = [i for i, it in enumerate(main_items) if it is not None]
+            jarr = (_lib.ColorJitterFrame * len(idx))()
+            joff = 0
+            for k, i in enumerate(idx):
+                f = jarr[k]
+                f.src, f.h, f.w, f.pitch = main_items[i]
+                f.out_off = joff
+                f.order[:] = [OP_NONE] * 4
+                f.brightness = f.contrast = f.saturation = 1.0
+                joff += _align(3 * f.h * f.w, 16)
+            jws = int(_lib.lib().vt_colorjitter_workspace_bytes(len(idx)))
+            jp = {"arr": jarr, "idx": idx, "out_off": total, "ws_off": total + _align(joff, 256), "ws_bytes": jws, "free": None}
+            if ws_ptr is not None:
+                jp["pin"] = torch.empty(C.sizeof(jarr), dtype=torch.uint8).pin_memory()
+                jp["dev"] = torch.empty(C.sizeof(jarr), dtype=torch.uint8, device=self.device)
+            main_items = list(main_items)
+            for k, i in enumerate(idx):
+                main_items[i] = (base + total + jarr[k].out_off, jarr[k].h, jarr[k].w, 3 * jarr[k].w)
+            total += _align(joff, 256) + _align(jws, 256)
+            plan["jit"], plan["main_off"] = jp, total
+            flags &= ~_lib.IMGPREP_BRIGHT
+            plan["flags"] = flags
         arr2, ws2, _ = self._stage(main_items, flags, self.S, [(self.S, self.S)] * n, BICUBIC)
         plan["arr"], plan["ws_bytes_main"], plan["ws_bytes"] = arr2, ws2, total + ws2
         if ws_ptr is not None:
@@ -271,21 +300,47 @@ class DevicePreprocessor:
         raw = np.frombuffer(bytes(memoryview(arr)), dtype=np.uint8).copy()
         return torch.from_numpy(raw).to(self.device)
 
-    def workspace_bytes(self, images: Sequence) -> int:
-        """Bytes of workspace a call on these frames needs (geometry only)."""
+    @staticmethod
+    def _jitter_list(images: Sequence, jitter):
+        """`jitter` checked against the frames -> the per-frame list, or None where no frame is jittered."""
+        if jitter is None:
+            return None
+        jitter = list(jitter)
+        if len(jitter) != len(images):
+            raise _lib.VtError(f"jitter has {len(jitter)} entries for {len(images)} frames")
+        for i, (im, p) in enumerate(zip(images, jitter)):
+            if p is None:
+                continue
+            if not isinstance(p, ColorJitterParams):
+                raise _lib.VtError(f"jitter entry {i} must be None or a ColorJitterParams, got {type(p).__name__}")
+            if im is None:
+                raise _lib.VtError(f"jitter entry {i} belongs to a missing frame (the reference never augments an invalid image)")
+        return jitter if any(p is not None for p in jitter) else None
+
+    def workspace_bytes(self, images: Sequence, jitter=None) -> int:
+        """Bytes of workspace a call on these frames needs (geometry only, plus whether any frame is jittered)."""
+        jit = self._jitter_list(images, jitter) is not None
         items, _ = self._gather(images)
-        return self._plan(items, None)["ws_bytes"]
+        return self._plan(items, None, jit)["ws_bytes"]
 
     @torch.no_grad()
-    def __call__(self, images: Sequence, out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def __call__(self, images: Sequence, out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None, jitter=None) -> torch.Tensor:
+        """-> pixel_values [n, 3, S, S].  `jitter`: None, or one entry per frame, each None or a `ColorJitterParams` (never on a missing
+        frame).  Without it, or with every entry None, the call is the unjittered one: same launches, same bits, capturable in a graph.
+        A call that jitters writes its parameters into a device table through a pinned buffer and waits for the previous such copy, so
+        it is not capturable in a graph."""
         n = len(images)
         if n < 1:
             raise _lib.VtError("DevicePreprocessor: no frames")
         S = self.S
+        jitter = self._jitter_list(images, jitter)
+        jit = jitter is not None
+        if jit and torch.cuda.is_current_stream_capturing():
+            raise _lib.VtError("DevicePreprocessor: a call with jitter= cannot be captured in a graph")
         with torch.cuda.device(self.device):
             items, keep = self._gather(images)
             if workspace is None:
-                need = self._plan(items, None)["ws_bytes"]
+                need = self._plan(items, None, jit)["ws_bytes"]
                 if self._ws is None or self._ws.numel() < need:
                     if self._ws is not None and any(v.get("captured") for v in self._plans.values()):
                         self._keepalive.append(self._ws)          # a captured graph still works in the old one
@@ -293,7 +348,7 @@ class DevicePreprocessor:
                 workspace = self._ws
             elif workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.device != self.device:
                 raise _lib.VtError("workspace must be a contiguous uint8 tensor on the preprocessor's device")
-            plan = self._plan(items, workspace.data_ptr())
+            plan = self._plan(items, workspace.data_ptr(), jit)
             if torch.cuda.is_current_stream_capturing():
                 plan["captured"] = True
             if workspace.numel() < plan["ws_bytes"]:
@@ -308,6 +363,20 @@ class DevicePreprocessor:
             if pre is not None:
                 _lib.check(L.vt_imgprep(pre["arr"], _lib.ptr(pre["dev"]), n, 0, None, 0, _lib.IMGPREP_OUT_U8, C.c_void_p(wp + pre["out_off"]),
                                         C.c_void_p(wp + pre["ws_off"]), pre["ws_bytes"], st), "vt_imgprep (pre-resize)")
+            if jit:
+                jp = plan["jit"]
+                arr = type(jp["arr"]).from_buffer_copy(jp["arr"])          # the cached geometry; this call's parameters go into the copy
+                for k, i in enumerate(jp["idx"]):
+                    if jitter[i] is not None:
+                        jitter[i].fill_record(arr[k])
+                if jp["free"] is not None:
+                    jp["free"].synchronize()                                # the previous call's copy has left the pinned table
+                jp["pin"].numpy()[:] = np.frombuffer(arr, dtype=np.uint8)
+                jp["dev"].copy_(jp["pin"], non_blocking=True)
+                jp["free"] = torch.cuda.Event()
+                jp["free"].record(torch.cuda.current_stream(self.device))
+                _lib.check(L.vt_colorjitter(arr, _lib.ptr(jp["dev"]), len(jp["idx"]), _lib.COLORJITTER_LIFT if self.brightness else 0,
+                                            C.c_void_p(wp + jp["out_off"]), C.c_void_p(wp + jp["ws_off"]), jp["ws_bytes"], st), "vt_colorjitter")
             _lib.check(L.vt_imgprep(plan["arr"], _lib.ptr(plan["dev"]), n, S, _lib.ptr(self.lut), self.fill, plan["flags"], _lib.ptr(out),
                                     C.c_void_p(wp + plan["main_off"]), plan["ws_bytes_main"], st), "vt_imgprep")
         return out

@@ -720,14 +720,69 @@ def latest_checkpoint(output_dir: str) -> Optional[str]:
     return max(dirs, key=lambda d: int(d.split("-", 1)[1])) if dirs else None
 
 
-def sample_eval(runner, batches, *, num_sample_batches: int, dataset_id2name, vision_encoder=None, text_encoder=None, return_raw: bool = False):
+def _batch_img_tokens(batch, B: int, who: str, vision_encoder, preprocessor, jitter):
+    """The image tokens of a collator batch: ready `img_tokens`; `images` [B, N, C, H, W] through `vision_encoder` (train.py:420-423,
+    sample.py:34-36); or `frames`, B lists of N raw frames (None = missing), through `preprocessor` (vlatouch.imgprep.DevicePreprocessor,
+    with the flat per-frame `jitter` list or B lists of N) and then `vision_encoder`."""
+    if "img_tokens" in batch:
+        return batch["img_tokens"]
+    if vision_encoder is None:
+        raise ValueError(f"{who}: a batch with `images` needs vision_encoder")
+    if "images" in batch or "frames" not in batch:
+        images = batch["images"]
+        pixel_values = images.reshape(-1, *images.shape[2:])
+    else:
+        if preprocessor is None:
+            raise ValueError(f"{who}: a batch with `frames` needs preprocessor")
+        frames = batch["frames"]
+        if len(frames) != B:
+            raise ValueError(f"{who}: `frames` must hold B = {B} lists of frames")
+        flat = [f for sample in frames for f in sample]
+        if jitter is not None and len(jitter) == B and all(isinstance(j, (list, tuple)) for j in jitter):
+            jitter = [p for sample in jitter for p in sample]
+        pixel_values = preprocessor(flat, jitter=jitter)
+    return vision_encoder(pixel_values).detach().reshape(B, -1, vision_encoder.hidden_size)
+
+
+def _batch_lang_tokens(batch, who: str, text_encoder):
+    if "lang_embeds" in batch:
+        return batch["lang_embeds"]
+    if text_encoder is None:
+        raise ValueError(f"{who}: a batch with `input_ids` needs text_encoder")
+    return text_encoder(input_ids=batch["input_ids"], attention_mask=batch["lang_attn_mask"])["last_hidden_state"].detach()
+
+
+def prepare_batch(batch, *, vision_encoder=None, text_encoder=None, preprocessor=None, jitter=None) -> dict:
+    """What train.py:407-437 does between the loader and `rdt(...)`: the reference collator's mapping -> `train_step`'s keyword arguments.
+    `states[:, -1:, :]` is the state token, `state_elem_mask.unsqueeze(1)` the action mask, `actions` the target, `ctrl_freqs` and
+    `lang_attn_mask` pass as they are; the language is `lang_embeds` or `input_ids` through `text_encoder`; the image tokens are `img_tokens`,
+    `images` through `vision_encoder`, or (not in the reference) raw `frames` through `preprocessor` and `vision_encoder`, with the colour
+    augmentation `jitter` (the argument, or the batch's key of that name; vlatouch.imgaug.draw_image_aug) applied on the device.  Optional
+    `noise` / `timesteps` keys prescribe train_step's two random draws."""
+    states = torch.as_tensor(batch["states"])
+    B = states.shape[0]
+    if jitter is None:
+        jitter = batch.get("jitter")
+    kw = {"lang_tokens": _batch_lang_tokens(batch, "prepare_batch", text_encoder), "lang_attn_mask": batch["lang_attn_mask"],
+          "img_tokens": _batch_img_tokens(batch, B, "prepare_batch", vision_encoder, preprocessor, jitter),
+          "state_tokens": states[:, -1:, :], "action_gt": batch["actions"], "action_mask": torch.as_tensor(batch["state_elem_mask"]).unsqueeze(1),
+          "ctrl_freqs": batch["ctrl_freqs"]}
+    for key in ("noise", "timesteps"):                # train_step's two random draws, where a batch prescribes them (tests)
+        if batch.get(key) is not None:
+            kw[key] = batch[key]
+    return kw
+
+
+def sample_eval(runner, batches, *, num_sample_batches: int, dataset_id2name, vision_encoder=None, text_encoder=None, return_raw: bool = False,
+                preprocessor=None):
     """`log_sample_res` (train/sample.py:7-98): sample an action chunk with `runner.predict_action` for the first `num_sample_batches` items of
     `batches` and report, per dataset and overall, the masked MSE and the masked, state-norm-relative L2 error against the ground truth.
 
     A batch is the reference collator's mapping: `data_indices` (a list of dataset ids), `ctrl_freqs`, `state_norm` [B, A], `states`
     [B, T, A] (the last one is the state token), `actions` [B, horizon, A], `state_elem_mask` [B, A], `lang_attn_mask`; the language as
     `lang_embeds` or as `input_ids` for `text_encoder`; the images as `images` [B, N, C, H, W] for `vision_encoder` (reshaped to
-    (B, -1, vision_encoder.hidden_size), sample.py:34-36) or, not in the reference, as ready `img_tokens`; an optional `x_init` replaces
+    (B, -1, vision_encoder.hidden_size), sample.py:34-36) or, not in the reference, as ready `img_tokens` or as raw `frames` (B lists of N,
+    through `preprocessor` and `vision_encoder`, see prepare_batch); an optional `x_init` replaces
     predict_action's draw of the start noise.  `dataset_id2name`: a mapping id -> name (or a sequence of names).
 
     One vt_sample_metrics launch per batch adds into sums on the device; they are read once, after the last batch.  -> the reference's dict:
@@ -760,20 +815,9 @@ def sample_eval(runner, batches, *, num_sample_batches: int, dataset_id2name, vi
         B, H, A = actions.shape
         if len(data_indices) != B or mask.shape != (B, A) or state_norm.shape != (B, A):
             raise ValueError("sample_eval: data_indices must hold B entries, state_elem_mask and state_norm must be [B, action_dim]")
-        if "img_tokens" in batch:
-            img_tokens = batch["img_tokens"]
-        else:
-            if vision_encoder is None:
-                raise ValueError("sample_eval: a batch with `images` needs vision_encoder")
-            images = batch["images"]
-            img_tokens = vision_encoder(images.reshape(-1, *images.shape[2:])).detach().reshape(B, -1, vision_encoder.hidden_size)
+        img_tokens = _batch_img_tokens(batch, B, "sample_eval", vision_encoder, preprocessor, batch.get("jitter"))
         lang_attn_mask = batch["lang_attn_mask"]
-        if "lang_embeds" in batch:
-            lang_tokens = batch["lang_embeds"]
-        else:
-            if text_encoder is None:
-                raise ValueError("sample_eval: a batch with `input_ids` needs text_encoder")
-            lang_tokens = text_encoder(input_ids=batch["input_ids"], attention_mask=lang_attn_mask)["last_hidden_state"].detach()
+        lang_tokens = _batch_lang_tokens(batch, "sample_eval", text_encoder)
         kw = {"x_init": batch["x_init"]} if batch.get("x_init") is not None else {}
         pred = runner.predict_action(lang_tokens=lang_tokens, lang_attn_mask=lang_attn_mask, img_tokens=img_tokens,
                                      state_tokens=torch.as_tensor(batch["states"])[:, -1:, :], action_mask=mask.unsqueeze(1),
@@ -807,9 +851,10 @@ def sample_eval_means(acc, count, keys, num_sample_batches: int) -> dict:
 
 def finetune(trainer: RdtTrainer, batches, *, max_train_steps: int, checkpointing_period: Optional[int] = None, output_dir: Optional[str] = None,
              resume_from_checkpoint: Optional[str] = None, sample_period: int = -1, sample_batches=None, num_sample_batches: int = 2,
-             dataset_id2name=None, sample_ema: bool = False, log=None, vision_encoder=None, text_encoder=None) -> List[torch.Tensor]:
+             dataset_id2name=None, sample_ema: bool = False, log=None, vision_encoder=None, text_encoder=None, preprocessor=None) -> List[torch.Tensor]:
     """The reference's loop (train.py:359-489) around `trainer.train_step`: every item of `batches` is one micro-batch, a mapping of train_step's
-    keyword arguments.  Stops when `max_train_steps` optimizer steps are taken; writes `output_dir`/checkpoint-{global_step} every
+    keyword arguments, or the reference collator's mapping (recognised by its `states` key, which train_step does not take), which goes through
+    `prepare_batch` with the loop's `vision_encoder`, `text_encoder` and `preprocessor`.  Stops when `max_train_steps` optimizer steps are taken; writes `output_dir`/checkpoint-{global_step} every
     `checkpointing_period` optimizer steps; `resume_from_checkpoint` = a checkpoint's name under `output_dir` or "latest" (a missing one starts a
     new run, as there); ends with save_pretrained(output_dir) and the averaged weights in `output_dir`/ema.  Like the reference's loop it does
     not skip the batches an earlier run consumed: `batches` continues where the caller wants.  sample_period > 0: after every optimizer step with
@@ -828,12 +873,14 @@ def finetune(trainer: RdtTrainer, batches, *, max_train_steps: int, checkpointin
     for batch in batches:
         if trainer.global_step >= max_train_steps:
             break
+        if "states" in batch:
+            batch = prepare_batch(batch, vision_encoder=vision_encoder, text_encoder=text_encoder, preprocessor=preprocessor)
         losses.append(trainer.train_step(**batch))
         if trainer.sync_gradients and checkpointing_period and trainer.global_step % checkpointing_period == 0:
             trainer.save_checkpoint(os.path.join(output_dir, f"checkpoint-{trainer.global_step}"))
         if trainer.sync_gradients and sample_period is not None and sample_period > 0 and trainer.global_step % sample_period == 0:
             metrics = sample_eval(trainer.sampler(ema=sample_ema), sample_batches, num_sample_batches=num_sample_batches,
-                                  dataset_id2name=dataset_id2name, vision_encoder=vision_encoder, text_encoder=text_encoder)
+                                  dataset_id2name=dataset_id2name, vision_encoder=vision_encoder, text_encoder=text_encoder, preprocessor=preprocessor)
             if log is not None:
                 log(metrics, trainer.global_step)
     if output_dir is not None:
