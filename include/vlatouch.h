@@ -558,6 +558,33 @@ size_t vt_colorjitter_workspace_bytes(int n);
 int vt_colorjitter(const vt_colorjitter_frame* frames_host, const void* frames_dev, int n, int flags, void* out, void* ws, size_t ws_bytes,
                    vt_stream_t stream);
 
+/* ---- one fine-tuning micro-batch out of device-resident episodes (vlatouch/rdt_data.py).  Stands for, per sample,
+ * UnifiedVLADataset.parse_file (data/unified_vla_dataset_episode.py:314-351: state row, action chunk from action_id = step_id + 2 padded
+ * with its last row, the episode's std / norm, fill_in_state), VLAConsumerDataset.__getitem__ (train/dataset.py:327-344: control frequency,
+ * state noise, the state / element-mask condition masks) and DataCollatorForVLAConsumerDataset (train/dataset.py:502-530: the stacks, the
+ * zero-padded language embeddings and their mask).  The random draws are the host's; they arrive in `plan`.
+ * Device-resident tables: qpos fp64 [sum N][S] with ep_off int32 [E + 1] (row offsets); ep_stats fp64 [E][3][S] = per-episode std | mean |
+ *   rms; ds_mean fp64 [S], the dataset mean a masked state is replaced with; col_map int32 [A], unified column -> robot column or -1 (the
+ *   inverse of the fill_in_state indices); lang fp32 [sum L][D] with lang_off int32 [E + 1].
+ * plan (device, 8-byte aligned, one upload): int32 [B][4] = (episode, step_id, flags, 0) followed by fp64 z [B][S], the standard-normal
+ *   draws of the state noise (read only for samples with VT_RDT_NOISE).
+ * Outputs: states [B][1][A], actions [B][H][A], elem_mask [B][A], state_norm [B][A] fp32; ctrl_freqs [B] int64 (ctrl_freq, or 0 with
+ *   VT_RDT_MASK_FREQ); lang_out [B][Lmax][D] fp32 and lang_mask [B][Lmax] bytes (1 = a token of the instruction).
+ *   action row r = qpos[min(step_id + 2 + r, N - 1)]; state = qpos[step_id], with VT_RDT_NOISE + (0 + (std / noise_div) * z) in fp64
+ *   without contraction (noise_div = sqrt(10^(snr / 10))), with VT_RDT_MASK_STATE ds_mean instead; elem_mask = 1 on the mapped columns, all
+ *   zero with VT_RDT_MASK_ELEM; state_norm = the episode's rms; unmapped columns are 0.  Values are rounded to fp32 once, at the store.
+ * Two launches, no atomics (two calls give the same bits), no host read, allocation or synchronisation.  The caller checks the plan against
+ * its tables; an episode outside [0, E) is written as NaN rows and a step is clamped into its episode, so no entry reads outside the tables.
+ * Null pointers, sizes < 1, A < S, a grid dimension above 65535, noise_div <= 0 and a misaligned plan return VT_ERR_ARG without a launch. */
+#define VT_RDT_MASK_FREQ 1
+#define VT_RDT_MASK_STATE 2
+#define VT_RDT_MASK_ELEM 4
+#define VT_RDT_NOISE 8
+int vt_rdt_batch(const double* qpos, const int* ep_off, const double* ep_stats, const double* ds_mean, const int* col_map, const float* lang,
+                 const int* lang_off, int E, int S, int A, int H, int D, int Lmax, int ctrl_freq, double noise_div, const void* plan, int B,
+                 float* states, float* actions, float* elem_mask, float* state_norm, long long* ctrl_freqs, float* lang_out,
+                 unsigned char* lang_mask, vt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

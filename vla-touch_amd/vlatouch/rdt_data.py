@@ -1,0 +1,402 @@
+"""Fine-tuning micro-batches drawn from device-resident episodes: what feeds `vlatouch.rdt_train.finetune`.
+
+Replaces the reference's data path for `episode_*.h5` files (VLAConsumerDataset -> UnifiedVLADataset -> DataCollatorForVLAConsumerDataset):
+  * `UnifiedVLADataset.parse_file` / `parse_file_state_only` (data/unified_vla_dataset_episode.py:250-495) re-read an episode for every
+    sample; `EpisodeStore` reads every episode once, derives `qpos`, `first_idx` and the per-episode statistics on the host in fp64 and keeps
+    them, the instruction embeddings and the camera frames on the device;
+  * `compute_dataset_stat_episode.process_hdf5_dataset` is `EpisodeStore.dataset_stat`;
+  * the random decisions of `get_item`, `parse_file` and `VLAConsumerDataset.__getitem__` (train/dataset.py:300-442) are `EpisodeStore.draw`,
+    which consumes numpy's, `random`'s and torch's streams in the reference's order and returns small host records (`SamplePlan`);
+  * the sample's arrays and the collator's stacks (train/dataset.py:460-533) are one vt_rdt_batch call (csrc/vt_rdt_data.hip) in
+    `EpisodeStore.assemble`, whose result is the mapping `prepare_batch` / `sample_eval` take, with raw `frames` and `jitter`.
+
+Only precomputed instruction embeddings are built (`instruct_embeddings[0]`, the reference's use_precomp_lang_embed); `input_ids` and the
+instruction masking draw are not.  Deviations from the reference are listed in INTEGRATION.md.  Everything except `upload` / `assemble` /
+`batches` works without a GPU.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import fnmatch
+import os
+import re
+from typing import Dict, Iterator, List, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from . import h5lite
+from .imgaug import draw_image_aug
+
+MIN_STEPS = 32                      # parse_file: "we drop too-short episodes"
+STILL_EPS = 1e-2                    # parse_file: the first step whose qpos moved more than this from the first one
+DROP_SHORT = "fewer than 32 steps"
+DROP_STILL = "no step moves more than 1e-2 away from the first"
+DROP_LATE = "first_idx - 1 >= N - int(horizon / 2): no step can be drawn"
+# configs/state_vec.py as scripts/franka_model_eef.py assumes it: eef_pos x y z, eef_angle_0..5, right_gripper_open
+DEFAULT_STATE_INDICES = (30, 31, 32, 33, 34, 35, 36, 37, 38, 10)
+MASK_FREQ, MASK_STATE, MASK_ELEM, NOISE = 1, 2, 4, 8      # VT_RDT_* of include/vlatouch.h
+
+
+def episode_number(path: str) -> int:
+    m = re.search(r"episode_(\d+)", os.path.basename(path))
+    return int(m.group(1)) if m else 0
+
+
+def quat_to_ortho6d(quat: np.ndarray) -> np.ndarray:
+    """xyzw quaternions [N, 4] -> the first two columns of their rotation matrices [N, 6] (column 0, then column 1), in fp64.  The
+    reference (docs/test_6drot.py:110-116) reaches the same matrix through scipy's quaternion -> Euler -> matrix round trip."""
+    q = np.asarray(quat, dtype=np.float64)
+    x, y, z, w = (q / np.linalg.norm(q, axis=-1, keepdims=True)).T
+    c0 = np.stack([1 - 2 * (y * y + z * z), 2 * (x * y + z * w), 2 * (x * z - y * w)], axis=1)
+    c1 = np.stack([2 * (x * y - z * w), 1 - 2 * (x * x + z * z), 2 * (y * z + x * w)], axis=1)
+    return np.concatenate([c0, c1], axis=1)
+
+
+def episode_qpos(ee_poses: np.ndarray, gripper_pos: np.ndarray) -> np.ndarray:
+    """converted_ee_pose_with_gripper: [N, 10] = position | 6-D rotation | gripper (raw, not yet divided by 255)."""
+    ee = np.asarray(ee_poses, dtype=np.float64)
+    return np.concatenate([ee[:, :3], quat_to_ortho6d(ee[:, 3:]), np.asarray(gripper_pos, dtype=np.float64).reshape(-1, 1)], axis=-1)
+
+
+def first_moving_index(qpos_raw: np.ndarray) -> Optional[int]:
+    """parse_file:303-312, on qpos before the gripper is rescaled; None when the episode never moves."""
+    idx = np.where(np.any(np.abs(qpos_raw - qpos_raw[0:1]) > STILL_EPS, axis=1))[0]
+    return int(idx[0]) if len(idx) else None
+
+
+class SamplePlan:
+    """The random decisions of one sample.  episode: index among the store's kept episodes; step_id and action_id = step_id + 2; ctrl_masked /
+    state_masked / elem_masked: the three condition masks; frame_idx [hist] and slot_valid [hist]: the frame each history slot shows and
+    whether parse_file marks it valid; frame_valid [hist * cameras] (slot-major): valid, present and not masked, i.e. not the background;
+    noise: the standard-normal draws at the state indices [S] or None, and noise_snr, the SNR in dB they are scaled for; jitter
+    [hist * cameras]: ColorJitterParams or None per frame."""
+    __slots__ = ("episode", "step_id", "action_id", "ctrl_masked", "state_masked", "elem_masked", "frame_idx", "slot_valid", "frame_valid", "noise",
+                 "noise_snr", "jitter")
+
+    def __init__(self, episode, step_id, ctrl_masked, state_masked, elem_masked, frame_idx, slot_valid, frame_valid, noise=None, jitter=None,
+                 action_id=None, noise_snr=None):
+        self.episode, self.step_id = int(episode), int(step_id)
+        self.action_id = self.step_id + 2 if action_id is None else int(action_id)
+        self.ctrl_masked, self.state_masked, self.elem_masked = bool(ctrl_masked), bool(state_masked), bool(elem_masked)
+        self.frame_idx, self.slot_valid, self.frame_valid = list(frame_idx), list(slot_valid), list(frame_valid)
+        self.noise = None if noise is None else np.asarray(noise, dtype=np.float64)
+        self.noise_snr = None if noise is None else noise_snr
+        self.jitter = [None] * len(self.frame_valid) if jitter is None else list(jitter)
+
+    def flags(self) -> int:
+        return (MASK_FREQ * self.ctrl_masked | MASK_STATE * self.state_masked | MASK_ELEM * self.elem_masked | NOISE * (self.noise is not None))
+
+    def __repr__(self):
+        return (f"SamplePlan(episode={self.episode}, step_id={self.step_id}, masked=(ctrl {self.ctrl_masked}, state {self.state_masked}, "
+                f"elem {self.elem_masked}), frame_idx={self.frame_idx}, frame_valid={self.frame_valid}, noise={self.noise is not None})")
+
+
+class _Episode:
+    __slots__ = ("path", "qpos", "first_idx", "stats", "lang", "frames", "has_cam")      # frames: host arrays until upload() moves them
+
+
+class EpisodeStore:
+    """paths_or_dir: a directory of `episode_<n>.h5` files or a sequence of paths, ordered by <n>.  dataset_name / dataset_names: this
+    dataset and the list its index is looked up in (configs/finetune_datasets.json); control_freq: its frequency, or a mapping name ->
+    frequency (configs/dataset_control_freq.json).  horizon = action_chunk_size, img_history_size and state_dim as configs/base.yaml.
+    cameras: per camera slot a top-level key (a group `c` holding the array `c`, or a plain array dataset) or None for the always-missing
+    camera; the order is the reference's (camera1, camera2, the missing left wrist).  frames="device" keeps the frames in HBM, at most
+    `max_device_bytes` of them: episodes are taken whole, in order, and the first one that does not fit and every one after it stay in pinned
+    host memory; frames="host" keeps all of them there.  Host frames reach the preprocessor as host arrays, which it stages and uploads in one
+    copy per call (the staging copy is a host memcpy, so the store's pinning saves no copy, it only locks the pages)."""
+
+    def __init__(self, paths_or_dir, *, dataset_name: str, dataset_names: Sequence[str], control_freq, horizon: int = 64, img_history_size: int = 2,
+                 state_dim: int = 128, state_indices: Optional[Sequence[int]] = None, cameras: Sequence[Optional[str]] = ("camera1", "camera2", None),
+                 device="cuda", frames: str = "device", max_device_bytes: Optional[int] = None):
+        if int(horizon) != horizon or horizon < 4:
+            raise ValueError(f"EpisodeStore: horizon must be an integer >= 4, got {horizon!r} (below 4 the last drawable step has an empty action chunk)")
+        if int(img_history_size) != img_history_size or img_history_size < 1:
+            raise ValueError(f"EpisodeStore: img_history_size must be an integer >= 1, got {img_history_size!r}")
+        idx = tuple(int(i) for i in (DEFAULT_STATE_INDICES if state_indices is None else state_indices))
+        if len(idx) != 10 or len(set(idx)) != 10 or min(idx) < 0 or max(idx) >= state_dim:
+            raise ValueError(f"EpisodeStore: state_indices must be 10 distinct columns of the {state_dim}-wide unified vector, got {idx}")
+        if frames not in ("device", "host"):
+            raise ValueError(f"EpisodeStore: frames must be 'device' or 'host', got {frames!r}")
+        if max_device_bytes is not None and max_device_bytes < 0:
+            raise ValueError("EpisodeStore: max_device_bytes must be >= 0")
+        dataset_names = list(dataset_names)
+        if dataset_name not in dataset_names:
+            raise ValueError(f"EpisodeStore: dataset_name {dataset_name!r} is not in dataset_names {dataset_names}")
+        freq = control_freq[dataset_name] if hasattr(control_freq, "keys") else control_freq
+        if int(freq) != freq or freq < 1:
+            raise ValueError(f"EpisodeStore: control_freq must be a positive integer, got {freq!r}")
+        if not cameras:
+            raise ValueError("EpisodeStore: at least one camera slot is needed")
+        self.dataset_name, self.dataset_names, self.data_idx, self.control_freq = dataset_name, dataset_names, dataset_names.index(dataset_name), int(freq)
+        self.horizon, self.hist, self.state_dim, self.state_indices = int(horizon), int(img_history_size), int(state_dim), idx
+        self.cameras, self.frames_mode, self.max_device_bytes = tuple(cameras), frames, max_device_bytes
+        self.device = torch.device(device)
+        if isinstance(paths_or_dir, (str, os.PathLike)):
+            d = os.fspath(paths_or_dir)
+            paths = [os.path.join(d, f) for f in fnmatch.filter(sorted(os.listdir(d)), "*.h5")]
+        else:
+            paths = [os.fspath(p) for p in paths_or_dir]
+        self.paths = sorted(paths, key=episode_number)                 # natural_sort_filenames: stable, by the number alone
+        self.report: Dict[str, str] = {}                               # dropped file -> reason
+        self.episodes: List[_Episode] = []
+        for p in self.paths:
+            self._load(p)
+        if not self.episodes:
+            raise ValueError(f"EpisodeStore: no usable episode among {len(self.paths)} files: {self.report}")
+        self.lengths = np.array([e.qpos.shape[0] - (e.first_idx - 1) for e in self.episodes])
+        self.weights = self.lengths / np.sum(self.lengths)             # UnifiedVLADataset.episode_sample_weights
+        self._stat = None
+        self._dev = None                                                # the device tables, built by upload()
+        self.resident_bytes = 0                                         # device bytes of tables and frames after upload()
+        self.host_frame_bytes = 0                                       # frame bytes that stayed in pinned host memory
+
+    # ---- loading
+    def _camera(self, f, key):
+        if key is None or key not in f:
+            return None
+        node = f[key]
+        if isinstance(node, h5lite.Group):
+            if key not in node:
+                return None
+            node = node[key]
+        a = np.asarray(node[...])
+        if a.dtype != np.uint8 or a.ndim != 4 or a.shape[3] != 3:
+            raise ValueError(f"EpisodeStore: camera {key!r} must be uint8 [N, H, W, 3], got {a.dtype} {a.shape}")
+        return a
+
+    def _load(self, path: str) -> None:
+        with h5lite.File(path) as f:
+            raw = episode_qpos(f["ee_poses"][...], f["gripper_pos"][...])
+            n = raw.shape[0]
+            name = os.path.basename(path)
+            if n < MIN_STEPS:
+                self.report[name] = DROP_SHORT
+                return
+            first = first_moving_index(raw)
+            if first is None:
+                self.report[name] = DROP_STILL
+                return
+            if first - 1 >= n - int(self.horizon / 2):
+                self.report[name] = DROP_LATE
+                return
+            ep = _Episode()
+            ep.path, ep.first_idx = path, first
+            ep.qpos = qpos = raw / np.array([[1, 1, 1, 1, 1, 1, 1, 1, 1, 255]])
+            ep.stats = np.stack([np.std(qpos, axis=0), np.mean(qpos, axis=0), np.sqrt(np.mean(qpos ** 2, axis=0))])
+            lang = np.asarray(f["instruct_embeddings"][...])[0]
+            if lang.ndim != 2 or lang.shape[0] < 1:
+                raise ValueError(f"EpisodeStore: {name}: instruct_embeddings[0] must be [L, D], got {lang.shape}")
+            ep.lang = np.ascontiguousarray(lang, dtype=np.float32)
+            ep.frames = [self._camera(f, c) for c in self.cameras]
+            ep.has_cam = [a is not None for a in ep.frames]
+            for c, a in zip(self.cameras, ep.frames):
+                if a is not None and a.shape[0] < n:
+                    raise ValueError(f"EpisodeStore: {name}: camera {c!r} has {a.shape[0]} frames for {n} steps")
+            if self.episodes and ep.lang.shape[1] != self.episodes[0].lang.shape[1]:
+                raise ValueError(f"EpisodeStore: {name}: instruction embedding width {ep.lang.shape[1]} differs from the first episode's")
+            self.episodes.append(ep)
+
+    def __len__(self) -> int:
+        """UnifiedVLADataset.get_totol_episode_lengths: what VLAConsumerDataset.__len__ returns."""
+        return int(np.sum(self.lengths))
+
+    # ---- statistics
+    def fill_in_state(self, values: np.ndarray) -> np.ndarray:
+        uni = np.zeros(values.shape[:-1] + (self.state_dim,))
+        uni[..., list(self.state_indices)] = values
+        return uni
+
+    def dataset_stat(self) -> dict:
+        """compute_dataset_stat_episode.process_hdf5_dataset over the kept episodes, in order: the dict that file writes under the dataset's name."""
+        if self._stat is not None:
+            return self._stat
+        EPS = 1e-8
+        state_sum = state_sum_sq = z_state_sum = z_state_sum_sq = 0
+        state_cnt, nz_state_cnt, state_max, state_min = 0, None, None, None
+        for ep in self.episodes:
+            states = self.fill_in_state(ep.qpos[ep.first_idx - 1:])
+            z_states = states.copy()
+            z_states[np.abs(states) <= EPS] = 0
+            if nz_state_cnt is None:
+                nz_state_cnt = np.zeros(states.shape[1])
+            nz_state_cnt += np.sum(np.abs(states) > EPS, axis=0)
+            state_sum += np.sum(states, axis=0)
+            state_sum_sq += np.sum(states ** 2, axis=0)
+            z_state_sum += np.sum(z_states, axis=0)
+            z_state_sum_sq += np.sum(z_states ** 2, axis=0)
+            state_cnt += states.shape[0]
+            if state_max is None:
+                state_max, state_min = np.max(states, axis=0), np.min(states, axis=0)
+            else:
+                state_max, state_min = np.maximum(state_max, np.max(states, axis=0)), np.minimum(state_min, np.min(states, axis=0))
+        nz_state_cnt = np.maximum(nz_state_cnt, np.ones_like(nz_state_cnt))
+        self._stat = {
+            "dataset_name": self.dataset_name,
+            "state_mean": (state_sum / state_cnt).tolist(),
+            "state_std": np.sqrt(np.maximum((z_state_sum_sq / nz_state_cnt) - (z_state_sum / state_cnt) ** 2 * (state_cnt / nz_state_cnt),
+                                            np.zeros_like(state_sum_sq))).tolist(),
+            "state_min": state_min.tolist(),
+            "state_max": state_max.tolist(),
+        }
+        return self._stat
+
+    # ---- the draws
+    def draw(self, B: int, *, np_rng, rng, generator: Optional[torch.Generator] = None, cond_mask_prob: float = 0.1, cam_ext_mask_prob: float = -1.0,
+             state_noise_snr: Optional[float] = None, image_aug: bool = False) -> List[SamplePlan]:
+        """B samples' decisions, one sample after the other, from np_rng (numpy's legacy interface: `np.random` or a RandomState), rng (`random`
+        or a random.Random) and generator (torch; None = the global one), each consumed as the reference consumes its global stream:
+        get_item's choice(p=weights), parse_file's randint(first_idx - 1, N - int(horizon / 2)), then __getitem__'s random() for ctrl_freq,
+        normal(0, 1, (1, state_dim)) when state_noise_snr is set (all state_dim draws; the reference's normal(0, scale, shape) equals scale
+        times these), random() for the state, random() for the element mask, one random() per frame that is valid and present (against
+        cam_ext_mask_prob for camera 0 when that is >= 0, else cond_mask_prob) in slot-major order, and the augmentation draws
+        (vlatouch.imgaug.draw_image_aug) when image_aug."""
+        if int(B) != B or B < 1:
+            raise ValueError(f"draw: B must be an integer >= 1, got {B!r}")
+        ncam, hist = len(self.cameras), self.hist
+        mask_probs = [cond_mask_prob] * ncam
+        if cam_ext_mask_prob >= 0.0:
+            mask_probs[0] = cam_ext_mask_prob
+        plans = []
+        for _ in range(B):
+            e = int(np_rng.choice(len(self.episodes), p=self.weights))
+            ep = self.episodes[e]
+            n = ep.qpos.shape[0]
+            step = int(np_rng.randint(ep.first_idx - 1, n - int(self.horizon / 2)))
+            ctrl_masked = not (rng.random() > cond_mask_prob)
+            noise = None
+            if state_noise_snr is not None:
+                noise = np.asarray(np_rng.normal(0.0, 1.0, (1, self.state_dim)))[0, list(self.state_indices)]
+            state_masked = not (rng.random() > cond_mask_prob)
+            elem_masked = not (rng.random() > cond_mask_prob)
+            valid_len = min(step - (ep.first_idx - 1) + 1, hist)
+            slot_valid = [i >= hist - valid_len for i in range(hist)]
+            frame_idx = [max(step - hist + 1 + i, 0) for i in range(hist)]
+            frame_valid = []
+            for i in range(hist):
+                for j in range(ncam):
+                    frame_valid.append(bool(slot_valid[i] and ep.has_cam[j] and rng.random() > mask_probs[j]))
+            jitter = draw_image_aug(frame_valid, rng=rng, generator=generator) if image_aug else None
+            plans.append(SamplePlan(e, step, ctrl_masked, state_masked, elem_masked, frame_idx, slot_valid, frame_valid, noise, jitter,
+                                    noise_snr=state_noise_snr))
+        return plans
+
+    def check_plans(self, plans: Sequence[SamplePlan]) -> None:
+        """Refuse a plan that does not fit the tables, on the host, before anything is launched."""
+        if len(plans) < 1:
+            raise ValueError("assemble: no plans")
+        nfr = self.hist * len(self.cameras)
+        snrs: dict = {}
+        for k, p in enumerate(plans):
+            if not 0 <= p.episode < len(self.episodes):
+                raise ValueError(f"assemble: plan {k}: episode {p.episode} is not one of the {len(self.episodes)} kept episodes")
+            ep = self.episodes[p.episode]
+            n = ep.qpos.shape[0]
+            lo, hi = ep.first_idx - 1, n - int(self.horizon / 2)
+            if not lo <= p.step_id < hi:
+                raise ValueError(f"assemble: plan {k}: step_id {p.step_id} is outside [{lo}, {hi}) of episode {p.episode} ({n} steps)")
+            if p.action_id != p.step_id + 2 or p.action_id > n - 1:
+                raise ValueError(f"assemble: plan {k}: action_id {p.action_id} must be step_id + 2 = {p.step_id + 2} and a row of the episode")
+            if p.noise is not None and p.noise.shape != (len(self.state_indices),):
+                raise ValueError(f"assemble: plan {k}: noise must hold {len(self.state_indices)} draws, got {p.noise.shape}")
+            if p.noise is not None and (p.noise_snr is None or p.noise_snr != snrs.setdefault("snr", p.noise_snr)):
+                raise ValueError(f"assemble: plan {k}: noise draws need a noise_snr, the same for every noised plan of a batch (got {p.noise_snr!r})")
+            if len(p.frame_idx) != self.hist or len(p.frame_valid) != nfr or len(p.jitter) != nfr:
+                raise ValueError(f"assemble: plan {k}: {self.hist} frame indices and {nfr} frame flags / jitter entries expected")
+            for i, fi in enumerate(p.frame_idx):
+                if not 0 <= fi < n:
+                    raise ValueError(f"assemble: plan {k}: frame index {fi} of slot {i} is outside the episode")
+            for q, v in enumerate(p.frame_valid):
+                if v and not ep.has_cam[q % len(self.cameras)]:
+                    raise ValueError(f"assemble: plan {k}: frame {q} is marked valid but episode {p.episode} has no camera {q % len(self.cameras)}")
+
+    # ---- the device half
+    def upload(self) -> "EpisodeStore":
+        """Build the device tables and move the frames (once; `assemble` calls it)."""
+        if self._dev is not None:
+            return self
+        dev = L.require_gpu(self.device)
+        eps = self.episodes
+        S = len(self.state_indices)
+        i32 = lambda a: torch.tensor(a, dtype=torch.int32).to(dev)
+        col_map = np.full(self.state_dim, -1, dtype=np.int32)
+        col_map[list(self.state_indices)] = np.arange(S, dtype=np.int32)
+        mean = np.asarray(self.dataset_stat()["state_mean"], dtype=np.float64)[list(self.state_indices)]
+        d = {
+            "qpos": torch.from_numpy(np.ascontiguousarray(np.concatenate([e.qpos for e in eps], axis=0))).to(dev),
+            "ep_off": i32(np.concatenate([[0], np.cumsum([e.qpos.shape[0] for e in eps])])),
+            "stats": torch.from_numpy(np.ascontiguousarray(np.stack([e.stats for e in eps]))).to(dev),
+            "mean": torch.from_numpy(np.ascontiguousarray(mean)).to(dev),
+            "col_map": torch.from_numpy(col_map).to(dev),
+            "lang": torch.from_numpy(np.ascontiguousarray(np.concatenate([e.lang for e in eps], axis=0))).to(dev),
+            "lang_off": i32(np.concatenate([[0], np.cumsum([e.lang.shape[0] for e in eps])])),
+        }
+        self.resident_bytes = sum(t.numel() * t.element_size() for t in d.values())
+        budget = 0 if self.frames_mode == "host" else self.max_device_bytes
+        frames = []
+        for e in eps:                                                  # decided per episode, in order: the first one past the cap and all after it stay on the host
+            need = sum(a.nbytes for a in e.frames if a is not None)
+            if budget is not None:
+                budget = budget - need if need <= budget else -1      # -1: the cap is reached, nothing more goes to the device
+            per_cam = []
+            for a in e.frames:
+                if a is None:
+                    per_cam.append(None)
+                elif budget is None or budget >= 0:
+                    per_cam.append(torch.from_numpy(a).to(dev))
+                    self.resident_bytes += a.nbytes
+                else:
+                    # Pinned as a resident host store should be; note that DevicePreprocessor still copies each host frame into its own pinned
+                    # staging buffer before its one upload, so the pinning saves no copy today: it only keeps the pages locked.
+                    pinned = torch.from_numpy(a).pin_memory()
+                    per_cam.append(pinned.numpy())
+                    d.setdefault("pinned", []).append(pinned)
+                    self.host_frame_bytes += a.nbytes
+            frames.append(per_cam)
+            e.frames = None                                            # the host copies are not kept
+        d["frames"] = frames
+        self._dev = d
+        return self
+
+    def assemble(self, plans: Sequence[SamplePlan]) -> dict:
+        """plans -> the collator's mapping on the device: states [B, 1, A], actions [B, H, A], state_elem_mask [B, A], state_norm [B, A] (fp32),
+        ctrl_freqs [B] int64, data_indices (list), lang_embeds [B, Lmax, D] zero padded, lang_attn_mask [B, Lmax] bool, frames (B lists of
+        hist * cameras entries, slot-major: a uint8 [H, W, 3] view into the resident episode, a host array for an episode kept in pinned
+        memory, or None for the background) and jitter (B lists, or None when no plan carries any)."""
+        plans = list(plans)
+        self.check_plans(plans)
+        snr = next((p.noise_snr for p in plans if p.noise is not None), None)
+        noise_div = float(np.sqrt(10 ** (snr / 10))) if snr is not None else 1.0      # train/dataset.py:332
+        self.upload()
+        d, dev = self._dev, self.device
+        B, S, A, H = len(plans), len(self.state_indices), self.state_dim, self.horizon
+        D = self.episodes[0].lang.shape[1]
+        Lmax = max(self.episodes[p.episode].lang.shape[0] for p in plans)
+        buf = np.zeros(16 * B + 8 * B * S, dtype=np.uint8)
+        hdr, z = buf[:16 * B].view(np.int32).reshape(B, 4), buf[16 * B:].view(np.float64).reshape(B, S)
+        for k, p in enumerate(plans):
+            hdr[k, :3] = (p.episode, p.step_id, p.flags())
+            if p.noise is not None:
+                z[k] = p.noise
+        plan_dev = torch.from_numpy(buf).to(dev)                       # the call's one upload
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        out = {"states": f32(B, 1, A), "actions": f32(B, H, A), "state_elem_mask": f32(B, A), "state_norm": f32(B, A),
+               "ctrl_freqs": torch.empty(B, dtype=torch.int64, device=dev), "lang_embeds": f32(B, Lmax, D),
+               "lang_attn_mask": torch.empty((B, Lmax), dtype=torch.bool, device=dev)}
+        L.check(L.lib().vt_rdt_batch(L.ptr(d["qpos"]), L.ptr(d["ep_off"]), L.ptr(d["stats"]), L.ptr(d["mean"]), L.ptr(d["col_map"]), L.ptr(d["lang"]),
+                                     L.ptr(d["lang_off"]), len(self.episodes), S, A, H, D, Lmax, self.control_freq, C.c_double(noise_div),
+                                     L.ptr(plan_dev), B, L.ptr(out["states"]), L.ptr(out["actions"]), L.ptr(out["state_elem_mask"]),
+                                     L.ptr(out["state_norm"]), L.ptr(out["ctrl_freqs"]), L.ptr(out["lang_embeds"]), L.ptr(out["lang_attn_mask"]),
+                                     L.stream_ptr(dev)), "vt_rdt_batch")
+        ncam = len(self.cameras)
+        out["data_indices"] = [self.data_idx] * B
+        out["frames"] = [[d["frames"][p.episode][q % ncam][p.frame_idx[q // ncam]] if v else None for q, v in enumerate(p.frame_valid)] for p in plans]
+        out["jitter"] = [list(p.jitter) for p in plans] if any(j is not None for p in plans for j in p.jitter) else None
+        return out
+
+    def batches(self, batch_size: int, **draw_kwargs) -> Iterator[dict]:
+        """An endless iterator of micro-batches: draw(batch_size, **draw_kwargs) then assemble.  A sample loader is the same call with
+        cond_mask_prob=0, state_noise_snr=None, image_aug=False."""
+        while True:
+            yield self.assemble(self.draw(batch_size, **draw_kwargs))
