@@ -472,6 +472,25 @@ int vt_mse_loss(const void* pred, const float* target, void* dpred, float* loss,
  *   vt_ema_update_dev per tensor. */
 int vt_grad_accum_multi(const void* table, const void* fresh, int ntensors, long total_chunks, float scale, int accumulate, vt_stream_t stream);
 int vt_ema_multi(const void* table, int ntensors, long total_chunks, const float* hyper, vt_stream_t stream);
+/* AdamW with block-wise 8-bit moments (csrc/vt_adam8.hip; the dynamic block-wise quantisation of Dettmers et al., "8-bit Optimizers via
+ * Block-wise Quantization"; stands where the reference passes --use_8bit_adam, train/train.py:216-237; the arithmetic is stated in
+ * DESIGN.md §8 and tests/adam8_ref.py, UNPINNED against bitsandbytes).  A moment tensor is n uint8 codes into a 256-entry table plus one
+ * fp32 scale per block of 256 consecutive elements (the last block may be partial): value = T[code] * scale.
+ * tables: 1024 fp32 on the device = T_s[256] (signed, first moment) | T_u[256] (unsigned, second moment) | B_s[256] | B_u[256], with
+ *   B[j] = fp32(((double)T[j] + T[j+1]) / 2) for j < 255 and B[255] = +inf.  The code of x is the number of B[j] strictly below x: the nearest
+ *   table value, ties to the lower index.  vlatouch/adam8.py builds the buffer.
+ * vt_adamw8_ema_multi: one launch over the table of vt_adamw_ema_multi, whose m / v columns hold `unsigned char*` code pointers for the
+ *   records that aux marks as quantised.  aux = ntensors records of 2 x 8 bytes {float* am, float* av} (ceil(n / 256) scales each); a null
+ *   pair means fp32 m / v for that record, which is then updated with the bits of vt_adamw_ema_multi.  Per block: m = T_s[m8] am,
+ *   v = T_u[v8] av; p, m', v' (and the shadow) as vt_adamw_ema_multi computes them, p from the unquantised m', v'; am' = max |m'|,
+ *   av' = max v'; m8' = code_s(m' / am') (127 when am' = 0), v8' = code_u(v' / av') (0 when av' = 0).  No allocation, synchronisation or
+ *   atomics: two calls on the same inputs give the same bits.
+ * vt_adam8_quantize / vt_adam8_dequantize: the same block rule on its own; signed_table 1 = T_s with absmax = max |x|, 0 = T_u with
+ *   absmax = max(x, 0); codes [n], absmax [ceil(n / 256)]. */
+int vt_adamw8_ema_multi(const void* table, const void* aux, const float* tables, int ntensors, long total_chunks, const float* hyper, float beta1,
+                        float beta2, float eps, float weight_decay, vt_stream_t stream);
+int vt_adam8_quantize(const float* x, unsigned char* codes, float* absmax, const float* tables, int signed_table, long n, vt_stream_t stream);
+int vt_adam8_dequantize(const unsigned char* codes, const float* absmax, const float* tables, int signed_table, float* out, long n, vt_stream_t stream);
 /* Metrics of fine-tuning's periodic sampling evaluation (VLA/train/sample.py:55-86, log_sample_res), one call per evaluation batch.
  * pred [B][H][A] of dtype `dt` (0 fp32, 1 bf16, 3 fp16), target [B][H][A], mask [B][A] (0 / 1) and state_norm [B][A] fp32, the last two
  * broadcast over H; dataset_idx [B] int32 in [0, n_datasets).  Per element in fp32: sq = (pred - target)^2, l2 = sqrt(sq) / (state_norm + 1e-3).

@@ -16,6 +16,13 @@ K - 1 micro-batches without an optimizer step) or clip + AdamW + EMA (the K-th);
 whole window; peak memory; the bytes the accumulate and EMA-only launches move (12 B per parameter each) against the HBM roof; and, from a K = 1
 trainer in the same process, the clip + AdamW + EMA phase the two launches together are held against.  Added to `--out` under the key
 `accumulation`; the other keys of the file stay as they are.
+
+`--optimizer adamw8bit` measures the optimizer phase with block-wise 8-bit moments (csrc/vt_adam8.hip) beside the 32-bit one at the first batch
+size: one trainer of each kind in one process, their steps alternating and swapping who goes first, `--steps` (at least 5) timed after `--warmup`,
+device-synchronised host wall clock and device events:
+the whole phase (clip + AdamW + EMA, and in bf16 the refresh of the 16-bit weight copies, as `clip_adamw_ema_ms` of the default run counts it)
+and the AdamW + EMA launch alone with the bytes it moves (24 B per parameter of a quantised tensor plus its scales, 36 B otherwise) against the
+HBM roof; optimizer state bytes; peak device memory of a step of each trainer.  Added to `--out` under the key `adamw8bit`; the other keys stay.
 """
 from __future__ import annotations
 
@@ -157,6 +164,85 @@ def accum_run(a, c, sd, params, dev):
     return out
 
 
+def optimizer_run(a, c, sd, params, dev):
+    """The optimizer phase of an "adamw8bit" and an "adamw" trainer, alternating in this process at batch a.batch[0] -> dict."""
+    from vlatouch import _lib as L
+    from vlatouch import adam8
+    from vlatouch.rdt_train import RdtTrainer, _sp
+    B = a.batch[0]
+    steps = max(5, a.steps)
+    sync = lambda: torch.cuda.synchronize(dev)
+    args, kw = inputs(a, B, dev)
+    kinds = ("adamw8bit", "adamw")
+    trs, peak = {}, {}
+    for kind in kinds:                                       # peak memory of one whole step of each trainer, over what is already resident
+        torch.cuda.empty_cache()
+        base = torch.cuda.memory_allocated(dev)
+        torch.cuda.reset_peak_memory_stats(dev)
+        tr = trs[kind] = RdtTrainer(sd, heads=c["heads"], horizon=64, action_dim=128, lr=a.lr, precision=a.precision, optimizer=kind, device=dev)
+        for _ in range(max(1, a.warmup)):
+            tr.get_loss(*args, **kw)
+            tr.optimizer_step()
+        sync()
+        peak[kind] = (torch.cuda.max_memory_allocated(dev) - base) / 2 ** 30
+    ev = lambda: torch.cuda.Event(enable_timing=True)
+    phase = {k: [] for k in kinds}
+    phase_dev = {k: [] for k in kinds}
+    losses = {k: [] for k in kinds}
+    for n in range(steps):
+        for kind in (kinds if n % 2 == 0 else kinds[::-1]):  # who goes first alternates, so neither kind always follows the other's step
+            tr = trs[kind]
+            loss = tr.get_loss(*args, **kw)
+            e0, e1 = ev(), ev()
+            sync(); t0 = time.perf_counter()
+            e0.record()
+            tr.optimizer_step()
+            e1.record()
+            sync(); t1 = time.perf_counter()
+            phase[kind].append(1e3 * (t1 - t0))              # host wall clock: the table's rows, the hyper floats' upload and the launches
+            phase_dev[kind].append(e0.elapsed_time(e1))      # device events: from before the first launch to after the last
+            losses[kind].append(float(loss))
+    # the AdamW + EMA launch alone, on the state the steps left (it moves the same bytes whatever the values)
+    launch = {k: [] for k in kinds}
+    lib = L.lib()
+    hy = torch.zeros(4)
+    L.check(lib.vt_train_hyper(a.lr, 0.9, 0.999, steps + a.warmup + 1, 0.9999, L.ptr(hy)), "vt_train_hyper")
+    hy = hy.to(dev)
+    for n in range(2 + steps):
+        for kind in (kinds if n % 2 == 0 else kinds[::-1]):
+            tr = trs[kind]
+            tab, nt, chunks = tr._table()
+            e0, e1 = ev(), ev()
+            sync()
+            e0.record()
+            if kind == "adamw8bit":
+                L.check(lib.vt_adamw8_ema_multi(L.ptr(tab), L.ptr(tr._aux_dev), L.ptr(tr._tables8), nt, chunks, L.ptr(hy), 0.9, 0.999, tr.eps, tr.wd, _sp(dev)),
+                        "vt_adamw8_ema_multi")
+            else:
+                L.check(lib.vt_adamw_ema_multi(L.ptr(tab), nt, chunks, L.ptr(hy), 0.9, 0.999, tr.eps, tr.wd, _sp(dev)), "vt_adamw_ema_multi")
+            e1.record()
+            sync()
+            if n >= 2:
+                launch[kind].append(e0.elapsed_time(e1))
+    numels = [v.numel() for v in sd.values()]
+    q = sum(n for n in numels if n >= adam8.MIN_8BIT_SIZE)
+    moved = {"adamw": 36.0 * params, "adamw8bit": 24.0 * q + 16.0 * sum(adam8.nblocks(n) for n in numels if n >= adam8.MIN_8BIT_SIZE) + 36.0 * (params - q)}
+    out = {"batch": B, "precision": a.precision, "parameters": params, "parameters_quantised": q, "warmup": a.warmup, "timed_steps": steps}
+    for kind in kinds:
+        ls = _stats(launch[kind])
+        rate = moved[kind] / (ls["median"] / 1e3)
+        ls.update(bytes_moved=moved[kind], bytes_per_s=rate, share_of_hbm_spec=rate / HBM_SPEC_BYTES_PER_S, share_of_float4_copy_rate=rate / HBM_COPY_BYTES_PER_S)
+        out[kind] = {"optimizer_phase_ms": _stats(phase[kind]), "optimizer_phase_device_ms": _stats(phase_dev[kind]), "adamw_ema_launch_ms": ls, "optimizer_state_bytes": trs[kind].optimizer_state_bytes(),
+                     "peak_memory_gib_of_a_step": peak[kind], "losses": losses[kind]}
+    out["phase_8bit_over_32bit"] = out["adamw8bit"]["optimizer_phase_ms"]["median"] / out["adamw"]["optimizer_phase_ms"]["median"]
+    out["launch_8bit_over_32bit"] = out["adamw8bit"]["adamw_ema_launch_ms"]["median"] / out["adamw"]["adamw_ema_launch_ms"]["median"]
+    out["phase_device_8bit_over_32bit"] = out["adamw8bit"]["optimizer_phase_device_ms"]["median"] / out["adamw"]["optimizer_phase_device_ms"]["median"]
+    out["timing"] = ("optimizer_phase_ms: host wall clock between two device synchronisations; optimizer_phase_device_ms and adamw_ema_launch_ms: "
+                     "device events; the two trainers alternate and swap who goes first every step")
+    out["no_slower_than_the_32bit_phase"] = bool(out["phase_8bit_over_32bit"] <= 1.0 and out["phase_device_8bit_over_32bit"] <= 1.0)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, nargs="+", default=[4, 32])
@@ -170,6 +256,8 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--accum", type=int, default=1, help="gradient_accumulation_steps; > 1 measures the accumulated step and adds it to --out")
+    ap.add_argument("--optimizer", default="adamw", choices=["adamw", "adamw8bit"],
+                    help="adamw8bit measures the 8-bit optimizer phase beside the 32-bit one and adds it to --out")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rdt_train_bench.json"))
     a = ap.parse_args()
     from vlatouch.rdt_train import RdtTrainer
@@ -178,6 +266,17 @@ def main():
              state_token_dim=128, max_lang_cond_len=1024, img_cond_len=a.img_len)
     sd = synth.fill_state_dict_device(synth.rdt_runner_shapes(**c), dev, torch.float32, seed=7)
     params = sum(v.numel() for v in sd.values())
+    if a.optimizer == "adamw8bit":
+        rec = {}
+        if os.path.exists(a.out):
+            with open(a.out) as f:
+                rec = json.load(f)
+        rec["adamw8bit"] = dict(optimizer_run(a, c, sd, params, dev), config=c, lang_len=a.lang_len, lr=a.lr, device=torch.cuda.get_device_name(dev))
+        print(json.dumps(rec["adamw8bit"]))
+        with open(a.out, "w") as f:
+            json.dump(rec, f, indent=1)
+        print("wrote", a.out)
+        return
     if a.accum > 1:
         rec = {}
         if os.path.exists(a.out):
@@ -189,10 +288,11 @@ def main():
             json.dump(rec, f, indent=1)
         print("wrote", a.out)
         return
-    kept = None
+    kept = {}
     if os.path.exists(a.out):
         with open(a.out) as f:
-            kept = json.load(f).get("accumulation")
+            old = json.load(f)
+        kept = {k: old[k] for k in ("accumulation", "adamw8bit") if k in old}
     rec = {"config": c, "precision": a.precision, "parameters": params, "lang_len": a.lang_len, "warmup": a.warmup, "steps": a.steps, "lr": a.lr,
            "device": torch.cuda.get_device_name(dev), "runs": []}
     sync = lambda: torch.cuda.synchronize(dev)
@@ -229,8 +329,7 @@ def main():
                 run["torch_autograd_yardstick"]["ratio_torch_over_this"] = run["torch_autograd_yardstick"]["fwd_bwd_ms"] / ((t_fb) * k)
         print(json.dumps(run))
         rec["runs"].append(run)
-    if kept is not None:
-        rec["accumulation"] = kept                # measured by --accum K: not this run's to drop
+    rec.update(kept)                              # measured by --accum K / --optimizer adamw8bit: not this run's to drop
     with open(a.out, "w") as f:
         json.dump(rec, f, indent=1)
     print("wrote", a.out)

@@ -8,6 +8,7 @@
 #include <math.h>
 #include "vt_common.h"
 #include "vt_host.h"
+#include "vt_adamw_elem.h"
 #include "../../include/vlatouch.h"
 
 namespace {
@@ -277,21 +278,7 @@ __global__ __launch_bounds__(256) void si_loss_kernel(const float* __restrict__ 
   if (threadIdx.x == 0) loss[0] = ((red[0] + red[1]) + (red[2] + red[3])) * invB;
 }
 
-// One element of torch.optim.AdamW / torch_ema.  Contraction is switched off so that the three kernels below (scalar arguments, scalars from
-// device memory, multi-tensor table) round identically: a replayed graph and the eager step then agree bit for bit.
-__device__ __forceinline__ float adamw_elem(float p, float gv, float& m, float& v, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt) {
-#pragma clang fp contract(off)
-  const float pv = p * (1.0f - lr * wd);
-  const float mv = b1 * m + (1.0f - b1) * gv;
-  const float vv = b2 * v + (1.0f - b2) * gv * gv;
-  m = mv; v = vv;
-  const float denom = sqrtf(vv) / bc2_sqrt + eps;
-  return pv - (lr / bc1) * (mv / denom);
-}
-__device__ __forceinline__ float ema_elem(float sh, float p, float one_minus_decay) {
-#pragma clang fp contract(off)
-  return sh - one_minus_decay * (sh - p);
-}
+// adamw_elem / ema_elem, one element of torch.optim.AdamW / torch_ema with contraction off: vt_adamw_elem.h (shared with vt_adam8.hip)
 // torch.optim.AdamW (decoupled weight decay, bias-corrected moments), one fused pass
 __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long n, float lr, float b1, float b2,
                              float eps, float wd, float bc1, float bc2_sqrt) {
@@ -328,16 +315,7 @@ __global__ __launch_bounds__(256) void adamw_ema_mt_kernel(const MtEntry* __rest
   const MtEntry e = tab[lo];
   const long base = (chunk - e.first_chunk) * 4096;
   const float lr = hyper[0], bc1 = hyper[1], bc2_sqrt = hyper[2], omd = hyper[3];
-#pragma unroll 4
-  for (int it = 0; it < 16; ++it) {
-    const long i = base + it * 256 + threadIdx.x;
-    if (i >= e.n) break;
-    float mv = e.m[i], vv = e.v[i];
-    const float pv = adamw_elem(e.p[i], e.g[i], mv, vv, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
-    e.m[i] = mv; e.v[i] = vv;
-    e.p[i] = pv;
-    if (e.shadow) e.shadow[i] = ema_elem(e.shadow[i], pv, omd);
-  }
+  adamw_ema_chunk_f32(e.p, e.g, e.m, e.v, e.shadow, base, e.n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, omd);
 }
 
 // torch_ema: shadow -= (1 - decay) * (shadow - p)

@@ -28,6 +28,7 @@ from typing import Dict, List, Optional
 import torch
 
 from . import _lib as L
+from . import adam8
 from . import ops
 from . import train as T
 from .train import _Optimizer, _empty, _sp
@@ -35,6 +36,7 @@ from .train import _Optimizer, _empty, _sp
 F32 = torch.float32
 LR_SCHEDULERS = ("constant", "constant_with_warmup")
 PREDICTION_TYPES = ("sample", "epsilon")
+OPTIMIZERS = ("adamw", "adamw8bit")
 
 
 # ---------------------------------------------------------------------------------------------- host-side schedules
@@ -206,19 +208,26 @@ class RdtTrainer(_Optimizer):
     """get_loss + backward + clip + AdamW + EMA for `RDTRunner` (all of its parameters train, the three position embeddings included).
 
     sd: the runner's state dict (reference keys).  Hyper-parameters default to main.py:125-210 (lr 5e-6, betas 0.9 / 0.999, eps 1e-8, weight decay
-    1e-2, max_grad_norm 1.0) and EMAModel's constructor."""
+    1e-2, max_grad_norm 1.0) and EMAModel's constructor.
+
+    optimizer="adamw8bit" (the reference's --use_8bit_adam, train.py:216-237) keeps the AdamW moments of every tensor of at least
+    adam8.MIN_8BIT_SIZE elements as uint8 codes with one fp32 scale per 256 elements (vlatouch/adam8.py, csrc/vt_adam8.hip; DESIGN.md §8 states
+    the arithmetic, UNPINNED against bitsandbytes); smaller tensors keep fp32 moments and the bits of the default step.  `_m` / `_v` then hold
+    the codes (uint8) or the fp32 moments, `_am` / `_av` the scales; `moments(name)` dequantises."""
 
     def __init__(self, sd, *, heads: int, horizon: int, action_dim: int, rms_mode: str = "meansq", prediction_type: str = "sample",
                  num_train_timesteps: int = 1000, beta_schedule: str = "squaredcos_cap_v2", precision: str = "fp32", lr: float = 5e-6,
                  betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, max_grad_norm: float = 1.0, lr_scheduler: str = "constant",
                  lr_warmup_steps: int = 500, ema: Optional[dict] = None, config: Optional[dict] = None, gradient_accumulation_steps: int = 1,
-                 device="cuda"):
+                 optimizer: str = "adamw", device="cuda"):
         if precision not in ("fp32", "bf16"):
             raise ValueError(f"precision must be 'fp32' or 'bf16', got {precision!r} (no fp16 training mode: its gradients underflow without loss scaling)")
         if prediction_type not in PREDICTION_TYPES:
             raise ValueError(f"Unsupported prediction type {prediction_type}")
         if rms_mode not in ("meansq", "var"):
             raise ValueError(f"rms_mode must be 'meansq' or 'var', got {rms_mode!r}")
+        if optimizer not in OPTIMIZERS:
+            raise ValueError(f"optimizer must be one of {OPTIMIZERS}, got {optimizer!r}")
         lr_at(lr, lr_scheduler, 0, lr_warmup_steps)                       # raises on an unknown scheduler
         if int(gradient_accumulation_steps) != gradient_accumulation_steps or gradient_accumulation_steps < 1:
             raise ValueError(f"gradient_accumulation_steps must be an integer >= 1, got {gradient_accumulation_steps!r}")
@@ -258,6 +267,11 @@ class RdtTrainer(_Optimizer):
         self._m: Dict[str, torch.Tensor] = {}                 # AdamW moments and the EMA copy appear with the first optimizer step (the parameters are
         self._v: Dict[str, torch.Tensor] = {}                 # still the initial ones then), so a trainer that only evaluates the loss holds one copy
         self.shadow: Dict[str, torch.Tensor] = {}
+        self.optimizer = optimizer
+        self._am: Dict[str, torch.Tensor] = {}                # adamw8bit: the per-block scales of the quantised tensors' two moments,
+        self._av: Dict[str, torch.Tensor] = {}                # the code tables + boundaries on the device, and the table's {am, av} companion
+        self._tables8: Optional[torch.Tensor] = None
+        self._aux_dev: Optional[torch.Tensor] = None
         self._norm_coef = torch.zeros(2, dtype=F32, device=dev)
         self._table_key = None
         self.last_loss: Optional[torch.Tensor] = None
@@ -510,8 +524,11 @@ class RdtTrainer(_Optimizer):
         if self.k > 1 and not self._acc:
             self._acc = {k: torch.empty_like(v) for k, v in self.p.items()}          # never read before the window's first, storing, accumulate
         if not self.shadow:
-            self._m = {k: torch.zeros_like(v) for k, v in self.p.items()}
-            self._v = {k: torch.zeros_like(v) for k, v in self.p.items()}
+            if self.optimizer == "adamw8bit":
+                self._set_state8(self._zero_state8())
+            else:
+                self._m = {k: torch.zeros_like(v) for k, v in self.p.items()}
+                self._v = {k: torch.zeros_like(v) for k, v in self.p.items()}
             self.shadow = {k: v.clone() for k, v in self.p.items()}
         for name, pt, gt in self._all_params():
             if gt is None:
@@ -543,11 +560,76 @@ class RdtTrainer(_Optimizer):
         L.check(lib.vt_train_hyper(self.lr, self.betas[0], self.betas[1], self.step_count, self._ema_decay(self.ema_updates), L.ptr(host)), "vt_train_hyper")
         hy = host.to(dev)
         L.check(lib.vt_grad_clip_multi(L.ptr(tab), n, chunks, self.max_grad_norm, L.ptr(self._chunk_part), L.ptr(self._norm_coef), _sp(dev)), "vt_grad_clip_multi")
-        L.check(lib.vt_adamw_ema_multi(L.ptr(tab), n, chunks, L.ptr(hy), self.betas[0], self.betas[1], self.eps, self.wd, _sp(dev)), "vt_adamw_ema_multi")
+        if self.optimizer == "adamw8bit":
+            L.check(lib.vt_adamw8_ema_multi(L.ptr(tab), L.ptr(self._aux_dev), L.ptr(self._tables8), n, chunks, L.ptr(hy), self.betas[0], self.betas[1],
+                                            self.eps, self.wd, _sp(dev)), "vt_adamw8_ema_multi")
+        else:
+            L.check(lib.vt_adamw_ema_multi(L.ptr(tab), n, chunks, L.ptr(hy), self.betas[0], self.betas[1], self.eps, self.wd, _sp(dev)), "vt_adamw_ema_multi")
         self._refresh16()
         self.micro_step, self.sync_gradients = 0, True
         self.weights_version += 1
         self.shadow_version += 1
+
+    # ---- adamw8bit state
+    def _zero_state8(self) -> Dict[str, torch.Tensor]:
+        """Exactly zero moments in the layout of checkpoint/adam8.safetensors: codes 127 / 0 with zero scales, or fp32 zeros for a small tensor."""
+        dev, out = self.device, {}
+        for k, v in self.p.items():
+            n = v.numel()
+            if n >= adam8.MIN_8BIT_SIZE:
+                out[f"m8.{k}"] = torch.full((n,), adam8.ZERO_CODE_SIGNED, dtype=torch.uint8, device=dev)
+                out[f"v8.{k}"] = torch.full((n,), adam8.ZERO_CODE_UNSIGNED, dtype=torch.uint8, device=dev)
+                out[f"am.{k}"] = torch.zeros(adam8.nblocks(n), dtype=F32, device=dev)
+                out[f"av.{k}"] = torch.zeros(adam8.nblocks(n), dtype=F32, device=dev)
+            else:
+                out[f"m.{k}"], out[f"v.{k}"] = torch.zeros(n, dtype=F32, device=dev), torch.zeros(n, dtype=F32, device=dev)
+        return out
+
+    def _state8(self) -> Dict[str, torch.Tensor]:
+        """The live 8-bit state under the keys of `_zero_state8` (device tensors, not copies)."""
+        out = {}
+        for k in self.p:
+            if k in self._am:
+                out[f"m8.{k}"], out[f"v8.{k}"], out[f"am.{k}"], out[f"av.{k}"] = self._m[k], self._v[k], self._am[k], self._av[k]
+            else:
+                out[f"m.{k}"], out[f"v.{k}"] = self._m[k], self._v[k]
+        return out
+
+    def _set_state8(self, st: Dict[str, torch.Tensor]) -> None:
+        """Adopt a state in that layout (checked against the parameters' sizes) and put the tables on the device."""
+        dev, m, v, am, av = self.device, {}, {}, {}, {}
+        for k, p in self.p.items():
+            n = p.numel()
+            spec = ((("m8", torch.uint8, n), ("v8", torch.uint8, n), ("am", F32, adam8.nblocks(n)), ("av", F32, adam8.nblocks(n)))
+                    if n >= adam8.MIN_8BIT_SIZE else (("m", F32, n), ("v", F32, n)))
+            for tag, dt, cnt in spec:
+                t = st.get(f"{tag}.{k}")
+                if t is None or t.dtype != dt or t.numel() != cnt:
+                    raise ValueError(f"adamw8bit state: {tag}.{k} missing or not {cnt} x {dt}")
+                {"m8": m, "m": m, "v8": v, "v": v, "am": am, "av": av}[tag][k] = t.to(dev).contiguous().reshape(cnt)
+        self._m, self._v, self._am, self._av = m, v, am, av
+        aux = [[am[k].data_ptr(), av[k].data_ptr()] if k in am else [0, 0] for k in self.p]      # {am, av} per row of the table, a null pair where the moments
+        self._aux_dev = torch.tensor(aux, dtype=torch.int64).to(dev)                             # are fp32; the state does not move, so it is built here, once
+        if self._tables8 is None:
+            self._tables8 = adam8.device_tables(dev)
+        self._table_key = None
+
+    def moments(self, name: str):
+        """AdamW's (m, v) of one parameter as fp32 device tensors of its shape (zeros before the first optimizer step); adamw8bit: dequantised."""
+        p = self.p[name]
+        if name not in self._m:
+            return torch.zeros_like(p), torch.zeros_like(p)
+        if name in self._am:
+            return (adam8.dequantize(self._m[name], self._am[name], self._tables8, True).view(p.shape),
+                    adam8.dequantize(self._v[name], self._av[name], self._tables8, False).view(p.shape))
+        return self._m[name].clone().view(p.shape), self._v[name].clone().view(p.shape)
+
+    def optimizer_state_bytes(self) -> int:
+        """Bytes of AdamW state (moments, and codes + scales for adamw8bit) this trainer holds once it has stepped; EMA shadows not counted."""
+        if self._m:
+            return sum(t.numel() * t.element_size() for d in (self._m, self._v, self._am, self._av) for t in d.values())
+        numels = [v.numel() for v in self.p.values()]
+        return adam8.state_bytes(numels) if self.optimizer == "adamw8bit" else 8 * sum(numels)
 
     def accumulate(self) -> None:
         """k > 1: fold the gradients get_loss left in `self.g` into the accumulators, scaled by 1 / k (accelerator.backward's loss / k); the
@@ -661,7 +743,9 @@ class RdtTrainer(_Optimizer):
     def save_checkpoint(self, path: str) -> None:
         """`path`/checkpoint/{model,adam_m,adam_v}.safetensors (fp32 master weights and AdamW moments), `path`/ema/ (the averaged weights as
         RDTRunner.from_pretrained reads them: the reference's checkpoint-N/ema placement) and `path`/trainer_state.json (the counters, k,
-        precision, hyper-parameters).  Only between accumulation windows, where the reference saves."""
+        precision, hyper-parameters).  Only between accumulation windows, where the reference saves.  optimizer="adamw8bit" writes
+        checkpoint/adam8.safetensors in place of adam_m / adam_v (codes `m8.` / `v8.` and scales `am.` / `av.` + parameter name, fp32 moments
+        `m.` / `v.` of the small tensors, the two code tables) and adds `optimizer` and `block` to trainer_state.json."""
         if self.micro_step != 0:
             raise RuntimeError(f"save_checkpoint in the middle of an accumulation window ({self.micro_step} of {self.k} micro-batches): "
                                "the partial gradient sum is not part of a checkpoint")
@@ -670,36 +754,60 @@ class RdtTrainer(_Optimizer):
         os.makedirs(os.path.join(path, "checkpoint"), exist_ok=True)
         os.makedirs(os.path.join(path, "ema"), exist_ok=True)
         save_file(cpu(self.p), os.path.join(path, "checkpoint", "model.safetensors"))
-        save_file(cpu(self._m), os.path.join(path, "checkpoint", "adam_m.safetensors"))
-        save_file(cpu(self._v), os.path.join(path, "checkpoint", "adam_v.safetensors"))
+        if self.optimizer == "adamw8bit":
+            ts, tu = adam8.code_tables()
+            st = {k: v.detach().cpu().contiguous() for k, v in (self._state8() if self._m else self._zero_state8()).items()}
+            st["table_signed"], st["table_unsigned"] = torch.from_numpy(ts), torch.from_numpy(tu)
+            save_file(st, os.path.join(path, "checkpoint", "adam8.safetensors"))
+        else:
+            save_file(cpu(self._m), os.path.join(path, "checkpoint", "adam_m.safetensors"))
+            save_file(cpu(self._v), os.path.join(path, "checkpoint", "adam_v.safetensors"))
         save_file({k: v.contiguous() for k, v in self.ema_state_dict().items()}, os.path.join(path, "ema", "model.safetensors"))
         if self.config is not None:
             with open(os.path.join(path, "ema", "config.json"), "w") as fjs:
                 json.dump(self.config, fjs, indent=2)
         state = dict(step_count=self.step_count, ema_updates=self.ema_updates, global_step=self.global_step, gradient_accumulation_steps=self.k,
                      precision=self.precision, hyper={n: getattr(self, n) for n in self._HYPER})
+        if self.optimizer == "adamw8bit":
+            state.update(optimizer=self.optimizer, block=adam8.BLOCK)
         with open(os.path.join(path, "trainer_state.json"), "w") as fjs:
             json.dump(state, fjs, indent=2)
 
     def load_checkpoint(self, path: str) -> None:
         """Restore what save_checkpoint wrote into this trainer (built on the same model with the same gradient_accumulation_steps): weights,
         moments, EMA shadows, counters and hyper-parameters; training then continues bit for bit.  Unlike the reference, which starts its
-        EMAModel.optimization_step at 0 again, the EMA update count is restored."""
+        EMAModel.optimization_step at 0 again, the EMA update count is restored.  A checkpoint written by the other optimizer is refused (a
+        trainer_state.json without the `optimizer` key is an "adamw" one): the two kinds of state are not converted into each other."""
         from safetensors.torch import load_file
         with open(os.path.join(path, "trainer_state.json")) as fjs:
             state = json.load(fjs)
         if state["gradient_accumulation_steps"] != self.k:
             raise ValueError(f"checkpoint was written with gradient_accumulation_steps={state['gradient_accumulation_steps']}, this trainer has {self.k}")
-        parts = {n: load_file(os.path.join(path, *f)) for n, f in (("p", ("checkpoint", "model.safetensors")), ("m", ("checkpoint", "adam_m.safetensors")),
-                                                                   ("v", ("checkpoint", "adam_v.safetensors")), ("ema", ("ema", "model.safetensors")))}
+        if state.get("optimizer", "adamw") != self.optimizer:
+            raise ValueError(f"checkpoint was written by optimizer={state.get('optimizer', 'adamw')!r}, this trainer has {self.optimizer!r}")
+        files = [("p", ("checkpoint", "model.safetensors")), ("ema", ("ema", "model.safetensors"))]
+        if self.optimizer == "adamw8bit":
+            if state.get("block") != adam8.BLOCK:
+                raise ValueError(f"checkpoint {path}: adamw8bit block size {state.get('block')!r}, this build has {adam8.BLOCK}")
+            st8 = load_file(os.path.join(path, "checkpoint", "adam8.safetensors"))
+            for key, want in zip(("table_signed", "table_unsigned"), adam8.code_tables()):
+                got = st8.pop(key, None)
+                if got is None or got.dtype != F32 or got.shape != (256,) or not torch.equal(got.view(torch.int32), torch.from_numpy(want).view(torch.int32)):
+                    raise ValueError(f"checkpoint {path}: {key} is not this build's code table")
+        else:
+            files += [("m", ("checkpoint", "adam_m.safetensors")), ("v", ("checkpoint", "adam_v.safetensors"))]
+        parts = {n: load_file(os.path.join(path, *f)) for n, f in files}
         for n, d in parts.items():
             if set(d) != set(self.p) or any(d[k].shape != v.shape or d[k].dtype != F32 for k, v in self.p.items()):
                 raise ValueError(f"checkpoint {path}: the {n} tensors do not match this trainer's parameters")
         dev = self.device
+        if self.optimizer == "adamw8bit":
+            self._set_state8(st8)                                 # checks before it adopts: a mismatch leaves the trainer as it was
         for k, v in self.p.items():
             v.copy_(parts["p"][k])
-        self._m = {k: parts["m"][k].to(dev).contiguous() for k in self.p}
-        self._v = {k: parts["v"][k].to(dev).contiguous() for k in self.p}
+        if self.optimizer != "adamw8bit":
+            self._m = {k: parts["m"][k].to(dev).contiguous() for k in self.p}
+            self._v = {k: parts["v"][k].to(dev).contiguous() for k in self.p}
         self.shadow = {k: parts["ema"][k].to(dev).contiguous() for k in self.p}
         for n, val in state["hyper"].items():
             setattr(self, n, tuple(val) if n == "betas" else val)
