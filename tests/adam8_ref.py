@@ -1,7 +1,7 @@
 """The block-wise 8-bit AdamW statement of DESIGN.md §8 in numpy: what csrc/vt_adam8.hip and vlatouch/adam8.py are held against.
 
 Tables in fp64, rounded once to fp32; boundaries the fp32-rounded fp64 midpoints; the code of x = the number of boundaries strictly below x
-(nearest value, ties to the lower index).  The step is fp32, one rounding per operation in the order of csrc/vt_adamw_elem.h (numpy does
+(nearest value, ties to the lower index).  The step is fp32, one rounding per operation in the order of csrc/vt_optim.h (numpy does
 not contract).  `step8(..., dtype=np.float64)` evaluates the same step from the same codes in fp64: the yardstick of the tolerances.
 Written on its own: nothing here imports the product."""
 import numpy as np
@@ -77,7 +77,7 @@ def hyper(lr, b1, b2, step, ema_decay):
 
 
 def adamw_elem(p, g, m, v, hy, b1, b2, eps, wd, dtype=F):
-    """csrc/vt_adamw_elem.h, operation by operation -> (p', m', v')."""
+    """csrc/vt_optim.h's adamw_elem, operation by operation -> (p', m', v')."""
     c = lambda s: dtype(F(s))                                  # the kernel's scalars are fp32 values in either evaluation
     lr, bc1, bc2s = c(hy[0]), c(hy[1]), c(hy[2])
     b1, b2, eps, wd, one = c(b1), c(b2), c(eps), c(wd), dtype(1)

@@ -1,11 +1,13 @@
 """Host side of the block-wise 8-bit AdamW state (vlatouch/adam8.py, the `optimizer` argument of RdtTrainer) against the numpy statement
 (tests/adam8_ref.py): the known answers of DESIGN.md §8, the product's tables bit for bit, the code rule on every table value, the round-trip
-bound, the exported entry points, and a CPU toy that holds the statement's 8-bit step against fp32 AdamW on an ill-scaled least-squares
-problem."""
+bound, the exported entry points, the moment store's checkpoint round trip and refusals on the CPU, and a CPU toy that holds the statement's
+8-bit step against fp32 AdamW on an ill-scaled least-squares problem."""
+import os
 import re
 
 import numpy as np
 import pytest
+import torch
 
 from tests import adam8_ref as A
 from tests import cases
@@ -98,6 +100,83 @@ def test_unknown_optimizer_raises():
     assert OPTIMIZERS == ("adamw", "adamw8bit")
     with pytest.raises(ValueError, match="optimizer"):
         RdtTrainer({}, heads=2, horizon=4, action_dim=8, optimizer="adam8", device="cpu")
+
+
+STORE_SHAPES = {"small": (255,), "edge.weight": (64, 64), "big.weight": (3, 1400), "scalar": ()}      # 255 | 4096 | 4200 (17 blocks, the last partial) | 1
+
+
+def _store_tensors(st):
+    return {f"{part}.{k}": t.clone() for part in ("m", "v", "am", "av") for k, t in getattr(st, part).items()}
+
+
+def _equal_tensors(a, b):
+    return set(a) == set(b) and all(a[k].dtype == b[k].dtype and a[k].shape == b[k].shape and torch.equal(a[k].view(torch.uint8), b[k].view(torch.uint8)) for k in a)
+
+
+def test_store_zero_state_round_trips_through_a_checkpoint_on_the_cpu(tmp_path):
+    """Moments8 without a GPU: the zero state (codes 127 / 0, zero scales; fp32 zeros below MIN_8BIT_SIZE), saved before and after it is held,
+    loads into a second store with equal tensors; byte counts are the count from the shapes either way."""
+    from safetensors.torch import load_file
+    from vlatouch import adam8
+    a = adam8.Moments8(STORE_SHAPES, "cpu")
+    want_bytes = 8 * 255 + 8 * 1 + (2 * 4096 + 8 * 16) + (2 * 4200 + 8 * 17)    # fp32 m, v | two codes per element + two scales per block
+    assert not a.m and a.nbytes() == want_bytes == adam8.state_bytes([255, 4096, 4200, 1])
+    os.makedirs(tmp_path / "early" / "checkpoint")
+    a.save(str(tmp_path / "early"))                              # before the first step: the file holds the zero state
+    a.zero()
+    assert a.m and a.nbytes() == want_bytes and a.state_json == {"optimizer": "adamw8bit", "block": 256}
+    assert set(a.am) == set(a.av) == {"edge.weight", "big.weight"} and set(a.m) == set(a.v) == set(STORE_SHAPES)
+    assert a.m["small"].dtype == torch.float32 and not a.m["small"].any() and a.m["scalar"].shape == (1,)
+    assert bool((a.m["big.weight"] == 127).all()) and bool((a.v["big.weight"] == 0).all()) and a.m["big.weight"].dtype == a.v["big.weight"].dtype == torch.uint8
+    assert a.am["big.weight"].shape == (17,) and not a.am["big.weight"].any() and not a.av["edge.weight"].any()
+    os.makedirs(tmp_path / "held" / "checkpoint")
+    a.save(str(tmp_path / "held"))
+    early, held = (load_file(str(tmp_path / d / "checkpoint" / "adam8.safetensors")) for d in ("early", "held"))
+    assert _equal_tensors(early, held)
+    assert np.array_equal(held["table_signed"].numpy().view(np.int32), A.TS.view(np.int32))
+    assert np.array_equal(held["table_unsigned"].numpy().view(np.int32), A.TU.view(np.int32))
+    a.am["big.weight"][3], a.m["big.weight"][700], a.v["small"][9] = 0.25, 200, 1.5          # a state that is not the zero one
+    a.save(str(tmp_path / "held"))
+    b = adam8.Moments8(STORE_SHAPES, "cpu")
+    b.load(str(tmp_path / "held"), a.state_json)
+    assert _equal_tensors(_store_tensors(a), _store_tensors(b))
+    m, v = b.moments("small")
+    assert torch.equal(v, a.v["small"]) and v.data_ptr() != b.v["small"].data_ptr()
+
+
+@pytest.mark.parametrize("what", ["missing key", "element count", "dtype", "code table bit", "block"])
+def test_store_refuses_a_mismatched_checkpoint_and_stays_as_it_was(what, tmp_path):
+    from safetensors.torch import load_file, save_file
+    from vlatouch import adam8
+    a = adam8.Moments8(STORE_SHAPES, "cpu")
+    a.zero()
+    os.makedirs(tmp_path / "checkpoint")
+    a.save(str(tmp_path))
+    f = str(tmp_path / "checkpoint" / "adam8.safetensors")
+    st, js = load_file(f), a.state_json
+    if what == "missing key":
+        del st["av.big.weight"]
+    elif what == "element count":
+        st["am.big.weight"] = torch.zeros(16)
+    elif what == "dtype":
+        st["m8.edge.weight"] = st["m8.edge.weight"].to(torch.int8)
+    elif what == "code table bit":
+        st["table_unsigned"] = (st["table_unsigned"].view(torch.int32) ^ torch.tensor([0] * 200 + [1] + [0] * 55, dtype=torch.int32)).view(torch.float32)
+    else:
+        js = dict(js, block=128)
+    save_file(st, f)
+    b = adam8.Moments8(STORE_SHAPES, "cpu")
+    b.zero()
+    b.m["big.weight"][5], b.av["edge.weight"][2], b.m["small"][1] = 3, 0.5, -2.0               # recognisably its own state
+    before, held = _store_tensors(b), {part: dict(getattr(b, part)) for part in ("m", "v", "am", "av")}
+    with pytest.raises(ValueError):
+        b.load(str(tmp_path), js)
+    assert _equal_tensors(before, _store_tensors(b))
+    assert all(getattr(b, part)[k] is t for part, d in held.items() for k, t in d.items()), "the store holds other tensors than before"
+    fresh = adam8.Moments8(STORE_SHAPES, "cpu")
+    with pytest.raises(ValueError):
+        fresh.load(str(tmp_path), js)
+    assert not (fresh.m or fresh.v or fresh.am or fresh.av)
 
 
 def _toy(seed):

@@ -3,7 +3,8 @@ vt_ema_multi of csrc/vt_train_rdt.hip) against fp64 torch on the CPU (tests/rdt_
 (tests/golden/g17_rdt_accum.npz).
 
 Kernel level: both kernels twice on NaN-filled outputs, bit-equal; vt_grad_accum_multi within k 2^-23 of sum|g_i| / k per element (k roundings
-of fp32), vt_ema_multi bit-equal to vt_ema_update_dev per tensor; guard words in front of and behind every tensor untouched.  Trainer level: the
+of fp32), vt_ema_multi bit-equal to vt_ema_update_dev per tensor; vt_grad_clip_multi's norm and clipped gradients within 2^-18 of fp64; guard
+words in front of and behind every tensor untouched.  Trainer level: the
 accumulated gradient within 1e-4 of each tensor's norm against (1/k) sum of fp64 autograd gradients and against the fp64 gradient of the
 concatenated batch; losses and norms 1e-5 against g17; three accumulated optimizer steps within 5 x what fp32 torch loses against fp64 torch; the
 bf16 rule of test_gradients_bf16; k = 1 bit-equal to the step without the keyword; resume bit-equal; the loop helper's files."""
@@ -175,6 +176,60 @@ def test_ema_multi_is_bit_equal_to_the_per_tensor_kernel(pre):
         for d in decays:
             want = want - (1 - d) * (want - p_host[i].double())
         assert float((a[i].double() - want).abs().max()) <= 1e-6 * float(want.abs().max())
+
+
+@pytest.mark.parametrize("pre", [4, 5], ids=["aligned", "unaligned"])
+@pytest.mark.parametrize("clipped", [True, False], ids=["clipped", "unclipped"])
+def test_grad_clip_multi_against_fp64(clipped, pre):
+    """vt_grad_clip_multi over the table, with the fp64 norm of the gradients above max_norm and, the same gradients scaled down, below it.
+    norm_coef[0] within 2^-18 of the fp64 norm; clipped, every element within 2^-18 |g| of g min(1, max_norm / (norm64 + 1e-6)); unclipped,
+    the gradients bit-unchanged.  The bar: any chain of additions of the non-negative squares is under 64 roundings (16 per thread, 8 levels in
+    the block, at most 1 + 8 in the coefficient kernel), so the sum of squares is within 64 x 2^-24 = 2^-18 and its root within 2^-19; the
+    coefficient and the product add four roundings, under 2^-22.  Twice, bit-equal; p, m, v, shadow and every guard word unchanged."""
+    L, lib = _L(), _L().lib()
+    gen = torch.Generator().manual_seed(40 + pre)
+    max_norm = 1.0
+    g_host = [torch.randn(n, generator=gen) * (torch.rand(n, generator=gen) > 0.1) * 10 ** float(torch.randint(-3, 3, (1,), generator=gen)) for n in SIZES]
+    norm_of = lambda gs: float(torch.sqrt(sum((x.double() ** 2).sum() for x in gs)))
+    s = (1.7 if clipped else 0.5) * max_norm / norm_of(g_host)     # a coefficient near 0.6: the bar is relative to |g|, so a small one would hide an error
+    g_host = [(x.double() * s).float() for x in g_host]
+    norm64 = norm_of(g_host)
+    assert (norm64 > max_norm) == clipped
+    coef64 = min(1.0, max_norm / (norm64 + 1e-6))
+    others_host = [torch.randn(n, generator=gen) for n in SIZES]
+
+    def run():
+        g = [_Guarded(x, pre) for x in g_host]
+        p, m, v, sh = ([_Guarded(x, pre) for x in others_host] for _ in range(4))
+        tab, chunks = _table(p, g, m, v, sh, SIZES)
+        part, out2 = _Guarded(torch.full((chunks,), NAN), 4), _Guarded(torch.full((2,), NAN), 4)
+        L.check(lib.vt_grad_clip_multi(L.ptr(tab), len(SIZES), chunks, max_norm, part.ptr, out2.ptr, _sp()), "vt_grad_clip_multi")
+        torch.cuda.synchronize()
+        for what, xs in (("g", g), ("p", p), ("m", m), ("v", v), ("shadow", sh), ("chunk_part", [part]), ("norm_coef", [out2])):
+            for x in xs:
+                assert x.guards_intact(), ("guard words", what, x.n)
+        for xs in (p, m, v, sh):
+            for x, want in zip(xs, others_host):
+                assert torch.equal(x.values(), want), ("p / m / v / shadow changed", x.n)
+        return out2.values(), [x.values() for x in g]
+
+    (nc, got), (nc2, again) = run(), run()
+    assert nc.view(torch.int32).equal(nc2.view(torch.int32)), "two runs differ in norm_coef"
+    err_norm = abs(float(nc[0]) - norm64) / norm64
+    worst = 0.0
+    for i, n in enumerate(SIZES):
+        assert got[i].view(torch.int32).equal(again[i].view(torch.int32)), ("two runs differ", n)
+        if not clipped:
+            assert got[i].view(torch.int32).equal(g_host[i].view(torch.int32)), ("unclipped gradients changed", n)
+            continue
+        mag = g_host[i].double().abs()
+        err = (got[i].double() - g_host[i].double() * coef64).abs()
+        nz = mag > 0
+        if bool(nz.any()):
+            worst = max(worst, float((err[nz] / mag[nz]).max()))
+        assert bool((err <= 2.0 ** -18 * mag).all()), (n, float((err - 2.0 ** -18 * mag).max()))
+    print(f"[vt_grad_clip_multi clipped={clipped} pre={pre}] norm error {err_norm / 2.0 ** -18:.4f} x 2^-18, worst element {worst / 2.0 ** -18:.4f} x 2^-18 of |g|")
+    assert err_norm <= 2.0 ** -18, (float(nc[0]), norm64)
 
 
 # ------------------------------------------------------------------------------------------------ the trainer

@@ -118,6 +118,24 @@ def test_two_fp64_references_agree():
     assert worst <= A.REFS_AGREE
 
 
+def test_table_builder_matches_the_hand_written_prefix_sum():
+    """train.mt_table against the layout written out here: rows {p, g, m, v, shadow, n, first_chunk}, first_chunk the running sum of
+    ceil(n / 4096), the total that sum over all rows; a tensor without a shadow carries 0."""
+    from vlatouch.train import MT_CHUNK, mt_table
+    assert MT_CHUNK == 4096
+    sizes = [1, 2, 3, 5, 255, 1023, 4095, 4096, 4097, 4099, 3 * 4096, 70001]
+    given = [(1000 + 16 * i, 2000 + 16 * i, 3000 + 16 * i, 4000 + 16 * i, 0 if i % 5 == 1 else 5000 + 16 * i, n) for i, n in enumerate(sizes)]
+    want, chunk0 = [], 0
+    for p, g, m, v, sh, n in given:
+        want.append([p, g, m, v, sh, n, chunk0])
+        chunk0 += (n + 4095) // 4096
+    rows, total = mt_table(iter(given))
+    assert rows.dtype == torch.int64 and rows.device.type == "cpu" and rows.shape == (len(sizes), 7) and rows.is_contiguous()
+    assert rows.tolist() == want and total == chunk0 == 8 * 1 + 2 * 2 + 3 + 18
+    one, total1 = mt_table([(8, 16, 24, 32, 40, 4096)])
+    assert one.tolist() == [[8, 16, 24, 32, 40, 4096, 0]] and total1 == 1
+
+
 def test_trainer_rejects_accumulation_steps_below_one():
     """Before the device is required, like the other constructor checks."""
     from vlatouch.rdt_train import RdtTrainer

@@ -168,7 +168,7 @@ def optimizer_run(a, c, sd, params, dev):
     """The optimizer phase of an "adamw8bit" and an "adamw" trainer, alternating in this process at batch a.batch[0] -> dict."""
     from vlatouch import _lib as L
     from vlatouch import adam8
-    from vlatouch.rdt_train import RdtTrainer, _sp
+    from vlatouch.rdt_train import RdtTrainer
     B = a.batch[0]
     steps = max(5, a.steps)
     sync = lambda: torch.cuda.synchronize(dev)
@@ -204,9 +204,8 @@ def optimizer_run(a, c, sd, params, dev):
             losses[kind].append(float(loss))
     # the AdamW + EMA launch alone, on the state the steps left (it moves the same bytes whatever the values)
     launch = {k: [] for k in kinds}
-    lib = L.lib()
     hy = torch.zeros(4)
-    L.check(lib.vt_train_hyper(a.lr, 0.9, 0.999, steps + a.warmup + 1, 0.9999, L.ptr(hy)), "vt_train_hyper")
+    L.check(L.lib().vt_train_hyper(a.lr, 0.9, 0.999, steps + a.warmup + 1, 0.9999, L.ptr(hy)), "vt_train_hyper")
     hy = hy.to(dev)
     for n in range(2 + steps):
         for kind in (kinds if n % 2 == 0 else kinds[::-1]):
@@ -215,11 +214,7 @@ def optimizer_run(a, c, sd, params, dev):
             e0, e1 = ev(), ev()
             sync()
             e0.record()
-            if kind == "adamw8bit":
-                L.check(lib.vt_adamw8_ema_multi(L.ptr(tab), L.ptr(tr._aux_dev), L.ptr(tr._tables8), nt, chunks, L.ptr(hy), 0.9, 0.999, tr.eps, tr.wd, _sp(dev)),
-                        "vt_adamw8_ema_multi")
-            else:
-                L.check(lib.vt_adamw_ema_multi(L.ptr(tab), nt, chunks, L.ptr(hy), 0.9, 0.999, tr.eps, tr.wd, _sp(dev)), "vt_adamw_ema_multi")
+            tr.opt_state.step(tab, nt, chunks, hy, (0.9, 0.999), tr.eps, tr.wd)
             e1.record()
             sync()
             if n >= 2:

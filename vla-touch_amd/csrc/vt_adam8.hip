@@ -4,19 +4,19 @@
 // arithmetic is the statement of DESIGN.md §8 (tests/adam8_ref.py is its numpy form); it is UNPINNED against bitsandbytes.
 //   tables (device, 1024 fp32, vlatouch/adam8.py): T_s[256] | T_u[256] | B_s[256] | B_u[256], B[j] = fp32(((double)T[j] + T[j+1]) / 2), B[255] = +inf
 //   code(x) = the number of B[j] strictly below x = the index of the nearest table value, ties to the lower index
-// The element update is adamw_elem / ema_elem of vt_adamw_elem.h, so a tensor kept in fp32 (aux pair null) gets the bits of
+// The element update is adamw_elem / ema_elem of vt_optim.h, so a tensor kept in fp32 (aux pair null) gets the bits of
 // vt_adamw_ema_multi, and so does every tensor on the first step, where the dequantised state is exactly zero.
 // HBM-bound by design: 24 B per parameter (p 8, g 4, codes 2 + 2, shadow 8) against vt_adamw_ema_multi's 36 B; no MFMA.
 #include <math.h>
 #include "vt_common.h"
 #include "vt_host.h"
-#include "vt_adamw_elem.h"
+#include "vt_optim.h"
 #include "../../include/vlatouch.h"
 
 namespace {
 
-// the table of vt_adamw_ema_multi; m / v are `unsigned char*` codes where aux[k] is not null, `float*` where it is
-struct MtEntry { float* p; const float* g; void* m; void* v; float* shadow; long n; long first_chunk; };
+// the table of vt_adamw_ema_multi (vt_optim.h); a row's m / v point at `unsigned char` codes where aux[k] is not null, at fp32 moments where it is
+static_assert(4 * 4 * 256 == MT_CHUNK, "4 passes of 4 waves, one 256-element quantisation block each, walk one chunk");
 struct AuxEntry { float* am; float* av; };
 
 // The code search.  The tables are decade-structured: decade d = 0 .. 6 holds the midpoints of n_d equal sub-intervals of [0.1, 1] x 10^(d-6),
@@ -102,7 +102,7 @@ __device__ __forceinline__ float div_by(float x, float d, float r) {
   return fmaf(fmaf(-q, d, x), r, q);
 }
 
-// A 256-thread block takes one 4096-element chunk of one tensor (found by binary search over first_chunk, as vt_adamw_ema_multi does): 16
+// A 256-thread block takes one MT_CHUNK-element chunk of one tensor (mt_find, as vt_adamw_ema_multi does): 16
 // quantisation blocks of 256 elements, none of which straddles a chunk.  A wave takes one block per iteration, 4 consecutive elements per
 // lane: one 32-bit word of each code array and 128-bit words of p / g / shadow where every base is aligned for them (a block starts 1 KiB
 // into p, 256 B into the codes, so the tensor's alignment is the block's); an unaligned tensor and the last partial block go element by
@@ -112,15 +112,14 @@ __global__ __launch_bounds__(256) void adamw8_ema_mt_kernel(const MtEntry* __res
                                                             int ntensors, const float* __restrict__ hyper, float b1, float b2, float eps, float wd) {
   __shared__ __attribute__((aligned(16))) float tb[1024];
   __shared__ Luts lut;
-  int lo = 0, hi = ntensors - 1;
   const long chunk = blockIdx.x;
-  while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (tab[mid].first_chunk <= chunk) lo = mid; else hi = mid - 1; }
-  const MtEntry e = tab[lo];
-  const AuxEntry ax = aux[lo];
-  const long base = (chunk - e.first_chunk) * 4096;
+  const int row = mt_find(tab, ntensors, chunk);
+  const MtEntry e = tab[row];
+  const AuxEntry ax = aux[row];
+  const long base = (chunk - e.first_chunk) * MT_CHUNK;
   const float lr = hyper[0], bc1 = hyper[1], bc2_sqrt = hyper[2], omd = hyper[3];
   if (!ax.am) {                                               // fp32 moments: the chunk body of vt_train.hip's adamw_ema_mt_kernel
-    adamw_ema_chunk_f32(e.p, e.g, (float*)e.m, (float*)e.v, e.shadow, base, e.n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, omd);
+    adamw_ema_chunk_f32(e.p, e.g, e.m, e.v, e.shadow, base, e.n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, omd);
     return;
   }
   reinterpret_cast<float4*>(tb)[threadIdx.x] = reinterpret_cast<const float4*>(tables)[threadIdx.x];

@@ -8,7 +8,7 @@
 #include <math.h>
 #include "vt_common.h"
 #include "vt_host.h"
-#include "vt_adamw_elem.h"
+#include "vt_optim.h"
 #include "../../include/vlatouch.h"
 
 namespace {
@@ -278,7 +278,7 @@ __global__ __launch_bounds__(256) void si_loss_kernel(const float* __restrict__ 
   if (threadIdx.x == 0) loss[0] = ((red[0] + red[1]) + (red[2] + red[3])) * invB;
 }
 
-// adamw_elem / ema_elem, one element of torch.optim.AdamW / torch_ema with contraction off: vt_adamw_elem.h (shared with vt_adam8.hip)
+// adamw_elem / ema_elem, one element of torch.optim.AdamW / torch_ema with contraction off: vt_optim.h (shared with vt_train_rdt.hip, vt_adam8.hip)
 // torch.optim.AdamW (decoupled weight decay, bias-corrected moments), one fused pass
 __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long n, float lr, float b1, float b2,
                              float eps, float wd, float bc1, float bc2_sqrt) {
@@ -304,16 +304,13 @@ __global__ void ema_dev_kernel(float* __restrict__ shadow, const float* __restri
   if (i < n) shadow[i] = ema_elem(shadow[i], p[i], hyper[3]);
 }
 // AdamW (+ EMA where the tensor has a shadow) over a TABLE of tensors in one launch: a training step updates ~380 tensors, most of them
-// a few KB, and one launch each is launch-gap-bound.  tab[k] = {p, g, m, v, shadow | null, n, first_chunk}; a block takes one 4096-
-// element chunk and finds its tensor by binary search over first_chunk.  Arithmetic identical to adamw_dev_kernel / ema_dev_kernel.
-struct MtEntry { float* p; const float* g; float* m; float* v; float* shadow; long n; long first_chunk; };
+// a few KB, and one launch each is launch-gap-bound.  Record, chunk and lookup: vt_optim.h.  Arithmetic identical to adamw_dev_kernel /
+// ema_dev_kernel.
 __global__ __launch_bounds__(256) void adamw_ema_mt_kernel(const MtEntry* __restrict__ tab, int ntensors, const float* __restrict__ hyper,
                                                            float b1, float b2, float eps, float wd) {
-  int lo = 0, hi = ntensors - 1;
   const long chunk = blockIdx.x;
-  while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (tab[mid].first_chunk <= chunk) lo = mid; else hi = mid - 1; }
-  const MtEntry e = tab[lo];
-  const long base = (chunk - e.first_chunk) * 4096;
+  const MtEntry e = tab[mt_find(tab, ntensors, chunk)];
+  const long base = (chunk - e.first_chunk) * MT_CHUNK;
   const float lr = hyper[0], bc1 = hyper[1], bc2_sqrt = hyper[2], omd = hyper[3];
   adamw_ema_chunk_f32(e.p, e.g, e.m, e.v, e.shadow, base, e.n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, omd);
 }

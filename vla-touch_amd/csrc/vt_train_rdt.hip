@@ -15,6 +15,7 @@
 #include <math.h>
 #include "vt_common.h"
 #include "vt_host.h"
+#include "vt_optim.h"
 #include "../../include/vlatouch.h"
 
 namespace {
@@ -282,17 +283,12 @@ __global__ void copy_cols_t_kernel(const T* __restrict__ src, long lds_, long of
 }
 
 // ------------------------------------------------------------------------------------------------ global-norm clipping
-// The table is vt_adamw_ema_multi's: tab[k] = {p, g, m, v, shadow, n, first_chunk}; a block takes one 4096-element chunk of one gradient.
-struct MtEntry { float* p; float* g; float* m; float* v; float* shadow; long n; long first_chunk; };
-__device__ __forceinline__ MtEntry mt_find(const MtEntry* tab, int ntensors, long chunk) {
-  int lo = 0, hi = ntensors - 1;
-  while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (tab[mid].first_chunk <= chunk) lo = mid; else hi = mid - 1; }
-  return tab[lo];
-}
+// The table is vt_adamw_ema_multi's (vt_optim.h: MtEntry, MT_CHUNK, mt_find); a block takes one chunk of one gradient.
+static_assert(16 * 256 == MT_CHUNK && 4 * 256 * 4 == MT_CHUNK, "the 16 scalar passes and the 4 float4 passes of 256 threads below walk one chunk");
 __global__ __launch_bounds__(256) void sumsq_mt_kernel(const MtEntry* __restrict__ tab, int ntensors, float* __restrict__ part) {
   __shared__ float red[4];
-  const MtEntry e = mt_find(tab, ntensors, blockIdx.x);
-  const long base = ((long)blockIdx.x - e.first_chunk) * 4096;
+  const MtEntry e = tab[mt_find(tab, ntensors, blockIdx.x)];
+  const long base = ((long)blockIdx.x - e.first_chunk) * MT_CHUNK;
   float s = 0.f;
   for (int it = 0; it < 16; ++it) {
     const long i = base + it * 256 + threadIdx.x;
@@ -314,8 +310,8 @@ __global__ __launch_bounds__(256) void clip_coef_kernel(const float* __restrict_
   }
 }
 __global__ __launch_bounds__(256) void scale_mt_kernel(const MtEntry* __restrict__ tab, int ntensors, const float* __restrict__ norm_coef) {
-  const MtEntry e = mt_find(tab, ntensors, blockIdx.x);
-  const long base = ((long)blockIdx.x - e.first_chunk) * 4096;
+  const MtEntry e = tab[mt_find(tab, ntensors, blockIdx.x)];
+  const long base = ((long)blockIdx.x - e.first_chunk) * MT_CHUNK;
   const float c = norm_coef[1];
   if (c >= 1.0f) return;                                       // torch multiplies by a coefficient clamped to 1: the same values
   for (int it = 0; it < 16; ++it) {
@@ -333,15 +329,14 @@ __global__ __launch_bounds__(256) void scale_mt_kernel(const MtEntry* __restrict
 // left of n behind the last whole quad, or the whole chunk of an unaligned tensor, goes element by element.
 __global__ __launch_bounds__(256) void grad_accum_mt_kernel(const MtEntry* __restrict__ tab, const float* const* __restrict__ fresh, int ntensors,
                                                             float scale, int accumulate) {
-  int lo = 0, hi = ntensors - 1;
   const long chunk = blockIdx.x;
-  while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (tab[mid].first_chunk <= chunk) lo = mid; else hi = mid - 1; }
-  const MtEntry e = tab[lo];
-  const long base = (chunk - e.first_chunk) * 4096;
+  const int row = mt_find(tab, ntensors, chunk);
+  const MtEntry e = tab[row];
+  const long base = (chunk - e.first_chunk) * MT_CHUNK;
   const long left = e.n - base;
-  const int cnt = left < 4096 ? (int)left : 4096;
+  const int cnt = left < MT_CHUNK ? (int)left : MT_CHUNK;
   float* __restrict__ acc = e.g + base;
-  const float* __restrict__ g = fresh[lo] + base;
+  const float* __restrict__ g = fresh[row] + base;
   const bool aligned = ((((size_t)acc) | ((size_t)g)) & 15) == 0;
   const int quads = aligned ? cnt >> 2 : 0;
 #pragma unroll
@@ -360,18 +355,14 @@ __global__ __launch_bounds__(256) void grad_accum_mt_kernel(const MtEntry* __res
   }
   for (int i = quads * 4 + threadIdx.x; i < cnt; i += 256) acc[i] = accumulate ? fmaf(g[i], scale, acc[i]) : g[i] * scale;
 }
-// EMAModel.step alone over the table (the micro-batches that take no optimizer step): shadow -= (1 - decay) (shadow - p), the arithmetic of
-// vt_train.hip's ema_elem with contraction off, so it gives the bits of vt_ema_update_dev per tensor.  hyper[3] = 1 - decay.
-__device__ __forceinline__ float ema_elem_rdt(float sh, float p, float one_minus_decay) {
-#pragma clang fp contract(off)
-  return sh - one_minus_decay * (sh - p);
-}
+// EMAModel.step alone over the table (the micro-batches that take no optimizer step): shadow -= (1 - decay) (shadow - p) by vt_optim.h's
+// ema_elem, so it gives the bits of vt_ema_update_dev per tensor.  hyper[3] = 1 - decay.
 __global__ __launch_bounds__(256) void ema_mt_kernel(const MtEntry* __restrict__ tab, int ntensors, const float* __restrict__ hyper) {
-  const MtEntry e = mt_find(tab, ntensors, blockIdx.x);
+  const MtEntry e = tab[mt_find(tab, ntensors, blockIdx.x)];
   if (!e.shadow) return;
-  const long base = ((long)blockIdx.x - e.first_chunk) * 4096;
+  const long base = ((long)blockIdx.x - e.first_chunk) * MT_CHUNK;
   const long left = e.n - base;
-  const int cnt = left < 4096 ? (int)left : 4096;
+  const int cnt = left < MT_CHUNK ? (int)left : MT_CHUNK;
   const float omd = hyper[3];
   float* __restrict__ sh = e.shadow + base;
   const float* __restrict__ p = e.p + base;
@@ -383,10 +374,10 @@ __global__ __launch_bounds__(256) void ema_mt_kernel(const MtEntry* __restrict__
     if (j >= quads) break;
     const float4 pv = reinterpret_cast<const float4*>(p)[j];
     float4 s = reinterpret_cast<const float4*>(sh)[j];
-    s.x = ema_elem_rdt(s.x, pv.x, omd); s.y = ema_elem_rdt(s.y, pv.y, omd); s.z = ema_elem_rdt(s.z, pv.z, omd); s.w = ema_elem_rdt(s.w, pv.w, omd);
+    s.x = ema_elem(s.x, pv.x, omd); s.y = ema_elem(s.y, pv.y, omd); s.z = ema_elem(s.z, pv.z, omd); s.w = ema_elem(s.w, pv.w, omd);
     reinterpret_cast<float4*>(sh)[j] = s;
   }
-  for (int i = quads * 4 + threadIdx.x; i < cnt; i += 256) sh[i] = ema_elem_rdt(sh[i], p[i], omd);
+  for (int i = quads * 4 + threadIdx.x; i < cnt; i += 256) sh[i] = ema_elem(sh[i], p[i], omd);
 }
 
 // mean squared error of pred against target (fp32) and its gradient: loss = mean((pred - target)^2), dpred = 2 (pred - target) / n; one block

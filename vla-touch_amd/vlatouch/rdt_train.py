@@ -31,7 +31,7 @@ from . import _lib as L
 from . import adam8
 from . import ops
 from . import train as T
-from .train import _Optimizer, _empty, _sp
+from .train import _empty, _sp
 
 F32 = torch.float32
 LR_SCHEDULERS = ("constant", "constant_with_warmup")
@@ -204,7 +204,65 @@ def _cols(src2d: torch.Tensor, off: int, cols: int) -> torch.Tensor:
 
 
 # ---------------------------------------------------------------------------------------------- the trainer
-class RdtTrainer(_Optimizer):
+def _load_matching(path: str, rel, shapes, what: str) -> Dict[str, torch.Tensor]:
+    """The file `rel` of the checkpoint under `path` if it holds fp32 tensors of exactly these names and shapes; ValueError otherwise."""
+    from safetensors.torch import load_file
+    d = load_file(os.path.join(path, *rel))
+    if set(d) != set(shapes) or any(d[k].shape != s or d[k].dtype != F32 for k, s in shapes.items()):
+        raise ValueError(f"checkpoint {path}: the {what} tensors do not match this trainer's parameters")
+    return d
+
+
+class Moments32:
+    """The AdamW moments of a trainer's tensors as fp32 tensors of the parameters' shapes; adam8.Moments8 is the block-wise 8-bit form with
+    the same interface.  Nothing here but `step` launches.
+
+    shapes: parameter name -> shape, in the order of the multi-tensor table's rows.  The state appears with `zero()` or `load()`; it is
+    checkpoint/adam_m.safetensors and checkpoint/adam_v.safetensors under the parameters' names, and adds nothing (`state_json`) to
+    trainer_state.json: a file without `optimizer` is an "adamw" one."""
+    state_json: dict = {}
+
+    def __init__(self, shapes, device):
+        self.shapes, self.device = dict(shapes), torch.device(device)
+        self.m: Dict[str, torch.Tensor] = {}
+        self.v: Dict[str, torch.Tensor] = {}
+
+    def _zeros(self):
+        return {k: torch.zeros(tuple(s), dtype=F32, device=self.device) for k, s in self.shapes.items()}
+
+    def zero(self) -> None:
+        self.m, self.v = self._zeros(), self._zeros()
+
+    def columns(self, k):
+        """The m / v addresses of tensor k's row of the multi-tensor table."""
+        return self.m[k].data_ptr(), self.v[k].data_ptr()
+
+    def step(self, table, ntensors, chunks, hyper, betas, eps, wd) -> None:
+        """AdamW + EMA over a table whose m / v columns are `columns()` of every tensor: one launch."""
+        L.check(L.lib().vt_adamw_ema_multi(L.ptr(table), ntensors, chunks, L.ptr(hyper), betas[0], betas[1], eps, wd, _sp(self.device)), "vt_adamw_ema_multi")
+
+    def moments(self, k):
+        """(m, v) of tensor k: copies, not views of the state."""
+        return self.m[k].clone(), self.v[k].clone()
+
+    def nbytes(self) -> int:
+        """Bytes of the state, held or, before it appears, counted from the shapes."""
+        return 8 * sum(math.prod(s) for s in self.shapes.values())
+
+    def save(self, path: str) -> None:
+        from safetensors.torch import save_file
+        for tag, d in (("m", self.m), ("v", self.v)):
+            save_file({k: t.detach().cpu().contiguous() for k, t in (d if d else self._zeros()).items()},
+                      os.path.join(path, "checkpoint", f"adam_{tag}.safetensors"))
+
+    def load(self, path: str, state: dict) -> None:
+        """Adopt what `save` wrote under `path`; raises ValueError, leaving this store as it was, unless both files hold fp32 tensors of exactly
+        the parameters' names and shapes."""
+        m, v = [_load_matching(path, ("checkpoint", f"adam_{tag}.safetensors"), self.shapes, tag) for tag in ("m", "v")]
+        self.m, self.v = ({k: d[k].to(self.device).contiguous() for k in self.shapes} for d in (m, v))
+
+
+class RdtTrainer:
     """get_loss + backward + clip + AdamW + EMA for `RDTRunner` (all of its parameters train, the three position embeddings included).
 
     sd: the runner's state dict (reference keys).  Hyper-parameters default to main.py:125-210 (lr 5e-6, betas 0.9 / 0.999, eps 1e-8, weight decay
@@ -212,8 +270,9 @@ class RdtTrainer(_Optimizer):
 
     optimizer="adamw8bit" (the reference's --use_8bit_adam, train.py:216-237) keeps the AdamW moments of every tensor of at least
     adam8.MIN_8BIT_SIZE elements as uint8 codes with one fp32 scale per 256 elements (vlatouch/adam8.py, csrc/vt_adam8.hip; DESIGN.md §8 states
-    the arithmetic, UNPINNED against bitsandbytes); smaller tensors keep fp32 moments and the bits of the default step.  `_m` / `_v` then hold
-    the codes (uint8) or the fp32 moments, `_am` / `_av` the scales; `moments(name)` dequantises."""
+    the arithmetic, UNPINNED against bitsandbytes); smaller tensors keep fp32 moments and the bits of the default step.  Either way the moments
+    live in one store, `opt_state` (Moments32 or adam8.Moments8: zero state, table columns, the AdamW + EMA launch, checkpoint files, byte count);
+    `moments(name)` reads them as fp32."""
 
     def __init__(self, sd, *, heads: int, horizon: int, action_dim: int, rms_mode: str = "meansq", prediction_type: str = "sample",
                  num_train_timesteps: int = 1000, beta_schedule: str = "squaredcos_cap_v2", precision: str = "fp32", lr: float = 5e-6,
@@ -264,14 +323,10 @@ class RdtTrainer(_Optimizer):
         self.micro_step = 0                                   # micro-batches folded into the open accumulation window
         self.sync_gradients = False                           # the last train_step took the optimizer step
         self._acc: Dict[str, torch.Tensor] = {}               # k > 1: persistent fp32 accumulators, the table's g column
-        self._m: Dict[str, torch.Tensor] = {}                 # AdamW moments and the EMA copy appear with the first optimizer step (the parameters are
-        self._v: Dict[str, torch.Tensor] = {}                 # still the initial ones then), so a trainer that only evaluates the loss holds one copy
+        self.optimizer = optimizer                            # AdamW moments and the EMA copy appear with the first optimizer step (the parameters are
+        shapes = OrderedDict((k, v.shape) for k, v in self.p.items())     # still the initial ones then), so a trainer that only evaluates the loss holds one copy
+        self.opt_state = adam8.Moments8(shapes, dev) if optimizer == "adamw8bit" else Moments32(shapes, dev)
         self.shadow: Dict[str, torch.Tensor] = {}
-        self.optimizer = optimizer
-        self._am: Dict[str, torch.Tensor] = {}                # adamw8bit: the per-block scales of the quantised tensors' two moments,
-        self._av: Dict[str, torch.Tensor] = {}                # the code tables + boundaries on the device, and the table's {am, av} companion
-        self._tables8: Optional[torch.Tensor] = None
-        self._aux_dev: Optional[torch.Tensor] = None
         self._norm_coef = torch.zeros(2, dtype=F32, device=dev)
         self._table_key = None
         self.last_loss: Optional[torch.Tensor] = None
@@ -292,18 +347,15 @@ class RdtTrainer(_Optimizer):
             raise ValueError(f"no weights for {name}")
         return out
 
-    # ---- _Optimizer plumbing
-    def _all_params(self):
-        src = self._acc if self.k > 1 else self.g
-        for k, v in self.p.items():
-            yield k, v, src.get(k)
-
     def _ema_decay(self, step: int) -> float:
         """`step` = number of EMA updates including this one; EMAModel.step evaluates get_decay at the count before it."""
         return ema_decay(step - 1, **self.ema_cfg)
 
-    def _shadow_source(self, name: str) -> torch.Tensor:
-        return self.p[name]
+    # the store's dicts under the names tests and tools have always read on the trainer (codes or fp32 moments; scales, empty for "adamw")
+    _m = property(lambda self: self.opt_state.m)
+    _v = property(lambda self: self.opt_state.v)
+    _am = property(lambda self: getattr(self.opt_state, "am", {}))
+    _av = property(lambda self: getattr(self.opt_state, "av", {}))
 
     @property
     def global_step(self) -> int:
@@ -518,32 +570,40 @@ class RdtTrainer(_Optimizer):
         return self.last_loss
 
     # ---- optimizer
+    def _fresh_grad(self, name: str) -> torch.Tensor:
+        """The gradient get_loss left for one parameter, checked and made contiguous."""
+        gt, pt = self.g.get(name), self.p[name]
+        if gt is None:
+            raise RuntimeError(f"no gradient for {name}: call get_loss first")
+        if gt.dtype != F32 or gt.numel() != pt.numel():
+            raise RuntimeError(f"gradient of {name}: fp32 with {pt.numel()} elements expected")
+        if not gt.is_contiguous():
+            gt = self.g[name] = gt.contiguous()
+        return gt
+
+    def _hyper(self, adam_step: int) -> torch.Tensor:
+        """[lr, 1 - b1^t, sqrt(1 - b2^t), 1 - ema_decay] of the kernels that read the step's scalars from memory, uploaded."""
+        host = torch.zeros(4, dtype=F32)
+        L.check(L.lib().vt_train_hyper(self.lr, self.betas[0], self.betas[1], adam_step, self._ema_decay(self.ema_updates), L.ptr(host)), "vt_train_hyper")
+        return host.to(self.device)
+
     def _table(self):
-        """The multi-tensor table vt_grad_clip_multi / vt_adamw_ema_multi read: {p, g, m, v, shadow, n, first_chunk} per tensor, on the device."""
-        rows, chunk0 = [], 0
+        """The multi-tensor table every optimizer launch reads (train.mt_table: {p, g, m, v, shadow, n, first_chunk} per tensor), on the device."""
         if self.k > 1 and not self._acc:
             self._acc = {k: torch.empty_like(v) for k, v in self.p.items()}          # never read before the window's first, storing, accumulate
         if not self.shadow:
-            if self.optimizer == "adamw8bit":
-                self._set_state8(self._zero_state8())
-            else:
-                self._m = {k: torch.zeros_like(v) for k, v in self.p.items()}
-                self._v = {k: torch.zeros_like(v) for k, v in self.p.items()}
+            self.opt_state.zero()
             self.shadow = {k: v.clone() for k, v in self.p.items()}
-        for name, pt, gt in self._all_params():
-            if gt is None:
-                raise RuntimeError(f"no gradient for {name}: call get_loss first")
-            if not gt.is_contiguous():
-                gt = self.g[name] = gt.contiguous()
-            rows.append([pt.data_ptr(), gt.data_ptr(), self._m[name].data_ptr(), self._v[name].data_ptr(), self.shadow[name].data_ptr(), pt.numel(), chunk0])
-            chunk0 += (pt.numel() + 4095) // 4096
-        key = tuple(r[1] for r in rows)
+        g = self._acc if self.k > 1 else {name: self._fresh_grad(name) for name in self.p}
+        key = tuple(t.data_ptr() for t in g.values())
         if key != self._table_key:                                # gradients are fresh allocations each step: their addresses usually repeat, not always
                                                                   # (k > 1: the g column holds the accumulators, so the table is built once)
-            self._mt_dev = torch.tensor(rows, dtype=torch.int64).to(self.device)
-            self._chunk_part = _empty((chunk0,), self.device)
-            self._table_key, self._chunks = key, chunk0
-        return self._mt_dev, len(rows), self._chunks
+            rows, chunks = T.mt_table((pt.data_ptr(), g[name].data_ptr(), *self.opt_state.columns(name), self.shadow[name].data_ptr(), pt.numel())
+                                      for name, pt in self.p.items())
+            self._mt_dev = rows.to(self.device)
+            self._chunk_part = _empty((chunks,), self.device)
+            self._table_key, self._chunks = key, chunks
+        return self._mt_dev, len(self.p), self._chunks
 
     def optimizer_step(self, hyper: Optional[torch.Tensor] = None):
         """clip_grad_norm_(max_grad_norm) -> AdamW -> EMA (train.py:440-448), three launches over one table; no host read."""
@@ -551,85 +611,30 @@ class RdtTrainer(_Optimizer):
             raise NotImplementedError("RdtTrainer: hipGraph capture of the step is not built")
         if self.k > 1 and self.micro_step != self.k:
             raise RuntimeError(f"optimizer_step needs a full accumulation window ({self.micro_step} of {self.k} micro-batches accumulated)")
-        lib, dev = L.lib(), self.device
         tab, n, chunks = self._table()
         self.lr = lr_at(self.base_lr, self.lr_scheduler, self.step_count, self.lr_warmup_steps * self.k)      # train.py:302 scales the warm-up by k
         self.step_count += 1
         self.ema_updates += 1
-        host = torch.zeros(4, dtype=F32)
-        L.check(lib.vt_train_hyper(self.lr, self.betas[0], self.betas[1], self.step_count, self._ema_decay(self.ema_updates), L.ptr(host)), "vt_train_hyper")
-        hy = host.to(dev)
-        L.check(lib.vt_grad_clip_multi(L.ptr(tab), n, chunks, self.max_grad_norm, L.ptr(self._chunk_part), L.ptr(self._norm_coef), _sp(dev)), "vt_grad_clip_multi")
-        if self.optimizer == "adamw8bit":
-            L.check(lib.vt_adamw8_ema_multi(L.ptr(tab), L.ptr(self._aux_dev), L.ptr(self._tables8), n, chunks, L.ptr(hy), self.betas[0], self.betas[1],
-                                            self.eps, self.wd, _sp(dev)), "vt_adamw8_ema_multi")
-        else:
-            L.check(lib.vt_adamw_ema_multi(L.ptr(tab), n, chunks, L.ptr(hy), self.betas[0], self.betas[1], self.eps, self.wd, _sp(dev)), "vt_adamw_ema_multi")
+        hy = self._hyper(self.step_count)
+        L.check(L.lib().vt_grad_clip_multi(L.ptr(tab), n, chunks, self.max_grad_norm, L.ptr(self._chunk_part), L.ptr(self._norm_coef), _sp(self.device)),
+                "vt_grad_clip_multi")
+        self.opt_state.step(tab, n, chunks, hy, self.betas, self.eps, self.wd)
         self._refresh16()
         self.micro_step, self.sync_gradients = 0, True
         self.weights_version += 1
         self.shadow_version += 1
 
-    # ---- adamw8bit state
-    def _zero_state8(self) -> Dict[str, torch.Tensor]:
-        """Exactly zero moments in the layout of checkpoint/adam8.safetensors: codes 127 / 0 with zero scales, or fp32 zeros for a small tensor."""
-        dev, out = self.device, {}
-        for k, v in self.p.items():
-            n = v.numel()
-            if n >= adam8.MIN_8BIT_SIZE:
-                out[f"m8.{k}"] = torch.full((n,), adam8.ZERO_CODE_SIGNED, dtype=torch.uint8, device=dev)
-                out[f"v8.{k}"] = torch.full((n,), adam8.ZERO_CODE_UNSIGNED, dtype=torch.uint8, device=dev)
-                out[f"am.{k}"] = torch.zeros(adam8.nblocks(n), dtype=F32, device=dev)
-                out[f"av.{k}"] = torch.zeros(adam8.nblocks(n), dtype=F32, device=dev)
-            else:
-                out[f"m.{k}"], out[f"v.{k}"] = torch.zeros(n, dtype=F32, device=dev), torch.zeros(n, dtype=F32, device=dev)
-        return out
-
-    def _state8(self) -> Dict[str, torch.Tensor]:
-        """The live 8-bit state under the keys of `_zero_state8` (device tensors, not copies)."""
-        out = {}
-        for k in self.p:
-            if k in self._am:
-                out[f"m8.{k}"], out[f"v8.{k}"], out[f"am.{k}"], out[f"av.{k}"] = self._m[k], self._v[k], self._am[k], self._av[k]
-            else:
-                out[f"m.{k}"], out[f"v.{k}"] = self._m[k], self._v[k]
-        return out
-
-    def _set_state8(self, st: Dict[str, torch.Tensor]) -> None:
-        """Adopt a state in that layout (checked against the parameters' sizes) and put the tables on the device."""
-        dev, m, v, am, av = self.device, {}, {}, {}, {}
-        for k, p in self.p.items():
-            n = p.numel()
-            spec = ((("m8", torch.uint8, n), ("v8", torch.uint8, n), ("am", F32, adam8.nblocks(n)), ("av", F32, adam8.nblocks(n)))
-                    if n >= adam8.MIN_8BIT_SIZE else (("m", F32, n), ("v", F32, n)))
-            for tag, dt, cnt in spec:
-                t = st.get(f"{tag}.{k}")
-                if t is None or t.dtype != dt or t.numel() != cnt:
-                    raise ValueError(f"adamw8bit state: {tag}.{k} missing or not {cnt} x {dt}")
-                {"m8": m, "m": m, "v8": v, "v": v, "am": am, "av": av}[tag][k] = t.to(dev).contiguous().reshape(cnt)
-        self._m, self._v, self._am, self._av = m, v, am, av
-        aux = [[am[k].data_ptr(), av[k].data_ptr()] if k in am else [0, 0] for k in self.p]      # {am, av} per row of the table, a null pair where the moments
-        self._aux_dev = torch.tensor(aux, dtype=torch.int64).to(dev)                             # are fp32; the state does not move, so it is built here, once
-        if self._tables8 is None:
-            self._tables8 = adam8.device_tables(dev)
-        self._table_key = None
-
     def moments(self, name: str):
         """AdamW's (m, v) of one parameter as fp32 device tensors of its shape (zeros before the first optimizer step); adamw8bit: dequantised."""
         p = self.p[name]
-        if name not in self._m:
+        if not self.shadow:                                       # the moments appear with the shadows
             return torch.zeros_like(p), torch.zeros_like(p)
-        if name in self._am:
-            return (adam8.dequantize(self._m[name], self._am[name], self._tables8, True).view(p.shape),
-                    adam8.dequantize(self._v[name], self._av[name], self._tables8, False).view(p.shape))
-        return self._m[name].clone().view(p.shape), self._v[name].clone().view(p.shape)
+        m, v = self.opt_state.moments(name)
+        return m.view(p.shape), v.view(p.shape)
 
     def optimizer_state_bytes(self) -> int:
         """Bytes of AdamW state (moments, and codes + scales for adamw8bit) this trainer holds once it has stepped; EMA shadows not counted."""
-        if self._m:
-            return sum(t.numel() * t.element_size() for d in (self._m, self._v, self._am, self._av) for t in d.values())
-        numels = [v.numel() for v in self.p.values()]
-        return adam8.state_bytes(numels) if self.optimizer == "adamw8bit" else 8 * sum(numels)
+        return self.opt_state.nbytes()
 
     def accumulate(self) -> None:
         """k > 1: fold the gradients get_loss left in `self.g` into the accumulators, scaled by 1 / k (accelerator.backward's loss / k); the
@@ -639,17 +644,7 @@ class RdtTrainer(_Optimizer):
         if self.micro_step >= self.k:
             raise RuntimeError("accumulate: the window is full, call optimizer_step")
         tab, n, chunks = self._table()
-        ptrs = []
-        for name, pt in self.p.items():
-            gt = self.g.get(name)
-            if gt is None:
-                raise RuntimeError(f"no gradient for {name}: call get_loss first")
-            if gt.dtype != F32 or gt.numel() != pt.numel():
-                raise RuntimeError(f"gradient of {name}: fp32 with {pt.numel()} elements expected")
-            if not gt.is_contiguous():
-                gt = self.g[name] = gt.contiguous()
-            ptrs.append(gt.data_ptr())
-        fresh = torch.tensor(ptrs, dtype=torch.int64).to(self.device)
+        fresh = torch.tensor([self._fresh_grad(name).data_ptr() for name in self.p], dtype=torch.int64).to(self.device)
         L.check(L.lib().vt_grad_accum_multi(L.ptr(tab), L.ptr(fresh), n, chunks, 1.0 / self.k, int(self.micro_step > 0), _sp(self.device)),
                 "vt_grad_accum_multi")
         self.micro_step += 1
@@ -658,10 +653,7 @@ class RdtTrainer(_Optimizer):
         """EMAModel.step alone (train.py:448 on a micro-batch without an optimizer step): the shadows move toward the unchanged parameters."""
         tab, n, chunks = self._table()
         self.ema_updates += 1
-        host = torch.zeros(4, dtype=F32)
-        L.check(L.lib().vt_train_hyper(self.lr, self.betas[0], self.betas[1], max(1, self.step_count), self._ema_decay(self.ema_updates), L.ptr(host)),
-                "vt_train_hyper")
-        L.check(L.lib().vt_ema_multi(L.ptr(tab), n, chunks, L.ptr(host.to(self.device)), _sp(self.device)), "vt_ema_multi")
+        L.check(L.lib().vt_ema_multi(L.ptr(tab), n, chunks, L.ptr(self._hyper(max(1, self.step_count))), _sp(self.device)), "vt_ema_multi")
         self.sync_gradients = False
         self.shadow_version += 1
 
@@ -750,26 +742,16 @@ class RdtTrainer(_Optimizer):
             raise RuntimeError(f"save_checkpoint in the middle of an accumulation window ({self.micro_step} of {self.k} micro-batches): "
                                "the partial gradient sum is not part of a checkpoint")
         from safetensors.torch import save_file
-        cpu = lambda d: {k: (d[k] if k in d else torch.zeros_like(v)).detach().cpu().contiguous() for k, v in self.p.items()}
         os.makedirs(os.path.join(path, "checkpoint"), exist_ok=True)
         os.makedirs(os.path.join(path, "ema"), exist_ok=True)
-        save_file(cpu(self.p), os.path.join(path, "checkpoint", "model.safetensors"))
-        if self.optimizer == "adamw8bit":
-            ts, tu = adam8.code_tables()
-            st = {k: v.detach().cpu().contiguous() for k, v in (self._state8() if self._m else self._zero_state8()).items()}
-            st["table_signed"], st["table_unsigned"] = torch.from_numpy(ts), torch.from_numpy(tu)
-            save_file(st, os.path.join(path, "checkpoint", "adam8.safetensors"))
-        else:
-            save_file(cpu(self._m), os.path.join(path, "checkpoint", "adam_m.safetensors"))
-            save_file(cpu(self._v), os.path.join(path, "checkpoint", "adam_v.safetensors"))
+        save_file({k: v.detach().cpu().contiguous() for k, v in self.p.items()}, os.path.join(path, "checkpoint", "model.safetensors"))
+        self.opt_state.save(path)
         save_file({k: v.contiguous() for k, v in self.ema_state_dict().items()}, os.path.join(path, "ema", "model.safetensors"))
         if self.config is not None:
             with open(os.path.join(path, "ema", "config.json"), "w") as fjs:
                 json.dump(self.config, fjs, indent=2)
         state = dict(step_count=self.step_count, ema_updates=self.ema_updates, global_step=self.global_step, gradient_accumulation_steps=self.k,
-                     precision=self.precision, hyper={n: getattr(self, n) for n in self._HYPER})
-        if self.optimizer == "adamw8bit":
-            state.update(optimizer=self.optimizer, block=adam8.BLOCK)
+                     precision=self.precision, hyper={n: getattr(self, n) for n in self._HYPER}, **self.opt_state.state_json)
         with open(os.path.join(path, "trainer_state.json"), "w") as fjs:
             json.dump(state, fjs, indent=2)
 
@@ -778,37 +760,18 @@ class RdtTrainer(_Optimizer):
         moments, EMA shadows, counters and hyper-parameters; training then continues bit for bit.  Unlike the reference, which starts its
         EMAModel.optimization_step at 0 again, the EMA update count is restored.  A checkpoint written by the other optimizer is refused (a
         trainer_state.json without the `optimizer` key is an "adamw" one): the two kinds of state are not converted into each other."""
-        from safetensors.torch import load_file
         with open(os.path.join(path, "trainer_state.json")) as fjs:
             state = json.load(fjs)
         if state["gradient_accumulation_steps"] != self.k:
             raise ValueError(f"checkpoint was written with gradient_accumulation_steps={state['gradient_accumulation_steps']}, this trainer has {self.k}")
         if state.get("optimizer", "adamw") != self.optimizer:
             raise ValueError(f"checkpoint was written by optimizer={state.get('optimizer', 'adamw')!r}, this trainer has {self.optimizer!r}")
-        files = [("p", ("checkpoint", "model.safetensors")), ("ema", ("ema", "model.safetensors"))]
-        if self.optimizer == "adamw8bit":
-            if state.get("block") != adam8.BLOCK:
-                raise ValueError(f"checkpoint {path}: adamw8bit block size {state.get('block')!r}, this build has {adam8.BLOCK}")
-            st8 = load_file(os.path.join(path, "checkpoint", "adam8.safetensors"))
-            for key, want in zip(("table_signed", "table_unsigned"), adam8.code_tables()):
-                got = st8.pop(key, None)
-                if got is None or got.dtype != F32 or got.shape != (256,) or not torch.equal(got.view(torch.int32), torch.from_numpy(want).view(torch.int32)):
-                    raise ValueError(f"checkpoint {path}: {key} is not this build's code table")
-        else:
-            files += [("m", ("checkpoint", "adam_m.safetensors")), ("v", ("checkpoint", "adam_v.safetensors"))]
-        parts = {n: load_file(os.path.join(path, *f)) for n, f in files}
-        for n, d in parts.items():
-            if set(d) != set(self.p) or any(d[k].shape != v.shape or d[k].dtype != F32 for k, v in self.p.items()):
-                raise ValueError(f"checkpoint {path}: the {n} tensors do not match this trainer's parameters")
-        dev = self.device
-        if self.optimizer == "adamw8bit":
-            self._set_state8(st8)                                 # checks before it adopts: a mismatch leaves the trainer as it was
+        shapes = {k: v.shape for k, v in self.p.items()}
+        parts = {n: _load_matching(path, f, shapes, n) for n, f in (("p", ("checkpoint", "model.safetensors")), ("ema", ("ema", "model.safetensors")))}
+        self.opt_state.load(path, state)                          # checks before it adopts: a mismatch leaves the trainer as it was
         for k, v in self.p.items():
             v.copy_(parts["p"][k])
-        if self.optimizer != "adamw8bit":
-            self._m = {k: parts["m"][k].to(dev).contiguous() for k in self.p}
-            self._v = {k: parts["v"][k].to(dev).contiguous() for k in self.p}
-        self.shadow = {k: parts["ema"][k].to(dev).contiguous() for k in self.p}
+        self.shadow = {k: parts["ema"][k].to(self.device).contiguous() for k in self.p}
         for n, val in state["hyper"].items():
             setattr(self, n, tuple(val) if n == "betas" else val)
         self.step_count, self.ema_updates = state["step_count"], state["ema_updates"]

@@ -500,6 +500,19 @@ _GAMMA = {"2^0.5*t(t-1)": 0, "(2t(t-1))^0.5": 1, "(1-t)^2(2t)^0.5": 2}
 _INTERPOLANT = {"linear": 0, "power3": 1, "power4": 2, "reverse_power3": 3, "reverse_power4": 4, "gaussian_encode_decode": 5, "reverse_linear": 6}
 
 
+MT_CHUNK = 4096        # elements of a tensor one block of the multi-tensor kernels takes: csrc/vt_optim.h's constant
+
+
+def mt_table(tensors):
+    """The multi-tensor table of csrc/vt_optim.h (the record include/vlatouch.h documents) from one (p, g, m, v, shadow | 0, n) per tensor,
+    addresses as integers and n in elements -> (int64 host tensor [ntensors, 7] of {p, g, m, v, shadow, n, first_chunk}, total chunks)."""
+    rows, chunk0 = [], 0
+    for p, g, m, v, shadow, n in tensors:
+        rows.append([p, g, m, v, shadow, n, chunk0])
+        chunk0 += (n + MT_CHUNK - 1) // MT_CHUNK
+    return torch.tensor(rows, dtype=torch.int64), chunk0
+
+
 class _Optimizer:
     """AdamW (+ EMA shadows) over the tensors a trainer yields from `_all_params()`, eager or inside a captured graph."""
     ema_decay = 0.0
@@ -527,16 +540,14 @@ class _Optimizer:
                 L.check(lib.vt_adamw(L.ptr(p), L.ptr(g.contiguous()), L.ptr(self._m[name]), L.ptr(self._v[name]), p.numel(), self.lr, self.betas[0],
                                      self.betas[1], self.eps, self.wd, self.step_count, _sp(dev)), "vt_adamw")
         if hyper is not None:       # graph path: every tensor's AdamW (+ EMA) in one launch over a device table of pointers
-            rows, chunk0 = [], 0
-            for name, p, g in self._all_params():
+            def row(name, p, g):
                 assert g.is_contiguous() and p.is_contiguous()
                 sh = self.shadow.get(name)
-                rows.append([p.data_ptr(), g.data_ptr(), self._m[name].data_ptr(), self._v[name].data_ptr(), 0 if sh is None else sh.data_ptr(),
-                             p.numel(), chunk0])
-                chunk0 += (p.numel() + 4095) // 4096
-            self._mt_host.copy_(torch.tensor(rows, dtype=torch.int64))          # pinned, allocated by _capture_prep() before the capture began
+                return p.data_ptr(), g.data_ptr(), self._m[name].data_ptr(), self._v[name].data_ptr(), 0 if sh is None else sh.data_ptr(), p.numel()
+            rows, chunks = mt_table(row(*t) for t in self._all_params())
+            self._mt_host.copy_(rows)                                           # pinned, allocated by _capture_prep() before the capture began
             self._mt_dev.copy_(self._mt_host, non_blocking=True)
-            L.check(lib.vt_adamw_ema_multi(L.ptr(self._mt_dev), len(rows), chunk0, L.ptr(hyper), self.betas[0], self.betas[1], self.eps, self.wd,
+            L.check(lib.vt_adamw_ema_multi(L.ptr(self._mt_dev), len(rows), chunks, L.ptr(hyper), self.betas[0], self.betas[1], self.eps, self.wd,
                                            _sp(dev)), "vt_adamw_ema_multi")
             return
         for name, sh in self.shadow.items():
