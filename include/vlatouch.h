@@ -79,7 +79,8 @@ int vt_pack_w32(const void* W, long ldw, void* out, int N, int K, vt_stream_t st
 int vt_tune(int knob, int value);
 
 /* Flash attention, head_dim 64 (or 96: params.hd): params = struct VtAttnParams (csrc/vt_kernels.h), host pointer.
- * Replaces F.scaled_dot_product_attention (models/rdt/blocks.py:116-123) and HF Dinov2SelfAttention. */
+ * Replaces F.scaled_dot_product_attention (models/rdt/blocks.py:116-123) and HF Dinov2SelfAttention.  A query row whose keys are all masked
+ * (kmask) is written as zeros, where torch's SDPA returns NaN: the row vt_attention_bwd gives zero gradients. */
 int vt_attention(const void* params, vt_stream_t stream);
 /* Cross-attention against a cached condition, head_dim 64, bf16 or fp16: params = struct VtAttnKvtParams (csrc/vt_kernels.h), host pointer.
  * K / V come as the per-head tile stream documented in csrc/vt_attn_kvt.hip; params.parts > 1 splits every sample's keys over that many

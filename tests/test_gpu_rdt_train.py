@@ -273,6 +273,43 @@ def test_loss_and_gradients_fp32(name, rms_mode, prediction_type):
     assert worst <= 1e-4, (wk, worst)
 
 
+def _sdpa_zero_for_empty_rows(q, k, v, mask=None):
+    """oracle.rdt._sdpa with the softmax of a row whose keys are all masked set to 0 (torch has NaN there): what vt_attention writes."""
+    dt = q.dtype
+    s = (q.float() @ k.float().transpose(-1, -2)) * (q.shape[-1] ** -0.5)
+    if mask is not None:
+        s = s.masked_fill(~mask, float("-inf"))
+    return (torch.softmax(s, dim=-1).nan_to_num(0.0) @ v.float()).to(dt)
+
+
+def test_loss_and_gradients_fp32_with_an_empty_instruction(monkeypatch):
+    """One sample's lang_attn_mask all False: its language cross-attention rows are zeros in the forward (vt_attention) and carry zero gradients
+    in the backward (vt_attention_bwd), so the loss and every gradient stay finite and meet the bars of test_loss_and_gradients_fp32."""
+    cfg, B, Ll = cases.RDT_TINY, 3, 12
+    sd, b = cases.rdt_sd(cfg), R.batch(cfg, B, Ll)
+    b["lang_attn_mask"] = b["lang_attn_mask"].clone()
+    b["lang_attn_mask"][1] = False
+    assert bool(b["lang_attn_mask"][0].any()) and bool(b["lang_attn_mask"][2].any())
+    monkeypatch.setattr(orr, "_sdpa", _sdpa_zero_for_empty_rows)
+    ref_loss, ref_g = R.loss_and_grads(sd, b, cfg)
+    assert np.isfinite(ref_loss) and all(bool(torch.isfinite(g).all()) for g in ref_g.values())
+    tr = _trainer(cfg, sd)
+    loss = float(_get_loss(tr, b))
+    grads = tr.grads()
+    assert set(grads) == set(ref_g) == set(sd)
+    assert np.isfinite(loss), loss
+    bad = [k for k in sd if not bool(torch.isfinite(grads[k]).all())]
+    assert not bad, bad[:8]
+    worst, wk = 0.0, None
+    for k in sd:
+        e = R.rel_err(grads[k], ref_g[k])
+        if e > worst:
+            worst, wk = e, k
+    print(f"[rdt_train tiny, sample 1 without instruction] loss {loss:.7f} vs {ref_loss:.7f}; worst gradient {worst:.2e} of its norm ({wk}), {len(sd)} tensors")
+    assert abs(loss - ref_loss) <= 1e-5 * abs(ref_loss), (loss, ref_loss)
+    assert worst <= 1e-4, (wk, worst)
+
+
 @pytest.mark.parametrize("prediction_type", ["sample", "epsilon"])
 @pytest.mark.parametrize("rms_mode", ["meansq", "var"])
 def test_loss_and_gradients_against_the_references_own_run(rms_mode, prediction_type):

@@ -204,7 +204,7 @@ __global__ __launch_bounds__(512) void attn_kernel(const VtAttnParams p) {
   float l = l_run;
   l += __shfl_xor(l, 16, 64);
   l += __shfl_xor(l, 32, 64);
-  const float inv = 1.0f / l;
+  const float inv = l > 0.f ? 1.0f / l : 0.f;   // a row whose keys are all masked: zeros (as vt_attention_kvt writes and vt_attention_bwd assumes)
   if (q < p.Nq) {
     T* O = reinterpret_cast<T*>(p.O) + (long)b * p.o_bs + (long)q * p.o_rs + h * HD;
 #pragma unroll
