@@ -451,6 +451,16 @@ typedef struct {
   float scale;
 } VtAttnBwdParams;
 int vt_attention_bwd(const VtAttnBwdParams* params, vt_stream_t stream);
+/* vt_attention_bwd_mfma (csrc/vt_attn_bwd.hip): the same gradients on bf16 MFMA, for bf16 operands, head_dim 64, 1 <= Nq <= 128, any Nk >= 1.
+ *   One rounding more than vt_attention_bwd: P and dS = P (dP - delta) are rounded to bf16 (nearest even) before they multiply dO, Q and K; the
+ *   scale is applied to the fp32 sums afterwards (tests/attn_bwd_mfma_ref.py states the arithmetic).  Unit inner stride, every other stride a
+ *   multiple of 8 elements, every base 16-byte aligned.  `ws` receives (max, 1 / sum, delta) as above; `ws2` (16-byte aligned, at least
+ *   vt_attention_bwd_mfma_ws_bytes(B, H, Nq, Nk) bytes, which is < 0 for a shape this entry does not take) holds per-key-run partial results.
+ *   Anything outside the contract is refused (VT_ERR_UNSUPPORTED / VT_ERR_ARG and a message) before any launch: there is no fallback.  No
+ *   allocation, no synchronisation, no atomics: two calls give the same bits.  vt_attention_bwd stays the default of the trainer and the only
+ *   fp32 path. */
+long vt_attention_bwd_mfma_ws_bytes(int B, int H, int Nq, int Nk);
+int vt_attention_bwd_mfma(const VtAttnBwdParams* params, void* ws2, long ws2_bytes, vt_stream_t stream);
 int vt_rmsnorm_bwd(const void* x, const float* w, const void* dy, void* dx, float* dyxr, int rows, int D, float eps, int mode, int dt, vt_stream_t stream);
 int vt_headnorm_bwd(const void* x, long x_stride, void* dy, long dy_stride, int heads, long tokens, const float* w, float* part, float eps,
                     int mode, int dt, vt_stream_t stream);

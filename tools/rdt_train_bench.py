@@ -23,6 +23,13 @@ device-synchronised host wall clock and device events:
 the whole phase (clip + AdamW + EMA, and in bf16 the refresh of the 16-bit weight copies, as `clip_adamw_ema_ms` of the default run counts it)
 and the AdamW + EMA launch alone with the bytes it moves (24 B per parameter of a quantised tensor plus its scales, 36 B otherwise) against the
 HBM roof; optimizer state bytes; peak device memory of a step of each trainer.  Added to `--out` under the key `adamw8bit`; the other keys stay.
+
+`--attention-backward mfma` measures the bf16 step with the MFMA attention backward (csrc/vt_attn_bwd.hip) beside the default "wave" kernels at
+every `--batch` size: one trainer of each kind in one process, their steps alternating and swapping who goes first, `--warmup` warm-up and
+`--steps` (default 21 here) timed steps, every phase device-synchronised: forward (get_loss without backward), backward, clip + AdamW + EMA,
+medians with min / max; by device events the attention-backward launches alone of one image cross-attention (`--img-len` keys), one language
+cross-attention and one self-attention at the trainer's strides; peak device memory of a step of each trainer; the bytes of `ws2`; the
+torch-autograd yardstick of the same run.  Added to `--out` under the key `attention_backward_mfma`; the other keys stay.
 """
 from __future__ import annotations
 
@@ -238,6 +245,98 @@ def optimizer_run(a, c, sd, params, dev):
     return out
 
 
+def attention_launches(a, c, B, dev):
+    """Device-event time of the attention-backward launches alone, both kernels alternating, at the trainer's packed layouts -> dict."""
+    from vlatouch import _lib as L
+    from vlatouch.rdt_train import attention_bwd
+    H, N = c["heads"], c["horizon"] + 3
+    D = H * 64
+    g = torch.Generator(device=dev).manual_seed(5)
+    rn = lambda *s: torch.randn(*s, generator=g, device=dev).bfloat16()
+    out = {}
+    for name, Nk, cross in (("image_cross_attention", a.img_len, True), ("language_cross_attention", a.lang_len, True), ("self_attention", N, False)):
+        if cross:
+            qb, kvb, dqb, dkvb = rn(B, N, D), rn(B, Nk, 2 * D), torch.empty(B, N, D, device=dev, dtype=torch.bfloat16), torch.empty(B, Nk, 2 * D, device=dev, dtype=torch.bfloat16)
+            v4 = lambda q_, kv_: (q_.view(B, N, H, 64), kv_.view(B, Nk, 2, H, 64)[:, :, 0], kv_.view(B, Nk, 2, H, 64)[:, :, 1])
+            (q, k, v), (dq, dk, dv) = v4(qb, kvb), v4(dqb, dkvb)
+        else:
+            qkv, dqkv = rn(B, N, 3 * D), torch.empty(B, N, 3 * D, device=dev, dtype=torch.bfloat16)
+            q, k, v = (qkv.view(B, N, 3, H, 64)[:, :, i] for i in range(3))
+            dq, dk, dv = (dqkv.view(B, N, 3, H, 64)[:, :, i] for i in range(3))
+        do = rn(B, N, H, 64)
+        km = torch.ones(B, Nk, dtype=torch.uint8, device=dev) if name == "language_cross_attention" else None
+        ms = {"wave": [], "mfma": []}
+        for n in range(2 + 7):
+            for kind in (("wave", "mfma") if n % 2 == 0 else ("mfma", "wave")):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize(dev)
+                e0.record()
+                attention_bwd(q, k, v, do, dq, dk, dv, kmask=km, kernel=kind)
+                e1.record()
+                torch.cuda.synchronize(dev)
+                if n >= 2:
+                    ms[kind].append(e0.elapsed_time(e1))
+        out[name] = {"Nq": N, "Nk": Nk, "wave_ms": _stats(ms["wave"]), "mfma_ms": _stats(ms["mfma"]),
+                     "mfma_over_wave": _stats(ms["mfma"])["median"] / _stats(ms["wave"])["median"],
+                     "ws2_bytes": int(L.lib().vt_attention_bwd_mfma_ws_bytes(B, H, N, Nk))}
+    out["timing"] = "device events around one attention_bwd call (workspace allocation from the caching allocator included), 2 warm-up + 7 timed, the two kernels alternating"
+    return out
+
+
+def attention_run(a, c, sd, params, dev, B):
+    """The bf16 step under attention_backward="mfma" and "wave", alternating in this process at batch B -> dict."""
+    from vlatouch.rdt_train import RdtTrainer
+    steps = a.steps
+    sync = lambda: torch.cuda.synchronize(dev)
+    args, kw = inputs(a, B, dev)
+    kinds = ("mfma", "wave")
+    trs, peak = {}, {}
+    for kind in kinds:                                       # peak memory of one whole step of each trainer, over what is already resident
+        torch.cuda.empty_cache()
+        base = torch.cuda.memory_allocated(dev)
+        torch.cuda.reset_peak_memory_stats(dev)
+        tr = trs[kind] = RdtTrainer(sd, heads=c["heads"], horizon=64, action_dim=128, lr=a.lr, precision="bf16", attention_backward=kind, device=dev)
+        for _ in range(max(1, a.warmup)):
+            tr.get_loss(*args, **kw)
+            tr.optimizer_step()
+        sync()
+        peak[kind] = (torch.cuda.max_memory_allocated(dev) - base) / 2 ** 30
+    ph = {k: {n: [] for n in ("forward_ms", "backward_ms", "clip_adamw_ema_ms", "step_ms")} for k in kinds}
+    losses = {k: [] for k in kinds}
+    for n in range(steps):
+        for kind in (kinds if n % 2 == 0 else kinds[::-1]):  # who goes first alternates
+            tr = trs[kind]
+            sync(); t0 = time.perf_counter()
+            tr.get_loss(*args, backward=False, **kw)
+            sync(); t1 = time.perf_counter()
+            loss = tr.get_loss(*args, **kw)
+            sync(); t2 = time.perf_counter()
+            tr.optimizer_step()
+            sync(); t3 = time.perf_counter()
+            f, fb, o = 1e3 * (t1 - t0), 1e3 * (t2 - t1), 1e3 * (t3 - t2)
+            ph[kind]["forward_ms"].append(f), ph[kind]["backward_ms"].append(fb - f), ph[kind]["clip_adamw_ema_ms"].append(o), ph[kind]["step_ms"].append(fb + o)
+            losses[kind].append(float(loss))
+    out = {"batch": B, "precision": "bf16", "parameters": params, "warmup": a.warmup, "timed_steps": steps}
+    for kind in kinds:
+        out[kind] = {n: _stats(v) for n, v in ph[kind].items()}
+        out[kind]["peak_memory_gib_of_a_step"] = peak[kind]
+        out[kind]["losses"] = losses[kind]
+        out[kind]["loss_decreases"] = bool(losses[kind][-1] < losses[kind][0])
+    out["backward_mfma_over_wave"] = out["mfma"]["backward_ms"]["median"] / out["wave"]["backward_ms"]["median"]
+    out["step_mfma_over_wave"] = out["mfma"]["step_ms"]["median"] / out["wave"]["step_ms"]["median"]
+    out["backward_faster_than_wave"] = bool(out["backward_mfma_over_wave"] < 1.0)
+    del trs, tr
+    torch.cuda.empty_cache()
+    out["attention_backward_launches"] = attention_launches(a, c, B, dev)
+    y = "not measured: --no-yardstick" if a.no_yardstick else yardstick(sd, c, args, kw, dev)
+    if isinstance(y, dict):
+        for kind in kinds:
+            y[f"ratio_torch_over_{kind}"] = y["fwd_bwd_ms"] / (out[kind]["forward_ms"]["median"] + out[kind]["backward_ms"]["median"])
+    out["torch_autograd_yardstick"] = y
+    out["timing"] = "host wall clock between two device synchronisations; the two trainers alternate and swap who goes first every step"
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, nargs="+", default=[4, 32])
@@ -248,19 +347,42 @@ def main():
     ap.add_argument("--img-len", type=int, default=4374)
     ap.add_argument("--lang-len", type=int, default=32)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps: 10, or 21 with --attention-backward mfma")
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--accum", type=int, default=1, help="gradient_accumulation_steps; > 1 measures the accumulated step and adds it to --out")
     ap.add_argument("--optimizer", default="adamw", choices=["adamw", "adamw8bit"],
                     help="adamw8bit measures the 8-bit optimizer phase beside the 32-bit one and adds it to --out")
+    ap.add_argument("--attention-backward", default="wave", choices=["wave", "mfma"],
+                    help="mfma measures the bf16 step with the MFMA attention backward beside the wave kernels and adds it to --out")
+    ap.add_argument("--step-attention-backward", default="wave", choices=["wave", "mfma"],
+                    help="the attention backward of the default run's trainer (a kernel trace of the step under \"mfma\" uses this)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rdt_train_bench.json"))
     a = ap.parse_args()
+    if a.attention_backward == "mfma" and a.precision != "bf16":
+        ap.error("--attention-backward mfma measures the bf16 step")
+    if a.steps is None:
+        a.steps = 21 if a.attention_backward == "mfma" else 10
     from vlatouch.rdt_train import RdtTrainer
     dev = torch.device("cuda:0")
     c = dict(hidden=a.hidden, depth=a.depth, heads=a.hidden // 64, horizon=64, action_dim=128, lang_token_dim=4096, img_token_dim=1152,
              state_token_dim=128, max_lang_cond_len=1024, img_cond_len=a.img_len)
     sd = synth.fill_state_dict_device(synth.rdt_runner_shapes(**c), dev, torch.float32, seed=7)
     params = sum(v.numel() for v in sd.values())
+    if a.attention_backward == "mfma":
+        rec = {}
+        if os.path.exists(a.out):
+            with open(a.out) as f:
+                rec = json.load(f)
+        runs = []
+        for B in a.batch:
+            runs.append(attention_run(a, c, sd, params, dev, B))
+            print(json.dumps(runs[-1]))
+        rec["attention_backward_mfma"] = dict(runs=runs, config=c, lang_len=a.lang_len, lr=a.lr, device=torch.cuda.get_device_name(dev),
+                                              backward_faster_than_wave_at_every_batch=all(r["backward_faster_than_wave"] for r in runs))
+        with open(a.out, "w") as f:
+            json.dump(rec, f, indent=1)
+        print("wrote", a.out)
+        return
     if a.optimizer == "adamw8bit":
         rec = {}
         if os.path.exists(a.out):
@@ -287,14 +409,17 @@ def main():
     if os.path.exists(a.out):
         with open(a.out) as f:
             old = json.load(f)
-        kept = {k: old[k] for k in ("accumulation", "adamw8bit") if k in old}
+        kept = {k: old[k] for k in ("accumulation", "adamw8bit", "attention_backward_mfma") if k in old}
     rec = {"config": c, "precision": a.precision, "parameters": params, "lang_len": a.lang_len, "warmup": a.warmup, "steps": a.steps, "lr": a.lr,
            "device": torch.cuda.get_device_name(dev), "runs": []}
+    if a.step_attention_backward != "wave":
+        rec["attention_backward"] = a.step_attention_backward
     sync = lambda: torch.cuda.synchronize(dev)
     for B in a.batch:
         torch.cuda.empty_cache()
         torch.cuda.reset_peak_memory_stats(dev)
-        tr = RdtTrainer(sd, heads=c["heads"], horizon=64, action_dim=128, lr=a.lr, precision=a.precision, device=dev)
+        tr = RdtTrainer(sd, heads=c["heads"], horizon=64, action_dim=128, lr=a.lr, precision=a.precision, attention_backward=a.step_attention_backward,
+                        device=dev)
         args, kw = inputs(a, B, dev)
         t_f = t_fb = t_o = 0.0
         losses = []

@@ -11,7 +11,9 @@
 // A wave owns one query row (dQ) or one key row (dK, dV) with lane = head-dim element (head_dim 64 = the wave width), so every sum has a
 // fixed order.  These are fp32 VALU kernels with one wave reduction per (query, key) pair: correct and reproducible, not fast — at RDT-1B size
 // the two attention-backward kernels are 40 % of the fp32 step's kernel time and 65 % of the bf16 step's (profiles/rdt_train_kernels*.txt), almost all of it the 4 374-key image
-// cross-attention, so an MFMA tile for that case is the first thing to build next.
+// cross-attention.  The MFMA tile for that case exists beside them: vt_attention_bwd_mfma (csrc/vt_attn_bwd.hip; bf16 only, at most 128 query rows,
+// P and dS rounded to bf16), which the trainer takes with attention_backward="mfma".  These kernels stay the default, the fp32-P statement and the
+// only fp32 path.
 #include <math.h>
 #include "vt_common.h"
 #include "vt_host.h"

@@ -282,6 +282,8 @@ SIGNATURES = {
     "vt_mul_": (_I, [_P, _P, _L, _P]),
     "vt_mse_residual": (_I, [_P, _P, _P, _P, _P, _P, _L, _P]),
     "vt_attention_bwd": (_I, [_P, _P]),
+    "vt_attention_bwd_mfma_ws_bytes": (_L, [_I, _I, _I, _I]),
+    "vt_attention_bwd_mfma": (_I, [_P, _P, _L, _P]),
     "vt_rmsnorm_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _F, _I, _I, _P]),
     "vt_headnorm_bwd": (_I, [_P, _L, _P, _L, _I, _L, _P, _P, _F, _I, _I, _P]),
     "vt_act_bwd": (_I, [_P, _P, _P, _L, _I, _I, _P]),

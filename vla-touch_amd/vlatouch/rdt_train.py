@@ -142,8 +142,16 @@ def headnorm_bwd_(x: torch.Tensor, dy: torch.Tensor, heads: int, w: torch.Tensor
     return T.colsum(part)
 
 
-def attention_bwd(q, k, v, do, dq, dk, dv, *, kmask: Optional[torch.Tensor] = None, scale: Optional[float] = None) -> None:
-    """q, do, dq [B, Nq, H, 64]; k, v, dk, dv [B, Nk, H, 64] (any strides with unit inner stride, one dtype: fp32 or bf16); kmask [B, Nk] uint8."""
+ATTENTION_BACKWARDS = ("wave", "mfma")
+
+
+def attention_bwd(q, k, v, do, dq, dk, dv, *, kmask: Optional[torch.Tensor] = None, scale: Optional[float] = None, kernel: str = "wave") -> torch.Tensor:
+    """q, do, dq [B, Nq, H, 64]; k, v, dk, dv [B, Nk, H, 64] (any strides with unit inner stride, one dtype: fp32 or bf16); kmask [B, Nk] uint8.
+    kernel="wave": vt_attention_bwd (fp32 probabilities, one wave per row).  kernel="mfma": vt_attention_bwd_mfma (bf16 operands, Nq <= 128,
+    strides in multiples of 8: P and dS are rounded to bf16, csrc/vt_attn_bwd.hip); a shape or dtype it does not take raises, nothing falls back.
+    -> the row statistics [B * H * Nq, 3] = (max, 1 / sum, delta)."""
+    if kernel not in ATTENTION_BACKWARDS:
+        raise ValueError(f"attention_bwd: kernel must be one of {ATTENTION_BACKWARDS}, got {kernel!r}")
     B, Nq, H, hd = q.shape
     Nk = k.shape[1]
     assert hd == 64 and k.shape == v.shape == dk.shape == dv.shape == (B, Nk, H, 64) and do.shape == dq.shape == q.shape
@@ -159,7 +167,17 @@ def attention_bwd(q, k, v, do, dq, dk, dv, *, kmask: Optional[torch.Tensor] = No
         p.kmask, p.km_bs = kmask.data_ptr(), Nk
     p.B, p.H, p.Nq, p.Nk, p.hd, p.dtype = B, H, Nq, Nk, 64, L.dt_code(q.dtype)
     p.scale = scale if scale is not None else hd ** -0.5
-    L.check(L.lib().vt_attention_bwd(C.byref(p), _sp(q.device)), "vt_attention_bwd")
+    if kernel == "mfma":
+        if q.dtype != torch.bfloat16:
+            raise ValueError(f"attention_bwd: kernel='mfma' takes bf16 tensors, got {q.dtype}")
+        nbytes = L.lib().vt_attention_bwd_mfma_ws_bytes(B, H, Nq, Nk)
+        if nbytes < 0:
+            raise ValueError(f"attention_bwd: kernel='mfma' does not take B={B}, H={H}, Nq={Nq}, Nk={Nk} (1 <= Nq <= 128, B * H <= 65535)")
+        ws2 = torch.empty(nbytes, dtype=torch.uint8, device=q.device)
+        L.check(L.lib().vt_attention_bwd_mfma(C.byref(p), L.ptr(ws2), nbytes, _sp(q.device)), "vt_attention_bwd_mfma")
+    else:
+        L.check(L.lib().vt_attention_bwd(C.byref(p), _sp(q.device)), "vt_attention_bwd")
+    return ws.view(-1, 3)
 
 
 def ddpm_qsample(state, action, noise, mask, timesteps, ab, dtype=F32) -> torch.Tensor:
@@ -278,7 +296,7 @@ class RdtTrainer:
                  num_train_timesteps: int = 1000, beta_schedule: str = "squaredcos_cap_v2", precision: str = "fp32", lr: float = 5e-6,
                  betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, max_grad_norm: float = 1.0, lr_scheduler: str = "constant",
                  lr_warmup_steps: int = 500, ema: Optional[dict] = None, config: Optional[dict] = None, gradient_accumulation_steps: int = 1,
-                 optimizer: str = "adamw", device="cuda"):
+                 optimizer: str = "adamw", attention_backward: str = "wave", device="cuda"):
         if precision not in ("fp32", "bf16"):
             raise ValueError(f"precision must be 'fp32' or 'bf16', got {precision!r} (no fp16 training mode: its gradients underflow without loss scaling)")
         if prediction_type not in PREDICTION_TYPES:
@@ -287,6 +305,12 @@ class RdtTrainer:
             raise ValueError(f"rms_mode must be 'meansq' or 'var', got {rms_mode!r}")
         if optimizer not in OPTIMIZERS:
             raise ValueError(f"optimizer must be one of {OPTIMIZERS}, got {optimizer!r}")
+        if attention_backward not in ATTENTION_BACKWARDS:
+            raise ValueError(f"attention_backward must be one of {ATTENTION_BACKWARDS}, got {attention_backward!r}")
+        if attention_backward == "mfma" and precision != "bf16":
+            raise ValueError("attention_backward='mfma' is a bf16 kernel: it needs precision='bf16' ('wave' is the fp32 path)")
+        if attention_backward == "mfma" and horizon + 3 > 128:
+            raise ValueError(f"attention_backward='mfma' holds at most 128 query rows, horizon + 3 = {horizon + 3}")
         lr_at(lr, lr_scheduler, 0, lr_warmup_steps)                       # raises on an unknown scheduler
         if int(gradient_accumulation_steps) != gradient_accumulation_steps or gradient_accumulation_steps < 1:
             raise ValueError(f"gradient_accumulation_steps must be an integer >= 1, got {gradient_accumulation_steps!r}")
@@ -308,6 +332,7 @@ class RdtTrainer:
         self.freqs = timestep_freqs(256).to(dev)
         self.adaptors = {n: self._adaptor_layers(n) for n in ("lang_adaptor", "img_adaptor", "state_adaptor")}
         self.precision = precision
+        self.attention_backward = attention_backward          # an execution choice, not state: checkpoints do not record it
         self.adt = F32 if precision == "fp32" else torch.bfloat16     # dtype of activations, activation gradients and MFMA operands
         self.w16: Dict[str, torch.Tensor] = {}                        # bf16 mode: copies of the Linear weights and of their transposes,
         self.w16t: Dict[str, torch.Tensor] = {}                       # refreshed after every optimizer step
@@ -532,7 +557,7 @@ class RdtTrainer:
             dq, dkv = new(B * N, D), new(B * Lc, 2 * D)
             attention_bwd(self._heads4(tb["q"], B, N, 0, D), self._heads4(tb["kv"], B, Lc, 0, 2 * D), self._heads4(tb["kv"], B, Lc, D, 2 * D),
                           self._heads4(do, B, N, 0, D), self._heads4(dq, B, N, 0, D), self._heads4(dkv, B, Lc, 0, 2 * D), self._heads4(dkv, B, Lc, D, 2 * D),
-                          kmask=km)
+                          kmask=km, kernel=self.attention_backward)
             g[f"{b}.cross_attn.q_norm.weight"] = headnorm_bwd_(tb["q_raw"], dq, Hh, p[f"{b}.cross_attn.q_norm.weight"], 1e-6, mode)
             g[f"{b}.cross_attn.k_norm.weight"] = headnorm_bwd_(tb["k_raw"], dkv[:, :D], Hh, p[f"{b}.cross_attn.k_norm.weight"], 1e-6, mode)
             dc = self._linear_bwd(f"{b}.cross_attn.kv", c, dkv)
@@ -544,7 +569,7 @@ class RdtTrainer:
             dqkv, qkv = new(B * N, 3 * D), tb["qkv"]
             attention_bwd(self._heads4(qkv, B, N, 0, 3 * D), self._heads4(qkv, B, N, D, 3 * D), self._heads4(qkv, B, N, 2 * D, 3 * D),
                           self._heads4(do, B, N, 0, D), self._heads4(dqkv, B, N, 0, 3 * D), self._heads4(dqkv, B, N, D, 3 * D),
-                          self._heads4(dqkv, B, N, 2 * D, 3 * D))
+                          self._heads4(dqkv, B, N, 2 * D, 3 * D), kernel=self.attention_backward)
             raw = tb["qkv_raw"]
             g[f"{b}.attn.q_norm.weight"] = headnorm_bwd_(raw[:, :D], dqkv[:, :D], Hh, p[f"{b}.attn.q_norm.weight"], 1e-6, mode)
             g[f"{b}.attn.k_norm.weight"] = headnorm_bwd_(raw[:, D:2 * D], dqkv[:, D:2 * D], Hh, p[f"{b}.attn.k_norm.weight"], 1e-6, mode)
