@@ -483,6 +483,16 @@ int vt_mse_loss(const void* pred, const float* target, void* dpred, float* loss,
  *   vt_ema_update_dev per tensor. */
 int vt_grad_accum_multi(const void* table, const void* fresh, int ntensors, long total_chunks, float scale, int accumulate, vt_stream_t stream);
 int vt_ema_multi(const void* table, int ntensors, long total_chunks, const float* hyper, vt_stream_t stream);
+/* The bf16 gradient exchange of data-parallel fine-tuning.  comm_bf16: total_chunks * 4096 bf16 on the device, 16-byte aligned, laid out as
+ * the table implies: tensor i occupies [first_chunk_i * 4096, first_chunk_i * 4096 + n_i), the rest of its last chunk is padding.
+ * vt_grad_fold_pack_multi: the window's last fold and the rounding in one pass.  comm = bf16 (round to nearest even, any NaN as 0x7FC0) of the
+ *   fp32 value vt_grad_accum_multi would have stored with the same arguments (g * scale, or fma(g, scale, acc)); the padding is written as
+ *   zeros; the accumulators (the table's g column) are read when accumulate != 0 and never written.
+ * vt_grad_unpack_multi: acc[e] = float(comm[first_chunk_i * 4096 + e]) for the n_i elements of every tensor; nothing else is written.
+ * One 256-thread block per chunk, no atomics, no allocation: two calls give the same bits. */
+int vt_grad_fold_pack_multi(const void* table, const void* fresh, int ntensors, long total_chunks, float scale, int accumulate, void* comm_bf16,
+                            vt_stream_t stream);
+int vt_grad_unpack_multi(const void* table, const void* comm_bf16, int ntensors, long total_chunks, vt_stream_t stream);
 /* AdamW with block-wise 8-bit moments (csrc/vt_adam8.hip; the dynamic block-wise quantisation of Dettmers et al., "8-bit Optimizers via
  * Block-wise Quantization"; stands where the reference passes --use_8bit_adam, train/train.py:216-237; the arithmetic is stated in
  * DESIGN.md §8 and tests/adam8_ref.py, UNPINNED against bitsandbytes).  A moment tensor is n uint8 codes into a 256-entry table plus one

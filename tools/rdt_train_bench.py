@@ -30,6 +30,14 @@ every `--batch` size: one trainer of each kind in one process, their steps alter
 medians with min / max; by device events the attention-backward launches alone of one image cross-attention (`--img-len` keys), one language
 cross-attention and one self-attention at the trainer's strides; peak device memory of a step of each trainer; the bytes of `ws2`; the
 torch-autograd yardstick of the same run.  Added to `--out` under the key `attention_backward_mfma`; the other keys stay.
+
+`--data-parallel fp32|bf16` measures the data-parallel step (`RdtTrainer(process_group=, comm_dtype=)`) at batch 4, bf16, `attention_backward="mfma"`
+over an RCCL ("nccl") process group of world size 1, which is all a one-GPU machine allows: NO SCALING NUMBER CAN BE PRODUCED ON A ONE-GPU BOX, and a
+world-size-1 all-reduce moves nothing between cards.  A grouped and an ungrouped trainer alternate in one process and swap who goes first; by device
+events, `--warmup` + 21 timed: vt_grad_accum_multi (the fold) and vt_grad_fold_pack_multi (fold + pack) on the same table with the same fresh
+gradients, the all-reduce on itself (the arena, or the bf16 buffer, in `comm_bucket_bytes` slices), vt_grad_unpack_multi, and the whole step of
+each trainer; medians with min / max, bytes moved against the HBM roof, and whether fold + pack took no longer than the fold (medians, with the
+min - max spread of the two as the only margin).  Added to `--out` under the key `data_parallel`; the other keys stay.
 """
 from __future__ import annotations
 
@@ -337,6 +345,95 @@ def attention_run(a, c, sd, params, dev, B):
     return out
 
 
+def data_parallel_run(a, c, sd, params, dev):
+    """The grouped step (world size 1 over RCCL) beside the ungrouped one, and the exchange launches alone, at batch 4 -> dict."""
+    import torch.distributed as dist
+    from vlatouch import _lib as L
+    from vlatouch import train as T
+    from vlatouch.rdt_train import RdtTrainer
+    os.environ.setdefault("MASTER_ADDR", "127.0.0.1"), os.environ.setdefault("MASTER_PORT", "29571")
+    torch.cuda.set_device(dev)
+    dist.init_process_group("nccl", rank=0, world_size=1, device_id=dev)
+    G = dist.group.WORLD
+    B, comm, timed = 4, a.data_parallel, 21
+    sync = lambda: torch.cuda.synchronize(dev)
+    ev = lambda: torch.cuda.Event(enable_timing=True)
+    args, kw = inputs(a, B, dev)
+    mk = lambda **k: RdtTrainer(sd, heads=c["heads"], horizon=64, action_dim=128, lr=a.lr, precision="bf16", attention_backward="mfma", device=dev, **k)
+    trs = {"grouped": mk(process_group=G, comm_dtype=comm), "ungrouped": mk()}
+    kinds = tuple(trs)
+    for _ in range(max(1, a.warmup)):
+        for kind in kinds:
+            trs[kind].train_step(*args, **kw)
+    sync()
+    step = {k: [] for k in kinds}
+    losses = {k: [] for k in kinds}
+    for n in range(timed):
+        for kind in (kinds if n % 2 == 0 else kinds[::-1]):      # who goes first alternates
+            e0, e1 = ev(), ev()
+            sync()
+            e0.record()
+            loss = trs[kind].train_step(*args, **kw)
+            e1.record()
+            sync()
+            step[kind].append(e0.elapsed_time(e1))
+            losses[kind].append(float(loss))
+    # the exchange's launches alone, on the grouped trainer's table with the last step's fresh gradients
+    tr = trs["grouped"]
+    tr.get_loss(*args, **kw)
+    tab, nt, chunks = tr._table()
+    fresh = torch.tensor([tr._fresh_grad(name).data_ptr() for name in tr.p], dtype=torch.int64).to(dev)
+    buf16 = tr._comm if tr._comm is not None else torch.zeros(chunks * T.MT_CHUNK, dtype=torch.bfloat16, device=dev)
+    lib, sp = L.lib(), lambda: L.stream_ptr(dev)
+    launches = {
+        "fold_store": lambda: L.check(lib.vt_grad_accum_multi(L.ptr(tab), L.ptr(fresh), nt, chunks, 1.0, 0, sp()), "vt_grad_accum_multi"),
+        "fold_pack_store": lambda: L.check(lib.vt_grad_fold_pack_multi(L.ptr(tab), L.ptr(fresh), nt, chunks, 1.0, 0, L.ptr(buf16), sp()), "vt_grad_fold_pack_multi"),
+        "fold_add": lambda: L.check(lib.vt_grad_accum_multi(L.ptr(tab), L.ptr(fresh), nt, chunks, 0.5, 1, sp()), "vt_grad_accum_multi"),
+        "fold_pack_add": lambda: L.check(lib.vt_grad_fold_pack_multi(L.ptr(tab), L.ptr(fresh), nt, chunks, 0.5, 1, L.ptr(buf16), sp()), "vt_grad_fold_pack_multi"),
+        "unpack": lambda: L.check(lib.vt_grad_unpack_multi(L.ptr(tab), L.ptr(buf16), nt, chunks, sp()), "vt_grad_unpack_multi"),
+        "all_reduce": lambda: tr._all_reduce(tr._comm if comm == "bf16" else tr._arena),
+    }
+    ms = {k: [] for k in launches}
+    order = tuple(launches)
+    for n in range(2 + timed):
+        for name in (order if n % 2 == 0 else order[::-1]):
+            e0, e1 = ev(), ev()
+            sync()
+            e0.record()
+            launches[name]()
+            e1.record()
+            sync()
+            if n >= 2:
+                ms[name].append(e0.elapsed_time(e1))
+    elems = chunks * T.MT_CHUNK
+    moved = {"fold_store": 8.0 * params, "fold_add": 12.0 * params, "fold_pack_store": 4.0 * params + 2.0 * elems, "fold_pack_add": 8.0 * params + 2.0 * elems,
+             "unpack": 6.0 * params, "all_reduce": (2.0 if comm == "bf16" else 4.0) * elems}
+    out = {"batch": B, "precision": "bf16", "attention_backward": "mfma", "comm_dtype": comm, "world_size": 1, "backend": dist.get_backend(),
+           "parameters": params, "arena_elements": elems, "comm_bucket_bytes": tr.comm_bucket_bytes, "warmup": a.warmup, "timed": timed}
+    for name, v in ms.items():
+        st = _stats(v)
+        if name != "all_reduce":
+            rate = moved[name] / (st["median"] / 1e3)
+            st.update(bytes_moved=moved[name], bytes_per_s=rate, share_of_hbm_spec=rate / HBM_SPEC_BYTES_PER_S, share_of_float4_copy_rate=rate / HBM_COPY_BYTES_PER_S)
+        else:
+            st.update(buffer_bytes=moved[name], note="world size 1: nothing crosses a link; this is RCCL's launch and its pass over the buffer")
+        out[f"{name}_ms"] = st
+    for mode in ("store", "add"):
+        f, fp = out[f"fold_{mode}_ms"], out[f"fold_pack_{mode}_ms"]
+        margin = max(f["max"] - f["min"], fp["max"] - fp["min"])
+        out[f"fold_pack_{mode}_over_fold"] = fp["median"] / f["median"]
+        out[f"fold_pack_{mode}_no_longer_than_fold"] = bool(fp["median"] <= f["median"] + margin)
+        out[f"fold_pack_{mode}_margin_ms"] = margin
+    for kind in kinds:
+        out[f"step_{kind}_ms"] = _stats(step[kind])
+        out[f"losses_{kind}"] = losses[kind]
+    out["step_grouped_over_ungrouped"] = out["step_grouped_ms"]["median"] / out["step_ungrouped_ms"]["median"]
+    out["scaling"] = "No scaling number can be produced on a one-GPU box; the all-reduce is not overlapped with the backward."
+    out["timing"] = "device events between two device synchronisations; the trainers, and the launches, alternate and swap who goes first"
+    dist.destroy_process_group()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, nargs="+", default=[4, 32])
@@ -356,6 +453,8 @@ def main():
                     help="mfma measures the bf16 step with the MFMA attention backward beside the wave kernels and adds it to --out")
     ap.add_argument("--step-attention-backward", default="wave", choices=["wave", "mfma"],
                     help="the attention backward of the default run's trainer (a kernel trace of the step under \"mfma\" uses this)")
+    ap.add_argument("--data-parallel", default=None, choices=["fp32", "bf16"],
+                    help="measures the data-parallel step over an RCCL group of world size 1 beside the ungrouped one and adds it to --out")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rdt_train_bench.json"))
     a = ap.parse_args()
     if a.attention_backward == "mfma" and a.precision != "bf16":
@@ -368,6 +467,18 @@ def main():
              state_token_dim=128, max_lang_cond_len=1024, img_cond_len=a.img_len)
     sd = synth.fill_state_dict_device(synth.rdt_runner_shapes(**c), dev, torch.float32, seed=7)
     params = sum(v.numel() for v in sd.values())
+    if a.data_parallel is not None:
+        rec = {}
+        if os.path.exists(a.out):
+            with open(a.out) as f:
+                rec = json.load(f)
+        rec.setdefault("data_parallel", {})[a.data_parallel] = dict(data_parallel_run(a, c, sd, params, dev), config=c, lang_len=a.lang_len, lr=a.lr,
+                                                                    device=torch.cuda.get_device_name(dev))
+        print(json.dumps(rec["data_parallel"][a.data_parallel]))
+        with open(a.out, "w") as f:
+            json.dump(rec, f, indent=1)
+        print("wrote", a.out)
+        return
     if a.attention_backward == "mfma":
         rec = {}
         if os.path.exists(a.out):
@@ -409,7 +520,7 @@ def main():
     if os.path.exists(a.out):
         with open(a.out) as f:
             old = json.load(f)
-        kept = {k: old[k] for k in ("accumulation", "adamw8bit", "attention_backward_mfma") if k in old}
+        kept = {k: old[k] for k in ("accumulation", "adamw8bit", "attention_backward_mfma", "data_parallel") if k in old}
     rec = {"config": c, "precision": a.precision, "parameters": params, "lang_len": a.lang_len, "warmup": a.warmup, "steps": a.steps, "lr": a.lr,
            "device": torch.cuda.get_device_name(dev), "runs": []}
     if a.step_attention_backward != "wave":

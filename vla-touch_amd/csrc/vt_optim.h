@@ -1,6 +1,6 @@
 // vt_optim.h — what every optimizer kernel has to agree on, stated once: one element of torch.optim.AdamW / torch_ema, and the multi-tensor
-// table (record, chunk size, chunk -> row lookup) of vt_adamw_ema_multi, vt_grad_clip_multi, vt_grad_accum_multi, vt_ema_multi
-// (vt_train.hip, vt_train_rdt.hip) and vt_adamw8_ema_multi (vt_adam8.hip).  Contraction is switched off in the element functions so that all
+// table (record, chunk size, chunk -> row lookup) of vt_adamw_ema_multi, vt_grad_clip_multi, vt_grad_accum_multi, vt_ema_multi,
+// vt_grad_fold_pack_multi, vt_grad_unpack_multi (vt_train.hip, vt_train_rdt.hip) and vt_adamw8_ema_multi (vt_adam8.hip).  Contraction is switched off in the element functions so that all
 // of their users round identically: a replayed graph and the eager step, the EMA-only launch and the per-tensor one, and the 8-bit step's
 // fp32 tensors and the 32-bit step, then agree bit for bit.
 #pragma once

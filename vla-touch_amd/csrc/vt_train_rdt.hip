@@ -5,7 +5,8 @@
 //   * RMSNorm / per-head RMSNorm backward in both timm forms (vt_rownorm modes 1 and 2),
 //   * tanh-GELU / SiLU and their derivatives on libm functions (gradients are not the place for the ~1 ulp shortcuts of the epilogues),
 //   * the DDPM forward process written into the state ‖ noisy-action ‖ mask token layout, the sinusoidal timestep embedding,
-//   * global-norm gradient clipping over the multi-tensor table vt_adamw_ema_multi reads,
+//   * global-norm gradient clipping over the multi-tensor table vt_adamw_ema_multi reads, gradient accumulation into that table and the bf16
+//     pack / unpack of the data-parallel gradient exchange,
 //   * a zero-padding transpose (the weight-gradient products reduce over the token count, which vt_gemm wants as a multiple of 4 / 8),
 //   * dtype-typed column sum / add / column copy for the bf16 mode (the helpers of vt_train.hip are fp32 only).
 // A wave owns one query row (dQ) or one key row (dK, dV) with lane = head-dim element (head_dim 64 = the wave width), so every sum has a
@@ -357,6 +358,73 @@ __global__ __launch_bounds__(256) void grad_accum_mt_kernel(const MtEntry* __res
   }
   for (int i = quads * 4 + threadIdx.x; i < cnt; i += 256) acc[i] = accumulate ? fmaf(g[i], scale, acc[i]) : g[i] * scale;
 }
+// ------------------------------------------------------------------------------------------------ bf16 gradient exchange
+// Data-parallel fine-tuning with comm_dtype="bf16": the window's last fold and the rounding for the exchange in one pass, and the way back.
+// comm is one bf16 buffer of total_chunks * MT_CHUNK elements laid out as the table implies: tensor i starts at first_chunk_i * MT_CHUNK, so
+// a block's chunk of comm starts 8 KiB-aligned whatever the tensors' own alignment.
+// bf16 bits of v, round-to-nearest-even, every NaN as the one quiet NaN 0x7FC0 (what torch's .to(bfloat16) gives)
+__device__ __forceinline__ uint32_t bf16_rne_bits(float v) { return v != v ? 0x7FC0u : (uint32_t)f2bf(v); }
+__device__ __forceinline__ uint2 bf16_rne_quad(float4 a) {
+  return make_uint2(bf16_rne_bits(a.x) | (bf16_rne_bits(a.y) << 16), bf16_rne_bits(a.z) | (bf16_rne_bits(a.w) << 16));
+}
+// comm[first_chunk * MT_CHUNK + e] = bf16_rne of the value grad_accum_mt_kernel would have stored (the same expressions: g * scale, or
+// fma(g, scale, acc)); the accumulator is read in add mode and never written.  The rest of a tensor's last chunk is written as zeros, so the
+// whole buffer is defined and a sum over it is too.  Aligned tensors: one float4 (two in add mode) in, one 8-byte store out per thread and pass.
+__global__ __launch_bounds__(256) void grad_fold_pack_mt_kernel(const MtEntry* __restrict__ tab, const float* const* __restrict__ fresh, int ntensors,
+                                                                float scale, int accumulate, bf16_t* __restrict__ comm) {
+  const long chunk = blockIdx.x;
+  const int row = mt_find(tab, ntensors, chunk);
+  const MtEntry e = tab[row];
+  const long base = (chunk - e.first_chunk) * MT_CHUNK;
+  const long left = e.n - base;
+  const int cnt = left < MT_CHUNK ? (int)left : MT_CHUNK;
+  const float* __restrict__ acc = e.g + base;
+  const float* __restrict__ g = fresh[row] + base;
+  bf16_t* __restrict__ out = comm + chunk * MT_CHUNK;
+  const bool aligned = ((((size_t)g) | (accumulate ? (size_t)acc : 0)) & 15) == 0;
+  const int quads = aligned ? cnt >> 2 : 0;
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    const int j = it * 256 + threadIdx.x;
+    if (j >= quads) break;
+    const float4 gv = reinterpret_cast<const float4*>(g)[j];
+    float4 a;
+    if (accumulate) {
+      a = reinterpret_cast<const float4*>(acc)[j];
+      a.x = fmaf(gv.x, scale, a.x); a.y = fmaf(gv.y, scale, a.y); a.z = fmaf(gv.z, scale, a.z); a.w = fmaf(gv.w, scale, a.w);
+    } else {
+      a.x = gv.x * scale; a.y = gv.y * scale; a.z = gv.z * scale; a.w = gv.w * scale;
+    }
+    reinterpret_cast<uint2*>(out)[j] = bf16_rne_quad(a);
+  }
+  for (int i = quads * 4 + threadIdx.x; i < cnt; i += 256) out[i] = (bf16_t)bf16_rne_bits(accumulate ? fmaf(g[i], scale, acc[i]) : g[i] * scale);
+  if (cnt < MT_CHUNK) {                                          // the padding behind the tensor's last element
+    const int z0 = (cnt + 3) & ~3;
+    for (int i = cnt + threadIdx.x; i < z0; i += 256) out[i] = 0;
+    for (int j = (z0 >> 2) + threadIdx.x; j < MT_CHUNK / 4; j += 256) reinterpret_cast<uint2*>(out)[j] = make_uint2(0u, 0u);
+  }
+}
+// acc[e] = float(comm[first_chunk * MT_CHUNK + e]) for the n real elements of every tensor; nothing else is written.
+__global__ __launch_bounds__(256) void grad_unpack_mt_kernel(const MtEntry* __restrict__ tab, int ntensors, const bf16_t* __restrict__ comm) {
+  const long chunk = blockIdx.x;
+  const MtEntry e = tab[mt_find(tab, ntensors, chunk)];
+  const long base = (chunk - e.first_chunk) * MT_CHUNK;
+  const long left = e.n - base;
+  const int cnt = left < MT_CHUNK ? (int)left : MT_CHUNK;
+  float* __restrict__ acc = e.g + base;
+  const bf16_t* __restrict__ in = comm + chunk * MT_CHUNK;
+  const int quads = (((size_t)acc) & 15) == 0 ? cnt >> 2 : 0;
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    const int j = it * 256 + threadIdx.x;
+    if (j >= quads) break;
+    const uint2 w = reinterpret_cast<const uint2*>(in)[j];
+    reinterpret_cast<float4*>(acc)[j] = make_float4(__uint_as_float(w.x << 16), __uint_as_float(w.x & 0xFFFF0000u), __uint_as_float(w.y << 16),
+                                                    __uint_as_float(w.y & 0xFFFF0000u));
+  }
+  for (int i = quads * 4 + threadIdx.x; i < cnt; i += 256) acc[i] = bf2f(in[i]);
+}
+
 // EMAModel.step alone over the table (the micro-batches that take no optimizer step): shadow -= (1 - decay) (shadow - p) by vt_optim.h's
 // ema_elem, so it gives the bits of vt_ema_update_dev per tensor.  hyper[3] = 1 - decay.
 __global__ __launch_bounds__(256) void ema_mt_kernel(const MtEntry* __restrict__ tab, int ntensors, const float* __restrict__ hyper) {
@@ -512,6 +580,20 @@ int vt_grad_accum_multi(const void* table, const void* fresh, int ntensors, long
   if (!table || !fresh || ntensors < 1 || total_chunks < 1 || !(scale > 0.f)) return vt_fail(VT_ERR_ARG, "vt_grad_accum_multi: bad argument");
   hipLaunchKernelGGL(grad_accum_mt_kernel, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)s, (const MtEntry*)table, (const float* const*)fresh, ntensors,
                      scale, accumulate);
+  return LAUNCH_OK();
+}
+int vt_grad_fold_pack_multi(const void* table, const void* fresh, int ntensors, long total_chunks, float scale, int accumulate, void* comm_bf16,
+                            vt_stream_t s) {
+  if (!table || !fresh || !comm_bf16 || ntensors < 1 || total_chunks < 1 || !(scale > 0.f)) return vt_fail(VT_ERR_ARG, "vt_grad_fold_pack_multi: bad argument");
+  if (((size_t)comm_bf16) & 15) return vt_fail(VT_ERR_ARG, "vt_grad_fold_pack_multi: comm_bf16 must be 16-byte aligned");
+  hipLaunchKernelGGL(grad_fold_pack_mt_kernel, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)s, (const MtEntry*)table, (const float* const*)fresh,
+                     ntensors, scale, accumulate, (bf16_t*)comm_bf16);
+  return LAUNCH_OK();
+}
+int vt_grad_unpack_multi(const void* table, const void* comm_bf16, int ntensors, long total_chunks, vt_stream_t s) {
+  if (!table || !comm_bf16 || ntensors < 1 || total_chunks < 1) return vt_fail(VT_ERR_ARG, "vt_grad_unpack_multi: bad argument");
+  if (((size_t)comm_bf16) & 15) return vt_fail(VT_ERR_ARG, "vt_grad_unpack_multi: comm_bf16 must be 16-byte aligned");
+  hipLaunchKernelGGL(grad_unpack_mt_kernel, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)s, (const MtEntry*)table, ntensors, (const bf16_t*)comm_bf16);
   return LAUNCH_OK();
 }
 int vt_ema_multi(const void* table, int ntensors, long total_chunks, const float* hyper, vt_stream_t s) {

@@ -298,6 +298,8 @@ SIGNATURES = {
     "vt_mse_loss": (_I, [_P, _P, _P, _P, _L, _I, _P]),
     "vt_grad_accum_multi": (_I, [_P, _P, _I, _L, _F, _I, _P]),
     "vt_ema_multi": (_I, [_P, _I, _L, _P, _P]),
+    "vt_grad_fold_pack_multi": (_I, [_P, _P, _I, _L, _F, _I, _P, _P]),
+    "vt_grad_unpack_multi": (_I, [_P, _P, _I, _L, _P]),
     "vt_adamw8_ema_multi": (_I, [_P, _P, _P, _I, _L, _P, _F, _F, _F, _F, _P]),
     "vt_adam8_quantize": (_I, [_P, _P, _P, _P, _I, _L, _P]),
     "vt_adam8_dequantize": (_I, [_P, _P, _P, _I, _P, _L, _P]),

@@ -19,21 +19,21 @@ def shard_range(n_items: int, rank: int, world: int):
     return start, start + base + (1 if rank < rem else 0)
 
 
-def broadcast_tensors(tensors: Iterable[torch.Tensor], src: int = 0, bucket_bytes: int = 256 << 20) -> int:
-    """In-place broadcast of a list of tensors from `src`; small tensors are coalesced into flat buckets so the
-    transfer is a few large messages (xGMI links are per-peer, large messages amortise the ring latency)."""
+def broadcast_tensors(tensors: Iterable[torch.Tensor], src: int = 0, bucket_bytes: int = 256 << 20, group=None) -> int:
+    """In-place broadcast of a list of tensors from `src` (a global rank) over `group` (None = the default group); small tensors are
+    coalesced into flat buckets so the transfer is a few large messages (xGMI links are per-peer, large messages amortise the ring latency)."""
     import torch.distributed as dist
     total = 0
     by_key = {}
-    host_staged = dist.get_backend() == "gloo"     # gloo moves device tensors through host memory: do it explicitly, once per bucket
+    host_staged = dist.get_backend(group) == "gloo"     # gloo moves device tensors through host memory: do it explicitly, once per bucket
 
     def bcast(t: torch.Tensor):
         if host_staged and t.is_cuda:
             h = t.cpu()
-            dist.broadcast(h, src)
+            dist.broadcast(h, src, group=group)
             t.copy_(h)
         else:
-            dist.broadcast(t, src)
+            dist.broadcast(t, src, group=group)
     for t in tensors:
         if t is None:
             continue
@@ -66,6 +66,32 @@ def broadcast_tensors(tensors: Iterable[torch.Tensor], src: int = 0, bucket_byte
             size += nb
         flush()
     return total
+
+
+def all_reduce_sum_(t: torch.Tensor, group=None) -> torch.Tensor:
+    """In-place sum of a contiguous tensor over the ranks of `group`.  RCCL ("nccl") takes the device buffer as it is, ordered with the
+    current stream; gloo gets a host copy (as in broadcast_tensors) and adds in the tensor's own dtype, bf16 included."""
+    import torch.distributed as dist
+    if t.is_cuda and dist.get_backend(group) == "gloo":
+        h = t.cpu()
+        dist.all_reduce(h, op=dist.ReduceOp.SUM, group=group)
+        t.copy_(h)
+    else:
+        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+    return t
+
+
+def differing_field(fields: dict, group=None):
+    """All-gather `fields` (a small mapping of plain values, the same keys on every rank) -> the first key whose value is not the same on all
+    ranks with the ranks' values, or None.  Every rank gets the same answer, so every rank can raise."""
+    import torch.distributed as dist
+    got = [None] * dist.get_world_size(group)
+    dist.all_gather_object(got, fields, group=group)
+    for key in fields:
+        vals = [g.get(key) for g in got]
+        if any(v != vals[0] for v in vals[1:]):
+            return key, vals
+    return None
 
 
 def controller_weight_tensors(ctrl) -> List[torch.Tensor]:

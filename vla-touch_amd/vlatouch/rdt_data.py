@@ -395,8 +395,23 @@ class EpisodeStore:
         out["jitter"] = [list(p.jitter) for p in plans] if any(j is not None for p in plans for j in p.jitter) else None
         return out
 
-    def batches(self, batch_size: int, **draw_kwargs) -> Iterator[dict]:
-        """An endless iterator of micro-batches: draw(batch_size, **draw_kwargs) then assemble.  A sample loader is the same call with
-        cond_mask_prob=0, state_noise_snr=None, image_aug=False."""
+    def plan_batches(self, batch_size: int, rank: int = 0, world_size: int = 1, **draw_kwargs) -> Iterator[List[SamplePlan]]:
+        """The plans of `batches`, on the host: an endless iterator of draw(batch_size, **draw_kwargs).  With world_size = W > 1 it yields
+        micro-batches rank, rank + W, ... of that one-process stream (the round-robin of accelerate's default batch sharding): the other
+        ranks' decisions are drawn, so that every rank's random streams stay those of the one-process run, and dropped.  The ranks must
+        seed np_rng, rng and the generator alike."""
+        if int(world_size) != world_size or world_size < 1 or int(rank) != rank or not 0 <= rank < world_size:
+            raise ValueError(f"plan_batches: rank must be in [0, world_size), got rank={rank!r}, world_size={world_size!r}")
+        i = 0
         while True:
-            yield self.assemble(self.draw(batch_size, **draw_kwargs))
+            plans = self.draw(batch_size, **draw_kwargs)
+            if i % world_size == rank:
+                yield plans
+            i += 1
+
+    def batches(self, batch_size: int, rank: int = 0, world_size: int = 1, **draw_kwargs) -> Iterator[dict]:
+        """An endless iterator of micro-batches: plan_batches(batch_size, rank, world_size, **draw_kwargs) then assemble, which only this
+        rank's micro-batches reach.  A W-rank run with gradient_accumulation_steps k so consumes exactly the samples of a one-rank run with
+        k W.  A sample loader is the same call with cond_mask_prob=0, state_noise_snr=None, image_aug=False."""
+        for plans in self.plan_batches(batch_size, rank, world_size, **draw_kwargs):
+            yield self.assemble(plans)

@@ -15,6 +15,11 @@ FFN pre-activations); the image K / V of the odd blocks are kept, not recomputed
 `precision="fp32"` is the parity mode.  `precision="bf16"` is the reference's execution dtype: bf16 copies of the Linear weights (and of their
 transposes) refreshed after each optimizer step, bf16 activations, activation gradients and MFMA operands, fp32 accumulators, fp32 master
 weights / gradients / moments / EMA (what DeepSpeed's bf16 mode keeps); norm gains, biases and position embeddings are read in fp32.
+
+Data parallelism (`process_group=`; the reference's `accelerate launch` with DeepSpeed ZeRO-2, finetune.sh) replicates all state: every rank
+folds its micro-batches, scaled by 1 / (k W), into one fp32 gradient arena laid out as the multi-tensor table implies, the arena is summed over
+the ranks once per optimizer step (fp32, or bf16 through vt_grad_fold_pack_multi / vt_grad_unpack_multi), and clip, AdamW and EMA then run
+identically everywhere.  Nothing is sharded and the all-reduce is not overlapped with the backward.
 """
 from __future__ import annotations
 
@@ -37,6 +42,7 @@ F32 = torch.float32
 LR_SCHEDULERS = ("constant", "constant_with_warmup")
 PREDICTION_TYPES = ("sample", "epsilon")
 OPTIMIZERS = ("adamw", "adamw8bit")
+COMM_DTYPES = ("fp32", "bf16")
 
 
 # ---------------------------------------------------------------------------------------------- host-side schedules
@@ -290,13 +296,23 @@ class RdtTrainer:
     adam8.MIN_8BIT_SIZE elements as uint8 codes with one fp32 scale per 256 elements (vlatouch/adam8.py, csrc/vt_adam8.hip; DESIGN.md §8 states
     the arithmetic, UNPINNED against bitsandbytes); smaller tensors keep fp32 moments and the bits of the default step.  Either way the moments
     live in one store, `opt_state` (Moments32 or adam8.Moments8: zero state, table columns, the AdamW + EMA launch, checkpoint files, byte count);
-    `moments(name)` reads them as fp32."""
+    `moments(name)` reads them as fp32.
+
+    process_group: a torch.distributed group of W ranks, one process per GPU, for data-parallel training with replicated state (None, the
+    default, is the one-process trainer: same launches, same bits).  The constructor is then collective: the ranks compare parameter names and
+    shapes, gradient_accumulation_steps, precision, optimizer, comm_dtype and attention_backward, every rank raising ValueError with the
+    differing field if they disagree, and rank 0's master parameters are broadcast.  For any k the accumulators are views into one fp32
+    arena (tensor i at first_chunk_i * MT_CHUNK, padding zeroed once); `accumulate` folds with scale 1 / (k W) and, after the window's last
+    fold, sums the arena over the ranks in chunk-aligned slices of at most `comm_bucket_bytes`; comm_dtype="bf16" (an exchange format, allowed
+    with either precision) sends bf16 instead, through vt_grad_fold_pack_multi and vt_grad_unpack_multi.  `load_checkpoint` is called on every
+    rank; `save_checkpoint` is an ordinary call (`finetune` makes it on rank 0)."""
 
     def __init__(self, sd, *, heads: int, horizon: int, action_dim: int, rms_mode: str = "meansq", prediction_type: str = "sample",
                  num_train_timesteps: int = 1000, beta_schedule: str = "squaredcos_cap_v2", precision: str = "fp32", lr: float = 5e-6,
                  betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, max_grad_norm: float = 1.0, lr_scheduler: str = "constant",
                  lr_warmup_steps: int = 500, ema: Optional[dict] = None, config: Optional[dict] = None, gradient_accumulation_steps: int = 1,
-                 optimizer: str = "adamw", attention_backward: str = "wave", device="cuda"):
+                 optimizer: str = "adamw", attention_backward: str = "wave", process_group=None, comm_dtype: str = "fp32",
+                 comm_bucket_bytes: int = 256 << 20, device="cuda"):
         if precision not in ("fp32", "bf16"):
             raise ValueError(f"precision must be 'fp32' or 'bf16', got {precision!r} (no fp16 training mode: its gradients underflow without loss scaling)")
         if prediction_type not in PREDICTION_TYPES:
@@ -311,12 +327,34 @@ class RdtTrainer:
             raise ValueError("attention_backward='mfma' is a bf16 kernel: it needs precision='bf16' ('wave' is the fp32 path)")
         if attention_backward == "mfma" and horizon + 3 > 128:
             raise ValueError(f"attention_backward='mfma' holds at most 128 query rows, horizon + 3 = {horizon + 3}")
+        if comm_dtype not in COMM_DTYPES:
+            raise ValueError(f"comm_dtype must be one of {COMM_DTYPES}, got {comm_dtype!r} (the format of the gradient exchange, whatever the precision)")
+        if int(comm_bucket_bytes) != comm_bucket_bytes or comm_bucket_bytes < 1:
+            raise ValueError(f"comm_bucket_bytes must be an integer >= 1, got {comm_bucket_bytes!r}")
         lr_at(lr, lr_scheduler, 0, lr_warmup_steps)                       # raises on an unknown scheduler
         if int(gradient_accumulation_steps) != gradient_accumulation_steps or gradient_accumulation_steps < 1:
             raise ValueError(f"gradient_accumulation_steps must be an integer >= 1, got {gradient_accumulation_steps!r}")
         self.device = dev = L.require_gpu(device)
         self.p: "OrderedDict[str, torch.Tensor]" = OrderedDict((k, v.detach().to(dev, F32).contiguous().clone()) for k, v in sd.items())
         self.g: Dict[str, torch.Tensor] = {}
+        # data parallelism: None is the one-process trainer.  With a group the ranks first agree on what must be the same everywhere, then
+        # rank 0's master parameters replace everyone's; from there on all state is replicated and only gradients travel.
+        self.group, self.world, self.rank = process_group, 1, 0
+        self.comm_dtype, self.comm_bucket_bytes = comm_dtype, int(comm_bucket_bytes)
+        self._arena: Optional[torch.Tensor] = None            # grouped: the fp32 buffer the accumulators are views of
+        self._comm: Optional[torch.Tensor] = None             # grouped, comm_dtype="bf16": the persistent bf16 exchange buffer
+        if process_group is not None:
+            import hashlib
+            import torch.distributed as dist
+            from . import dist as D
+            self.world, self.rank = dist.get_world_size(process_group), dist.get_rank(process_group)
+            digest = hashlib.sha256(repr([(k, tuple(v.shape)) for k, v in self.p.items()]).encode()).hexdigest()
+            diff = D.differing_field({"parameter names and shapes": digest, "gradient_accumulation_steps": int(gradient_accumulation_steps),
+                                      "precision": precision, "optimizer": optimizer, "comm_dtype": comm_dtype,
+                                      "attention_backward": attention_backward}, process_group)
+            if diff is not None:
+                raise ValueError(f"RdtTrainer: the ranks of the process group disagree on {diff[0]}: {diff[1]}")
+            D.broadcast_tensors(self.p.values(), src=dist.get_global_rank(process_group, 0), group=process_group)
         self.depth = 0
         while f"model.blocks.{self.depth}.norm1.weight" in self.p:
             self.depth += 1
@@ -347,7 +385,7 @@ class RdtTrainer:
         self.ema_updates = 0                                  # EMAModel.optimization_step: one per micro-batch
         self.micro_step = 0                                   # micro-batches folded into the open accumulation window
         self.sync_gradients = False                           # the last train_step took the optimizer step
-        self._acc: Dict[str, torch.Tensor] = {}               # k > 1: persistent fp32 accumulators, the table's g column
+        self._acc: Dict[str, torch.Tensor] = {}               # k > 1 or grouped: persistent fp32 accumulators, the table's g column
         self.optimizer = optimizer                            # AdamW moments and the EMA copy appear with the first optimizer step (the parameters are
         shapes = OrderedDict((k, v.shape) for k, v in self.p.items())     # still the initial ones then), so a trainer that only evaluates the loss holds one copy
         self.opt_state = adam8.Moments8(shapes, dev) if optimizer == "adamw8bit" else Moments32(shapes, dev)
@@ -614,12 +652,14 @@ class RdtTrainer:
 
     def _table(self):
         """The multi-tensor table every optimizer launch reads (train.mt_table: {p, g, m, v, shadow, n, first_chunk} per tensor), on the device."""
+        if self.group is not None and not self._acc:
+            self._alloc_arena()
         if self.k > 1 and not self._acc:
             self._acc = {k: torch.empty_like(v) for k, v in self.p.items()}          # never read before the window's first, storing, accumulate
         if not self.shadow:
             self.opt_state.zero()
             self.shadow = {k: v.clone() for k, v in self.p.items()}
-        g = self._acc if self.k > 1 else {name: self._fresh_grad(name) for name in self.p}
+        g = self._acc if self._accumulates else {name: self._fresh_grad(name) for name in self.p}
         key = tuple(t.data_ptr() for t in g.values())
         if key != self._table_key:                                # gradients are fresh allocations each step: their addresses usually repeat, not always
                                                                   # (k > 1: the g column holds the accumulators, so the table is built once)
@@ -630,11 +670,37 @@ class RdtTrainer:
             self._table_key, self._chunks = key, chunks
         return self._mt_dev, len(self.p), self._chunks
 
+    @property
+    def _accumulates(self) -> bool:
+        """The table's g column holds persistent accumulators (k > 1, or any k with a process group) and not the fresh gradients."""
+        return self.k > 1 or self.group is not None
+
+    def _alloc_arena(self) -> None:
+        """Grouped: the accumulators as views into one fp32 buffer of total_chunks * MT_CHUNK elements, tensor i at first_chunk_i * MT_CHUNK
+        (the layout train.mt_table gives the rows, in the parameters' order), so that the exchange is a few large chunk-aligned messages.
+        The padding behind each tensor's last element is zeroed here, once; no kernel writes it."""
+        chunks = sum((v.numel() + T.MT_CHUNK - 1) // T.MT_CHUNK for v in self.p.values())
+        self._arena = torch.zeros(chunks * T.MT_CHUNK, dtype=F32, device=self.device)
+        if self.comm_dtype == "bf16":
+            self._comm = torch.zeros(chunks * T.MT_CHUNK, dtype=torch.bfloat16, device=self.device)
+        off = 0
+        for k, v in self.p.items():
+            self._acc[k] = self._arena[off:off + v.numel()].view(v.shape)
+            off += (v.numel() + T.MT_CHUNK - 1) // T.MT_CHUNK * T.MT_CHUNK
+
+    def _all_reduce(self, buf: torch.Tensor) -> None:
+        """Sum `buf` (the arena or the bf16 buffer) over the ranks in chunk-aligned slices of at most comm_bucket_bytes, in order, on the
+        current stream."""
+        from . import dist as D
+        step = max(1, self.comm_bucket_bytes // (T.MT_CHUNK * buf.element_size())) * T.MT_CHUNK
+        for off in range(0, buf.numel(), step):
+            D.all_reduce_sum_(buf[off:off + step], self.group)
+
     def optimizer_step(self, hyper: Optional[torch.Tensor] = None):
         """clip_grad_norm_(max_grad_norm) -> AdamW -> EMA (train.py:440-448), three launches over one table; no host read."""
         if hyper is not None:
             raise NotImplementedError("RdtTrainer: hipGraph capture of the step is not built")
-        if self.k > 1 and self.micro_step != self.k:
+        if self._accumulates and self.micro_step != self.k:
             raise RuntimeError(f"optimizer_step needs a full accumulation window ({self.micro_step} of {self.k} micro-batches accumulated)")
         tab, n, chunks = self._table()
         self.lr = lr_at(self.base_lr, self.lr_scheduler, self.step_count, self.lr_warmup_steps * self.k)      # train.py:302 scales the warm-up by k
@@ -663,15 +729,27 @@ class RdtTrainer:
 
     def accumulate(self) -> None:
         """k > 1: fold the gradients get_loss left in `self.g` into the accumulators, scaled by 1 / k (accelerator.backward's loss / k); the
-        first micro-batch of a window stores, the others add.  One launch; the fresh gradients' addresses travel as a second device array."""
-        if self.k == 1:
+        first micro-batch of a window stores, the others add.  One launch; the fresh gradients' addresses travel as a second device array.
+        With a process group of W ranks (any k) the scale is 1 / (k W) and the window's last fold is followed by the sum over the ranks, so
+        that the accumulators then hold the mean gradient of all k W micro-batches on every rank: comm_dtype="fp32" all-reduces the arena;
+        "bf16" folds and rounds into the bf16 buffer in one launch (vt_grad_fold_pack_multi), all-reduces that and widens it back into the
+        accumulators (vt_grad_unpack_multi).  The earlier micro-batches of a window call no collective."""
+        if not self._accumulates:
             raise RuntimeError("accumulate: the trainer was built with gradient_accumulation_steps=1")
         if self.micro_step >= self.k:
             raise RuntimeError("accumulate: the window is full, call optimizer_step")
         tab, n, chunks = self._table()
         fresh = torch.tensor([self._fresh_grad(name).data_ptr() for name in self.p], dtype=torch.int64).to(self.device)
-        L.check(L.lib().vt_grad_accum_multi(L.ptr(tab), L.ptr(fresh), n, chunks, 1.0 / self.k, int(self.micro_step > 0), _sp(self.device)),
-                "vt_grad_accum_multi")
+        scale, add, last = 1.0 / (self.k * self.world), int(self.micro_step > 0), self.micro_step == self.k - 1
+        if self.group is not None and last and self.comm_dtype == "bf16":
+            L.check(L.lib().vt_grad_fold_pack_multi(L.ptr(tab), L.ptr(fresh), n, chunks, scale, add, L.ptr(self._comm), _sp(self.device)),
+                    "vt_grad_fold_pack_multi")
+            self._all_reduce(self._comm)
+            L.check(L.lib().vt_grad_unpack_multi(L.ptr(tab), L.ptr(self._comm), n, chunks, _sp(self.device)), "vt_grad_unpack_multi")
+        else:
+            L.check(L.lib().vt_grad_accum_multi(L.ptr(tab), L.ptr(fresh), n, chunks, scale, add, _sp(self.device)), "vt_grad_accum_multi")
+            if self.group is not None and last:
+                self._all_reduce(self._arena)
         self.micro_step += 1
 
     def ema_step(self) -> None:
@@ -689,7 +767,7 @@ class RdtTrainer:
         if timesteps is None:
             timesteps = torch.randint(0, self.num_train_timesteps, (B,), device=self.device)
         loss = self.get_loss(lang_tokens, lang_attn_mask, img_tokens, state_tokens, action_gt, action_mask, ctrl_freqs, noise=noise, timesteps=timesteps)
-        if self.k == 1:
+        if not self._accumulates:
             self.optimizer_step()
             return loss
         self.accumulate()
@@ -701,7 +779,7 @@ class RdtTrainer:
 
     # ---- state
     def grads(self):
-        src = self._acc if self.k > 1 else self.g
+        src = self._acc if self._accumulates else self.g
         return OrderedDict((k, src[k].detach().cpu().reshape(self.p[k].shape)) for k in self.p)
 
     def state_dict(self):
@@ -760,7 +838,8 @@ class RdtTrainer:
     def save_checkpoint(self, path: str) -> None:
         """`path`/checkpoint/{model,adam_m,adam_v}.safetensors (fp32 master weights and AdamW moments), `path`/ema/ (the averaged weights as
         RDTRunner.from_pretrained reads them: the reference's checkpoint-N/ema placement) and `path`/trainer_state.json (the counters, k,
-        precision, hyper-parameters).  Only between accumulation windows, where the reference saves.  optimizer="adamw8bit" writes
+        precision, hyper-parameters, and for information `world_size` and `comm_dtype`: all state is replicated, so a checkpoint resumes under any
+        world size).  Only between accumulation windows, where the reference saves.  optimizer="adamw8bit" writes
         checkpoint/adam8.safetensors in place of adam_m / adam_v (codes `m8.` / `v8.` and scales `am.` / `av.` + parameter name, fp32 moments
         `m.` / `v.` of the small tensors, the two code tables) and adds `optimizer` and `block` to trainer_state.json."""
         if self.micro_step != 0:
@@ -776,7 +855,8 @@ class RdtTrainer:
             with open(os.path.join(path, "ema", "config.json"), "w") as fjs:
                 json.dump(self.config, fjs, indent=2)
         state = dict(step_count=self.step_count, ema_updates=self.ema_updates, global_step=self.global_step, gradient_accumulation_steps=self.k,
-                     precision=self.precision, hyper={n: getattr(self, n) for n in self._HYPER}, **self.opt_state.state_json)
+                     precision=self.precision, hyper={n: getattr(self, n) for n in self._HYPER}, world_size=self.world, comm_dtype=self.comm_dtype,
+                     **self.opt_state.state_json)
         with open(os.path.join(path, "trainer_state.json"), "w") as fjs:
             json.dump(state, fjs, indent=2)
 
@@ -870,7 +950,7 @@ def prepare_batch(batch, *, vision_encoder=None, text_encoder=None, preprocessor
 
 
 def sample_eval(runner, batches, *, num_sample_batches: int, dataset_id2name, vision_encoder=None, text_encoder=None, return_raw: bool = False,
-                preprocessor=None):
+                preprocessor=None, group=None):
     """`log_sample_res` (train/sample.py:7-98): sample an action chunk with `runner.predict_action` for the first `num_sample_batches` items of
     `batches` and report, per dataset and overall, the masked MSE and the masked, state-norm-relative L2 error against the ground truth.
 
@@ -884,7 +964,29 @@ def sample_eval(runner, batches, *, num_sample_batches: int, dataset_id2name, vi
     One vt_sample_metrics launch per batch adds into sums on the device; they are read once, after the last batch.  -> the reference's dict:
     `<name>_sample_mse` / `<name>_sample_l2err` = mean over that dataset's samples, for the datasets that occurred, and
     `overall_avg_sample_mse` / `overall_avg_sample_l2err` = sum of the batches' overall values / num_sample_batches (also when `batches` ends
-    early, as there), all rounded to 4 decimals.  return_raw=True: (that dict, the same keys unrounded)."""
+    early, as there), all rounded to 4 decimals.  return_raw=True: (that dict, the same keys unrounded).
+
+    group: a process group of W ranks, each evaluating its own `num_sample_batches` items.  The device-resident sums and counts are
+    all-reduced once, a dataset's sums are divided by its sample count over all ranks and the overall pair by num_sample_batches * W
+    (`accelerator.gather(...).mean()`, sample.py:80-85); every rank returns the same dict, which names the datasets any rank saw."""
+    acc, count, keys = sample_eval_sums(runner, batches, num_sample_batches=num_sample_batches, dataset_id2name=dataset_id2name,
+                                        vision_encoder=vision_encoder, text_encoder=text_encoder, preprocessor=preprocessor, group=group)
+    if acc is None:                                                      # no batch: the reference returns an empty dict
+        return ({}, {}) if return_raw else {}
+    world = 1
+    if group is not None:
+        import torch.distributed as dist
+        world = dist.get_world_size(group)
+    raw = sample_eval_means(acc, count, keys, num_sample_batches * world)
+    metrics = {name: round(v, 4) for name, v in raw.items()}
+    return (metrics, raw) if return_raw else metrics
+
+
+def sample_eval_sums(runner, batches, *, num_sample_batches: int, dataset_id2name, vision_encoder=None, text_encoder=None, preprocessor=None,
+                     group=None):
+    """The sums behind `sample_eval` (its arguments): -> (acc [n + 1, 2] fp64: per dataset row, and overall in the last row, the summed MSE and
+    L2 error; count [n + 1] int32: the samples per row; keys: result key -> (row, column)), all on the host, or (None, None, {}) when there
+    was no batch and no group.  With a group the sums and counts are those of all ranks."""
     ids = list(dataset_id2name.keys()) if hasattr(dataset_id2name, "keys") else list(range(len(dataset_id2name)))
     if not ids:
         raise ValueError("sample_eval: dataset_id2name is empty")
@@ -930,12 +1032,26 @@ def sample_eval(runner, batches, *, num_sample_batches: int, dataset_id2name, vi
                 keys.setdefault(dataset_id2name[i] + suffix, (row_of[i], col))
         keys.setdefault("overall_avg_sample_mse", (n, 0))
         keys.setdefault("overall_avg_sample_l2err", (n, 1))
-    if state is None:                                                    # no batch: the reference returns an empty dict
-        return ({}, {}) if return_raw else {}
+    if group is not None:
+        from . import dist as D
+        if state is None:                                                # this rank had no batch: it still takes part in the sum
+            dev = L.require_gpu(runner.device)
+            state = torch.zeros(2 * (n + 1) + (n + 2) // 2, dtype=torch.float64, device=dev)
+            acc, count = state[:2 * (n + 1)], state[2 * (n + 1):].view(torch.int32)
+        both = D.all_reduce_sum_(torch.cat([acc, count[:n + 1].to(torch.float64)]), group).cpu()      # counts are exact in fp64; one collective
+        acc_h, count_h = both[:2 * (n + 1)].view(n + 1, 2), both[2 * (n + 1):].to(torch.int32)
+        for col, suffix in enumerate(("_sample_mse", "_sample_l2err")):   # the datasets only other ranks saw
+            for i in ids:
+                if int(count_h[row_of[i]]) > 0:
+                    keys.setdefault(dataset_id2name[i] + suffix, (row_of[i], col))
+        if int(count_h[:n].sum()) > 0:
+            keys.setdefault("overall_avg_sample_mse", (n, 0))
+            keys.setdefault("overall_avg_sample_l2err", (n, 1))
+        return acc_h, count_h, keys
+    if state is None:
+        return None, None, keys
     host = state.cpu()                                                   # the evaluation's one device read
-    raw = sample_eval_means(host[:2 * (n + 1)].view(n + 1, 2), host[2 * (n + 1):].view(torch.int32), keys, num_sample_batches)
-    metrics = {name: round(v, 4) for name, v in raw.items()}
-    return (metrics, raw) if return_raw else metrics
+    return host[:2 * (n + 1)].view(n + 1, 2), host[2 * (n + 1):].view(torch.int32)[:n + 1], keys
 
 
 def sample_eval_means(acc, count, keys, num_sample_batches: int) -> dict:
@@ -956,7 +1072,17 @@ def finetune(trainer: RdtTrainer, batches, *, max_train_steps: int, checkpointin
     not skip the batches an earlier run consumed: `batches` continues where the caller wants.  sample_period > 0: after every optimizer step with
     global_step % sample_period == 0, and after that step's checkpoint (train.py:455-475), `sample_eval` runs on `trainer.sampler(ema=sample_ema)`
     over `sample_batches` (iterated afresh at each visit; `vision_encoder` / `text_encoder` go to it for batches with `images` / `input_ids`)
-    and `log(metrics, global_step)` is called if given; the evaluation reads the weights and writes none.  -> the micro-batch losses (device tensors)."""
+    and `log(metrics, global_step)` is called if given; the evaluation reads the weights and writes none.  -> the micro-batch losses (device tensors).
+    A trainer built with a process group: every rank runs this loop on its own micro-batches (`EpisodeStore.batches(rank=, world_size=)`); rank 0
+    alone writes the checkpoints and the final weights, with a barrier behind each write, and alone calls `log`; the sampling evaluation runs on
+    every rank and is reduced over the group (`sample_eval(group=)`); a resume loads the checkpoint on every rank."""
+    group = getattr(trainer, "group", None)
+    writer = group is None or trainer.rank == 0
+
+    def written():
+        if group is not None:
+            import torch.distributed as dist
+            dist.barrier(group=group)
     if (checkpointing_period or resume_from_checkpoint) and output_dir is None:
         raise ValueError("finetune: checkpointing_period / resume_from_checkpoint need output_dir")
     if sample_period is not None and sample_period > 0 and (sample_batches is None or dataset_id2name is None):
@@ -973,15 +1099,20 @@ def finetune(trainer: RdtTrainer, batches, *, max_train_steps: int, checkpointin
             batch = prepare_batch(batch, vision_encoder=vision_encoder, text_encoder=text_encoder, preprocessor=preprocessor)
         losses.append(trainer.train_step(**batch))
         if trainer.sync_gradients and checkpointing_period and trainer.global_step % checkpointing_period == 0:
-            trainer.save_checkpoint(os.path.join(output_dir, f"checkpoint-{trainer.global_step}"))
+            if writer:
+                trainer.save_checkpoint(os.path.join(output_dir, f"checkpoint-{trainer.global_step}"))
+            written()
         if trainer.sync_gradients and sample_period is not None and sample_period > 0 and trainer.global_step % sample_period == 0:
             metrics = sample_eval(trainer.sampler(ema=sample_ema), sample_batches, num_sample_batches=num_sample_batches,
-                                  dataset_id2name=dataset_id2name, vision_encoder=vision_encoder, text_encoder=text_encoder, preprocessor=preprocessor)
-            if log is not None:
+                                  dataset_id2name=dataset_id2name, vision_encoder=vision_encoder, text_encoder=text_encoder, preprocessor=preprocessor,
+                                  group=group)
+            if log is not None and writer:
                 log(metrics, trainer.global_step)
     if output_dir is not None:
         if trainer.micro_step != 0:
             raise RuntimeError("finetune: the batches ended in the middle of an accumulation window")
-        trainer.save_pretrained(output_dir)
-        trainer.save_pretrained(os.path.join(output_dir, "ema"), ema=True)
+        if writer:
+            trainer.save_pretrained(output_dir)
+            trainer.save_pretrained(os.path.join(output_dir, "ema"), ema=True)
+        written()
     return losses
