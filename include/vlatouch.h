@@ -436,9 +436,15 @@ int vt_mse_residual(const float* base, const float* delta, const float* target, 
  * vt_grad_clip_multi: torch.nn.utils.clip_grad_norm_ over the table of vt_adamw_ema_multi: chunk_part [total_chunks] scratch,
  *   norm_coef[0] = the global L2 norm of the gradients before clipping, norm_coef[1] = min(1, max_norm / (norm + 1e-6)), every gradient
  *   multiplied by it in place.  Nothing is read back by the host.
- * Activations (x, dy, dx, out, pred, a ...) are of dtype `dt` / `odt`: 0 = fp32, 1 = bf16 storage with fp32 arithmetic; gains, targets and every
- *   sum (dyxr, part, loss, norm) are fp32.
- * vt_mse_loss: F.mse_loss and its gradient: loss[0] = mean((pred - target)^2), dpred = 2 (pred - target) / n. */
+ * Activations (x, dy, dx, out, pred, a ...) are of dtype `dt` / `odt`: 0 = fp32, 1 = bf16 or 3 = fp16 storage with fp32 arithmetic and one
+ *   rounding at the store; gains, targets and every sum (dyxr, part, loss, norm) are fp32.
+ * vt_mse_loss: F.mse_loss and its gradient: loss[0] = mean((pred - target)^2), dpred = 2 (pred - target) / n.
+ * vt_mse_loss_scaled (fp16 training with a loss scale): the same loss, NOT scaled, and dpred = grad_scale * 2 (pred - target) / n rounded once.
+ * vt_grad_unscale_clip_multi: GradScaler.unscale_ followed by clip_grad_norm_ over the table whose gradients are inv_scale^-1 times too large:
+ *   found_inf[0] = 1 if any RAW gradient element is inf or NaN, else 0 (cleared by this call, set by an integer atomic); norm_coef[0] = the
+ *   L2 norm of g * inv_scale, norm_coef[1] = min(1, max_norm / (norm + 1e-6)); then, only if the flag is clear, g = (g * inv_scale) * coef as
+ *   two multiplications (torch's bits for any scale).  With the flag set no gradient is written.  The float sums have a fixed order: two calls
+ *   give the same bits.  The caller reads found_inf to decide whether the optimizer step is taken. */
 typedef struct {
   const void *Q, *K, *V, *dO;
   void *dQ, *dK, *dV;
@@ -451,7 +457,8 @@ typedef struct {
   float scale;
 } VtAttnBwdParams;
 int vt_attention_bwd(const VtAttnBwdParams* params, vt_stream_t stream);
-/* vt_attention_bwd_mfma (csrc/vt_attn_bwd.hip): the same gradients on bf16 MFMA, for bf16 operands, head_dim 64, 1 <= Nq <= 128, any Nk >= 1.
+/* vt_attention_bwd_mfma (csrc/vt_attn_bwd.hip): the same gradients on 16-bit MFMA, for bf16 or fp16 operands (dtype 1 / 3; fp16 rounds P, dS and
+ *   the results to fp16 instead, without clamping: tests/attn_bwd_mfma16_ref.py), head_dim 64, 1 <= Nq <= 128, any Nk >= 1.
  *   One rounding more than vt_attention_bwd: P and dS = P (dP - delta) are rounded to bf16 (nearest even) before they multiply dO, Q and K; the
  *   scale is applied to the fp32 sums afterwards (tests/attn_bwd_mfma_ref.py states the arithmetic).  Unit inner stride, every other stride a
  *   multiple of 8 elements, every base 16-byte aligned.  `ws` receives (max, 1 / sum, delta) as above; `ws2` (16-byte aligned, at least
@@ -470,12 +477,15 @@ int vt_ddpm_qsample(const float* state, const float* action, const float* noise,
 int vt_timestep_embed(const float* t, const float* freqs, void* out, int odt, int B, int dim, vt_stream_t stream);
 int vt_add_rowvec_(void* a, int dt, const float* v, long rows, long cols, vt_stream_t stream);
 int vt_transpose_pad(const void* in, void* out, int dt, int M, int N, int Mp, vt_stream_t stream);
-/* vt_colsum / vt_add_ / vt_copy_cols (fp32 only, above) for an activation dtype `dt` (0 fp32, 1 bf16): column sums in fp32, a += b, dst[:, doff..] = src[:, off..] */
+/* vt_colsum / vt_add_ / vt_copy_cols (fp32 only, above) for an activation dtype `dt` (0 fp32, 1 bf16, 3 fp16): column sums in fp32, a += b, dst[:, doff..] = src[:, off..] */
 int vt_colsum_dt(const void* x, int dt, long ld, float* out, int M, int N, vt_stream_t stream);
 int vt_add_dt(void* a, const void* b, long n, int dt, vt_stream_t stream);
 int vt_copy_cols_dt(const void* src, long lds, long off, void* dst, long ldd, long doff, long rows, long cols, int dt, vt_stream_t stream);
 int vt_grad_clip_multi(const void* table, int ntensors, long total_chunks, float max_norm, float* chunk_part, float* norm_coef, vt_stream_t stream);
 int vt_mse_loss(const void* pred, const float* target, void* dpred, float* loss, long n, int dt, vt_stream_t stream);
+int vt_mse_loss_scaled(const void* pred, const float* target, void* dpred, float* loss, long n, int dt, float grad_scale, vt_stream_t stream);
+int vt_grad_unscale_clip_multi(const void* table, int ntensors, long total_chunks, float max_norm, float inv_scale, float* chunk_part, float* norm_coef,
+                               int* found_inf, vt_stream_t stream);
 /* Gradient accumulation over the table of vt_adamw_ema_multi, whose g column holds the persistent fp32 accumulators.
  * vt_grad_accum_multi: fresh = device array of ntensors `const float*`, the micro-batch's gradients in table order.  accumulate = 0:
  *   acc = g * scale (the accumulator is not read); otherwise acc = fma(g, scale, acc).  scale = 1 / gradient_accumulation_steps.

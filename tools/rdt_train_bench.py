@@ -38,6 +38,11 @@ events, `--warmup` + 21 timed: vt_grad_accum_multi (the fold) and vt_grad_fold_p
 gradients, the all-reduce on itself (the arena, or the bf16 buffer, in `comm_bucket_bytes` slices), vt_grad_unpack_multi, and the whole step of
 each trainer; medians with min / max, bytes moved against the HBM roof, and whether fold + pack took no longer than the fold (medians, with the
 min - max spread of the two as the only margin).  Added to `--out` under the key `data_parallel`; the other keys stay.
+
+`--precision fp16` (with `--attention-backward mfma` and `--optimizer adamw8bit` as wanted): an fp16 trainer under dynamic loss scaling and a bf16
+trainer of the same settings alternate in one process, swapping who goes first, 3 warm-up + 21 timed steps: forward, backward, optimizer phase
+and step of each with min / max, the losses of both, the scale after every fp16 step and which steps it skipped, and by device events the
+attention-backward launches of both kernels in fp16 against bf16 at the three attention shapes.  Added to `--out` under the key `fp16`.
 """
 from __future__ import annotations
 
@@ -345,6 +350,105 @@ def attention_run(a, c, sd, params, dev, B):
     return out
 
 
+def fp16_attention_launches(a, c, B, dev):
+    """Device-event time of the attention-backward launches alone in fp16 and in bf16, "wave" and "mfma", alternating, at the trainer's packed
+    layouts and the three attention shapes of the step -> dict."""
+    from vlatouch.rdt_train import attention_bwd
+    H, N = c["heads"], c["horizon"] + 3
+    D = H * 64
+    g = torch.Generator(device=dev).manual_seed(5)
+    out = {}
+    for name, Nk, cross in (("image_cross_attention", a.img_len, True), ("language_cross_attention", a.lang_len, True), ("self_attention", N, False)):
+        views = {}
+        for dt in (torch.float16, torch.bfloat16):
+            rn = lambda *s: (0.5 * torch.randn(*s, generator=g, device=dev)).to(dt)
+            if cross:
+                qb, kvb, dqb, dkvb = rn(B, N, D), rn(B, Nk, 2 * D), torch.empty(B, N, D, device=dev, dtype=dt), torch.empty(B, Nk, 2 * D, device=dev, dtype=dt)
+                v4 = lambda q_, kv_: (q_.view(B, N, H, 64), kv_.view(B, Nk, 2, H, 64)[:, :, 0], kv_.view(B, Nk, 2, H, 64)[:, :, 1])
+                qkv3, d3 = v4(qb, kvb), v4(dqb, dkvb)
+            else:
+                qkv, dqkv = rn(B, N, 3 * D), torch.empty(B, N, 3 * D, device=dev, dtype=dt)
+                qkv3 = tuple(qkv.view(B, N, 3, H, 64)[:, :, i] for i in range(3))
+                d3 = tuple(dqkv.view(B, N, 3, H, 64)[:, :, i] for i in range(3))
+            views[dt] = (qkv3, d3, rn(B, N, H, 64))
+        km = torch.ones(B, Nk, dtype=torch.uint8, device=dev) if name == "language_cross_attention" else None
+        combos = [(dt, kind) for kind in ("mfma", "wave") for dt in (torch.float16, torch.bfloat16)]
+        ms = {cb: [] for cb in combos}
+        for n in range(2 + 7):
+            for dt, kind in (combos if n % 2 == 0 else combos[::-1]):
+                (q, k, v), (dq, dk, dv), do = views[dt]
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize(dev)
+                e0.record()
+                attention_bwd(q, k, v, do, dq, dk, dv, kmask=km, kernel=kind)
+                e1.record()
+                torch.cuda.synchronize(dev)
+                if n >= 2:
+                    ms[(dt, kind)].append(e0.elapsed_time(e1))
+        rec = {"Nq": N, "Nk": Nk}
+        for kind in ("mfma", "wave"):
+            f, b = _stats(ms[(torch.float16, kind)]), _stats(ms[(torch.bfloat16, kind)])
+            rec[kind] = {"fp16_ms": f, "bf16_ms": b, "fp16_over_bf16": f["median"] / b["median"]}
+        out[name] = rec
+    out["timing"] = "device events around one attention_bwd call (workspace allocation from the caching allocator included), 2 warm-up + 7 timed, the four (dtype, kernel) pairs alternating"
+    return out
+
+
+def fp16_run(a, c, sd, params, dev, B):
+    """The fp16 step (dynamic loss scaling) beside the bf16 step, alternating in this process at batch B, both under a.attention_backward and
+    a.optimizer -> dict with the phases, the losses and the scale trajectory."""
+    from vlatouch.rdt_train import RdtTrainer
+    steps = a.steps
+    sync = lambda: torch.cuda.synchronize(dev)
+    args, kw = inputs(a, B, dev)
+    kinds = ("fp16", "bf16")
+    trs, peak = {}, {}
+    for kind in kinds:
+        torch.cuda.empty_cache()
+        base = torch.cuda.memory_allocated(dev)
+        torch.cuda.reset_peak_memory_stats(dev)
+        extra = dict(loss_scale="dynamic") if kind == "fp16" else {}
+        tr = trs[kind] = RdtTrainer(sd, heads=c["heads"], horizon=64, action_dim=128, lr=a.lr, precision=kind, attention_backward=a.attention_backward,
+                                    optimizer=a.optimizer, device=dev, **extra)
+        for _ in range(max(1, a.warmup)):
+            tr.get_loss(*args, **kw)
+            tr.optimizer_step()
+        sync()
+        peak[kind] = (torch.cuda.max_memory_allocated(dev) - base) / 2 ** 30
+    ph = {k: {n: [] for n in ("forward_ms", "backward_ms", "clip_adamw_ema_ms", "step_ms")} for k in kinds}
+    losses = {k: [] for k in kinds}
+    scales, skipped = [], []
+    for n in range(steps):
+        for kind in (kinds if n % 2 == 0 else kinds[::-1]):  # who goes first alternates
+            tr = trs[kind]
+            sync(); t0 = time.perf_counter()
+            tr.get_loss(*args, backward=False, **kw)
+            sync(); t1 = time.perf_counter()
+            loss = tr.get_loss(*args, **kw)
+            sync(); t2 = time.perf_counter()
+            tr.optimizer_step()
+            sync(); t3 = time.perf_counter()
+            f, fb, o = 1e3 * (t1 - t0), 1e3 * (t2 - t1), 1e3 * (t3 - t2)
+            ph[kind]["forward_ms"].append(f), ph[kind]["backward_ms"].append(fb - f), ph[kind]["clip_adamw_ema_ms"].append(o), ph[kind]["step_ms"].append(fb + o)
+            losses[kind].append(float(loss))
+            if kind == "fp16":
+                scales.append(tr.loss_scale_value), skipped.append(bool(tr.last_step_skipped))
+    out = {"batch": B, "attention_backward": a.attention_backward, "optimizer": a.optimizer, "parameters": params, "warmup": a.warmup, "timed_steps": steps}
+    for kind in kinds:
+        out[kind] = {n: _stats(v) for n, v in ph[kind].items()}
+        out[kind]["peak_memory_gib_of_a_step"] = peak[kind]
+        out[kind]["losses"] = losses[kind]
+    out["fp16"].update(loss_scale_after_each_step=scales, step_skipped=skipped, skipped_steps_warmup_included=trs["fp16"].skipped_steps)
+    for n in ("forward_ms", "backward_ms", "clip_adamw_ema_ms", "step_ms"):
+        out[f"{n[:-3]}_fp16_over_bf16"] = out["fp16"][n]["median"] / out["bf16"][n]["median"]
+        out[f"{n[:-3]}_fp16_minus_bf16_ms"] = out["fp16"][n]["median"] - out["bf16"][n]["median"]
+    del trs, tr
+    torch.cuda.empty_cache()
+    out["attention_backward_launches"] = fp16_attention_launches(a, c, B, dev)
+    out["timing"] = "host wall clock between two device synchronisations; the two trainers alternate and swap who goes first every step"
+    return out
+
+
 def data_parallel_run(a, c, sd, params, dev):
     """The grouped step (world size 1 over RCCL) beside the ungrouped one, and the exchange launches alone, at batch 4 -> dict."""
     import torch.distributed as dist
@@ -437,7 +541,8 @@ def data_parallel_run(a, c, sd, params, dev):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, nargs="+", default=[4, 32])
-    ap.add_argument("--precision", default="bf16", choices=["fp32", "bf16"])
+    ap.add_argument("--precision", default="bf16", choices=["fp32", "bf16", "fp16"],
+                    help="fp16 measures the fp16 step (dynamic loss scaling) beside the bf16 step in one process and adds it to --out")
     ap.add_argument("--no-yardstick", action="store_true")
     ap.add_argument("--depth", type=int, default=28)
     ap.add_argument("--hidden", type=int, default=2048)
@@ -457,16 +562,30 @@ def main():
                     help="measures the data-parallel step over an RCCL group of world size 1 beside the ungrouped one and adds it to --out")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rdt_train_bench.json"))
     a = ap.parse_args()
-    if a.attention_backward == "mfma" and a.precision != "bf16":
-        ap.error("--attention-backward mfma measures the bf16 step")
+    if a.attention_backward == "mfma" and a.precision == "fp32":
+        ap.error("--attention-backward mfma measures a 16-bit step")
     if a.steps is None:
-        a.steps = 21 if a.attention_backward == "mfma" else 10
+        a.steps = 21 if a.attention_backward == "mfma" or a.precision == "fp16" else 10
     from vlatouch.rdt_train import RdtTrainer
     dev = torch.device("cuda:0")
     c = dict(hidden=a.hidden, depth=a.depth, heads=a.hidden // 64, horizon=64, action_dim=128, lang_token_dim=4096, img_token_dim=1152,
              state_token_dim=128, max_lang_cond_len=1024, img_cond_len=a.img_len)
     sd = synth.fill_state_dict_device(synth.rdt_runner_shapes(**c), dev, torch.float32, seed=7)
     params = sum(v.numel() for v in sd.values())
+    if a.precision == "fp16":
+        rec = {}
+        if os.path.exists(a.out):
+            with open(a.out) as f:
+                rec = json.load(f)
+        runs = []
+        for B in a.batch:
+            runs.append(fp16_run(a, c, sd, params, dev, B))
+            print(json.dumps(runs[-1]))
+        rec["fp16"] = dict(runs=runs, config=c, lang_len=a.lang_len, lr=a.lr, device=torch.cuda.get_device_name(dev))
+        with open(a.out, "w") as f:
+            json.dump(rec, f, indent=1)
+        print("wrote", a.out)
+        return
     if a.data_parallel is not None:
         rec = {}
         if os.path.exists(a.out):
@@ -520,7 +639,7 @@ def main():
     if os.path.exists(a.out):
         with open(a.out) as f:
             old = json.load(f)
-        kept = {k: old[k] for k in ("accumulation", "adamw8bit", "attention_backward_mfma", "data_parallel") if k in old}
+        kept = {k: old[k] for k in ("accumulation", "adamw8bit", "attention_backward_mfma", "data_parallel", "fp16") if k in old}
     rec = {"config": c, "precision": a.precision, "parameters": params, "lang_len": a.lang_len, "warmup": a.warmup, "steps": a.steps, "lr": a.lr,
            "device": torch.cuda.get_device_name(dev), "runs": []}
     if a.step_attention_backward != "wave":

@@ -1,4 +1,4 @@
-// vt_attn_bwd.hip — attention backward on bf16 MFMA for head_dim 64 and at most 128 query rows (gfx950): the image cross-attention of RDT
+// vt_attn_bwd.hip — attention backward on 16-bit MFMA (bf16, or IEEE fp16 for fp16 fine-tuning) for head_dim 64 and at most 128 query rows (gfx950): the image cross-attention of RDT
 // fine-tuning (67 queries x 4 374 keys), where the one-wave-per-row kernels of vt_train_rdt.hip spend 65 % of the bf16 step.
 //
 // Arithmetic (tests/attn_bwd_mfma_ref.py is the statement): S = scale Q K^T and dP = dO V^T are exact bf16 products summed in fp32; per query row
@@ -22,6 +22,9 @@
 // accumulator is (j >> 2) * 16 + g * 4 + (j & 3), which the transposed reads reproduce (vt_attn.hip, attn16u_kernel).
 // Padded query rows (Nq up to the 32-row block), masked keys and the padding keys of a ragged tile have P = dS = 0 by predicate, never by
 // multiplication, so they add nothing and NaNs behind a mask stay there.
+// Every kernel is a template on the 16-bit type T: bf16_t (v_mfma_f32_16x16x32_bf16) or half_t (v_mfma_f32_16x16x32_f16; tests/attn_bwd_mfma16_ref.py is
+// that statement).  The two forms share tiling, workspaces and summation orders; P, dS and the results are rounded once to T with the hardware's
+// round-to-nearest-even conversion.  fp16 does not clamp: a dS or a result beyond 65504 becomes inf, which the loss scaler's flag catches.
 #include <math.h>
 #include "vt_common.h"
 #include "vt_host.h"
@@ -36,7 +39,8 @@ typedef __attribute__((ext_vector_type(4))) short short4_t;
 typedef __attribute__((address_space(3))) short4_t lds_short4_t;
 
 // stage `rows` rows of 64 bf16 (128 B) from a strided global view into the swizzled LDS image of vt_common.h (lds_frag); rows >= live are zeros
-__device__ __forceinline__ void stage_rows(char* dst, const bf16_t* src, long rs, int rows, int live) {
+template <typename T>
+__device__ __forceinline__ void stage_rows(char* dst, const T* src, long rs, int rows, int live) {
   for (int ci = threadIdx.x; ci < rows * 8; ci += 256) {
     const int r = ci >> 3, c = ci & 7;
     uint4 v = make_uint4(0, 0, 0, 0);
@@ -53,20 +57,30 @@ __device__ __forceinline__ unsigned tr_off(int l15, int g, int dt) {
   return (unsigned)(row * 128 + (((dt * 2) ^ sw) * 16) + (l15 & 1) * 8);
 }
 // A fragment X^T[column dt * 16 + l15][rows r0 + (j >> 2) * 16 + g * 4 + (j & 3)] of a row-major image
-__device__ __forceinline__ void tr_frag(Frag<bf16_t>& f, const char* img, int r0, unsigned off) {
+template <typename T>
+__device__ __forceinline__ void tr_frag(Frag<T>& f, const char* img, int r0, unsigned off) {
 #pragma unroll
   for (int hh = 0; hh < 2; ++hh) {
     const short4_t t = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_short4_t*)(img + (r0 + hh * 16) * 128 + off));
     f.v[hh * 4 + 0] = t[0]; f.v[hh * 4 + 1] = t[1]; f.v[hh * 4 + 2] = t[2]; f.v[hh * 4 + 3] = t[3];
   }
 }
-__device__ __forceinline__ void pack8(Frag<bf16_t>& f, const float4_t lo, const float4_t hi) {
-  const uint4 w = make_uint4(pk_bf16(lo[0], lo[1]), pk_bf16(lo[2], lo[3]), pk_bf16(hi[0], hi[1]), pk_bf16(hi[2], hi[3]));
+// two fp32 -> two T in one word, round-to-nearest-even (fp16: v_cvt_f16_f32 semantics, overflow gives inf)
+typedef __attribute__((ext_vector_type(2))) _Float16 f16x2_t;
+template <typename T> __device__ __forceinline__ uint32_t pk16(float lo, float hi);
+template <> __device__ __forceinline__ uint32_t pk16<bf16_t>(float lo, float hi) { return pk_bf16(lo, hi); }
+template <> __device__ __forceinline__ uint32_t pk16<half_t>(float lo, float hi) {
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector((float2_t){lo, hi}, f16x2_t));
+}
+template <typename T>
+__device__ __forceinline__ void pack8(Frag<T>& f, const float4_t lo, const float4_t hi) {
+  const uint4 w = make_uint4(pk16<T>(lo[0], lo[1]), pk16<T>(lo[2], lo[3]), pk16<T>(hi[0], hi[1]), pk16<T>(hi[2], hi[3]));
   f.v = __builtin_bit_cast(short8_t, w);
 }
 
 // the tile's K, V images and key validity bytes (0: masked or past Nk)
-__device__ __forceinline__ void stage_tile(char* Ks, char* Vs, unsigned char* kval, const bf16_t* K, const bf16_t* V, long k_rs, long v_rs,
+template <typename T>
+__device__ __forceinline__ void stage_tile(char* Ks, char* Vs, unsigned char* kval, const T* K, const T* V, long k_rs, long v_rs,
                                            const unsigned char* km, int key0, int Nk) {
   const int live = min(KT, Nk - key0);
   stage_rows(Ks, K + (long)key0 * k_rs, k_rs, KT, live);
@@ -78,15 +92,16 @@ __device__ __forceinline__ void stage_tile(char* Ks, char* Vs, unsigned char* kv
 }
 
 // S^T and dP^T of one key tile for the 16 queries of (qf, gf): lane holds [key = kt * 16 + g * 4 + r][query = l15]
-__device__ __forceinline__ void sdp_qlane(float4_t s[4], float4_t dp[4], const char* Ks, const char* Vs, const Frag<bf16_t> qf[2],
-                                          const Frag<bf16_t> gf[2], int l15, int g) {
+template <typename T>
+__device__ __forceinline__ void sdp_qlane(float4_t s[4], float4_t dp[4], const char* Ks, const char* Vs, const Frag<T> qf[2],
+                                          const Frag<T> gf[2], int l15, int g) {
 #pragma unroll
   for (int kt = 0; kt < 4; ++kt) {
     s[kt] = (float4_t){0.f, 0.f, 0.f, 0.f};
     dp[kt] = (float4_t){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
-      Frag<bf16_t> kf, vf;
+      Frag<T> kf, vf;
       lds_frag(kf, Ks, kt * 16 + l15, ks * 4 + g);
       lds_frag(vf, Vs, kt * 16 + l15, ks * 4 + g);
       mma16(s[kt], kf, qf[ks]);
@@ -96,22 +111,23 @@ __device__ __forceinline__ void sdp_qlane(float4_t s[4], float4_t dp[4], const c
 }
 
 // ---- statistics: one partial (max, sum exp, sum exp dP) per (batch * head, run, query row)
+template <typename T>
 __global__ __launch_bounds__(256) void attn_bwd_mfma_stats_kernel(VtAttnBwdParams p, float* part, int nruns) {
   __shared__ __attribute__((aligned(16))) char Ks[KT * 128];
   __shared__ __attribute__((aligned(16))) char Vs[KT * 128];
   __shared__ __attribute__((aligned(4))) unsigned char kval[KT];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, g = lane >> 4;
   const int run = blockIdx.x, bh = blockIdx.y, h = bh % p.H, b = bh / p.H;
-  const bf16_t* Q = (const bf16_t*)p.Q + (long)b * p.q_bs + (long)h * p.q_hs;
-  const bf16_t* G = (const bf16_t*)p.dO + (long)b * p.do_bs + (long)h * p.do_hs;
-  const bf16_t* K = (const bf16_t*)p.K + (long)b * p.k_bs + (long)h * p.k_hs;
-  const bf16_t* V = (const bf16_t*)p.V + (long)b * p.v_bs + (long)h * p.v_hs;
+  const T* Q = (const T*)p.Q + (long)b * p.q_bs + (long)h * p.q_hs;
+  const T* G = (const T*)p.dO + (long)b * p.do_bs + (long)h * p.do_hs;
+  const T* K = (const T*)p.K + (long)b * p.k_bs + (long)h * p.k_hs;
+  const T* V = (const T*)p.V + (long)b * p.v_bs + (long)h * p.v_hs;
   const unsigned char* km = p.kmask ? p.kmask + (long)b * p.km_bs : nullptr;
   const int nqt = (p.Nq + 15) >> 4;
   const int ntiles = (p.Nk + KT - 1) / KT;
   const int t0 = run * RUN_TILES, t1 = min(t0 + RUN_TILES, ntiles);
 
-  Frag<bf16_t> qf[2][2], gf[2][2];
+  Frag<T> qf[2][2], gf[2][2];
   float m[2], l[2], acc[2];
 #pragma unroll
   for (int qi = 0; qi < 2; ++qi) {
@@ -197,6 +213,7 @@ __global__ __launch_bounds__(256) void attn_bwd_mfma_combine_kernel(const float*
 }
 
 // ---- dK, dV of the run's keys and the run's dQ partial
+template <typename T>
 __global__ __launch_bounds__(256) void attn_bwd_mfma_main_kernel(VtAttnBwdParams p, float* dqpart, int nruns) {
   __shared__ __attribute__((aligned(16))) char Qs[MAXQ * 128];
   __shared__ __attribute__((aligned(16))) char Gs[MAXQ * 128];
@@ -206,15 +223,15 @@ __global__ __launch_bounds__(256) void attn_bwd_mfma_main_kernel(VtAttnBwdParams
   __shared__ __attribute__((aligned(4))) unsigned char kval[KT];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, g = lane >> 4;
   const int run = blockIdx.x, bh = blockIdx.y, h = bh % p.H, b = bh / p.H;
-  const bf16_t* K = (const bf16_t*)p.K + (long)b * p.k_bs + (long)h * p.k_hs;
-  const bf16_t* V = (const bf16_t*)p.V + (long)b * p.v_bs + (long)h * p.v_hs;
+  const T* K = (const T*)p.K + (long)b * p.k_bs + (long)h * p.k_hs;
+  const T* V = (const T*)p.V + (long)b * p.v_bs + (long)h * p.v_hs;
   const unsigned char* km = p.kmask ? p.kmask + (long)b * p.km_bs : nullptr;
   const int nqt = (p.Nq + 15) >> 4, nqb = (nqt + 1) >> 1;
   const int ntiles = (p.Nk + KT - 1) / KT;
   const int t0 = run * RUN_TILES, t1 = min(t0 + RUN_TILES, ntiles);
 
-  stage_rows(Qs, (const bf16_t*)p.Q + (long)b * p.q_bs + (long)h * p.q_hs, p.q_rs, nqb * 32, p.Nq);
-  stage_rows(Gs, (const bf16_t*)p.dO + (long)b * p.do_bs + (long)h * p.do_hs, p.do_rs, nqb * 32, p.Nq);
+  stage_rows(Qs, (const T*)p.Q + (long)b * p.q_bs + (long)h * p.q_hs, p.q_rs, nqb * 32, p.Nq);
+  stage_rows(Gs, (const T*)p.dO + (long)b * p.do_bs + (long)h * p.do_hs, p.do_rs, nqb * 32, p.Nq);
   for (int i = tid; i < nqb * 32 * 3; i += 256) st[i] = i < p.Nq * 3 ? p.ws[(long)bh * p.Nq * 3 + i] : 0.f;
 
   unsigned troff[4];
@@ -234,7 +251,7 @@ __global__ __launch_bounds__(256) void attn_bwd_mfma_main_kernel(VtAttnBwdParams
 
     // ---- part 1: this wave's 16 keys against every query block -> dK^T, dV^T [d = dt * 16 + g * 4 + r][key = wave * 16 + l15]
     {
-      Frag<bf16_t> kf[2], vf[2];
+      Frag<T> kf[2], vf[2];
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
         lds_frag(kf[ks], Ks, wave * 16 + l15, ks * 4 + g);
@@ -252,7 +269,7 @@ __global__ __launch_bounds__(256) void attn_bwd_mfma_main_kernel(VtAttnBwdParams
           float4_t s = (float4_t){0.f, 0.f, 0.f, 0.f}, dp = (float4_t){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
           for (int ks = 0; ks < 2; ++ks) {
-            Frag<bf16_t> qf, gf;
+            Frag<T> qf, gf;
             lds_frag(qf, Qs, q0 + l15, ks * 4 + g);
             lds_frag(gf, Gs, q0 + l15, ks * 4 + g);
             mma16(s, qf, kf[ks]);
@@ -268,12 +285,12 @@ __global__ __launch_bounds__(256) void attn_bwd_mfma_main_kernel(VtAttnBwdParams
             ds[t][r] = live ? pv * (dp[r] - w[2]) : 0.f;
           }
         }
-        Frag<bf16_t> pf, sf;
+        Frag<T> pf, sf;
         pack8(pf, pr[0], pr[1]);
         pack8(sf, ds[0], ds[1]);
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) {
-          Frag<bf16_t> gt, qt;
+          Frag<T> gt, qt;
           tr_frag(gt, Gs, qb * 32, troff[dt]);
           tr_frag(qt, Qs, qb * 32, troff[dt]);
           mma16(dv[dt], gt, pf);
@@ -282,12 +299,12 @@ __global__ __launch_bounds__(256) void attn_bwd_mfma_main_kernel(VtAttnBwdParams
       }
       const int key = key0 + wave * 16 + l15;
       if (key < p.Nk) {                                         // masked keys store their zeros, padding keys nothing
-        bf16_t* dK = (bf16_t*)p.dK + (long)b * p.dk_bs + (long)key * p.dk_rs + (long)h * p.dk_hs;
-        bf16_t* dV = (bf16_t*)p.dV + (long)b * p.dv_bs + (long)key * p.dv_rs + (long)h * p.dv_hs;
+        T* dK = (T*)p.dK + (long)b * p.dk_bs + (long)key * p.dk_rs + (long)h * p.dk_hs;
+        T* dV = (T*)p.dV + (long)b * p.dv_bs + (long)key * p.dv_rs + (long)h * p.dv_hs;
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) {
-          *reinterpret_cast<uint2*>(dK + dt * 16 + g * 4) = make_uint2(pk_bf16(dk[dt][0] * p.scale, dk[dt][1] * p.scale), pk_bf16(dk[dt][2] * p.scale, dk[dt][3] * p.scale));
-          *reinterpret_cast<uint2*>(dV + dt * 16 + g * 4) = make_uint2(pk_bf16(dv[dt][0], dv[dt][1]), pk_bf16(dv[dt][2], dv[dt][3]));
+          *reinterpret_cast<uint2*>(dK + dt * 16 + g * 4) = make_uint2(pk16<T>(dk[dt][0] * p.scale, dk[dt][1] * p.scale), pk16<T>(dk[dt][2] * p.scale, dk[dt][3] * p.scale));
+          *reinterpret_cast<uint2*>(dV + dt * 16 + g * 4) = make_uint2(pk16<T>(dv[dt][0], dv[dt][1]), pk16<T>(dv[dt][2], dv[dt][3]));
         }
       }
     }
@@ -297,7 +314,7 @@ __global__ __launch_bounds__(256) void attn_bwd_mfma_main_kernel(VtAttnBwdParams
     for (int qi = 0; qi < 2; ++qi) {
       const int qt = wave + qi * 4;
       if (qt >= nqt) continue;                                  // wave-uniform
-      Frag<bf16_t> qf[2], gf[2];
+      Frag<T> qf[2], gf[2];
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
         lds_frag(qf[ks], Qs, qt * 16 + l15, ks * 4 + g);
@@ -319,11 +336,11 @@ __global__ __launch_bounds__(256) void attn_bwd_mfma_main_kernel(VtAttnBwdParams
       }
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb) {
-        Frag<bf16_t> sf;
+        Frag<T> sf;
         pack8(sf, s[kb * 2], s[kb * 2 + 1]);
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) {
-          Frag<bf16_t> ktf;
+          Frag<T> ktf;
           tr_frag(ktf, Ks, kb * 32, troff[dt]);
           mma16(dq[qi][dt], ktf, sf);
         }
@@ -342,6 +359,7 @@ __global__ __launch_bounds__(256) void attn_bwd_mfma_main_kernel(VtAttnBwdParams
 }
 
 // dQ = scale * (sum of the run partials, in run order); one wave per (batch * head, query row), lane = head-dim element
+template <typename T>
 __global__ __launch_bounds__(256) void attn_bwd_mfma_dq_kernel(VtAttnBwdParams p, const float* __restrict__ dqpart, int nruns) {
   const int lane = threadIdx.x & 63;
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -350,7 +368,7 @@ __global__ __launch_bounds__(256) void attn_bwd_mfma_dq_kernel(VtAttnBwdParams p
   const int i = (int)(row - bh * p.Nq), h = (int)(bh % p.H), b = (int)(bh / p.H);
   float s = 0.f;
   for (int r = 0; r < nruns; ++r) s += dqpart[((bh * nruns + r) * p.Nq + i) * 64 + lane];
-  ((bf16_t*)p.dQ)[(long)b * p.dq_bs + (long)i * p.dq_rs + (long)h * p.dq_hs + lane] = f2bf(s * p.scale);
+  stf<T>((T*)p.dQ, (long)b * p.dq_bs + (long)i * p.dq_rs + (long)h * p.dq_hs + lane, s * p.scale);
 }
 
 inline int nruns_of(int Nk) { return ((Nk + KT - 1) / KT + RUN_TILES - 1) / RUN_TILES; }
@@ -366,7 +384,7 @@ int vt_attention_bwd_mfma(const VtAttnBwdParams* p, void* ws2, long ws2_bytes, v
   if (!p) return vt_fail(VT_ERR_ARG, "vt_attention_bwd_mfma: null params");
   if (!p->Q || !p->K || !p->V || !p->dO || !p->dQ || !p->dK || !p->dV || !p->ws || !ws2) return vt_fail(VT_ERR_ARG, "vt_attention_bwd_mfma: null pointer");
   if (p->B < 1 || p->H < 1 || p->Nq < 1 || p->Nk < 1 || p->hd != 64) return vt_fail(VT_ERR_ARG, "vt_attention_bwd_mfma: bad shape (head_dim must be 64)");
-  if (p->dtype != VT_BF16) return vt_fail(VT_ERR_UNSUPPORTED, "vt_attention_bwd_mfma: bf16 operands only (vt_attention_bwd takes fp32)");
+  if (p->dtype != VT_BF16 && p->dtype != VT_F16) return vt_fail(VT_ERR_UNSUPPORTED, "vt_attention_bwd_mfma: bf16 or fp16 operands only (vt_attention_bwd takes fp32)");
   if (p->Nq > MAXQ) return vt_fail(VT_ERR_UNSUPPORTED, "vt_attention_bwd_mfma: Nq = %d > %d query rows", p->Nq, MAXQ);
   if ((long)p->B * p->H > 65535) return vt_fail(VT_ERR_ARG, "vt_attention_bwd_mfma: B * H > 65535");
   if (p->kmask && p->km_bs < p->Nk) return vt_fail(VT_ERR_ARG, "vt_attention_bwd_mfma: key mask row shorter than Nk");
@@ -384,9 +402,17 @@ int vt_attention_bwd_mfma(const VtAttnBwdParams* p, void* ws2, long ws2_bytes, v
   float* dqpart = (float*)ws2;                                  // [B * H][nruns][Nq][64], first: its rows are stored 16 bytes at a time
   float* part = dqpart + rows * nruns * 64;                     // [B * H][nruns][Nq][3]
   const dim3 grid((unsigned)nruns, (unsigned)(p->B * p->H));
-  hipLaunchKernelGGL(attn_bwd_mfma_stats_kernel, grid, dim3(256), 0, (hipStream_t)s, *p, part, nruns);
-  hipLaunchKernelGGL(attn_bwd_mfma_combine_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)s, part, p->ws, rows, p->Nq, nruns);
-  hipLaunchKernelGGL(attn_bwd_mfma_main_kernel, grid, dim3(256), 0, (hipStream_t)s, *p, dqpart, nruns);
-  hipLaunchKernelGGL(attn_bwd_mfma_dq_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)s, *p, dqpart, nruns);
+  const dim3 gc((unsigned)((rows + 255) / 256)), gq((unsigned)((rows + 3) / 4));
+  if (p->dtype == VT_BF16) {
+    hipLaunchKernelGGL(attn_bwd_mfma_stats_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)s, *p, part, nruns);
+    hipLaunchKernelGGL(attn_bwd_mfma_combine_kernel, gc, dim3(256), 0, (hipStream_t)s, part, p->ws, rows, p->Nq, nruns);
+    hipLaunchKernelGGL(attn_bwd_mfma_main_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)s, *p, dqpart, nruns);
+    hipLaunchKernelGGL(attn_bwd_mfma_dq_kernel<bf16_t>, gq, dim3(256), 0, (hipStream_t)s, *p, dqpart, nruns);
+  } else {
+    hipLaunchKernelGGL(attn_bwd_mfma_stats_kernel<half_t>, grid, dim3(256), 0, (hipStream_t)s, *p, part, nruns);
+    hipLaunchKernelGGL(attn_bwd_mfma_combine_kernel, gc, dim3(256), 0, (hipStream_t)s, part, p->ws, rows, p->Nq, nruns);
+    hipLaunchKernelGGL(attn_bwd_mfma_main_kernel<half_t>, grid, dim3(256), 0, (hipStream_t)s, *p, dqpart, nruns);
+    hipLaunchKernelGGL(attn_bwd_mfma_dq_kernel<half_t>, gq, dim3(256), 0, (hipStream_t)s, *p, dqpart, nruns);
+  }
   return vt_check_launch();
 }

@@ -104,7 +104,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(VtAttnBwdParams p) {
 // y = x r w with r = rsqrt(v + eps); mode 1: v = mean(x^2); mode 2: v = sum (x - mean)^2 / (D - 1)  (timm <= 1.0.8).  With g = dy w:
 //   mode 1: dx = r g - r^3 <g, x> x / D          mode 2: dx = r g - r^3 <g, x> (x - mean) / (D - 1)
 // One block per row.  dyxr (fp32) = dy x r, whose column sums are d w (vt_colsum finishes, as after vt_ln_bwd).
-// Every element-wise kernel below is typed on the activation type T (fp32, or bf16 storage with fp32 arithmetic and one rounding at the store).
+// Every element-wise kernel below is typed on the activation type T (fp32, or bf16 / fp16 storage with fp32 arithmetic and one rounding at the store).
 __device__ __forceinline__ float block_sum4(float t, float* red) {
   t = wave_sum(t);
   __syncthreads();
@@ -323,6 +323,62 @@ __global__ __launch_bounds__(256) void scale_mt_kernel(const MtEntry* __restrict
   }
 }
 
+// fp16 training (dynamic loss scaling): the table's gradients are S times too large.  Pass 1 looks at every RAW element (found_inf |= !isfinite(g),
+// what torch's _amp_foreach_non_finite_check_and_unscale_ checks) and forms the chunk's sum of squares of u = g * inv_S; the flag is an integer OR (order
+// independent), the float partials keep sumsq_mt_kernel's fixed orders.  A chunk is read as 128-bit words where its tensor is 16-byte aligned.
+static_assert(4 * 256 * 4 == MT_CHUNK, "the 4 float4 passes of 256 threads of the two kernels below walk one chunk");
+__global__ __launch_bounds__(256) void unscale_sumsq_mt_kernel(const MtEntry* __restrict__ tab, int ntensors, float inv_scale, float* __restrict__ part,
+                                                               int* __restrict__ found_inf) {
+  __shared__ float red[4];
+  const MtEntry e = tab[mt_find(tab, ntensors, blockIdx.x)];
+  const long base = ((long)blockIdx.x - e.first_chunk) * MT_CHUNK;
+  const long left = e.n - base;
+  const int cnt = left < MT_CHUNK ? (int)left : MT_CHUNK;
+  const float* __restrict__ g = e.g + base;
+  const int quads = (((size_t)g) & 15) == 0 ? cnt >> 2 : 0;
+  float s = 0.f;
+  bool bad = false;
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    const int j = it * 256 + threadIdx.x;
+    if (j >= quads) break;
+    const float4 v = reinterpret_cast<const float4*>(g)[j];
+    bad |= !(isfinite(v.x) && isfinite(v.y) && isfinite(v.z) && isfinite(v.w));
+    const float ux = v.x * inv_scale, uy = v.y * inv_scale, uz = v.z * inv_scale, uw = v.w * inv_scale;
+    s += ux * ux; s += uy * uy; s += uz * uz; s += uw * uw;
+  }
+  for (int i = quads * 4 + threadIdx.x; i < cnt; i += 256) {
+    const float v = g[i], u = v * inv_scale;
+    bad |= !isfinite(v);
+    s += u * u;
+  }
+  s = block_sum4(s, red);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+  if (bad) atomicOr(found_inf, 1);
+}
+// pass 2: g = (g * inv_S) * coef as TWO multiplications (the bits of torch's unscale followed by its clip, for any S); nothing is written when the
+// flag is set.  No coef >= 1 exit: the unscale is always due.
+__global__ __launch_bounds__(256) void unscale_scale_mt_kernel(const MtEntry* __restrict__ tab, int ntensors, float inv_scale,
+                                                               const float* __restrict__ norm_coef, const int* __restrict__ found_inf) {
+  if (*found_inf) return;
+  const MtEntry e = tab[mt_find(tab, ntensors, blockIdx.x)];
+  const long base = ((long)blockIdx.x - e.first_chunk) * MT_CHUNK;
+  const long left = e.n - base;
+  const int cnt = left < MT_CHUNK ? (int)left : MT_CHUNK;
+  float* __restrict__ g = e.g + base;
+  const float c = norm_coef[1];
+  const int quads = (((size_t)g) & 15) == 0 ? cnt >> 2 : 0;
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    const int j = it * 256 + threadIdx.x;
+    if (j >= quads) break;
+    float4 v = reinterpret_cast<const float4*>(g)[j];
+    v.x = (v.x * inv_scale) * c; v.y = (v.y * inv_scale) * c; v.z = (v.z * inv_scale) * c; v.w = (v.w * inv_scale) * c;
+    reinterpret_cast<float4*>(g)[j] = v;
+  }
+  for (int i = quads * 4 + threadIdx.x; i < cnt; i += 256) g[i] = (g[i] * inv_scale) * c;
+}
+
 // ------------------------------------------------------------------------------------------------ gradient accumulation
 // Folds one micro-batch's fresh gradients (fresh[k], a second device array of pointers: they are new allocations every micro-batch) into the
 // persistent fp32 accumulators, which are the table's g column, so that the clip and AdamW kernels read the accumulated gradient from the
@@ -450,13 +506,14 @@ __global__ __launch_bounds__(256) void ema_mt_kernel(const MtEntry* __restrict__
   for (int i = quads * 4 + threadIdx.x; i < cnt; i += 256) sh[i] = ema_elem(sh[i], p[i], omd);
 }
 
-// mean squared error of pred against target (fp32) and its gradient: loss = mean((pred - target)^2), dpred = 2 (pred - target) / n; one block
-template <typename T>
+// mean squared error of pred against target (fp32) and its gradient: loss = mean((pred - target)^2), dpred = 2 (pred - target) / n; one block.
+// SCALED (fp16 training): dpred = grad_scale * 2 (pred - target) / n, the factor formed once in fp32, one rounding at the store; the loss is not scaled.
+template <typename T, bool SCALED>
 __global__ __launch_bounds__(256) void mse_kernel(const T* __restrict__ pred, const float* __restrict__ tgt, T* __restrict__ dpred,
-                                                  float* __restrict__ loss, long n) {
+                                                  float* __restrict__ loss, long n, float grad_scale) {
   __shared__ float red[4];
   float s = 0.f;
-  const float k = 2.0f / (float)n;
+  const float k = SCALED ? grad_scale * (2.0f / (float)n) : 2.0f / (float)n;
   for (long i = threadIdx.x; i < n; i += 256) {
     const float d = ldf<T>(pred, i) - tgt[i];
     s += d * d;
@@ -469,8 +526,8 @@ __global__ __launch_bounds__(256) void mse_kernel(const T* __restrict__ pred, co
 }  // namespace
 
 #define LAUNCH_OK() (vt_check_launch())
-// launch KERNEL<float> or KERNEL<bf16_t> by the activation dtype code `dt` (void* arguments are cast by the CAST macro at the call site)
-#define BAD_DT(name) vt_fail(VT_ERR_UNSUPPORTED, name ": activation dtype must be fp32 (0) or bf16 (1)")
+// launch KERNEL<float>, KERNEL<bf16_t> or KERNEL<half_t> by the activation dtype code `dt`
+#define BAD_DT(name) vt_fail(VT_ERR_UNSUPPORTED, name ": activation dtype must be fp32 (0), bf16 (1) or fp16 (3)")
 
 int vt_attention_bwd(const VtAttnBwdParams* p, vt_stream_t s) {
   if (!p) return vt_fail(VT_ERR_ARG, "vt_attention_bwd: null params");
@@ -486,8 +543,11 @@ int vt_attention_bwd(const VtAttnBwdParams* p, vt_stream_t s) {
   } else if (p->dtype == VT_BF16) {
     hipLaunchKernelGGL(attn_bwd_dq_kernel<bf16_t>, gq, dim3(256), 0, (hipStream_t)s, *p);
     hipLaunchKernelGGL(attn_bwd_dkv_kernel<bf16_t>, gk, dim3(256), 0, (hipStream_t)s, *p);
+  } else if (p->dtype == VT_F16) {
+    hipLaunchKernelGGL(attn_bwd_dq_kernel<half_t>, gq, dim3(256), 0, (hipStream_t)s, *p);
+    hipLaunchKernelGGL(attn_bwd_dkv_kernel<half_t>, gk, dim3(256), 0, (hipStream_t)s, *p);
   } else {
-    return vt_fail(VT_ERR_UNSUPPORTED, "vt_attention_bwd: fp32 or bf16 operands");
+    return vt_fail(VT_ERR_UNSUPPORTED, "vt_attention_bwd: fp32, bf16 or fp16 operands");
   }
   return LAUNCH_OK();
 }
@@ -495,6 +555,7 @@ int vt_rmsnorm_bwd(const void* x, const float* w, const void* dy, void* dx, floa
   if (!x || !w || !dy || !dx || !dyxr || rows < 1 || D < 2 || (mode != 1 && mode != 2)) return vt_fail(VT_ERR_ARG, "vt_rmsnorm_bwd: bad argument");
   if (dt == VT_F32) hipLaunchKernelGGL(rmsnorm_bwd_kernel<float>, dim3(rows), dim3(256), 0, (hipStream_t)s, (const float*)x, w, (const float*)dy, (float*)dx, dyxr, D, eps, mode);
   else if (dt == VT_BF16) hipLaunchKernelGGL(rmsnorm_bwd_kernel<bf16_t>, dim3(rows), dim3(256), 0, (hipStream_t)s, (const bf16_t*)x, w, (const bf16_t*)dy, (bf16_t*)dx, dyxr, D, eps, mode);
+  else if (dt == VT_F16) hipLaunchKernelGGL(rmsnorm_bwd_kernel<half_t>, dim3(rows), dim3(256), 0, (hipStream_t)s, (const half_t*)x, w, (const half_t*)dy, (half_t*)dx, dyxr, D, eps, mode);
   else return BAD_DT("vt_rmsnorm_bwd");
   return LAUNCH_OK();
 }
@@ -506,6 +567,7 @@ int vt_headnorm_bwd(const void* x, long x_stride, void* dy, long dy_stride, int 
   const dim3 g((unsigned)((pairs + 63) / 64));
   if (dt == VT_F32) hipLaunchKernelGGL(headnorm_bwd_kernel<float>, g, dim3(256), 0, (hipStream_t)s, (const float*)x, x_stride, (float*)dy, dy_stride, heads, pairs, w, part, eps, mode);
   else if (dt == VT_BF16) hipLaunchKernelGGL(headnorm_bwd_kernel<bf16_t>, g, dim3(256), 0, (hipStream_t)s, (const bf16_t*)x, x_stride, (bf16_t*)dy, dy_stride, heads, pairs, w, part, eps, mode);
+  else if (dt == VT_F16) hipLaunchKernelGGL(headnorm_bwd_kernel<half_t>, g, dim3(256), 0, (hipStream_t)s, (const half_t*)x, x_stride, (half_t*)dy, dy_stride, heads, pairs, w, part, eps, mode);
   else return BAD_DT("vt_headnorm_bwd");
   return LAUNCH_OK();
 }
@@ -513,6 +575,7 @@ int vt_act_bwd(const void* x, const void* dy, void* out, long n, int act, int dt
   if (!x || !out || n < 1 || (act != VT_ACT_GELU_TANH && act != VT_ACT_SILU)) return vt_fail(VT_ERR_ARG, "vt_act_bwd: bad argument (act 2 = tanh-GELU, 3 = SiLU)");
   if (dt == VT_F32) hipLaunchKernelGGL(act_kernel<float>, g1(n), dim3(256), 0, (hipStream_t)s, (const float*)x, (const float*)dy, (float*)out, n, act);
   else if (dt == VT_BF16) hipLaunchKernelGGL(act_kernel<bf16_t>, g1(n), dim3(256), 0, (hipStream_t)s, (const bf16_t*)x, (const bf16_t*)dy, (bf16_t*)out, n, act);
+  else if (dt == VT_F16) hipLaunchKernelGGL(act_kernel<half_t>, g1(n), dim3(256), 0, (hipStream_t)s, (const half_t*)x, (const half_t*)dy, (half_t*)out, n, act);
   else return BAD_DT("vt_act_bwd");
   return LAUNCH_OK();
 }
@@ -523,6 +586,7 @@ int vt_ddpm_qsample(const float* state, const float* action, const float* noise,
   const dim3 g = g1((long)B * (horizon + 1) * 2 * action_dim);
   if (odt == VT_F32) hipLaunchKernelGGL(ddpm_qsample_kernel<float>, g, dim3(256), 0, (hipStream_t)s, state, action, noise, mask, timesteps, alphas_cumprod, num_train_timesteps, (float*)out, B, horizon, action_dim);
   else if (odt == VT_BF16) hipLaunchKernelGGL(ddpm_qsample_kernel<bf16_t>, g, dim3(256), 0, (hipStream_t)s, state, action, noise, mask, timesteps, alphas_cumprod, num_train_timesteps, (bf16_t*)out, B, horizon, action_dim);
+  else if (odt == VT_F16) hipLaunchKernelGGL(ddpm_qsample_kernel<half_t>, g, dim3(256), 0, (hipStream_t)s, state, action, noise, mask, timesteps, alphas_cumprod, num_train_timesteps, (half_t*)out, B, horizon, action_dim);
   else return BAD_DT("vt_ddpm_qsample");
   return LAUNCH_OK();
 }
@@ -530,6 +594,7 @@ int vt_timestep_embed(const float* t, const float* freqs, void* out, int odt, in
   if (!t || !freqs || !out || B < 1 || dim < 2 || dim % 2) return vt_fail(VT_ERR_ARG, "vt_timestep_embed: bad argument");
   if (odt == VT_F32) hipLaunchKernelGGL(timestep_embed_kernel<float>, g1((long)B * dim), dim3(256), 0, (hipStream_t)s, t, freqs, (float*)out, B, dim);
   else if (odt == VT_BF16) hipLaunchKernelGGL(timestep_embed_kernel<bf16_t>, g1((long)B * dim), dim3(256), 0, (hipStream_t)s, t, freqs, (bf16_t*)out, B, dim);
+  else if (odt == VT_F16) hipLaunchKernelGGL(timestep_embed_kernel<half_t>, g1((long)B * dim), dim3(256), 0, (hipStream_t)s, t, freqs, (half_t*)out, B, dim);
   else return BAD_DT("vt_timestep_embed");
   return LAUNCH_OK();
 }
@@ -537,6 +602,7 @@ int vt_add_rowvec_(void* a, int dt, const float* v, long rows, long cols, vt_str
   if (!a || !v || rows < 1 || cols < 1) return vt_fail(VT_ERR_ARG, "vt_add_rowvec_: bad argument");
   if (dt == VT_F32) hipLaunchKernelGGL(add_rowvec_kernel<float>, g1(rows * cols), dim3(256), 0, (hipStream_t)s, (float*)a, v, rows, cols);
   else if (dt == VT_BF16) hipLaunchKernelGGL(add_rowvec_kernel<bf16_t>, g1(rows * cols), dim3(256), 0, (hipStream_t)s, (bf16_t*)a, v, rows, cols);
+  else if (dt == VT_F16) hipLaunchKernelGGL(add_rowvec_kernel<half_t>, g1(rows * cols), dim3(256), 0, (hipStream_t)s, (half_t*)a, v, rows, cols);
   else return BAD_DT("vt_add_rowvec_");
   return LAUNCH_OK();
 }
@@ -545,6 +611,7 @@ int vt_transpose_pad(const void* in, void* out, int dt, int M, int N, int Mp, vt
   const dim3 g((N + 31) / 32, (Mp + 31) / 32);
   if (dt == VT_F32) hipLaunchKernelGGL(transpose_pad_kernel<float>, g, dim3(256), 0, (hipStream_t)s, (const float*)in, (float*)out, M, N, Mp);
   else if (dt == VT_BF16) hipLaunchKernelGGL(transpose_pad_kernel<bf16_t>, g, dim3(256), 0, (hipStream_t)s, (const bf16_t*)in, (bf16_t*)out, M, N, Mp);
+  else if (dt == VT_F16) hipLaunchKernelGGL(transpose_pad_kernel<half_t>, g, dim3(256), 0, (hipStream_t)s, (const half_t*)in, (half_t*)out, M, N, Mp);
   else return BAD_DT("vt_transpose_pad");
   return LAUNCH_OK();
 }
@@ -552,6 +619,7 @@ int vt_colsum_dt(const void* x, int dt, long ld, float* out, int M, int N, vt_st
   if (!x || !out || M < 1 || N < 1) return vt_fail(VT_ERR_ARG, "vt_colsum_dt: bad argument");
   if (dt == VT_F32) hipLaunchKernelGGL(colsum_t_kernel<float>, dim3((N + 31) / 32), dim3(1024), 0, (hipStream_t)s, (const float*)x, ld, out, M, N);
   else if (dt == VT_BF16) hipLaunchKernelGGL(colsum_t_kernel<bf16_t>, dim3((N + 31) / 32), dim3(1024), 0, (hipStream_t)s, (const bf16_t*)x, ld, out, M, N);
+  else if (dt == VT_F16) hipLaunchKernelGGL(colsum_t_kernel<half_t>, dim3((N + 31) / 32), dim3(1024), 0, (hipStream_t)s, (const half_t*)x, ld, out, M, N);
   else return BAD_DT("vt_colsum_dt");
   return LAUNCH_OK();
 }
@@ -559,6 +627,7 @@ int vt_add_dt(void* a, const void* b, long n, int dt, vt_stream_t s) {
   if (!a || !b || n < 1) return vt_fail(VT_ERR_ARG, "vt_add_dt: bad argument");
   if (dt == VT_F32) hipLaunchKernelGGL(add_t_kernel<float>, g1(n), dim3(256), 0, (hipStream_t)s, (float*)a, (const float*)b, n);
   else if (dt == VT_BF16) hipLaunchKernelGGL(add_t_kernel<bf16_t>, g1(n), dim3(256), 0, (hipStream_t)s, (bf16_t*)a, (const bf16_t*)b, n);
+  else if (dt == VT_F16) hipLaunchKernelGGL(add_t_kernel<half_t>, g1(n), dim3(256), 0, (hipStream_t)s, (half_t*)a, (const half_t*)b, n);
   else return BAD_DT("vt_add_dt");
   return LAUNCH_OK();
 }
@@ -566,6 +635,7 @@ int vt_copy_cols_dt(const void* src, long lds_, long off, void* dst, long ldd, l
   if (!src || !dst || rows < 1 || cols < 1) return vt_fail(VT_ERR_ARG, "vt_copy_cols_dt: bad argument");
   if (dt == VT_F32) hipLaunchKernelGGL(copy_cols_t_kernel<float>, g1(rows * cols), dim3(256), 0, (hipStream_t)s, (const float*)src, lds_, off, (float*)dst, ldd, doff, rows, cols);
   else if (dt == VT_BF16) hipLaunchKernelGGL(copy_cols_t_kernel<bf16_t>, g1(rows * cols), dim3(256), 0, (hipStream_t)s, (const bf16_t*)src, lds_, off, (bf16_t*)dst, ldd, doff, rows, cols);
+  else if (dt == VT_F16) hipLaunchKernelGGL(copy_cols_t_kernel<half_t>, g1(rows * cols), dim3(256), 0, (hipStream_t)s, (const half_t*)src, lds_, off, (half_t*)dst, ldd, doff, rows, cols);
   else return BAD_DT("vt_copy_cols_dt");
   return LAUNCH_OK();
 }
@@ -574,6 +644,17 @@ int vt_grad_clip_multi(const void* table, int ntensors, long total_chunks, float
   hipLaunchKernelGGL(sumsq_mt_kernel, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)s, (const MtEntry*)table, ntensors, chunk_part);
   hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(256), 0, (hipStream_t)s, chunk_part, total_chunks, max_norm, norm_coef);
   hipLaunchKernelGGL(scale_mt_kernel, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)s, (const MtEntry*)table, ntensors, norm_coef);
+  return LAUNCH_OK();
+}
+int vt_grad_unscale_clip_multi(const void* table, int ntensors, long total_chunks, float max_norm, float inv_scale, float* chunk_part, float* norm_coef,
+                               int* found_inf, vt_stream_t s) {
+  if (!table || !chunk_part || !norm_coef || !found_inf || ntensors < 1 || total_chunks < 1 || !(max_norm > 0.f) || !(inv_scale > 0.f) || isinf(inv_scale))
+    return vt_fail(VT_ERR_ARG, "vt_grad_unscale_clip_multi: bad argument");
+  if (hipMemsetAsync(found_inf, 0, sizeof(int), (hipStream_t)s) != hipSuccess) return vt_fail(VT_ERR_LAUNCH, "vt_grad_unscale_clip_multi: clearing the flag failed");
+  hipLaunchKernelGGL(unscale_sumsq_mt_kernel, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)s, (const MtEntry*)table, ntensors, inv_scale, chunk_part, found_inf);
+  hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(256), 0, (hipStream_t)s, chunk_part, total_chunks, max_norm, norm_coef);
+  hipLaunchKernelGGL(unscale_scale_mt_kernel, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)s, (const MtEntry*)table, ntensors, inv_scale, norm_coef,
+                     found_inf);
   return LAUNCH_OK();
 }
 int vt_grad_accum_multi(const void* table, const void* fresh, int ntensors, long total_chunks, float scale, int accumulate, vt_stream_t s) {
@@ -603,8 +684,17 @@ int vt_ema_multi(const void* table, int ntensors, long total_chunks, const float
 }
 int vt_mse_loss(const void* pred, const float* target, void* dpred, float* loss, long n, int dt, vt_stream_t s) {
   if (!pred || !target || !dpred || !loss || n < 1) return vt_fail(VT_ERR_ARG, "vt_mse_loss: bad argument");
-  if (dt == VT_F32) hipLaunchKernelGGL(mse_kernel<float>, dim3(1), dim3(256), 0, (hipStream_t)s, (const float*)pred, target, (float*)dpred, loss, n);
-  else if (dt == VT_BF16) hipLaunchKernelGGL(mse_kernel<bf16_t>, dim3(1), dim3(256), 0, (hipStream_t)s, (const bf16_t*)pred, target, (bf16_t*)dpred, loss, n);
+  if (dt == VT_F32) hipLaunchKernelGGL((mse_kernel<float, false>), dim3(1), dim3(256), 0, (hipStream_t)s, (const float*)pred, target, (float*)dpred, loss, n, 1.0f);
+  else if (dt == VT_BF16) hipLaunchKernelGGL((mse_kernel<bf16_t, false>), dim3(1), dim3(256), 0, (hipStream_t)s, (const bf16_t*)pred, target, (bf16_t*)dpred, loss, n, 1.0f);
+  else if (dt == VT_F16) hipLaunchKernelGGL((mse_kernel<half_t, false>), dim3(1), dim3(256), 0, (hipStream_t)s, (const half_t*)pred, target, (half_t*)dpred, loss, n, 1.0f);
   else return BAD_DT("vt_mse_loss");
+  return LAUNCH_OK();
+}
+int vt_mse_loss_scaled(const void* pred, const float* target, void* dpred, float* loss, long n, int dt, float grad_scale, vt_stream_t s) {
+  if (!pred || !target || !dpred || !loss || n < 1 || !(grad_scale > 0.f) || isinf(grad_scale)) return vt_fail(VT_ERR_ARG, "vt_mse_loss_scaled: bad argument");
+  if (dt == VT_F32) hipLaunchKernelGGL((mse_kernel<float, true>), dim3(1), dim3(256), 0, (hipStream_t)s, (const float*)pred, target, (float*)dpred, loss, n, grad_scale);
+  else if (dt == VT_BF16) hipLaunchKernelGGL((mse_kernel<bf16_t, true>), dim3(1), dim3(256), 0, (hipStream_t)s, (const bf16_t*)pred, target, (bf16_t*)dpred, loss, n, grad_scale);
+  else if (dt == VT_F16) hipLaunchKernelGGL((mse_kernel<half_t, true>), dim3(1), dim3(256), 0, (hipStream_t)s, (const half_t*)pred, target, (half_t*)dpred, loss, n, grad_scale);
+  else return BAD_DT("vt_mse_loss_scaled");
   return LAUNCH_OK();
 }

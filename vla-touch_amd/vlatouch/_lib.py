@@ -296,6 +296,8 @@ SIGNATURES = {
     "vt_copy_cols_dt": (_I, [_P, _L, _L, _P, _L, _L, _L, _L, _I, _P]),
     "vt_grad_clip_multi": (_I, [_P, _I, _L, _F, _P, _P, _P]),
     "vt_mse_loss": (_I, [_P, _P, _P, _P, _L, _I, _P]),
+    "vt_mse_loss_scaled": (_I, [_P, _P, _P, _P, _L, _I, _F, _P]),
+    "vt_grad_unscale_clip_multi": (_I, [_P, _I, _L, _F, _F, _P, _P, _P, _P]),
     "vt_grad_accum_multi": (_I, [_P, _P, _I, _L, _F, _I, _P]),
     "vt_ema_multi": (_I, [_P, _I, _L, _P, _P]),
     "vt_grad_fold_pack_multi": (_I, [_P, _P, _I, _L, _F, _I, _P, _P]),

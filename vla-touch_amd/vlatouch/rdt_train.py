@@ -12,7 +12,8 @@ every Linear — forward, data gradient, weight gradient — is a vt_gemm call i
 split-K for the long reductions), the attention forward is vt_attention, the norms vt_rownorm / vt_headnorm, and everything autograd would
 add is csrc/vt_train_rdt.hip.  The forward keeps what the backward reads (block inputs, pre-norm q / k, normed q / k / v, attention outputs,
 FFN pre-activations); the image K / V of the odd blocks are kept, not recomputed.  Orchestration is host Python like the reference's loop.
-`precision="fp32"` is the parity mode.  `precision="bf16"` is the reference's execution dtype: bf16 copies of the Linear weights (and of their
+`precision="fp32"` is the parity mode.  `precision="fp16"` (with `loss_scale=`) is the bf16 mode on IEEE half with GradScaler's dynamic loss
+scaling and step skipping (the reference's --mixed_precision fp16; LossScaler below).  `precision="bf16"` is the reference's execution dtype: bf16 copies of the Linear weights (and of their
 transposes) refreshed after each optimizer step, bf16 activations, activation gradients and MFMA operands, fp32 accumulators, fp32 master
 weights / gradients / moments / EMA (what DeepSpeed's bf16 mode keeps); norm gains, biases and position embeddings are read in fp32.
 
@@ -43,6 +44,8 @@ LR_SCHEDULERS = ("constant", "constant_with_warmup")
 PREDICTION_TYPES = ("sample", "epsilon")
 OPTIMIZERS = ("adamw", "adamw8bit")
 COMM_DTYPES = ("fp32", "bf16")
+PRECISIONS = ("fp32", "bf16", "fp16")
+LOSS_SCALE_DEFAULTS = dict(init_scale=65536.0, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000)      # torch.amp.GradScaler's
 
 
 # ---------------------------------------------------------------------------------------------- host-side schedules
@@ -70,14 +73,102 @@ def lr_at(base: float, scheduler: str, steps_done: int, warmup: int) -> float:
     raise ValueError(f"lr_scheduler must be one of {LR_SCHEDULERS}, got {scheduler!r}")
 
 
+# ---------------------------------------------------------------------------------------------- loss scaling (host)
+def _f32(x: float) -> float:
+    """x rounded to fp32: GradScaler keeps its scale in an fp32 tensor, so every product below is an fp32 one."""
+    return float(torch.tensor(x, dtype=torch.float64).to(F32))
+
+
+def inv_scale(scale: float) -> float:
+    """float(1 / double(S)), as GradScaler._unscale_grads_ forms it (`self._scale.double().reciprocal().float()`)."""
+    return _f32(1.0 / _f32(scale))                     # the scale is an fp32 tensor there
+
+
+def loss_scale_settings(loss_scale) -> dict:
+    """RdtTrainer's `loss_scale` argument -> {init_scale, growth_factor, backoff_factor, growth_interval, dynamic}; ValueError for anything
+    else.  "dynamic": GradScaler's defaults; a dict: any of its four keys over the defaults; a positive finite number: a static scale (it
+    never changes, an overflow still skips the step)."""
+    out = dict(LOSS_SCALE_DEFAULTS, dynamic=True)
+    if isinstance(loss_scale, str):
+        if loss_scale != "dynamic":
+            raise ValueError(f"loss_scale must be 'dynamic', a dict of {sorted(LOSS_SCALE_DEFAULTS)} or a positive finite number, got {loss_scale!r}")
+    elif isinstance(loss_scale, dict):
+        unknown = sorted(set(loss_scale) - set(LOSS_SCALE_DEFAULTS))
+        if unknown:
+            raise ValueError(f"loss_scale: unknown keys {unknown} (known: {sorted(LOSS_SCALE_DEFAULTS)})")
+        out.update(loss_scale)
+    elif isinstance(loss_scale, (int, float)) and not isinstance(loss_scale, bool):
+        out.update(init_scale=loss_scale, dynamic=False)
+    else:
+        raise ValueError(f"loss_scale must be 'dynamic', a dict of {sorted(LOSS_SCALE_DEFAULTS)} or a positive finite number, got {loss_scale!r}")
+    for key in ("init_scale", "growth_factor", "backoff_factor"):
+        v = out[key]
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+            raise ValueError(f"loss_scale: {key} must be a finite number, got {v!r}")
+        out[key] = float(v)
+    if not out["init_scale"] > 0.0 or not math.isfinite(_f32(out["init_scale"])) or _f32(out["init_scale"]) == 0.0:
+        raise ValueError(f"loss_scale: the scale must be positive and finite in fp32, got {out['init_scale']!r}")
+    if not out["growth_factor"] > 1.0:
+        raise ValueError(f"loss_scale: growth_factor must be > 1, got {out['growth_factor']!r}")
+    if not 0.0 < out["backoff_factor"] < 1.0:
+        raise ValueError(f"loss_scale: backoff_factor must be in (0, 1), got {out['backoff_factor']!r}")
+    gi = out["growth_interval"]
+    if isinstance(gi, bool) or not isinstance(gi, (int, float)) or int(gi) != gi or gi < 1:
+        raise ValueError(f"loss_scale: growth_interval must be an integer >= 1, got {gi!r}")
+    out["growth_interval"] = int(gi)
+    return out
+
+
+class LossScaler:
+    """torch.amp.GradScaler's scale arithmetic on the host (torch/amp/grad_scaler.py `update`, ATen _amp_update_scale_), in fp32 like its
+    scale tensor: an overflow multiplies the scale by backoff_factor and clears the tracker; a clean step advances the tracker and, when it
+    reaches growth_interval, multiplies the scale by growth_factor (unless that would leave fp32's range) and clears it.  No floor.  A static
+    scaler (`dynamic` False) counts the same but never changes the scale.  tests/loss_scale_ref.py pins this against torch."""
+
+    def __init__(self, settings: dict):
+        self.settings = dict(settings)
+        self.reset()
+
+    def reset(self) -> None:
+        self.scale = _f32(self.settings["init_scale"])
+        self.growth_tracker = 0
+        self.skipped_steps = 0
+        self.skipped_nonfinite_loss = 0
+
+    def update(self, found_inf: bool) -> None:
+        st = self.settings
+        if found_inf:
+            self.skipped_steps += 1
+            self.growth_tracker = 0
+            if st["dynamic"]:
+                self.scale = _f32(self.scale * _f32(st["backoff_factor"]))
+            return
+        self.growth_tracker += 1
+        if self.growth_tracker == st["growth_interval"]:
+            self.growth_tracker = 0
+            grown = _f32(self.scale * _f32(st["growth_factor"]))
+            if st["dynamic"] and math.isfinite(grown):
+                self.scale = grown
+
+    def state(self) -> dict:
+        return dict(scale=self.scale, growth_tracker=self.growth_tracker, skipped_steps=self.skipped_steps,
+                    skipped_nonfinite_loss=self.skipped_nonfinite_loss, settings=dict(self.settings))
+
+    def load_state(self, st: dict) -> None:
+        self.settings = loss_scale_settings({k: st["settings"][k] for k in LOSS_SCALE_DEFAULTS})
+        self.settings["dynamic"] = bool(st["settings"]["dynamic"])
+        self.scale, self.growth_tracker = _f32(st["scale"]), int(st["growth_tracker"])
+        self.skipped_steps, self.skipped_nonfinite_loss = int(st["skipped_steps"]), int(st["skipped_nonfinite_loss"])
+
+
 # ---------------------------------------------------------------------------------------------- primitive wrappers
-# Activations are fp32 or bf16 tensors; every wrapper takes the dtype from its operands.  Sums (weight / bias / gain gradients) are always fp32.
+# Activations are fp32, bf16 or fp16 tensors; every wrapper takes the dtype from its operands.  Sums (weight / bias / gain gradients) are always fp32.
 def _dt(t: torch.Tensor) -> int:
     return L.dt_code(t.dtype)
 
 
 def transpose_pad(x2d: torch.Tensor) -> torch.Tensor:
-    """[M, N] -> [N, Mp] with zero padding, Mp = M rounded up to the GEMM's reduction alignment (4 fp32, 8 bf16): the operand form of a
+    """[M, N] -> [N, Mp] with zero padding, Mp = M rounded up to the GEMM's reduction alignment (4 fp32, 8 bf16 / fp16): the operand form of a
     weight-gradient product (reduction over the M token rows) and of a data-gradient product (W -> W^T)."""
     M, N = x2d.shape
     al = 4 if x2d.dtype == F32 else 8
@@ -152,9 +243,9 @@ ATTENTION_BACKWARDS = ("wave", "mfma")
 
 
 def attention_bwd(q, k, v, do, dq, dk, dv, *, kmask: Optional[torch.Tensor] = None, scale: Optional[float] = None, kernel: str = "wave") -> torch.Tensor:
-    """q, do, dq [B, Nq, H, 64]; k, v, dk, dv [B, Nk, H, 64] (any strides with unit inner stride, one dtype: fp32 or bf16); kmask [B, Nk] uint8.
-    kernel="wave": vt_attention_bwd (fp32 probabilities, one wave per row).  kernel="mfma": vt_attention_bwd_mfma (bf16 operands, Nq <= 128,
-    strides in multiples of 8: P and dS are rounded to bf16, csrc/vt_attn_bwd.hip); a shape or dtype it does not take raises, nothing falls back.
+    """q, do, dq [B, Nq, H, 64]; k, v, dk, dv [B, Nk, H, 64] (any strides with unit inner stride, one dtype: fp32, bf16 or fp16); kmask [B, Nk] uint8.
+    kernel="wave": vt_attention_bwd (fp32 probabilities, one wave per row).  kernel="mfma": vt_attention_bwd_mfma (bf16 or fp16 operands,
+    Nq <= 128, strides in multiples of 8: P and dS are rounded to the operands' type, csrc/vt_attn_bwd.hip); a shape or dtype it does not take raises, nothing falls back.
     -> the row statistics [B * H * Nq, 3] = (max, 1 / sum, delta)."""
     if kernel not in ATTENTION_BACKWARDS:
         raise ValueError(f"attention_bwd: kernel must be one of {ATTENTION_BACKWARDS}, got {kernel!r}")
@@ -174,8 +265,8 @@ def attention_bwd(q, k, v, do, dq, dk, dv, *, kmask: Optional[torch.Tensor] = No
     p.B, p.H, p.Nq, p.Nk, p.hd, p.dtype = B, H, Nq, Nk, 64, L.dt_code(q.dtype)
     p.scale = scale if scale is not None else hd ** -0.5
     if kernel == "mfma":
-        if q.dtype != torch.bfloat16:
-            raise ValueError(f"attention_bwd: kernel='mfma' takes bf16 tensors, got {q.dtype}")
+        if q.dtype not in (torch.bfloat16, torch.float16):
+            raise ValueError(f"attention_bwd: kernel='mfma' takes bf16 or fp16 tensors, got {q.dtype}")
         nbytes = L.lib().vt_attention_bwd_mfma_ws_bytes(B, H, Nq, Nk)
         if nbytes < 0:
             raise ValueError(f"attention_bwd: kernel='mfma' does not take B={B}, H={H}, Nq={Nq}, Nk={Nk} (1 <= Nq <= 128, B * H <= 65535)")
@@ -214,9 +305,14 @@ def add_rowvec_(a2d: torch.Tensor, v: torch.Tensor) -> None:
     L.check(L.lib().vt_add_rowvec_(L.ptr(a2d), _dt(a2d), L.ptr(v), rows, cols, _sp(a2d.device)), "vt_add_rowvec_")
 
 
-def mse_loss(pred: torch.Tensor, target: torch.Tensor):
-    """pred (activation dtype), target fp32 -> (loss [1] fp32, d pred in pred's dtype)."""
+def mse_loss(pred: torch.Tensor, target: torch.Tensor, grad_scale: Optional[float] = None):
+    """pred (activation dtype), target fp32 -> (loss [1] fp32, d pred in pred's dtype).  grad_scale (fp16 training): d pred is multiplied by
+    it before its one rounding (vt_mse_loss_scaled); the loss is not."""
     dpred, loss = torch.empty_like(pred), _empty((1,), pred.device)
+    if grad_scale is not None:
+        L.check(L.lib().vt_mse_loss_scaled(L.ptr(pred), L.ptr(target), L.ptr(dpred), L.ptr(loss), pred.numel(), _dt(pred), grad_scale, _sp(pred.device)),
+                "vt_mse_loss_scaled")
+        return loss, dpred
     L.check(L.lib().vt_mse_loss(L.ptr(pred), L.ptr(target), L.ptr(dpred), L.ptr(loss), pred.numel(), _dt(pred), _sp(pred.device)), "vt_mse_loss")
     return loss, dpred
 
@@ -298,6 +394,14 @@ class RdtTrainer:
     live in one store, `opt_state` (Moments32 or adam8.Moments8: zero state, table columns, the AdamW + EMA launch, checkpoint files, byte count);
     `moments(name)` reads them as fp32.
 
+    precision="fp16" with loss_scale= ("dynamic", a dict of GradScaler's init_scale / growth_factor / backoff_factor / growth_interval, or a
+    positive number for a static scale) is torch.amp.GradScaler around the bf16 mode's step on IEEE half: dL/dpred is multiplied by the scale S
+    (the loss is reported unscaled), the accumulators and the exchange hold scaled gradients, and optimizer_step unscales, checks and clips in
+    one launch group (vt_grad_unscale_clip_multi), reads the overflow flag, the norm and the loss in one small copy and either steps or skips:
+    a skipped step moves no parameter, moment, step_count or lr, runs the EMA update alone, multiplies S by backoff_factor and closes the
+    window.  `loss_scale_value`, `growth_tracker`, `skipped_steps`, `skipped_nonfinite_loss`, `last_step_skipped` read the state;
+    `global_step` counts skipped steps too, as the reference's does.
+
     process_group: a torch.distributed group of W ranks, one process per GPU, for data-parallel training with replicated state (None, the
     default, is the one-process trainer: same launches, same bits).  The constructor is then collective: the ranks compare parameter names and
     shapes, gradient_accumulation_steps, precision, optimizer, comm_dtype and attention_backward, every rank raising ValueError with the
@@ -312,9 +416,15 @@ class RdtTrainer:
                  betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, max_grad_norm: float = 1.0, lr_scheduler: str = "constant",
                  lr_warmup_steps: int = 500, ema: Optional[dict] = None, config: Optional[dict] = None, gradient_accumulation_steps: int = 1,
                  optimizer: str = "adamw", attention_backward: str = "wave", process_group=None, comm_dtype: str = "fp32",
-                 comm_bucket_bytes: int = 256 << 20, device="cuda"):
-        if precision not in ("fp32", "bf16"):
-            raise ValueError(f"precision must be 'fp32' or 'bf16', got {precision!r} (no fp16 training mode: its gradients underflow without loss scaling)")
+                 comm_bucket_bytes: int = 256 << 20, loss_scale=None, device="cuda"):
+        if precision not in PRECISIONS:
+            raise ValueError(f"precision must be one of {PRECISIONS}, got {precision!r}")
+        if precision == "fp16" and loss_scale is None:
+            raise ValueError("precision='fp16' needs loss_scale= ('dynamic', a dict of GradScaler's settings, or a static scale): its gradients "
+                             "underflow without loss scaling")
+        if precision != "fp16" and loss_scale is not None:
+            raise ValueError(f"loss_scale belongs to precision='fp16', not {precision!r}")
+        scale_settings = loss_scale_settings(loss_scale) if loss_scale is not None else None
         if prediction_type not in PREDICTION_TYPES:
             raise ValueError(f"Unsupported prediction type {prediction_type}")
         if rms_mode not in ("meansq", "var"):
@@ -323,8 +433,8 @@ class RdtTrainer:
             raise ValueError(f"optimizer must be one of {OPTIMIZERS}, got {optimizer!r}")
         if attention_backward not in ATTENTION_BACKWARDS:
             raise ValueError(f"attention_backward must be one of {ATTENTION_BACKWARDS}, got {attention_backward!r}")
-        if attention_backward == "mfma" and precision != "bf16":
-            raise ValueError("attention_backward='mfma' is a bf16 kernel: it needs precision='bf16' ('wave' is the fp32 path)")
+        if attention_backward == "mfma" and precision == "fp32":
+            raise ValueError("attention_backward='mfma' is a 16-bit kernel: it needs precision='bf16' or 'fp16' ('wave' is the fp32 path)")
         if attention_backward == "mfma" and horizon + 3 > 128:
             raise ValueError(f"attention_backward='mfma' holds at most 128 query rows, horizon + 3 = {horizon + 3}")
         if comm_dtype not in COMM_DTYPES:
@@ -351,7 +461,8 @@ class RdtTrainer:
             digest = hashlib.sha256(repr([(k, tuple(v.shape)) for k, v in self.p.items()]).encode()).hexdigest()
             diff = D.differing_field({"parameter names and shapes": digest, "gradient_accumulation_steps": int(gradient_accumulation_steps),
                                       "precision": precision, "optimizer": optimizer, "comm_dtype": comm_dtype,
-                                      "attention_backward": attention_backward}, process_group)
+                                      "attention_backward": attention_backward,
+                                      **({} if scale_settings is None else {"loss_scale": repr(sorted(scale_settings.items()))})}, process_group)
             if diff is not None:
                 raise ValueError(f"RdtTrainer: the ranks of the process group disagree on {diff[0]}: {diff[1]}")
             D.broadcast_tensors(self.p.values(), src=dist.get_global_rank(process_group, 0), group=process_group)
@@ -371,8 +482,10 @@ class RdtTrainer:
         self.adaptors = {n: self._adaptor_layers(n) for n in ("lang_adaptor", "img_adaptor", "state_adaptor")}
         self.precision = precision
         self.attention_backward = attention_backward          # an execution choice, not state: checkpoints do not record it
-        self.adt = F32 if precision == "fp32" else torch.bfloat16     # dtype of activations, activation gradients and MFMA operands
-        self.w16: Dict[str, torch.Tensor] = {}                        # bf16 mode: copies of the Linear weights and of their transposes,
+        self.adt = {"fp32": F32, "bf16": torch.bfloat16, "fp16": torch.float16}[precision]      # dtype of activations, activation gradients and MFMA operands
+        self.scaler: Optional[LossScaler] = LossScaler(scale_settings) if scale_settings is not None else None      # fp16: GradScaler's state
+        self.last_step_skipped = False                                # the last optimizer_step found a non-finite gradient and took no step
+        self.w16: Dict[str, torch.Tensor] = {}                        # 16-bit modes: copies of the Linear weights and of their transposes,
         self.w16t: Dict[str, torch.Tensor] = {}                       # refreshed after every optimizer step
         self._refresh16()
         self.base_lr, self.lr, self.wd, self.betas, self.eps, self.max_grad_norm = lr, lr, weight_decay, betas, eps, max_grad_norm
@@ -390,7 +503,8 @@ class RdtTrainer:
         shapes = OrderedDict((k, v.shape) for k, v in self.p.items())     # still the initial ones then), so a trainer that only evaluates the loss holds one copy
         self.opt_state = adam8.Moments8(shapes, dev) if optimizer == "adamw8bit" else Moments32(shapes, dev)
         self.shadow: Dict[str, torch.Tensor] = {}
-        self._norm_coef = torch.zeros(2, dtype=F32, device=dev)
+        # [norm, clip coefficient]; fp16: + [overflow flag as int32 bits, the last micro-batch's loss], what optimizer_step reads in one copy
+        self._norm_coef = torch.zeros(2 if self.scaler is None else 4, dtype=F32, device=dev)
         self._table_key = None
         self.last_loss: Optional[torch.Tensor] = None
         self.weights_version = 0                              # optimizer steps and load_checkpoint calls: changes of the master parameters
@@ -422,8 +536,14 @@ class RdtTrainer:
 
     @property
     def global_step(self) -> int:
-        """Optimizer steps taken (train.py's global_step)."""
-        return self.step_count
+        """Optimizer steps taken or, in fp16 mode, skipped: train.py:451-453 counts every sync_gradients, whatever the scaler decided."""
+        return self.step_count + self.skipped_steps
+
+    # fp16 mode's GradScaler state, read-only (1.0 / zeros for the other precisions)
+    loss_scale_value = property(lambda self: self.scaler.scale if self.scaler is not None else 1.0)
+    growth_tracker = property(lambda self: self.scaler.growth_tracker if self.scaler is not None else 0)
+    skipped_steps = property(lambda self: self.scaler.skipped_steps if self.scaler is not None else 0)
+    skipped_nonfinite_loss = property(lambda self: self.scaler.skipped_nonfinite_loss if self.scaler is not None else 0)
 
     @property
     def grad_norm(self) -> torch.Tensor:
@@ -569,7 +689,7 @@ class RdtTrainer:
         out = self._linear(f"{fl}.ffn_final.fc2", gf)                                 # [B*N, A]
         pred = _cols(out.view(B, N * A), 3 * A, hor * A)                               # x[:, -horizon:]
         target = (act_gt if self.prediction_type == "sample" else noise).view(B, hor * A)
-        loss, dpred = mse_loss(pred, target)
+        loss, dpred = mse_loss(pred, target, None if self.scaler is None else self.scaler.scale)      # fp16: d pred carries the loss scale
         self.last_loss = loss.reshape(())
         self.last_pred = pred.view(B, hor, A)
         if not backward:
@@ -703,6 +823,8 @@ class RdtTrainer:
         if self._accumulates and self.micro_step != self.k:
             raise RuntimeError(f"optimizer_step needs a full accumulation window ({self.micro_step} of {self.k} micro-batches accumulated)")
         tab, n, chunks = self._table()
+        if self.scaler is not None:
+            return self._optimizer_step_scaled(tab, n, chunks)
         self.lr = lr_at(self.base_lr, self.lr_scheduler, self.step_count, self.lr_warmup_steps * self.k)      # train.py:302 scales the warm-up by k
         self.step_count += 1
         self.ema_updates += 1
@@ -713,6 +835,35 @@ class RdtTrainer:
         self._refresh16()
         self.micro_step, self.sync_gradients = 0, True
         self.weights_version += 1
+        self.shadow_version += 1
+
+    def _optimizer_step_scaled(self, tab, n, chunks) -> None:
+        """fp16: accelerator.clip_grad_norm_ (GradScaler.unscale_ first) -> scaler.step(optimizer) -> scaler.update -> scheduler -> EMAModel.step.
+        One launch group unscales, checks and clips; the host reads (norm, coefficient, flag, loss) once, as GradScaler.step synchronises,
+        and takes the step or skips it: a skip runs the EMA update alone (train.py:448 is unconditional) and leaves parameters, moments,
+        step_count and lr where they were (AcceleratedScheduler does not step after a skipped optimizer step)."""
+        sc = self.scaler
+        L.check(L.lib().vt_grad_unscale_clip_multi(L.ptr(tab), n, chunks, self.max_grad_norm, inv_scale(sc.scale), L.ptr(self._chunk_part),
+                                                   L.ptr(self._norm_coef), C.c_void_p(self._norm_coef.data_ptr() + 8), _sp(self.device)),
+                "vt_grad_unscale_clip_multi")
+        if self.last_loss is not None:
+            self._norm_coef[3:4].copy_(self.last_loss.reshape(1))
+        host = self._norm_coef.cpu()                              # the mode's one host read
+        found_inf = int(host.view(torch.int32)[2]) != 0
+        self.ema_updates += 1
+        if found_inf:
+            L.check(L.lib().vt_ema_multi(L.ptr(tab), n, chunks, L.ptr(self._hyper(max(1, self.step_count))), _sp(self.device)), "vt_ema_multi")
+            if self.last_loss is not None and not math.isfinite(float(host[3])):
+                sc.skipped_nonfinite_loss += 1                    # the forward overflowed: no smaller scale repairs that
+        else:
+            self.lr = lr_at(self.base_lr, self.lr_scheduler, self.step_count, self.lr_warmup_steps * self.k)
+            self.step_count += 1
+            self.opt_state.step(tab, n, chunks, self._hyper(self.step_count), self.betas, self.eps, self.wd)
+            self._refresh16()
+            self.weights_version += 1
+        sc.update(found_inf)
+        self.last_step_skipped = found_inf
+        self.micro_step, self.sync_gradients = 0, True
         self.shadow_version += 1
 
     def moments(self, name: str):
@@ -838,7 +989,7 @@ class RdtTrainer:
     def save_checkpoint(self, path: str) -> None:
         """`path`/checkpoint/{model,adam_m,adam_v}.safetensors (fp32 master weights and AdamW moments), `path`/ema/ (the averaged weights as
         RDTRunner.from_pretrained reads them: the reference's checkpoint-N/ema placement) and `path`/trainer_state.json (the counters, k,
-        precision, hyper-parameters, and for information `world_size` and `comm_dtype`: all state is replicated, so a checkpoint resumes under any
+        precision, hyper-parameters, in fp16 mode `loss_scale` = the scaler's scale, tracker, skip counters and settings, and for information `world_size` and `comm_dtype`: all state is replicated, so a checkpoint resumes under any
         world size).  Only between accumulation windows, where the reference saves.  optimizer="adamw8bit" writes
         checkpoint/adam8.safetensors in place of adam_m / adam_v (codes `m8.` / `v8.` and scales `am.` / `av.` + parameter name, fp32 moments
         `m.` / `v.` of the small tensors, the two code tables) and adds `optimizer` and `block` to trainer_state.json."""
@@ -857,6 +1008,8 @@ class RdtTrainer:
         state = dict(step_count=self.step_count, ema_updates=self.ema_updates, global_step=self.global_step, gradient_accumulation_steps=self.k,
                      precision=self.precision, hyper={n: getattr(self, n) for n in self._HYPER}, world_size=self.world, comm_dtype=self.comm_dtype,
                      **self.opt_state.state_json)
+        if self.scaler is not None:
+            state["loss_scale"] = self.scaler.state()
         with open(os.path.join(path, "trainer_state.json"), "w") as fjs:
             json.dump(state, fjs, indent=2)
 
@@ -880,6 +1033,12 @@ class RdtTrainer:
         for n, val in state["hyper"].items():
             setattr(self, n, tuple(val) if n == "betas" else val)
         self.step_count, self.ema_updates = state["step_count"], state["ema_updates"]
+        if self.scaler is not None:                               # an fp32 / bf16 checkpoint starts from init_scale; the other precisions ignore the key
+            if "loss_scale" in state:
+                self.scaler.load_state(state["loss_scale"])
+            else:
+                self.scaler.reset()
+            self.last_step_skipped = False
         self.micro_step, self.sync_gradients, self._table_key = 0, False, None
         self.lr = lr_at(self.base_lr, self.lr_scheduler, max(0, self.step_count - 1), self.lr_warmup_steps * self.k)
         self._refresh16()
@@ -1066,13 +1225,13 @@ def finetune(trainer: RdtTrainer, batches, *, max_train_steps: int, checkpointin
              dataset_id2name=None, sample_ema: bool = False, log=None, vision_encoder=None, text_encoder=None, preprocessor=None) -> List[torch.Tensor]:
     """The reference's loop (train.py:359-489) around `trainer.train_step`: every item of `batches` is one micro-batch, a mapping of train_step's
     keyword arguments, or the reference collator's mapping (recognised by its `states` key, which train_step does not take), which goes through
-    `prepare_batch` with the loop's `vision_encoder`, `text_encoder` and `preprocessor`.  Stops when `max_train_steps` optimizer steps are taken; writes `output_dir`/checkpoint-{global_step} every
-    `checkpointing_period` optimizer steps; `resume_from_checkpoint` = a checkpoint's name under `output_dir` or "latest" (a missing one starts a
+    `prepare_batch` with the loop's `vision_encoder`, `text_encoder` and `preprocessor`.  Stops when `global_step` reaches `max_train_steps` (optimizer steps taken or, in fp16 mode, skipped: the reference counts both); writes `output_dir`/checkpoint-{global_step} every
+    `checkpointing_period` of them; `resume_from_checkpoint` = a checkpoint's name under `output_dir` or "latest" (a missing one starts a
     new run, as there); ends with save_pretrained(output_dir) and the averaged weights in `output_dir`/ema.  Like the reference's loop it does
     not skip the batches an earlier run consumed: `batches` continues where the caller wants.  sample_period > 0: after every optimizer step with
     global_step % sample_period == 0, and after that step's checkpoint (train.py:455-475), `sample_eval` runs on `trainer.sampler(ema=sample_ema)`
     over `sample_batches` (iterated afresh at each visit; `vision_encoder` / `text_encoder` go to it for batches with `images` / `input_ids`)
-    and `log(metrics, global_step)` is called if given; the evaluation reads the weights and writes none.  -> the micro-batch losses (device tensors).
+    and `log(metrics, global_step)` is called if given (an fp16 trainer adds `loss_scale`, `skipped_steps` and `skipped_nonfinite_loss` to the metrics); the evaluation reads the weights and writes none.  -> the micro-batch losses (device tensors).
     A trainer built with a process group: every rank runs this loop on its own micro-batches (`EpisodeStore.batches(rank=, world_size=)`); rank 0
     alone writes the checkpoints and the final weights, with a barrier behind each write, and alone calls `log`; the sampling evaluation runs on
     every rank and is reduced over the group (`sample_eval(group=)`); a resume loads the checkpoint on every rank."""
@@ -1106,6 +1265,9 @@ def finetune(trainer: RdtTrainer, batches, *, max_train_steps: int, checkpointin
             metrics = sample_eval(trainer.sampler(ema=sample_ema), sample_batches, num_sample_batches=num_sample_batches,
                                   dataset_id2name=dataset_id2name, vision_encoder=vision_encoder, text_encoder=text_encoder, preprocessor=preprocessor,
                                   group=group)
+            if getattr(trainer, "scaler", None) is not None:   # fp16: where the scale stands and how often it backed off
+                metrics = dict(metrics, loss_scale=trainer.loss_scale_value, skipped_steps=trainer.skipped_steps,
+                               skipped_nonfinite_loss=trainer.skipped_nonfinite_loss)
             if log is not None and writer:
                 log(metrics, trainer.global_step)
     if output_dir is not None:
