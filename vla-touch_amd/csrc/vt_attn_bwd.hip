@@ -403,16 +403,11 @@ int vt_attention_bwd_mfma(const VtAttnBwdParams* p, void* ws2, long ws2_bytes, v
   float* part = dqpart + rows * nruns * 64;                     // [B * H][nruns][Nq][3]
   const dim3 grid((unsigned)nruns, (unsigned)(p->B * p->H));
   const dim3 gc((unsigned)((rows + 255) / 256)), gq((unsigned)((rows + 3) / 4));
-  if (p->dtype == VT_BF16) {
-    hipLaunchKernelGGL(attn_bwd_mfma_stats_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)s, *p, part, nruns);
+  DISPATCH_T16(p->dtype, T, {                                   // bf16 or fp16: checked above
+    hipLaunchKernelGGL(attn_bwd_mfma_stats_kernel<T>, grid, dim3(256), 0, (hipStream_t)s, *p, part, nruns);
     hipLaunchKernelGGL(attn_bwd_mfma_combine_kernel, gc, dim3(256), 0, (hipStream_t)s, part, p->ws, rows, p->Nq, nruns);
-    hipLaunchKernelGGL(attn_bwd_mfma_main_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)s, *p, dqpart, nruns);
-    hipLaunchKernelGGL(attn_bwd_mfma_dq_kernel<bf16_t>, gq, dim3(256), 0, (hipStream_t)s, *p, dqpart, nruns);
-  } else {
-    hipLaunchKernelGGL(attn_bwd_mfma_stats_kernel<half_t>, grid, dim3(256), 0, (hipStream_t)s, *p, part, nruns);
-    hipLaunchKernelGGL(attn_bwd_mfma_combine_kernel, gc, dim3(256), 0, (hipStream_t)s, part, p->ws, rows, p->Nq, nruns);
-    hipLaunchKernelGGL(attn_bwd_mfma_main_kernel<half_t>, grid, dim3(256), 0, (hipStream_t)s, *p, dqpart, nruns);
-    hipLaunchKernelGGL(attn_bwd_mfma_dq_kernel<half_t>, gq, dim3(256), 0, (hipStream_t)s, *p, dqpart, nruns);
-  }
+    hipLaunchKernelGGL(attn_bwd_mfma_main_kernel<T>, grid, dim3(256), 0, (hipStream_t)s, *p, dqpart, nruns);
+    hipLaunchKernelGGL(attn_bwd_mfma_dq_kernel<T>, gq, dim3(256), 0, (hipStream_t)s, *p, dqpart, nruns);
+  })
   return vt_check_launch();
 }

@@ -192,3 +192,12 @@ __device__ __forceinline__ void vt_range_note(unsigned* flag, unsigned bit) {
 __device__ __forceinline__ bool vt_nonfinite(float v) { return !(fabsf(v) <= 3.4028234664e38f); }      // inf or NaN
 
 static inline int vt_check_launch() { return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_LAUNCH; }
+
+// Host-side dispatch on a storage dtype code: the statement is compiled once per element type, with `T` naming it.  An unknown code falls to
+// bf16_t, so an entry point that has to refuse one tests the code first (vt_is_act_dtype, or a condition of its own).  DISPATCH_T16 is the
+// form for the kernels that exist for the two 16-bit types only (nothing is instantiated for float).
+#define DISPATCH_T(dt, T, ...) \
+  if ((dt) == VT_F32) { using T = float; __VA_ARGS__; } else if ((dt) == VT_F16) { using T = half_t; __VA_ARGS__; } else { using T = bf16_t; __VA_ARGS__; }
+#define DISPATCH_T16(dt, T, ...) \
+  if ((dt) == VT_F16) { using T = half_t; __VA_ARGS__; } else { using T = bf16_t; __VA_ARGS__; }
+static inline bool vt_is_act_dtype(int dt) { return dt == VT_F32 || dt == VT_BF16 || dt == VT_F16; }      // the activation types of training: what DISPATCH_T names

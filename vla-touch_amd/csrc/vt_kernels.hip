@@ -668,32 +668,24 @@ inline dim3 g1(long n, int bs = 256) { return dim3((unsigned)((n + bs - 1) / bs)
 }  // namespace
 
 // =============================================================================== host launchers
-#define DISPATCH_T(dt, T, ...) \
-  if ((dt) == VT_F32) { using T = float; __VA_ARGS__; } else if ((dt) == VT_F16) { using T = half_t; __VA_ARGS__; } else { using T = bf16_t; __VA_ARGS__; }
-
+// (DISPATCH_T: vt_common.h)
 int vt_k_rownorm(const void* x, int xdt, long ldx, void* y, int ydt, long ldy, const float* w, const float* b, int rows, int D,
                  float eps, int mode, hipStream_t s, unsigned* range_flag) {
   if (xdt == VT_F32 && D > 2048 && D <= 4096 && D % 4 == 0 && rows > 0 && (ldx % 4) == 0 && (ldy % 4) == 0) {   // T5-XXL width: block per row, 4 float4 per thread
-    if (ydt == VT_F32) hipLaunchKernelGGL((rownorm_block_kernel<float, 4>), dim3(rows), dim3(256), 0, s, (const float*)x, ldx, (float*)y, ldy, w, b, D, eps, mode, range_flag);
-    else if (ydt == VT_F16) hipLaunchKernelGGL((rownorm_block_kernel<half_t, 4>), dim3(rows), dim3(256), 0, s, (const float*)x, ldx, (half_t*)y, ldy, w, b, D, eps, mode, range_flag);
-    else hipLaunchKernelGGL((rownorm_block_kernel<bf16_t, 4>), dim3(rows), dim3(256), 0, s, (const float*)x, ldx, (bf16_t*)y, ldy, w, b, D, eps, mode, range_flag);
+    DISPATCH_T(ydt, TO, hipLaunchKernelGGL((rownorm_block_kernel<TO, 4>), dim3(rows), dim3(256), 0, s, (const float*)x, ldx, (TO*)y, ldy, w, b, D, eps, mode, range_flag))
     return vt_check_launch();
   }
   if (D % 4 || D > 64 * 4 * 8 || rows <= 0) return VT_ERR_ARG;
   constexpr int wave_rows = 8192;                 // rows from which the wave-per-row kernel takes over
   if (xdt == VT_F32 && D >= 512 && rows >= wave_rows && (ldx % 4) == 0 && (ldy % 4) == 0) {
     const dim3 grid((unsigned)((rows + 3) / 4));
-#define VT_RNW(TO, NV) hipLaunchKernelGGL((rownorm_wave_kernel<TO, NV>), grid, dim3(256), 0, s, (const float*)x, ldx, (TO*)y, ldy, w, b, rows, D, eps, mode, range_flag)
-#define VT_RNW_T(TO) do { if (D <= 1024) VT_RNW(TO, 4); else if (D <= 1280) VT_RNW(TO, 5); else VT_RNW(TO, 8); } while (0)
-    if (ydt == VT_F32) VT_RNW_T(float); else if (ydt == VT_F16) VT_RNW_T(half_t); else VT_RNW_T(bf16_t);
-#undef VT_RNW_T
+#define VT_RNW(NV) hipLaunchKernelGGL((rownorm_wave_kernel<TO, NV>), grid, dim3(256), 0, s, (const float*)x, ldx, (TO*)y, ldy, w, b, rows, D, eps, mode, range_flag)
+    DISPATCH_T(ydt, TO, { if (D <= 1024) VT_RNW(4); else if (D <= 1280) VT_RNW(5); else VT_RNW(8); })
 #undef VT_RNW
     return vt_check_launch();
   }
   if (xdt == VT_F32 && D >= 512 && (rows >= 256 || D >= 1024) && (ldx % 4) == 0 && (ldy % 4) == 0) {    // block per row (also for few wide rows: latency)
-    if (ydt == VT_F32) hipLaunchKernelGGL((rownorm_block_kernel<float, 2>), dim3(rows), dim3(256), 0, s, (const float*)x, ldx, (float*)y, ldy, w, b, D, eps, mode, range_flag);
-    else if (ydt == VT_F16) hipLaunchKernelGGL((rownorm_block_kernel<half_t, 2>), dim3(rows), dim3(256), 0, s, (const float*)x, ldx, (half_t*)y, ldy, w, b, D, eps, mode, range_flag);
-    else hipLaunchKernelGGL((rownorm_block_kernel<bf16_t, 2>), dim3(rows), dim3(256), 0, s, (const float*)x, ldx, (bf16_t*)y, ldy, w, b, D, eps, mode, range_flag);
+    DISPATCH_T(ydt, TO, hipLaunchKernelGGL((rownorm_block_kernel<TO, 2>), dim3(rows), dim3(256), 0, s, (const float*)x, ldx, (TO*)y, ldy, w, b, D, eps, mode, range_flag))
     return vt_check_launch();
   }
   dim3 grid((rows + 3) / 4);

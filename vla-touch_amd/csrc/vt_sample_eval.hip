@@ -81,10 +81,8 @@ int vt_sample_metrics(const void* pred, int dt, const float* target, const float
   if (!pred || !target || !mask || !state_norm || !dataset_idx || !per_sample || !overall || !acc || !count || !ws)
     return vt_fail(VT_ERR_ARG, "vt_sample_metrics: null pointer");
   if (B < 1 || H < 1 || A < 1 || n_datasets < 1) return vt_fail(VT_ERR_ARG, "vt_sample_metrics: B, H, A and n_datasets must be >= 1");
-  if (dt == VT_F32) hipLaunchKernelGGL(sample_sums_kernel<float>, dim3(B), dim3(256), 0, (hipStream_t)s, (const float*)pred, target, mask, state_norm, ws, H, A);
-  else if (dt == VT_BF16) hipLaunchKernelGGL(sample_sums_kernel<bf16_t>, dim3(B), dim3(256), 0, (hipStream_t)s, (const bf16_t*)pred, target, mask, state_norm, ws, H, A);
-  else if (dt == VT_F16) hipLaunchKernelGGL(sample_sums_kernel<half_t>, dim3(B), dim3(256), 0, (hipStream_t)s, (const half_t*)pred, target, mask, state_norm, ws, H, A);
-  else return vt_fail(VT_ERR_UNSUPPORTED, "vt_sample_metrics: pred dtype must be fp32 (0), bf16 (1) or fp16 (3)");
+  if (!vt_is_act_dtype(dt)) return vt_fail(VT_ERR_UNSUPPORTED, "vt_sample_metrics: pred dtype must be fp32 (0), bf16 (1) or fp16 (3)");
+  DISPATCH_T(dt, T, hipLaunchKernelGGL(sample_sums_kernel<T>, dim3(B), dim3(256), 0, (hipStream_t)s, (const T*)pred, target, mask, state_norm, ws, H, A))
   hipLaunchKernelGGL(sample_fold_kernel, dim3(1), dim3(64), 0, (hipStream_t)s, (const double*)ws, dataset_idx, B, n_datasets, per_sample, overall, acc, count);
   return vt_check_launch();
 }

@@ -286,16 +286,16 @@ __global__ void copy_cols_t_kernel(const T* __restrict__ src, long lds_, long of
 }
 
 // ------------------------------------------------------------------------------------------------ global-norm clipping
-// The table is vt_adamw_ema_multi's (vt_optim.h: MtEntry, MT_CHUNK, mt_find); a block takes one chunk of one gradient.
-static_assert(16 * 256 == MT_CHUNK && 4 * 256 * 4 == MT_CHUNK, "the 16 scalar passes and the 4 float4 passes of 256 threads below walk one chunk");
+// The table is vt_adamw_ema_multi's (vt_optim.h: MtEntry, MT_CHUNK); a block takes one chunk of one gradient (mt_chunk).  The kernels of this
+// and the next three sections that take 128-bit words where their tensors are 16-byte aligned share the walk over a chunk too (mt_walk).
+static_assert(16 * 256 == MT_CHUNK, "the 16 scalar passes of 256 threads of sumsq_mt_kernel and scale_mt_kernel walk one chunk");
 __global__ __launch_bounds__(256) void sumsq_mt_kernel(const MtEntry* __restrict__ tab, int ntensors, float* __restrict__ part) {
   __shared__ float red[4];
-  const MtEntry e = tab[mt_find(tab, ntensors, blockIdx.x)];
-  const long base = ((long)blockIdx.x - e.first_chunk) * MT_CHUNK;
+  const MtChunk c = mt_chunk(tab, ntensors);
   float s = 0.f;
   for (int it = 0; it < 16; ++it) {
-    const long i = base + it * 256 + threadIdx.x;
-    if (i < e.n) { const float v = e.g[i]; s += v * v; }
+    const long i = c.base + it * 256 + threadIdx.x;
+    if (i < c.e.n) { const float v = c.e.g[i]; s += v * v; }
   }
   s = block_sum4(s, red);
   if (threadIdx.x == 0) part[blockIdx.x] = s;
@@ -313,45 +313,40 @@ __global__ __launch_bounds__(256) void clip_coef_kernel(const float* __restrict_
   }
 }
 __global__ __launch_bounds__(256) void scale_mt_kernel(const MtEntry* __restrict__ tab, int ntensors, const float* __restrict__ norm_coef) {
-  const MtEntry e = tab[mt_find(tab, ntensors, blockIdx.x)];
-  const long base = ((long)blockIdx.x - e.first_chunk) * MT_CHUNK;
-  const float c = norm_coef[1];
-  if (c >= 1.0f) return;                                       // torch multiplies by a coefficient clamped to 1: the same values
+  const MtChunk c = mt_chunk(tab, ntensors);
+  const float k = norm_coef[1];
+  if (k >= 1.0f) return;                                       // torch multiplies by a coefficient clamped to 1: the same values
   for (int it = 0; it < 16; ++it) {
-    const long i = base + it * 256 + threadIdx.x;
-    if (i < e.n) e.g[i] *= c;
+    const long i = c.base + it * 256 + threadIdx.x;
+    if (i < c.e.n) c.e.g[i] *= k;
   }
 }
 
 // fp16 training (dynamic loss scaling): the table's gradients are S times too large.  Pass 1 looks at every RAW element (found_inf |= !isfinite(g),
 // what torch's _amp_foreach_non_finite_check_and_unscale_ checks) and forms the chunk's sum of squares of u = g * inv_S; the flag is an integer OR (order
-// independent), the float partials keep sumsq_mt_kernel's fixed orders.  A chunk is read as 128-bit words where its tensor is 16-byte aligned.
-static_assert(4 * 256 * 4 == MT_CHUNK, "the 4 float4 passes of 256 threads of the two kernels below walk one chunk");
+// independent), the float partials have a fixed order of their own: a thread adds its 4 words of 4, not sumsq_mt_kernel's 16 scalars.  A word's
+// squares are rounded before they are added and the tail's are fused, which is what the compiler made of `s += u * u` when the norms of fp16
+// training were first recorded: written out (contract(off), fmaf) so that their last bits do not hang on where it chooses to contract.
 __global__ __launch_bounds__(256) void unscale_sumsq_mt_kernel(const MtEntry* __restrict__ tab, int ntensors, float inv_scale, float* __restrict__ part,
                                                                int* __restrict__ found_inf) {
   __shared__ float red[4];
-  const MtEntry e = tab[mt_find(tab, ntensors, blockIdx.x)];
-  const long base = ((long)blockIdx.x - e.first_chunk) * MT_CHUNK;
-  const long left = e.n - base;
-  const int cnt = left < MT_CHUNK ? (int)left : MT_CHUNK;
-  const float* __restrict__ g = e.g + base;
-  const int quads = (((size_t)g) & 15) == 0 ? cnt >> 2 : 0;
+  const MtChunk c = mt_chunk(tab, ntensors);
+  const float* __restrict__ g = c.e.g + c.base;
   float s = 0.f;
   bool bad = false;
-#pragma unroll
-  for (int it = 0; it < 4; ++it) {
-    const int j = it * 256 + threadIdx.x;
-    if (j >= quads) break;
-    const float4 v = reinterpret_cast<const float4*>(g)[j];
-    bad |= !(isfinite(v.x) && isfinite(v.y) && isfinite(v.z) && isfinite(v.w));
-    const float ux = v.x * inv_scale, uy = v.y * inv_scale, uz = v.z * inv_scale, uw = v.w * inv_scale;
-    s += ux * ux; s += uy * uy; s += uz * uz; s += uw * uw;
-  }
-  for (int i = quads * 4 + threadIdx.x; i < cnt; i += 256) {
-    const float v = g[i], u = v * inv_scale;
-    bad |= !isfinite(v);
-    s += u * u;
-  }
+  mt_walk(c.cnt, (((size_t)g) & 15) == 0,
+          [&](int j) {
+#pragma clang fp contract(off)
+            const float4 v = reinterpret_cast<const float4*>(g)[j];
+            bad |= !(isfinite(v.x) && isfinite(v.y) && isfinite(v.z) && isfinite(v.w));
+            const float ux = v.x * inv_scale, uy = v.y * inv_scale, uz = v.z * inv_scale, uw = v.w * inv_scale;
+            s += ux * ux; s += uy * uy; s += uz * uz; s += uw * uw;
+          },
+          [&](int i) {
+            const float v = g[i], u = v * inv_scale;
+            bad |= !isfinite(v);
+            s = fmaf(u, u, s);
+          });
   s = block_sum4(s, red);
   if (threadIdx.x == 0) part[blockIdx.x] = s;
   if (bad) atomicOr(found_inf, 1);
@@ -361,58 +356,45 @@ __global__ __launch_bounds__(256) void unscale_sumsq_mt_kernel(const MtEntry* __
 __global__ __launch_bounds__(256) void unscale_scale_mt_kernel(const MtEntry* __restrict__ tab, int ntensors, float inv_scale,
                                                                const float* __restrict__ norm_coef, const int* __restrict__ found_inf) {
   if (*found_inf) return;
-  const MtEntry e = tab[mt_find(tab, ntensors, blockIdx.x)];
-  const long base = ((long)blockIdx.x - e.first_chunk) * MT_CHUNK;
-  const long left = e.n - base;
-  const int cnt = left < MT_CHUNK ? (int)left : MT_CHUNK;
-  float* __restrict__ g = e.g + base;
-  const float c = norm_coef[1];
-  const int quads = (((size_t)g) & 15) == 0 ? cnt >> 2 : 0;
-#pragma unroll
-  for (int it = 0; it < 4; ++it) {
-    const int j = it * 256 + threadIdx.x;
-    if (j >= quads) break;
-    float4 v = reinterpret_cast<const float4*>(g)[j];
-    v.x = (v.x * inv_scale) * c; v.y = (v.y * inv_scale) * c; v.z = (v.z * inv_scale) * c; v.w = (v.w * inv_scale) * c;
-    reinterpret_cast<float4*>(g)[j] = v;
-  }
-  for (int i = quads * 4 + threadIdx.x; i < cnt; i += 256) g[i] = (g[i] * inv_scale) * c;
+  const MtChunk c = mt_chunk(tab, ntensors);
+  float* __restrict__ g = c.e.g + c.base;
+  const float k = norm_coef[1];
+  mt_walk(c.cnt, (((size_t)g) & 15) == 0,
+          [&](int j) {
+            float4 v = reinterpret_cast<const float4*>(g)[j];
+            v.x = (v.x * inv_scale) * k; v.y = (v.y * inv_scale) * k; v.z = (v.z * inv_scale) * k; v.w = (v.w * inv_scale) * k;
+            reinterpret_cast<float4*>(g)[j] = v;
+          },
+          [&](int i) { g[i] = (g[i] * inv_scale) * k; });
 }
 
 // ------------------------------------------------------------------------------------------------ gradient accumulation
 // Folds one micro-batch's fresh gradients (fresh[k], a second device array of pointers: they are new allocations every micro-batch) into the
 // persistent fp32 accumulators, which are the table's g column, so that the clip and AdamW kernels read the accumulated gradient from the
 // table as it stands.  accumulate = 0 stores g * scale (first micro-batch of a window: no zero pass, the accumulator is not read), otherwise
-// acc = fma(g, scale, acc): one rounding per element and micro-batch in a fixed order, no atomics.  A chunk is read and written as 128-bit
-// words where both tensors are 16-byte aligned (a chunk starts 16 KiB into its tensor, so the tensor's alignment is the chunk's); what is
-// left of n behind the last whole quad, or the whole chunk of an unaligned tensor, goes element by element.
+// acc = fma(g, scale, acc): one rounding per element and micro-batch in a fixed order, no atomics (vt_optim.h's grad_fold_elem).  A chunk is
+// read and written as 128-bit words where both tensors are 16-byte aligned.
+// The folded element i / word j of a chunk, for this kernel and for the bf16 pack below:
+__device__ __forceinline__ float fold_at(const float* g, const float* acc, int i, float scale, int accumulate) {
+  return accumulate ? grad_fold_elem(g[i], scale, acc[i], 1) : grad_fold_elem(g[i], scale, 0.f, 0);      // store mode does not read the accumulator
+}
+__device__ __forceinline__ float4 fold_quad_at(const float* g, const float* acc, int j, float scale, int accumulate) {
+  const float4 gv = reinterpret_cast<const float4*>(g)[j];
+  if (!accumulate)                                             // store mode does not read the accumulator (nor ask for its alignment)
+    return make_float4(grad_fold_elem(gv.x, scale, 0.f, 0), grad_fold_elem(gv.y, scale, 0.f, 0), grad_fold_elem(gv.z, scale, 0.f, 0),
+                       grad_fold_elem(gv.w, scale, 0.f, 0));
+  const float4 a = reinterpret_cast<const float4*>(acc)[j];
+  return make_float4(grad_fold_elem(gv.x, scale, a.x, 1), grad_fold_elem(gv.y, scale, a.y, 1), grad_fold_elem(gv.z, scale, a.z, 1),
+                     grad_fold_elem(gv.w, scale, a.w, 1));
+}
 __global__ __launch_bounds__(256) void grad_accum_mt_kernel(const MtEntry* __restrict__ tab, const float* const* __restrict__ fresh, int ntensors,
                                                             float scale, int accumulate) {
-  const long chunk = blockIdx.x;
-  const int row = mt_find(tab, ntensors, chunk);
-  const MtEntry e = tab[row];
-  const long base = (chunk - e.first_chunk) * MT_CHUNK;
-  const long left = e.n - base;
-  const int cnt = left < MT_CHUNK ? (int)left : MT_CHUNK;
-  float* __restrict__ acc = e.g + base;
-  const float* __restrict__ g = fresh[row] + base;
-  const bool aligned = ((((size_t)acc) | ((size_t)g)) & 15) == 0;
-  const int quads = aligned ? cnt >> 2 : 0;
-#pragma unroll
-  for (int it = 0; it < 4; ++it) {
-    const int j = it * 256 + threadIdx.x;
-    if (j >= quads) break;
-    const float4 gv = reinterpret_cast<const float4*>(g)[j];
-    float4 a;
-    if (accumulate) {
-      a = reinterpret_cast<const float4*>(acc)[j];
-      a.x = fmaf(gv.x, scale, a.x); a.y = fmaf(gv.y, scale, a.y); a.z = fmaf(gv.z, scale, a.z); a.w = fmaf(gv.w, scale, a.w);
-    } else {
-      a.x = gv.x * scale; a.y = gv.y * scale; a.z = gv.z * scale; a.w = gv.w * scale;
-    }
-    reinterpret_cast<float4*>(acc)[j] = a;
-  }
-  for (int i = quads * 4 + threadIdx.x; i < cnt; i += 256) acc[i] = accumulate ? fmaf(g[i], scale, acc[i]) : g[i] * scale;
+  const MtChunk c = mt_chunk(tab, ntensors);
+  float* __restrict__ acc = c.e.g + c.base;
+  const float* __restrict__ g = fresh[c.row] + c.base;
+  mt_walk(c.cnt, ((((size_t)acc) | ((size_t)g)) & 15) == 0,
+          [&](int j) { reinterpret_cast<float4*>(acc)[j] = fold_quad_at(g, acc, j, scale, accumulate); },
+          [&](int i) { acc[i] = fold_at(g, acc, i, scale, accumulate); });
 }
 // ------------------------------------------------------------------------------------------------ bf16 gradient exchange
 // Data-parallel fine-tuning with comm_dtype="bf16": the window's last fold and the rounding for the exchange in one pass, and the way back.
@@ -423,37 +405,19 @@ __device__ __forceinline__ uint32_t bf16_rne_bits(float v) { return v != v ? 0x7
 __device__ __forceinline__ uint2 bf16_rne_quad(float4 a) {
   return make_uint2(bf16_rne_bits(a.x) | (bf16_rne_bits(a.y) << 16), bf16_rne_bits(a.z) | (bf16_rne_bits(a.w) << 16));
 }
-// comm[first_chunk * MT_CHUNK + e] = bf16_rne of the value grad_accum_mt_kernel would have stored (the same expressions: g * scale, or
-// fma(g, scale, acc)); the accumulator is read in add mode and never written.  The rest of a tensor's last chunk is written as zeros, so the
+// comm[first_chunk * MT_CHUNK + e] = bf16_rne of the value grad_accum_mt_kernel would have stored (fold_at / fold_quad_at above, shared with
+// it); the accumulator is read in add mode and never written.  The rest of a tensor's last chunk is written as zeros, so the
 // whole buffer is defined and a sum over it is too.  Aligned tensors: one float4 (two in add mode) in, one 8-byte store out per thread and pass.
 __global__ __launch_bounds__(256) void grad_fold_pack_mt_kernel(const MtEntry* __restrict__ tab, const float* const* __restrict__ fresh, int ntensors,
                                                                 float scale, int accumulate, bf16_t* __restrict__ comm) {
-  const long chunk = blockIdx.x;
-  const int row = mt_find(tab, ntensors, chunk);
-  const MtEntry e = tab[row];
-  const long base = (chunk - e.first_chunk) * MT_CHUNK;
-  const long left = e.n - base;
-  const int cnt = left < MT_CHUNK ? (int)left : MT_CHUNK;
-  const float* __restrict__ acc = e.g + base;
-  const float* __restrict__ g = fresh[row] + base;
-  bf16_t* __restrict__ out = comm + chunk * MT_CHUNK;
-  const bool aligned = ((((size_t)g) | (accumulate ? (size_t)acc : 0)) & 15) == 0;
-  const int quads = aligned ? cnt >> 2 : 0;
-#pragma unroll
-  for (int it = 0; it < 4; ++it) {
-    const int j = it * 256 + threadIdx.x;
-    if (j >= quads) break;
-    const float4 gv = reinterpret_cast<const float4*>(g)[j];
-    float4 a;
-    if (accumulate) {
-      a = reinterpret_cast<const float4*>(acc)[j];
-      a.x = fmaf(gv.x, scale, a.x); a.y = fmaf(gv.y, scale, a.y); a.z = fmaf(gv.z, scale, a.z); a.w = fmaf(gv.w, scale, a.w);
-    } else {
-      a.x = gv.x * scale; a.y = gv.y * scale; a.z = gv.z * scale; a.w = gv.w * scale;
-    }
-    reinterpret_cast<uint2*>(out)[j] = bf16_rne_quad(a);
-  }
-  for (int i = quads * 4 + threadIdx.x; i < cnt; i += 256) out[i] = (bf16_t)bf16_rne_bits(accumulate ? fmaf(g[i], scale, acc[i]) : g[i] * scale);
+  const MtChunk c = mt_chunk(tab, ntensors);
+  const int cnt = c.cnt;
+  const float* __restrict__ acc = c.e.g + c.base;
+  const float* __restrict__ g = fresh[c.row] + c.base;
+  bf16_t* __restrict__ out = comm + (long)blockIdx.x * MT_CHUNK;
+  mt_walk(cnt, ((((size_t)g) | (accumulate ? (size_t)acc : 0)) & 15) == 0,
+          [&](int j) { reinterpret_cast<uint2*>(out)[j] = bf16_rne_quad(fold_quad_at(g, acc, j, scale, accumulate)); },
+          [&](int i) { out[i] = (bf16_t)bf16_rne_bits(fold_at(g, acc, i, scale, accumulate)); });
   if (cnt < MT_CHUNK) {                                          // the padding behind the tensor's last element
     const int z0 = (cnt + 3) & ~3;
     for (int i = cnt + threadIdx.x; i < z0; i += 256) out[i] = 0;
@@ -462,58 +426,45 @@ __global__ __launch_bounds__(256) void grad_fold_pack_mt_kernel(const MtEntry* _
 }
 // acc[e] = float(comm[first_chunk * MT_CHUNK + e]) for the n real elements of every tensor; nothing else is written.
 __global__ __launch_bounds__(256) void grad_unpack_mt_kernel(const MtEntry* __restrict__ tab, int ntensors, const bf16_t* __restrict__ comm) {
-  const long chunk = blockIdx.x;
-  const MtEntry e = tab[mt_find(tab, ntensors, chunk)];
-  const long base = (chunk - e.first_chunk) * MT_CHUNK;
-  const long left = e.n - base;
-  const int cnt = left < MT_CHUNK ? (int)left : MT_CHUNK;
-  float* __restrict__ acc = e.g + base;
-  const bf16_t* __restrict__ in = comm + chunk * MT_CHUNK;
-  const int quads = (((size_t)acc) & 15) == 0 ? cnt >> 2 : 0;
-#pragma unroll
-  for (int it = 0; it < 4; ++it) {
-    const int j = it * 256 + threadIdx.x;
-    if (j >= quads) break;
-    const uint2 w = reinterpret_cast<const uint2*>(in)[j];
-    reinterpret_cast<float4*>(acc)[j] = make_float4(__uint_as_float(w.x << 16), __uint_as_float(w.x & 0xFFFF0000u), __uint_as_float(w.y << 16),
-                                                    __uint_as_float(w.y & 0xFFFF0000u));
-  }
-  for (int i = quads * 4 + threadIdx.x; i < cnt; i += 256) acc[i] = bf2f(in[i]);
+  const MtChunk c = mt_chunk(tab, ntensors);
+  float* __restrict__ acc = c.e.g + c.base;
+  const bf16_t* __restrict__ in = comm + (long)blockIdx.x * MT_CHUNK;
+  mt_walk(c.cnt, (((size_t)acc) & 15) == 0,
+          [&](int j) {
+            const uint2 w = reinterpret_cast<const uint2*>(in)[j];
+            reinterpret_cast<float4*>(acc)[j] = make_float4(__uint_as_float(w.x << 16), __uint_as_float(w.x & 0xFFFF0000u), __uint_as_float(w.y << 16),
+                                                            __uint_as_float(w.y & 0xFFFF0000u));
+          },
+          [&](int i) { acc[i] = bf2f(in[i]); });
 }
 
 // EMAModel.step alone over the table (the micro-batches that take no optimizer step): shadow -= (1 - decay) (shadow - p) by vt_optim.h's
 // ema_elem, so it gives the bits of vt_ema_update_dev per tensor.  hyper[3] = 1 - decay.
 __global__ __launch_bounds__(256) void ema_mt_kernel(const MtEntry* __restrict__ tab, int ntensors, const float* __restrict__ hyper) {
-  const MtEntry e = tab[mt_find(tab, ntensors, blockIdx.x)];
-  if (!e.shadow) return;
-  const long base = ((long)blockIdx.x - e.first_chunk) * MT_CHUNK;
-  const long left = e.n - base;
-  const int cnt = left < MT_CHUNK ? (int)left : MT_CHUNK;
+  const MtChunk c = mt_chunk(tab, ntensors);
+  if (!c.e.shadow) return;
   const float omd = hyper[3];
-  float* __restrict__ sh = e.shadow + base;
-  const float* __restrict__ p = e.p + base;
-  const bool aligned = ((((size_t)sh) | ((size_t)p)) & 15) == 0;
-  const int quads = aligned ? cnt >> 2 : 0;
-#pragma unroll
-  for (int it = 0; it < 4; ++it) {
-    const int j = it * 256 + threadIdx.x;
-    if (j >= quads) break;
-    const float4 pv = reinterpret_cast<const float4*>(p)[j];
-    float4 s = reinterpret_cast<const float4*>(sh)[j];
-    s.x = ema_elem(s.x, pv.x, omd); s.y = ema_elem(s.y, pv.y, omd); s.z = ema_elem(s.z, pv.z, omd); s.w = ema_elem(s.w, pv.w, omd);
-    reinterpret_cast<float4*>(sh)[j] = s;
-  }
-  for (int i = quads * 4 + threadIdx.x; i < cnt; i += 256) sh[i] = ema_elem(sh[i], p[i], omd);
+  float* __restrict__ sh = c.e.shadow + c.base;
+  const float* __restrict__ p = c.e.p + c.base;
+  mt_walk(c.cnt, ((((size_t)sh) | ((size_t)p)) & 15) == 0,
+          [&](int j) {
+            const float4 pv = reinterpret_cast<const float4*>(p)[j];
+            float4 s = reinterpret_cast<const float4*>(sh)[j];
+            s.x = ema_elem(s.x, pv.x, omd); s.y = ema_elem(s.y, pv.y, omd); s.z = ema_elem(s.z, pv.z, omd); s.w = ema_elem(s.w, pv.w, omd);
+            reinterpret_cast<float4*>(sh)[j] = s;
+          },
+          [&](int i) { sh[i] = ema_elem(sh[i], p[i], omd); });
 }
 
-// mean squared error of pred against target (fp32) and its gradient: loss = mean((pred - target)^2), dpred = 2 (pred - target) / n; one block.
-// SCALED (fp16 training): dpred = grad_scale * 2 (pred - target) / n, the factor formed once in fp32, one rounding at the store; the loss is not scaled.
-template <typename T, bool SCALED>
+// mean squared error of pred against target (fp32) and its gradient: loss = mean((pred - target)^2), dpred = grad_scale * 2 (pred - target) / n,
+// the factor formed once in fp32, one rounding at the store; the loss is not scaled.  grad_scale is the loss scale of fp16 training and 1
+// otherwise (1 * x is exact: the unscaled gradient's bits).  One block.
+template <typename T>
 __global__ __launch_bounds__(256) void mse_kernel(const T* __restrict__ pred, const float* __restrict__ tgt, T* __restrict__ dpred,
                                                   float* __restrict__ loss, long n, float grad_scale) {
   __shared__ float red[4];
   float s = 0.f;
-  const float k = SCALED ? grad_scale * (2.0f / (float)n) : 2.0f / (float)n;
+  const float k = grad_scale * (2.0f / (float)n);
   for (long i = threadIdx.x; i < n; i += 256) {
     const float d = ldf<T>(pred, i) - tgt[i];
     s += d * d;
@@ -526,7 +477,8 @@ __global__ __launch_bounds__(256) void mse_kernel(const T* __restrict__ pred, co
 }  // namespace
 
 #define LAUNCH_OK() (vt_check_launch())
-// launch KERNEL<float>, KERNEL<bf16_t> or KERNEL<half_t> by the activation dtype code `dt`
+// The dtype-typed entry points: arguments first, then the activation dtype code `dt` (BAD_DT), then KERNEL<float>, <bf16_t> or <half_t> by
+// vt_common.h's DISPATCH_T.
 #define BAD_DT(name) vt_fail(VT_ERR_UNSUPPORTED, name ": activation dtype must be fp32 (0), bf16 (1) or fp16 (3)")
 
 int vt_attention_bwd(const VtAttnBwdParams* p, vt_stream_t s) {
@@ -535,110 +487,87 @@ int vt_attention_bwd(const VtAttnBwdParams* p, vt_stream_t s) {
   if (p->B < 1 || p->H < 1 || p->Nq < 1 || p->Nk < 1 || p->hd != 64) return vt_fail(VT_ERR_ARG, "vt_attention_bwd: bad shape (head_dim must be 64)");
   if ((long)p->B * p->H > 65535) return vt_fail(VT_ERR_ARG, "vt_attention_bwd: B * H > 65535");
   if (p->kmask && p->km_bs < p->Nk) return vt_fail(VT_ERR_ARG, "vt_attention_bwd: key mask row shorter than Nk");
+  if (!vt_is_act_dtype(p->dtype)) return vt_fail(VT_ERR_UNSUPPORTED, "vt_attention_bwd: fp32, bf16 or fp16 operands");
   const long rows = (long)p->B * p->H * p->Nq;
   const dim3 gq((unsigned)((rows + 3) / 4)), gk((unsigned)((p->Nk + 3) / 4), (unsigned)(p->B * p->H));
-  if (p->dtype == VT_F32) {
-    hipLaunchKernelGGL(attn_bwd_dq_kernel<float>, gq, dim3(256), 0, (hipStream_t)s, *p);
-    hipLaunchKernelGGL(attn_bwd_dkv_kernel<float>, gk, dim3(256), 0, (hipStream_t)s, *p);
-  } else if (p->dtype == VT_BF16) {
-    hipLaunchKernelGGL(attn_bwd_dq_kernel<bf16_t>, gq, dim3(256), 0, (hipStream_t)s, *p);
-    hipLaunchKernelGGL(attn_bwd_dkv_kernel<bf16_t>, gk, dim3(256), 0, (hipStream_t)s, *p);
-  } else if (p->dtype == VT_F16) {
-    hipLaunchKernelGGL(attn_bwd_dq_kernel<half_t>, gq, dim3(256), 0, (hipStream_t)s, *p);
-    hipLaunchKernelGGL(attn_bwd_dkv_kernel<half_t>, gk, dim3(256), 0, (hipStream_t)s, *p);
-  } else {
-    return vt_fail(VT_ERR_UNSUPPORTED, "vt_attention_bwd: fp32, bf16 or fp16 operands");
-  }
+  DISPATCH_T(p->dtype, T, {
+    hipLaunchKernelGGL(attn_bwd_dq_kernel<T>, gq, dim3(256), 0, (hipStream_t)s, *p);
+    hipLaunchKernelGGL(attn_bwd_dkv_kernel<T>, gk, dim3(256), 0, (hipStream_t)s, *p);
+  })
   return LAUNCH_OK();
 }
 int vt_rmsnorm_bwd(const void* x, const float* w, const void* dy, void* dx, float* dyxr, int rows, int D, float eps, int mode, int dt, vt_stream_t s) {
   if (!x || !w || !dy || !dx || !dyxr || rows < 1 || D < 2 || (mode != 1 && mode != 2)) return vt_fail(VT_ERR_ARG, "vt_rmsnorm_bwd: bad argument");
-  if (dt == VT_F32) hipLaunchKernelGGL(rmsnorm_bwd_kernel<float>, dim3(rows), dim3(256), 0, (hipStream_t)s, (const float*)x, w, (const float*)dy, (float*)dx, dyxr, D, eps, mode);
-  else if (dt == VT_BF16) hipLaunchKernelGGL(rmsnorm_bwd_kernel<bf16_t>, dim3(rows), dim3(256), 0, (hipStream_t)s, (const bf16_t*)x, w, (const bf16_t*)dy, (bf16_t*)dx, dyxr, D, eps, mode);
-  else if (dt == VT_F16) hipLaunchKernelGGL(rmsnorm_bwd_kernel<half_t>, dim3(rows), dim3(256), 0, (hipStream_t)s, (const half_t*)x, w, (const half_t*)dy, (half_t*)dx, dyxr, D, eps, mode);
-  else return BAD_DT("vt_rmsnorm_bwd");
+  if (!vt_is_act_dtype(dt)) return BAD_DT("vt_rmsnorm_bwd");
+  DISPATCH_T(dt, T, hipLaunchKernelGGL(rmsnorm_bwd_kernel<T>, dim3(rows), dim3(256), 0, (hipStream_t)s, (const T*)x, w, (const T*)dy, (T*)dx, dyxr, D, eps, mode))
   return LAUNCH_OK();
 }
 int vt_headnorm_bwd(const void* x, long x_stride, void* dy, long dy_stride, int heads, long tokens, const float* w, float* part, float eps, int mode,
                     int dt, vt_stream_t s) {
   if (!x || !dy || !w || !part || heads < 1 || tokens < 1 || x_stride < (long)heads * 64 || dy_stride < (long)heads * 64 || (mode != 1 && mode != 2))
     return vt_fail(VT_ERR_ARG, "vt_headnorm_bwd: bad argument");
+  if (!vt_is_act_dtype(dt)) return BAD_DT("vt_headnorm_bwd");
   const long pairs = tokens * heads;
   const dim3 g((unsigned)((pairs + 63) / 64));
-  if (dt == VT_F32) hipLaunchKernelGGL(headnorm_bwd_kernel<float>, g, dim3(256), 0, (hipStream_t)s, (const float*)x, x_stride, (float*)dy, dy_stride, heads, pairs, w, part, eps, mode);
-  else if (dt == VT_BF16) hipLaunchKernelGGL(headnorm_bwd_kernel<bf16_t>, g, dim3(256), 0, (hipStream_t)s, (const bf16_t*)x, x_stride, (bf16_t*)dy, dy_stride, heads, pairs, w, part, eps, mode);
-  else if (dt == VT_F16) hipLaunchKernelGGL(headnorm_bwd_kernel<half_t>, g, dim3(256), 0, (hipStream_t)s, (const half_t*)x, x_stride, (half_t*)dy, dy_stride, heads, pairs, w, part, eps, mode);
-  else return BAD_DT("vt_headnorm_bwd");
+  DISPATCH_T(dt, T, hipLaunchKernelGGL(headnorm_bwd_kernel<T>, g, dim3(256), 0, (hipStream_t)s, (const T*)x, x_stride, (T*)dy, dy_stride, heads, pairs, w, part, eps, mode))
   return LAUNCH_OK();
 }
 int vt_act_bwd(const void* x, const void* dy, void* out, long n, int act, int dt, vt_stream_t s) {
   if (!x || !out || n < 1 || (act != VT_ACT_GELU_TANH && act != VT_ACT_SILU)) return vt_fail(VT_ERR_ARG, "vt_act_bwd: bad argument (act 2 = tanh-GELU, 3 = SiLU)");
-  if (dt == VT_F32) hipLaunchKernelGGL(act_kernel<float>, g1(n), dim3(256), 0, (hipStream_t)s, (const float*)x, (const float*)dy, (float*)out, n, act);
-  else if (dt == VT_BF16) hipLaunchKernelGGL(act_kernel<bf16_t>, g1(n), dim3(256), 0, (hipStream_t)s, (const bf16_t*)x, (const bf16_t*)dy, (bf16_t*)out, n, act);
-  else if (dt == VT_F16) hipLaunchKernelGGL(act_kernel<half_t>, g1(n), dim3(256), 0, (hipStream_t)s, (const half_t*)x, (const half_t*)dy, (half_t*)out, n, act);
-  else return BAD_DT("vt_act_bwd");
+  if (!vt_is_act_dtype(dt)) return BAD_DT("vt_act_bwd");
+  DISPATCH_T(dt, T, hipLaunchKernelGGL(act_kernel<T>, g1(n), dim3(256), 0, (hipStream_t)s, (const T*)x, (const T*)dy, (T*)out, n, act))
   return LAUNCH_OK();
 }
 int vt_ddpm_qsample(const float* state, const float* action, const float* noise, const float* mask, const long* timesteps, const float* alphas_cumprod,
                     int num_train_timesteps, void* out, int odt, int B, int horizon, int action_dim, vt_stream_t s) {
   if (!state || !action || !noise || !mask || !timesteps || !alphas_cumprod || !out || num_train_timesteps < 1 || B < 1 || horizon < 1 || action_dim < 1)
     return vt_fail(VT_ERR_ARG, "vt_ddpm_qsample: bad argument");
+  if (!vt_is_act_dtype(odt)) return BAD_DT("vt_ddpm_qsample");
   const dim3 g = g1((long)B * (horizon + 1) * 2 * action_dim);
-  if (odt == VT_F32) hipLaunchKernelGGL(ddpm_qsample_kernel<float>, g, dim3(256), 0, (hipStream_t)s, state, action, noise, mask, timesteps, alphas_cumprod, num_train_timesteps, (float*)out, B, horizon, action_dim);
-  else if (odt == VT_BF16) hipLaunchKernelGGL(ddpm_qsample_kernel<bf16_t>, g, dim3(256), 0, (hipStream_t)s, state, action, noise, mask, timesteps, alphas_cumprod, num_train_timesteps, (bf16_t*)out, B, horizon, action_dim);
-  else if (odt == VT_F16) hipLaunchKernelGGL(ddpm_qsample_kernel<half_t>, g, dim3(256), 0, (hipStream_t)s, state, action, noise, mask, timesteps, alphas_cumprod, num_train_timesteps, (half_t*)out, B, horizon, action_dim);
-  else return BAD_DT("vt_ddpm_qsample");
+  DISPATCH_T(odt, T, hipLaunchKernelGGL(ddpm_qsample_kernel<T>, g, dim3(256), 0, (hipStream_t)s, state, action, noise, mask, timesteps, alphas_cumprod,
+                                        num_train_timesteps, (T*)out, B, horizon, action_dim))
   return LAUNCH_OK();
 }
 int vt_timestep_embed(const float* t, const float* freqs, void* out, int odt, int B, int dim, vt_stream_t s) {
   if (!t || !freqs || !out || B < 1 || dim < 2 || dim % 2) return vt_fail(VT_ERR_ARG, "vt_timestep_embed: bad argument");
-  if (odt == VT_F32) hipLaunchKernelGGL(timestep_embed_kernel<float>, g1((long)B * dim), dim3(256), 0, (hipStream_t)s, t, freqs, (float*)out, B, dim);
-  else if (odt == VT_BF16) hipLaunchKernelGGL(timestep_embed_kernel<bf16_t>, g1((long)B * dim), dim3(256), 0, (hipStream_t)s, t, freqs, (bf16_t*)out, B, dim);
-  else if (odt == VT_F16) hipLaunchKernelGGL(timestep_embed_kernel<half_t>, g1((long)B * dim), dim3(256), 0, (hipStream_t)s, t, freqs, (half_t*)out, B, dim);
-  else return BAD_DT("vt_timestep_embed");
+  if (!vt_is_act_dtype(odt)) return BAD_DT("vt_timestep_embed");
+  DISPATCH_T(odt, T, hipLaunchKernelGGL(timestep_embed_kernel<T>, g1((long)B * dim), dim3(256), 0, (hipStream_t)s, t, freqs, (T*)out, B, dim))
   return LAUNCH_OK();
 }
 int vt_add_rowvec_(void* a, int dt, const float* v, long rows, long cols, vt_stream_t s) {
   if (!a || !v || rows < 1 || cols < 1) return vt_fail(VT_ERR_ARG, "vt_add_rowvec_: bad argument");
-  if (dt == VT_F32) hipLaunchKernelGGL(add_rowvec_kernel<float>, g1(rows * cols), dim3(256), 0, (hipStream_t)s, (float*)a, v, rows, cols);
-  else if (dt == VT_BF16) hipLaunchKernelGGL(add_rowvec_kernel<bf16_t>, g1(rows * cols), dim3(256), 0, (hipStream_t)s, (bf16_t*)a, v, rows, cols);
-  else if (dt == VT_F16) hipLaunchKernelGGL(add_rowvec_kernel<half_t>, g1(rows * cols), dim3(256), 0, (hipStream_t)s, (half_t*)a, v, rows, cols);
-  else return BAD_DT("vt_add_rowvec_");
+  if (!vt_is_act_dtype(dt)) return BAD_DT("vt_add_rowvec_");
+  DISPATCH_T(dt, T, hipLaunchKernelGGL(add_rowvec_kernel<T>, g1(rows * cols), dim3(256), 0, (hipStream_t)s, (T*)a, v, rows, cols))
   return LAUNCH_OK();
 }
 int vt_transpose_pad(const void* in, void* out, int dt, int M, int N, int Mp, vt_stream_t s) {
   if (!in || !out || M < 1 || N < 1 || Mp < M) return vt_fail(VT_ERR_ARG, "vt_transpose_pad: bad argument");
+  if (!vt_is_act_dtype(dt)) return BAD_DT("vt_transpose_pad");
   const dim3 g((N + 31) / 32, (Mp + 31) / 32);
-  if (dt == VT_F32) hipLaunchKernelGGL(transpose_pad_kernel<float>, g, dim3(256), 0, (hipStream_t)s, (const float*)in, (float*)out, M, N, Mp);
-  else if (dt == VT_BF16) hipLaunchKernelGGL(transpose_pad_kernel<bf16_t>, g, dim3(256), 0, (hipStream_t)s, (const bf16_t*)in, (bf16_t*)out, M, N, Mp);
-  else if (dt == VT_F16) hipLaunchKernelGGL(transpose_pad_kernel<half_t>, g, dim3(256), 0, (hipStream_t)s, (const half_t*)in, (half_t*)out, M, N, Mp);
-  else return BAD_DT("vt_transpose_pad");
+  DISPATCH_T(dt, T, hipLaunchKernelGGL(transpose_pad_kernel<T>, g, dim3(256), 0, (hipStream_t)s, (const T*)in, (T*)out, M, N, Mp))
   return LAUNCH_OK();
 }
 int vt_colsum_dt(const void* x, int dt, long ld, float* out, int M, int N, vt_stream_t s) {
   if (!x || !out || M < 1 || N < 1) return vt_fail(VT_ERR_ARG, "vt_colsum_dt: bad argument");
-  if (dt == VT_F32) hipLaunchKernelGGL(colsum_t_kernel<float>, dim3((N + 31) / 32), dim3(1024), 0, (hipStream_t)s, (const float*)x, ld, out, M, N);
-  else if (dt == VT_BF16) hipLaunchKernelGGL(colsum_t_kernel<bf16_t>, dim3((N + 31) / 32), dim3(1024), 0, (hipStream_t)s, (const bf16_t*)x, ld, out, M, N);
-  else if (dt == VT_F16) hipLaunchKernelGGL(colsum_t_kernel<half_t>, dim3((N + 31) / 32), dim3(1024), 0, (hipStream_t)s, (const half_t*)x, ld, out, M, N);
-  else return BAD_DT("vt_colsum_dt");
+  if (!vt_is_act_dtype(dt)) return BAD_DT("vt_colsum_dt");
+  DISPATCH_T(dt, T, hipLaunchKernelGGL(colsum_t_kernel<T>, dim3((N + 31) / 32), dim3(1024), 0, (hipStream_t)s, (const T*)x, ld, out, M, N))
   return LAUNCH_OK();
 }
 int vt_add_dt(void* a, const void* b, long n, int dt, vt_stream_t s) {
   if (!a || !b || n < 1) return vt_fail(VT_ERR_ARG, "vt_add_dt: bad argument");
-  if (dt == VT_F32) hipLaunchKernelGGL(add_t_kernel<float>, g1(n), dim3(256), 0, (hipStream_t)s, (float*)a, (const float*)b, n);
-  else if (dt == VT_BF16) hipLaunchKernelGGL(add_t_kernel<bf16_t>, g1(n), dim3(256), 0, (hipStream_t)s, (bf16_t*)a, (const bf16_t*)b, n);
-  else if (dt == VT_F16) hipLaunchKernelGGL(add_t_kernel<half_t>, g1(n), dim3(256), 0, (hipStream_t)s, (half_t*)a, (const half_t*)b, n);
-  else return BAD_DT("vt_add_dt");
+  if (!vt_is_act_dtype(dt)) return BAD_DT("vt_add_dt");
+  DISPATCH_T(dt, T, hipLaunchKernelGGL(add_t_kernel<T>, g1(n), dim3(256), 0, (hipStream_t)s, (T*)a, (const T*)b, n))
   return LAUNCH_OK();
 }
 int vt_copy_cols_dt(const void* src, long lds_, long off, void* dst, long ldd, long doff, long rows, long cols, int dt, vt_stream_t s) {
   if (!src || !dst || rows < 1 || cols < 1) return vt_fail(VT_ERR_ARG, "vt_copy_cols_dt: bad argument");
-  if (dt == VT_F32) hipLaunchKernelGGL(copy_cols_t_kernel<float>, g1(rows * cols), dim3(256), 0, (hipStream_t)s, (const float*)src, lds_, off, (float*)dst, ldd, doff, rows, cols);
-  else if (dt == VT_BF16) hipLaunchKernelGGL(copy_cols_t_kernel<bf16_t>, g1(rows * cols), dim3(256), 0, (hipStream_t)s, (const bf16_t*)src, lds_, off, (bf16_t*)dst, ldd, doff, rows, cols);
-  else if (dt == VT_F16) hipLaunchKernelGGL(copy_cols_t_kernel<half_t>, g1(rows * cols), dim3(256), 0, (hipStream_t)s, (const half_t*)src, lds_, off, (half_t*)dst, ldd, doff, rows, cols);
-  else return BAD_DT("vt_copy_cols_dt");
+  if (!vt_is_act_dtype(dt)) return BAD_DT("vt_copy_cols_dt");
+  DISPATCH_T(dt, T, hipLaunchKernelGGL(copy_cols_t_kernel<T>, g1(rows * cols), dim3(256), 0, (hipStream_t)s, (const T*)src, lds_, off, (T*)dst, ldd, doff, rows, cols))
   return LAUNCH_OK();
 }
+// vt_grad_clip_multi and vt_grad_unscale_clip_multi below stay two launch groups on purpose: their first passes add a chunk's squares in
+// different orders (16 scalar passes per thread against 4 float4 passes), so one in place of the other would move the last bits of the norm
+// that fp32 / bf16 training, or fp16 training, reports and clips by.
 int vt_grad_clip_multi(const void* table, int ntensors, long total_chunks, float max_norm, float* chunk_part, float* norm_coef, vt_stream_t s) {
   if (!table || !chunk_part || !norm_coef || ntensors < 1 || total_chunks < 1 || !(max_norm > 0.f)) return vt_fail(VT_ERR_ARG, "vt_grad_clip_multi: bad argument");
   hipLaunchKernelGGL(sumsq_mt_kernel, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)s, (const MtEntry*)table, ntensors, chunk_part);
@@ -682,19 +611,17 @@ int vt_ema_multi(const void* table, int ntensors, long total_chunks, const float
   hipLaunchKernelGGL(ema_mt_kernel, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)s, (const MtEntry*)table, ntensors, hyper);
   return LAUNCH_OK();
 }
+static int mse_launch(const void* pred, const float* target, void* dpred, float* loss, long n, int dt, float grad_scale, vt_stream_t s) {
+  DISPATCH_T(dt, T, hipLaunchKernelGGL(mse_kernel<T>, dim3(1), dim3(256), 0, (hipStream_t)s, (const T*)pred, target, (T*)dpred, loss, n, grad_scale))
+  return LAUNCH_OK();
+}
 int vt_mse_loss(const void* pred, const float* target, void* dpred, float* loss, long n, int dt, vt_stream_t s) {
   if (!pred || !target || !dpred || !loss || n < 1) return vt_fail(VT_ERR_ARG, "vt_mse_loss: bad argument");
-  if (dt == VT_F32) hipLaunchKernelGGL((mse_kernel<float, false>), dim3(1), dim3(256), 0, (hipStream_t)s, (const float*)pred, target, (float*)dpred, loss, n, 1.0f);
-  else if (dt == VT_BF16) hipLaunchKernelGGL((mse_kernel<bf16_t, false>), dim3(1), dim3(256), 0, (hipStream_t)s, (const bf16_t*)pred, target, (bf16_t*)dpred, loss, n, 1.0f);
-  else if (dt == VT_F16) hipLaunchKernelGGL((mse_kernel<half_t, false>), dim3(1), dim3(256), 0, (hipStream_t)s, (const half_t*)pred, target, (half_t*)dpred, loss, n, 1.0f);
-  else return BAD_DT("vt_mse_loss");
-  return LAUNCH_OK();
+  if (!vt_is_act_dtype(dt)) return BAD_DT("vt_mse_loss");
+  return mse_launch(pred, target, dpred, loss, n, dt, 1.0f, s);
 }
 int vt_mse_loss_scaled(const void* pred, const float* target, void* dpred, float* loss, long n, int dt, float grad_scale, vt_stream_t s) {
   if (!pred || !target || !dpred || !loss || n < 1 || !(grad_scale > 0.f) || isinf(grad_scale)) return vt_fail(VT_ERR_ARG, "vt_mse_loss_scaled: bad argument");
-  if (dt == VT_F32) hipLaunchKernelGGL((mse_kernel<float, true>), dim3(1), dim3(256), 0, (hipStream_t)s, (const float*)pred, target, (float*)dpred, loss, n, grad_scale);
-  else if (dt == VT_BF16) hipLaunchKernelGGL((mse_kernel<bf16_t, true>), dim3(1), dim3(256), 0, (hipStream_t)s, (const bf16_t*)pred, target, (bf16_t*)dpred, loss, n, grad_scale);
-  else if (dt == VT_F16) hipLaunchKernelGGL((mse_kernel<half_t, true>), dim3(1), dim3(256), 0, (hipStream_t)s, (const half_t*)pred, target, (half_t*)dpred, loss, n, grad_scale);
-  else return BAD_DT("vt_mse_loss_scaled");
-  return LAUNCH_OK();
+  if (!vt_is_act_dtype(dt)) return BAD_DT("vt_mse_loss_scaled");
+  return mse_launch(pred, target, dpred, loss, n, dt, grad_scale, s);
 }

@@ -825,17 +825,27 @@ class RdtTrainer:
         tab, n, chunks = self._table()
         if self.scaler is not None:
             return self._optimizer_step_scaled(tab, n, chunks)
+        self.ema_updates += 1
+        self._take_step(tab, n, chunks, clip=True)
+        self.micro_step, self.sync_gradients = 0, True
+        self.shadow_version += 1
+
+    def _take_step(self, tab, n, chunks, clip: bool) -> None:
+        """The scheduler's lr, then AdamW + EMA over the table (the EMA update counted by the caller) and the 16-bit copies of the new weights.
+        clip: clip the gradients first (the fp16 path has unscaled and clipped them before its host read)."""
         self.lr = lr_at(self.base_lr, self.lr_scheduler, self.step_count, self.lr_warmup_steps * self.k)      # train.py:302 scales the warm-up by k
         self.step_count += 1
-        self.ema_updates += 1
         hy = self._hyper(self.step_count)
-        L.check(L.lib().vt_grad_clip_multi(L.ptr(tab), n, chunks, self.max_grad_norm, L.ptr(self._chunk_part), L.ptr(self._norm_coef), _sp(self.device)),
-                "vt_grad_clip_multi")
+        if clip:
+            L.check(L.lib().vt_grad_clip_multi(L.ptr(tab), n, chunks, self.max_grad_norm, L.ptr(self._chunk_part), L.ptr(self._norm_coef), _sp(self.device)),
+                    "vt_grad_clip_multi")
         self.opt_state.step(tab, n, chunks, hy, self.betas, self.eps, self.wd)
         self._refresh16()
-        self.micro_step, self.sync_gradients = 0, True
         self.weights_version += 1
-        self.shadow_version += 1
+
+    def _ema_alone(self, tab, n, chunks) -> None:
+        """EMAModel.step without an optimizer step (the EMA update counted by the caller): the shadows move toward the unchanged parameters."""
+        L.check(L.lib().vt_ema_multi(L.ptr(tab), n, chunks, L.ptr(self._hyper(max(1, self.step_count))), _sp(self.device)), "vt_ema_multi")
 
     def _optimizer_step_scaled(self, tab, n, chunks) -> None:
         """fp16: accelerator.clip_grad_norm_ (GradScaler.unscale_ first) -> scaler.step(optimizer) -> scaler.update -> scheduler -> EMAModel.step.
@@ -852,15 +862,11 @@ class RdtTrainer:
         found_inf = int(host.view(torch.int32)[2]) != 0
         self.ema_updates += 1
         if found_inf:
-            L.check(L.lib().vt_ema_multi(L.ptr(tab), n, chunks, L.ptr(self._hyper(max(1, self.step_count))), _sp(self.device)), "vt_ema_multi")
+            self._ema_alone(tab, n, chunks)
             if self.last_loss is not None and not math.isfinite(float(host[3])):
                 sc.skipped_nonfinite_loss += 1                    # the forward overflowed: no smaller scale repairs that
         else:
-            self.lr = lr_at(self.base_lr, self.lr_scheduler, self.step_count, self.lr_warmup_steps * self.k)
-            self.step_count += 1
-            self.opt_state.step(tab, n, chunks, self._hyper(self.step_count), self.betas, self.eps, self.wd)
-            self._refresh16()
-            self.weights_version += 1
+            self._take_step(tab, n, chunks, clip=False)
         sc.update(found_inf)
         self.last_step_skipped = found_inf
         self.micro_step, self.sync_gradients = 0, True
@@ -907,7 +913,7 @@ class RdtTrainer:
         """EMAModel.step alone (train.py:448 on a micro-batch without an optimizer step): the shadows move toward the unchanged parameters."""
         tab, n, chunks = self._table()
         self.ema_updates += 1
-        L.check(L.lib().vt_ema_multi(L.ptr(tab), n, chunks, L.ptr(self._hyper(max(1, self.step_count))), _sp(self.device)), "vt_ema_multi")
+        self._ema_alone(tab, n, chunks)
         self.sync_gradients = False
         self.shadow_version += 1
 
