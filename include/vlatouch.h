@@ -480,6 +480,26 @@ int vt_transpose_pad(const void* in, void* out, int dt, int M, int N, int Mp, vt
 /* vt_colsum / vt_add_ / vt_copy_cols (fp32 only, above) for an activation dtype `dt` (0 fp32, 1 bf16, 3 fp16): column sums in fp32, a += b, dst[:, doff..] = src[:, off..] */
 int vt_colsum_dt(const void* x, int dt, long ld, float* out, int M, int N, vt_stream_t stream);
 int vt_add_dt(void* a, const void* b, long n, int dt, vt_stream_t stream);
+/* vt_gemm_tn (csrc/vt_gemm_tn.hip): a Linear's weight gradient on 16-bit MFMA with no transposed copy of an operand:
+ *   dw[N][K] = sum_m dy[m][n] x[m][k] (fp32, row pitch K) and, if db is not null, db[N] = sum_m dy[m][n] (fp32) from the same launch.
+ *   dy [M][N] and x [M][K] are both bf16 or both fp16 (dt 1 / 3), rows token-major with unit inner stride and row pitches ld_dy >= N, ld_x >= K in
+ *   elements, so a column slice of a wider buffer is read in place.  M >= 1 (int), N and K multiples of 8, pitches multiples of 8, every base
+ *   16-byte aligned.  Products are exact and accumulated in fp32.  Anything else (fp32 operands included) is refused with VT_ERR_ARG and a
+ *   message before any launch: there is no fallback.
+ * vt_gemm_tn_plan: host only, a pure function of (M, N, K): the token rows are cut into `splits` runs of `rows_per_split` rows (a multiple of
+ *   m_step = 32, the kernel's reduction step; the last run may be shorter), split s = rows s * rows_per_split ... of dy and x.  splits = 1:
+ *   ws_bytes = 0, ws may be null and dw / db are stored directly.  splits > 1: ws (device, 16-byte aligned, at least ws_bytes =
+ *   splits * (N * K + N) * 4 rounded up to a multiple of 256) receives per split an fp32 partial [N][K] followed by a db partial [N], and a
+ *   second kernel adds them in split order.  The rule: splits = min(ceil(256 / tiles), floor(ceil(M / 32) / 4), 16), at least 1, for
+ *   tiles = ceil(N / 128) * ceil(K / 128) workgroup tiles; rows_per_split = ceil(ceil(M / 32) / splits) * 32; splits = ceil(M / rows_per_split).
+ *   No allocation, no synchronisation, no atomics, no counters: the bits depend on the shapes only, and two calls give the same bits.
+ *   Returns VT_OK, or VT_ERR_ARG for M < 1 or an N or K that is not a positive multiple of 8 (the plan is then zeroed). */
+typedef struct {
+  int splits, rows_per_split, m_step;
+  long ws_bytes;
+} VtGemmTnPlan;
+int vt_gemm_tn_plan(int M, int N, int K, VtGemmTnPlan* plan);
+int vt_gemm_tn(const void* dy, long ld_dy, const void* x, long ld_x, int dt, int M, int N, int K, float* dw, float* db, void* ws, long ws_bytes, vt_stream_t stream);
 int vt_copy_cols_dt(const void* src, long lds, long off, void* dst, long ldd, long doff, long rows, long cols, int dt, vt_stream_t stream);
 int vt_grad_clip_multi(const void* table, int ntensors, long total_chunks, float max_norm, float* chunk_part, float* norm_coef, vt_stream_t stream);
 int vt_mse_loss(const void* pred, const float* target, void* dpred, float* loss, long n, int dt, vt_stream_t stream);

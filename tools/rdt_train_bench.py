@@ -31,6 +31,13 @@ medians with min / max; by device events the attention-backward launches alone o
 cross-attention and one self-attention at the trainer's strides; peak device memory of a step of each trainer; the bytes of `ws2`; the
 torch-autograd yardstick of the same run.  Added to `--out` under the key `attention_backward_mfma`; the other keys stay.
 
+`--weight-gradient tn` measures the bf16 step (under `attention_backward="mfma"`) with the transpose-free weight-gradient GEMM (csrc/vt_gemm_tn.hip)
+beside the default "gemm" path (two transposes, the NT GEMM, a column sum: the path of every commit before it) at every `--batch` size: one trainer of
+each kind in one process, their steps alternating and swapping who goes first, `--warmup` warm-up and `--steps` (default 21 here) timed steps, every
+phase device-synchronised, medians with min / max; by device events the weight-gradient work alone, old and new, of the image K|V product
+(`--img-len` x batch rows), a hidden x hidden product (67 x batch rows) and the timestep embedder's (batch rows), with the plan of each; peak device
+memory of a step of each trainer.  Added to `--out` under the key `weight_gradient_tn`; the other keys stay.
+
 `--data-parallel fp32|bf16` measures the data-parallel step (`RdtTrainer(process_group=, comm_dtype=)`) at batch 4, bf16, `attention_backward="mfma"`
 over an RCCL ("nccl") process group of world size 1, which is all a one-GPU machine allows: NO SCALING NUMBER CAN BE PRODUCED ON A ONE-GPU BOX, and a
 world-size-1 all-reduce moves nothing between cards.  A grouped and an ungrouped trainer alternate in one process and swap who goes first; by device
@@ -350,6 +357,95 @@ def attention_run(a, c, sd, params, dev, B):
     return out
 
 
+def weight_gradient_launches(a, c, B, dev):
+    """Device-event time of the weight-gradient work of one Linear alone, "gemm" (transpose_pad x 2, ops.gemm, colsum) and "tn" (weight_grad_tn)
+    alternating, at three of the step's shapes -> dict."""
+    from vlatouch import _lib as L
+    from vlatouch import ops
+    from vlatouch.rdt_train import colsum, transpose_pad, weight_grad_tn
+    import ctypes as C
+    D = c["hidden"]
+    g = torch.Generator(device=dev).manual_seed(5)
+    rn = lambda *s: torch.randn(*s, generator=g, device=dev).bfloat16()
+    old = lambda dy, x: (ops.gemm(transpose_pad(dy), transpose_pad(x), out_dtype=torch.float32), colsum(dy))
+    out = {}
+    for name, M, N, K in (("image_kv", a.img_len * B, 2 * D, D), ("hidden_square", (c["horizon"] + 3) * B, D, D), ("timestep_embedder", B, D, 256)):
+        dy, x = rn(M, N), rn(M, K)
+        ms = {"gemm": [], "tn": []}
+        for n in range(2 + 7):
+            for kind in (("gemm", "tn") if n % 2 == 0 else ("tn", "gemm")):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize(dev)
+                e0.record()
+                res = old(dy, x) if kind == "gemm" else weight_grad_tn(dy, x)
+                e1.record()
+                torch.cuda.synchronize(dev)
+                if n >= 2:
+                    ms[kind].append(e0.elapsed_time(e1))
+        del res
+        plan = L.GemmTnPlan()
+        L.lib().vt_gemm_tn_plan(M, N, K, C.byref(plan))
+        out[name] = {"M": M, "N": N, "K": K, "gemm_ms": _stats(ms["gemm"]), "tn_ms": _stats(ms["tn"]),
+                     "tn_over_gemm": _stats(ms["tn"])["median"] / _stats(ms["gemm"])["median"], "launches": {"gemm": 4, "tn": 1 if plan.splits == 1 else 2},
+                     "splits": plan.splits, "rows_per_split": plan.rows_per_split, "workspace_bytes": plan.ws_bytes,
+                     "tn_tflops": 2.0 * M * N * K / (_stats(ms["tn"])["median"] * 1e-3) / 1e12}
+        del dy, x
+        torch.cuda.empty_cache()
+    out["timing"] = ("device events around the calls of one weight gradient (output and workspace allocation from the caching allocator included), "
+                     "2 warm-up + 7 timed, the two paths alternating")
+    return out
+
+
+def weight_gradient_run(a, c, sd, params, dev, B):
+    """The bf16 step (attention_backward="mfma") under weight_gradient="tn" and "gemm", alternating in this process at batch B -> dict."""
+    from vlatouch.rdt_train import RdtTrainer
+    steps = a.steps
+    sync = lambda: torch.cuda.synchronize(dev)
+    args, kw = inputs(a, B, dev)
+    kinds = ("tn", "gemm")
+    trs, peak = {}, {}
+    for kind in kinds:                                       # peak memory of one whole step of each trainer, over what is already resident
+        torch.cuda.empty_cache()
+        base = torch.cuda.memory_allocated(dev)
+        torch.cuda.reset_peak_memory_stats(dev)
+        tr = trs[kind] = RdtTrainer(sd, heads=c["heads"], horizon=64, action_dim=128, lr=a.lr, precision="bf16", attention_backward="mfma",
+                                    weight_gradient=kind, device=dev)
+        for _ in range(max(1, a.warmup)):
+            tr.get_loss(*args, **kw)
+            tr.optimizer_step()
+        sync()
+        peak[kind] = (torch.cuda.max_memory_allocated(dev) - base) / 2 ** 30
+    ph = {k: {n: [] for n in ("forward_ms", "backward_ms", "clip_adamw_ema_ms", "step_ms")} for k in kinds}
+    losses = {k: [] for k in kinds}
+    for n in range(steps):
+        for kind in (kinds if n % 2 == 0 else kinds[::-1]):  # who goes first alternates
+            tr = trs[kind]
+            sync(); t0 = time.perf_counter()
+            tr.get_loss(*args, backward=False, **kw)
+            sync(); t1 = time.perf_counter()
+            loss = tr.get_loss(*args, **kw)
+            sync(); t2 = time.perf_counter()
+            tr.optimizer_step()
+            sync(); t3 = time.perf_counter()
+            f, fb, o = 1e3 * (t1 - t0), 1e3 * (t2 - t1), 1e3 * (t3 - t2)
+            ph[kind]["forward_ms"].append(f), ph[kind]["backward_ms"].append(fb - f), ph[kind]["clip_adamw_ema_ms"].append(o), ph[kind]["step_ms"].append(fb + o)
+            losses[kind].append(float(loss))
+    out = {"batch": B, "precision": "bf16", "attention_backward": "mfma", "parameters": params, "warmup": a.warmup, "timed_steps": steps}
+    for kind in kinds:
+        out[kind] = {n: _stats(v) for n, v in ph[kind].items()}
+        out[kind]["peak_memory_gib_of_a_step"] = peak[kind]
+        out[kind]["losses"] = losses[kind]
+        out[kind]["loss_decreases"] = bool(losses[kind][-1] < losses[kind][0])
+    out["backward_tn_over_gemm"] = out["tn"]["backward_ms"]["median"] / out["gemm"]["backward_ms"]["median"]
+    out["step_tn_over_gemm"] = out["tn"]["step_ms"]["median"] / out["gemm"]["step_ms"]["median"]
+    out["backward_faster_than_gemm"] = bool(out["backward_tn_over_gemm"] < 1.0)
+    del trs, tr
+    torch.cuda.empty_cache()
+    out["weight_gradient_launches"] = weight_gradient_launches(a, c, B, dev)
+    out["timing"] = "host wall clock between two device synchronisations; the two trainers alternate and swap who goes first every step"
+    return out
+
+
 def fp16_attention_launches(a, c, B, dev):
     """Device-event time of the attention-backward launches alone in fp16 and in bf16, "wave" and "mfma", alternating, at the trainer's packed
     layouts and the three attention shapes of the step -> dict."""
@@ -558,14 +654,20 @@ def main():
                     help="mfma measures the bf16 step with the MFMA attention backward beside the wave kernels and adds it to --out")
     ap.add_argument("--step-attention-backward", default="wave", choices=["wave", "mfma"],
                     help="the attention backward of the default run's trainer (a kernel trace of the step under \"mfma\" uses this)")
+    ap.add_argument("--weight-gradient", default="gemm", choices=["gemm", "tn"],
+                    help="tn measures the bf16 step with the transpose-free weight-gradient GEMM beside the gemm path and adds it to --out")
+    ap.add_argument("--step-weight-gradient", default="gemm", choices=["gemm", "tn"],
+                    help="the weight gradient of the default run's trainer (a kernel trace of the step under \"tn\" uses this)")
     ap.add_argument("--data-parallel", default=None, choices=["fp32", "bf16"],
                     help="measures the data-parallel step over an RCCL group of world size 1 beside the ungrouped one and adds it to --out")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rdt_train_bench.json"))
     a = ap.parse_args()
     if a.attention_backward == "mfma" and a.precision == "fp32":
         ap.error("--attention-backward mfma measures a 16-bit step")
+    if "tn" in (a.weight_gradient, a.step_weight_gradient) and a.precision == "fp32":
+        ap.error("weight_gradient tn is a 16-bit kernel")
     if a.steps is None:
-        a.steps = 21 if a.attention_backward == "mfma" or a.precision == "fp16" else 10
+        a.steps = 21 if a.attention_backward == "mfma" or a.weight_gradient == "tn" or a.precision == "fp16" else 10
     from vlatouch.rdt_train import RdtTrainer
     dev = torch.device("cuda:0")
     c = dict(hidden=a.hidden, depth=a.depth, heads=a.hidden // 64, horizon=64, action_dim=128, lang_token_dim=4096, img_token_dim=1152,
@@ -594,6 +696,21 @@ def main():
         rec.setdefault("data_parallel", {})[a.data_parallel] = dict(data_parallel_run(a, c, sd, params, dev), config=c, lang_len=a.lang_len, lr=a.lr,
                                                                     device=torch.cuda.get_device_name(dev))
         print(json.dumps(rec["data_parallel"][a.data_parallel]))
+        with open(a.out, "w") as f:
+            json.dump(rec, f, indent=1)
+        print("wrote", a.out)
+        return
+    if a.weight_gradient == "tn":
+        rec = {}
+        if os.path.exists(a.out):
+            with open(a.out) as f:
+                rec = json.load(f)
+        runs = []
+        for B in a.batch:
+            runs.append(weight_gradient_run(a, c, sd, params, dev, B))
+            print(json.dumps(runs[-1]))
+        rec["weight_gradient_tn"] = dict(runs=runs, config=c, lang_len=a.lang_len, lr=a.lr, device=torch.cuda.get_device_name(dev),
+                                         backward_faster_than_gemm_at_every_batch=all(r["backward_faster_than_gemm"] for r in runs))
         with open(a.out, "w") as f:
             json.dump(rec, f, indent=1)
         print("wrote", a.out)
@@ -639,17 +756,19 @@ def main():
     if os.path.exists(a.out):
         with open(a.out) as f:
             old = json.load(f)
-        kept = {k: old[k] for k in ("accumulation", "adamw8bit", "attention_backward_mfma", "data_parallel", "fp16") if k in old}
+        kept = {k: old[k] for k in ("accumulation", "adamw8bit", "attention_backward_mfma", "data_parallel", "fp16", "weight_gradient_tn") if k in old}
     rec = {"config": c, "precision": a.precision, "parameters": params, "lang_len": a.lang_len, "warmup": a.warmup, "steps": a.steps, "lr": a.lr,
            "device": torch.cuda.get_device_name(dev), "runs": []}
     if a.step_attention_backward != "wave":
         rec["attention_backward"] = a.step_attention_backward
+    if a.step_weight_gradient != "gemm":
+        rec["weight_gradient"] = a.step_weight_gradient
     sync = lambda: torch.cuda.synchronize(dev)
     for B in a.batch:
         torch.cuda.empty_cache()
         torch.cuda.reset_peak_memory_stats(dev)
         tr = RdtTrainer(sd, heads=c["heads"], horizon=64, action_dim=128, lr=a.lr, precision=a.precision, attention_backward=a.step_attention_backward,
-                        device=dev)
+                        weight_gradient=a.step_weight_gradient, device=dev)
         args, kw = inputs(a, B, dev)
         t_f = t_fb = t_o = 0.0
         losses = []

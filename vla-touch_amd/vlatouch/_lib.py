@@ -123,6 +123,10 @@ class AttnBwdParams(C.Structure):     # VtAttnBwdParams (include/vlatouch.h)
                 [(n, C.c_int) for n in ("B", "H", "Nq", "Nk", "hd", "dtype")] + [("scale", C.c_float)])
 
 
+class GemmTnPlan(C.Structure):        # VtGemmTnPlan (include/vlatouch.h)
+    _fields_ = [("splits", C.c_int), ("rows_per_split", C.c_int), ("m_step", C.c_int), ("ws_bytes", C.c_long)]
+
+
 class UnetDesc(C.Structure):
     _fields_ = [("nets", C.c_int), ("input_dim", C.c_int), ("input_pad", C.c_int), ("cond_dim", C.c_int),
                 ("dsed", C.c_int), ("n_groups", C.c_int), ("ksize", C.c_int), ("n_levels", C.c_int),
@@ -293,6 +297,8 @@ SIGNATURES = {
     "vt_transpose_pad": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "vt_colsum_dt": (_I, [_P, _I, _L, _P, _I, _I, _P]),
     "vt_add_dt": (_I, [_P, _P, _L, _I, _P]),
+    "vt_gemm_tn_plan": (_I, [_I, _I, _I, _P]),
+    "vt_gemm_tn": (_I, [_P, _L, _P, _L, _I, _I, _I, _I, _P, _P, _P, _L, _P]),
     "vt_copy_cols_dt": (_I, [_P, _L, _L, _P, _L, _L, _L, _L, _I, _P]),
     "vt_grad_clip_multi": (_I, [_P, _I, _L, _F, _P, _P, _P]),
     "vt_mse_loss": (_I, [_P, _P, _P, _P, _L, _I, _P]),

@@ -206,13 +206,44 @@ def copy_cols(src: torch.Tensor, off: int, dst: torch.Tensor, doff: int, cols: i
             "vt_copy_cols_dt")
 
 
-def linear_bwd(x: torch.Tensor, w: torch.Tensor, dy: torch.Tensor, need_dx: bool = True, wt: Optional[torch.Tensor] = None):
+WEIGHT_GRADIENTS = ("gemm", "tn")
+
+
+def weight_grad_tn(dy: torch.Tensor, x: torch.Tensor, *, bias: bool = True):
+    """dy [M, N], x [M, K], both bf16 or both fp16, unit inner stride and row strides in multiples of 8 (column slices are read in place)
+    -> (dw [N, K] fp32 = dy^T x, db [N] fp32 = the column sums of dy, or None without `bias`): vt_gemm_tn (csrc/vt_gemm_tn.hip), one launch with
+    both operands read transposed out of LDS, plus the sum over the row splits where vt_gemm_tn_plan cuts the rows.  A shape or dtype the
+    kernel does not take raises, nothing falls back."""
+    if dy.dtype != x.dtype or dy.dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError(f"weight_grad_tn takes two bf16 or two fp16 tensors, got {dy.dtype} and {x.dtype}")
+    if dy.dim() != 2 or x.dim() != 2 or dy.shape[0] != x.shape[0] or dy.stride(1) != 1 or x.stride(1) != 1:
+        raise ValueError(f"weight_grad_tn: dy [M, N] and x [M, K] with unit inner stride, got {tuple(dy.shape)} and {tuple(x.shape)}")
+    (M, N), K = dy.shape, x.shape[1]
+    plan = L.GemmTnPlan()
+    if L.lib().vt_gemm_tn_plan(M, N, K, C.byref(plan)) != 0:
+        raise ValueError(f"weight_grad_tn does not take M={M}, N={N}, K={K}: {L.lib().vt_last_error().decode()}")
+    dw, db = _empty((N, K), dy.device), (_empty((N,), dy.device) if bias else None)
+    ws = torch.empty(plan.ws_bytes, dtype=torch.uint8, device=dy.device) if plan.ws_bytes else None
+    L.check(L.lib().vt_gemm_tn(L.ptr(dy), dy.stride(0), L.ptr(x), x.stride(0), _dt(dy), M, N, K, L.ptr(dw), L.ptr(db), L.ptr(ws), plan.ws_bytes,
+                               _sp(dy.device)), "vt_gemm_tn")
+    return dw, db
+
+
+def linear_bwd(x: torch.Tensor, w: torch.Tensor, dy: torch.Tensor, need_dx: bool = True, wt: Optional[torch.Tensor] = None, kernel: str = "gemm"):
     """y = x w^T + b -> (dx | None, dw fp32, db fp32).  fp32: exact-fp32 MFMA with the deterministic split-K of vlatouch.train.gemm;
-    bf16 operands (w, or its cached transpose wt, in bf16): bf16 MFMA with fp32 accumulation, dx rounded to bf16, dw written in fp32."""
+    bf16 operands (w, or its cached transpose wt, in bf16): bf16 MFMA with fp32 accumulation, dx rounded to bf16, dw written in fp32.
+    kernel="tn" (16-bit operands only) forms dw and db in one weight_grad_tn call instead of two transposes, a GEMM and a column sum; dx is the
+    same launch either way."""
+    if kernel not in WEIGHT_GRADIENTS:
+        raise ValueError(f"linear_bwd: kernel must be one of {WEIGHT_GRADIENTS}, got {kernel!r}")
     if x.dtype == F32:
+        if kernel == "tn":
+            raise ValueError("linear_bwd: kernel='tn' is a 16-bit kernel, got fp32 operands")
         dx = T.gemm(dy, T.transpose(w)) if need_dx else None
         return dx, T.gemm(transpose_pad(dy), transpose_pad(x)), colsum(dy)
     dx = ops.gemm(dy, wt if wt is not None else transpose_pad(w)) if need_dx else None
+    if kernel == "tn":
+        return (dx, *weight_grad_tn(dy, x))
     return dx, ops.gemm(transpose_pad(dy), transpose_pad(x), out_dtype=F32), colsum(dy)
 
 
@@ -394,6 +425,11 @@ class RdtTrainer:
     live in one store, `opt_state` (Moments32 or adam8.Moments8: zero state, table columns, the AdamW + EMA launch, checkpoint files, byte count);
     `moments(name)` reads them as fp32.
 
+    weight_gradient="tn" (bf16 / fp16 only; the default "gemm" is two transposes, the NT GEMM and a column sum per Linear) forms every Linear's
+    weight and bias gradient in one vt_gemm_tn launch (weight_grad_tn, csrc/vt_gemm_tn.hip).  Like attention_backward it is an execution choice,
+    not state: gradient bits change, checkpoints do not record it and resume under either setting.  Every 2-D weight must then have dimensions
+    that are multiples of 8 (ValueError at construction, naming the tensor).
+
     precision="fp16" with loss_scale= ("dynamic", a dict of GradScaler's init_scale / growth_factor / backoff_factor / growth_interval, or a
     positive number for a static scale) is torch.amp.GradScaler around the bf16 mode's step on IEEE half: dL/dpred is multiplied by the scale S
     (the loss is reported unscaled), the accumulators and the exchange hold scaled gradients, and optimizer_step unscales, checks and clips in
@@ -404,7 +440,7 @@ class RdtTrainer:
 
     process_group: a torch.distributed group of W ranks, one process per GPU, for data-parallel training with replicated state (None, the
     default, is the one-process trainer: same launches, same bits).  The constructor is then collective: the ranks compare parameter names and
-    shapes, gradient_accumulation_steps, precision, optimizer, comm_dtype and attention_backward, every rank raising ValueError with the
+    shapes, gradient_accumulation_steps, precision, optimizer, comm_dtype, attention_backward and weight_gradient, every rank raising ValueError with the
     differing field if they disagree, and rank 0's master parameters are broadcast.  For any k the accumulators are views into one fp32
     arena (tensor i at first_chunk_i * MT_CHUNK, padding zeroed once); `accumulate` folds with scale 1 / (k W) and, after the window's last
     fold, sums the arena over the ranks in chunk-aligned slices of at most `comm_bucket_bytes`; comm_dtype="bf16" (an exchange format, allowed
@@ -415,8 +451,8 @@ class RdtTrainer:
                  num_train_timesteps: int = 1000, beta_schedule: str = "squaredcos_cap_v2", precision: str = "fp32", lr: float = 5e-6,
                  betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, max_grad_norm: float = 1.0, lr_scheduler: str = "constant",
                  lr_warmup_steps: int = 500, ema: Optional[dict] = None, config: Optional[dict] = None, gradient_accumulation_steps: int = 1,
-                 optimizer: str = "adamw", attention_backward: str = "wave", process_group=None, comm_dtype: str = "fp32",
-                 comm_bucket_bytes: int = 256 << 20, loss_scale=None, device="cuda"):
+                 optimizer: str = "adamw", attention_backward: str = "wave", weight_gradient: str = "gemm", process_group=None,
+                 comm_dtype: str = "fp32", comm_bucket_bytes: int = 256 << 20, loss_scale=None, device="cuda"):
         if precision not in PRECISIONS:
             raise ValueError(f"precision must be one of {PRECISIONS}, got {precision!r}")
         if precision == "fp16" and loss_scale is None:
@@ -437,6 +473,14 @@ class RdtTrainer:
             raise ValueError("attention_backward='mfma' is a 16-bit kernel: it needs precision='bf16' or 'fp16' ('wave' is the fp32 path)")
         if attention_backward == "mfma" and horizon + 3 > 128:
             raise ValueError(f"attention_backward='mfma' holds at most 128 query rows, horizon + 3 = {horizon + 3}")
+        if weight_gradient not in WEIGHT_GRADIENTS:
+            raise ValueError(f"weight_gradient must be one of {WEIGHT_GRADIENTS}, got {weight_gradient!r}")
+        if weight_gradient == "tn" and precision == "fp32":
+            raise ValueError("weight_gradient='tn' is a 16-bit kernel: it needs precision='bf16' or 'fp16' ('gemm' is the fp32 path)")
+        if weight_gradient == "tn":
+            for k, v in sd.items():
+                if k.endswith(".weight") and v.dim() == 2 and (v.shape[0] % 8 or v.shape[1] % 8):
+                    raise ValueError(f"weight_gradient='tn' takes Linear weights whose dimensions are multiples of 8, {k} is {tuple(v.shape)}")
         if comm_dtype not in COMM_DTYPES:
             raise ValueError(f"comm_dtype must be one of {COMM_DTYPES}, got {comm_dtype!r} (the format of the gradient exchange, whatever the precision)")
         if int(comm_bucket_bytes) != comm_bucket_bytes or comm_bucket_bytes < 1:
@@ -461,7 +505,7 @@ class RdtTrainer:
             digest = hashlib.sha256(repr([(k, tuple(v.shape)) for k, v in self.p.items()]).encode()).hexdigest()
             diff = D.differing_field({"parameter names and shapes": digest, "gradient_accumulation_steps": int(gradient_accumulation_steps),
                                       "precision": precision, "optimizer": optimizer, "comm_dtype": comm_dtype,
-                                      "attention_backward": attention_backward,
+                                      "attention_backward": attention_backward, "weight_gradient": weight_gradient,
                                       **({} if scale_settings is None else {"loss_scale": repr(sorted(scale_settings.items()))})}, process_group)
             if diff is not None:
                 raise ValueError(f"RdtTrainer: the ranks of the process group disagree on {diff[0]}: {diff[1]}")
@@ -482,6 +526,7 @@ class RdtTrainer:
         self.adaptors = {n: self._adaptor_layers(n) for n in ("lang_adaptor", "img_adaptor", "state_adaptor")}
         self.precision = precision
         self.attention_backward = attention_backward          # an execution choice, not state: checkpoints do not record it
+        self.weight_gradient = weight_gradient                # likewise: a checkpoint written under either setting resumes under the other
         self.adt = {"fp32": F32, "bf16": torch.bfloat16, "fp16": torch.float16}[precision]      # dtype of activations, activation gradients and MFMA operands
         self.scaler: Optional[LossScaler] = LossScaler(scale_settings) if scale_settings is not None else None      # fp16: GradScaler's state
         self.last_step_skipped = False                                # the last optimizer_step found a non-finite gradient and took no step
@@ -568,7 +613,8 @@ class RdtTrainer:
 
     def _linear_bwd(self, name, x, dy, need_dx=True):
         k = f"{name}.weight"
-        dx, self.g[k], self.g[f"{name}.bias"] = linear_bwd(x, self.w16.get(k, self.p[k]), dy, need_dx, self.w16t.get(k))
+        dx, self.g[k], self.g[f"{name}.bias"] = linear_bwd(x, self.w16.get(k, self.p[k]), dy, need_dx, self.w16t.get(k),
+                                                                 kernel=self.weight_gradient)
         return dx
 
     def _norm(self, name, x):
