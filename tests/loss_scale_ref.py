@@ -1,4 +1,4 @@
-"""The statement of fp16 fine-tuning's loss scaling (vlatouch/rdt_train.py: LossScaler, RdtTrainer._optimizer_step_scaled;
+"""The statement of fp16 fine-tuning's loss scaling (vlatouch/rdt_train.py: LossScaler, RdtTrainer.optimizer_step;
 csrc/vt_train_rdt.hip: vt_grad_unscale_clip_multi), in torch on the CPU, written apart from the code it states.
 
 Order of one optimizer step (the reference's loop, VLA/train/train.py:404-453, under accelerate's fp16 mode):

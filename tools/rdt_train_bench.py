@@ -130,6 +130,69 @@ def inputs(a, B, dev):
     return args, kw
 
 
+def timed_step(tr, args, kw, dev):
+    """One step of `tr` between device synchronisations -> (forward only, forward + backward, optimizer phase) in host-clock ms, the loss."""
+    sync = lambda: torch.cuda.synchronize(dev)
+    sync(); t0 = time.perf_counter()
+    tr.get_loss(*args, backward=False, **kw)
+    sync(); t1 = time.perf_counter()
+    loss = tr.get_loss(*args, **kw)
+    sync(); t2 = time.perf_counter()
+    tr.optimizer_step()
+    sync(); t3 = time.perf_counter()
+    return 1e3 * (t1 - t0), 1e3 * (t2 - t1), 1e3 * (t3 - t2), loss
+
+
+def build_trainers(a, dev, args, kw, makers):
+    """makers: {name: factory of a trainer}.  Builds and warms up each in turn -> ({name: trainer}, {name: peak device memory in GiB of one
+    whole step of that trainer, over what was already resident})."""
+    trs, peak = {}, {}
+    for kind, make in makers.items():
+        torch.cuda.empty_cache()
+        base = torch.cuda.memory_allocated(dev)
+        torch.cuda.reset_peak_memory_stats(dev)
+        tr = trs[kind] = make()
+        for _ in range(max(1, a.warmup)):
+            tr.get_loss(*args, **kw)
+            tr.optimizer_step()
+        torch.cuda.synchronize(dev)
+        peak[kind] = (torch.cuda.max_memory_allocated(dev) - base) / 2 ** 30
+    return trs, peak
+
+
+def compare_steps(a, dev, args, kw, makers, each_step=None):
+    """The comparison every two-trainer mode makes: the trainers of `makers` (build_trainers) take `a.steps` timed steps in turn, swapping who
+    goes first, every phase device-synchronised -> {name: forward / backward / optimizer / step statistics, peak memory, losses}.
+    each_step(name, trainer) is called after every timed step."""
+    trs, peak = build_trainers(a, dev, args, kw, makers)
+    kinds = tuple(makers)
+    ph = {k: {n: [] for n in ("forward_ms", "backward_ms", "clip_adamw_ema_ms", "step_ms")} for k in kinds}
+    losses = {k: [] for k in kinds}
+    for n in range(a.steps):
+        for kind in (kinds if n % 2 == 0 else kinds[::-1]):  # who goes first alternates
+            f, fb, o, loss = timed_step(trs[kind], args, kw, dev)
+            ph[kind]["forward_ms"].append(f), ph[kind]["backward_ms"].append(fb - f), ph[kind]["clip_adamw_ema_ms"].append(o), ph[kind]["step_ms"].append(fb + o)
+            losses[kind].append(float(loss))
+            if each_step is not None:
+                each_step(kind, trs[kind])
+    del trs
+    torch.cuda.empty_cache()
+    return {k: dict({n: _stats(v) for n, v in ph[k].items()}, peak_memory_gib_of_a_step=peak[k], losses=losses[k]) for k in kinds}
+
+
+STEP_TIMING = "host wall clock between two device synchronisations; the two trainers alternate and swap who goes first every step"
+
+
+def packed_attention_views(B, N, Nk, H, cross, dt, rn, dev):
+    """(q, k, v), (dq, dk, dv) as [B, N | Nk, H, 64] views at the trainer's packed layouts: q beside a k | v buffer (cross) or one q | k | v
+    buffer; the operands drawn from `rn`, the gradients uninitialised."""
+    widths = ((N, 1), (Nk, 2)) if cross else ((N, 3),)
+    bufs = [rn(B, rows, w * H * 64) for rows, w in widths]
+    grads = [torch.empty(B, rows, w * H * 64, device=dev, dtype=dt) for rows, w in widths]
+    v3 = lambda ts: tuple(t.view(B, rows, w, H, 64)[:, :, i] for t, (rows, w) in zip(ts, widths) for i in range(w))
+    return v3(bufs), v3(grads)
+
+
 def accum_run(a, c, sd, params, dev):
     """The accumulated step at batch a.batch[0], K = a.accum, and the K = 1 optimizer phase in the same process -> dict."""
     from vlatouch.rdt_train import RdtTrainer
@@ -201,17 +264,8 @@ def optimizer_run(a, c, sd, params, dev):
     sync = lambda: torch.cuda.synchronize(dev)
     args, kw = inputs(a, B, dev)
     kinds = ("adamw8bit", "adamw")
-    trs, peak = {}, {}
-    for kind in kinds:                                       # peak memory of one whole step of each trainer, over what is already resident
-        torch.cuda.empty_cache()
-        base = torch.cuda.memory_allocated(dev)
-        torch.cuda.reset_peak_memory_stats(dev)
-        tr = trs[kind] = RdtTrainer(sd, heads=c["heads"], horizon=64, action_dim=128, lr=a.lr, precision=a.precision, optimizer=kind, device=dev)
-        for _ in range(max(1, a.warmup)):
-            tr.get_loss(*args, **kw)
-            tr.optimizer_step()
-        sync()
-        peak[kind] = (torch.cuda.max_memory_allocated(dev) - base) / 2 ** 30
+    make = lambda kind: lambda: RdtTrainer(sd, heads=c["heads"], horizon=64, action_dim=128, lr=a.lr, precision=a.precision, optimizer=kind, device=dev)
+    trs, peak = build_trainers(a, dev, args, kw, {kind: make(kind) for kind in kinds})
     ev = lambda: torch.cuda.Event(enable_timing=True)
     phase = {k: [] for k in kinds}
     phase_dev = {k: [] for k in kinds}
@@ -270,19 +324,11 @@ def attention_launches(a, c, B, dev):
     from vlatouch import _lib as L
     from vlatouch.rdt_train import attention_bwd
     H, N = c["heads"], c["horizon"] + 3
-    D = H * 64
     g = torch.Generator(device=dev).manual_seed(5)
     rn = lambda *s: torch.randn(*s, generator=g, device=dev).bfloat16()
     out = {}
     for name, Nk, cross in (("image_cross_attention", a.img_len, True), ("language_cross_attention", a.lang_len, True), ("self_attention", N, False)):
-        if cross:
-            qb, kvb, dqb, dkvb = rn(B, N, D), rn(B, Nk, 2 * D), torch.empty(B, N, D, device=dev, dtype=torch.bfloat16), torch.empty(B, Nk, 2 * D, device=dev, dtype=torch.bfloat16)
-            v4 = lambda q_, kv_: (q_.view(B, N, H, 64), kv_.view(B, Nk, 2, H, 64)[:, :, 0], kv_.view(B, Nk, 2, H, 64)[:, :, 1])
-            (q, k, v), (dq, dk, dv) = v4(qb, kvb), v4(dqb, dkvb)
-        else:
-            qkv, dqkv = rn(B, N, 3 * D), torch.empty(B, N, 3 * D, device=dev, dtype=torch.bfloat16)
-            q, k, v = (qkv.view(B, N, 3, H, 64)[:, :, i] for i in range(3))
-            dq, dk, dv = (dqkv.view(B, N, 3, H, 64)[:, :, i] for i in range(3))
+        (q, k, v), (dq, dk, dv) = packed_attention_views(B, N, Nk, H, cross, torch.bfloat16, rn, dev)
         do = rn(B, N, H, 64)
         km = torch.ones(B, Nk, dtype=torch.uint8, device=dev) if name == "language_cross_attention" else None
         ms = {"wave": [], "mfma": []}
@@ -306,54 +352,23 @@ def attention_launches(a, c, B, dev):
 def attention_run(a, c, sd, params, dev, B):
     """The bf16 step under attention_backward="mfma" and "wave", alternating in this process at batch B -> dict."""
     from vlatouch.rdt_train import RdtTrainer
-    steps = a.steps
-    sync = lambda: torch.cuda.synchronize(dev)
     args, kw = inputs(a, B, dev)
     kinds = ("mfma", "wave")
-    trs, peak = {}, {}
-    for kind in kinds:                                       # peak memory of one whole step of each trainer, over what is already resident
-        torch.cuda.empty_cache()
-        base = torch.cuda.memory_allocated(dev)
-        torch.cuda.reset_peak_memory_stats(dev)
-        tr = trs[kind] = RdtTrainer(sd, heads=c["heads"], horizon=64, action_dim=128, lr=a.lr, precision="bf16", attention_backward=kind, device=dev)
-        for _ in range(max(1, a.warmup)):
-            tr.get_loss(*args, **kw)
-            tr.optimizer_step()
-        sync()
-        peak[kind] = (torch.cuda.max_memory_allocated(dev) - base) / 2 ** 30
-    ph = {k: {n: [] for n in ("forward_ms", "backward_ms", "clip_adamw_ema_ms", "step_ms")} for k in kinds}
-    losses = {k: [] for k in kinds}
-    for n in range(steps):
-        for kind in (kinds if n % 2 == 0 else kinds[::-1]):  # who goes first alternates
-            tr = trs[kind]
-            sync(); t0 = time.perf_counter()
-            tr.get_loss(*args, backward=False, **kw)
-            sync(); t1 = time.perf_counter()
-            loss = tr.get_loss(*args, **kw)
-            sync(); t2 = time.perf_counter()
-            tr.optimizer_step()
-            sync(); t3 = time.perf_counter()
-            f, fb, o = 1e3 * (t1 - t0), 1e3 * (t2 - t1), 1e3 * (t3 - t2)
-            ph[kind]["forward_ms"].append(f), ph[kind]["backward_ms"].append(fb - f), ph[kind]["clip_adamw_ema_ms"].append(o), ph[kind]["step_ms"].append(fb + o)
-            losses[kind].append(float(loss))
-    out = {"batch": B, "precision": "bf16", "parameters": params, "warmup": a.warmup, "timed_steps": steps}
+    make = lambda kind: lambda: RdtTrainer(sd, heads=c["heads"], horizon=64, action_dim=128, lr=a.lr, precision="bf16", attention_backward=kind, device=dev)
+    out = {"batch": B, "precision": "bf16", "parameters": params, "warmup": a.warmup, "timed_steps": a.steps}
+    out.update(compare_steps(a, dev, args, kw, {kind: make(kind) for kind in kinds}))
     for kind in kinds:
-        out[kind] = {n: _stats(v) for n, v in ph[kind].items()}
-        out[kind]["peak_memory_gib_of_a_step"] = peak[kind]
-        out[kind]["losses"] = losses[kind]
-        out[kind]["loss_decreases"] = bool(losses[kind][-1] < losses[kind][0])
+        out[kind]["loss_decreases"] = bool(out[kind]["losses"][-1] < out[kind]["losses"][0])
     out["backward_mfma_over_wave"] = out["mfma"]["backward_ms"]["median"] / out["wave"]["backward_ms"]["median"]
     out["step_mfma_over_wave"] = out["mfma"]["step_ms"]["median"] / out["wave"]["step_ms"]["median"]
     out["backward_faster_than_wave"] = bool(out["backward_mfma_over_wave"] < 1.0)
-    del trs, tr
-    torch.cuda.empty_cache()
     out["attention_backward_launches"] = attention_launches(a, c, B, dev)
     y = "not measured: --no-yardstick" if a.no_yardstick else yardstick(sd, c, args, kw, dev)
     if isinstance(y, dict):
         for kind in kinds:
             y[f"ratio_torch_over_{kind}"] = y["fwd_bwd_ms"] / (out[kind]["forward_ms"]["median"] + out[kind]["backward_ms"]["median"])
     out["torch_autograd_yardstick"] = y
-    out["timing"] = "host wall clock between two device synchronisations; the two trainers alternate and swap who goes first every step"
+    out["timing"] = STEP_TIMING
     return out
 
 
@@ -399,50 +414,19 @@ def weight_gradient_launches(a, c, B, dev):
 def weight_gradient_run(a, c, sd, params, dev, B):
     """The bf16 step (attention_backward="mfma") under weight_gradient="tn" and "gemm", alternating in this process at batch B -> dict."""
     from vlatouch.rdt_train import RdtTrainer
-    steps = a.steps
-    sync = lambda: torch.cuda.synchronize(dev)
     args, kw = inputs(a, B, dev)
     kinds = ("tn", "gemm")
-    trs, peak = {}, {}
-    for kind in kinds:                                       # peak memory of one whole step of each trainer, over what is already resident
-        torch.cuda.empty_cache()
-        base = torch.cuda.memory_allocated(dev)
-        torch.cuda.reset_peak_memory_stats(dev)
-        tr = trs[kind] = RdtTrainer(sd, heads=c["heads"], horizon=64, action_dim=128, lr=a.lr, precision="bf16", attention_backward="mfma",
-                                    weight_gradient=kind, device=dev)
-        for _ in range(max(1, a.warmup)):
-            tr.get_loss(*args, **kw)
-            tr.optimizer_step()
-        sync()
-        peak[kind] = (torch.cuda.max_memory_allocated(dev) - base) / 2 ** 30
-    ph = {k: {n: [] for n in ("forward_ms", "backward_ms", "clip_adamw_ema_ms", "step_ms")} for k in kinds}
-    losses = {k: [] for k in kinds}
-    for n in range(steps):
-        for kind in (kinds if n % 2 == 0 else kinds[::-1]):  # who goes first alternates
-            tr = trs[kind]
-            sync(); t0 = time.perf_counter()
-            tr.get_loss(*args, backward=False, **kw)
-            sync(); t1 = time.perf_counter()
-            loss = tr.get_loss(*args, **kw)
-            sync(); t2 = time.perf_counter()
-            tr.optimizer_step()
-            sync(); t3 = time.perf_counter()
-            f, fb, o = 1e3 * (t1 - t0), 1e3 * (t2 - t1), 1e3 * (t3 - t2)
-            ph[kind]["forward_ms"].append(f), ph[kind]["backward_ms"].append(fb - f), ph[kind]["clip_adamw_ema_ms"].append(o), ph[kind]["step_ms"].append(fb + o)
-            losses[kind].append(float(loss))
-    out = {"batch": B, "precision": "bf16", "attention_backward": "mfma", "parameters": params, "warmup": a.warmup, "timed_steps": steps}
+    make = lambda kind: lambda: RdtTrainer(sd, heads=c["heads"], horizon=64, action_dim=128, lr=a.lr, precision="bf16", attention_backward="mfma",
+                                           weight_gradient=kind, device=dev)
+    out = {"batch": B, "precision": "bf16", "attention_backward": "mfma", "parameters": params, "warmup": a.warmup, "timed_steps": a.steps}
+    out.update(compare_steps(a, dev, args, kw, {kind: make(kind) for kind in kinds}))
     for kind in kinds:
-        out[kind] = {n: _stats(v) for n, v in ph[kind].items()}
-        out[kind]["peak_memory_gib_of_a_step"] = peak[kind]
-        out[kind]["losses"] = losses[kind]
-        out[kind]["loss_decreases"] = bool(losses[kind][-1] < losses[kind][0])
+        out[kind]["loss_decreases"] = bool(out[kind]["losses"][-1] < out[kind]["losses"][0])
     out["backward_tn_over_gemm"] = out["tn"]["backward_ms"]["median"] / out["gemm"]["backward_ms"]["median"]
     out["step_tn_over_gemm"] = out["tn"]["step_ms"]["median"] / out["gemm"]["step_ms"]["median"]
     out["backward_faster_than_gemm"] = bool(out["backward_tn_over_gemm"] < 1.0)
-    del trs, tr
-    torch.cuda.empty_cache()
     out["weight_gradient_launches"] = weight_gradient_launches(a, c, B, dev)
-    out["timing"] = "host wall clock between two device synchronisations; the two trainers alternate and swap who goes first every step"
+    out["timing"] = STEP_TIMING
     return out
 
 
@@ -451,22 +435,13 @@ def fp16_attention_launches(a, c, B, dev):
     layouts and the three attention shapes of the step -> dict."""
     from vlatouch.rdt_train import attention_bwd
     H, N = c["heads"], c["horizon"] + 3
-    D = H * 64
     g = torch.Generator(device=dev).manual_seed(5)
     out = {}
     for name, Nk, cross in (("image_cross_attention", a.img_len, True), ("language_cross_attention", a.lang_len, True), ("self_attention", N, False)):
         views = {}
         for dt in (torch.float16, torch.bfloat16):
             rn = lambda *s: (0.5 * torch.randn(*s, generator=g, device=dev)).to(dt)
-            if cross:
-                qb, kvb, dqb, dkvb = rn(B, N, D), rn(B, Nk, 2 * D), torch.empty(B, N, D, device=dev, dtype=dt), torch.empty(B, Nk, 2 * D, device=dev, dtype=dt)
-                v4 = lambda q_, kv_: (q_.view(B, N, H, 64), kv_.view(B, Nk, 2, H, 64)[:, :, 0], kv_.view(B, Nk, 2, H, 64)[:, :, 1])
-                qkv3, d3 = v4(qb, kvb), v4(dqb, dkvb)
-            else:
-                qkv, dqkv = rn(B, N, 3 * D), torch.empty(B, N, 3 * D, device=dev, dtype=dt)
-                qkv3 = tuple(qkv.view(B, N, 3, H, 64)[:, :, i] for i in range(3))
-                d3 = tuple(dqkv.view(B, N, 3, H, 64)[:, :, i] for i in range(3))
-            views[dt] = (qkv3, d3, rn(B, N, H, 64))
+            views[dt] = (*packed_attention_views(B, N, Nk, H, cross, dt, rn, dev), rn(B, N, H, 64))
         km = torch.ones(B, Nk, dtype=torch.uint8, device=dev) if name == "language_cross_attention" else None
         combos = [(dt, kind) for kind in ("mfma", "wave") for dt in (torch.float16, torch.bfloat16)]
         ms = {cb: [] for cb in combos}
@@ -494,54 +469,19 @@ def fp16_run(a, c, sd, params, dev, B):
     """The fp16 step (dynamic loss scaling) beside the bf16 step, alternating in this process at batch B, both under a.attention_backward and
     a.optimizer -> dict with the phases, the losses and the scale trajectory."""
     from vlatouch.rdt_train import RdtTrainer
-    steps = a.steps
-    sync = lambda: torch.cuda.synchronize(dev)
     args, kw = inputs(a, B, dev)
-    kinds = ("fp16", "bf16")
-    trs, peak = {}, {}
-    for kind in kinds:
-        torch.cuda.empty_cache()
-        base = torch.cuda.memory_allocated(dev)
-        torch.cuda.reset_peak_memory_stats(dev)
-        extra = dict(loss_scale="dynamic") if kind == "fp16" else {}
-        tr = trs[kind] = RdtTrainer(sd, heads=c["heads"], horizon=64, action_dim=128, lr=a.lr, precision=kind, attention_backward=a.attention_backward,
-                                    optimizer=a.optimizer, device=dev, **extra)
-        for _ in range(max(1, a.warmup)):
-            tr.get_loss(*args, **kw)
-            tr.optimizer_step()
-        sync()
-        peak[kind] = (torch.cuda.max_memory_allocated(dev) - base) / 2 ** 30
-    ph = {k: {n: [] for n in ("forward_ms", "backward_ms", "clip_adamw_ema_ms", "step_ms")} for k in kinds}
-    losses = {k: [] for k in kinds}
-    scales, skipped = [], []
-    for n in range(steps):
-        for kind in (kinds if n % 2 == 0 else kinds[::-1]):  # who goes first alternates
-            tr = trs[kind]
-            sync(); t0 = time.perf_counter()
-            tr.get_loss(*args, backward=False, **kw)
-            sync(); t1 = time.perf_counter()
-            loss = tr.get_loss(*args, **kw)
-            sync(); t2 = time.perf_counter()
-            tr.optimizer_step()
-            sync(); t3 = time.perf_counter()
-            f, fb, o = 1e3 * (t1 - t0), 1e3 * (t2 - t1), 1e3 * (t3 - t2)
-            ph[kind]["forward_ms"].append(f), ph[kind]["backward_ms"].append(fb - f), ph[kind]["clip_adamw_ema_ms"].append(o), ph[kind]["step_ms"].append(fb + o)
-            losses[kind].append(float(loss))
-            if kind == "fp16":
-                scales.append(tr.loss_scale_value), skipped.append(bool(tr.last_step_skipped))
-    out = {"batch": B, "attention_backward": a.attention_backward, "optimizer": a.optimizer, "parameters": params, "warmup": a.warmup, "timed_steps": steps}
-    for kind in kinds:
-        out[kind] = {n: _stats(v) for n, v in ph[kind].items()}
-        out[kind]["peak_memory_gib_of_a_step"] = peak[kind]
-        out[kind]["losses"] = losses[kind]
-    out["fp16"].update(loss_scale_after_each_step=scales, step_skipped=skipped, skipped_steps_warmup_included=trs["fp16"].skipped_steps)
+    make = lambda kind, **extra: lambda: RdtTrainer(sd, heads=c["heads"], horizon=64, action_dim=128, lr=a.lr, precision=kind,
+                                                    attention_backward=a.attention_backward, optimizer=a.optimizer, device=dev, **extra)
+    traj = []                                                # fp16: (scale, step skipped, steps skipped so far) after every timed step
+    each_step = lambda kind, tr: traj.append((tr.loss_scale_value, bool(tr.last_step_skipped), tr.skipped_steps)) if kind == "fp16" else None
+    out = {"batch": B, "attention_backward": a.attention_backward, "optimizer": a.optimizer, "parameters": params, "warmup": a.warmup, "timed_steps": a.steps}
+    out.update(compare_steps(a, dev, args, kw, {"fp16": make("fp16", loss_scale="dynamic"), "bf16": make("bf16")}, each_step))
+    out["fp16"].update(loss_scale_after_each_step=[t[0] for t in traj], step_skipped=[t[1] for t in traj], skipped_steps_warmup_included=traj[-1][2])
     for n in ("forward_ms", "backward_ms", "clip_adamw_ema_ms", "step_ms"):
         out[f"{n[:-3]}_fp16_over_bf16"] = out["fp16"][n]["median"] / out["bf16"][n]["median"]
         out[f"{n[:-3]}_fp16_minus_bf16_ms"] = out["fp16"][n]["median"] - out["bf16"][n]["median"]
-    del trs, tr
-    torch.cuda.empty_cache()
     out["attention_backward_launches"] = fp16_attention_launches(a, c, B, dev)
-    out["timing"] = "host wall clock between two device synchronisations; the two trainers alternate and swap who goes first every step"
+    out["timing"] = STEP_TIMING
     return out
 
 
@@ -634,6 +574,36 @@ def data_parallel_run(a, c, sd, params, dev):
     return out
 
 
+SECTIONS = ("accumulation", "adamw8bit", "attention_backward_mfma", "data_parallel", "fp16", "weight_gradient_tn")      # the modes' keys of --out
+
+
+def merge_record(path, key, section, sub=None) -> None:
+    """Set `key` (or `key`[`sub`]) of the JSON record at `path` to `section`, keeping what else the file holds.  key=None is the default
+    run: `section`'s keys become the record's and only the other modes' SECTIONS stay."""
+    rec = {}
+    if os.path.exists(path):
+        with open(path) as f:
+            rec = json.load(f)
+    if key is None:
+        rec = dict(section, **{k: rec[k] for k in SECTIONS if k in rec})
+    elif sub is None:
+        rec[key] = section
+    else:
+        rec.setdefault(key, {})[sub] = section
+    with open(path, "w") as f:
+        json.dump(rec, f, indent=1)
+    print("wrote", path)
+
+
+def per_batch(run, a, *rest) -> list:
+    """run(a, *rest, B) for every --batch size, each result printed as it arrives."""
+    runs = []
+    for B in a.batch:
+        runs.append(run(a, *rest, B))
+        print(json.dumps(runs[-1]))
+    return runs
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, nargs="+", default=[4, 32])
@@ -674,96 +644,30 @@ def main():
              state_token_dim=128, max_lang_cond_len=1024, img_cond_len=a.img_len)
     sd = synth.fill_state_dict_device(synth.rdt_runner_shapes(**c), dev, torch.float32, seed=7)
     params = sum(v.numel() for v in sd.values())
+    meta = dict(config=c, lang_len=a.lang_len, lr=a.lr, device=torch.cuda.get_device_name(dev))
     if a.precision == "fp16":
-        rec = {}
-        if os.path.exists(a.out):
-            with open(a.out) as f:
-                rec = json.load(f)
-        runs = []
-        for B in a.batch:
-            runs.append(fp16_run(a, c, sd, params, dev, B))
-            print(json.dumps(runs[-1]))
-        rec["fp16"] = dict(runs=runs, config=c, lang_len=a.lang_len, lr=a.lr, device=torch.cuda.get_device_name(dev))
-        with open(a.out, "w") as f:
-            json.dump(rec, f, indent=1)
-        print("wrote", a.out)
-        return
+        return merge_record(a.out, "fp16", dict(runs=per_batch(fp16_run, a, c, sd, params, dev), **meta))
     if a.data_parallel is not None:
-        rec = {}
-        if os.path.exists(a.out):
-            with open(a.out) as f:
-                rec = json.load(f)
-        rec.setdefault("data_parallel", {})[a.data_parallel] = dict(data_parallel_run(a, c, sd, params, dev), config=c, lang_len=a.lang_len, lr=a.lr,
-                                                                    device=torch.cuda.get_device_name(dev))
-        print(json.dumps(rec["data_parallel"][a.data_parallel]))
-        with open(a.out, "w") as f:
-            json.dump(rec, f, indent=1)
-        print("wrote", a.out)
-        return
+        section = dict(data_parallel_run(a, c, sd, params, dev), **meta)
+        print(json.dumps(section))
+        return merge_record(a.out, "data_parallel", section, sub=a.data_parallel)
     if a.weight_gradient == "tn":
-        rec = {}
-        if os.path.exists(a.out):
-            with open(a.out) as f:
-                rec = json.load(f)
-        runs = []
-        for B in a.batch:
-            runs.append(weight_gradient_run(a, c, sd, params, dev, B))
-            print(json.dumps(runs[-1]))
-        rec["weight_gradient_tn"] = dict(runs=runs, config=c, lang_len=a.lang_len, lr=a.lr, device=torch.cuda.get_device_name(dev),
-                                         backward_faster_than_gemm_at_every_batch=all(r["backward_faster_than_gemm"] for r in runs))
-        with open(a.out, "w") as f:
-            json.dump(rec, f, indent=1)
-        print("wrote", a.out)
-        return
+        runs = per_batch(weight_gradient_run, a, c, sd, params, dev)
+        return merge_record(a.out, "weight_gradient_tn", dict(runs=runs, **meta, backward_faster_than_gemm_at_every_batch=all(r["backward_faster_than_gemm"] for r in runs)))
     if a.attention_backward == "mfma":
-        rec = {}
-        if os.path.exists(a.out):
-            with open(a.out) as f:
-                rec = json.load(f)
-        runs = []
-        for B in a.batch:
-            runs.append(attention_run(a, c, sd, params, dev, B))
-            print(json.dumps(runs[-1]))
-        rec["attention_backward_mfma"] = dict(runs=runs, config=c, lang_len=a.lang_len, lr=a.lr, device=torch.cuda.get_device_name(dev),
-                                              backward_faster_than_wave_at_every_batch=all(r["backward_faster_than_wave"] for r in runs))
-        with open(a.out, "w") as f:
-            json.dump(rec, f, indent=1)
-        print("wrote", a.out)
-        return
-    if a.optimizer == "adamw8bit":
-        rec = {}
-        if os.path.exists(a.out):
-            with open(a.out) as f:
-                rec = json.load(f)
-        rec["adamw8bit"] = dict(optimizer_run(a, c, sd, params, dev), config=c, lang_len=a.lang_len, lr=a.lr, device=torch.cuda.get_device_name(dev))
-        print(json.dumps(rec["adamw8bit"]))
-        with open(a.out, "w") as f:
-            json.dump(rec, f, indent=1)
-        print("wrote", a.out)
-        return
-    if a.accum > 1:
-        rec = {}
-        if os.path.exists(a.out):
-            with open(a.out) as f:
-                rec = json.load(f)
-        rec["accumulation"] = dict(accum_run(a, c, sd, params, dev), config=c, lang_len=a.lang_len, lr=a.lr, device=torch.cuda.get_device_name(dev))
-        print(json.dumps(rec["accumulation"]))
-        with open(a.out, "w") as f:
-            json.dump(rec, f, indent=1)
-        print("wrote", a.out)
-        return
-    kept = {}
-    if os.path.exists(a.out):
-        with open(a.out) as f:
-            old = json.load(f)
-        kept = {k: old[k] for k in ("accumulation", "adamw8bit", "attention_backward_mfma", "data_parallel", "fp16", "weight_gradient_tn") if k in old}
+        runs = per_batch(attention_run, a, c, sd, params, dev)
+        return merge_record(a.out, "attention_backward_mfma", dict(runs=runs, **meta, backward_faster_than_wave_at_every_batch=all(r["backward_faster_than_wave"] for r in runs)))
+    if a.optimizer == "adamw8bit" or a.accum > 1:
+        key, run = ("adamw8bit", optimizer_run) if a.optimizer == "adamw8bit" else ("accumulation", accum_run)
+        section = dict(run(a, c, sd, params, dev), **meta)
+        print(json.dumps(section))
+        return merge_record(a.out, key, section)
     rec = {"config": c, "precision": a.precision, "parameters": params, "lang_len": a.lang_len, "warmup": a.warmup, "steps": a.steps, "lr": a.lr,
            "device": torch.cuda.get_device_name(dev), "runs": []}
     if a.step_attention_backward != "wave":
         rec["attention_backward"] = a.step_attention_backward
     if a.step_weight_gradient != "gemm":
         rec["weight_gradient"] = a.step_weight_gradient
-    sync = lambda: torch.cuda.synchronize(dev)
     for B in a.batch:
         torch.cuda.empty_cache()
         torch.cuda.reset_peak_memory_stats(dev)
@@ -773,17 +677,11 @@ def main():
         t_f = t_fb = t_o = 0.0
         losses = []
         for n in range(a.warmup + a.steps):
-            sync(); t0 = time.perf_counter()
-            tr.get_loss(*args, backward=False, **kw)
-            sync(); t1 = time.perf_counter()
-            loss = tr.get_loss(*args, **kw)
-            sync(); t2 = time.perf_counter()
-            tr.optimizer_step()
-            sync(); t3 = time.perf_counter()
+            f, fb, o, loss = timed_step(tr, args, kw, dev)
             if n >= a.warmup:
-                t_f, t_fb, t_o = t_f + t1 - t0, t_fb + t2 - t1, t_o + t3 - t2
+                t_f, t_fb, t_o = t_f + f, t_fb + fb, t_o + o
                 losses.append(float(loss))
-        k = 1e3 / a.steps
+        k = 1.0 / a.steps
         flops = 3 * 2 * forward_macs(c, B, a.lang_len)
         step_ms = (t_fb + t_o) * k
         run = {"batch": B, "forward_ms": t_f * k, "backward_ms": (t_fb - t_f) * k, "clip_adamw_ema_ms": t_o * k, "step_ms": step_ms,
@@ -798,10 +696,7 @@ def main():
                 run["torch_autograd_yardstick"]["ratio_torch_over_this"] = run["torch_autograd_yardstick"]["fwd_bwd_ms"] / ((t_fb) * k)
         print(json.dumps(run))
         rec["runs"].append(run)
-    rec.update(kept)                              # measured by --accum K / --optimizer adamw8bit: not this run's to drop
-    with open(a.out, "w") as f:
-        json.dump(rec, f, indent=1)
-    print("wrote", a.out)
+    merge_record(a.out, None, rec)                # the other modes' sections are not this run's to drop
 
 
 if __name__ == "__main__":

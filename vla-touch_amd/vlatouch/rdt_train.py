@@ -644,20 +644,78 @@ class RdtTrainer:
     def _embed_fwd(self, name, t):
         return self._mlp_fwd([f"{name}.mlp.0", f"{name}.mlp.2"], timestep_embed(t, self.freqs, self.adt), L.ACT_SILU)
 
-    def _heads4(self, buf2d, B, N, col0, row_width):
-        """[B*N, row_width] buffer -> the [B, N, H, 64] view of its columns col0 .. col0 + hidden."""
-        return buf2d.view(B, N, row_width)[:, :, col0:col0 + self.hidden].unflatten(2, (self.heads, 64))
+    def _empty(self, *shape) -> torch.Tensor:
+        return torch.empty(shape, dtype=self.adt, device=self.device)
 
-    # ---- forward with the tape, loss, backward
-    def get_loss(self, lang_tokens, lang_attn_mask, img_tokens, state_tokens, action_gt, action_mask, ctrl_freqs, *, noise, timesteps,
-                 backward: bool = True) -> torch.Tensor:
-        """compute_loss's arguments (rdt_runner.py:168-182) plus the two random draws it makes: noise [B, horizon, action_dim] and timesteps [B]
-        (integers in [0, num_train_timesteps)).  -> the loss as a 0-d fp32 device tensor; with backward=True the gradients are left in `self.g`."""
-        dev, D, Hh, hor, A = self.device, self.hidden, self.heads, self.horizon, self.action_dim
+    def _heads4(self, cols2d, B):
+        """A 2-D column view [B * N, hidden] (unit inner stride, any row stride) -> its [B, N, H, 64] view."""
+        return cols2d.unflatten(0, (B, cols2d.shape[0] // B)).unflatten(2, (self.heads, 64))
+
+    # ---- the attention sub-block the self- and the cross-attention share (timm Attention with q / k RmsNorm; blocks.py:102-138)
+    def _attn_fwd(self, name, q, k, v, B, kmask=None):
+        """q [B * Nq, hidden], k, v [B * Nk, hidden]: column views of the projections' outputs (unit inner stride, any row stride).  Saves the
+        pre-norm q and k, applies `name`.q_norm / k_norm in place and attends -> (o [B * Nq, hidden], what `_attn_bwd` reads)."""
+        raw = q.clone(), k.clone()
+        for t, n in ((q, "q_norm"), (k, "k_norm")):
+            ops.headnorm_(t, self.heads, self.p[f"{name}.{n}.weight"], 1e-6, self.norm_mode, tok_stride=t.stride(0), tokens=t.shape[0])
+        return ops.attention(*(self._heads4(t, B) for t in (q, k, v)), kmask=kmask).view(q.shape[0], self.hidden), (q, k, v, *raw)
+
+    def _attn_bwd(self, name, saved, do, dq, dk, dv, B, kmask=None) -> None:
+        """do [B * Nq, hidden] -> dq, dk, dv: column views of the buffer the projections' backward reads, filled with the gradients of the
+        pre-norm q, k and of v; leaves d `name`.q_norm / k_norm in `self.g`."""
+        q, k, v, q_raw, k_raw = saved
+        attention_bwd(*(self._heads4(t, B) for t in (q, k, v, do, dq, dk, dv)), kmask=kmask, kernel=self.attention_backward)
+        for n, raw, d in (("q_norm", q_raw, dq), ("k_norm", k_raw, dk)):
+            self.g[f"{name}.{n}.weight"] = headnorm_bwd_(raw, d, self.heads, self.p[f"{name}.{n}.weight"], 1e-6, self.norm_mode)
+
+    # ---- one RDT block; its condition is c [B * Lc, hidden], the tokens it attends to, and km, their key mask or None
+    def _block_fwd(self, i, x, c, km):
+        """Block i: (x [B * N, hidden], condition) -> (x, tape entry)."""
+        b, D, B = f"model.blocks.{i}", self.hidden, x.shape[0] // (self.horizon + 3)
+        tb = {"x0": x}
+        # self-attention
+        tb["h1"] = self._norm(f"{b}.norm1", x)
+        tb["o1"], tb["attn"] = self._attn_fwd(f"{b}.attn", *self._linear(f"{b}.attn.qkv", tb["h1"]).split(D, dim=1), B)
+        x = tb["x1"] = self._linear(f"{b}.attn.proj", tb["o1"], residual=x)
+        # cross-attention: q from the block, k | v from the condition
+        tb["h2"] = self._norm(f"{b}.norm2", x)
+        q = self._linear(f"{b}.cross_attn.q", tb["h2"])
+        tb["o2"], tb["cross_attn"] = self._attn_fwd(f"{b}.cross_attn", q, *self._linear(f"{b}.cross_attn.kv", c).split(D, dim=1), B, km)
+        x = tb["x2"] = self._linear(f"{b}.cross_attn.proj", tb["o2"], residual=x)
+        # FFN (timm Mlp, tanh-GELU)
+        tb["h3"] = self._norm(f"{b}.norm3", x)
+        tb["a"] = self._linear(f"{b}.ffn.fc1", tb["h3"])
+        tb["gl"] = act(tb["a"], L.ACT_GELU_TANH)
+        return self._linear(f"{b}.ffn.fc2", tb["gl"], residual=x), tb
+
+    def _block_bwd(self, i, tb, d, c, km):
+        """Block i: (tape entry, d loss / d its output, condition) -> (d loss / d its input, d loss / d c)."""
+        b, D, B = f"model.blocks.{i}", self.hidden, d.shape[0] // (self.horizon + 3)
+        # FFN
+        dg = self._linear_bwd(f"{b}.ffn.fc2", tb["gl"], d)
+        dh = self._linear_bwd(f"{b}.ffn.fc1", tb["h3"], act(tb["a"], L.ACT_GELU_TANH, dg))
+        d = add_(self._norm_bwd(f"{b}.norm3", tb["x2"], dh), d)
+        # cross-attention
+        do = self._linear_bwd(f"{b}.cross_attn.proj", tb["o2"], d)
+        dq, dkv = self._empty(d.shape[0], D), self._empty(c.shape[0], 2 * D)
+        self._attn_bwd(f"{b}.cross_attn", tb["cross_attn"], do, dq, *dkv.split(D, dim=1), B, km)
+        dc = self._linear_bwd(f"{b}.cross_attn.kv", c, dkv)
+        dh = self._linear_bwd(f"{b}.cross_attn.q", tb["h2"], dq)
+        d = add_(self._norm_bwd(f"{b}.norm2", tb["x1"], dh), d)
+        # self-attention
+        do = self._linear_bwd(f"{b}.attn.proj", tb["o1"], d)
+        dqkv = self._empty(d.shape[0], 3 * D)
+        self._attn_bwd(f"{b}.attn", tb["attn"], do, *dqkv.split(D, dim=1), B)
+        dh = self._linear_bwd(f"{b}.attn.qkv", tb["h1"], dqkv)
+        return add_(self._norm_bwd(f"{b}.norm1", tb["x0"], dh), d), dc
+
+    # ---- get_loss's stages: inputs, a forward that returns the tape, the loss, a backward that consumes the tape
+    def _inputs(self, lang_tokens, lang_attn_mask, img_tokens, state_tokens, action_gt, action_mask, ctrl_freqs, noise, timesteps) -> dict:
+        """get_loss's arguments checked and on the device: fp32 and contiguous, the language and image tokens in the activation dtype."""
+        dev, hor, A = self.device, self.horizon, self.action_dim
         f = lambda a: torch.as_tensor(a).to(dev, F32).contiguous()
         lang, img, state, act_gt, amask, noise = f(lang_tokens), f(img_tokens), f(state_tokens), f(action_gt), f(action_mask), f(noise)
         B, Ll, Li = lang.shape[0], lang.shape[1], img.shape[1]
-        N = hor + 3
         if act_gt.shape != (B, hor, A) or noise.shape != act_gt.shape or state.shape != (B, 1, A) or amask.shape != (B, 1, A):
             raise ValueError("get_loss: state_tokens / action_mask must be [B, 1, action_dim], action_gt / noise [B, horizon, action_dim]")
         if Ll > self.p["model.lang_cond_pos_embed"].shape[1] or Li != self.p["model.img_cond_pos_embed"].shape[1]:
@@ -665,137 +723,85 @@ class RdtTrainer:
         ts = torch.as_tensor(timesteps)
         if ts.numel() != B:
             raise ValueError("get_loss: timesteps must hold one integer per sample")
-        ts = ts.reshape(B).to(dev, torch.int64).contiguous()
-        freqs = f(ctrl_freqs).reshape(B)
         kmask = torch.as_tensor(lang_attn_mask).to(dev).to(torch.uint8).contiguous()
         if kmask.shape != (B, Ll):
             raise ValueError("get_loss: lang_attn_mask must be [B, lang_len]")
-        gelu, mode = L.ACT_GELU_TANH, self.norm_mode
-        p = self.p
+        if self.adt != F32:
+            lang, img = ops.cast(lang, self.adt), ops.cast(img, self.adt)
+        return dict(B=B, lang=lang, img=img, state=state, act_gt=act_gt, amask=amask, noise=noise, ts=ts.reshape(B).to(dev, torch.int64).contiguous(),
+                    freqs=f(ctrl_freqs).reshape(B), kmask=kmask)
 
-        # tokens: DDPM forward process + layout, the three adaptors, the two embedders, position embeddings
-        adt = self.adt
-        new = lambda *shape: torch.empty(shape, dtype=adt, device=dev)
-        if adt != F32:
-            lang, img = ops.cast(lang, adt), ops.cast(img, adt)
-        sa_in = ddpm_qsample(state, act_gt, noise, amask, ts, self.ab, adt).view(B * (hor + 1), 2 * A)
-        sa, tp_state = self._mlp_fwd(self.adaptors["state_adaptor"], sa_in, gelu)
-        lang_c, tp_lang = self._mlp_fwd(self.adaptors["lang_adaptor"], lang.view(B * Ll, -1), gelu)
-        img_c, tp_img = self._mlp_fwd(self.adaptors["img_adaptor"], img.view(B * Li, -1), gelu)
-        te, tp_t = self._embed_fwd("model.t_embedder", ts.to(F32))
-        fe, tp_f = self._embed_fwd("model.freq_embedder", freqs)
-        x = new(B, N * D)
+    def _forward(self, inp: dict) -> dict:
+        """Tokens (DDPM forward process + layout, the three adaptors, the two embedders, position embeddings), the blocks and the final layer
+        -> the tape: what the loss and `_backward` read."""
+        p, D, hor, A, gelu = self.p, self.hidden, self.horizon, self.action_dim, L.ACT_GELU_TANH
+        B, N, tape = inp["B"], hor + 3, {"B": inp["B"], "blocks": []}
+        sa_in = ddpm_qsample(inp["state"], inp["act_gt"], inp["noise"], inp["amask"], inp["ts"], self.ab, self.adt).view(B * (hor + 1), 2 * A)
+        sa, tape["state_adaptor"] = self._mlp_fwd(self.adaptors["state_adaptor"], sa_in, gelu)
+        lang_c, tape["lang_adaptor"] = self._mlp_fwd(self.adaptors["lang_adaptor"], inp["lang"].flatten(0, 1), gelu)
+        img_c, tape["img_adaptor"] = self._mlp_fwd(self.adaptors["img_adaptor"], inp["img"].flatten(0, 1), gelu)
+        te, tape["t_embedder"] = self._embed_fwd("model.t_embedder", inp["ts"].to(F32))
+        fe, tape["freq_embedder"] = self._embed_fwd("model.freq_embedder", inp["freqs"])
+        x = self._empty(B, N * D)
         copy_cols(te, 0, x, 0, D)
         copy_cols(fe, 0, x, D, D)
         copy_cols(sa.view(B, (hor + 1) * D), 0, x, 2 * D, (hor + 1) * D)
         add_rowvec_(x, p["model.x_pos_embed"])
-        add_rowvec_(lang_c.view(B, Ll * D), p["model.lang_cond_pos_embed"])
-        add_rowvec_(img_c.view(B, Li * D), p["model.img_cond_pos_embed"])
+        add_rowvec_(lang_c.view(B, -1), p["model.lang_cond_pos_embed"])
+        add_rowvec_(img_c.view(B, -1), p["model.img_cond_pos_embed"])
         x = x.view(B * N, D)
-        conds = ((lang_c, Ll, kmask), (img_c, Li, None))
-
-        blocks = []
+        tape["conds"] = ((lang_c, inp["kmask"]), (img_c, None))        # the blocks attend to the language (masked) and the image in turn
         for i in range(self.depth):
-            b = f"model.blocks.{i}"
-            c, Lc, km = conds[i % 2]
-            tb = {"x0": x}
-            # self-attention (timm Attention with q / k RmsNorm)
-            h1 = self._norm(f"{b}.norm1", x)
-            qkv = self._linear(f"{b}.attn.qkv", h1)
-            tb["h1"], tb["qkv_raw"] = h1, qkv.clone()
-            ops.headnorm_(qkv[:, :D], Hh, p[f"{b}.attn.q_norm.weight"], 1e-6, mode, tok_stride=3 * D, tokens=B * N)
-            ops.headnorm_(qkv[:, D:2 * D], Hh, p[f"{b}.attn.k_norm.weight"], 1e-6, mode, tok_stride=3 * D, tokens=B * N)
-            o = ops.attention(self._heads4(qkv, B, N, 0, 3 * D), self._heads4(qkv, B, N, D, 3 * D), self._heads4(qkv, B, N, 2 * D, 3 * D)).view(B * N, D)
-            tb["qkv"], tb["o1"] = qkv, o
-            x = self._linear(f"{b}.attn.proj", o, residual=x)
-            tb["x1"] = x
-            # cross-attention (blocks.py:102-138)
-            h2 = self._norm(f"{b}.norm2", x)
-            q = self._linear(f"{b}.cross_attn.q", h2)
-            kv = self._linear(f"{b}.cross_attn.kv", c)
-            tb["h2"], tb["q_raw"], tb["k_raw"] = h2, q.clone(), kv[:, :D].clone()
-            ops.headnorm_(q, Hh, p[f"{b}.cross_attn.q_norm.weight"], 1e-6, mode, tok_stride=D, tokens=B * N)
-            ops.headnorm_(kv[:, :D], Hh, p[f"{b}.cross_attn.k_norm.weight"], 1e-6, mode, tok_stride=2 * D, tokens=B * Lc)
-            o = ops.attention(self._heads4(q, B, N, 0, D), self._heads4(kv, B, Lc, 0, 2 * D), self._heads4(kv, B, Lc, D, 2 * D), kmask=km).view(B * N, D)
-            tb["q"], tb["kv"], tb["o2"] = q, kv, o
-            x = self._linear(f"{b}.cross_attn.proj", o, residual=x)
-            tb["x2"] = x
-            # FFN (timm Mlp, tanh-GELU)
-            h3 = self._norm(f"{b}.norm3", x)
-            a = self._linear(f"{b}.ffn.fc1", h3)
-            gl = act(a, gelu)
-            x = self._linear(f"{b}.ffn.fc2", gl, residual=x)
-            tb["h3"], tb["a"], tb["gl"] = h3, a, gl
-            blocks.append(tb)
+            x, tb = self._block_fwd(i, x, *tape["conds"][i % 2])
+            tape["blocks"].append(tb)
+        tape["x"] = x
+        tape["hf"] = self._norm("model.final_layer.norm_final", x)
+        tape["af"] = self._linear("model.final_layer.ffn_final.fc1", tape["hf"])
+        tape["gf"] = act(tape["af"], gelu)
+        tape["out"] = self._linear("model.final_layer.ffn_final.fc2", tape["gf"])      # [B*N, A]
+        return tape
 
-        fl = "model.final_layer"
-        hf = self._norm(f"{fl}.norm_final", x)
-        af = self._linear(f"{fl}.ffn_final.fc1", hf)
-        gf = act(af, gelu)
-        out = self._linear(f"{fl}.ffn_final.fc2", gf)                                 # [B*N, A]
-        pred = _cols(out.view(B, N * A), 3 * A, hor * A)                               # x[:, -horizon:]
-        target = (act_gt if self.prediction_type == "sample" else noise).view(B, hor * A)
-        loss, dpred = mse_loss(pred, target, None if self.scaler is None else self.scaler.scale)      # fp16: d pred carries the loss scale
-        self.last_loss = loss.reshape(())
-        self.last_pred = pred.view(B, hor, A)
-        if not backward:
-            return self.last_loss
-
-        # ---------------- backward
-        g = self.g
-        dout = torch.zeros(B, N * A, dtype=adt, device=dev)
+    def _backward(self, tape: dict, dpred: torch.Tensor) -> None:
+        """d loss / d pred back through the final layer, the blocks (their tape entries are dropped as they are read), the token assembly,
+        the position embeddings, the embedders and the adaptors: leaves every gradient in `self.g`."""
+        p, g, D, hor, A, gelu = self.p, self.g, self.hidden, self.horizon, self.action_dim, L.ACT_GELU_TANH
+        B, N, fl = tape["B"], hor + 3, "model.final_layer"
+        dout = torch.zeros(B, N * A, dtype=self.adt, device=self.device)
         copy_cols(dpred, 0, dout, 3 * A, hor * A)
-        d = self._linear_bwd(f"{fl}.ffn_final.fc2", gf, dout.view(B * N, A))
-        d = self._linear_bwd(f"{fl}.ffn_final.fc1", hf, act(af, gelu, d))
-        d = self._norm_bwd(f"{fl}.norm_final", x, d)                                   # d loss / d x after the last block
+        d = self._linear_bwd(f"{fl}.ffn_final.fc2", tape["gf"], dout.view(B * N, A))
+        d = self._linear_bwd(f"{fl}.ffn_final.fc1", tape["hf"], act(tape["af"], gelu, d))
+        d = self._norm_bwd(f"{fl}.norm_final", tape["x"], d)                           # d loss / d x after the last block
         dconds = [None, None]
         for i in range(self.depth - 1, -1, -1):
-            b, tb = f"model.blocks.{i}", blocks[i]
-            c, Lc, km = conds[i % 2]
-            # FFN
-            dg = self._linear_bwd(f"{b}.ffn.fc2", tb["gl"], d)
-            dh = self._linear_bwd(f"{b}.ffn.fc1", tb["h3"], act(tb["a"], gelu, dg))
-            d = add_(self._norm_bwd(f"{b}.norm3", tb["x2"], dh), d)
-            # cross-attention
-            do = self._linear_bwd(f"{b}.cross_attn.proj", tb["o2"], d)
-            dq, dkv = new(B * N, D), new(B * Lc, 2 * D)
-            attention_bwd(self._heads4(tb["q"], B, N, 0, D), self._heads4(tb["kv"], B, Lc, 0, 2 * D), self._heads4(tb["kv"], B, Lc, D, 2 * D),
-                          self._heads4(do, B, N, 0, D), self._heads4(dq, B, N, 0, D), self._heads4(dkv, B, Lc, 0, 2 * D), self._heads4(dkv, B, Lc, D, 2 * D),
-                          kmask=km, kernel=self.attention_backward)
-            g[f"{b}.cross_attn.q_norm.weight"] = headnorm_bwd_(tb["q_raw"], dq, Hh, p[f"{b}.cross_attn.q_norm.weight"], 1e-6, mode)
-            g[f"{b}.cross_attn.k_norm.weight"] = headnorm_bwd_(tb["k_raw"], dkv[:, :D], Hh, p[f"{b}.cross_attn.k_norm.weight"], 1e-6, mode)
-            dc = self._linear_bwd(f"{b}.cross_attn.kv", c, dkv)
+            d, dc = self._block_bwd(i, tape["blocks"].pop(), d, *tape["conds"][i % 2])
             dconds[i % 2] = dc if dconds[i % 2] is None else add_(dconds[i % 2], dc)
-            dh = self._linear_bwd(f"{b}.cross_attn.q", tb["h2"], dq)
-            d = add_(self._norm_bwd(f"{b}.norm2", tb["x1"], dh), d)
-            # self-attention
-            do = self._linear_bwd(f"{b}.attn.proj", tb["o1"], d)
-            dqkv, qkv = new(B * N, 3 * D), tb["qkv"]
-            attention_bwd(self._heads4(qkv, B, N, 0, 3 * D), self._heads4(qkv, B, N, D, 3 * D), self._heads4(qkv, B, N, 2 * D, 3 * D),
-                          self._heads4(do, B, N, 0, D), self._heads4(dqkv, B, N, 0, 3 * D), self._heads4(dqkv, B, N, D, 3 * D),
-                          self._heads4(dqkv, B, N, 2 * D, 3 * D), kernel=self.attention_backward)
-            raw = tb["qkv_raw"]
-            g[f"{b}.attn.q_norm.weight"] = headnorm_bwd_(raw[:, :D], dqkv[:, :D], Hh, p[f"{b}.attn.q_norm.weight"], 1e-6, mode)
-            g[f"{b}.attn.k_norm.weight"] = headnorm_bwd_(raw[:, D:2 * D], dqkv[:, D:2 * D], Hh, p[f"{b}.attn.k_norm.weight"], 1e-6, mode)
-            dh = self._linear_bwd(f"{b}.attn.qkv", tb["h1"], dqkv)
-            d = add_(self._norm_bwd(f"{b}.norm1", tb["x0"], dh), d)
         # token assembly, position embeddings, embedders, adaptors
         dx = d.view(B, N * D)
         g["model.x_pos_embed"] = colsum(dx).view(1, N, D)
-        self._mlp_bwd(["model.t_embedder.mlp.0", "model.t_embedder.mlp.2"], tp_t, _cols(dx, 0, D), L.ACT_SILU)
-        self._mlp_bwd(["model.freq_embedder.mlp.0", "model.freq_embedder.mlp.2"], tp_f, _cols(dx, D, D), L.ACT_SILU)
-        self._mlp_bwd(self.adaptors["state_adaptor"], tp_state, _cols(dx, 2 * D, (hor + 1) * D).view(B * (hor + 1), D), gelu)
-        for name, dc, Lc, tp_, key in (("lang_adaptor", dconds[0], Ll, tp_lang, "model.lang_cond_pos_embed"),
-                                       ("img_adaptor", dconds[1], Li, tp_img, "model.img_cond_pos_embed")):
-            gp = torch.zeros_like(p[key])
+        self._mlp_bwd(["model.t_embedder.mlp.0", "model.t_embedder.mlp.2"], tape["t_embedder"], _cols(dx, 0, D), L.ACT_SILU)
+        self._mlp_bwd(["model.freq_embedder.mlp.0", "model.freq_embedder.mlp.2"], tape["freq_embedder"], _cols(dx, D, D), L.ACT_SILU)
+        self._mlp_bwd(self.adaptors["state_adaptor"], tape["state_adaptor"], _cols(dx, 2 * D, (hor + 1) * D).view(B * (hor + 1), D), gelu)
+        for name, dc, key in (("lang_adaptor", dconds[0], "model.lang_cond_pos_embed"), ("img_adaptor", dconds[1], "model.img_cond_pos_embed")):
+            gp = g[key] = torch.zeros_like(p[key])
             if dc is None:                                        # depth 1: no block attends to the image tokens
-                for k in self.p:
-                    if k.startswith(name + "."):
-                        g[k] = torch.zeros_like(p[k])
+                g.update({k: torch.zeros_like(v) for k, v in p.items() if k.startswith(name + ".")})
             else:
-                colsum(dc.view(B, Lc * D), gp)
-                self._mlp_bwd(self.adaptors[name], tp_, dc, gelu)
-            g[key] = gp
+                colsum(dc.view(B, -1), gp)
+                self._mlp_bwd(self.adaptors[name], tape[name], dc, gelu)
+
+    def get_loss(self, lang_tokens, lang_attn_mask, img_tokens, state_tokens, action_gt, action_mask, ctrl_freqs, *, noise, timesteps,
+                 backward: bool = True) -> torch.Tensor:
+        """compute_loss's arguments (rdt_runner.py:168-182) plus the two random draws it makes: noise [B, horizon, action_dim] and timesteps [B]
+        (integers in [0, num_train_timesteps)).  -> the loss as a 0-d fp32 device tensor; with backward=True the gradients are left in `self.g`."""
+        inp = self._inputs(lang_tokens, lang_attn_mask, img_tokens, state_tokens, action_gt, action_mask, ctrl_freqs, noise, timesteps)
+        tape = self._forward(inp)
+        B, hor, A = inp["B"], self.horizon, self.action_dim
+        pred = _cols(tape.pop("out").view(B, -1), 3 * A, hor * A)                      # x[:, -horizon:]
+        target = (inp["act_gt"] if self.prediction_type == "sample" else inp["noise"]).view(B, hor * A)
+        loss, dpred = mse_loss(pred, target, None if self.scaler is None else self.scaler.scale)      # fp16: d pred carries the loss scale
+        self.last_loss, self.last_pred = loss.reshape(()), pred.view(B, hor, A)
+        if backward:
+            self._backward(tape, dpred)
         return self.last_loss
 
     # ---- optimizer
@@ -863,29 +869,44 @@ class RdtTrainer:
             D.all_reduce_sum_(buf[off:off + step], self.group)
 
     def optimizer_step(self, hyper: Optional[torch.Tensor] = None):
-        """clip_grad_norm_(max_grad_norm) -> AdamW -> EMA (train.py:440-448), three launches over one table; no host read."""
+        """clip_grad_norm_(max_grad_norm) -> AdamW -> EMA (train.py:440-448), three launches over one table; fp32 / bf16: no host read.
+        fp16: GradScaler.unscale_ with the clip -> scaler.step(optimizer) -> scaler.update -> scheduler -> EMAModel.step; a non-finite gradient
+        skips the step, leaving parameters, moments, step_count and lr where they were (AcceleratedScheduler does not step after a skipped one)."""
         if hyper is not None:
             raise NotImplementedError("RdtTrainer: hipGraph capture of the step is not built")
         if self._accumulates and self.micro_step != self.k:
             raise RuntimeError(f"optimizer_step needs a full accumulation window ({self.micro_step} of {self.k} micro-batches accumulated)")
         tab, n, chunks = self._table()
-        if self.scaler is not None:
-            return self._optimizer_step_scaled(tab, n, chunks)
+        found_inf = self._prepare_grads(tab, n, chunks)
         self.ema_updates += 1
-        self._take_step(tab, n, chunks, clip=True)
-        self.micro_step, self.sync_gradients = 0, True
-        self.shadow_version += 1
+        (self._ema_alone if found_inf else self._take_step)(tab, n, chunks)      # a skipped step still moves the shadows: train.py:448 is unconditional
+        if self.scaler is not None:
+            self.scaler.update(found_inf)
+        self.last_step_skipped = found_inf
+        self._close(sync_gradients=True)
 
-    def _take_step(self, tab, n, chunks, clip: bool) -> None:
-        """The scheduler's lr, then AdamW + EMA over the table (the EMA update counted by the caller) and the 16-bit copies of the new weights.
-        clip: clip the gradients first (the fp16 path has unscaled and clipped them before its host read)."""
+    def _prepare_grads(self, tab, n, chunks) -> bool:
+        """Clip the table's gradients -> whether one is non-finite.  fp32 / bf16: nothing is checked or read back, the answer is False.
+        fp16: one launch group unscales, checks and clips; the host reads (norm, coefficient, flag, loss) once, as GradScaler.step synchronises."""
+        args = L.ptr(self._chunk_part), L.ptr(self._norm_coef)
+        if self.scaler is None:
+            L.check(L.lib().vt_grad_clip_multi(L.ptr(tab), n, chunks, self.max_grad_norm, *args, _sp(self.device)), "vt_grad_clip_multi")
+            return False
+        L.check(L.lib().vt_grad_unscale_clip_multi(L.ptr(tab), n, chunks, self.max_grad_norm, inv_scale(self.scaler.scale), *args,
+                                                   C.c_void_p(self._norm_coef.data_ptr() + 8), _sp(self.device)), "vt_grad_unscale_clip_multi")
+        if self.last_loss is not None:
+            self._norm_coef[3:4].copy_(self.last_loss.reshape(1))
+        host = self._norm_coef.cpu()
+        found_inf = int(host.view(torch.int32)[2]) != 0
+        if found_inf and self.last_loss is not None and not math.isfinite(float(host[3])):
+            self.scaler.skipped_nonfinite_loss += 1               # the forward overflowed: no smaller scale repairs that
+        return found_inf
+
+    def _take_step(self, tab, n, chunks) -> None:
+        """The scheduler's lr, then AdamW + EMA over the table (the EMA update counted by the caller) and the 16-bit copies of the new weights."""
         self.lr = lr_at(self.base_lr, self.lr_scheduler, self.step_count, self.lr_warmup_steps * self.k)      # train.py:302 scales the warm-up by k
         self.step_count += 1
-        hy = self._hyper(self.step_count)
-        if clip:
-            L.check(L.lib().vt_grad_clip_multi(L.ptr(tab), n, chunks, self.max_grad_norm, L.ptr(self._chunk_part), L.ptr(self._norm_coef), _sp(self.device)),
-                    "vt_grad_clip_multi")
-        self.opt_state.step(tab, n, chunks, hy, self.betas, self.eps, self.wd)
+        self.opt_state.step(tab, n, chunks, self._hyper(self.step_count), self.betas, self.eps, self.wd)
         self._refresh16()
         self.weights_version += 1
 
@@ -893,29 +914,9 @@ class RdtTrainer:
         """EMAModel.step without an optimizer step (the EMA update counted by the caller): the shadows move toward the unchanged parameters."""
         L.check(L.lib().vt_ema_multi(L.ptr(tab), n, chunks, L.ptr(self._hyper(max(1, self.step_count))), _sp(self.device)), "vt_ema_multi")
 
-    def _optimizer_step_scaled(self, tab, n, chunks) -> None:
-        """fp16: accelerator.clip_grad_norm_ (GradScaler.unscale_ first) -> scaler.step(optimizer) -> scaler.update -> scheduler -> EMAModel.step.
-        One launch group unscales, checks and clips; the host reads (norm, coefficient, flag, loss) once, as GradScaler.step synchronises,
-        and takes the step or skips it: a skip runs the EMA update alone (train.py:448 is unconditional) and leaves parameters, moments,
-        step_count and lr where they were (AcceleratedScheduler does not step after a skipped optimizer step)."""
-        sc = self.scaler
-        L.check(L.lib().vt_grad_unscale_clip_multi(L.ptr(tab), n, chunks, self.max_grad_norm, inv_scale(sc.scale), L.ptr(self._chunk_part),
-                                                   L.ptr(self._norm_coef), C.c_void_p(self._norm_coef.data_ptr() + 8), _sp(self.device)),
-                "vt_grad_unscale_clip_multi")
-        if self.last_loss is not None:
-            self._norm_coef[3:4].copy_(self.last_loss.reshape(1))
-        host = self._norm_coef.cpu()                              # the mode's one host read
-        found_inf = int(host.view(torch.int32)[2]) != 0
-        self.ema_updates += 1
-        if found_inf:
-            self._ema_alone(tab, n, chunks)
-            if self.last_loss is not None and not math.isfinite(float(host[3])):
-                sc.skipped_nonfinite_loss += 1                    # the forward overflowed: no smaller scale repairs that
-        else:
-            self._take_step(tab, n, chunks, clip=False)
-        sc.update(found_inf)
-        self.last_step_skipped = found_inf
-        self.micro_step, self.sync_gradients = 0, True
+    def _close(self, sync_gradients: bool) -> None:
+        """The end of a micro-batch, after its EMA update; sync_gradients: it took (or skipped) the optimizer step, which closes the window."""
+        self.micro_step, self.sync_gradients = 0 if sync_gradients else self.micro_step, sync_gradients
         self.shadow_version += 1
 
     def moments(self, name: str):
@@ -960,8 +961,7 @@ class RdtTrainer:
         tab, n, chunks = self._table()
         self.ema_updates += 1
         self._ema_alone(tab, n, chunks)
-        self.sync_gradients = False
-        self.shadow_version += 1
+        self._close(sync_gradients=False)
 
     def train_step(self, lang_tokens, lang_attn_mask, img_tokens, state_tokens, action_gt, action_mask, ctrl_freqs, *, noise=None, timesteps=None):
         B = torch.as_tensor(action_gt).shape[0]
@@ -970,14 +970,12 @@ class RdtTrainer:
         if timesteps is None:
             timesteps = torch.randint(0, self.num_train_timesteps, (B,), device=self.device)
         loss = self.get_loss(lang_tokens, lang_attn_mask, img_tokens, state_tokens, action_gt, action_mask, ctrl_freqs, noise=noise, timesteps=timesteps)
-        if not self._accumulates:
-            self.optimizer_step()
-            return loss
-        self.accumulate()
-        if self.micro_step == self.k:
-            self.optimizer_step()
+        if self._accumulates:
+            self.accumulate()
+        if self._accumulates and self.micro_step < self.k:
+            self.ema_step()                                       # the window stays open
         else:
-            self.ema_step()
+            self.optimizer_step()
         return loss
 
     # ---- state
