@@ -272,20 +272,26 @@ def test_attention_head_dim_80(dev, mode, Nq, Nk):
 
 
 @pytest.mark.parametrize("mode", ["bf16", "f16"])
-@pytest.mark.parametrize("N,hd,B,H", [(729, 80, 3, 4), (257, 64, 5, 3), (730, 64, 2, 3), (1370, 64, 1, 6), (128, 64, 2, 2), (200, 80, 2, 2)])
-def test_grouped_query_attention_is_bit_identical_to_one_group_per_wave(dev, mode, N, hd, B, H):
+@pytest.mark.parametrize("case", [(729, 80, 3, 4), (257, 64, 5, 3), (730, 64, 2, 3), (1370, 64, 1, 6), (128, 64, 2, 2), (200, 80, 2, 2),
+                                  # (Nq, hd, B, H, Nk): one ragged key tile (the second stage of the prologue is not issued), one whole tile (the clamped
+                                  # staging branch never runs), exactly three whole tiles (every ring slot once, nothing ragged)
+                                  (130, 64, 2, 2, 40), (130, 64, 2, 2, 64), (130, 64, 2, 2, 192)], ids=lambda c: "-".join(map(str, c)))
+def test_grouped_query_attention_is_bit_identical_to_one_group_per_wave(dev, mode, case):
     """attn16g_kernel (a block walks the key tiles ONCE for G groups of 16 query rows per wave: one block per (image, head) for SigLIP's 729 and
     DINOv2's 257 tokens) against attn16u_kernel (one group per wave, six / three blocks per (image, head)): per query row the two kernels do the same
     operations in the same order, so the outputs must be BIT-identical — for G chosen by the launcher and for G pinned to 3 and 6 (partly filled
-    last blocks, groups of padding rows skipped, a ragged last key tile) — and equal to a torch fp32 reference within the 16-bit tolerance."""
+    last blocks, groups of padding rows skipped, a ragged last key tile) — and equal to a torch fp32 reference within the 16-bit tolerance.
+    A case is (N, hd, B, H) for self-attention or (Nq, hd, B, H, Nk) with a key count of its own."""
     from vlatouch import ops, _lib as L
     lib = L.lib()
     dt = {"bf16": torch.bfloat16, "f16": torch.float16}[mode]
+    N, hd, B, H = case[:4]
+    Nk = case[4] if len(case) > 4 else N
     real = 72 if hd == 80 else hd
-    qkv = rnd((B, N, 3, H, hd), 11, dev, dt)
+    qkv = rnd((B, max(N, Nk), 3, H, hd), 11, dev, dt)
     if hd == 80:
         qkv[..., 72:] = 0
-    q, k, v = qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2]
+    q, k, v = qkv[:, :N, 0], qkv[:, :Nk, 1], qkv[:, :Nk, 2]
     outs = {}
     try:
         for knob in (0, 1, 3, 6):

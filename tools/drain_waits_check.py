@@ -1,11 +1,14 @@
-"""Digest of the outputs of the hand-scheduled GEMM tiles (gemm_pt / gemm_pp256d / gemm_pw / gemm_pws) on a set of shapes that cover every epilogue kind, ragged
-edges and the smallest K — printed as one sha256 per case.  tools/drain_waits_check.sh runs it against the product library and against a debug build whose counted
+"""Digest of the outputs of the kernels with hand-counted waits — the hand-scheduled GEMM tiles (gemm_pt / gemm_pp256d / gemm_pw / gemm_pws) on a set of shapes
+that cover every epilogue kind, ragged edges and the smallest K; the DMA-staged self-attention (attn16u / attn16g), the cached cross-attention ring and the
+fp32 ring GEMM on the smallest test shapes that keep their rings full — printed as one sha256 per case.  tools/drain_waits_check.sh runs it against the product library and against a debug build whose counted
 `s_waitcnt vmcnt(N)` are all `vmcnt(0)`: a wait count that is too LARGE (a race the tests happen not to hit) shows up as a differing digest."""
 import hashlib, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "vla-touch_amd")]
+import ctypes as C
 import torch
 from vlatouch import ops, _lib as L
+from tests import cases
 dev = torch.device("cuda:0")
 L.lib()
 
@@ -58,3 +61,50 @@ for dt in (torch.bfloat16, torch.float16):
         wp = ops.pack_w32(w)
         for rep in range(2):
             digest(f"pws {tag} {M} #{rep}", ops.gemm(a, w, b, wp=wp, out_dtype=torch.float32))
+
+# DMA-staged self-attention: (N, hd) of test_grouped_query_attention_is_bit_identical_to_one_group_per_wave / test_attention — ragged last key tile, a whole
+# number of tiles + 1, 96-wide heads (attn16u only); the first two under every grouping policy (vt_tune(9, .): attn16u everywhere, G = 3, G = 6)
+for dt in (torch.bfloat16, torch.float16):
+    tag = "bf16" if dt == torch.bfloat16 else "f16"
+    for (N, hd, knobs) in [(200, 80, (0, 3, 6)), (257, 64, (0, 3, 6)), (130, 96, (1,))]:
+        qkv = rnd((2, N, 3, 2, hd), 11, dt)
+        q, k, v = qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2]
+        try:
+            for knob in knobs:
+                L.check(L.lib().vt_tune(9, knob), "tune")
+                for rep in range(2):
+                    digest(f"attn16 {tag} N{N} hd{hd} knob{knob} #{rep}", ops.attention(q, k, v, scale=hd ** -0.5))
+        finally:
+            L.lib().vt_tune(9, 1)
+
+# cached cross-attention ring, online and fixed-maximum form: (B, Nk, Nq, H) = (3, 2100, 67, 3) of tests/test_gpu_attn_kvt.py, its smallest shape whose
+# samples are longer than the ring (33 key tiles each: every arm of the wait ladder runs)
+for dt in (torch.bfloat16, torch.float16):
+    tag = "bf16" if dt == torch.bfloat16 else "f16"
+    B, Nk, Nq, H = 3, 2100, 67, 3
+    T = (B * Nk + 63) // 64 + 1
+    q, k, v = rnd((B, Nq, H * 64), 1, dt, 0.3), rnd((B * Nk, H, 64), 2, dt, 0.3), rnd((B * Nk, H, 64), 3, dt)
+    kv = cases.kv_tile_stream(k, v, T)
+    out = torch.zeros(B, Nq, H * 64, dtype=dt, device=dev)
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    p = L.AttnKvtParams()
+    p.Q, p.KV, p.O = q.data_ptr(), kv.data_ptr(), out.data_ptr()
+    p.q_bs, p.q_rs, p.o_bs, p.o_rs = Nq * H * 64, H * 64, Nq * H * 64, H * 64
+    p.B, p.H, p.Nq, p.Nk, p.T = B, H, Nq, Nk, T
+    p.scale, p.dtype, p.range_flag = 0.125, L.dt_code(dt), flag.data_ptr()
+    for form, bound in (("online", 0.0), ("fixed", 8.0)):       # |q.k| * scale stays far below 8 at these operand scales
+        p.fixed_max = bound
+        for rep in range(2):
+            out.zero_()
+            L.check(L.lib().vt_attention_kvt(C.byref(p), L.stream_ptr(dev)), "vt_attention_kvt")
+            digest(f"kvt {tag} {form} B{B} Nk{Nk} Nq{Nq} #{rep}", out)
+
+# fp32 ring GEMM, exact and split-bf16: (512, 512, 2560) of test_fp32_ring_gemm_edges, unsplit (80 k-tiles through the ring of 4; split-bf16 wants K % 64 == 0)
+M, N, K = 512, 512, 2560
+a, w, b = rnd((M, K), 1), rnd((N, K), 2, torch.float32, K ** -0.5), rnd((N,), 3)
+for name, code in (("f32", None), ("x3", L.F32X3)):
+    out = torch.zeros(M, N, device=dev)
+    for rep in range(2):
+        out.zero_()
+        ops.gemm_block(a, w, out, b, route="F32R", w_code=code)
+        digest(f"f32r {name} {M}x{N}x{K} #{rep}", out)

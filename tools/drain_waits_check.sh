@@ -1,6 +1,7 @@
 #!/bin/bash
-# a debug build of the library whose hand-counted `s_waitcnt vmcnt(N)` (gemm_pt / gemm_pp256d / gemm_pw / gemm_pws) all drain the queue, compared
-# bit for bit with the product build on tools/drain_waits_check.py's cases (each run twice).   gpurun -- tools/drain_waits_check.sh
+# a debug build of the library whose hand-counted `s_waitcnt vmcnt(N)` all drain the queue — every one goes through vt_wait_vm (vt_common.h):
+# gemm_pt / gemm_pp256d / gemm_pw / gemm_pws, the DMA-staged self-attention (attn16u / attn16g), the cached cross-attention ring and the fp32 ring GEMM —
+# compared bit for bit with the product build on tools/drain_waits_check.py's cases (each run twice).  Needs the GPU.
 cd $GRAFT_REPO_ROOT/vla-touch_amd/csrc
 rm -rf /tmp/build_drain; mkdir -p /tmp/build_drain
 for f in *.hip; do e=""; [ $f = vt_uconv.hip ] && e="-Xclang -target-feature -Xclang -packed-fp32-ops"; /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -fno-gpu-rdc -DVLATOUCH_DRAIN_WAITS $e -c $f -o /tmp/build_drain/${f%.hip}.o 2>/dev/null & done; wait

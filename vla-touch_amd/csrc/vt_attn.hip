@@ -214,9 +214,6 @@ __global__ __launch_bounds__(512) void attn_kernel(const VtAttnParams p) {
   }
 }
 
-typedef __attribute__((address_space(3))) void lds_void_a;
-typedef const __attribute__((address_space(1))) void glb_void_a;
-typedef __attribute__((ext_vector_type(4))) short short4_t;
 
 // 16-deep tail step of a head dimension that is not a multiple of 32 (SigLIP's 72-wide heads run padded to 80 = 2 x 32 + 16): v_mfma_f32_16x16x16,
 // a lane (row l15, group g) holds the 4 elements k = g*4 .. g*4+3 of both operands
@@ -244,19 +241,20 @@ template <> __device__ __forceinline__ void mma16_k16<half_t>(float4_t& acc, con
 //     that a block pays one memory round trip before its first MFMA, not two.
 // No key mask here (masked calls keep attn_kernel).  Keys past Nk in the last tile are clamped loads, masked in the softmax.
 
-// max / sum over the four 16-lane rows of a wave (lanes that differ in bits 4 and 5), result in every lane, on v_permlane16_swap / v_permlane32_swap
-// (VALU) instead of two __shfl_xor = ds_bpermute round trips (round 5: the same change took the cached cross-attention's online softmax from 114 to 104 us)
-template <bool MAX> __device__ __forceinline__ float rows4_reduce(float v) {
-  const unsigned u = __builtin_bit_cast(unsigned, v);
-  const auto a = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-  const float a0 = __builtin_bit_cast(float, (unsigned)a[0]), a1 = __builtin_bit_cast(float, (unsigned)a[1]);
-  const float w = MAX ? fmaxf(a0, a1) : a0 + a1;
-  const unsigned x = __builtin_bit_cast(unsigned, w);
-  const auto b = __builtin_amdgcn_permlane32_swap(x, x, false, false);
-  const float b0 = __builtin_bit_cast(float, (unsigned)b[0]), b1 = __builtin_bit_cast(float, (unsigned)b[1]);
-  return MAX ? fmaxf(b0, b1) : b0 + b1;
+// The wait ladder of both attn16 kernels: this wave's pieces of the oldest stage in flight have landed; a younger stage (my_pieces operations of
+// this wave) may stay in flight.  The kernels call it through a [&] lambda of their own: called directly it changes attn16g_kernel's code.
+// (The two kernels still state the tile — constants, DMA plan, per-tile arithmetic — once each: moved into shared functions or a shared struct, every
+// one of their code objects changed, and the 80-wide attn16u_kernel measured slower than its parent; profiles/attn16_refactor.json.)
+__device__ __forceinline__ void attn16_wait_own(const int my_pieces, const bool younger_in_flight) {
+  if (!younger_in_flight) vt_wait_vm<0>();
+  else if (my_pieces == 1) vt_wait_vm<1>();
+  else if (my_pieces == 2) vt_wait_vm<2>();
+  else if (my_pieces == 3) vt_wait_vm<3>();
+  else if (my_pieces == 4) vt_wait_vm<4>();
+  else if (my_pieces == 5) vt_wait_vm<5>();
+  else if (my_pieces == 6) vt_wait_vm<6>();
+  else vt_wait_vm<0>();
 }
-template <int I> struct IC { static constexpr int value = I; };
 
 template <typename T, int HD>
 __global__ __launch_bounds__(512) void attn16u_kernel(const VtAttnParams p) {
@@ -320,7 +318,7 @@ __global__ __launch_bounds__(512) void attn16u_kernel(const VtAttnParams p) {
       for (int n = 0; n < MAXP; ++n) {
         const int i = wave + n * nw;
         if (i < PIECES)
-          __builtin_amdgcn_global_load_lds((glb_void_a*)((i >= PT ? vb : kb) + poff[n]), (lds_void_a*)piece_dst(slot, i), 16, 0, 0);
+          __builtin_amdgcn_global_load_lds((glb_void*)((i >= PT ? vb : kb) + poff[n]), (lds_void*)piece_dst(slot, i), 16, 0, 0);
       }
     } else {                                          // last tile: rows clamped to the last key (masked in the softmax)
       for (int i = wave; i < PIECES; i += nw) {
@@ -331,25 +329,16 @@ __global__ __launch_bounds__(512) void attn16u_kernel(const VtAttnParams p) {
         if (TP == 0 || j < 8) {
           const int r = j * 8 + (lane >> 3);
           const int c = (lane & 7) ^ ((r >> 1) & 7);
-          __builtin_amdgcn_global_load_lds((glb_void_a*)(base + (long)min(key0 + r, p.Nk - 1) * rs + c * 8), (lds_void_a*)piece_dst(slot, i), 16, 0, 0);
+          __builtin_amdgcn_global_load_lds((glb_void*)(base + (long)min(key0 + r, p.Nk - 1) * rs + c * 8), (lds_void*)piece_dst(slot, i), 16, 0, 0);
         } else {
           const int r = (j - 8) * (64 / CPR) + lane / CPR;
           const int c = lane % CPR;
-          __builtin_amdgcn_global_load_lds((glb_void_a*)(base + (long)min(key0 + r, p.Nk - 1) * rs + 64 + c * 8), (lds_void_a*)piece_dst(slot, i), 16, 0, 0);
+          __builtin_amdgcn_global_load_lds((glb_void*)(base + (long)min(key0 + r, p.Nk - 1) * rs + 64 + c * 8), (lds_void*)piece_dst(slot, i), 16, 0, 0);
         }
       }
     }
   };
-  auto wait_own = [&](const bool younger_in_flight) __attribute__((always_inline)) {
-    if (!younger_in_flight) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if (my_pieces == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-    else if (my_pieces == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    else if (my_pieces == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-    else if (my_pieces == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else if (my_pieces == 5) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-    else if (my_pieces == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  };
+  auto wait_own = [&](const bool younger_in_flight) __attribute__((always_inline)) { attn16_wait_own(my_pieces, younger_in_flight); };
 
   // first two stages, THEN the Q fragments; everything retired together (an ordinary load pending beside LDS-DMA makes hipcc drain the whole
   // queue at its first use anyway)
@@ -360,7 +349,7 @@ __global__ __launch_bounds__(512) void attn16u_kernel(const VtAttnParams p) {
   for (int ks = 0; ks < NKS; ++ks) QLoad<T>::ld(qf[ks], Q + (long)q * p.q_rs + ks * 32 + g * 8, q < p.Nq);
   short4_t q16 = {0, 0, 0, 0};
   if constexpr (TAIL16) { if (q < p.Nq) q16 = *reinterpret_cast<const short4_t*>(Q + (long)q * p.q_rs + NKS * 32 + g * 4); }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  vt_wait_vm<0>();
 #pragma unroll
   for (int ks = 0; ks < NKS; ++ks) asm volatile("" : "+v"(qf[ks].v));
   asm volatile("" : "+v"(q16));
@@ -439,7 +428,7 @@ __global__ __launch_bounds__(512) void attn16u_kernel(const VtAttnParams p) {
     float mx = sv[0];
 #pragma unroll
     for (int i = 1; i < 16; ++i) mx = fmaxf(mx, sv[i]);
-    mx = rows4_reduce<true>(mx);
+    mx = rows4_max(mx);
     const float m_new = fmaxf(m_run, mx);
     if (__any(m_new != m_run)) {
       const float alpha = (m_run == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f((m_run - m_new) * cscale);
@@ -469,8 +458,7 @@ __global__ __launch_bounds__(512) void attn16u_kernel(const VtAttnParams p) {
         for (int hh = 0; hh < 2; ++hh) {
           const char* a = dt < 4 ? Vs + (kb * 32 + hh * 16) * 128 + voff[dt < 4 ? dt : 0]
                                  : Vs + (kb * 32 + hh * 16) * TW + (dt - 4) * 32 + vtail;
-          const short4_t t = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4_t*)a);
-          vf.v[hh * 4 + 0] = t[0]; vf.v[hh * 4 + 1] = t[1]; vf.v[hh * 4 + 2] = t[2]; vf.v[hh * 4 + 3] = t[3];
+          tr_frag_half(vf, hh, a);
         }
         mma16(o[dt], vf, pf);
       }
@@ -478,15 +466,15 @@ __global__ __launch_bounds__(512) void attn16u_kernel(const VtAttnParams p) {
   };
 
   for (int tile = 0; tile < ntiles; tile += 3) {
-    body(IC<0>{}, tile);
+    body(std::integral_constant<int, 0>{}, tile);
     if (tile + 1 >= ntiles) break;
-    body(IC<1>{}, tile + 1);
+    body(std::integral_constant<int, 1>{}, tile + 1);
     if (tile + 2 >= ntiles) break;
-    body(IC<2>{}, tile + 2);
+    body(std::integral_constant<int, 2>{}, tile + 2);
   }
 
   float l = l_run;
-  l = rows4_reduce<false>(l);
+  l = rows4_sum(l);
   const float inv = 1.0f / l;
   if (q < p.Nq) {
     T* O = reinterpret_cast<T*>(p.O) + (long)b * p.o_bs + (long)q * p.o_rs + h * HD;
@@ -508,10 +496,6 @@ __global__ __launch_bounds__(512) void attn16u_kernel(const VtAttnParams p) {
 // work of group i.  Same tile image, DMA plan, fragment conventions and arithmetic (per row: identical operations in identical order) as
 // attn16u_kernel, so results are bit-identical to it.  Group gi of wave w = rows (gi * nw + w) * 16 .. + 15 of the block; groups that start past Nq
 // are skipped (wave-uniform branch).  The ring slot is a run-time value here (8 address adds per tile, amortised over G groups).
-template <int N, typename F> __device__ __forceinline__ void ag_for(F&& f) {
-  if constexpr (N > 0) { ag_for<N - 1>(f); f(IC<N - 1>{}); }
-}
-
 template <typename T, int HD, int G>
 __global__ __launch_bounds__(512) void attn16g_kernel(const VtAttnParams p) {
   static_assert(sizeof(T) == 2, "16-bit types only");
@@ -571,7 +555,7 @@ __global__ __launch_bounds__(512) void attn16g_kernel(const VtAttnParams p) {
       for (int n = 0; n < MAXP; ++n) {
         const int i = wave + n * nw;
         if (i < PIECES)
-          __builtin_amdgcn_global_load_lds((glb_void_a*)((i >= PT ? vb : kb) + poff[n]), (lds_void_a*)piece_dst(slot, i), 16, 0, 0);
+          __builtin_amdgcn_global_load_lds((glb_void*)((i >= PT ? vb : kb) + poff[n]), (lds_void*)piece_dst(slot, i), 16, 0, 0);
       }
     } else {
       for (int i = wave; i < PIECES; i += nw) {
@@ -582,31 +566,22 @@ __global__ __launch_bounds__(512) void attn16g_kernel(const VtAttnParams p) {
         if (TP == 0 || j < 8) {
           const int r = j * 8 + (lane >> 3);
           const int c = (lane & 7) ^ ((r >> 1) & 7);
-          __builtin_amdgcn_global_load_lds((glb_void_a*)(base + (long)min(key0 + r, p.Nk - 1) * rs + c * 8), (lds_void_a*)piece_dst(slot, i), 16, 0, 0);
+          __builtin_amdgcn_global_load_lds((glb_void*)(base + (long)min(key0 + r, p.Nk - 1) * rs + c * 8), (lds_void*)piece_dst(slot, i), 16, 0, 0);
         } else {
           const int r = (j - 8) * (64 / CPR) + lane / CPR;
           const int c = lane % CPR;
-          __builtin_amdgcn_global_load_lds((glb_void_a*)(base + (long)min(key0 + r, p.Nk - 1) * rs + 64 + c * 8), (lds_void_a*)piece_dst(slot, i), 16, 0, 0);
+          __builtin_amdgcn_global_load_lds((glb_void*)(base + (long)min(key0 + r, p.Nk - 1) * rs + 64 + c * 8), (lds_void*)piece_dst(slot, i), 16, 0, 0);
         }
       }
     }
   };
-  auto wait_own = [&](const bool younger_in_flight) __attribute__((always_inline)) {
-    if (!younger_in_flight) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if (my_pieces == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-    else if (my_pieces == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    else if (my_pieces == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-    else if (my_pieces == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else if (my_pieces == 5) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-    else if (my_pieces == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  };
+  auto wait_own = [&](const bool younger_in_flight) __attribute__((always_inline)) { attn16_wait_own(my_pieces, younger_in_flight); };
 
   stage(0, 0);
   if (ntiles > 1) stage(1, 1);
   Frag<T> qf[G][NKS];
   short4_t q16[G];
-  ag_for<G>([&](auto gc) {
+  static_for<G>([&](auto gc) {
     constexpr int gi = decltype(gc)::value;
     const int q = row_base + gi * nw * 16 + l15;
 #pragma unroll
@@ -614,7 +589,7 @@ __global__ __launch_bounds__(512) void attn16g_kernel(const VtAttnParams p) {
     q16[gi] = (short4_t){0, 0, 0, 0};
     if constexpr (TAIL16) { if (q < p.Nq) q16[gi] = *reinterpret_cast<const short4_t*>(Q + (long)q * p.q_rs + NKS * 32 + g * 4); }
   });
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  vt_wait_vm<0>();
 #pragma unroll
   for (int gi = 0; gi < G; ++gi) {
 #pragma unroll
@@ -637,7 +612,7 @@ __global__ __launch_bounds__(512) void attn16g_kernel(const VtAttnParams p) {
 
   float4_t o[G][NDT];
   float m_run[G], l_run[G];
-  ag_for<G>([&](auto gc) {
+  static_for<G>([&](auto gc) {
     constexpr int gi = decltype(gc)::value;
 #pragma unroll
     for (int i = 0; i < NDT; ++i) o[gi][i] = (float4_t){0.f, 0.f, 0.f, 0.f};
@@ -664,7 +639,7 @@ __global__ __launch_bounds__(512) void attn16g_kernel(const VtAttnParams p) {
     slot = slot == NST - 1 ? 0 : slot + 1;
     const bool ragged = key0 + KT > p.Nk;
 
-    ag_for<G>([&](auto gc) {
+    static_for<G>([&](auto gc) {
       constexpr int gi = decltype(gc)::value;
       if (row_base + gi * nw * 16 >= p.Nq) return;                      // a group of padding rows only (wave-uniform)
       float4_t sacc[4], tacc[4];
@@ -700,7 +675,7 @@ __global__ __launch_bounds__(512) void attn16g_kernel(const VtAttnParams p) {
       float mx = sv[0];
 #pragma unroll
       for (int i = 1; i < 16; ++i) mx = fmaxf(mx, sv[i]);
-      mx = rows4_reduce<true>(mx);
+      mx = rows4_max(mx);
       const float m_new = fmaxf(m_run[gi], mx);
       if (__any(m_new != m_run[gi])) {
         const float alpha = (m_run[gi] == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f((m_run[gi] - m_new) * cscale);
@@ -730,8 +705,7 @@ __global__ __launch_bounds__(512) void attn16g_kernel(const VtAttnParams p) {
           for (int hh = 0; hh < 2; ++hh) {
             const char* a = dt < 4 ? va[dt < 4 ? dt : 0] + (kb * 32 + hh * 16) * 128
                                    : vt_ + (kb * 32 + hh * 16) * TW + (dt - 4) * 32;
-            const short4_t t = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4_t*)a);
-            vf.v[hh * 4 + 0] = t[0]; vf.v[hh * 4 + 1] = t[1]; vf.v[hh * 4 + 2] = t[2]; vf.v[hh * 4 + 3] = t[3];
+            tr_frag_half(vf, hh, a);
           }
           mma16(o[gi][dt], vf, pf);
         }
@@ -739,11 +713,11 @@ __global__ __launch_bounds__(512) void attn16g_kernel(const VtAttnParams p) {
     });
   }
 
-  ag_for<G>([&](auto gc) {
+  static_for<G>([&](auto gc) {
     constexpr int gi = decltype(gc)::value;
     const int q = row_base + gi * nw * 16 + l15;
     float l = l_run[gi];
-    l = rows4_reduce<false>(l);
+    l = rows4_sum(l);
     const float inv = 1.0f / l;
     if (q < p.Nq) {
       T* O = reinterpret_cast<T*>(p.O) + (long)b * p.o_bs + (long)q * p.o_rs + h * HD;

@@ -35,8 +35,6 @@ namespace {
 constexpr int KT = 64;            // keys per tile
 constexpr int RUN_TILES = 4;      // key tiles per workgroup
 constexpr int MAXQ = 128;         // query rows held in LDS
-typedef __attribute__((ext_vector_type(4))) short short4_t;
-typedef __attribute__((address_space(3))) short4_t lds_short4_t;
 
 // stage `rows` rows of 64 bf16 (128 B) from a strided global view into the swizzled LDS image of vt_common.h (lds_frag); rows >= live are zeros
 template <typename T>
@@ -60,17 +58,7 @@ __device__ __forceinline__ unsigned tr_off(int l15, int g, int dt) {
 template <typename T>
 __device__ __forceinline__ void tr_frag(Frag<T>& f, const char* img, int r0, unsigned off) {
 #pragma unroll
-  for (int hh = 0; hh < 2; ++hh) {
-    const short4_t t = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_short4_t*)(img + (r0 + hh * 16) * 128 + off));
-    f.v[hh * 4 + 0] = t[0]; f.v[hh * 4 + 1] = t[1]; f.v[hh * 4 + 2] = t[2]; f.v[hh * 4 + 3] = t[3];
-  }
-}
-// two fp32 -> two T in one word, round-to-nearest-even (fp16: v_cvt_f16_f32 semantics, overflow gives inf)
-typedef __attribute__((ext_vector_type(2))) _Float16 f16x2_t;
-template <typename T> __device__ __forceinline__ uint32_t pk16(float lo, float hi);
-template <> __device__ __forceinline__ uint32_t pk16<bf16_t>(float lo, float hi) { return pk_bf16(lo, hi); }
-template <> __device__ __forceinline__ uint32_t pk16<half_t>(float lo, float hi) {
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector((float2_t){lo, hi}, f16x2_t));
+  for (int hh = 0; hh < 2; ++hh) tr_frag_half(f, hh, img + (r0 + hh * 16) * 128 + off);
 }
 template <typename T>
 __device__ __forceinline__ void pack8(Frag<T>& f, const float4_t lo, const float4_t hi) {

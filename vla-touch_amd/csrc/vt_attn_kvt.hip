@@ -17,28 +17,7 @@
 
 namespace {
 
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void glb_void;
 constexpr int KT = 64;                 // keys per tile
-typedef __attribute__((ext_vector_type(2))) _Float16 kvt_half2_t;
-template <typename T> __device__ __forceinline__ uint32_t kvt_pk(float lo, float hi);
-template <> __device__ __forceinline__ uint32_t kvt_pk<bf16_t>(float lo, float hi) { return pk_bf16(lo, hi); }
-template <> __device__ __forceinline__ uint32_t kvt_pk<half_t>(float lo, float hi) {
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector((float2_t){lo, hi}, kvt_half2_t));
-}
-// max over the four 16-lane rows of a wave (lanes that differ in bits 4 and 5), result in every lane, on v_permlane16_swap / v_permlane32_swap
-// (two VALU ops) instead of two __shfl_xor = ds_bpermute round trips through the LDS crossbar
-__device__ __forceinline__ float kvt_max_rows4(float v) {
-  const unsigned u = __builtin_bit_cast(unsigned, v);
-  const auto a = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-  const float w = fmaxf(__builtin_bit_cast(float, (unsigned)a[0]), __builtin_bit_cast(float, (unsigned)a[1]));
-  const unsigned x = __builtin_bit_cast(unsigned, w);
-  const auto b = __builtin_amdgcn_permlane32_swap(x, x, false, false);
-  return fmaxf(__builtin_bit_cast(float, (unsigned)b[0]), __builtin_bit_cast(float, (unsigned)b[1]));
-}
-template <typename T> struct KvtOne;      // 1.0 in the 16-bit type (the fragment of ones that sums P on the matrix pipe)
-template <> struct KvtOne<bf16_t> { static constexpr short v = 0x3f80; };
-template <> struct KvtOne<half_t> { static constexpr short v = 0x3c00; };
 // ---- attn_kvt_ring_kernel: the tile stream staged in HALF tiles (K half, Vt half: 8 KiB each) through a ring of RING = 5 slots, DMA
 // waits COUNTED (s_waitcnt vmcnt(2 * halves still wanted in flight)) and raw s_barrier, so that RING-1 half tiles stay in flight across
 // the barriers instead of the single whole tile a 2-stage ring keeps between two draining __syncthreads(): the kernel is bound by HBM
@@ -99,10 +78,10 @@ __global__ __launch_bounds__(512) void attn_kvt_ring_kernel(const VtAttnKvtParam
   // wait until half hh has landed (this wave's pieces), leaving the younger halves in flight; then the block-wide barrier
   auto arrive = [&](int hh) {
     const int rem = min(RING - 2, nh - 1 - hh);      // halves younger than hh that are already issued
-    if (rem >= 3) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    else if (rem == 2) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else if (rem == 1) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (rem >= 3) vt_wait_vm<6>();
+    else if (rem == 2) vt_wait_vm<4>();
+    else if (rem == 1) vt_wait_vm<2>();
+    else vt_wait_vm<0>();
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
@@ -121,8 +100,8 @@ __global__ __launch_bounds__(512) void attn_kvt_ring_kernel(const VtAttnKvtParam
   const float fixed_mc = p.fixed_max * 1.4426950408889634f - P_SHIFT;
   float4_t lacc = {0.f, 0.f, 0.f, 0.f};                           // row sums of P on the matrix pipe (every row of the tile = l)
   Frag<T> ones;
-  constexpr short one16 = KvtOne<T>::v;
-  ones.v = (short8_t){one16, one16, one16, one16, one16, one16, one16, one16};
+  constexpr short one = one16<T>();
+  ones.v = (short8_t){one, one, one, one, one, one, one, one};
 
 #pragma unroll
   for (int hh = 0; hh < RING - 1; ++hh)
@@ -185,7 +164,7 @@ __global__ __launch_bounds__(512) void attn_kvt_ring_kernel(const VtAttnKvtParam
       float mx = sv[0];
 #pragma unroll
       for (int i = 1; i < 16; ++i) mx = fmaxf(mx, sv[i]);
-      mx = kvt_max_rows4(mx);
+      mx = rows4_max(mx);
       const float m_new = fmaxf(m_run, mx);
       if (__any(m_new != m_run)) {          // rescale only when some row's running max moved (rare after the first tiles)
         const float alpha = (m_run == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f((m_run - m_new) * cscale);
@@ -207,10 +186,10 @@ __global__ __launch_bounds__(512) void attn_kvt_ring_kernel(const VtAttnKvtParam
     for (int kb = 0; kb < 2; ++kb) {
       // P fragment = this lane's own scores: k index j <-> key kb*32 + (j>>2)*16 + g*4 + (j&3)
       uint4 pw;
-      pw.x = kvt_pk<T>(sv[(kb * 2) * 4 + 0], sv[(kb * 2) * 4 + 1]);
-      pw.y = kvt_pk<T>(sv[(kb * 2) * 4 + 2], sv[(kb * 2) * 4 + 3]);
-      pw.z = kvt_pk<T>(sv[(kb * 2 + 1) * 4 + 0], sv[(kb * 2 + 1) * 4 + 1]);
-      pw.w = kvt_pk<T>(sv[(kb * 2 + 1) * 4 + 2], sv[(kb * 2 + 1) * 4 + 3]);
+      pw.x = pk16<T>(sv[(kb * 2) * 4 + 0], sv[(kb * 2) * 4 + 1]);
+      pw.y = pk16<T>(sv[(kb * 2) * 4 + 2], sv[(kb * 2) * 4 + 3]);
+      pw.z = pk16<T>(sv[(kb * 2 + 1) * 4 + 0], sv[(kb * 2 + 1) * 4 + 1]);
+      pw.w = pk16<T>(sv[(kb * 2 + 1) * 4 + 2], sv[(kb * 2 + 1) * 4 + 3]);
       pf[kb].v = __builtin_bit_cast(short8_t, pw);
     }
     slot = next_slot(slot);
@@ -262,8 +241,8 @@ __global__ __launch_bounds__(512) void attn_kvt_ring_kernel(const VtAttnKvtParam
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) {
       uint2 t;
-      t.x = kvt_pk<T>(o[dt][0] * inv, o[dt][1] * inv);
-      t.y = kvt_pk<T>(o[dt][2] * inv, o[dt][3] * inv);
+      t.x = pk16<T>(o[dt][0] * inv, o[dt][1] * inv);
+      t.y = pk16<T>(o[dt][2] * inv, o[dt][3] * inv);
       *reinterpret_cast<uint2*>(O + dt * 16 + g * 4) = t;
     }
   }
@@ -308,8 +287,8 @@ __global__ __launch_bounds__(256) void attn_combine_kernel(const float* __restri
   const float inv = l_bad ? 0.f : 1.0f / l;
   if (l_bad) vt_range_note(range_flag, VT_RANGE_ATTN_EMPTY);
   uint2 t;
-  t.x = kvt_pk<T>(acc[0] * inv, acc[1] * inv);
-  t.y = kvt_pk<T>(acc[2] * inv, acc[3] * inv);
+  t.x = pk16<T>(acc[0] * inv, acc[1] * inv);
+  t.y = pk16<T>(acc[2] * inv, acc[3] * inv);
   *reinterpret_cast<uint2*>(O + (long)b * o_bs + (long)row * o_rs + h * 64 + d4) = t;
 }
 

@@ -16,6 +16,13 @@ typedef __attribute__((ext_vector_type(4))) float float4_t;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;
 struct half_t { uint16_t b; };   // raw IEEE binary16 bits, a distinct type so templates can tell it from bf16_t
+typedef __attribute__((ext_vector_type(4))) short short4_t;
+typedef __attribute__((ext_vector_type(4))) int int4_t;
+typedef __attribute__((ext_vector_type(16))) float float16_t;
+// address spaces, as the LDS-DMA and transposing-read builtins want their pointers
+typedef __attribute__((address_space(3))) void lds_void;
+typedef const __attribute__((address_space(1))) void glb_void;
+typedef __attribute__((address_space(3))) short4_t lds_short4_t;
 
 #define VT_OK 0
 #define VT_ERR_ARG (-22)
@@ -36,6 +43,15 @@ typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
 __device__ __forceinline__ uint32_t pk_bf16(float lo, float hi) {
   return __builtin_bit_cast(uint32_t, __builtin_convertvector((float2_t){lo, hi}, bf16x2_t));
 }
+typedef __attribute__((ext_vector_type(2))) _Float16 f16x2_t;
+// two fp32 -> two T in one word, round-to-nearest-even (fp16: v_cvt_f16_f32 semantics, overflow gives inf)
+template <typename T> __device__ __forceinline__ uint32_t pk16(float lo, float hi);
+template <> __device__ __forceinline__ uint32_t pk16<bf16_t>(float lo, float hi) { return pk_bf16(lo, hi); }
+template <> __device__ __forceinline__ uint32_t pk16<half_t>(float lo, float hi) {
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector((float2_t){lo, hi}, f16x2_t));
+}
+// 1.0 in the 16-bit type T (a fragment of ones sums its other operand on the matrix pipe)
+template <typename T> __host__ __device__ constexpr short one16() { return std::is_same<T, half_t>::value ? (short)0x3C00 : (short)0x3F80; }
 __device__ __forceinline__ bf16_t f2bf(float f) { return __builtin_bit_cast(bf16_t, (__bf16)f); }
 __device__ __forceinline__ float h2f(half_t h) { return (float)__builtin_bit_cast(_Float16, h.b); }
 __device__ __forceinline__ half_t f2h(float f) { half_t r; r.b = __builtin_bit_cast(uint16_t, (_Float16)f); return r; }   // v_cvt_f16_f32: RNE, saturates to inf
@@ -74,6 +90,52 @@ __device__ __forceinline__ void mma16(float4_t& acc, const Frag<float>& a, const
   for (int j = 0; j < 8; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.v[j], b.v[j], acc, 0, 0, 0);
 }
 
+// v_mfma_f32_32x32x16: D[n][m] += W-fragment x A-fragment of the packed-weights GEMMs (vt_gemm_pw.hip, vt_gemm_pws.hip)
+template <typename T16> __device__ __forceinline__ float16_t mma32(const int4_t w, const int4_t a, const float16_t c);
+template <> __device__ __forceinline__ float16_t mma32<bf16_t>(const int4_t w, const int4_t a, const float16_t c) {
+  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, w), __builtin_bit_cast(bf16x8_t, a), c, 0, 0, 0);
+}
+template <> __device__ __forceinline__ float16_t mma32<half_t>(const int4_t w, const int4_t a, const float16_t c) {
+  return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, w), __builtin_bit_cast(f16x8_t, a), c, 0, 0, 0);
+}
+
+// compile-time loop: f(std::integral_constant<int, 0>{}) .. f(std::integral_constant<int, N - 1>{}).  Indices are constants by construction (a
+// loop that the unroller gives up on would index register arrays dynamically and push them to scratch)
+template <int N, typename F> __device__ __forceinline__ void static_for(F&& f) {
+  if constexpr (N > 0) { static_for<N - 1>(f); f(std::integral_constant<int, N - 1>{}); }
+}
+
+// counted wait: at most N of this wave's vector-memory operations (loads, LDS-DMA and stores share the in-order counter on gfx950) stay in flight.
+// The second form names the registers the wait retires (filled by loads hipcc does not see, wload) as "+v", which is what orders their uses behind
+// it: ONE statement, so that no copy of them can be placed ahead of the wait.  A run-time count is an if-chain over compile-time counts.
+// VLATOUCH_DRAIN_WAITS (debug build, tools/drain_waits_check.sh): every counted wait drains the whole queue — results must not change by a bit.
+#ifdef VLATOUCH_DRAIN_WAITS
+#define VT_VMCNT(N) 0
+#else
+#define VT_VMCNT(N) N
+#endif
+template <int N> __device__ __forceinline__ void vt_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(VT_VMCNT(N)) : "memory"); }
+template <int N> __device__ __forceinline__ void vt_wait_vm(int4_t (&w)[4]) {
+  asm volatile("s_waitcnt vmcnt(%[n])" : "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[3]) : [n] "i"(VT_VMCNT(N)) : "memory");
+}
+template <int N> __device__ __forceinline__ void vt_wait_vm(int4_t (&w)[8]) {
+  asm volatile("s_waitcnt vmcnt(%[n])" : "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[3]), "+v"(w[4]), "+v"(w[5]), "+v"(w[6]), "+v"(w[7]) : [n] "i"(VT_VMCNT(N)) : "memory");
+}
+
+// one KiB of fragment-packed weights -> 4 VGPRs per lane; saddr form: uniform 64-bit base + 32-bit lane offset + immediate.  The load is inline
+// asm because hipcc drains the whole queue with vmcnt(0) at the first use of an ordinary VGPR load issued beside LDS-DMA; it does not see this
+// one, whose completion is counted by hand (vt_wait_vm).  FIRST: the base SGPRs may come from a VALU readfirstlane -> 5 wait states.
+template <int OFF, bool FIRST>
+__device__ __forceinline__ void wload(int4_t& d, const unsigned voff, const char* sbase) {
+  if constexpr (FIRST) asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(d) : "v"(voff), "s"(sbase), "i"(OFF) : "memory");
+  else asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(d) : "v"(voff), "s"(sbase), "i"(OFF) : "memory");
+}
+// a wave-uniform `const char*` rebuilt in SGPRs for the saddr form (the builtin returns int: widen through unsigned, or a low half with bit 31
+// set sign-extends into the high half).  A macro: as an inlined function it reorders hipcc's register definitions in gemm_pws_kernel.
+#define VT_UNIFORM_PTR(p)                                                                                                             \
+  reinterpret_cast<const char*>(((unsigned long)(unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned long)(p) >> 32)) << 32) | \
+                                (unsigned long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned long)(p)))
+
 // read an 8-element fragment from LDS rows of 8 16-byte chunks (128 B), chunk XOR-swizzled by row.
 // `k8` = index of the 8-element group inside the row (0 .. 128/ (8*sizeof(T)) - 1).
 __device__ __forceinline__ int swz(int row, int chunk) { return chunk ^ ((row >> 1) & 7); }
@@ -89,6 +151,15 @@ __device__ __forceinline__ void lds_frag(Frag<float>& f, const char* tile, int r
   const float4_t hi = *reinterpret_cast<const float4_t*>(tile + row * 128 + swz(row, 2 * k8 + 1) * 16);
   f.v[0] = lo[0]; f.v[1] = lo[1]; f.v[2] = lo[2]; f.v[3] = lo[3];
   f.v[4] = hi[0]; f.v[5] = hi[1]; f.v[6] = hi[2]; f.v[7] = hi[3];
+}
+
+// transposing fragment read (ds_read_b64_tr_b16) from a row-major 16-bit image: the 16 lanes of a lane group address a [4 rows][16 columns] block
+// (lane i: row i / 4, columns (i % 4) * 4 .. + 3) and the hardware hands lane i the 4 rows of column i = elements hh * 4 .. + 3 of the fragment.
+// `a` = this lane's finished LDS address for half hh; row pitch, swizzle and slab arithmetic are the caller's.
+template <typename T>
+__device__ __forceinline__ void tr_frag_half(Frag<T>& f, const int hh, const char* a) {
+  const short4_t t = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_short4_t*)a);
+  f.v[hh * 4 + 0] = t[0]; f.v[hh * 4 + 1] = t[1]; f.v[hh * 4 + 2] = t[2]; f.v[hh * 4 + 3] = t[3];
 }
 
 // exp(x) on the hardware exp2 unit (v_exp_f32, ~1 ulp): the activations below are evaluated per output element of GEMM / GroupNorm
@@ -126,22 +197,23 @@ __device__ __forceinline__ float act_apply(float x, int act) {
 
 // sum / max over the 64 lanes, result in every lane.  Round 5: inside a row of 16 on DPP lane permutes, across the four rows on v_permlane16_swap /
 // v_permlane32_swap — all VALU — instead of six __shfl_xor = ds_bpermute round trips through the LDS crossbar.
-__device__ __forceinline__ float rows4_sum(float v) {
+// rows_pair<W>: every lane's value combined with that of the lane W away (W = 16: rows (0,1) and (2,3); W = 32: the two halves of the wave).
+template <int W, bool MAX> __device__ __forceinline__ float rows_pair(float v) {
+  static_assert(W == 16 || W == 32, "a row is 16 lanes: pairs of rows, then pairs of pairs");
   const unsigned u = __builtin_bit_cast(unsigned, v);
-  const auto a = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-  const float w = __builtin_bit_cast(float, (unsigned)a[0]) + __builtin_bit_cast(float, (unsigned)a[1]);
-  const unsigned x = __builtin_bit_cast(unsigned, w);
-  const auto b = __builtin_amdgcn_permlane32_swap(x, x, false, false);
-  return __builtin_bit_cast(float, (unsigned)b[0]) + __builtin_bit_cast(float, (unsigned)b[1]);
+  float a0, a1;
+  if constexpr (W == 16) {
+    const auto a = __builtin_amdgcn_permlane16_swap(u, u, false, false);
+    a0 = __builtin_bit_cast(float, (unsigned)a[0]); a1 = __builtin_bit_cast(float, (unsigned)a[1]);
+  } else {
+    const auto a = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+    a0 = __builtin_bit_cast(float, (unsigned)a[0]); a1 = __builtin_bit_cast(float, (unsigned)a[1]);
+  }
+  return MAX ? fmaxf(a0, a1) : a0 + a1;
 }
-__device__ __forceinline__ float rows4_max(float v) {
-  const unsigned u = __builtin_bit_cast(unsigned, v);
-  const auto a = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-  const float w = fmaxf(__builtin_bit_cast(float, (unsigned)a[0]), __builtin_bit_cast(float, (unsigned)a[1]));
-  const unsigned x = __builtin_bit_cast(unsigned, w);
-  const auto b = __builtin_amdgcn_permlane32_swap(x, x, false, false);
-  return fmaxf(__builtin_bit_cast(float, (unsigned)b[0]), __builtin_bit_cast(float, (unsigned)b[1]));
-}
+// over the four 16-lane rows of a wave (lanes that differ in bits 4 and 5)
+__device__ __forceinline__ float rows4_sum(float v) { return rows_pair<32, false>(rows_pair<16, false>(v)); }
+__device__ __forceinline__ float rows4_max(float v) { return rows_pair<32, true>(rows_pair<16, true>(v)); }
 // sum over each aligned group of 16 lanes, result in every lane, on DPP lane permutes only (no LDS crossbar round trips as
 // __shfl_xor would take): pairs inside quads, quads inside 8s (row_half_mirror pairs quad 0 <-> quad 1), 8s inside the row of 16
 // (row_mirror); for a sum any pairing that covers the group works.

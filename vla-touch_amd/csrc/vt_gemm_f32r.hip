@@ -18,8 +18,6 @@
 
 namespace {
 
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void glb_void;
 
 constexpr int BM = 64, BN = 64, BK = 32;           // BK floats = 128 B per LDS row
 constexpr int STAGE = (BM + BN) * 128;             // 16 KiB per k-tile
@@ -100,17 +98,19 @@ __global__ __launch_bounds__(256, 2) void gemm_f32r_kernel(const VtGemmParams p)
       __builtin_amdgcn_global_load_lds((glb_void*)(w_src[e] + k), (lds_void*)(base + BM * 128 + (wave + 4 * e) * 1024), 16, 0, 0);
   };
   // wait until k-tile i (of this block's nk) has landed — this wave's 4 pieces — leaving the younger tiles in flight; then the barrier
-  auto arrive = [&](int i) {
-    const int rem = min(RING - 3, nk - 1 - i);       // tiles younger than i already issued (4 DMA instructions of this wave each)
-    if (rem >= 3) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-    else if (rem == 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if (rem == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  // wait with `rem` younger tiles (4 DMA instructions of this wave each) left in flight; then the barrier
+  auto arrive_rem = [&](const int rem) {
+    if (rem >= 4) vt_wait_vm<16>();
+    else if (rem == 3) vt_wait_vm<12>();
+    else if (rem == 2) vt_wait_vm<8>();
+    else if (rem == 1) vt_wait_vm<4>();
+    else vt_wait_vm<0>();
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
   };
-  static_assert(RING >= 4 && RING <= 6, "vmcnt table above covers up to 3 younger tiles");
+  auto arrive = [&](int i) { arrive_rem(min(RING - 3, nk - 1 - i)); };      // tiles younger than i already issued
+  static_assert(RING >= 4 && RING <= 6, "vmcnt table above covers up to 4 younger tiles");
 
   float4_t acc[2][2];
 #pragma unroll
@@ -171,17 +171,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32r_kernel(const VtGemmParams p)
     if (i < nk) stage(i, kt0 + i);
   Frags f0, f1;
   if (nk > 0) {
-    {   // tile 0: wait for it alone (up to RING-2 younger tiles in flight)
-      const int rem = min(RING - 2, nk - 1);
-      if (rem >= 4) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-      else if (rem == 3) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-      else if (rem == 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-      else if (rem == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_sched_barrier(0);
-    }
+    arrive_rem(min(RING - 2, nk - 1));      // tile 0: wait for it alone (up to RING-2 younger tiles in flight)
     read_frags(f0, 0);
     for (int i = 0; i < nk; i += 2) {
       body(i, f0, f1);

@@ -25,17 +25,8 @@
 
 namespace {
 
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void glb_void;
-
 constexpr int BM = 256, BN = 256, BK = 64;
 constexpr int BUF_BYTES = (BM + BN) * 128;      // one k-tile: A rows 0..255 then B rows 0..255, 128 B each
-
-#ifdef VLATOUCH_DRAIN_WAITS      // debug build (tools/drain_waits_check.sh): counted waits drain the queue
-#define VT_WAIT_VM(n) asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
-#else
-#define VT_WAIT_VM(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
-#endif
 
 template <typename T16, typename TC, int CMAP>
 __global__ __launch_bounds__(512, 2) void gemm_pp256d_kernel(const VtGemmParams p, const int tiles_n, const int tiles_per_group, const int total_tiles, const int GM) {
@@ -109,7 +100,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp256d_kernel(const VtGemmParams 
 #pragma unroll
   for (int n = 0; n < 6; ++n)
     if (n < NU) stage(n & 3, (n >> 2) & 1, n >> 2);
-  if (NU > 4) { VT_WAIT_VM(8); } else { VT_WAIT_VM(4); }      // units 0, 1 landed
+  if (NU > 4) { vt_wait_vm<8>(); } else { vt_wait_vm<4>(); }      // units 0, 1 landed
   __builtin_amdgcn_s_barrier();
   if (wm == 1) __builtin_amdgcn_s_barrier();       // stagger group 1 by one barrier (group 0 pays it back after the loop)
 
@@ -126,15 +117,15 @@ __global__ __launch_bounds__(512, 2) void gemm_pp256d_kernel(const VtGemmParams 
       const int P = 4 * kt + ph, n = P + 6;
       if (STEADY) {
         stage(U, (kt + DT) & 1, kt + DT);
-        VT_WAIT_VM(8);
+        vt_wait_vm<8>();
       } else {
         if (n < NU) stage(U, (kt + DT) & 1, kt + DT);
         const int fly = min(4, NU - 1 - (P + 2));              // units younger than P+2 that have been issued
-        if (fly >= 4) VT_WAIT_VM(8);
-        else if (fly == 3) VT_WAIT_VM(6);
-        else if (fly == 2) VT_WAIT_VM(4);
-        else if (fly == 1) VT_WAIT_VM(2);
-        else VT_WAIT_VM(0);
+        if (fly >= 4) vt_wait_vm<8>();
+        else if (fly == 3) vt_wait_vm<6>();
+        else if (fly == 2) vt_wait_vm<4>();
+        else if (fly == 1) vt_wait_vm<2>();
+        else vt_wait_vm<0>();
       }
       __builtin_amdgcn_sched_barrier(0);
       __builtin_amdgcn_s_barrier();

@@ -20,8 +20,6 @@
 
 namespace {
 
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void glb_void;
 
 constexpr int BM = 160, BN = 128, BK = 64;
 constexpr int TM = 5;                            // 16-row MFMA tiles per wave along M (wave tile 80 x 64)

@@ -39,7 +39,6 @@
 
 namespace {
 
-typedef __attribute__((address_space(3))) void lds_void;
 typedef __attribute__((ext_vector_type(4))) unsigned uint4_t;
 typedef __attribute__((ext_vector_type(2))) unsigned uint2_t;
 
@@ -56,12 +55,6 @@ enum { MODE_STEADY = 0, MODE_FIRST = 1, MODE_SECOND = 2, MODE_SWITCH = 3, MODE_L
 // the epilogue's store
 __device__ __forceinline__ void pt_store(const uint4_t d, const __amdgpu_buffer_rsrc_t rc, const int off) {
   __builtin_amdgcn_raw_buffer_store_b128(d, rc, off, 0, 0);
-}
-
-// compile-time loop: indices are constants by construction (an epilogue slot that the unroller gives up on would index the accumulators
-// dynamically and push all 128 of them to scratch)
-template <int I0, int I1, typename F> __device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I0 < I1) { f(std::integral_constant<int, I0>{}); static_for<I0 + 1, I1>(f); }
 }
 
 // a value the optimiser must treat as new at this point: derived addresses cannot be hoisted out of the tile walk as loop invariants
@@ -92,24 +85,6 @@ __device__ __forceinline__ void lds_wait(float4_t& a, float4_t& b) { asm volatil
 __device__ __forceinline__ void lds_wait(float4_t& a, float4_t& b, float4_t& c, float4_t& d) { asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d)); }
 __device__ __forceinline__ void lds_wait(float& a, float& b) { asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b)); }
 
-// sum over the four 16-lane rows of a wave (lanes that differ in bits 4 and 5), result in every lane, on the VALU only: v_permlane16_swap pairs rows
-// (0,1) and (2,3), v_permlane32_swap the two halves — a __shfl_xor (ds_bpermute) costs an LDS round trip per step, and a slot runs these on its
-// critical path
-__device__ __forceinline__ float sum_rows4(float v) {
-  const unsigned u = __builtin_bit_cast(unsigned, v);
-  const auto a = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-  const float w = __builtin_bit_cast(float, (unsigned)a[0]) + __builtin_bit_cast(float, (unsigned)a[1]);
-  const unsigned x = __builtin_bit_cast(unsigned, w);
-  const auto b = __builtin_amdgcn_permlane32_swap(x, x, false, false);
-  return __builtin_bit_cast(float, (unsigned)b[0]) + __builtin_bit_cast(float, (unsigned)b[1]);
-}
-
-#ifdef VLATOUCH_DRAIN_WAITS      // debug build (tools/drain_waits_check.sh): every counted wait drains the whole queue — results must not change by a bit
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-#else
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-#endif
-
 // ops allowed to stay in flight after phase `ph` of a k-tile of kind MODE has staged its unit (see the header).  NST = 4 stores per store slot.
 //   STEADY                       8 pieces
 //   SWITCH (k-tile nk-2)         ph 2, 3: + the parameter piece issued at the head of ph 2 (younger than the target units P+2 <= L-2+3+2 ... staged before it)
@@ -129,12 +104,10 @@ __host__ __device__ constexpr int wait_count(int kind, int mode, int ph) {
         : 8);
 }
 
-template <typename T16> __device__ __forceinline__ unsigned pack16(float a, float b);
-template <> __device__ __forceinline__ unsigned pack16<bf16_t>(float a, float b) { return pk_bf16(a, b); }
-template <> __device__ __forceinline__ unsigned pack16<half_t>(float a, float b) {
-  typedef __attribute__((ext_vector_type(2))) _Float16 h2_t;
-  return __builtin_bit_cast(unsigned, (h2_t){(_Float16)a, (_Float16)b});
-}
+// pk16 of vt_common.h with the fp16 pair converted element by element: handed a vector convert, hipcc also pairs the bias adds in front of it into
+// v_pk_add_f32 in the fp16 P16 kernels (the cached attention and the attention backward, the helper's other users, are built on the vector form)
+template <typename T16> __device__ __forceinline__ unsigned pack16(float a, float b) { return pk16<T16>(a, b); }
+template <> __device__ __forceinline__ unsigned pack16<half_t>(float a, float b) { return __builtin_bit_cast(unsigned, (f16x2_t){(_Float16)a, (_Float16)b}); }
 
 __device__ __forceinline__ void mma16z(float4_t& acc, const Frag<bf16_t>& a, const Frag<bf16_t>& b) {
   acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a.v), __builtin_bit_cast(bf16x8_t, b.v), (float4_t){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
@@ -257,10 +230,10 @@ __device__ __forceinline__ void pt_body(const VtGemmParams& p, char* smem, const
       float4_t b4[4];
       b4[0] = lds_ld128<0>(pa); b4[1] = lds_ld128<64>(pa); b4[2] = lds_ld128<128>(pa); b4[3] = lds_ld128<192>(pa);
       lds_wait(b4[0], b4[1], b4[2], b4[3]);
-      static_for<0, 4>([&](auto jj_) __attribute__((always_inline)) {
+      static_for<4>([&](auto jj_) __attribute__((always_inline)) {
         constexpr int jj = decltype(jj_)::value, j = JB + jj;
         float q = 0.f, sm = 0.f;
-        static_for<0, 4>([&](auto i_) __attribute__((always_inline)) {
+        static_for<4>([&](auto i_) __attribute__((always_inline)) {
           constexpr int i = decltype(i_)::value;
           float4_t x = acc[i][j];
           x += b4[i];
@@ -268,10 +241,10 @@ __device__ __forceinline__ void pt_body(const VtGemmParams& p, char* smem, const
           q = fmaf(x[0], x[0], q); q = fmaf(x[1], x[1], q); q = fmaf(x[2], x[2], q); q = fmaf(x[3], x[3], q);
           if (p.hn_mode == 2) sm += (x[0] + x[1]) + (x[2] + x[3]);
         });
-        q = sum_rows4(q);
+        q = rows4_sum(q);
         float var;
         if (p.hn_mode == 2) {
-          sm = sum_rows4(sm);
+          sm = rows4_sum(sm);
           const float mean = sm * (1.f / 64.f);
           var = (q - 64.f * mean * mean) * (1.f / 63.f);
         } else var = q * (1.f / 64.f);
@@ -302,10 +275,10 @@ __device__ __forceinline__ void pt_body(const VtGemmParams& p, char* smem, const
         g4[0] = lds_ld128<IB * 64>(ha); g4[1] = lds_ld128<IB * 64 + 64>(ha);
         lds_wait(g4[0], g4[1]);
         const int lb = flbK;
-        static_for<0, 4>([&](auto jj_) __attribute__((always_inline)) {
+        static_for<4>([&](auto jj_) __attribute__((always_inline)) {
           constexpr int jj = decltype(jj_)::value, j = JB + jj;
           unsigned d[2][2];
-          static_for<0, 2>([&](auto ii_) __attribute__((always_inline)) {
+          static_for<2>([&](auto ii_) __attribute__((always_inline)) {
             constexpr int ii = decltype(ii_)::value;
             const float4_t x = acc[IB + ii][j];
             const float r_ = rs[jj];
@@ -328,10 +301,10 @@ __device__ __forceinline__ void pt_body(const VtGemmParams& p, char* smem, const
         float bvs[2];
         bvs[0] = lds_ld32<IB * 64>(va); bvs[1] = lds_ld32<IB * 64 + 64>(va);
         lds_wait(bvs[0], bvs[1]);
-        static_for<0, 2>([&](auto ii_) __attribute__((always_inline)) {
+        static_for<2>([&](auto ii_) __attribute__((always_inline)) {
           constexpr int i = IB + decltype(ii_)::value;
           const float bv = bvs[decltype(ii_)::value];
-          static_for<0, 2>([&](auto jp_) __attribute__((always_inline)) {
+          static_for<2>([&](auto jp_) __attribute__((always_inline)) {
             constexpr int j = JB + 2 * decltype(jp_)::value;
             float4_t lo = acc[i][j], hi = acc[i][j + 1];
 #pragma unroll
@@ -362,10 +335,10 @@ __device__ __forceinline__ void pt_body(const VtGemmParams& p, char* smem, const
       lds_wait(b4[0], b4[1]);
       const int rowb = (int)p.ldc * 2;
       const int lb = fl15 * rowb + (flbK & 127);
-      static_for<0, 4>([&](auto jj_) __attribute__((always_inline)) {
+      static_for<4>([&](auto jj_) __attribute__((always_inline)) {
         constexpr int j = JB + decltype(jj_)::value;
         unsigned d[2][2];
-        static_for<0, 2>([&](auto ii_) __attribute__((always_inline)) {
+        static_for<2>([&](auto ii_) __attribute__((always_inline)) {
           constexpr int ii = decltype(ii_)::value;
           const float4_t x = acc[IB + ii][j];
           float o0 = x[0] + b4[ii][0], o1 = x[1] + b4[ii][1], o2 = x[2] + b4[ii][2], o3 = x[3] + b4[ii][3];
@@ -407,17 +380,17 @@ __device__ __forceinline__ void pt_body(const VtGemmParams& p, char* smem, const
       const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc((void*)rbase, 0, ok ? (int)((nrows - 1) * p.ldr * 4 + 256) : 0, 0x00020000);
       const int crow = (int)p.ldc * 4, rrow = (int)p.ldr * 4;
       const int clane = fl15 * crow + fg * 16, rlane = fl15 * rrow + fg * 16;
-      static_for<0, 2>([&](auto h_) __attribute__((always_inline)) {          // rows 0..63, then rows 64..127 of the wave
+      static_for<2>([&](auto h_) __attribute__((always_inline)) {          // rows 0..63, then rows 64..127 of the wave
         constexpr int JB = decltype(h_)::value * 4;
         uint4_t rv[4][4];
-        static_for<0, 4>([&](auto jj_) __attribute__((always_inline)) {
-          static_for<0, 4>([&](auto i_) __attribute__((always_inline)) {
+        static_for<4>([&](auto jj_) __attribute__((always_inline)) {
+          static_for<4>([&](auto i_) __attribute__((always_inline)) {
             constexpr int jj = decltype(jj_)::value, i = decltype(i_)::value, j = JB + jj;
             rv[jj][i] = __builtin_amdgcn_raw_buffer_load_b128(rr, rlane + j * 16 * rrow + i * 64, 0, 0);
           });
         });
-        static_for<0, 4>([&](auto jj_) __attribute__((always_inline)) {
-          static_for<0, 4>([&](auto i_) __attribute__((always_inline)) {
+        static_for<4>([&](auto jj_) __attribute__((always_inline)) {
+          static_for<4>([&](auto i_) __attribute__((always_inline)) {
             constexpr int jj = decltype(jj_)::value, i = decltype(i_)::value, j = JB + jj;
             float4_t x = acc[i][j];
             const float4_t r = __builtin_bit_cast(float4_t, rv[jj][i]);
@@ -448,7 +421,7 @@ __device__ __forceinline__ void pt_body(const VtGemmParams& p, char* smem, const
   stage_params(cur, 0);
 #pragma unroll
   for (int n = 0; n < 6; ++n) stage(n & 3, (n >> 2) & 1, n >> 2);          // nk >= 4: units 0..5 exist
-  wait_vm<8>();                                                             // the parameter piece(s) and units 0, 1 landed
+  vt_wait_vm<8>();                                                             // the parameter piece(s) and units 0, 1 landed
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                        // wave 0's gain row (a __syncthreads() here would drain the DMA queue)
   __builtin_amdgcn_s_barrier();
   if (wm == 1) __builtin_amdgcn_s_barrier();       // stagger group 1 by one barrier (group 0 pays it back after the loop)
@@ -494,7 +467,7 @@ __device__ __forceinline__ void pt_body(const VtGemmParams& p, char* smem, const
       if constexpr (MODE == MODE_SWITCH) { if (ph >= 2) ks = 0; }
       if constexpr (MODE == MODE_LAST) ks = ph < 2 ? 0 : 1;
       stage(U, (kt + DT + par) & 1, ks);
-      wait_vm<wait_count(KIND, MODE, ph)>();
+      vt_wait_vm<wait_count(KIND, MODE, ph)>();
       __builtin_amdgcn_sched_barrier(0);
       __builtin_amdgcn_s_barrier();
       __builtin_amdgcn_sched_barrier(0);
@@ -502,7 +475,7 @@ __device__ __forceinline__ void pt_body(const VtGemmParams& p, char* smem, const
     // 16 MFMAs of one quadrant; FIRST: the ks = 0 MFMAs start from a zero C (the quadrant's previous contents were stored by its slot)
 #define VT_PT_MMA(AF, BF, ah, bh)                                                                                          \
     __builtin_amdgcn_s_setprio(1);                                                                                         \
-    static_for<0, 16>([&](auto n_) __attribute__((always_inline)) {                                                        \
+    static_for<16>([&](auto n_) __attribute__((always_inline)) {                                                        \
       constexpr int n = decltype(n_)::value, ks = n >> 3, i = (n >> 2) & 1, j = n & 3;                                      \
       float4_t& c_ = acc[(bh) * 2 + i][(ah) * 4 + j];                                                                       \
       if constexpr (!SWAP) {                                                                                               \
@@ -576,7 +549,7 @@ __device__ __forceinline__ void pt_body(const VtGemmParams& p, char* smem, const
   slot_run(std::integral_constant<int, 3>{});
   slot_run(std::integral_constant<int, 4>{});
   slot_run(std::integral_constant<int, 5>{});
-  wait_vm<0>();
+  vt_wait_vm<0>();
 }
 
 // KV kind: the K-half and the V-half tiles are walked by DIFFERENT blocks (roles alternate in groups of 8 blocks = one block per XCD), because the

@@ -32,43 +32,10 @@
 
 namespace {
 
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((ext_vector_type(4))) int int4_t;
-typedef __attribute__((ext_vector_type(16))) float float16_t;
-
 constexpr int BM = 160, BN = 128, BK = 64;
 constexpr int TMW = BM / 32;                     // 32-row MFMA tiles per wave
 constexpr int A_TILE = BM * 128;                 // one k-tile of the activation panel (20 KiB)
 constexpr int OPS = BM / 8 / 4 + 4;              // vector-memory operations per wave per k-tile: 5 DMA pieces + 4 weight loads
-
-template <typename T16> __device__ __forceinline__ float16_t mma32(const int4_t w, const int4_t a, const float16_t c);
-template <> __device__ __forceinline__ float16_t mma32<bf16_t>(const int4_t w, const int4_t a, const float16_t c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, w), __builtin_bit_cast(bf16x8_t, a), c, 0, 0, 0);
-}
-template <> __device__ __forceinline__ float16_t mma32<half_t>(const int4_t w, const int4_t a, const float16_t c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, w), __builtin_bit_cast(f16x8_t, a), c, 0, 0, 0);
-}
-
-// one KiB of packed weights -> 4 VGPRs per lane; saddr form: uniform 64-bit base + 32-bit lane offset + immediate.  hipcc does not see
-// this load: its completion is counted by hand (pw_wait).  FIRST: the base SGPRs may come from a VALU readfirstlane -> 5 wait states.
-template <int OFF, bool FIRST>
-__device__ __forceinline__ void pw_wload(int4_t& d, const unsigned voff, const char* sbase) {
-  if constexpr (FIRST) asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(d) : "v"(voff), "s"(sbase), "i"(OFF) : "memory");
-  else asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(d) : "v"(voff), "s"(sbase), "i"(OFF) : "memory");
-}
-// counted wait that retires weight buffer w[0..3] (and everything older in this wave's queue, i.e. its DMA pieces of that k-tile)
-template <int N>
-__device__ __forceinline__ void pw_wait(int4_t (&w)[4]) {
-#ifdef VLATOUCH_DRAIN_WAITS      // debug build (tools/drain_waits_check.sh)
-  asm volatile("s_waitcnt vmcnt(0)" : "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[3]) : : "memory");
-#else
-  asm volatile("s_waitcnt vmcnt(%[n])" : "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[3]) : [n] "i"(N) : "memory");
-#endif
-}
-
-template <int N, typename F> __device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (N > 0) { static_for<N - 1>(f); f(std::integral_constant<int, N - 1>{}); }
-}
 
 // FUSE: 0 = plain, 1 = producer of a fused RMSNorm hand-off (xn_out / xn_part), 2 = its consumer (rs_part) — own instantiations: the plain kernels keep their registers
 template <typename T16, typename TC, int NB, int FUSE = 0>
@@ -105,9 +72,7 @@ __global__ __launch_bounds__(256, 1) void gemm_pw_kernel(const VtGemmParams p, c
   }
   // weight stream of this wave: 32-column block n0/32 + wave, K/16 fragments of 1 KiB back to back
   const char* wbase = reinterpret_cast<const char*>(p.Wp) + ((long)grp * p.w_gs) * 2 + ((long)(n0 / 32 + wave) * (p.K / 16)) * 1024;
-  // (the builtin returns int: widen through unsigned, or a low half with bit 31 set sign-extends into the high half)
-  wbase = reinterpret_cast<const char*>(((unsigned long)(unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned long)wbase >> 32)) << 32) |
-                                        (unsigned long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned long)wbase));
+  wbase = VT_UNIFORM_PTR(wbase);
   const unsigned wvoff = lane * 16;
 
   int4_t wb[NB][4];
@@ -117,10 +82,10 @@ __global__ __launch_bounds__(256, 1) void gemm_pw_kernel(const VtGemmParams p, c
     for (int e = 0; e < 5; ++e)
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_void*)(smem + b * A_TILE + (wave + 4 * e) * 1024), 16, asrc[e], kt * (BK * 2), 0, 0);
     const char* sb = wbase + (long)kt * 4096;
-    pw_wload<0, true>(wb[b][0], wvoff, sb);
-    pw_wload<1024, false>(wb[b][1], wvoff, sb);
-    pw_wload<2048, false>(wb[b][2], wvoff, sb);
-    pw_wload<3072, false>(wb[b][3], wvoff, sb);
+    wload<0, true>(wb[b][0], wvoff, sb);
+    wload<1024, false>(wb[b][1], wvoff, sb);
+    wload<2048, false>(wb[b][2], wvoff, sb);
+    wload<3072, false>(wb[b][3], wvoff, sb);
   };
 
   // fragment (32 rows x 16 k) of k-step s of the tile in slot b: lane reads row j*32 + l31, chunk s*2 + hk (swizzled by the row)
@@ -141,8 +106,8 @@ __global__ __launch_bounds__(256, 1) void gemm_pw_kernel(const VtGemmParams p, c
 
   // prologue: tiles 0 .. NB-2 in flight, tiles 0 and 1 landed and block-visible, fragments of (tile 0, step 0) in registers
   static_for<NB - 1>([&](auto bc) { if (decltype(bc)::value < nk) issue(decltype(bc)::value, bc); });
-  pw_wait<(NB - 3) * OPS>(wb[0]);
-  pw_wait<(NB - 3) * OPS>(wb[1]);
+  vt_wait_vm<(NB - 3) * OPS>(wb[0]);
+  vt_wait_vm<(NB - 3) * OPS>(wb[1]);
   __builtin_amdgcn_sched_barrier(0);
   __builtin_amdgcn_s_barrier();
   __builtin_amdgcn_sched_barrier(0);
@@ -183,8 +148,8 @@ __global__ __launch_bounds__(256, 1) void gemm_pw_kernel(const VtGemmParams p, c
       __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);      // one DS read
     }
     // tile t + 2: retire it (and this wave's DMA pieces of it), then make every wave's pieces block-visible
-    if constexpr (!TAIL) pw_wait<(NB - 3) * OPS>(wb[(U + 2) % NB]);
-    else if constexpr (U + 2 < NB) pw_wait<(NB - 3 - U > 0 ? NB - 3 - U : 0) * OPS>(wb[(U + 2) % NB]);
+    if constexpr (!TAIL) vt_wait_vm<(NB - 3) * OPS>(wb[(U + 2) % NB]);
+    else if constexpr (U + 2 < NB) vt_wait_vm<(NB - 3 - U > 0 ? NB - 3 - U : 0) * OPS>(wb[(U + 2) % NB]);
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);

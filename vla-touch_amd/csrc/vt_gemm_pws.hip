@@ -23,37 +23,12 @@
 
 namespace {
 
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((ext_vector_type(4))) int int4_t;
-typedef __attribute__((ext_vector_type(16))) float float16_t;
-
 constexpr int BM = 96, BN = 64, BK = 64;
 constexpr int TMW = BM / 32;                     // 32-row MFMA tiles per wave
 constexpr int A_TILE = BM * 128;                 // one k-tile of the activation rows (12 KiB)
 constexpr int CH = 4;                            // k-tiles per chunk
 constexpr int CHUNK = CH * A_TILE;               // 48 KiB
 constexpr int OPS = CH * 3 + 8;                  // vector-memory operations per wave per chunk: 12 DMA pieces + 8 weight loads
-
-template <typename T16> __device__ __forceinline__ float16_t mma32s(const int4_t w, const int4_t a, const float16_t c);
-template <> __device__ __forceinline__ float16_t mma32s<bf16_t>(const int4_t w, const int4_t a, const float16_t c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, w), __builtin_bit_cast(bf16x8_t, a), c, 0, 0, 0);
-}
-template <> __device__ __forceinline__ float16_t mma32s<half_t>(const int4_t w, const int4_t a, const float16_t c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, w), __builtin_bit_cast(f16x8_t, a), c, 0, 0, 0);
-}
-template <int OFF, bool FIRST>
-__device__ __forceinline__ void pws_wload(int4_t& d, const unsigned voff, const char* sbase) {
-  if constexpr (FIRST) asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(d) : "v"(voff), "s"(sbase), "i"(OFF) : "memory");
-  else asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(d) : "v"(voff), "s"(sbase), "i"(OFF) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void pws_wait(int4_t (&w)[8]) {
-#ifdef VLATOUCH_DRAIN_WAITS      // debug build (tools/drain_waits_check.sh)
-  asm volatile("s_waitcnt vmcnt(0)" : "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[3]), "+v"(w[4]), "+v"(w[5]), "+v"(w[6]), "+v"(w[7]) : : "memory");
-#else
-  asm volatile("s_waitcnt vmcnt(%[n])" : "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[3]), "+v"(w[4]), "+v"(w[5]), "+v"(w[6]), "+v"(w[7]) : [n] "i"(N) : "memory");
-#endif
-}
 
 template <typename T16, typename TC>
 __global__ __launch_bounds__(256, 1) void gemm_pws_kernel(const VtGemmParams p, const int S, const int tiles_n) {
@@ -80,8 +55,7 @@ __global__ __launch_bounds__(256, 1) void gemm_pws_kernel(const VtGemmParams p, 
     asrc[e] = (int)(((long)(min(m0 + r, p.M - 1) - m0) * p.lda + c * 8) * 2);
   }
   const char* wbase = reinterpret_cast<const char*>(p.Wp) + ((long)(n0 / 32 + wc) * (p.K / 16)) * 1024;
-  wbase = reinterpret_cast<const char*>(((unsigned long)(unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned long)wbase >> 32)) << 32) |
-                                        (unsigned long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned long)wbase));
+  wbase = VT_UNIFORM_PTR(wbase);
   const unsigned wvoff = lane * 16;
 
   int4_t wb[2][8];                                  // [chunk buffer][own k-tile 0/1 of the chunk x 4 k-steps]
@@ -94,15 +68,15 @@ __global__ __launch_bounds__(256, 1) void gemm_pws_kernel(const VtGemmParams p, 
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_void*)(smem + b * CHUNK + kk * A_TILE + (wave + 4 * e) * 1024), 16, asrc[e],
                                                  (kt0 + c * CH + kk) * (BK * 2), 0, 0);
     const char* sb0 = wbase + (long)(kt0 + c * CH + wp) * 4096;         // this wave's k-tiles of the chunk: wp and wp + 2
-    pws_wload<0, true>(wb[b][0], wvoff, sb0);
-    pws_wload<1024, false>(wb[b][1], wvoff, sb0);
-    pws_wload<2048, false>(wb[b][2], wvoff, sb0);
-    pws_wload<3072, false>(wb[b][3], wvoff, sb0);
+    wload<0, true>(wb[b][0], wvoff, sb0);
+    wload<1024, false>(wb[b][1], wvoff, sb0);
+    wload<2048, false>(wb[b][2], wvoff, sb0);
+    wload<3072, false>(wb[b][3], wvoff, sb0);
     const char* sb1 = sb0 + 2 * 4096;
-    pws_wload<0, true>(wb[b][4], wvoff, sb1);
-    pws_wload<1024, false>(wb[b][5], wvoff, sb1);
-    pws_wload<2048, false>(wb[b][6], wvoff, sb1);
-    pws_wload<3072, false>(wb[b][7], wvoff, sb1);
+    wload<0, true>(wb[b][4], wvoff, sb1);
+    wload<1024, false>(wb[b][5], wvoff, sb1);
+    wload<2048, false>(wb[b][6], wvoff, sb1);
+    wload<3072, false>(wb[b][7], wvoff, sb1);
   };
 
   const int xr = (l31 >> 1) & 7;
@@ -125,7 +99,7 @@ __global__ __launch_bounds__(256, 1) void gemm_pws_kernel(const VtGemmParams p, 
     // places BEFORE the wait of one branch — i.e. it copies registers whose loads have not landed); the last chunk drains the queue with
     // an operand-less wait ahead of it
     if (c + 1 >= NC) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    pws_wait<OPS>(wb[b]);
+    vt_wait_vm<OPS>(wb[b]);
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();                   // every wave's pieces of chunk c are block-visible
     __builtin_amdgcn_sched_barrier(0);
@@ -137,7 +111,7 @@ __global__ __launch_bounds__(256, 1) void gemm_pws_kernel(const VtGemmParams p, 
 #pragma unroll
         for (int j = 0; j < TMW; ++j) af[j] = *reinterpret_cast<const int4_t*>(smem + b * CHUNK + (wp + 2 * kk) * A_TILE + j * 4096 + foff[s]);
 #pragma unroll
-        for (int j = 0; j < TMW; ++j) acc[j] = mma32s<T16>(wb[b][kk * 4 + s], af[j], acc[j]);
+        for (int j = 0; j < TMW; ++j) acc[j] = mma32<T16>(wb[b][kk * 4 + s], af[j], acc[j]);
       }
     if (c + 2 < NC) {
       __builtin_amdgcn_sched_barrier(0);

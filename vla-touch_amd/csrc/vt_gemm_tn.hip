@@ -39,21 +39,12 @@ constexpr int IMG = BM * PITCH;         // one operand tile
 constexpr int FULL_WAVE = 256;          // workgroups the grid should reach: one per CU
 constexpr int MIN_STEPS = 4;            // a split walks at least this many m-steps
 constexpr int MAX_SPLITS = 16;
-typedef __attribute__((ext_vector_type(4))) short short4_t;
-typedef __attribute__((address_space(3))) short4_t lds_short4_t;
-
-template <typename T> __device__ __forceinline__ short one16();
-template <> __device__ __forceinline__ short one16<bf16_t>() { return (short)0x3F80; }
-template <> __device__ __forceinline__ short one16<half_t>() { return (short)0x3C00; }
 
 // fragment [column c0 + l15][rows (j >> 2) * 16 + g * 4 + (j & 3)] of a row-major [32][128] image; `off` = the lane's offset inside a 16-row slab
 template <typename T>
 __device__ __forceinline__ void tr_frag(Frag<T>& f, const char* img, unsigned off) {
 #pragma unroll
-  for (int hh = 0; hh < 2; ++hh) {
-    const short4_t t = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_short4_t*)(img + hh * 16 * PITCH + off));
-    f.v[hh * 4 + 0] = t[0]; f.v[hh * 4 + 1] = t[1]; f.v[hh * 4 + 2] = t[2]; f.v[hh * 4 + 3] = t[3];
-  }
+  for (int hh = 0; hh < 2; ++hh) tr_frag_half(f, hh, img + hh * 16 * PITCH + off);
 }
 
 // out / dbout: dW and db (gridDim.z = 1, part_stride = 0) or the first split's partials in the workspace (part_stride = N K + N); dbout may be null

@@ -35,16 +35,8 @@ __device__ __forceinline__ float seg_sum(float v, int n) {
   if (n >= 8) v += dpp(v, std::integral_constant<int, 0x141>{});   // row_half_mirror
   if (n >= 16) v += dpp(v, std::integral_constant<int, 0x140>{});  // row_mirror
   // across rows: v_permlane16_swap pairs rows (0,1) and (2,3), v_permlane32_swap the two halves — VALU, no ds_bpermute round trip (round 5)
-  if (n >= 32) {
-    const unsigned u = __builtin_bit_cast(unsigned, v);
-    const auto a = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-    v = __builtin_bit_cast(float, (unsigned)a[0]) + __builtin_bit_cast(float, (unsigned)a[1]);
-  }
-  if (n >= 64) {
-    const unsigned u = __builtin_bit_cast(unsigned, v);
-    const auto b = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-    v = __builtin_bit_cast(float, (unsigned)b[0]) + __builtin_bit_cast(float, (unsigned)b[1]);
-  }
+  if (n >= 32) v = rows_pair<16, false>(v);
+  if (n >= 64) v = rows_pair<32, false>(v);
   return v;
 }
 
