@@ -19,12 +19,13 @@ def mish(x: torch.Tensor) -> torch.Tensor:
     return x * torch.tanh(F.softplus(x))
 
 
-def sinusoidal_pos_emb(t: torch.Tensor, dim: int) -> torch.Tensor:
-    """conditional_unet_1D.py:12-19 — cat(sin, cos) of t * exp(-k*ln(1e4)/(half-1))."""
+def sinusoidal_pos_emb(t: torch.Tensor, dim: int, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """conditional_unet_1D.py:12-19 — cat(sin, cos) of t * exp(-k*ln(1e4)/(half-1)).  The frequencies are evaluated in float32, as the
+    reference and the kernels evaluate them, and then promoted to `dtype`."""
     half = dim // 2
     c = math.log(10000) / (half - 1)
     freqs = torch.exp(torch.arange(half, dtype=torch.float32) * -c)
-    e = t.float()[:, None] * freqs[None, :]
+    e = t.to(dtype)[:, None] * freqs.to(dtype)[None, :]
     return torch.cat((e.sin(), e.cos()), dim=-1)
 
 
@@ -53,7 +54,7 @@ def res_block(sd: SD, p: str, x: torch.Tensor, g: torch.Tensor, n_groups: int = 
 
 def step_embedding(sd: SD, prefix: str, t: torch.Tensor, dsed: int = 256) -> torch.Tensor:
     """diffusion_step_encoder: sinusoid -> Linear -> Mish -> Linear (conditional_unet_1D.py:133-138)."""
-    e = sinusoidal_pos_emb(t, dsed)
+    e = sinusoidal_pos_emb(t, dsed, sd[f"{prefix}diffusion_step_encoder.1.weight"].dtype)
     e = F.linear(e, sd[f"{prefix}diffusion_step_encoder.1.weight"], sd[f"{prefix}diffusion_step_encoder.1.bias"])
     e = mish(e)
     return F.linear(e, sd[f"{prefix}diffusion_step_encoder.3.weight"], sd[f"{prefix}diffusion_step_encoder.3.bias"])
@@ -61,10 +62,12 @@ def step_embedding(sd: SD, prefix: str, t: torch.Tensor, dsed: int = 256) -> tor
 
 def unet_forward(sd: SD, prefix: str, sample: torch.Tensor, timestep: torch.Tensor,
                  global_cond: torch.Tensor, n_down: int = 3, n_groups: int = 8) -> torch.Tensor:
-    """sample (B,T,C), timestep (B,), global_cond (B,G) -> (B,T,C)  (conditional_unet_1D.py:194-247)."""
-    x = sample.movedim(-1, -2).float()
+    """sample (B,T,C), timestep (B,), global_cond (B,G) -> (B,T,C)  (conditional_unet_1D.py:194-247), computed in the dtype of the
+    weights: a float64 state dict gives a float64 forward."""
+    dtype = sd[f"{prefix}final_conv.1.weight"].dtype
+    x = sample.movedim(-1, -2).to(dtype)
     t = timestep.expand(x.shape[0])
-    g = torch.cat([step_embedding(sd, prefix, t), global_cond.float()], dim=-1)
+    g = torch.cat([step_embedding(sd, prefix, t), global_cond.to(dtype)], dim=-1)
     h = []
     for i in range(n_down):
         x = res_block(sd, f"{prefix}down_modules.{i}.0", x, g, n_groups)

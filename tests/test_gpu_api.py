@@ -80,35 +80,47 @@ def test_checkpoint_roundtrip_reference_format(controllers):
     assert torch.equal(out, ref)
 
 
+def sampler_is_fused(si, B, T, n_steps):
+    """Whether the engine the interpolant last sampled with takes the fused path at this shape."""
+    from vlatouch import _lib as L
+    return L.lib().vt_unet_fused_covers(si._sampler[1]._h, B, T, n_steps) == 1
+
+
+@pytest.mark.parametrize("prec", ["fp32", "bf16"])
 @pytest.mark.parametrize("tag,sde,gt,et", SCHEDULE_CASES)
-def test_other_schedules_and_bs_integrator(controllers, tag, sde, gt, et):
+def test_other_schedules_and_bs_integrator(controllers, tag, sde, gt, et, prec):
+    """fp32: the launch-per-op driver and sde_update_kernel; bf16: the fused path (its own update, coefficient table and FiLM rows)."""
     g = G(f"g2_si_{tag}")
-    si = controllers["fp32"].diffusion_model
+    si = controllers[prec].diffusion_model
     old = (si.sde_type, si.gamma_type, si.epsilon_type)
     try:
         si.sde_type, si.gamma_type, si.epsilon_type = sde, gt, et
         x0, cond, _ = cases.si_inputs(2, 16)
         xT, traj = si.sample(x0, cond, diffuse_step=8, recod_traj=True, noise=torch.from_numpy(g["z"]))
+        assert sampler_is_fused(si, 2, 16, 8) == (prec == "bf16")
         assert len(traj) == 9
-        assert err(torch.stack(traj), g["traj"]) < 1e-4, (tag, err(torch.stack(traj), g["traj"]))
+        assert err(torch.stack(traj), g["traj"]) < TOL[prec], (tag, err(torch.stack(traj), g["traj"]))
     finally:
         si.sde_type, si.gamma_type, si.epsilon_type = old
 
 
+@pytest.mark.parametrize("prec", ["fp32", "bf16"])
 @pytest.mark.parametrize("tag,sde,sw,direction", [("vs_backward_w07", "vs", 0.7, "backward"), ("bs_backward_w13", "bs", 1.3, "backward"),
                                                   ("vs_forward_w05", "vs", 0.5, "forward")])
-def test_backward_direction_and_score_weight(controllers, tag, sde, sw, direction):
-    """sde_vs / sde_bs of the mirror with direction='backward' and score_weight != 1 against the reference's own run (g2 variants)."""
+def test_backward_direction_and_score_weight(controllers, tag, sde, sw, direction, prec):
+    """sde_vs / sde_bs of the mirror with direction='backward' and score_weight != 1 against the reference's own run (g2 variants); bf16 is
+    the fused path, at the bf16 north-star tolerance."""
     g = G(f"g2_si_{tag}")
-    si = controllers["fp32"].diffusion_model
+    si = controllers[prec].diffusion_model
     x0, cond, _ = cases.si_inputs(2, 16)
     fn = si.sde_bs if sde == "bs" else si.sde_vs
     xT, traj = fn(x_initial=x0, cond=cond, delta_t=float(1.0 / 8), score_weight=sw, direction=direction, noise=torch.from_numpy(g["z"]))
+    assert sampler_is_fused(si, 2, 16, 8) == (prec == "bf16")
     assert len(traj) == 9
     scale = max(1.0, float(np.abs(g["traj"]).max()))       # the backward SDE blows up in its last step (|x| ~ 77): relative tolerance there
-    assert err(torch.stack(traj[:-1]), g["traj"][:-1]) < 1e-4, (tag, err(torch.stack(traj[:-1]), g["traj"][:-1]))
-    assert err(torch.stack(traj), g["traj"]) < 1e-4 * scale, (tag, err(torch.stack(traj), g["traj"]))
-    assert err(xT, g["traj"][-1]) < 1e-4 * scale
+    assert err(torch.stack(traj[:-1]), g["traj"][:-1]) < TOL[prec], (tag, err(torch.stack(traj[:-1]), g["traj"][:-1]))
+    assert err(torch.stack(traj), g["traj"]) < TOL[prec] * scale, (tag, err(torch.stack(traj), g["traj"]))
+    assert err(xT, g["traj"][-1]) < TOL[prec] * scale
     with pytest.raises(NotImplementedError):
         si.sde_vs(x_initial=x0, cond=cond, delta_t=0.125, direction="sideways")
 
