@@ -6,7 +6,9 @@
 // Grouped (z) launches: z = group*splitk + slice; each group offsets A/W/C/bias/residual by a fixed
 // element stride; each split-K slice writes a raw fp32 partial slab (no epilogue) at C + slice*c_slab.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
+#include <string.h>
 
 struct VtGemmParams {
   const void* A; const void* W; void* C;
@@ -56,3 +58,17 @@ struct VtGemmParams {
   // range guard (include/vlatouch.h, vt_rdt_set_range_flag): device word the hand-off producer ORs VT_RANGE_XN_SAT into when it clamps; null = none
   unsigned* range_flag;
 };
+
+// The block of a Linear, C[M, N] = act(A[M, K] W[N, K]^T + bias): every other field zero, one group, no split.  The drivers build their launches
+// from it and set what else a launch needs (conv mode, residual, Wp, ...); vt_gemm_groups turns it into a grouped launch.
+inline VtGemmParams vt_linear(const void* A, int adt, long lda, const void* W, int cdt, long ldw, const float* bias, void* C, int odt, long ldc,
+                              int M, int N, int K, int act) {
+  VtGemmParams p;
+  memset(&p, 0, sizeof(p));
+  p.A = A; p.W = W; p.C = C; p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldw = ldw; p.ldc = ldc;
+  p.bias = bias; p.act = act; p.groups = 1; p.splitk = 1; p.a_dtype = adt; p.w_dtype = cdt; p.c_dtype = odt;
+  return p;
+}
+inline void vt_gemm_groups(VtGemmParams& p, int groups, long a_gs, long w_gs, long c_gs, long bias_gs) {
+  p.groups = groups; p.a_gs = a_gs; p.w_gs = w_gs; p.c_gs = c_gs; p.bias_gs = bias_gs;
+}

@@ -172,7 +172,7 @@ int vt_gemm_tn_plan(int M, int N, int K, VtGemmTnPlan* plan) {
   S = ((long)M + rps - 1) / rps;                            // no empty split
   plan->splits = (int)S;
   plan->rows_per_split = (int)rps;
-  plan->ws_bytes = S == 1 ? 0 : (S * ((long)N * K + N) * 4 + 255) / 256 * 256;
+  plan->ws_bytes = S == 1 ? 0 : (long)vt_round256((size_t)(S * ((long)N * K + N) * 4));
   return VT_OK;
 }
 

@@ -297,7 +297,7 @@ struct vt_lstm_s {
 };
 int vt_lstm_num_weights(const vt_lstm_desc* d) { return 4 + 2 * d->layers + 6; }
 int vt_lstm_create(const vt_lstm_desc* desc, const void* const* w, int n, vt_lstm_t* out) {
-  if (!desc || !w || !out) return vt_fail(VT_ERR_ARG, "vt_lstm_create: null argument");
+  CK(vt_create_args("vt_lstm_create", desc, w, out));
   const vt_lstm_desc& d = *desc;
   if (d.hidden != 128 && d.hidden != 256 && d.hidden != 384)
     return vt_fail(VT_ERR_UNSUPPORTED, "vt_lstm_create: hidden must be 128, 256 or 384 (got %d): each of the 8 waves owns hidden/8 = whole 16-unit tiles, and 512 "
@@ -306,17 +306,16 @@ int vt_lstm_create(const vt_lstm_desc* desc, const void* const* w, int n, vt_lst
     return vt_fail(VT_ERR_ARG, "vt_lstm_create: bad descriptor (layers 1..4, state_dim <= 16, force_dim <= %d)", KF);
   if (d.hidden == 384 && d.layers > 3) return vt_fail(VT_ERR_UNSUPPORTED, "vt_lstm_create: hidden 384 with 4 layers does not fit the CU's LDS");
   if (d.cdt != VT_F32 && d.cdt != VT_BF16 && d.cdt != VT_F32X3) return vt_fail(VT_ERR_ARG, "vt_lstm_create: weights must be fp32, split-bf16 (x3) or bf16");
-  if (n != vt_lstm_num_weights(desc)) return vt_fail(VT_ERR_ARG, "vt_lstm_create: expected %d weights, got %d", vt_lstm_num_weights(desc), n);
-  for (int k = 0; k < n; ++k) if (!w[k]) return vt_fail(VT_ERR_ARG, "vt_lstm_create: weight %d is null", k);
+  VtWeights W;
+  CK(W.open("vt_lstm_create", w, n, vt_lstm_num_weights(desc)));
   vt_lstm_s* h = new (std::nothrow) vt_lstm_s();
   if (!h) return vt_fail(-12, "out of host memory");
   h->d = d;
   memset(&h->w, 0, sizeof(h->w));
-  int i = 0;
-  h->w.fe1 = w[i++]; h->w.fe_b1 = (const float*)w[i++]; h->w.fe2 = w[i++]; h->w.fe_b2 = (const float*)w[i++];
-  for (int l = 0; l < d.layers; ++l) { h->w.wl[l] = w[i++]; h->w.bl[l] = (const float*)w[i++]; }
-  h->w.h1 = w[i++]; h->w.h1_b = (const float*)w[i++]; h->w.ln_w = (const float*)w[i++]; h->w.ln_b = (const float*)w[i++];
-  h->w.h2 = w[i++]; h->w.h2_b = (const float*)w[i++];
+  h->w.fe1 = W.next(); h->w.fe_b1 = W.next_f32(); h->w.fe2 = W.next(); h->w.fe_b2 = W.next_f32();
+  for (int l = 0; l < d.layers; ++l) { h->w.wl[l] = W.next(); h->w.bl[l] = W.next_f32(); }
+  h->w.h1 = W.next(); h->w.h1_b = W.next_f32(); h->w.ln_w = W.next_f32(); h->w.ln_b = W.next_f32();
+  h->w.h2 = W.next(); h->w.h2_b = W.next_f32();
   h->w.layers = d.layers; h->w.S = d.state_dim; h->w.F = d.force_dim;
   *out = h;
   return VT_OK;

@@ -307,11 +307,10 @@ __global__ __launch_bounds__(64) void marker_disp_kernel(const int* __restrict__
 }  // namespace
 
 // workspace: binary [N][H][W] u8 | labels [N][H][W] i32 | candidates [N][max_cand] | candidate counters [N]
-static size_t al256(size_t b) { return (b + 255) / 256 * 256; }
 size_t vt_marker_workspace_bytes(int N, int H, int W, int max_cand) {
   if (N < 1 || H < 1 || W < 1 || max_cand < 1) return 0;
-  return al256((size_t)N * H * W) + al256((size_t)N * H * W * 4) + al256((size_t)N * max_cand * sizeof(Cand)) + al256((size_t)N * 4) +
-         al256((size_t)N * 256 * 4) + al256((size_t)N * 256);      // + HSR histogram and equalisation table
+  return vt_round256((size_t)N * H * W) + vt_round256((size_t)N * H * W * 4) + vt_round256((size_t)N * max_cand * sizeof(Cand)) + vt_round256((size_t)N * 4) +
+         vt_round256((size_t)N * 256 * 4) + vt_round256((size_t)N * 256);      // + HSR histogram and equalisation table
 }
 
 int vt_marker_detect(const uint8_t* frames, int channels, int mode, int N, int H, int W, double min_area, double max_area, int max_cand,
@@ -326,11 +325,11 @@ int vt_marker_detect(const uint8_t* frames, int channels, int mode, int N, int H
     return vt_fail(VT_ERR_ARG, "vt_marker_detect: bad shape (channels 1|3, H, W >= 5)");
   hipStream_t s = (hipStream_t)stream;
   char* ws = (char*)workspace;
-  uint8_t* binary = (uint8_t*)ws; ws += al256((size_t)N * H * W);
-  int* labels = (int*)ws; ws += al256((size_t)N * H * W * 4);
-  Cand* cand = (Cand*)ws; ws += al256((size_t)N * max_cand * sizeof(Cand));
-  int* ncand = (int*)ws; ws += al256((size_t)N * 4);
-  int* hist = (int*)ws; ws += al256((size_t)N * 256 * 4);
+  uint8_t* binary = (uint8_t*)ws; ws += vt_round256((size_t)N * H * W);
+  int* labels = (int*)ws; ws += vt_round256((size_t)N * H * W * 4);
+  Cand* cand = (Cand*)ws; ws += vt_round256((size_t)N * max_cand * sizeof(Cand));
+  int* ncand = (int*)ws; ws += vt_round256((size_t)N * 4);
+  int* hist = (int*)ws; ws += vt_round256((size_t)N * 256 * 4);
   uint8_t* lut = (uint8_t*)ws;
   const int HW = H * W;
   // cv::getGaussianKernel(11, sigma <= 0): sigma = 0.3*((11-1)*0.5-1)+0.8 = 2.0, float32 taps

@@ -18,18 +18,6 @@
 #include "vt_gemm_route.h"
 #include "../../include/vlatouch.h"
 
-#define CK(x) do { int _r = (x); if (_r) return _r; } while (0)
-static int es(int dt) { return (dt == VT_BF16 || dt == VT_F16) ? 2 : 4; }
-
-static VtGemmParams lin(const void* A, int adt, long lda, const void* W, int cdt, long ldw, const float* b, void* C, int odt, long ldc,
-                        int M, int N, int K, int act) {
-  VtGemmParams p;
-  memset(&p, 0, sizeof(p));
-  p.A = A; p.W = W; p.C = C; p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldw = ldw; p.ldc = ldc;
-  p.bias = b; p.act = act; p.groups = 1; p.splitk = 1; p.a_dtype = adt; p.w_dtype = cdt; p.c_dtype = odt;
-  return p;
-}
-
 // ======================================================================================= DINOv2
 struct DinoLayer {
   const float *ln1_w, *ln1_b, *qkv_b, *proj_b, *ls1, *ln2_w, *ln2_b, *fc1_b, *fc2_b, *ls2;
@@ -51,27 +39,26 @@ int vt_dino_set_range_flag(vt_dino_t h, unsigned* word) {
 }
 
 int vt_dino_create(const vt_dino_desc* desc, const void* const* w, int n, vt_dino_t* out) {
-  if (!desc || !w || !out) return vt_fail(VT_ERR_ARG, "vt_dino_create: null argument");
+  CK(vt_create_args("vt_dino_create", desc, w, out));
   const vt_dino_desc& d = *desc;
   const int hd = d.head_dim ? d.head_dim : 64;
   if (d.layers < 1 || d.layers > 48 || d.hidden % 64 || (hd != 64 && hd != 96 && !(hd == 80 && d.adt != VT_F32)) || (hd == 64 && d.hidden / d.heads != 64) || d.patch != 14 ||
       d.kpad % 16 || d.kpad < 588 || (d.mlp_dim % 16))
     return vt_fail(VT_ERR_ARG, "vt_dino_create: unsupported config (head_dim 64 / 96, or 80 in a 16-bit mode; patch 14)");
-  if (n != vt_dino_num_weights(desc)) return vt_fail(VT_ERR_ARG, "vt_dino_create: expected %d weights, got %d", vt_dino_num_weights(desc), n);
-  for (int k = 0; k < n; ++k) if (!w[k]) return vt_fail(VT_ERR_ARG, "vt_dino_create: weight %d is null", k);
+  VtWeights W;
+  CK(W.open("vt_dino_create", w, n, vt_dino_num_weights(desc)));
   vt_dino_s* h = new (std::nothrow) vt_dino_s();
   if (!h) return vt_fail(-12, "out of host memory");
   h->d = d;
-  int i = 0;
-  h->patch_w = w[i++]; h->patch_b = (const float*)w[i++]; h->cls_pos0 = (const float*)w[i++];
+  h->patch_w = W.next(); h->patch_b = W.next_f32(); h->cls_pos0 = W.next_f32();
   for (int l = 0; l < d.layers; ++l) {
     DinoLayer& L = h->L[l];
-    L.ln1_w = (const float*)w[i++]; L.ln1_b = (const float*)w[i++]; L.qkv_w = w[i++]; L.qkv_b = (const float*)w[i++];
-    L.proj_w = w[i++]; L.proj_b = (const float*)w[i++]; L.ls1 = (const float*)w[i++];
-    L.ln2_w = (const float*)w[i++]; L.ln2_b = (const float*)w[i++]; L.fc1_w = w[i++]; L.fc1_b = (const float*)w[i++];
-    L.fc2_w = w[i++]; L.fc2_b = (const float*)w[i++]; L.ls2 = (const float*)w[i++];
+    L.ln1_w = W.next_f32(); L.ln1_b = W.next_f32(); L.qkv_w = W.next(); L.qkv_b = W.next_f32();
+    L.proj_w = W.next(); L.proj_b = W.next_f32(); L.ls1 = W.next_f32();
+    L.ln2_w = W.next_f32(); L.ln2_b = W.next_f32(); L.fc1_w = W.next(); L.fc1_b = W.next_f32();
+    L.fc2_w = W.next(); L.fc2_b = W.next_f32(); L.ls2 = W.next_f32();
   }
-  h->lnf_w = (const float*)w[i++]; h->lnf_b = (const float*)w[i++];
+  h->lnf_w = W.next_f32(); h->lnf_b = W.next_f32();
   *out = h;
   return VT_OK;
 }
@@ -109,21 +96,20 @@ constexpr int DINO_SPLITK = 4, DINO_SPLIT_ROWS = 1100;
 struct DWs { size_t part, flags, apatch, tok, xn, qkv, att, h1, slab, slab_bytes, total; };
 DWs dcarve(const vt_dino_s* h, int Bt, int res) {
   const vt_dino_desc& d = h->d;
-  const int a = es(d.adt), g = res / d.patch, N = g * g + (d.no_cls ? 0 : 1), D = d.hidden;
+  const int a = vt_dt_bytes(d.adt), g = res / d.patch, N = g * g + (d.no_cls ? 0 : 1), D = d.hidden;
   const int Da = d.heads * (d.head_dim ? d.head_dim : 64), Dm = d.mlp_dim ? d.mlp_dim : 4 * D;
-  DWs w; size_t o = 0;
-  auto take = [&](size_t b) { size_t r = o; o += (b + 255) / 256 * 256; return r; };
-  w.part = take(512 * 4 * 8); w.flags = take(8 * 4 * 8);
-  w.apatch = take((size_t)Bt * g * g * d.kpad * a);
-  w.tok = take((size_t)Bt * N * D * 4);
-  w.xn = take((size_t)Bt * N * D * a);
-  w.qkv = take((size_t)Bt * N * 3 * Da * a);
-  w.att = take((size_t)Bt * N * Da * a);
-  w.h1 = take((size_t)Bt * N * Dm * a * (d.act == VT_ACT_SWIGLU ? 2 : 1));      // SwiGLU: fc1 produces [x1 | x2]
+  DWs w; VtCarver cv;
+  w.part = cv.take(512 * 4 * 8); w.flags = cv.take(8 * 4 * 8);
+  w.apatch = cv.take((size_t)Bt * g * g * d.kpad * a);
+  w.tok = cv.take((size_t)Bt * N * D * 4);
+  w.xn = cv.take((size_t)Bt * N * D * a);
+  w.qkv = cv.take((size_t)Bt * N * 3 * Da * a);
+  w.att = cv.take((size_t)Bt * N * Da * a);
+  w.h1 = cv.take((size_t)Bt * N * Dm * a * (d.act == VT_ACT_SWIGLU ? 2 : 1));      // SwiGLU: fc1 produces [x1 | x2]
   // split-K scratch of fc2 at a few images (batch 1 of the robot loop: 2 x 257 rows): DINO_SPLITK fp32 slabs of [rows][D]
   w.slab_bytes = (size_t)Bt * N <= DINO_SPLIT_ROWS ? (size_t)DINO_SPLITK * Bt * N * D * 4 : 0;
-  w.slab = take(w.slab_bytes);
-  w.total = o;
+  w.slab = cv.take(w.slab_bytes);
+  w.total = cv.o;
   return w;
 }
 }  // namespace
@@ -136,7 +122,7 @@ int vt_dino_forward(vt_dino_t h, const void* const* imgs, int ncams, int is_u8, 
   if (ncams < 1 || ncams > 8 || B < 1 || res < 14) return vt_fail(VT_ERR_ARG, "vt_dino_forward: bad sizes");
   const vt_dino_desc& d = h->d;
   hipStream_t s = (hipStream_t)stream;
-  const int g = res / d.patch, np = g * g, cls = d.no_cls ? 0 : 1, N = np + cls, D = d.hidden, Bt = ncams * B, a = es(d.adt);
+  const int g = res / d.patch, np = g * g, cls = d.no_cls ? 0 : 1, N = np + cls, D = d.hidden, Bt = ncams * B, a = vt_dt_bytes(d.adt);
   const int hd = d.head_dim ? d.head_dim : 64, Da = d.heads * hd, Dm = d.mlp_dim ? d.mlp_dim : 4 * D;
   const int act = d.act ? d.act : VT_ACT_GELU_ERF;
   const float scale = d.attn_scale > 0.f ? d.attn_scale : 1.0f / sqrtf((float)hd);
@@ -153,7 +139,7 @@ int vt_dino_forward(vt_dino_t h, const void* const* imgs, int ncams, int is_u8, 
   }
   // 2. patch-embed GEMM, one group per image, + position embedding (shared residual) -> fp32 tokens rows 1..np
   {
-    VtGemmParams p = lin(ws + w.apatch, d.adt, d.kpad, h->patch_w, d.cdt, d.kpad, h->patch_b, tok + (size_t)cls * D, VT_F32, D, np, D, d.kpad, VT_ACT_NONE);
+    VtGemmParams p = vt_linear(ws + w.apatch, d.adt, d.kpad, h->patch_w, d.cdt, d.kpad, h->patch_b, tok + (size_t)cls * D, VT_F32, D, np, D, d.kpad, VT_ACT_NONE);
     p.groups = Bt; p.a_gs = (long)np * d.kpad; p.w_gs = 0; p.c_gs = (long)N * D; p.bias_gs = 0;
     p.residual = pos_patch; p.ldr = D; p.r_gs = 0;
     CK(vt_wrap(vt_gemm_launch(p, s), "dino patch embed"));
@@ -167,12 +153,12 @@ int vt_dino_forward(vt_dino_t h, const void* const* imgs, int ncams, int is_u8, 
   const bool swiglu = act == VT_ACT_SWIGLU;
   auto ffn = [&](const DinoLayer& L, int rows, long tok_stride) -> int {
     const int N1 = swiglu ? 2 * Dm : Dm;
-    { VtGemmParams p = lin(ws + w.xn, d.adt, D, L.fc1_w, d.cdt, D, L.fc1_b, ws + w.h1, d.adt, N1, rows, N1, D, swiglu ? VT_ACT_NONE : act);
+    { VtGemmParams p = vt_linear(ws + w.xn, d.adt, D, L.fc1_w, d.cdt, D, L.fc1_b, ws + w.h1, d.adt, N1, rows, N1, D, swiglu ? VT_ACT_NONE : act);
       p.Wp = swiglu ? nullptr : L.fc1_wp;
       if (p.Wp && vt_gemm_route(p) == VT_GEMM_PW) p.Wp = nullptr;   // the 160 x 128 weights-in-registers tile is the RDT denoise loop's; ViT GEMMs stay on the persistent tile
       CK(vt_wrap(vt_gemm_launch(p, s), "dino fc1")); }
     if (swiglu) CK(vt_wrap(vt_k_swiglu(ws + w.h1, d.adt, N1, rows, Dm, s, h->range_flag), "dino swiglu gate"));
-    { VtGemmParams p = lin(ws + w.h1, d.adt, N1, L.fc2_w, d.cdt, Dm, L.fc2_b, tok, VT_F32, tok_stride, rows, D, Dm, VT_ACT_NONE);
+    { VtGemmParams p = vt_linear(ws + w.h1, d.adt, N1, L.fc2_w, d.cdt, Dm, L.fc2_b, tok, VT_F32, tok_stride, rows, D, Dm, VT_ACT_NONE);
       p.colscale = L.ls2; p.residual = tok; p.ldr = tok_stride;
       // a few images (2 x 257 rows at batch 1): 108 tiles of 64 x 64 would each walk K = 3072 alone (50 us); DINO_SPLITK slices per tile into fp32
       // slabs + the slab reduction (bias, LayerScale, residual) take 17
@@ -196,10 +182,10 @@ int vt_dino_forward(vt_dino_t h, const void* const* imgs, int ncams, int is_u8, 
     if (cls_only) {
       const long tstride = (long)N * D;                 // CLS row of image b = row b * N of the token matrix
       // K | V of every token (rows Da .. 3 Da of the fused qkv weight) + Q of the CLS rows only
-      { VtGemmParams p = lin(ws + w.xn, d.adt, D, (const char*)L.qkv_w + (size_t)Da * D * es(d.cdt), d.cdt, D, L.qkv_b + Da, ws + w.qkv + (size_t)Da * a, d.adt, 3 * Da,
+      { VtGemmParams p = vt_linear(ws + w.xn, d.adt, D, (const char*)L.qkv_w + (size_t)Da * D * vt_dt_bytes(d.cdt), d.cdt, D, L.qkv_b + Da, ws + w.qkv + (size_t)Da * a, d.adt, 3 * Da,
                              M, 2 * Da, D, VT_ACT_NONE);
         CK(vt_wrap(vt_gemm_launch(p, s), "dino kv (last block)")); }
-      { VtGemmParams p = lin(ws + w.xn, d.adt, tstride, L.qkv_w, d.cdt, D, L.qkv_b, ws + w.qkv, d.adt, (long)N * 3 * Da, Bt, Da, D, VT_ACT_NONE);
+      { VtGemmParams p = vt_linear(ws + w.xn, d.adt, tstride, L.qkv_w, d.cdt, D, L.qkv_b, ws + w.qkv, d.adt, (long)N * 3 * Da, Bt, Da, D, VT_ACT_NONE);
         CK(vt_wrap(vt_gemm_launch(p, s), "dino q (CLS rows)")); }
       { VtAttnParams p;
         memset(&p, 0, sizeof(p));
@@ -208,14 +194,14 @@ int vt_dino_forward(vt_dino_t h, const void* const* imgs, int ncams, int is_u8, 
         p.o_bs = Da; p.o_rs = Da;                         // one output row per image, compact [Bt][Da]
         p.B = Bt; p.H = d.heads; p.Nq = 1; p.Nk = N; p.scale = scale; p.dtype = d.adt; p.hd = hd;
         CK(vt_wrap(vt_attn_launch(p, s), "dino attention (CLS query)")); }
-      { VtGemmParams p = lin(ws + w.att, d.adt, Da, L.proj_w, d.cdt, Da, L.proj_b, tok, VT_F32, tstride, Bt, D, Da, VT_ACT_NONE);
+      { VtGemmParams p = vt_linear(ws + w.att, d.adt, Da, L.proj_w, d.cdt, Da, L.proj_b, tok, VT_F32, tstride, Bt, D, Da, VT_ACT_NONE);
         p.colscale = L.ls1; p.residual = tok; p.ldr = tstride;
         CK(vt_wrap(vt_gemm_launch(p, s), "dino proj (CLS rows)")); }
       CK(vt_k_rownorm(tok, VT_F32, tstride, ws + w.xn, d.adt, D, L.ln2_w, L.ln2_b, Bt, D, d.eps, VT_NORM_LAYER, s));
       CK(ffn(L, Bt, tstride));
       continue;
     }
-    { VtGemmParams p = lin(ws + w.xn, d.adt, D, L.qkv_w, d.cdt, D, L.qkv_b, ws + w.qkv, d.adt, 3 * Da, M, 3 * Da, D, VT_ACT_NONE);
+    { VtGemmParams p = vt_linear(ws + w.xn, d.adt, D, L.qkv_w, d.cdt, D, L.qkv_b, ws + w.qkv, d.adt, 3 * Da, M, 3 * Da, D, VT_ACT_NONE);
       CK(vt_wrap(vt_gemm_launch(p, s), "dino qkv")); }
     { VtAttnParams p;
       memset(&p, 0, sizeof(p));
@@ -224,7 +210,7 @@ int vt_dino_forward(vt_dino_t h, const void* const* imgs, int ncams, int is_u8, 
       p.o_bs = (long)N * Da; p.o_rs = Da;
       p.B = Bt; p.H = d.heads; p.Nq = N; p.Nk = N; p.scale = scale; p.dtype = d.adt; p.hd = hd;
       CK(vt_wrap(vt_attn_launch(p, s), "dino attention")); }
-    { VtGemmParams p = lin(ws + w.att, d.adt, Da, L.proj_w, d.cdt, Da, L.proj_b, tok, VT_F32, D, M, D, Da, VT_ACT_NONE);
+    { VtGemmParams p = vt_linear(ws + w.att, d.adt, Da, L.proj_w, d.cdt, Da, L.proj_b, tok, VT_F32, D, M, D, Da, VT_ACT_NONE);
       p.colscale = L.ls1; p.residual = tok; p.ldr = D;
       CK(vt_wrap(vt_gemm_launch(p, s), "dino proj")); }
     CK(vt_k_rownorm(tok, VT_F32, D, ws + w.xn, d.adt, D, L.ln2_w, L.ln2_b, M, D, d.eps, VT_NORM_LAYER, s));
@@ -247,8 +233,8 @@ int vt_mlp(const void* x, long ldx, int B, int n_layers, const int* dims, const 
   const void* cur = x; long ld = ldx;
   for (int i = 0; i < n_layers; ++i) {
     const bool last = i == n_layers - 1;
-    void* dst = last ? y : (char*)tmp + (size_t)(i & 1) * B * mx * es(adt);
-    VtGemmParams p = lin(cur, adt, ld, W[i], cdt, dims[i], b[i], dst, last ? ydt : adt, last ? ldy : dims[i + 1], B, dims[i + 1], dims[i],
+    void* dst = last ? y : (char*)tmp + (size_t)(i & 1) * B * mx * vt_dt_bytes(adt);
+    VtGemmParams p = vt_linear(cur, adt, ld, W[i], cdt, dims[i], b[i], dst, last ? ydt : adt, last ? ldy : dims[i + 1], B, dims[i + 1], dims[i],
                          last ? VT_ACT_NONE : act);
     CK(vt_wrap(vt_gemm_launch(p, s), "vt_mlp layer"));
     cur = dst; ld = dims[i + 1];
@@ -259,7 +245,7 @@ int vt_mlp(const void* x, long ldx, int B, int n_layers, const int* dims, const 
 int vt_concat_obs(const float* cls1, const float* cls2, int dv, const float* state, int sdim, const float* forces, int fdim,
                   void* out, int odt, long ldo, int B, vt_stream_t stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (hipMemsetAsync(out, 0, (size_t)B * ldo * es(odt), s) != hipSuccess) return vt_fail(VT_ERR_LAUNCH, "memset");
+  if (hipMemsetAsync(out, 0, (size_t)B * ldo * vt_dt_bytes(odt), s) != hipSuccess) return vt_fail(VT_ERR_LAUNCH, "memset");
   CK(vt_k_place_cols(cls1, VT_F32, dv, out, odt, ldo, 0, B, dv, s));
   CK(vt_k_place_cols(cls2, VT_F32, dv, out, odt, ldo, dv, B, dv, s));
   CK(vt_k_place_cols(state, VT_F32, sdim, out, odt, ldo, 2 * dv, B, sdim, s));

@@ -27,9 +27,6 @@
 #include "vt_gemm_route.h"
 #include "../../include/vlatouch.h"
 
-#define CK(x) do { int _r = (x); if (_r) return _r; } while (0)
-static int es(int dt) { return dt == VT_F32 ? 4 : 2; }
-static bool is16(int dt) { return dt == VT_BF16 || dt == VT_F16; }
 // element i of a buffer of type dt (VT_F32 / VT_BF16 / VT_F16) as float, and back; rnd16 = round to that type's grid
 __device__ __forceinline__ float ldx(const void* p, long i, int dt) {
   return dt == VT_F32 ? ((const float*)p)[i] : dt == VT_F16 ? h2f(((const half_t*)p)[i]) : bf2f(((const bf16_t*)p)[i]);
@@ -48,13 +45,11 @@ struct Blk {
 };
 struct Adaptor { int n; const void* w[4]; const float* b[4]; int kin; const void* wp[4]; };
 
+// a Linear's block (vt_gemm.h) with its fragment-packed second copy of W, where the handle has one
 VtGemmParams lin(const void* A, int adt, long lda, const void* W, int cdt, long ldw, const float* b, void* C, int odt, long ldc, int M, int N,
                  int K, int act, const void* Wp = nullptr) {
-  VtGemmParams p;
-  memset(&p, 0, sizeof(p));
+  VtGemmParams p = vt_linear(A, adt, lda, W, cdt, ldw, b, C, odt, ldc, M, N, K, act);
   p.Wp = Wp;
-  p.A = A; p.W = W; p.C = C; p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldw = ldw; p.ldc = ldc;
-  p.bias = b; p.act = act; p.groups = 1; p.splitk = 1; p.a_dtype = adt; p.w_dtype = cdt; p.c_dtype = odt;
   return p;
 }
 }  // namespace
@@ -78,32 +73,30 @@ struct vt_rdt_s {
 int vt_rdt_num_weights(const vt_rdt_desc* d) { return 11 + 21 * d->depth + 5 + 2 * (d->n_lang + d->n_img + d->n_state); }
 
 int vt_rdt_create(const vt_rdt_desc* desc, const void* const* w, int n, vt_rdt_t* out) {
-  if (!desc || !w || !out) return vt_fail(VT_ERR_ARG, "vt_rdt_create: null argument");
+  CK(vt_create_args("vt_rdt_create", desc, w, out));
   const vt_rdt_desc& d = *desc;
   if (d.hidden % 64 || d.hidden / d.heads != 64 || d.depth < 1 || d.depth > 64 || d.horizon < 1 || d.out_dim < 1)
     return vt_fail(VT_ERR_ARG, "vt_rdt_create: unsupported config (head_dim must be 64)");
   if (d.n_lang < 1 || d.n_lang > 4 || d.n_img < 1 || d.n_img > 4 || d.n_state < 1 || d.n_state > 4) return vt_fail(VT_ERR_ARG, "vt_rdt_create: adaptor depth 1..4");
   if (d.lang_dim % 16 || d.img_dim % 16 || (2 * d.state_dim) % 16) return vt_fail(VT_ERR_ARG, "vt_rdt_create: token dims must be multiples of 16");
-  if (d.cdt != d.adt || (d.cdt != VT_F32 && !is16(d.cdt))) return vt_fail(VT_ERR_ARG, "vt_rdt_create: cdt == adt in {fp32, bf16, fp16}");
-  if (n != vt_rdt_num_weights(desc)) return vt_fail(VT_ERR_ARG, "vt_rdt_create: expected %d weights, got %d", vt_rdt_num_weights(desc), n);
-  for (int k = 0; k < n; ++k) if (!w[k]) return vt_fail(VT_ERR_ARG, "vt_rdt_create: weight %d is null", k);
+  if (d.cdt != d.adt || (d.cdt != VT_F32 && !vt_is16(d.cdt))) return vt_fail(VT_ERR_ARG, "vt_rdt_create: cdt == adt in {fp32, bf16, fp16}");
+  VtWeights W;
+  CK(W.open("vt_rdt_create", w, n, vt_rdt_num_weights(desc)));
   vt_rdt_s* h = new (std::nothrow) vt_rdt_s();
   if (!h) return vt_fail(-12, "out of host memory");
   h->d = d;
   h->io_dt = d.adt == VT_F16 ? VT_F16 : VT_BF16;
-  int i = 0;
-  auto F = [&]() { return (const float*)w[i++]; };
-  h->t_w1 = w[i++]; h->t_b1 = F(); h->t_w2 = w[i++]; h->t_b2 = F();
-  h->f_w1 = w[i++]; h->f_b1 = F(); h->f_w2 = w[i++]; h->f_b2 = F();
-  h->x_pos = F(); h->lang_pos = w[i++]; h->img_pos = w[i++];
+  h->t_w1 = W.next(); h->t_b1 = W.next_f32(); h->t_w2 = W.next(); h->t_b2 = W.next_f32();
+  h->f_w1 = W.next(); h->f_b1 = W.next_f32(); h->f_w2 = W.next(); h->f_b2 = W.next_f32();
+  h->x_pos = W.next_f32(); h->lang_pos = W.next(); h->img_pos = W.next();
   for (int l = 0; l < d.depth; ++l) {
     Blk& b = h->blk[l];
-    b.norm1 = F(); b.qkv_w = w[i++]; b.qkv_b = F(); b.qn = F(); b.kn = F(); b.proj_w = w[i++]; b.proj_b = F();
-    b.norm2 = F(); b.cq_w = w[i++]; b.cq_b = F(); b.ckv_w = w[i++]; b.ckv_b = F(); b.cqn = F(); b.ckn = F(); b.cproj_w = w[i++]; b.cproj_b = F();
-    b.norm3 = F(); b.fc1_w = w[i++]; b.fc1_b = F(); b.fc2_w = w[i++]; b.fc2_b = F();
+    b.norm1 = W.next_f32(); b.qkv_w = W.next(); b.qkv_b = W.next_f32(); b.qn = W.next_f32(); b.kn = W.next_f32(); b.proj_w = W.next(); b.proj_b = W.next_f32();
+    b.norm2 = W.next_f32(); b.cq_w = W.next(); b.cq_b = W.next_f32(); b.ckv_w = W.next(); b.ckv_b = W.next_f32(); b.cqn = W.next_f32(); b.ckn = W.next_f32(); b.cproj_w = W.next(); b.cproj_b = W.next_f32();
+    b.norm3 = W.next_f32(); b.fc1_w = W.next(); b.fc1_b = W.next_f32(); b.fc2_w = W.next(); b.fc2_b = W.next_f32();
   }
-  h->normf = F(); h->ffc1_w = w[i++]; h->ffc1_b = F(); h->ffc2_w = w[i++]; h->ffc2_b = F();
-  auto rd = [&](Adaptor& a, int nl, int kin) { a.n = nl; a.kin = kin; for (int k = 0; k < nl; ++k) { a.w[k] = w[i++]; a.b[k] = F(); } };
+  h->normf = W.next_f32(); h->ffc1_w = W.next(); h->ffc1_b = W.next_f32(); h->ffc2_w = W.next(); h->ffc2_b = W.next_f32();
+  auto rd = [&](Adaptor& a, int nl, int kin) { a.n = nl; a.kin = kin; for (int k = 0; k < nl; ++k) { a.w[k] = W.next(); a.b[k] = W.next_f32(); } };
   rd(h->lang, d.n_lang, d.lang_dim); rd(h->img, d.n_img, d.img_dim); rd(h->state, d.n_state, 2 * d.state_dim);
   *out = h;
   return VT_OK;
@@ -148,7 +141,7 @@ int vt_rdt_set_state_precision(vt_rdt_t h, int fp32_state) {
 // on `stream`.  Returns 0 bytes when the configuration has no use for them (fp32 mode, hidden size not a multiple of 512).
 static bool pk_ok(int N, int K) { return N % 64 == 0 && K % 256 == 0; }      // what vt_gemm_pws.hip / vt_gemm_pw.hip can take
 size_t vt_rdt_packed_bytes(vt_rdt_t h) {
-  if (!h || !is16(h->d.cdt) || h->d.hidden % 512) return 0;
+  if (!h || !vt_is16(h->d.cdt) || h->d.hidden % 512) return 0;
   const size_t D = h->d.hidden, DD = D * D * 2;
   size_t n = (size_t)h->d.depth * 8 * DD + DD;                                // blocks + final fc1
   if (pk_ok(h->d.out_dim, (int)D)) n += (size_t)h->d.out_dim * D * 2;           // final fc2
@@ -200,43 +193,42 @@ VtGemmParams cond_kv_params(const vt_rdt_desc& d, int R) {
 }
 RWs rcarve(const vt_rdt_s* h, int B, int L) {
   const vt_rdt_desc& d = h->d;
-  const int a = es(d.adt), D = d.hidden, N = d.horizon + 3, Li = d.img_len;
-  RWs w; size_t o = 0;
-  auto take = [&](size_t b) { size_t r = o; o += (b + 255) / 256 * 256; return r; };
-  w.lang_c = take((size_t)B * L * D * a);
-  w.img_c = take((size_t)B * Li * D * a);
+  const int a = vt_dt_bytes(d.adt), D = d.hidden, N = d.horizon + 3, Li = d.img_len;
+  RWs w; VtCarver cv;
+  w.lang_c = cv.take((size_t)B * L * D * a);
+  w.img_c = cv.take((size_t)B * Li * D * a);
   const size_t rows = (size_t)B * (Li > L ? Li : L);
-  w.tmpA = take(rows * D * a); w.tmpB = take(rows * D * a);
+  w.tmpA = cv.take(rows * D * a); w.tmpB = cv.take(rows * D * a);
   // row-major [R][2D] scratch of the K | V product of a condition that falls off the large-GEMM path (few rows: the language tokens at batch 1..3,
   // every condition of the tiny test configs) — its own buffer: 2 R D elements do not fit tmpA when 2 R > max(Li, L) * B
   { size_t rs = 0;
-    if (is16(d.adt)) for (int R : {B * L, B * Li}) if (!vt_gemm_can_fuse_headnorm(cond_kv_params(d, R)) && (size_t)R > rs) rs = (size_t)R;
-    w.kv_small = take(rs * 2 * D * a); }
-  w.state_tok = take((size_t)B * D * a); w.freq_emb = take((size_t)B * D * a); w.t_emb = take((size_t)B * D * a);
-  w.emb_tmp = take((size_t)B * D * a); w.sin = take((size_t)B * 256 * a);
+    if (vt_is16(d.adt)) for (int R : {B * L, B * Li}) if (!vt_gemm_can_fuse_headnorm(cond_kv_params(d, R)) && (size_t)R > rs) rs = (size_t)R;
+    w.kv_small = cv.take(rs * 2 * D * a); }
+  w.state_tok = cv.take((size_t)B * D * a); w.freq_emb = cv.take((size_t)B * D * a); w.t_emb = cv.take((size_t)B * D * a);
+  w.emb_tmp = cv.take((size_t)B * D * a); w.sin = cv.take((size_t)B * 256 * a);
   const int n_lang_blk = (d.depth + 1) / 2, n_img_blk = d.depth / 2;
   // per block: fp32 mode [B*L][2D] (K | V interleaved per token); bf16 mode K [B*L][D] followed by Vt [B][H][64][Lpad]
   // bf16: per-head tile stream of 16-KiB [K | Vt] tiles over the B*L rows (vt_attn_kvt.hip); fp32: row-major [B*L][2D]
-  w.kv_lang_blk = ((size_t)D * 2 * lpad64(B * L) * a + 255) / 256 * 256;
-  w.kv_img_blk = ((size_t)D * 2 * lpad64(B * Li) * a + 255) / 256 * 256;
-  w.kv_lang = take(w.kv_lang_blk * n_lang_blk);
-  w.kv_img = take(w.kv_img_blk * n_img_blk);
+  w.kv_lang_blk = vt_round256((size_t)D * 2 * lpad64(B * L) * a);
+  w.kv_img_blk = vt_round256((size_t)D * 2 * lpad64(B * Li) * a);
+  w.kv_lang = cv.take(w.kv_lang_blk * n_lang_blk);
+  w.kv_img = cv.take(w.kv_img_blk * n_img_blk);
   const size_t M = (size_t)B * N;
-  w.rs_part = take(M * (2 * (D / 128) + 4) * 8);      // fused RMSNorm hand-off: (sum of squares, sum) per (row, 64 columns)
-  w.x = take(M * D * 4); w.xn = take(M * D * a); w.qkv = take(M * 3 * D * a); w.q = take(M * D * a); w.att = take(M * D * a); w.hid = take(M * D * a);
-  w.sa_in = take((size_t)B * d.horizon * 2 * d.state_dim * a);
-  w.sa_tmpA = take((size_t)B * d.horizon * D * a); w.sa_tmpB = take((size_t)B * d.horizon * D * a);
-  w.out_tok = take(M * d.out_dim * 4);                 // (sized for the fp32 form of vt_rdt_sample's solver loop)
-  w.x0_cur = take((size_t)B * d.horizon * d.out_dim * 4); w.x0_prev = take((size_t)B * d.horizon * d.out_dim * 4);
-  w.noisy = take((size_t)B * d.horizon * d.out_dim * 4); w.noisy_a = take((size_t)B * d.horizon * d.out_dim * a);
+  w.rs_part = cv.take(M * (2 * (D / 128) + 4) * 8);      // fused RMSNorm hand-off: (sum of squares, sum) per (row, 64 columns)
+  w.x = cv.take(M * D * 4); w.xn = cv.take(M * D * a); w.qkv = cv.take(M * 3 * D * a); w.q = cv.take(M * D * a); w.att = cv.take(M * D * a); w.hid = cv.take(M * D * a);
+  w.sa_in = cv.take((size_t)B * d.horizon * 2 * d.state_dim * a);
+  w.sa_tmpA = cv.take((size_t)B * d.horizon * D * a); w.sa_tmpB = cv.take((size_t)B * d.horizon * D * a);
+  w.out_tok = cv.take(M * d.out_dim * 4);                 // (sized for the fp32 form of vt_rdt_sample's solver loop)
+  w.x0_cur = cv.take((size_t)B * d.horizon * d.out_dim * 4); w.x0_prev = cv.take((size_t)B * d.horizon * d.out_dim * 4);
+  w.noisy = cv.take((size_t)B * d.horizon * d.out_dim * 4); w.noisy_a = cv.take((size_t)B * d.horizon * d.out_dim * a);
   w.slab_bytes = M <= 512 ? (size_t)RDT_MAX_SPLITK * M * 3 * D * 4 : 0;
-  w.slab = take(w.slab_bytes);
-  w.sk_cnt = take(RDT_SK_CNT * sizeof(int));    // ticket counters of the small-M tile (vt_gemm_pws.hip), zeroed once per call
+  w.slab = cv.take(w.slab_bytes);
+  w.sk_cnt = cv.take(RDT_SK_CNT * sizeof(int));    // ticket counters of the small-M tile (vt_gemm_pws.hip), zeroed once per call
   // cached cross-attention: B*H blocks stream a sample's whole key range each; below ~512 blocks split the range (flash-decoding)
   w.attn_parts = 1;
   { const int bh = B * d.heads; if (bh < 512 && N <= 128) { w.attn_parts = 512 / bh; if (w.attn_parts > 16) w.attn_parts = 16; if (w.attn_parts < 1) w.attn_parts = 1; } }
-  w.attn_part = take(vt_attn_kvt_part_bytes(B, d.heads, N, w.attn_parts));
-  w.total = o;
+  w.attn_part = cv.take(vt_attn_kvt_part_bytes(B, d.heads, N, w.attn_parts));
+  w.total = cv.o;
   return w;
 }
 
@@ -381,7 +373,7 @@ int cache_cond(RCtx& c) {
     const int Lc = lang ? c.L : d.img_len;
     char* kv = lang ? c.ws + c.w.kv_lang + (size_t)(l / 2) * c.w.kv_lang_blk : c.ws + c.w.kv_img + (size_t)(l / 2) * c.w.kv_img_blk;
     const void* src = lang ? c.ws + c.w.lang_c : c.ws + c.w.img_c;
-    if (is16(d.adt)) {
+    if (vt_is16(d.adt)) {
       // 16-bit: K (k_norm fused) and V go straight from the GEMM epilogues into the tile stream when the projection takes the
       // large-GEMM path; small shapes go row-major through tmpA / tmpB and the retile kernels.
       const int T = lpad64(c.B * Lc) / 64;
@@ -418,7 +410,7 @@ int cross_attn(RCtx& c, int l, const uint8_t* lang_mask, int N) {
   const bool lang = (l % 2) == 0;
   const int Lc = lang ? c.L : d.img_len;
   const char* kv = lang ? c.ws + c.w.kv_lang + (size_t)(l / 2) * c.w.kv_lang_blk : c.ws + c.w.kv_img + (size_t)(l / 2) * c.w.kv_img_blk;
-  if (is16(d.adt)) {
+  if (vt_is16(d.adt)) {
     VtAttnKvtParams p;
     memset(&p, 0, sizeof(p));
     p.Q = c.ws + c.w.q; p.KV = kv; p.O = c.ws + c.w.att;
@@ -618,7 +610,7 @@ inline dim3 g1(long n) { return dim3((unsigned)((n + 255) / 256)); }
 int make_rctx(RCtx& c, vt_rdt_t h, int B, int L, void* ws, vt_stream_t s) {
   if (!h || !ws) return vt_fail(VT_ERR_ARG, "rdt: null handle/workspace");
   if (B < 1 || L < 1 || L > h->d.max_lang_len) return vt_fail(VT_ERR_ARG, "rdt: bad batch / language length %d (max %d)", L, h->d.max_lang_len);
-  c.h = h; c.B = B; c.L = L; c.ws = (char*)ws; c.w = rcarve(h, B, L); c.s = (hipStream_t)s; c.a = es(h->d.adt);
+  c.h = h; c.B = B; c.L = L; c.ws = (char*)ws; c.w = rcarve(h, B, L); c.s = (hipStream_t)s; c.a = vt_dt_bytes(h->d.adt);
   return VT_OK;
 }
 }  // namespace
@@ -648,7 +640,7 @@ int vt_rdt_forward(vt_rdt_t h, const void* x_tokens, const float* freq, const fl
   CK(vt_check_launch());
   CK(run_blocks(c, lang_mask));
   hipLaunchKernelGGL(take_actions_kernel, g1((long)B * d.horizon * d.out_dim), dim3(256), 0, c.s, (const void*)(c.ws + c.w.out_tok), out, B, N, d.horizon,
-                     d.out_dim, is16(dt) ? 1 : 0, dt, h->range_flag);
+                     d.out_dim, vt_is16(dt) ? 1 : 0, dt, h->range_flag);
   return vt_check_launch();
 }
 
@@ -664,7 +656,7 @@ int vt_rdt_sample(vt_rdt_t h, const void* lang_tokens, const uint8_t* lang_mask,
     return vt_fail(VT_ERR_ARG, "vt_rdt_sample: null argument");
   const vt_rdt_desc& d = h->d;
   const int D = d.hidden, N = d.horizon + 3, Hh = d.horizon, S = d.state_dim, dt = d.adt, a = c.a;
-  const bool bf = is16(dt);                       // a 16-bit mode (bf16 or IEEE fp16 activations)
+  const bool bf = vt_is16(dt);                       // a 16-bit mode (bf16 or IEEE fp16 activations)
   if (d.out_dim != S) return vt_fail(VT_ERR_ARG, "vt_rdt_sample: action_dim must equal state_token_dim");
   hipStream_t s = c.s;
   if (hipMemsetAsync(c.ws + c.w.sk_cnt, 0, RDT_SK_CNT * sizeof(int), s) != hipSuccess) return vt_fail(VT_ERR_LAUNCH, "ticket counters");

@@ -20,8 +20,6 @@
 #include "vt_host.h"
 #include "../../include/vlatouch.h"
 
-#define CK(x) do { int _r = (x); if (_r) return _r; } while (0)
-
 namespace {
 
 constexpr int T5_MAX_L = 1024;
@@ -226,20 +224,10 @@ struct vt_t5_s {
   std::vector<T5Layer> L;
 };
 
-static int es(int dt) { return dt == VT_BF16 ? 2 : 4; }
-
-static VtGemmParams t5_lin(const void* A, int adt, long lda, const void* W, int cdt, void* C, int odt, long ldc, int M, int N, int K) {
-  VtGemmParams p;
-  memset(&p, 0, sizeof(p));
-  p.A = A; p.W = W; p.C = C; p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldw = K; p.ldc = ldc;
-  p.groups = 1; p.splitk = 1; p.a_dtype = adt; p.w_dtype = cdt; p.c_dtype = odt;
-  return p;
-}
-
 int vt_t5_num_weights(const vt_t5_desc* d) { return d ? 2 + 6 * d->layers + 1 : -1; }
 
 int vt_t5_create(const vt_t5_desc* desc, const void* const* w, int n, vt_t5_t* out) {
-  if (!desc || !w || !out) return vt_fail(VT_ERR_ARG, "vt_t5_create: null argument");
+  CK(vt_create_args("vt_t5_create", desc, w, out));
   const vt_t5_desc& d = *desc;
   if (d.d_kv != 64) return vt_fail(VT_ERR_UNSUPPORTED, "vt_t5_create: d_kv must be 64 (got %d)", d.d_kv);
   if (!((d.cdt == VT_F32 && d.adt == VT_F32) || (d.cdt == VT_BF16 && d.adt == VT_BF16)))
@@ -247,19 +235,18 @@ int vt_t5_create(const vt_t5_desc* desc, const void* const* w, int n, vt_t5_t* o
   if (d.layers < 1 || d.heads < 1 || d.vocab < 1 || d.d_model < 64 || d.d_model % 64 || d.d_model > 4096 || d.d_ff < 64 || d.d_ff % 64 ||
       d.num_buckets < 1 || d.num_buckets > 127 || d.max_distance < 1 || !(d.eps > 0.f))
     return vt_fail(VT_ERR_ARG, "vt_t5_create: unsupported config (d_model, d_ff multiples of 64, d_model <= 4096, 1 <= num_buckets <= 127)");
-  if (n != vt_t5_num_weights(desc)) return vt_fail(VT_ERR_ARG, "vt_t5_create: expected %d weights, got %d", vt_t5_num_weights(desc), n);
-  for (int k = 0; k < n; ++k) if (!w[k]) return vt_fail(VT_ERR_ARG, "vt_t5_create: weight %d is null", k);
+  VtWeights W;
+  CK(W.open("vt_t5_create", w, n, vt_t5_num_weights(desc)));
   vt_t5_s* h = new (std::nothrow) vt_t5_s();
   if (!h) return vt_fail(-12, "out of host memory");
   h->d = d;
   h->L.resize(d.layers);
-  int i = 0;
-  h->shared = w[i++]; h->rel_bias = (const float*)w[i++];
+  h->shared = W.next(); h->rel_bias = W.next_f32();
   for (auto& L : h->L) {
-    L.ln1 = (const float*)w[i++]; L.qkv_w = w[i++]; L.o_w = w[i++];
-    L.ln2 = (const float*)w[i++]; L.wi_w = w[i++]; L.wo_w = w[i++];
+    L.ln1 = W.next_f32(); L.qkv_w = W.next(); L.o_w = W.next();
+    L.ln2 = W.next_f32(); L.wi_w = W.next(); L.wo_w = W.next();
   }
-  h->final_ln = (const float*)w[i++];
+  h->final_ln = W.next_f32();
   *out = h;
   return VT_OK;
 }
@@ -269,17 +256,16 @@ namespace {
 struct TWs { size_t ids, mask, tok, xn, qkv, att, g, hf, total; };
 TWs t5_carve(const vt_t5_s* h, int B, int L) {
   const vt_t5_desc& d = h->d;
-  const size_t M = (size_t)B * L, a = es(d.adt), I = (size_t)d.heads * d.d_kv;
-  TWs w; size_t o = 0;
-  auto take = [&](size_t b) { size_t r = o; o += (b + 255) / 256 * 256; return r; };
-  w.ids = take(M * 4); w.mask = take(M);
-  w.tok = take(M * d.d_model * 4);
-  w.xn = take(M * d.d_model * a);
-  w.qkv = take(M * 3 * I * a);
-  w.att = take(M * I * a);
-  w.g = take(M * 2 * d.d_ff * a);
-  w.hf = take(M * d.d_ff * a);
-  w.total = o;
+  const size_t M = (size_t)B * L, a = vt_dt_bytes(d.adt), I = (size_t)d.heads * d.d_kv;
+  TWs w; VtCarver cv;
+  w.ids = cv.take(M * 4); w.mask = cv.take(M);
+  w.tok = cv.take(M * d.d_model * 4);
+  w.xn = cv.take(M * d.d_model * a);
+  w.qkv = cv.take(M * 3 * I * a);
+  w.att = cv.take(M * I * a);
+  w.g = cv.take(M * 2 * d.d_ff * a);
+  w.hf = cv.take(M * d.d_ff * a);
+  w.total = cv.o;
   return w;
 }
 }  // namespace
@@ -309,6 +295,8 @@ int vt_t5_forward(vt_t5_t h, const int32_t* ids, const uint8_t* mask, int B, int
   if (hipMemcpyAsync(ws + w.ids, ids, (size_t)M * 4, hipMemcpyHostToDevice, s) != hipSuccess) return vt_fail(VT_ERR_LAUNCH, "vt_t5_forward: id upload");
   if (mask && hipMemcpyAsync(ws + w.mask, mask, (size_t)M, hipMemcpyHostToDevice, s) != hipSuccess) return vt_fail(VT_ERR_LAUNCH, "vt_t5_forward: mask upload");
   float* tok = (float*)(ws + w.tok);
+  // the typed kernels (gather, attention, GEGLU gate) are chosen by hand between the two types `create` admits: DISPATCH_T (vt_common.h) would also
+  // instantiate them for half_t, which no T5 handle can ask for
   if (cdt == VT_BF16) hipLaunchKernelGGL((t5_gather_kernel<bf16_t>), g1((long)M * D / 4), dim3(256), 0, s, (const int*)(ws + w.ids), (const bf16_t*)h->shared, tok, (long)M, D, d.vocab);
   else hipLaunchKernelGGL((t5_gather_kernel<float>), g1((long)M * D / 4), dim3(256), 0, s, (const int*)(ws + w.ids), (const float*)h->shared, tok, (long)M, D, d.vocab);
   CK(vt_wrap(vt_check_launch(), "t5 token gather"));
@@ -318,19 +306,19 @@ int vt_t5_forward(vt_t5_t h, const int32_t* ids, const uint8_t* mask, int B, int
   ap.B = B; ap.H = d.heads; ap.L = L; ap.inner = I; ap.num_buckets = d.num_buckets;
   for (const T5Layer& Ly : h->L) {
     CK(vt_wrap(vt_k_rownorm(tok, VT_F32, D, ws + w.xn, adt, D, Ly.ln1, nullptr, M, D, d.eps, VT_NORM_RMS_MEANSQ, s), "t5 rms1"));
-    { VtGemmParams p = t5_lin(ws + w.xn, adt, D, Ly.qkv_w, cdt, ws + w.qkv, adt, 3 * I, M, 3 * I, D);
+    { VtGemmParams p = vt_linear(ws + w.xn, adt, D, Ly.qkv_w, cdt, D, nullptr, ws + w.qkv, adt, 3 * I, M, 3 * I, D, VT_ACT_NONE);
       CK(vt_wrap(vt_gemm_launch(p, s), "t5 qkv")); }
     CK(vt_wrap(adt == VT_BF16 ? t5_attn_launch<bf16_t>(ap, s) : t5_attn_launch<float>(ap, s), "t5 attention"));
-    { VtGemmParams p = t5_lin(ws + w.att, adt, I, Ly.o_w, cdt, tok, VT_F32, D, M, D, I);
+    { VtGemmParams p = vt_linear(ws + w.att, adt, I, Ly.o_w, cdt, I, nullptr, tok, VT_F32, D, M, D, I, VT_ACT_NONE);
       p.residual = tok; p.ldr = D;
       CK(vt_wrap(vt_gemm_launch(p, s), "t5 o")); }
     CK(vt_wrap(vt_k_rownorm(tok, VT_F32, D, ws + w.xn, adt, D, Ly.ln2, nullptr, M, D, d.eps, VT_NORM_RMS_MEANSQ, s), "t5 rms2"));
-    { VtGemmParams p = t5_lin(ws + w.xn, adt, D, Ly.wi_w, cdt, ws + w.g, adt, 2 * F, M, 2 * F, D);
+    { VtGemmParams p = vt_linear(ws + w.xn, adt, D, Ly.wi_w, cdt, D, nullptr, ws + w.g, adt, 2 * F, M, 2 * F, D, VT_ACT_NONE);
       CK(vt_wrap(vt_gemm_launch(p, s), "t5 wi")); }
     if (adt == VT_BF16) hipLaunchKernelGGL((t5_geglu_kernel<bf16_t>), g1((long)M * F / 8), dim3(256), 0, s, (const bf16_t*)(ws + w.g), (long)2 * F, (bf16_t*)(ws + w.hf), (long)F, (long)M, F);
     else hipLaunchKernelGGL((t5_geglu_kernel<float>), g1((long)M * F / 4), dim3(256), 0, s, (const float*)(ws + w.g), (long)2 * F, (float*)(ws + w.hf), (long)F, (long)M, F);
     CK(vt_wrap(vt_check_launch(), "t5 geglu gate"));
-    { VtGemmParams p = t5_lin(ws + w.hf, adt, F, Ly.wo_w, cdt, tok, VT_F32, D, M, D, F);
+    { VtGemmParams p = vt_linear(ws + w.hf, adt, F, Ly.wo_w, cdt, F, nullptr, tok, VT_F32, D, M, D, F, VT_ACT_NONE);
       p.residual = tok; p.ldr = D;
       CK(vt_wrap(vt_gemm_launch(p, s), "t5 wo")); }
   }

@@ -30,27 +30,25 @@ struct View { char* p; long ld; long gs; };   // element strides; p is a byte po
 
 }  // namespace
 
-static int es(int dt) { return dt == VT_BF16 ? 2 : 4; }
-
 int vt_unet_num_weights(const vt_unet_desc* d) {
   const int L = d->n_levels;
   return 6 + (2 * L + 2 + 2 * (L - 1)) * 10 + (L - 1) * 2 + (L - 1) * 3 + 6;
 }
 
 int vt_unet_create(const vt_unet_desc* desc, const void* const* w, int n, vt_unet_t* out) {
-  if (!desc || !w || !out) return vt_fail(VT_ERR_ARG, "vt_unet_create: null argument");
+  CK(vt_create_args("vt_unet_create", desc, w, out));
   const vt_unet_desc& d = *desc;
   if (d.nets < 1 || d.nets > 2 || d.n_levels < 2 || d.n_levels > 4 || d.input_pad % 16 || d.input_pad < d.input_dim)
     return vt_fail(VT_ERR_ARG, "vt_unet_create: bad descriptor");
-  if (n != vt_unet_num_weights(desc)) return vt_fail(VT_ERR_ARG, "vt_unet_create: expected %d weight pointers, got %d", vt_unet_num_weights(desc), n);
+  VtWeights W;      // (a resblock that keeps its width has null residual-conv slots)
+  CK(W.open("vt_unet_create", w, n, vt_unet_num_weights(desc), "weight pointers", true));
   for (int l = 0; l < d.n_levels; ++l)
     if (d.dims[l] % (8 * d.n_groups) || d.dims[l] % 16) return vt_fail(VT_ERR_ARG, "vt_unet_create: dims must be multiples of 16 and of 8*n_groups");
   vt_unet_s* h = new (std::nothrow) vt_unet_s();
   if (!h) return vt_fail(-12, "out of host memory");
   h->d = d;
-  int i = 0;
-  h->step_w1 = w[i++]; h->step_b1 = (const float*)w[i++]; h->step_w2 = w[i++]; h->step_b2 = (const float*)w[i++];
-  h->film_w = w[i++]; h->film_b = (const float*)w[i++];
+  h->step_w1 = W.next(); h->step_b1 = W.next_f32(); h->step_w2 = W.next(); h->step_b2 = W.next_f32();
+  h->film_w = W.next(); h->film_b = W.next_f32();
   const int L = d.n_levels;
   int nrb = 0;
   long F = 0;
@@ -58,9 +56,9 @@ int vt_unet_create(const vt_unet_desc* desc, const void* const* w, int n, vt_une
   auto add = [&](int cin, int cout) {
     ResBlk& r = h->rb[nrb++];
     r.cin = cin; r.cin_pad = (cin + 15) / 16 * 16; r.cout = cout;
-    r.c0_w = w[i++]; r.c0_b = (const float*)w[i++]; r.g0 = (const float*)w[i++]; r.be0 = (const float*)w[i++];
-    r.c1_w = w[i++]; r.c1_b = (const float*)w[i++]; r.g1 = (const float*)w[i++]; r.be1 = (const float*)w[i++];
-    r.res_w = w[i++]; r.res_b = (const float*)w[i++];
+    r.c0_w = W.next(); r.c0_b = W.next_f32(); r.g0 = W.next_f32(); r.be0 = W.next_f32();
+    r.c1_w = W.next(); r.c1_b = W.next_f32(); r.g1 = W.next_f32(); r.be1 = W.next_f32();
+    r.res_w = W.next(); r.res_b = W.next_f32();
     r.film_off = F; F += 2 * cout;
     if (cout > cmax) cmax = cout;
     if (r.cin_pad > cmax) cmax = r.cin_pad;
@@ -69,10 +67,10 @@ int vt_unet_create(const vt_unet_desc* desc, const void* const* w, int n, vt_une
   add(d.dims[L - 1], d.dims[L - 1]); add(d.dims[L - 1], d.dims[L - 1]);
   for (int u = 0; u < L - 1; ++u) { const int din = d.dims[L - 2 - u], dout = d.dims[L - 1 - u]; add(2 * dout, din); add(din, din); }
   h->nrb = nrb; h->F = F; h->cmax = cmax;
-  for (int l = 0; l < L - 1; ++l) { h->down_w[l] = w[i++]; h->down_b[l] = (const float*)w[i++]; }
-  for (int u = 0; u < L - 1; ++u) { h->up_we[u] = w[i++]; h->up_wo[u] = w[i++]; h->up_b[u] = (const float*)w[i++]; }
-  h->fc_w = w[i++]; h->fc_b = (const float*)w[i++]; h->fg = (const float*)w[i++]; h->fbe = (const float*)w[i++];
-  h->out_w = w[i++]; h->out_b = (const float*)w[i++];
+  for (int l = 0; l < L - 1; ++l) { h->down_w[l] = W.next(); h->down_b[l] = W.next_f32(); }
+  for (int u = 0; u < L - 1; ++u) { h->up_we[u] = W.next(); h->up_wo[u] = W.next(); h->up_b[u] = W.next_f32(); }
+  h->fc_w = W.next(); h->fc_b = W.next_f32(); h->fg = W.next_f32(); h->fbe = W.next_f32();
+  h->out_w = W.next(); h->out_b = W.next_f32();
   vt_unet_fused_init_meta(h);
   *out = h;
   return VT_OK;
@@ -91,26 +89,25 @@ struct UWs {   // workspace carve (byte offsets)
 
 UWs carve(const vt_unet_s* h, int B, int T) {
   const vt_unet_desc& d = h->d;
-  const int a = es(d.adt);
+  const int a = vt_dt_bytes(d.adt);
   const long M = (long)B * T;
   UWs w;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { size_t r = o; o += (bytes + 255) / 256 * 256; return r; };
-  w.xp = take((size_t)M * d.input_pad * a);
-  w.sin = take((size_t)B * d.dsed * a);
-  w.h1 = take((size_t)d.nets * B * 4 * d.dsed * a);
-  w.gin = take((size_t)d.nets * B * (d.dsed + d.cond_dim) * a);
-  w.film = take((size_t)d.nets * B * h->F * 4);
+  VtCarver cv;
+  w.xp = cv.take((size_t)M * d.input_pad * a);
+  w.sin = cv.take((size_t)B * d.dsed * a);
+  w.h1 = cv.take((size_t)d.nets * B * 4 * d.dsed * a);
+  w.gin = cv.take((size_t)d.nets * B * (d.dsed + d.cond_dim) * a);
+  w.film = cv.take((size_t)d.nets * B * h->F * 4);
   w.slab_stride = (long)d.nets * M * h->cmax;
-  w.slabs = take((size_t)MAX_SPLITK * w.slab_stride * 4);
+  w.slabs = cv.take((size_t)MAX_SPLITK * w.slab_stride * 4);
   const size_t act = (size_t)d.nets * M * h->cmax * a;
-  w.bufX = take(act); w.bufY = take(act); w.bufH = take(act); w.bufR = take(act);
+  w.bufX = cv.take(act); w.bufY = cv.take(act); w.bufH = cv.take(act); w.bufR = cv.take(act);
   for (int u = 0; u < d.n_levels - 1; ++u) {
     const int lvl = d.n_levels - 1 - u;
-    w.cat[u] = take((size_t)d.nets * (M >> lvl) * 2 * d.dims[lvl] * a);
+    w.cat[u] = cv.take((size_t)d.nets * (M >> lvl) * 2 * d.dims[lvl] * a);
   }
-  w.vs_out = take((size_t)d.nets * M * d.input_dim * 4);
-  w.total = o;
+  w.vs_out = cv.take((size_t)d.nets * M * d.input_dim * 4);
+  w.total = cv.o;
   return w;
 }
 
@@ -162,8 +159,6 @@ int gn(Ctx& c, int nsl, int M_rows_T, int C, const float* cb, const float* g, co
   return vt_k_groupnorm(p, c.s);
 }
 
-#define CK(x) do { int _r = (x); if (_r) return _r; } while (0)
-
 int resblock(Ctx& c, const ResBlk& r, View x, int Tl, View out) {
   const vt_unet_desc& d = c.h->d;
   const long M = (long)c.B * Tl;
@@ -174,13 +169,8 @@ int resblock(Ctx& c, const ResBlk& r, View x, int Tl, View out) {
   CK(conv_slabs(c, hbuf, r.cout, r.c1_w, r.cout, d.ksize, Tl, Tl, 1, -(d.ksize / 2), &nsl));
   View res = x;
   if (r.res_w) {
-    VtGemmParams p;
-    memset(&p, 0, sizeof(p));
-    p.A = x.p; p.W = r.res_w; p.C = c.ws + c.w.bufR;
-    p.M = (int)M; p.N = r.cout; p.K = r.cin_pad; p.lda = x.ld; p.ldw = r.cin_pad; p.ldc = r.cout;
-    p.bias = r.res_b; p.bias_gs = r.cout;
-    p.groups = d.nets; p.splitk = 1; p.a_gs = x.gs; p.w_gs = (long)r.cout * r.cin_pad; p.c_gs = M * r.cout;
-    p.a_dtype = c.adt; p.w_dtype = c.cdt; p.c_dtype = c.adt;
+    VtGemmParams p = vt_linear(x.p, c.adt, x.ld, r.res_w, c.cdt, r.cin_pad, r.res_b, c.ws + c.w.bufR, c.adt, r.cout, (int)M, r.cout, r.cin_pad, VT_ACT_NONE);
+    vt_gemm_groups(p, d.nets, x.gs, (long)r.cout * r.cin_pad, M * r.cout, r.cout);
     CK(vt_gemm_launch(p, c.s));
     res = View{c.ws + c.w.bufR, r.cout, M * r.cout};
   }
@@ -194,32 +184,21 @@ int film_tables(Ctx& c, const float* t_dev, float t_host, bool cond_ready, const
   const vt_unet_desc& d = h->d;
   const int G = d.dsed + d.cond_dim;
   CK(vt_k_sinusoid(t_dev, t_host, c.ws + c.w.sin, c.adt, c.B, d.dsed, 1, 0, 0, c.s));
-  VtGemmParams p;
-  memset(&p, 0, sizeof(p));
-  p.groups = d.nets; p.splitk = 1; p.a_dtype = c.adt; p.w_dtype = c.cdt; p.c_dtype = c.adt;
+  const int H4 = 4 * d.dsed;
   // Linear(dsed -> 4 dsed) + Mish
-  p.A = c.ws + c.w.sin; p.a_gs = 0; p.lda = d.dsed;
-  p.W = h->step_w1; p.w_gs = (long)4 * d.dsed * d.dsed; p.ldw = d.dsed;
-  p.bias = h->step_b1; p.bias_gs = 4 * d.dsed; p.act = VT_ACT_MISH;
-  p.C = c.ws + c.w.h1; p.c_gs = (long)c.B * 4 * d.dsed; p.ldc = 4 * d.dsed;
-  p.M = c.B; p.N = 4 * d.dsed; p.K = d.dsed;
+  VtGemmParams p = vt_linear(c.ws + c.w.sin, c.adt, d.dsed, h->step_w1, c.cdt, d.dsed, h->step_b1, c.ws + c.w.h1, c.adt, H4, c.B, H4, d.dsed, VT_ACT_MISH);
+  vt_gemm_groups(p, d.nets, 0, (long)H4 * d.dsed, (long)c.B * H4, H4);
   CK(vt_gemm_launch(p, c.s));
   // Linear(4 dsed -> dsed), then the FiLM cond_encoder's leading Mish, written into g[:, :dsed]
-  p.A = c.ws + c.w.h1; p.a_gs = (long)c.B * 4 * d.dsed; p.lda = 4 * d.dsed;
-  p.W = h->step_w2; p.w_gs = (long)4 * d.dsed * d.dsed; p.ldw = 4 * d.dsed;
-  p.bias = h->step_b2; p.bias_gs = d.dsed; p.act = VT_ACT_MISH;
-  p.C = c.ws + c.w.gin; p.c_gs = (long)c.B * G; p.ldc = G;
-  p.M = c.B; p.N = d.dsed; p.K = 4 * d.dsed;
+  p = vt_linear(c.ws + c.w.h1, c.adt, H4, h->step_w2, c.cdt, H4, h->step_b2, c.ws + c.w.gin, c.adt, G, c.B, d.dsed, H4, VT_ACT_MISH);
+  vt_gemm_groups(p, d.nets, (long)c.B * H4, (long)H4 * d.dsed, (long)c.B * G, d.dsed);
   CK(vt_gemm_launch(p, c.s));
   if (!cond_ready) {
     for (int n = 0; n < d.nets; ++n)
       CK(vt_k_act_copy(cond, VT_F32, d.cond_dim, c.ws + c.w.gin + ((size_t)n * c.B * G + d.dsed) * c.a_es, c.adt, G, c.B, d.cond_dim, VT_ACT_MISH, c.s));
   }
-  p.A = c.ws + c.w.gin; p.a_gs = (long)c.B * G; p.lda = G;
-  p.W = h->film_w; p.w_gs = h->F * G; p.ldw = G;
-  p.bias = h->film_b; p.bias_gs = h->F; p.act = VT_ACT_NONE;
-  p.C = c.ws + c.w.film; p.c_gs = (long)c.B * h->F; p.ldc = h->F; p.c_dtype = VT_F32;
-  p.M = c.B; p.N = (int)h->F; p.K = G;
+  p = vt_linear(c.ws + c.w.gin, c.adt, G, h->film_w, c.cdt, G, h->film_b, c.ws + c.w.film, VT_F32, h->F, c.B, (int)h->F, G, VT_ACT_NONE);
+  vt_gemm_groups(p, d.nets, (long)c.B * G, h->F * G, (long)c.B * h->F, h->F);
   CK(vt_gemm_launch(p, c.s));
   return VT_OK;
 }
@@ -251,15 +230,9 @@ int trunk(Ctx& c, const float* x, float* out) {
     CK(resblock(c, h->rb[rbi++], o1, Tl, o2));
     cur = o2;
     if (l < L - 1) {   // Downsample1d: Conv1d(C, C, 3, stride 2, pad 1)
-      VtGemmParams p;
-      memset(&p, 0, sizeof(p));
-      p.A = cur.p; p.lda = cur.ld; p.a_gs = cur.gs;
-      p.W = h->down_w[l]; p.ldw = 3 * C; p.w_gs = (long)C * 3 * C;
-      p.bias = h->down_b[l]; p.bias_gs = C;
-      p.M = (int)(M / 2); p.N = C; p.K = 3 * C;
+      VtGemmParams p = vt_linear(cur.p, c.adt, cur.ld, h->down_w[l], c.cdt, 3 * C, h->down_b[l], ping, c.adt, C, (int)(M / 2), C, 3 * C, VT_ACT_NONE);
+      vt_gemm_groups(p, d.nets, cur.gs, (long)C * 3 * C, (M / 2) * C, C);
       p.taps = 3; p.cin = C; p.tout = Tl / 2; p.tin = Tl; p.stride = 2; p.off0 = -1; p.tstep = 1;
-      p.C = ping; p.ldc = C; p.c_gs = (M / 2) * C;
-      p.groups = d.nets; p.splitk = 1; p.a_dtype = c.adt; p.w_dtype = c.cdt; p.c_dtype = c.adt;
       CK(vt_gemm_launch(p, c.s));
       // next level reads `ping`; keep ping/pong roles by swapping
       cur = View{ping, C, (M / 2) * C};
@@ -290,15 +263,10 @@ int trunk(Ctx& c, const float* x, float* out) {
     if (u + 1 < L - 1) { const int cn = d.dims[L - 2 - u]; dst = c.ws + c.w.cat[u + 1]; dld = 2 * cn; dgs = 2 * M * dld; }
     else { dst = c.ws + c.w.bufX; dld = din; dgs = 2 * M * din; }
     for (int par = 0; par < 2; ++par) {
-      VtGemmParams p;
-      memset(&p, 0, sizeof(p));
-      p.A = o2.p; p.lda = o2.ld; p.a_gs = o2.gs;
-      p.W = par == 0 ? h->up_we[u] : h->up_wo[u]; p.ldw = 2 * din; p.w_gs = (long)din * 2 * din;
-      p.bias = h->up_b[u]; p.bias_gs = din;
-      p.M = (int)M; p.N = din; p.K = 2 * din;
+      VtGemmParams p = vt_linear(o2.p, c.adt, o2.ld, par == 0 ? h->up_we[u] : h->up_wo[u], c.cdt, 2 * din, h->up_b[u], dst + (size_t)par * dld * a, c.adt, 2 * dld,
+                                 (int)M, din, 2 * din, VT_ACT_NONE);
+      vt_gemm_groups(p, d.nets, o2.gs, (long)din * 2 * din, dgs, din);
       p.taps = 2; p.cin = din; p.tout = Tl; p.tin = Tl; p.stride = 1; p.off0 = par == 0 ? 0 : 1; p.tstep = -1;
-      p.C = dst + (size_t)par * dld * a; p.ldc = 2 * dld; p.c_gs = dgs;
-      p.groups = d.nets; p.splitk = 1; p.a_dtype = c.adt; p.w_dtype = c.cdt; p.c_dtype = c.adt;
       CK(vt_gemm_launch(p, c.s));
     }
     Tl *= 2;
@@ -311,14 +279,8 @@ int trunk(Ctx& c, const float* x, float* out) {
     CK(conv_slabs(c, xin, C, h->fc_w, C, d.ksize, Tl, Tl, 1, -(d.ksize / 2), &nsl));
     View hb = {c.ws + c.w.bufH, C, M * C};
     CK(gn(c, nsl, Tl, C, h->fc_b, h->fg, h->fbe, 0, false, nullptr, hb));
-    VtGemmParams p;
-    memset(&p, 0, sizeof(p));
-    p.A = hb.p; p.lda = C; p.a_gs = M * C;
-    p.W = h->out_w; p.ldw = C; p.w_gs = (long)d.input_dim * C;
-    p.bias = h->out_b; p.bias_gs = d.input_dim;
-    p.M = (int)M; p.N = d.input_dim; p.K = C;
-    p.C = out; p.ldc = d.input_dim; p.c_gs = M * d.input_dim;
-    p.groups = d.nets; p.splitk = 1; p.a_dtype = c.adt; p.w_dtype = c.cdt; p.c_dtype = VT_F32;
+    VtGemmParams p = vt_linear(hb.p, c.adt, C, h->out_w, c.cdt, C, h->out_b, out, VT_F32, d.input_dim, (int)M, d.input_dim, C, VT_ACT_NONE);
+    vt_gemm_groups(p, d.nets, M * C, (long)d.input_dim * C, M * d.input_dim, d.input_dim);
     CK(vt_gemm_launch(p, c.s));
   }
   return VT_OK;
@@ -328,7 +290,7 @@ int make_ctx(Ctx& c, vt_unet_t h, int B, int T, void* ws, vt_stream_t s) {
   if (!h || !ws) return vt_fail(VT_ERR_ARG, "unet: null handle/workspace");
   if (B <= 0 || T <= 0 || (T % (1 << (h->d.n_levels - 1)))) return vt_fail(VT_ERR_ARG, "unet: T=%d must be divisible by %d", T, 1 << (h->d.n_levels - 1));
   c.h = h; c.B = B; c.T = T; c.ws = (char*)ws; c.w = carve(h, B, T); c.s = (hipStream_t)s;
-  c.adt = h->d.adt; c.cdt = h->d.cdt; c.a_es = es(h->d.adt);
+  c.adt = h->d.adt; c.cdt = h->d.cdt; c.a_es = vt_dt_bytes(h->d.adt);
   return VT_OK;
 }
 

@@ -79,8 +79,6 @@ struct Run {
   void want(int id, size_t bytes) { if (bytes > need[id]) need[id] = bytes; }
 };
 
-#define CK(x) do { int _r = (x); if (_r) return _r; } while (0)
-
 USrc src_zero() { USrc u; memset(&u, 0, sizeof(u)); return u; }
 
 // slabs [net][S][rows][C] of a convolution + its bias (+ GroupNorm / FiLM set by the caller)
@@ -244,16 +242,15 @@ int plan(Run& R) {   // dry run: buffer sizes -> offsets
   CK(trunk(R, nullptr, nullptr));
   const vt_unet_s* h = R.h;
   const vt_unet_desc& d = h->d;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { size_t r = o; o += (bytes + 255) / 256 * 256; return r; };
-  R.o_film_s = take((size_t)d.nets * R.n_steps * h->F * 4);
-  R.o_film_c = take((size_t)d.nets * R.B * h->F * 4);
-  R.o_sin = take((size_t)R.n_steps * d.dsed * 4);
-  R.o_h1 = take((size_t)d.nets * R.n_steps * 4 * d.dsed * 4);
-  R.o_gs = take((size_t)d.nets * R.n_steps * d.dsed * 4);
-  R.o_gc = take((size_t)R.B * d.cond_dim * 4);
-  for (int i = 0; i < NBUF; ++i) R.off[i] = take(R.need[i]);
-  R.total = o;
+  VtCarver cv;
+  R.o_film_s = cv.take((size_t)d.nets * R.n_steps * h->F * 4);
+  R.o_film_c = cv.take((size_t)d.nets * R.B * h->F * 4);
+  R.o_sin = cv.take((size_t)R.n_steps * d.dsed * 4);
+  R.o_h1 = cv.take((size_t)d.nets * R.n_steps * 4 * d.dsed * 4);
+  R.o_gs = cv.take((size_t)d.nets * R.n_steps * d.dsed * 4);
+  R.o_gc = cv.take((size_t)R.B * d.cond_dim * 4);
+  for (int i = 0; i < NBUF; ++i) R.off[i] = cv.take(R.need[i]);
+  R.total = cv.o;
   R.dry = false;
   return VT_OK;
 }
@@ -264,33 +261,20 @@ int film_tables(Run& R, const float* ts, const float* cond) {
   const vt_unet_desc& d = h->d;
   const int G = d.dsed + d.cond_dim, n = R.n_steps;
   CK(vt_usin_launch(ts, n, reinterpret_cast<float*>(R.ws + R.o_sin), d.dsed, R.s));
-  VtGemmParams p;
-  memset(&p, 0, sizeof(p));
-  p.groups = d.nets; p.splitk = 1; p.a_dtype = VT_F32; p.w_dtype = d.cdt; p.c_dtype = VT_F32;
-  p.A = R.ws + R.o_sin; p.a_gs = 0; p.lda = d.dsed;
-  p.W = h->step_w1; p.w_gs = (long)4 * d.dsed * d.dsed; p.ldw = d.dsed;
-  p.bias = h->step_b1; p.bias_gs = 4 * d.dsed; p.act = VT_ACT_MISH;
-  p.C = R.ws + R.o_h1; p.c_gs = (long)n * 4 * d.dsed; p.ldc = 4 * d.dsed;
-  p.M = n; p.N = 4 * d.dsed; p.K = d.dsed;
+  const int H4 = 4 * d.dsed, F = (int)h->F;
+  VtGemmParams p = vt_linear(R.ws + R.o_sin, VT_F32, d.dsed, h->step_w1, d.cdt, d.dsed, h->step_b1, R.ws + R.o_h1, VT_F32, H4, n, H4, d.dsed, VT_ACT_MISH);
+  vt_gemm_groups(p, d.nets, 0, (long)H4 * d.dsed, (long)n * H4, H4);
   CK(vt_gemm_launch(p, R.s));
-  p.A = R.ws + R.o_h1; p.a_gs = (long)n * 4 * d.dsed; p.lda = 4 * d.dsed;
-  p.W = h->step_w2; p.w_gs = (long)4 * d.dsed * d.dsed; p.ldw = 4 * d.dsed;
-  p.bias = h->step_b2; p.bias_gs = d.dsed; p.act = VT_ACT_MISH;        // cond_encoder's leading Mish
-  p.C = R.ws + R.o_gs; p.c_gs = (long)n * d.dsed; p.ldc = d.dsed;
-  p.M = n; p.N = d.dsed; p.K = 4 * d.dsed;
+  p = vt_linear(R.ws + R.o_h1, VT_F32, H4, h->step_w2, d.cdt, H4, h->step_b2, R.ws + R.o_gs, VT_F32, d.dsed, n, d.dsed, H4, VT_ACT_MISH);        // cond_encoder's leading Mish
+  vt_gemm_groups(p, d.nets, (long)n * H4, (long)H4 * d.dsed, (long)n * d.dsed, d.dsed);
   CK(vt_gemm_launch(p, R.s));
-  p.A = R.ws + R.o_gs; p.a_gs = (long)n * d.dsed; p.lda = d.dsed;
-  p.W = h->film_w; p.w_gs = h->F * G; p.ldw = G;
-  p.bias = h->film_b; p.bias_gs = h->F; p.act = VT_ACT_NONE;
-  p.C = R.ws + R.o_film_s; p.c_gs = (long)n * h->F; p.ldc = h->F;
-  p.M = n; p.N = (int)h->F; p.K = d.dsed;
+  p = vt_linear(R.ws + R.o_gs, VT_F32, d.dsed, h->film_w, d.cdt, G, h->film_b, R.ws + R.o_film_s, VT_F32, h->F, n, F, d.dsed, VT_ACT_NONE);
+  vt_gemm_groups(p, d.nets, (long)n * d.dsed, h->F * G, (long)n * h->F, h->F);
   CK(vt_gemm_launch(p, R.s));
   CK(vt_k_act_copy(cond, VT_F32, d.cond_dim, R.ws + R.o_gc, VT_F32, d.cond_dim, R.B, d.cond_dim, VT_ACT_MISH, R.s));
-  p.A = R.ws + R.o_gc; p.a_gs = 0; p.lda = d.cond_dim;
-  p.W = reinterpret_cast<const float*>(h->film_w) + d.dsed; p.w_gs = h->F * G; p.ldw = G;
-  p.bias = nullptr; p.bias_gs = 0;
-  p.C = R.ws + R.o_film_c; p.c_gs = (long)R.B * h->F; p.ldc = h->F;
-  p.M = R.B; p.N = (int)h->F; p.K = d.cond_dim;
+  p = vt_linear(R.ws + R.o_gc, VT_F32, d.cond_dim, reinterpret_cast<const float*>(h->film_w) + d.dsed, d.cdt, G, nullptr, R.ws + R.o_film_c, VT_F32, h->F, R.B, F,
+                d.cond_dim, VT_ACT_NONE);
+  vt_gemm_groups(p, d.nets, 0, h->F * G, (long)R.B * h->F, 0);
   CK(vt_gemm_launch(p, R.s));
   return VT_OK;
 }

@@ -50,6 +50,56 @@ class _Workspace:
         return buf
 
 
+class _Engine:
+    """The handle protocol every engine follows: `_create` makes the C handle `_h` from a descriptor and the packed weights (which the handle
+    only points into: the engine keeps them alive), `_derive` allocates and fills the derived copy of the weights where the driver has one,
+    `repack` rebuilds it, `__del__` destroys the handle."""
+
+    _h = None
+    _derived: Optional[torch.Tensor] = None
+
+    def _create(self, prefix: str, desc, weights, what: Optional[str] = None) -> None:
+        lib = L.lib()
+        n = getattr(lib, f"vt_{prefix}_num_weights")(C.byref(desc))
+        assert n == len(weights), (n, len(weights))
+        self._prefix = prefix
+        self._h = C.c_void_p()
+        L.check(getattr(lib, f"vt_{prefix}_create")(C.byref(desc), L.ptr_array(weights), len(weights), C.byref(self._h)), what or f"vt_{prefix}_create")
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                getattr(L.lib(), f"vt_{self._prefix}_destroy")(self._h)
+        except Exception:
+            pass
+
+    def _derive(self, bytes_fn: str, pack_fn: str) -> Optional[torch.Tensor]:
+        """Allocate the derived copy (`bytes_fn(handle)` bytes; None where this configuration has none), fill it through `repack()` and
+        wait for the packing kernels.  The engine keeps the returned buffer under its own name (`_packed`, `_fused`)."""
+        nb = getattr(L.lib(), bytes_fn)(self._h)
+        self._pack_fn = pack_fn
+        self._derived = torch.empty(nb, dtype=torch.uint8, device=self.device) if nb else None
+        self.repack()
+        torch.cuda.synchronize(self.device)
+        return self._derived
+
+    def repack(self) -> None:
+        """Rebuild the derived copy of the weights from `self._weights` (after they were overwritten in place, e.g. by the one-time broadcast of
+        rank 0's weights, vlatouch/dist.py).
+
+        INVARIANT: the derived copy (DINOv2's `_packed`: a second, fragment-ordered copy of every fc1 weight; RDT's `_packed`; the U-Net's
+        `_fused` stream) is DERIVED from `self._weights`; some launches read it while all others read `_weights`.  Any in-place write to
+        `_weights` must be followed by `repack()` — use `update_weights()` for that, never write the tensors and walk away."""
+        if self._derived is not None:
+            L.check(getattr(L.lib(), self._pack_fn)(self._h, L.ptr(self._derived), L.stream_ptr(self.device)), self._pack_fn)
+
+    def update_weights(self, fn) -> None:
+        """The one sanctioned way to change weights in place: `fn(list_of_packed_device_tensors)` mutates them (checkpoint reload into the same
+        tensors, a broadcast, a fine-tuning step), then every derived copy is rebuilt."""
+        fn(self._weights)
+        self.repack()
+
+
 class RangeGuard:
     """Mixin of the engines with a 16-bit mode: ONE uint32 in device memory that the engine's kernels OR bits into when a value left the 16-bit type's range
     (include/vlatouch.h, vt_rdt_set_range_flag / vt_dino_set_range_flag; bit names: vlatouch._lib.RANGE_NAMES).  Sticky across calls and hipGraph replays.
@@ -124,7 +174,7 @@ def _convT_parity(w: torch.Tensor, taps) -> torch.Tensor:
     return torch.cat([w[:, :, t].t() for t in taps], dim=1).contiguous()
 
 
-class UNetEngine:
+class UNetEngine(_Engine):
     """`nets` structurally identical conditional 1-D U-Nets evaluated together (v_net + s_net for the sampler).
 
     sds: one state dict per net with keys relative to the net (e.g. 'down_modules.0.0.blocks.0.block.0.weight').
@@ -215,34 +265,13 @@ class UNetEngine:
         for i, d in enumerate(self.dims):
             desc.dims[i] = d
         desc.cdt, desc.adt = cdt, adt
-        lib = L.lib()
-        n = lib.vt_unet_num_weights(C.byref(desc))
-        assert n == len(W), (n, len(W))
-        self._h = C.c_void_p()
-        L.check(lib.vt_unet_create(C.byref(desc), L.ptr_array(W), len(W), C.byref(self._h)), "vt_unet_create")
+        self._create("unet", desc, W)
         # fused sampler path (split-bf16 mode): pre-split hi / lo weights in MFMA fragment order, packed once on the device
-        self._fused = None
-        nb = lib.vt_unet_fused_bytes(self._h)
-        if nb:
-            self._fused = torch.empty(nb, dtype=torch.uint8, device=self.device)
-            self.repack()
+        self._fused = self._derive("vt_unet_fused_bytes", "vt_unet_fused_pack")
         self._ws = _Workspace(self.device)
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                L.lib().vt_unet_destroy(self._h)
-        except Exception:
-            pass
 
     def _workspace(self, B: int, T: int) -> torch.Tensor:
         return self._ws.get(L.lib().vt_unet_workspace_bytes(self._h, B, T))
-
-    def repack(self) -> None:
-        """Rebuild the derived weight copy of the fused path from `self._weights` (after they were overwritten in place, e.g. by the
-        one-time broadcast of rank 0's weights, vlatouch/dist.py)."""
-        if self._fused is not None:
-            L.check(L.lib().vt_unet_fused_pack(self._h, L.ptr(self._fused), L.stream_ptr(self.device)), "vt_unet_fused_pack")
 
     def forward(self, x: torch.Tensor, t, cond: torch.Tensor) -> torch.Tensor:
         """x [B,T,dim], t scalar or [B], cond [B,G]  ->  [nets,B,T,dim] fp32."""
@@ -283,7 +312,7 @@ class UNetEngine:
 
 
 # =========================================================================================== DINOv2
-class DinoEngine(RangeGuard):
+class DinoEngine(_Engine, RangeGuard):
     """HF Dinov2Model state dict -> CLS features (pooler_output)."""
 
     def __init__(self, sd: SD, *, heads: int, precision: str = "fp32", device="cuda", patch: int = 14, eps: float = 1e-6):
@@ -330,44 +359,14 @@ class DinoEngine(RangeGuard):
         desc.cdt, desc.adt, desc.eps = cdt, adt, eps
         if self.swiglu:
             desc.act, desc.mlp_dim = L.ACT_SWIGLU, sd[f"encoder.layer.0.{fc2n}.weight"].shape[1]
-        lib = L.lib()
-        assert lib.vt_dino_num_weights(C.byref(desc)) == len(W)
-        self._h = C.c_void_p()
-        L.check(lib.vt_dino_create(C.byref(desc), L.ptr_array(W), len(W), C.byref(self._h)), "vt_dino_create")
+        self._create("dino", desc, W)
         # fragment-packed second copies of the fc1 weights (16-bit GELU models): the rows a 256-row tiling of the token matrix leaves over, and the CLS-only last
         # block, run fc1 on the small-M packed-weight tile (csrc/vt_gemm_pws.hip)
-        nb = lib.vt_dino_packed_bytes(self._h)
-        if nb:
-            self._packed = torch.empty(nb, dtype=torch.uint8, device=self.device)
-            L.check(lib.vt_dino_set_packed(self._h, L.ptr(self._packed), L.stream_ptr(self.device)), "vt_dino_set_packed")
-            torch.cuda.synchronize(self.device)
-        self._range_init(lib.vt_dino_set_range_flag, "vt_dino_set_range_flag")
+        self._packed = self._derive("vt_dino_packed_bytes", "vt_dino_set_packed")
+        self._range_init(L.lib().vt_dino_set_range_flag, "vt_dino_set_range_flag")
         self._ws = _Workspace(self.device)
         self._pos_cache: Dict[int, torch.Tensor] = {}
         self.last_flags: Optional[torch.Tensor] = None
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                L.lib().vt_dino_destroy(self._h)
-        except Exception:
-            pass
-
-    def repack(self) -> None:
-        """Rebuild the fragment-packed fc1 copy from `self._weights` (after they were overwritten in place, e.g. by the one-time broadcast of rank 0's
-        weights, vlatouch/dist.py).
-
-        INVARIANT: `self._packed` (a second, fragment-ordered copy of every fc1 weight) is DERIVED from `self._weights`; the remainder rows of the
-        token matrix and the CLS-only last block read it while all other rows read `_weights`.  Any in-place write to `_weights` must be followed
-        by `repack()` — use `update_weights()` for that, never write the tensors and walk away."""
-        if getattr(self, "_packed", None) is not None:
-            L.check(L.lib().vt_dino_set_packed(self._h, L.ptr(self._packed), L.stream_ptr(self.device)), "vt_dino_set_packed")
-
-    def update_weights(self, fn) -> None:
-        """The one sanctioned way to change weights in place: `fn(list_of_packed_device_tensors)` mutates them (checkpoint reload into the same
-        tensors, a broadcast, a fine-tuning step), then every derived copy is rebuilt."""
-        fn(self._weights)
-        self.repack()
 
     def pos_patch(self, grid: int) -> torch.Tensor:
         """Position embeddings of the patch tokens for a grid x grid image: input-independent, so the bicubic
@@ -415,7 +414,7 @@ class DinoEngine(RangeGuard):
 
 
 # =========================================================================================== SigLIP image tokens
-class SiglipEngine(RangeGuard):
+class SiglipEngine(_Engine, RangeGuard):
     """HF SiglipVisionModel state dict -> last_hidden_state [B, tokens, hidden] (the RDT image tower).
 
     Runs on the same ViT driver as DINOv2 (vt_dino_*): no CLS token, tanh-GELU, every token through the final LayerNorm.
@@ -492,19 +491,9 @@ class SiglipEngine(RangeGuard):
         desc.cdt, desc.adt, desc.eps = cdt, adt, eps
         desc.no_cls, desc.act, desc.head_dim, desc.mlp_dim, desc.out_all = 1, L.ACT_GELU_TANH, HP, Dm, 1
         desc.attn_scale = float(hd) ** -0.5
-        lib = L.lib()
-        assert lib.vt_dino_num_weights(C.byref(desc)) == len(W)
-        self._h = C.c_void_p()
-        L.check(lib.vt_dino_create(C.byref(desc), L.ptr_array(W), len(W), C.byref(self._h)), "vt_dino_create (siglip)")
-        self._range_init(lib.vt_dino_set_range_flag, "vt_dino_set_range_flag")
+        self._create("dino", desc, W, "vt_dino_create (siglip)")
+        self._range_init(L.lib().vt_dino_set_range_flag, "vt_dino_set_range_flag")
         self._ws = _Workspace(self.device)
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                L.lib().vt_dino_destroy(self._h)
-        except Exception:
-            pass
 
     @property
     def num_patches(self) -> int:
@@ -611,7 +600,7 @@ def action_normalize(x: torch.Tensor, mins: torch.Tensor, maxs: torch.Tensor, de
 
 
 # =========================================================================================== LSTM residual head
-class LstmEngine:
+class LstmEngine(_Engine):
     def __init__(self, mods: Mapping[str, SD], *, state_dim: int = 10, hidden: int = 256, layers: int = 2, force_dim: int = 3,
                  precision: str = "fp32", device="cuda"):
         self.device = L.require_gpu(device)
@@ -668,18 +657,8 @@ class LstmEngine:
         desc = L.LstmDesc()
         desc.state_dim, desc.hidden, desc.layers, desc.force_dim, desc.force_pad, desc.in_pad, desc.cdt = \
             state_dim, H, layers, force_dim, fpad, inpad, cdt
-        lib = L.lib()
-        assert lib.vt_lstm_num_weights(C.byref(desc)) == len(W)
-        self._h = C.c_void_p()
-        L.check(lib.vt_lstm_create(C.byref(desc), L.ptr_array(W), len(W), C.byref(self._h)), "vt_lstm_create")
+        self._create("lstm", desc, W)
         self._ws = _Workspace(dev)
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                L.lib().vt_lstm_destroy(self._h)
-        except Exception:
-            pass
 
     def step(self, obs_cond, vla_n, force, h, c) -> torch.Tensor:
         """One tick; h, c [layers,B,H] fp32 are updated in place; returns normalised vla_n + delta."""

@@ -11,7 +11,7 @@ import torch
 
 from . import _lib as L
 from . import dpm
-from .engine import RangeGuard, _Workspace
+from .engine import RangeGuard, _Engine, _Workspace
 
 SD = Mapping[str, torch.Tensor]
 
@@ -25,7 +25,7 @@ def adaptor_depth(kind: str) -> int:
     return int(m.group(1))
 
 
-class RdtEngine(RangeGuard):
+class RdtEngine(_Engine, RangeGuard):
     def __init__(self, sd: SD, *, hidden: int, depth: int, heads: int, horizon: int, action_dim: int, lang_token_dim: int,
                  img_token_dim: int, state_token_dim: int, max_lang_cond_len: int, img_cond_len: int,
                  lang_adaptor: str = "mlp2x_gelu", img_adaptor: str = "mlp2x_gelu", state_adaptor: str = "mlp3x_gelu",
@@ -91,9 +91,7 @@ class RdtEngine(RangeGuard):
         d.cdt = d.adt = cdt
         d.rms_mode = {"meansq": L.NORM_RMS_MEANSQ, "var": L.NORM_RMS_VAR}[rms_mode]
         lib = L.lib()
-        assert lib.vt_rdt_num_weights(C.byref(d)) == len(W), (lib.vt_rdt_num_weights(C.byref(d)), len(W))
-        self._h = C.c_void_p()
-        L.check(lib.vt_rdt_create(C.byref(d), L.ptr_array(W), len(W), C.byref(self._h)), "vt_rdt_create")
+        self._create("rdt", d, W)
         L.check(lib.vt_rdt_set_state_precision(self._h, int(solver_state == "fp32")), "vt_rdt_set_state_precision")
         if dtype != torch.float32 and self.io_dtype != torch.float32:
             L.check(lib.vt_rdt_set_io_dtype(self._h, L.dt_code(self.io_dtype)), "vt_rdt_set_io_dtype")
@@ -106,14 +104,10 @@ class RdtEngine(RangeGuard):
         self.headnorm_gain_absmax = float(torch.stack([t.abs().max() for t in hn]).max())
         self.fits_fp16 = self.weight_absmax <= 65504.0 and 8.0 * self.headnorm_gain_absmax <= 65504.0
         self._ws = _Workspace(dev)
-        # frozen weights of the denoise-loop Linears, a second time in MFMA fragment order (csrc/vt_gemm_pw.hip streams them global -> VGPR)
+        # the cross-attention score bounds, and the frozen weights of the denoise-loop Linears a second time in MFMA fragment order
+        # (csrc/vt_gemm_pw.hip streams them global -> VGPR): both through repack()
         self._depth, self._rms_mode = depth, rms_mode
-        self._set_score_bounds()
-        nb = lib.vt_rdt_packed_bytes(self._h)
-        self._packed = None
-        if nb:
-            self._packed = torch.empty(nb, dtype=torch.uint8, device=dev)
-            L.check(lib.vt_rdt_set_packed(self._h, L.ptr(self._packed), L.stream_ptr(dev)), "vt_rdt_set_packed")
+        self._packed = self._derive("vt_rdt_packed_bytes", "vt_rdt_set_packed")
 
     def _set_score_bounds(self):
         """|q . k| / 8 <= 8 max_i |w_q[i] w_k[i]| for the mean-square per-head RMSNorm of cross_attn.q_norm / k_norm (blocks.py:86-87, 112-113):
@@ -134,8 +128,7 @@ class RdtEngine(RangeGuard):
         """Re-derive what was computed from `_weights` at load time after they changed in place (e.g. the multi-GPU weight broadcast):
         the fragment-packed copies and the cross-attention score bounds."""
         self._set_score_bounds()
-        if self._packed is not None:
-            L.check(L.lib().vt_rdt_set_packed(self._h, L.ptr(self._packed), L.stream_ptr(self.device)), "vt_rdt_set_packed")
+        super().repack()
 
     def load_weights(self, sd: SD) -> None:
         """Overwrite the packed weights in place from `sd` (tensors on this device, the constructor's keys and shapes), then `repack()`:
@@ -153,18 +146,6 @@ class RdtEngine(RangeGuard):
             else:
                 ops.cast(src, dst.dtype, out=dst)
         self.repack()
-
-    def update_weights(self, fn):
-        """In-place change of the packed weights through `fn(self._weights)`, followed by `repack()` (the derived copies never go stale)."""
-        fn(self._weights)
-        self.repack()
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                L.lib().vt_rdt_destroy(self._h)
-        except Exception:
-            pass
 
     @staticmethod
     def _expect(name, t, shape):

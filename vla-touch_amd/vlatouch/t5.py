@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from vlatouch import _lib as L
+from vlatouch.engine import _Engine
 
 MAX_LEN = 1024          # longest sequence of the attention kernel (RDT-1B's max_lang_cond_len)
 REL_SPAN = MAX_LEN - 1  # bucket table covers rel = -REL_SPAN .. REL_SPAN
@@ -100,7 +101,7 @@ def slot_shapes(cfg: Dict) -> Dict[str, Tuple[int, ...]]:
 PRECISIONS = {"fp32": L.F32, "bf16": L.BF16}
 
 
-class T5Engine:
+class T5Engine(_Engine):
     """HF T5EncoderModel (v1.1, gated-gelu) on libvlatouch_hip.so.  `sd` maps HF keys to tensors (any device / dtype; values are read
     one at a time and moved to `device`, so a lazily loading mapping keeps the host footprint at one tensor)."""
 
@@ -125,24 +126,13 @@ class T5Engine:
         c = self.cfg
         self.desc = L.T5Desc(c["vocab_size"], c["d_model"], c["num_heads"], c["d_kv"], c["d_ff"], c["num_layers"],
                              c["relative_attention_num_buckets"], c["relative_attention_max_distance"], c["layer_norm_epsilon"], code, code)
-        lib = L.lib()
-        self._h = L.C.c_void_p()
-        L.check(lib.vt_t5_create(L.C.byref(self.desc), L.ptr_array(self.weights), len(self.weights), L.C.byref(self._h)), "vt_t5_create")
+        self._create("t5", self.desc, self.weights)
         self.buckets = torch.from_numpy(bucket_table(c["relative_attention_num_buckets"], c["relative_attention_max_distance"])).to(self.device)
         self._ws: Optional[torch.Tensor] = None
 
     @property
     def d_model(self) -> int:
         return self.cfg["d_model"]
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            try:
-                L.lib().vt_t5_destroy(h)
-            except Exception:
-                pass
-            self._h = None
 
     @torch.no_grad()
     def forward(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, out_dtype=torch.float32) -> torch.Tensor:
