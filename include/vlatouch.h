@@ -655,6 +655,39 @@ int vt_rdt_batch(const double* qpos, const int* ep_off, const double* ep_stats, 
                  float* states, float* actions, float* elem_mask, float* state_norm, long long* ctrl_freqs, float* lang_out,
                  unsigned char* lang_mask, vt_stream_t stream);
 
+/* ---- one controller-training batch out of device-resident episodes (vlatouch/ctrl_data.py).  Stands for, per sample,
+ * ControllerDataset.__getitem__ (controller_dataset.py:101-170: the window's pose rows, VLA chunk and force rows), normalize_actions
+ * (:303-346), the slicing of DiffusionControllerTrainer._prepare_batch_for_diffusion (bridge_train.py:105-164) or
+ * LSTMControllerTrainer._prepare_batch (lstm_train.py:56-84) and the concatenation in front of the observation MLP; and, per step, for the
+ * frozen DINOv2 tower, whose CLS vectors were encoded once per frame.
+ * Device-resident tables: pose10 fp64 [rows][10] = converted_ee_pose_with_gripper, gripper NOT divided; vla fp64 [rows][Hv][10], the raw
+ *   vla_action; forces fp32 [rows][Fd]; ep_off int32 [E + 1] (row offsets, rows = ep_off[E]); feat fp32 [2 cameras][rows][2 modes][dv], the
+ *   CLS vector of each frame with the ImageNet normalisation off (mode 0) and on (mode 1); pix_sum uint64 [2][rows], the exact sum of each
+ *   frame's P bytes (vt_ctrl_pixsum); stats fp32 [4][10] = expert mins | expert maxs | vla mins | vla maxs.
+ * plan (device, one upload): int32 [B][2] = (episode, start).  The window's last context frame is f = start + cf - 1.
+ * Normalisation decision, per camera, over the call's batch as the reference's DINOv2Encoder.forward takes it (visual_encoder.py:78,100):
+ *   norm_flags[cam] = 1 iff 2 * sum_b pix_sum[cam][f_b] >= 255 * B * P, in exact integer arithmetic.  It replaces the fp32 mean of
+ *   vt_dino_forward's statistics kernel and can differ from it only when the batch mean is within fp32 rounding of 0.5.
+ * Outputs, fp32: obs_in [B][in_pad] = [feat[0][f][flag 0] | feat[1][f][flag 1] | pose10[f] | forces[f] | 0 ..] in vt_concat_obs's columns
+ *   (the force columns only with VT_CTRL_BRIDGE and use_force); expert_act [B][h][10] = pose10[f + 1 + r] and vla_act [B][h][10] =
+ *   vla[f + 1][r], gripper / 255 in fp64, rounded once to fp32, then normalised with the arithmetic of vt_action_normalize
+ *   (padding_factor, the fp32 mins / maxs of `stats`); forces_out [B][h][Fd] = rows f + 1 .. f + h (VT_CTRL_BRIDGE) or f .. f + h - 1
+ *   (VT_CTRL_LSTM, the reference's forces[:, cf - 1:-1]); current_force [B][Fd] = forces[f] (required for VT_CTRL_BRIDGE, may be null for
+ *   VT_CTRL_LSTM); norm_flags [2].
+ * Two launches, no atomics (two calls give the same bits), no host read, allocation or synchronisation.  The caller checks the plan against
+ * its tables; an episode outside [0, E) or shorter than cf + h is written as NaN rows and adds nothing to the decision's sums, and a start
+ * is clamped into [0, N - cf - h], so no entry reads outside the tables.  Null pointers, sizes < 1, h > Hv, an unknown layout, in_pad
+ * smaller than the row, B, h or cf above 2^20, P above 2^32 and pose10 / vla not 16-byte aligned return VT_ERR_ARG without a launch. */
+#define VT_CTRL_BRIDGE 0
+#define VT_CTRL_LSTM 1
+int vt_ctrl_batch(const double* pose10, const double* vla, const float* forces, const int* ep_off, const float* feat, const unsigned long long* pix_sum,
+                  int E, long long rows, int Hv, int Fd, int dv, long long P, const float* stats, float padding_factor, int cf, int h, int layout,
+                  int use_force, const int* plan, int B, float* obs_in, int in_pad, float* expert_act, float* vla_act, float* forces_out,
+                  float* current_force, float* norm_flags, vt_stream_t stream);
+/* sums [n] = the exact sum of the P bytes of each of n frames laid one after the other (uint8, any layout): what the decision above reads.
+ * One block per frame, no atomics. */
+int vt_ctrl_pixsum(const unsigned char* frames, long long P, int n, unsigned long long* sums, vt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

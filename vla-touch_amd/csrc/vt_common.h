@@ -250,6 +250,19 @@ template <> __device__ __forceinline__ void stf<float>(float* p, size_t i, float
 template <> __device__ __forceinline__ void stf<bf16_t>(bf16_t* p, size_t i, float v) { p[i] = f2bf(v); }
 template <> __device__ __forceinline__ void stf<half_t>(half_t* p, size_t i, float v) { p[i] = f2h(v); }
 
+// normalize_actions / denormalize_actions of one value (controller_dataset.py:303-346: <1e-6 range guard / :349-384: no guard): the padded
+// min-max range of its column mapped to [-1, 1].  One statement for actnorm_kernel (vt_kernels.hip) and ctrl_batch_kernel (vt_ctrl_data.hip),
+// so that a batch assembled on the device carries the bits vt_action_normalize gives.
+__device__ __forceinline__ float vt_actnorm(float x, float mn, float mx, float pad, int denorm) {
+  const float pr = (mx - mn) * pad;
+  const float ctr = (mn + mx) / 2;
+  const float pmin = ctr - pr / 2, pmax = ctr + pr / 2;
+  float rng = pmax - pmin;
+  if (denorm) return (x + 1.0f) / 2.0f * rng + pmin;
+  if (rng < 1e-6f) rng = 1.0f;
+  return 2.0f * (x - pmin) / rng - 1.0f;
+}
+
 // (bit values: include/vlatouch.h)
 #ifndef VT_RANGE_XN_SAT
 #define VT_RANGE_XN_SAT 1u

@@ -483,17 +483,7 @@ __global__ void actnorm_kernel(const float* __restrict__ in, float* __restrict__
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int c = (int)(i % dim);
-  const float mn = mins[c], mx = maxs[c];
-  const float pr = (mx - mn) * pad;
-  const float ctr = (mn + mx) / 2;
-  const float pmin = ctr - pr / 2, pmax = ctr + pr / 2;
-  float rng = pmax - pmin;
-  if (denorm) {
-    out[i] = (in[i] + 1.0f) / 2.0f * rng + pmin;
-  } else {
-    if (rng < 1e-6f) rng = 1.0f;
-    out[i] = 2.0f * (in[i] - pmin) / rng - 1.0f;
-  }
+  out[i] = vt_actnorm(in[i], mins[c], maxs[c], pad, denorm);
 }
 
 template <typename TO>

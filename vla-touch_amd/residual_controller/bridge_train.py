@@ -9,7 +9,9 @@ Same constructor, `_prepare_batch_for_diffusion`, `_train_epoch`, `_evaluate`, `
   `obs_cond`, because the MLP is trained through the interpolant loss and its backward needs the input;
 * `t` and `z` (the reference's `torch.rand` / `torch.randn_like` draws inside `get_loss`, bridge_model.py:190,199) may be passed in for
   reproducible steps; they are drawn on the device otherwise;
-* TensorBoard / file logging are replaced by a plain list of per-step records (`self.history`): no tensorboard in this image.
+* TensorBoard / file logging are replaced by a plain list of per-step records (`self.history`): no tensorboard in this image;
+* a loader may yield `vlatouch.ctrl_data.StoreBatch` objects in place of collated dicts (`ControllerStoreModule`): the batch is then assembled
+  on the device from resident episodes and cached CLS features, and every step, epoch and checkpoint function takes either kind.
 """
 from __future__ import annotations
 
@@ -21,6 +23,7 @@ from typing import Dict, Optional
 import torch
 
 from vlatouch import _lib as L
+from vlatouch.ctrl_data import StoreBatch
 from vlatouch.engine import concat_obs
 from vlatouch.train import SITrainer
 
@@ -48,8 +51,11 @@ class DiffusionControllerTrainer:
 
     # ------------------------------------------------------------------------------------------------ batch preparation
     def _prepare_batch_for_diffusion(self, batch) -> Dict[str, torch.Tensor]:
-        states, forces = batch['states'], batch['forces']
         cf = (self.controller.model_args or {}).get('context_frames', 2)
+        if isinstance(batch, StoreBatch):      # device-resident episodes (vlatouch/ctrl_data.py): the same mapping from one vt_ctrl_batch call
+            return batch.store.assemble_for(self.controller, batch.index, layout="bridge", kin=self.trainer.mlp.kin, use_force=self.use_force,
+                                            context_frames=cf)
+        states, forces = batch['states'], batch['forces']
         current_state, current_forces, future_forces = states[:, cf - 1], forces[:, cf - 1], forces[:, cf:]
         vla_n = normalize_actions(batch['vla_actions'], self.stats, 'vla')
         expert_n = normalize_actions(batch['expert_actions'], self.stats, 'expert')

@@ -5,7 +5,8 @@ Same constructor, `_prepare_batch`, `train`, `_train_epoch`, `_evaluate`, `_save
 `trainable_modules` (:26-30), cosine LR (:31-33), back-propagation through the T ticks of both LSTM layers.  `_prepare_batch` returns
 `obs_in` ([cls_cam1 | cls_cam2 | state], the obs_encoder's input) next to the other entries because the obs_encoder is trained through the
 loss; TensorBoard / file logging are replaced by `self.history`.  In `controller.train()` mode the two dropouts draw keep-masks on the
-device; `_evaluate` runs without them, as `controller.eval()` does in the reference.
+device; `_evaluate` runs without them, as `controller.eval()` does in the reference.  A loader may yield `vlatouch.ctrl_data.StoreBatch`
+objects in place of collated dicts (`ControllerStoreModule`); `_prepare_batch` then assembles the batch on the device.
 """
 from __future__ import annotations
 
@@ -15,6 +16,7 @@ from typing import Dict
 import torch
 
 from vlatouch import _lib as L
+from vlatouch.ctrl_data import StoreBatch
 from vlatouch.engine import concat_obs
 from vlatouch.train import LstmTrainer
 
@@ -42,6 +44,8 @@ class LSTMControllerTrainer:
 
     def _prepare_batch(self, batch) -> Dict[str, torch.Tensor]:
         cf = 2
+        if isinstance(batch, StoreBatch):      # device-resident episodes (vlatouch/ctrl_data.py): the same mapping from one vt_ctrl_batch call
+            return batch.store.assemble_for(self.controller, batch.index, layout="lstm", kin=self.trainer.obs.kin, context_frames=cf)
         current_state = batch['states'][:, cf - 1]
         forces = batch['forces'][:, cf - 1:-1]
         vla_n = normalize_actions(batch['vla_actions'], self.controller.stats, 'vla')

@@ -317,6 +317,9 @@ SIGNATURES = {
     "vt_colorjitter_workspace_bytes": (_Z, [_I]),
     "vt_colorjitter": (_I, [_P, _P, _I, _I, _P, _P, _Z, _P]),
     "vt_rdt_batch": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, C.c_double, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "vt_ctrl_batch": (_I, [_P, _P, _P, _P, _P, _P, _I, C.c_longlong, _I, _I, _I, C.c_longlong, _P, _F, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P,
+                           _P, _P]),
+    "vt_ctrl_pixsum": (_I, [_P, C.c_longlong, _I, _P, _P]),
     "vt_marker_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     "vt_marker_detect": (_I, [_P, _I, _I, _I, _I, _I, C.c_double, C.c_double, _I, _P, _P, _I, _P, _P, _P]),
     "vt_marker_displacement": (_I, [_P, _P, _I, _I, _P, _I, _P, _P, _P]),
