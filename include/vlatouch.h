@@ -628,6 +628,32 @@ size_t vt_colorjitter_workspace_bytes(int n);
 int vt_colorjitter(const vt_colorjitter_frame* frames_host, const void* frames_dev, int n, int flags, void* out, void* ws, size_t ws_bytes,
                    vt_stream_t stream);
 
+/* ---- the pixel mapping of a JPEG round trip of camera frames (residual_controller/frank_inference_eef.py:84-87 and
+ * data/create_controller_dataset_episode.py:54-62: cv2.imencode('.jpg') -> cv2.imdecode, "to align with training").  Bit-identical to
+ * libjpeg with jpeg_set_defaults at `quality` (Annex K tables scaled as jpeg_set_quality does, 4:2:0, islow DCT) and a default decompress
+ * (islow, fancy up-sampling; components at most 2 samples wide are replicated, as jdsample.c does); the entropy coder is lossless and is
+ * not run.  uint8 HWC in (pitched), uint8 HWC out, frame i tight (pitch 3 * w) at out + out_off; source and output must not overlap.
+ * flags: VT_JPEGMAP_CV2_ORDER: channel 0 of the array plays blue's role, as cv2 treats whatever it is given; without it channel 0 is red.
+ * Two launches: per 16 x 16 MCU the conversion, down-sampling, forward DCT, quantise / dequantise and inverse DCT into the decoded planes
+ * Y' | Cb' | Cr' in `ws` (1.5 bytes per pixel of the frame padded to multiples of 16), then per output pixel the up-sampling and the
+ * conversion back.  int32 arithmetic, no atomics: a pure function of the inputs.  No host read, allocation or synchronisation.
+ * vt_jpegmap_workspace_bytes checks the table, WRITES every record's ws_off and returns the bytes vt_jpegmap needs (0 on a bad table, see
+ * vt_last_error); copy the table to the device after it.  The table is passed as host memory (checked here) and as the same bytes in device
+ * memory (read by the kernels).  n < 1, a null source, h < 1, w < 1, a side above 32768, pitch < 3 * w, quality outside 1..100, unknown flag
+ * bits, a ws_off that vt_jpegmap_workspace_bytes did not write and a short or misaligned (8 bytes) workspace return VT_ERR_ARG without a
+ * launch. */
+typedef struct {
+  const void* src;      /* uint8 HWC, device */
+  long pitch;           /* bytes between rows of src, >= 3 * w */
+  int h, w;             /* frame size */
+  long out_off;         /* byte offset of this frame's output in `out` */
+  long ws_off;          /* written by vt_jpegmap_workspace_bytes */
+} vt_jpegmap_frame;
+#define VT_JPEGMAP_CV2_ORDER 1
+size_t vt_jpegmap_workspace_bytes(vt_jpegmap_frame* frames_host, int n);
+int vt_jpegmap(const vt_jpegmap_frame* frames_host, const void* frames_dev, int n, int quality, int flags, void* out, void* ws,
+               size_t ws_bytes, vt_stream_t stream);
+
 /* ---- one fine-tuning micro-batch out of device-resident episodes (vlatouch/rdt_data.py).  Stands for, per sample,
  * UnifiedVLADataset.parse_file (data/unified_vla_dataset_episode.py:314-351: state row, action chunk from action_id = step_id + 2 padded
  * with its last row, the episode's std / norm, fill_in_state), VLAConsumerDataset.__getitem__ (train/dataset.py:327-344: control frequency,

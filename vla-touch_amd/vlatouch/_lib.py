@@ -162,6 +162,13 @@ class ColorJitterFrame(C.Structure):     # vt_colorjitter_frame (operation ids: 
 COLORJITTER_LIFT = 1
 
 
+class JpegmapFrame(C.Structure):     # vt_jpegmap_frame
+    _fields_ = [("src", C.c_void_p), ("pitch", C.c_long), ("h", C.c_int), ("w", C.c_int), ("out_off", C.c_long), ("ws_off", C.c_long)]
+
+
+JPEGMAP_CV2_ORDER = 1
+
+
 class LstmDesc(C.Structure):
     _fields_ = [("state_dim", C.c_int), ("hidden", C.c_int), ("layers", C.c_int), ("force_dim", C.c_int),
                 ("force_pad", C.c_int), ("in_pad", C.c_int), ("cdt", C.c_int)]
@@ -316,6 +323,8 @@ SIGNATURES = {
     "vt_imgprep": (_I, [_P, _P, _I, _I, _P, C.c_uint, _I, _P, _P, _Z, _P]),
     "vt_colorjitter_workspace_bytes": (_Z, [_I]),
     "vt_colorjitter": (_I, [_P, _P, _I, _I, _P, _P, _Z, _P]),
+    "vt_jpegmap_workspace_bytes": (_Z, [_P, _I]),
+    "vt_jpegmap": (_I, [_P, _P, _I, _I, _I, _P, _P, _Z, _P]),
     "vt_rdt_batch": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, C.c_double, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vt_ctrl_batch": (_I, [_P, _P, _P, _P, _P, _P, _I, C.c_longlong, _I, _I, _I, C.c_longlong, _P, _F, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P,
                            _P, _P]),

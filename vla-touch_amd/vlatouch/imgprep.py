@@ -13,6 +13,8 @@ Host side of the feature:
     a graph together with the tower.
   * `jitter=`: the training-time ColorJitter (vlatouch/imgaug.py, csrc/vt_colorjitter.hip) between the `image_size` pre-resize and the
     pad, where the reference's dataset applies it (train/dataset.py:373-409): Resize -> lift -> jitter -> pad -> resize -> normalise.
+  * `jpeg=`: the reference's cv2 JPEG round trip of the raw frames (vlatouch/jpegmap.py, csrc/vt_jpegmap.hip) ahead of all of the above,
+    where the robot loop and the labeller apply it: JPEG -> Resize -> lift -> jitter -> pad -> resize -> normalise.
 
 All launches go to the current stream; the staging buffers are reused from call to call on the assumption that calls are issued in
 stream order (the pinned buffer itself is guarded by an event).
@@ -238,8 +240,8 @@ class DevicePreprocessor:
             raise _lib.VtError("vt_imgprep_workspace_bytes: " + L.vt_last_error().decode())
         return arr, ws_bytes, off
 
-    def _plan(self, items, ws_ptr: Optional[int], jit: bool = False):
-        key = (tuple(items), ws_ptr, self.force_two_pass, jit)
+    def _plan(self, items, ws_ptr: Optional[int], jit: bool = False, jpeg_idx: Optional[tuple] = None):
+        key = (tuple(items), ws_ptr, self.force_two_pass, jit, jpeg_idx)
         plan = self._plans.get(key)
         if plan is not None:
             return plan
@@ -247,19 +249,31 @@ class DevicePreprocessor:
             self._plans = {k: v for k, v in self._plans.items() if v.get("captured")}
         n = len(items)
         flags = self.flags | (_lib.IMGPREP_TWO_PASS if self.force_two_pass else 0)
-        plan = {"pre": None}
+        plan = {"pre": None, "jpeg": None}
         total = 0
-        if self.image_size is not None:                   # step 1: bilinear pre-resize into uint8 frames at the head of the workspace
+        # every later stage's table needs addresses inside the workspace: sized first with a placeholder base
+        base = ws_ptr if ws_ptr is not None else 4096
+        if jpeg_idx:
+            # the JPEG round trip of the raw frames (vlatouch/jpegmap.py), ahead of everything else as in the reference: frames that exist
+            # are mapped into tight uint8 frames at the head of the workspace, which the next stage reads; a missing frame's fill is not
+            from .jpegmap import jpeg_table
+            jarr, jout, jws = jpeg_table([items[i] for i in jpeg_idx])
+            plan["jpeg"] = {"arr": jarr, "n": len(jpeg_idx), "out_off": 0, "ws_off": _align(jout, 256), "ws_bytes": jws}
+            if ws_ptr is not None:
+                plan["jpeg"]["dev"] = self._to_device(jarr)
+            total = _align(jout, 256) + _align(jws, 256)
+            items = list(items)
+            for k, i in enumerate(jpeg_idx):
+                items[i] = (base + jarr[k].out_off, jarr[k].h, jarr[k].w, 3 * jarr[k].w)
+        if self.image_size is not None:                   # step 1: bilinear pre-resize into uint8 frames of the workspace
             sizes = [self._resized(it[1], it[2]) for it in items]
             arr1, ws1, out1 = self._stage(items, _lib.IMGPREP_OUT_U8, 0, sizes, BILINEAR)
-            plan["pre"] = {"arr": arr1, "out_off": 0, "ws_off": _align(out1, 256), "ws_bytes": ws1}
-            total = _align(out1, 256) + _align(ws1, 256)
-            mid = [(None, sizes[i][0], sizes[i][1], 3 * sizes[i][1], arr1[i].out_off) for i in range(n)]
+            plan["pre"] = {"arr": arr1, "out_off": total, "ws_off": total + _align(out1, 256), "ws_bytes": ws1}
+            mid = [(None, sizes[i][0], sizes[i][1], 3 * sizes[i][1], total + arr1[i].out_off) for i in range(n)]
+            total += _align(out1, 256) + _align(ws1, 256)
         else:
             mid = None
         plan["flags"], plan["main_off"] = flags, total
-        # the main stage's table needs the addresses of the pre-resized frames, i.e. the workspace: sized first with a placeholder base
-        base = ws_ptr if ws_ptr is not None else 4096
         main_items = items if mid is None else [(base + m[4], m[1], m[2], m[3]) for m in mid]
         if jit:
             # the jitter stage: every frame that exists goes through it (an unjittered one with an empty operation list) into tight uint8
@@ -317,30 +331,43 @@ class DevicePreprocessor:
                 raise _lib.VtError(f"jitter entry {i} belongs to a missing frame (the reference never augments an invalid image)")
         return jitter if any(p is not None for p in jitter) else None
 
-    def workspace_bytes(self, images: Sequence, jitter=None) -> int:
-        """Bytes of workspace a call on these frames needs (geometry only, plus whether any frame is jittered)."""
+    @staticmethod
+    def _jpeg_idx(images: Sequence, jpeg):
+        """`jpeg` checked -> (quality, the indices of the frames that exist) or (None, None)."""
+        if jpeg is None:
+            return None, None
+        if isinstance(jpeg, bool) or not isinstance(jpeg, (int, np.integer)) or not 1 <= int(jpeg) <= 100:
+            raise _lib.VtError(f"jpeg must be None or a quality in 1..100, got {jpeg!r}")
+        return int(jpeg), tuple(i for i, im in enumerate(images) if im is not None)
+
+    def workspace_bytes(self, images: Sequence, jitter=None, jpeg=None) -> int:
+        """Bytes of workspace a call on these frames needs (geometry only, plus whether any frame is jittered or JPEG-mapped)."""
         jit = self._jitter_list(images, jitter) is not None
         items, _ = self._gather(images)
-        return self._plan(items, None, jit)["ws_bytes"]
+        return self._plan(items, None, jit, self._jpeg_idx(images, jpeg)[1])["ws_bytes"]
 
     @torch.no_grad()
-    def __call__(self, images: Sequence, out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None, jitter=None) -> torch.Tensor:
+    def __call__(self, images: Sequence, out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None, jitter=None,
+                 jpeg=None) -> torch.Tensor:
         """-> pixel_values [n, 3, S, S].  `jitter`: None, or one entry per frame, each None or a `ColorJitterParams` (never on a missing
         frame).  Without it, or with every entry None, the call is the unjittered one: same launches, same bits, capturable in a graph.
         A call that jitters writes its parameters into a device table through a pinned buffer and waits for the previous such copy, so
-        it is not capturable in a graph."""
+        it is not capturable in a graph.
+        `jpeg`: None, or the quality of the reference's cv2 JPEG round trip (vlatouch/jpegmap.py, order "cv2"), applied to every frame
+        that exists before anything else.  Its table is cached with the plan: the call stays as capturable as the plain one."""
         n = len(images)
         if n < 1:
             raise _lib.VtError("DevicePreprocessor: no frames")
         S = self.S
         jitter = self._jitter_list(images, jitter)
         jit = jitter is not None
+        quality, jpeg_idx = self._jpeg_idx(images, jpeg)
         if jit and torch.cuda.is_current_stream_capturing():
             raise _lib.VtError("DevicePreprocessor: a call with jitter= cannot be captured in a graph")
         with torch.cuda.device(self.device):
             items, keep = self._gather(images)
             if workspace is None:
-                need = self._plan(items, None, jit)["ws_bytes"]
+                need = self._plan(items, None, jit, jpeg_idx)["ws_bytes"]
                 if self._ws is None or self._ws.numel() < need:
                     if self._ws is not None and any(v.get("captured") for v in self._plans.values()):
                         self._keepalive.append(self._ws)          # a captured graph still works in the old one
@@ -348,7 +375,7 @@ class DevicePreprocessor:
                 workspace = self._ws
             elif workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.device != self.device:
                 raise _lib.VtError("workspace must be a contiguous uint8 tensor on the preprocessor's device")
-            plan = self._plan(items, workspace.data_ptr(), jit)
+            plan = self._plan(items, workspace.data_ptr(), jit, jpeg_idx)
             if torch.cuda.is_current_stream_capturing():
                 plan["captured"] = True
             if workspace.numel() < plan["ws_bytes"]:
@@ -359,6 +386,10 @@ class DevicePreprocessor:
                 raise _lib.VtError(f"out must be a contiguous {self.dtype} [{n}, 3, {S}, {S}] tensor on {self.device}")
             L, st = _lib.lib(), _lib.stream_ptr(self.device)
             wp = workspace.data_ptr()
+            jm = plan["jpeg"]
+            if jm is not None:
+                _lib.check(L.vt_jpegmap(jm["arr"], _lib.ptr(jm["dev"]), jm["n"], quality, _lib.JPEGMAP_CV2_ORDER, C.c_void_p(wp + jm["out_off"]),
+                                        C.c_void_p(wp + jm["ws_off"]), jm["ws_bytes"], st), "vt_jpegmap")
             pre = plan["pre"]
             if pre is not None:
                 _lib.check(L.vt_imgprep(pre["arr"], _lib.ptr(pre["dev"]), n, 0, None, 0, _lib.IMGPREP_OUT_U8, C.c_void_p(wp + pre["out_off"]),

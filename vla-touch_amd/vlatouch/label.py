@@ -7,8 +7,10 @@ dummy, :50-97) and calls `policy.step(proprio=qpos[t], images=[ext_{t-1}, right_
   * every distinct frame goes through the SigLIP tower ONCE (a frame serves the windows of t and t+1; the None slots are one cached
     background image): 2 image encodes per timestep instead of 6, in large batches;
   * the RDT chunks of `batch` timesteps are generated together (323 vs 32 chunks/s at batch 32 vs 1 on an MI355X).
-Frames are expected already padded/resized for SigLIP (the `camera{1,2}_resized` arrays the reference's labeller writes); the
-reference's cv2 JPEG round trip (:53-57, "to align with training") is data preparation and is not reproduced (no cv2 here).
+Frames are expected already padded/resized for SigLIP (the `camera{1,2}_resized` arrays the reference's labeller writes).  The
+reference's cv2 JPEG round trip of every frame (:53-57, "to align with training") is `jpeg_mapping=True`: on the card
+(csrc/vt_jpegmap.hip, ahead of the resize) with the model's device preprocessing, through Pillow without it; both give the pixels of
+vlatouch.jpegmap.jpeg_mapping, which is pinned to libjpeg-turbo and UNPINNED against cv2 itself (see that module).
 """
 from __future__ import annotations
 
@@ -19,34 +21,39 @@ import torch
 
 
 @torch.no_grad()
-def encode_frames(model, frames: Sequence, batch: int = 48) -> torch.Tensor:
-    """frames: sequence of HxWx3 uint8 arrays / PIL images / None -> SigLIP tokens [n, num_patches, hidden] on the model's device."""
+def encode_frames(model, frames: Sequence, batch: int = 48, jpeg_mapping=False) -> torch.Tensor:
+    """frames: sequence of HxWx3 uint8 arrays / PIL images / None -> SigLIP tokens [n, num_patches, hidden] on the model's device.
+    jpeg_mapping: False, True (quality 95) or a quality: the reference's JPEG round trip of every frame that exists, first."""
     from PIL import Image
+    from .jpegmap import jpeg_mapped_pil, jpeg_quality
+    quality = jpeg_quality(jpeg_mapping)
     out = []
     for i in range(0, len(frames), batch):
         if getattr(model, "device_preprocess", False):
-            px = model.preprocess_images_device(list(frames[i:i + batch]))       # raw bytes up in one copy, resized and normalised on the card
+            kw = {} if quality is None else {"jpeg": quality}
+            px = model.preprocess_images_device(list(frames[i:i + batch]), **kw)   # raw bytes up in one copy, mapped, resized and normalised on the card
         else:
             pil = [None if f is None else (f if isinstance(f, Image.Image) else Image.fromarray(np.asarray(f))) for f in frames[i:i + batch]]
-            px = model.preprocess_images(pil).to(model.device, dtype=model.dtype)
+            px = model.preprocess_images(jpeg_mapped_pil(pil, quality)).to(model.device, dtype=model.dtype)
         out.append(model.vision_model(px))
     return torch.cat(out, dim=0)
 
 
 @torch.no_grad()
 def label_episode(model, frames_cam1: Sequence, frames_cam2: Sequence, qpos, lang_embeddings: torch.Tensor, *, batch: int = 32,
-                  noise: Optional[torch.Tensor] = None, encode_batch: int = 48) -> np.ndarray:
+                  noise: Optional[torch.Tensor] = None, encode_batch: int = 48, jpeg_mapping=False) -> np.ndarray:
     """VLA action chunks for every timestep of an episode: [N, horizon, 10] float32 (gripper back in 0..255), what the reference's
     per-timestep loop stores as `vla_action`.
 
     model: scripts.franka_model_eef.RoboticDiffusionTransformerModel;  frames_cam{1,2}: N frames each (ext / right-wrist camera);
     qpos [N, 10] (utils_eef.converted_ee_pose_with_gripper);  lang_embeddings [1, L, lang_dim] cached instruction embedding;
-    noise: optional [N, horizon, action_dim] start noise per timestep (the reference draws it inside predict_action)."""
+    noise: optional [N, horizon, action_dim] start noise per timestep (the reference draws it inside predict_action);
+    jpeg_mapping: as in `encode_frames` (the reference's labeller maps every frame)."""
     N = len(frames_cam1)
     assert len(frames_cam2) == N and len(qpos) == N
     dev, dt = model.device, model.dtype
-    tok1 = encode_frames(model, list(frames_cam1), encode_batch)             # [N, P, D]
-    tok2 = encode_frames(model, list(frames_cam2), encode_batch)
+    tok1 = encode_frames(model, list(frames_cam1), encode_batch, jpeg_mapping)             # [N, P, D]
+    tok2 = encode_frames(model, list(frames_cam2), encode_batch, jpeg_mapping)
     bg = encode_frames(model, [None], 1)[0]                                  # the None slots: one background image
     qpos = torch.as_tensor(np.asarray(qpos), dtype=torch.float32, device=dev)
     text = lang_embeddings.to(dev, dtype=dt)
