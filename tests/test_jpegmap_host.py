@@ -147,3 +147,16 @@ def test_bad_order_and_frames_raise():
         for bad in (a.astype(np.float32), a[..., 0], a[..., :2], np.zeros((0, 4, 3), np.uint8)):
             with pytest.raises(ValueError):
                 fn(bad, 95)
+
+
+def test_the_device_mapping_refuses_a_cpu_device_as_the_preprocessor_does():
+    """`jpeg_mapping_device` stands on a frame stager of its own, which has no CPU route either."""
+    from vlatouch import _lib
+    from vlatouch.imgprep import DevicePreprocessor, FrameStager
+    from vlatouch.jpegmap import jpeg_mapping_device
+    with pytest.raises(_lib.VtError):
+        jpeg_mapping_device([J.make_frame("noise", 8, 8)], device="cpu")
+    with pytest.raises(_lib.VtError):
+        FrameStager("cpu")
+    with pytest.raises(_lib.VtError):
+        DevicePreprocessor(16, (0.5,) * 3, (0.5,) * 3, "cpu")

@@ -18,7 +18,8 @@
 #include <stdint.h>
 #include <limits.h>
 #include "vt_common.h"
-#include "vt_host.h"
+#include "vt_frames.h"
+#include "vt_pixel.h"
 #include "../../include/vlatouch.h"
 
 #pragma clang fp contract(off)   // after the includes: it governs every expression of this file, and only those
@@ -28,15 +29,11 @@ constexpr int kSumBlocks = 64;   // blocks per frame of colorjitter_sum_kernel =
 constexpr int kSums = 3;         // per frame: byte sum, sum of L (unlifted), sum of L (lifted)
 constexpr int kNT = 256;
 
-__device__ __forceinline__ int clip8(const int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
-// ImageEnhance.Brightness(1.75) against black: min(255, (int)(1.75f * v)); 1.75f * v is exact, so the truncation is (7 v) >> 2
-__device__ __forceinline__ int lift8(const int v) { const int t = (v * 7) >> 2; return t > 255 ? 255 : t; }
 // Image.blend(a, b, f) of one byte; for 0 <= f <= 1 PIL truncates without clipping, where t lies in [0, 255] anyway
 __device__ __forceinline__ int blend8(const int a, const int b, const float f) {
   const float t = (float)a + f * (float)(b - a);
   return t <= 0.f ? 0 : (t >= 255.f ? 255 : (int)t);
 }
-__device__ __forceinline__ int luma8(const int r, const int g, const int b) { return (19595 * r + 38470 * g + 7471 * b + 0x8000) >> 16; }
 
 // Pillow's rgb2hsv, H += shift (mod 256), hsv2rgb
 __device__ __forceinline__ void hue_px(int& r, int& g, int& b, const int shift) {
@@ -107,13 +104,8 @@ __device__ __forceinline__ int load_run(const vt_colorjitter_frame& f, const int
   x0 = (it - row * rpr) << 2;
   const int npx = f.w - x0 < 4 ? f.w - x0 : 4;
   const uint8_t* sp = (const uint8_t*)f.src + (long)row * f.pitch + 3L * x0;
-  if (npx == 4 && ((uintptr_t)sp & 3) == 0) {
-    const uint32_t a = ((const uint32_t*)sp)[0], b = ((const uint32_t*)sp)[1], c = ((const uint32_t*)sp)[2];
-    px[0] = a & 0xffffffu;
-    px[1] = (a >> 24) | ((b & 0xffffu) << 8);
-    px[2] = (b >> 16) | ((c & 0xffu) << 16);
-    px[3] = c >> 8;
-  } else {
+  if (npx == 4 && ((uintptr_t)sp & 3) == 0) load_px4(sp, px);
+  else {
     for (int j = 0; j < 4; ++j) {
       px[j] = 0;
       if (j < npx) px[j] = (uint32_t)sp[3 * j] | ((uint32_t)sp[3 * j + 1] << 8) | ((uint32_t)sp[3 * j + 2] << 16);
@@ -151,16 +143,7 @@ __global__ void __launch_bounds__(kNT) colorjitter_sum_kernel(const vt_colorjitt
     }
     tot[0] += s0; tot[1] += s1; tot[2] += s2;
   }
-  __shared__ unsigned long long part[kSums][kNT / 64];
-  for (int k = 0; k < kSums; ++k) {
-    unsigned long long v = tot[k];
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    if ((threadIdx.x & 63) == 0) part[k][threadIdx.x >> 6] = v;
-  }
-  __syncthreads();
-  // one partial per block and sum, every slot rewritten by every call: nothing to zero beforehand, no atomics
-  if (threadIdx.x < kSums)
-    sums[((long)blockIdx.y * kSums + threadIdx.x) * kSumBlocks + blockIdx.x] = part[threadIdx.x][0] + part[threadIdx.x][1] + part[threadIdx.x][2] + part[threadIdx.x][3];
+  block_sums_store(tot, sums + (long)blockIdx.y * kSums * kSumBlocks + blockIdx.x, kSumBlocks);
 }
 
 // the frame's sum k: every lane of the wave adds one block's partial
@@ -176,9 +159,7 @@ __global__ void __launch_bounds__(kNT) colorjitter_apply_kernel(const vt_colorji
   const vt_colorjitter_frame f = frames[i];
   const int items = f.h * ((f.w + 3) >> 2);
   if ((long)blockIdx.x * kNT >= items) return;         // block-uniform: the shuffles below see whole waves
-  bool lift = false;
-  if (flags & VT_COLORJITTER_LIFT)                     // the host's test, in double: sum / (h * w * 255.0 * 3) <= 0.15
-    lift = (double)frame_sum(sums, i, 0) / ((double)((long)f.h * f.w) * 255.0 * 3.0) <= 0.15;
+  const bool lift = (flags & VT_COLORJITTER_LIFT) && lift_decision(frame_sum(sums, i, 0), f.h, f.w);
   int mean = 0;
   if (contrast_slot(f) >= 0)                           // ImageEnhance.Contrast: int(ImageStat.Stat(image.convert("L")).mean[0] + 0.5)
     mean = (int)((double)frame_sum(sums, i, lift ? 2 : 1) / (double)((long)f.h * f.w) + 0.5);
@@ -193,39 +174,25 @@ __global__ void __launch_bounds__(kNT) colorjitter_apply_kernel(const vt_colorji
     apply_slots(f, 4, mean, r, g, b);
     px[j] = (uint32_t)r | ((uint32_t)g << 8) | ((uint32_t)b << 16);
   }
-  uint8_t* dp = out + f.out_off + ((long)row * f.w + x0) * 3;
-  if (npx == 4 && ((uintptr_t)dp & 3) == 0) {
-    ((uint32_t*)dp)[0] = px[0] | (px[1] << 24);
-    ((uint32_t*)dp)[1] = (px[1] >> 8) | (px[2] << 16);
-    ((uint32_t*)dp)[2] = (px[2] >> 16) | (px[3] << 8);
-  } else {
-    for (int j = 0; j < npx; ++j) {
-      dp[3 * j] = (uint8_t)px[j]; dp[3 * j + 1] = (uint8_t)(px[j] >> 8); dp[3 * j + 2] = (uint8_t)(px[j] >> 16);
-    }
-  }
+  store_px4(out + f.out_off + ((long)row * f.w + x0) * 3, px, npx);
 }
 
-inline size_t align_up(const size_t v, const size_t a) { return (v + a - 1) / a * a; }
+inline size_t sums_bytes(const int n) { return vt_round256((size_t)n * kSums * kSumBlocks * sizeof(unsigned long long)); }
 }  // namespace
 
 extern "C" size_t vt_colorjitter_workspace_bytes(int n) {
   if (n < 1) { vt_fail(VT_ERR_ARG, "vt_colorjitter_workspace_bytes: n < 1"); return 0; }
-  return align_up((size_t)n * kSums * kSumBlocks * sizeof(unsigned long long), 256);
+  return sums_bytes(n);
 }
 
 extern "C" int vt_colorjitter(const vt_colorjitter_frame* frames_host, const void* frames_dev, int n, int flags, void* out, void* ws,
                               size_t ws_bytes, vt_stream_t stream) {
-  if (!frames_host || n < 1) return vt_fail(VT_ERR_ARG, "vt_colorjitter: null frame table or n < 1");
-  if (n > 65535) return vt_fail(VT_ERR_ARG, "vt_colorjitter: %d frames, at most 65535 in one call", n);
-  if (flags & ~VT_COLORJITTER_LIFT) return vt_fail(VT_ERR_ARG, "vt_colorjitter: unknown flag bits %#x", flags);
+  CK(vt_frames_call_check("vt_colorjitter", frames_host, n, flags, VT_COLORJITTER_LIFT));
   bool need_sums = flags & VT_COLORJITTER_LIFT;
   long max_items = 1;
   for (int i = 0; i < n; ++i) {
     const vt_colorjitter_frame& f = frames_host[i];
-    if (!f.src) return vt_fail(VT_ERR_ARG, "vt_colorjitter: frame %d has a null source", i);
-    if (f.h < 1 || f.w < 1) return vt_fail(VT_ERR_ARG, "vt_colorjitter: frame %d has a zero size (%d x %d)", i, f.h, f.w);
-    if (f.pitch < 3L * f.w) return vt_fail(VT_ERR_ARG, "vt_colorjitter: frame %d: row pitch %ld < 3 * width %d", i, f.pitch, f.w);
-    if (f.out_off < 0) return vt_fail(VT_ERR_ARG, "vt_colorjitter: frame %d: negative out_off", i);
+    CK(vt_frame_check("vt_colorjitter", f, i));
     const long items = (long)f.h * ((f.w + 3) / 4);
     if (items > INT_MAX - kSumBlocks * kNT) return vt_fail(VT_ERR_ARG, "vt_colorjitter: frame %d of %d x %d is too large", i, f.h, f.w);
     unsigned seen = 0;
@@ -239,14 +206,11 @@ extern "C" int vt_colorjitter(const vt_colorjitter_frame* frames_host, const voi
     if (seen & (1u << VT_COLORJITTER_CONTRAST)) need_sums = true;
     max_items = items > max_items ? items : max_items;
   }
-  if (!frames_dev || !out || !ws) return vt_fail(VT_ERR_ARG, "vt_colorjitter: null device frame table, output or workspace");
-  const size_t need = align_up((size_t)n * kSums * kSumBlocks * sizeof(unsigned long long), 256);
-  if (ws_bytes < need) return vt_fail(VT_ERR_ARG, "vt_colorjitter: workspace of %zu bytes, %zu needed", ws_bytes, need);
-  if ((uintptr_t)ws & 7) return vt_fail(VT_ERR_ARG, "vt_colorjitter: the workspace must be 8-byte aligned");
+  CK(vt_frames_buffers_check("vt_colorjitter", frames_dev, out, ws, ws_bytes, sums_bytes(n), true));
   hipStream_t st = (hipStream_t)stream;
   const vt_colorjitter_frame* fd = (const vt_colorjitter_frame*)frames_dev;
   unsigned long long* sums = (unsigned long long*)ws;
   if (need_sums) hipLaunchKernelGGL(colorjitter_sum_kernel, dim3(kSumBlocks, n), dim3(kNT), 0, st, fd, flags, sums);
   hipLaunchKernelGGL(colorjitter_apply_kernel, dim3((unsigned)((max_items + kNT - 1) / kNT), n), dim3(kNT), 0, st, fd, flags, (const unsigned long long*)sums, (uint8_t*)out);
-  return vt_check_launch() ? vt_fail(VT_ERR_LAUNCH, "vt_colorjitter: launch failure") : VT_OK;
+  return vt_frames_launched("vt_colorjitter");
 }

@@ -15,7 +15,8 @@
 // Integer VALU arithmetic only; every result is a pure function of the inputs (no atomics; the brightness sum is an integer sum).
 #include <stdint.h>
 #include "vt_common.h"
-#include "vt_host.h"
+#include "vt_frames.h"
+#include "vt_pixel.h"
 #include "../../include/vlatouch.h"
 
 namespace {
@@ -51,18 +52,15 @@ __device__ __forceinline__ Ctx make_ctx(const vt_imgprep_frame& f, const int fla
   }
   c.fill = fill;
   c.lift = false;
-  if ((flags & VT_IMGPREP_BRIGHT) && c.src) {   // the host's test, in double: sum / (h * w * 255.0 * 3) <= 0.15
+  if ((flags & VT_IMGPREP_BRIGHT) && c.src) {
     unsigned long long tot = 0;
     for (int j = 0; j < kSumBlocks; ++j) tot += __hip_atomic_load(&sums[(long)i * kSumBlocks + j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    c.lift = (double)tot / ((double)((long)f.h * f.w) * 255.0 * 3.0) <= 0.15;
+    c.lift = lift_decision(tot, f.h, f.w);
   }
   return c;
 }
 
 __device__ __forceinline__ int clampi(const int v, const int lo, const int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-__device__ __forceinline__ int clip8(const int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
-// ImageEnhance.Brightness(1.75) against black: min(255, (int)(1.75f * v)); 1.75f * v is exact, so the truncation is (7 v) >> 2
-__device__ __forceinline__ int lift8(const int v) { const int t = (v * 7) >> 2; return t > 255 ? 255 : t; }
 
 // Horizontal pass of virtual rows [r0, r1) x output columns [xx0, xx1) of one frame: dst[(r - r0) * dst_stride + (xx - xx0) * 3 + c].
 // Thread tid owns element tid = (xx - xx0) * 3 + c of every row.  The real source rows of a chunk are first copied to `stage` with
@@ -209,7 +207,7 @@ __global__ void __launch_bounds__(256) imgprep_sum_kernel(const vt_imgprep_frame
   if (!f.src) return;        // a missing frame's partials are never read
   const uint8_t* src = (const uint8_t*)f.src;
   const int nb = 3 * f.w;
-  unsigned long long tot = 0;
+  unsigned long long tot[1] = {0};
   for (int row = blockIdx.x; row < f.h; row += gridDim.x) {
     const uintptr_t A = (uintptr_t)(src + (long)row * f.pitch);
     const int head = (int)(A & 3);
@@ -227,14 +225,9 @@ __global__ void __launch_bounds__(256) imgprep_sum_kernel(const vt_imgprep_frame
         }
       }
     }
-    tot += s;
+    tot[0] += s;
   }
-  for (int o = 32; o > 0; o >>= 1) tot += __shfl_down(tot, o, 64);
-  __shared__ unsigned long long part[4];
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = tot;
-  __syncthreads();
-  // one partial per block, every slot rewritten by every call: nothing to zero beforehand, no atomics
-  if (threadIdx.x == 0) sums[(long)blockIdx.y * kSumBlocks + blockIdx.x] = part[0] + part[1] + part[2] + part[3];
+  block_sums_store(tot, sums + (long)blockIdx.y * kSumBlocks + blockIdx.x, 0);
 }
 
 template <typename T>
@@ -291,19 +284,18 @@ __global__ void __launch_bounds__(kNT) imgprep_v_kernel(const vt_imgprep_frame* 
   }
 }
 
-inline size_t align_up(const size_t v, const size_t a) { return (v + a - 1) / a * a; }
 inline void virt_size(const vt_imgprep_frame& f, const int flags, int& in_h, int& in_w) {
   in_h = f.h; in_w = f.w;
   if (flags & VT_IMGPREP_PAD) in_h = in_w = f.h > f.w ? f.h : f.w;
 }
-// argument check of one call; returns 0 or a vt_fail code.  `fused` (may be null) receives whether every frame fits the fused kernel
-int check_frames(const vt_imgprep_frame* fr, const int n, const int S, const int flags, bool* fused) {
-  if (!fr || n < 1) return vt_fail(VT_ERR_ARG, "vt_imgprep: null frame table or n < 1");
+// argument check of one call; returns 0 or a vt_fail code.  `fused` receives whether every frame fits the fused kernel
+int check_frames(const vt_imgprep_frame* fr, const int n, const int S, const int flags, bool& fused) {
+  CK(vt_frames_table_check("vt_imgprep", fr, n));
   const bool u8 = flags & VT_IMGPREP_OUT_U8;
   if (u8 && (flags & (VT_IMGPREP_OUT_BF16 | VT_IMGPREP_BRIGHT | VT_IMGPREP_PAD)))
     return vt_fail(VT_ERR_ARG, "vt_imgprep: the uint8 HWC output mode takes no pad / brightness / bf16 flag");
   if (!u8 && S < 1) return vt_fail(VT_ERR_ARG, "vt_imgprep: output size S < 1");
-  bool fz = !u8 && !(flags & VT_IMGPREP_TWO_PASS);
+  fused = !u8 && !(flags & VT_IMGPREP_TWO_PASS);
   for (int i = 0; i < n; ++i) {
     const vt_imgprep_frame& f = fr[i];
     if (!f.src) {
@@ -311,7 +303,7 @@ int check_frames(const vt_imgprep_frame* fr, const int n, const int S, const int
       continue;
     }
     if (f.h < 1 || f.w < 1 || f.out_h < 1 || f.out_w < 1) return vt_fail(VT_ERR_ARG, "vt_imgprep: frame %d has a zero size (%d x %d -> %d x %d)", i, f.h, f.w, f.out_h, f.out_w);
-    if (f.pitch < 3L * f.w) return vt_fail(VT_ERR_ARG, "vt_imgprep: frame %d: row pitch %ld < 3 * width %d", i, f.pitch, f.w);
+    CK(vt_frame_pitch_check("vt_imgprep", f, i));
     if (!u8 && (f.out_h != S || f.out_w != S)) return vt_fail(VT_ERR_ARG, "vt_imgprep: frame %d: output %d x %d is not S = %d", i, f.out_h, f.out_w, S);
     int in_h, in_w;
     virt_size(f, flags, in_h, in_w);
@@ -319,23 +311,22 @@ int check_frames(const vt_imgprep_frame* fr, const int n, const int S, const int
     if (!f.coef_v && in_h != f.out_h) return vt_fail(VT_ERR_ARG, "vt_imgprep: frame %d: null vertical table but height %d != %d", i, in_h, f.out_h);
     if ((f.coef_h && f.ksize_h < 1) || (f.coef_v && f.ksize_v < 1)) return vt_fail(VT_ERR_ARG, "vt_imgprep: frame %d: tap count < 1", i);
     if (f.rows_max < 1) return vt_fail(VT_ERR_ARG, "vt_imgprep: frame %d: rows_max < 1", i);
-    if (f.rows_max > kFusedRows) fz = false;
+    if (f.rows_max > kFusedRows) fused = false;
   }
-  if (fused) *fused = fz;
   return VT_OK;
 }
 }  // namespace
 
 extern "C" size_t vt_imgprep_workspace_bytes(vt_imgprep_frame* frames, int n, int S, int flags) {
   bool fused = false;
-  if (check_frames(frames, n, S, flags, &fused)) return 0;
-  size_t off = align_up((size_t)n * kSumBlocks * sizeof(unsigned long long), 256);
+  if (check_frames(frames, n, S, flags, fused)) return 0;
+  size_t off = vt_round256((size_t)n * kSumBlocks * sizeof(unsigned long long));
   for (int i = 0; i < n; ++i) {
     frames[i].ws_off = (long)off;
     if (fused || !frames[i].src) continue;
     int in_h, in_w;
     virt_size(frames[i], flags, in_h, in_w);
-    off += align_up((size_t)in_h * frames[i].out_w * 3, 16);
+    off += vt_round16((size_t)in_h * frames[i].out_w * 3);
   }
   return off;
 }
@@ -343,14 +334,12 @@ extern "C" size_t vt_imgprep_workspace_bytes(vt_imgprep_frame* frames, int n, in
 extern "C" int vt_imgprep(const vt_imgprep_frame* frames_host, const void* frames_dev, int n, int S, const void* lut, unsigned fill_rgb,
                           int flags, void* out, void* ws, size_t ws_bytes, vt_stream_t stream) {
   bool fused = false;
-  const int r = check_frames(frames_host, n, S, flags, &fused);
-  if (r) return r;
+  CK(check_frames(frames_host, n, S, flags, fused));
   const bool u8 = flags & VT_IMGPREP_OUT_U8;
-  if (!frames_dev || !out || !ws) return vt_fail(VT_ERR_ARG, "vt_imgprep: null device frame table, output or workspace");
   if (!u8 && !lut) return vt_fail(VT_ERR_ARG, "vt_imgprep: null normalise table");
   if (!u8 && ((uintptr_t)out & 15)) return vt_fail(VT_ERR_ARG, "vt_imgprep: the output must be 16-byte aligned");
   // the workspace layout vt_imgprep_workspace_bytes gave (ws_off of every frame) must be the one in the table
-  size_t need = align_up((size_t)n * kSumBlocks * sizeof(unsigned long long), 256);
+  size_t need = vt_round256((size_t)n * kSumBlocks * sizeof(unsigned long long));
   int max_in_h = 1, max_out_h = u8 ? 1 : S, max_out_w = u8 ? 1 : S, rows_cap = 1;
   for (int i = 0; i < n; ++i) {
     const vt_imgprep_frame& f = frames_host[i];
@@ -359,7 +348,7 @@ extern "C" int vt_imgprep(const vt_imgprep_frame* frames_host, const void* frame
     virt_size(f, flags, in_h, in_w);
     if (!fused) {
       if (f.ws_off != (long)need) return vt_fail(VT_ERR_ARG, "vt_imgprep: frame %d: ws_off %ld is not the planned %zu (call vt_imgprep_workspace_bytes on the table first)", i, f.ws_off, need);
-      need += align_up((size_t)in_h * f.out_w * 3, 16);
+      need += vt_round16((size_t)in_h * f.out_w * 3);
     }
     if (u8 && f.out_off < 0) return vt_fail(VT_ERR_ARG, "vt_imgprep: frame %d: negative out_off", i);
     max_in_h = in_h > max_in_h ? in_h : max_in_h;
@@ -367,7 +356,7 @@ extern "C" int vt_imgprep(const vt_imgprep_frame* frames_host, const void* frame
     max_out_w = f.out_w > max_out_w ? f.out_w : max_out_w;
     rows_cap = f.rows_max > rows_cap ? f.rows_max : rows_cap;
   }
-  if (ws_bytes < need) return vt_fail(VT_ERR_ARG, "vt_imgprep: workspace of %zu bytes, %zu needed", ws_bytes, need);
+  CK(vt_frames_buffers_check("vt_imgprep", frames_dev, out, ws, ws_bytes, need, false));      // (this entry point never asked for an aligned workspace)
   hipStream_t st = (hipStream_t)stream;
   const vt_imgprep_frame* fd = (const vt_imgprep_frame*)frames_dev;
   unsigned long long* sums = (unsigned long long*)ws;
@@ -386,5 +375,5 @@ extern "C" int vt_imgprep(const vt_imgprep_frame* frames_host, const void* frame
     else if (bf) hipLaunchKernelGGL((imgprep_v_kernel<uint16_t>), tiles, dim3(kNT), 0, st, fd, S, (const uint16_t*)lut, fill, flags, (const uint8_t*)ws, (uint16_t*)out);
     else hipLaunchKernelGGL((imgprep_v_kernel<float>), tiles, dim3(kNT), 0, st, fd, S, (const float*)lut, fill, flags, (const uint8_t*)ws, (float*)out);
   }
-  return vt_check_launch() ? vt_fail(VT_ERR_LAUNCH, "vt_imgprep: launch failure") : VT_OK;
+  return vt_frames_launched("vt_imgprep");
 }

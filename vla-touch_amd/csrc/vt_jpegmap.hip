@@ -17,7 +17,8 @@
 // Workspace: per frame the planes Y' [H16][W16], Cb' and Cr' [H16 / 2][W16 / 2] of the frame padded to multiples of 16 (1.5 bytes per pixel).
 #include <stdint.h>
 #include "vt_common.h"
-#include "vt_host.h"
+#include "vt_frames.h"
+#include "vt_pixel.h"
 #include "../../include/vlatouch.h"
 
 namespace {
@@ -33,7 +34,6 @@ __device__ const unsigned char kBase[2][64] = {
     {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
      99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99}};
 
-__device__ __forceinline__ int clip8(const int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
 __device__ __forceinline__ int descale(const int x, const int n) { return (x + (1 << (n - 1))) >> n; }
 
 // the odd part that jfdctint and jidctint share: (t4, t5, t6, t7) -> the sums of out7 / 5 / 3 / 1 (forward) or tmp0..3 (inverse)
@@ -103,13 +103,8 @@ __global__ void __launch_bounds__(64) jpegmap_mcu_kernel(const vt_jpegmap_frame*
     const uint8_t* rowp = (const uint8_t*)f.src + (long)y * f.pitch;
     uint32_t px[4];
     const uint8_t* sp = rowp + 3L * x0;
-    if (x0 + 4 <= f.w && ((uintptr_t)sp & 3) == 0) {
-      const uint32_t a = ((const uint32_t*)sp)[0], b = ((const uint32_t*)sp)[1], c = ((const uint32_t*)sp)[2];
-      px[0] = a & 0xffffffu;
-      px[1] = (a >> 24) | ((b & 0xffffu) << 8);
-      px[2] = (b >> 16) | ((c & 0xffu) << 16);
-      px[3] = c >> 8;
-    } else {
+    if (x0 + 4 <= f.w && ((uintptr_t)sp & 3) == 0) load_px4(sp, px);
+    else {
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const uint8_t* p = rowp + 3L * min(x0 + j, f.w - 1);
@@ -122,7 +117,7 @@ __global__ void __launch_bounds__(64) jpegmap_mcu_kernel(const vt_jpegmap_frame*
     for (int j = 0; j < 4; ++j) {
       int R = px[j] & 255, G = (px[j] >> 8) & 255, B = px[j] >> 16;
       if (flags & VT_JPEGMAP_CV2_ORDER) { const int t = R; R = B; B = t; }
-      yb[j] = ((19595 * R + 38470 * G + 7471 * B + kHalf) >> 16) - 128;
+      yb[j] = ((19595 * R + 38470 * G + 7471 * B + kHalf) >> 16) - 128;      // luma8(R, G, B) written out: through the helper this kernel came out 20 bytes shorter, and it is held to its size
       cbv[j] = (-11059 * R - 21709 * G + 32768 * B + (128 << 16) + kHalf - 1) >> 16;
       crv[j] = (32768 * R - 27439 * G - 5329 * B + (128 << 16) + kHalf - 1) >> 16;
     }
@@ -238,16 +233,7 @@ __global__ void __launch_bounds__(kNT) jpegmap_upsample_kernel(const vt_jpegmap_
       if (flags & VT_JPEGMAP_CV2_ORDER) { const int t = R; R = B; B = t; }
       px[k] = (uint32_t)R | ((uint32_t)G << 8) | ((uint32_t)B << 16);
     }
-    uint8_t* dp = out + f.out_off + ((long)y * f.w + x0) * 3;
-    if (npx == 4 && ((uintptr_t)dp & 3) == 0) {
-      ((uint32_t*)dp)[0] = px[0] | (px[1] << 24);
-      ((uint32_t*)dp)[1] = (px[1] >> 8) | (px[2] << 16);
-      ((uint32_t*)dp)[2] = (px[2] >> 16) | (px[3] << 8);
-    } else {
-      for (int k = 0; k < npx; ++k) {
-        dp[3 * k] = (uint8_t)px[k]; dp[3 * k + 1] = (uint8_t)(px[k] >> 8); dp[3 * k + 2] = (uint8_t)(px[k] >> 16);
-      }
-    }
+    store_px4(out + f.out_off + ((long)y * f.w + x0) * 3, px, npx);
   }
 }
 
@@ -255,12 +241,8 @@ constexpr int kMaxSide = 32768;
 
 // the checks of one record that both entry points make; 0 or VT_ERR_ARG with the message set
 int check_frame(const char* fn, const vt_jpegmap_frame& f, const int i) {
-  if (!f.src) return vt_fail(VT_ERR_ARG, "%s: frame %d has a null source", fn, i);
-  if (f.h < 1 || f.w < 1) return vt_fail(VT_ERR_ARG, "%s: frame %d has a zero size (%d x %d)", fn, i, f.h, f.w);
-  if (f.h > kMaxSide || f.w > kMaxSide) return vt_fail(VT_ERR_ARG, "%s: frame %d of %d x %d is too large (at most %d a side)", fn, i, f.h, f.w, kMaxSide);
-  if (f.pitch < 3L * f.w) return vt_fail(VT_ERR_ARG, "%s: frame %d: row pitch %ld < 3 * width %d", fn, i, f.pitch, f.w);
-  if (f.out_off < 0) return vt_fail(VT_ERR_ARG, "%s: frame %d: negative out_off", fn, i);
-  return VT_OK;
+  CK(vt_frame_check(fn, f, i));
+  return (f.h > kMaxSide || f.w > kMaxSide) ? vt_fail(VT_ERR_ARG, "%s: frame %d of %d x %d is too large (at most %d a side)", fn, i, f.h, f.w, kMaxSide) : VT_OK;
 }
 inline size_t frame_ws_bytes(const vt_jpegmap_frame& f) {
   const PlaneGeom g = plane_geom(f.h, f.w);
@@ -269,7 +251,7 @@ inline size_t frame_ws_bytes(const vt_jpegmap_frame& f) {
 }  // namespace
 
 extern "C" size_t vt_jpegmap_workspace_bytes(vt_jpegmap_frame* frames_host, int n) {
-  if (!frames_host || n < 1) { vt_fail(VT_ERR_ARG, "vt_jpegmap_workspace_bytes: null frame table or n < 1"); return 0; }
+  if (vt_frames_table_check("vt_jpegmap_workspace_bytes", frames_host, n)) return 0;
   VtCarver ws;
   for (int i = 0; i < n; ++i) {
     if (check_frame("vt_jpegmap_workspace_bytes", frames_host[i], i)) return 0;
@@ -280,10 +262,8 @@ extern "C" size_t vt_jpegmap_workspace_bytes(vt_jpegmap_frame* frames_host, int 
 
 extern "C" int vt_jpegmap(const vt_jpegmap_frame* frames_host, const void* frames_dev, int n, int quality, int flags, void* out, void* ws,
                           size_t ws_bytes, vt_stream_t stream) {
-  if (!frames_host || n < 1) return vt_fail(VT_ERR_ARG, "vt_jpegmap: null frame table or n < 1");
-  if (n > 65535) return vt_fail(VT_ERR_ARG, "vt_jpegmap: %d frames, at most 65535 in one call", n);
+  CK(vt_frames_call_check("vt_jpegmap", frames_host, n, flags, VT_JPEGMAP_CV2_ORDER));
   if (quality < 1 || quality > 100) return vt_fail(VT_ERR_ARG, "vt_jpegmap: quality %d is not in 1..100", quality);
-  if (flags & ~VT_JPEGMAP_CV2_ORDER) return vt_fail(VT_ERR_ARG, "vt_jpegmap: unknown flag bits %#x", flags);
   long max_mcus = 1, max_items = 1;
   VtCarver need;
   for (int i = 0; i < n; ++i) {
@@ -298,14 +278,12 @@ extern "C" int vt_jpegmap(const vt_jpegmap_frame* frames_host, const void* frame
     max_mcus = mcus > max_mcus ? mcus : max_mcus;
     max_items = items > max_items ? items : max_items;
   }
-  if (!frames_dev || !out || !ws) return vt_fail(VT_ERR_ARG, "vt_jpegmap: null device frame table, output or workspace");
-  if (ws_bytes < need.o) return vt_fail(VT_ERR_ARG, "vt_jpegmap: workspace of %zu bytes, %zu needed", ws_bytes, need.o);
-  if ((uintptr_t)ws & 7) return vt_fail(VT_ERR_ARG, "vt_jpegmap: the workspace must be 8-byte aligned");
+  CK(vt_frames_buffers_check("vt_jpegmap", frames_dev, out, ws, ws_bytes, need.o, true));
   const int scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;      // jpeg_quality_scaling
   hipStream_t st = (hipStream_t)stream;
   const vt_jpegmap_frame* fd = (const vt_jpegmap_frame*)frames_dev;
   hipLaunchKernelGGL(jpegmap_mcu_kernel, dim3((unsigned)max_mcus, n), dim3(64), 0, st, fd, scale, flags, (uint8_t*)ws);
   hipLaunchKernelGGL(jpegmap_upsample_kernel, dim3((unsigned)((max_items + kNT - 1) / kNT), n), dim3(kNT), 0, st, fd, flags, (const uint8_t*)ws,
                      (uint8_t*)out);
-  return vt_check_launch() ? vt_fail(VT_ERR_LAUNCH, "vt_jpegmap: launch failure") : VT_OK;
+  return vt_frames_launched("vt_jpegmap");
 }

@@ -7,10 +7,12 @@ Host side of the feature:
     (src/libImaging/Resample.c).  Cached per geometry, on the host and on the device.
   * `norm_table(mean, std, dtype)`: the 256 possible outputs of a channel, built with the very expressions of
     `SiglipPreprocessor.preprocess` and torch's own cast, so the kernel only looks up.
-  * `DevicePreprocessor`: frames of any accepted kind -> one pinned staging buffer -> one host-to-device copy of raw bytes ->
-    `vt_imgprep`.  Device-resident frames (pitched views included) are used in place; with frames of an already-seen geometry at
-    already-seen addresses the call allocates nothing (given `out=`), copies nothing and never synchronises, so it can be captured in
-    a graph together with the tower.
+  * `FrameStager`: frames of any accepted kind -> one pinned staging buffer -> one host-to-device copy of raw bytes; device-resident
+    frames (pitched views included) are used in place.  `DevicePreprocessor` owns one, `jpeg_mapping_device` one per device.
+  * `DevicePreprocessor`: the stager's frames -> a list of stages, each one driver call (`_JpegStage`, `_ResampleStage` for the pre-resize
+    and for the main pass, `_JitterStage`), planned in one loop that carves the workspace and launched in one loop.  With frames of an
+    already-seen geometry at already-seen addresses the call allocates nothing (given `out=`), copies nothing and never synchronises,
+    so it can be captured in a graph together with the tower.
   * `jitter=`: the training-time ColorJitter (vlatouch/imgaug.py, csrc/vt_colorjitter.hip) between the `image_size` pre-resize and the
     pad, where the reference's dataset applies it (train/dataset.py:373-409): Resize -> lift -> jitter -> pad -> resize -> normalise.
   * `jpeg=`: the reference's cv2 JPEG round trip of the raw frames (vlatouch/jpegmap.py, csrc/vt_jpegmap.hip) ahead of all of the above,
@@ -30,6 +32,7 @@ import torch
 
 from . import _lib
 from .imgaug import OP_NONE, ColorJitterParams
+from .jpegmap import jpeg_table
 
 BILINEAR, BICUBIC = 1, 2
 _SUPPORT = {BILINEAR: 1.0, BICUBIC: 2.0}
@@ -100,66 +103,28 @@ def _align(v: int, a: int) -> int:
     return (v + a - 1) // a * a
 
 
-class DevicePreprocessor:
-    """`preprocess_images` of one model configuration on one device.  image_size / pad / brightness as in the wrapper."""
+_SIZING_BASE = 4096     # the drivers size only tables whose sources are set: where a plan is sized before there is a workspace, it stands at this address
 
-    def __init__(self, size: int, image_mean, image_std, device, dtype: torch.dtype = torch.float32, *, pad: bool = True,
-                 brightness: bool = False, image_size=None, rescale_factor: float = 1 / 255.0):
+
+class FrameStager:
+    """Frames of every accepted kind -> (ptr, h, w, pitch) on one device: PIL images, uint8 [H, W, 3] arrays and host tensors go through one
+    pinned buffer (guarded by an event) and up in one copy, 16 bytes apart; device tensors, pitched views included, are used in place."""
+
+    def __init__(self, device):
         self.device = _lib.require_gpu(device)
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
-        if dtype not in (torch.float32, torch.bfloat16):
-            raise _lib.VtError(f"DevicePreprocessor: fp32 or bf16 output, got {dtype}")
-        self.S, self.dtype, self.pad, self.brightness, self.image_size = int(size), dtype, bool(pad), bool(brightness), image_size
-        self.mean255 = tuple(int(x * 255) for x in image_mean)
-        self.fill = self.mean255[0] | self.mean255[1] << 8 | self.mean255[2] << 16
-        self.lut = norm_table(image_mean, image_std, dtype, rescale_factor).to(self.device)
-        self.flags = (_lib.IMGPREP_PAD if self.pad else 0) | (_lib.IMGPREP_BRIGHT if self.brightness else 0) | \
-                     (_lib.IMGPREP_OUT_BF16 if dtype == torch.bfloat16 else 0)
-        self.force_two_pass = False           # tests: run the two-launch form where the fused one would do
-        # a missing frame is the S x S fill image; the kernel writes it directly unless a pre-resize or a brightness lift could touch it
-        bg_dark = self.brightness and sum(self.mean255) / (255.0 * 3) <= 0.15
-        self._bg_as_frame = image_size is not None or bg_dark
-        self._bg: Optional[torch.Tensor] = None
-        self._tables: dict = {}               # (in, out, filter) -> (device int32 table, ksize, rows_max)
-        self._plans: dict = {}
         self._pinned: Optional[torch.Tensor] = None
         self._pinned_free: Optional[torch.cuda.Event] = None
         self._upload: Optional[torch.Tensor] = None
-        self._ws: Optional[torch.Tensor] = None
-        self._keepalive: list = []
 
-    # ---- tables
-    def _table(self, in_size: int, out_size: int, filt: int):
-        if in_size == out_size:
-            return None, 0, TILE_ROWS
-        key = (in_size, out_size, filt)
-        hit = self._tables.get(key)
-        if hit is None:
-            b, k = resample_coeffs(in_size, out_size, filt)
-            flat = np.concatenate([b.reshape(-1), k.reshape(-1)]).astype(np.int32)
-            hit = (torch.from_numpy(flat).to(self.device), int(k.shape[1]), tile_rows_max(b))
-            self._tables[key] = hit
-        return hit
-
-    def _background(self) -> torch.Tensor:
-        if self._bg is None:
-            bg = np.ones((self.S, self.S, 3), dtype=np.uint8) * np.array(self.mean255, dtype=np.uint8).reshape(1, 1, 3)
-            self._bg = torch.from_numpy(bg).to(self.device)
-        return self._bg
-
-    # ---- frames
-    def _gather(self, images: Sequence):
-        """-> list of (ptr, h, w, pitch) or None per frame, plus the tensors that must stay alive; host frames go up in one copy."""
+    def gather(self, images: Sequence, missing=None):
+        """-> per frame (ptr, h, w, pitch), or `missing` for a None entry, plus the tensors that must stay alive until the launches are queued."""
         from PIL import Image
         items, host, keep = [], [], []
         for im in images:
             if im is None:
-                if self._bg_as_frame:
-                    bg = self._background()
-                    items.append((bg.data_ptr(), self.S, self.S, 3 * self.S))
-                else:
-                    items.append(None)
+                items.append(missing)
                 continue
             if isinstance(im, torch.Tensor) and im.is_cuda:
                 if im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3:
@@ -204,6 +169,160 @@ class DevicePreprocessor:
                 items[i] = (base + o, int(a.shape[0]), int(a.shape[1]), 3 * int(a.shape[1]))
         return items, keep
 
+    def to_device(self, arr) -> torch.Tensor:
+        """A ctypes table's bytes on the device."""
+        return torch.from_numpy(np.frombuffer(bytes(memoryview(arr)), dtype=np.uint8).copy()).to(self.device)
+
+
+# ---- the stages of a call.  Each kind answers the same two questions:
+#   plan(items) -> (output bytes, scratch bytes, [(frame index, offset in the output, h, w), ...]): builds `self.table` over the incoming items
+#       (ptr, h, w, pitch), None for a frame that is missing; the list names the tight uint8 frames it writes, which the next stage reads
+#   launch(wp, st, out, jitter, quality): enqueues on stream `st`, workspace at address `wp`, with this call's arguments
+# `_plan` places the output at `out_off` and the scratch at `ws_off` of the workspace and, once there is a workspace, calls bind().
+class _Stage:
+    def bind(self, stager: FrameStager) -> None:
+        self.dev = stager.to_device(self.table)
+
+
+class _JpegStage(_Stage):
+    """The JPEG round trip of the frames `idx` (those that exist; a missing frame's fill is not mapped), vlatouch/jpegmap.py."""
+
+    def __init__(self, idx):
+        self.idx = idx
+
+    def plan(self, items):
+        self.table, out_bytes, ws_bytes = jpeg_table([items[i] for i in self.idx])
+        return out_bytes, ws_bytes, [(i, f.out_off, f.h, f.w) for i, f in zip(self.idx, self.table)]
+
+    def launch(self, wp, st, out, jitter, quality):
+        _lib.check(_lib.lib().vt_jpegmap(self.table, _lib.ptr(self.dev), len(self.idx), quality, _lib.JPEGMAP_CV2_ORDER, C.c_void_p(wp + self.out_off),
+                                         C.c_void_p(wp + self.ws_off), self.ws_bytes, st), "vt_jpegmap")
+
+
+class _ResampleStage(_Stage):
+    """One vt_imgprep call of preprocessor `pp`: the uint8 pre-resize into the workspace (`final` False), or the main pass into `out`."""
+
+    def __init__(self, pp, flags: int, final: bool):
+        self.pp, self.flags, self.final = pp, flags, final
+        self.S, self.filt, self.what = (pp.S, BICUBIC, "vt_imgprep") if final else (0, BILINEAR, "vt_imgprep (pre-resize)")
+
+    def plan(self, items):
+        n = len(items)
+        self.table = arr = (_lib.ImgprepFrame * n)()
+        off, outputs = 0, []
+        for i, it in enumerate(items):
+            if it is None:
+                continue
+            ptr, h, w, pitch = it
+            oh, ow = (self.S, self.S) if self.final else self.pp._resized(h, w)
+            ih, iw = (max(h, w), max(h, w)) if self.flags & _lib.IMGPREP_PAD else (h, w)
+            if ih > 100 * iw and oh < ih:
+                # recent Pillow resizes such a sliver vertically first (Image.resize), older ones do not: there is no single result to match
+                raise _lib.VtError(f"frame of {h} x {w} resized without padding: more than 100 times taller than wide is not supported "
+                                   "on the device (use preprocess_images)")
+            th, kh, _ = self.pp._table(iw, ow, self.filt)
+            tv, kv, rows = self.pp._table(ih, oh, self.filt)
+            f = arr[i]
+            f.src, f.pitch, f.h, f.w, f.out_h, f.out_w = ptr, pitch, h, w, oh, ow
+            f.coef_h = th.data_ptr() if th is not None else None
+            f.coef_v = tv.data_ptr() if tv is not None else None
+            f.ksize_h, f.ksize_v, f.rows_max = kh, kv, rows
+            f.out_off = off
+            outputs.append((i, off, oh, ow))
+            off += _align(oh * ow * 3, 16)
+        L = _lib.lib()
+        ws_bytes = int(L.vt_imgprep_workspace_bytes(arr, n, self.S, self.flags))
+        if ws_bytes == 0:
+            raise _lib.VtError("vt_imgprep_workspace_bytes: " + L.vt_last_error().decode())
+        return (0, ws_bytes, []) if self.final else (off, ws_bytes, outputs)
+
+    def launch(self, wp, st, out, jitter, quality):
+        lut, fill, dst = (_lib.ptr(self.pp.lut), self.pp.fill, _lib.ptr(out)) if self.final else (None, 0, C.c_void_p(wp + self.out_off))
+        _lib.check(_lib.lib().vt_imgprep(self.table, _lib.ptr(self.dev), len(self.table), self.S, lut, fill, self.flags, dst,
+                                         C.c_void_p(wp + self.ws_off), self.ws_bytes, st), self.what)
+
+
+class _JitterStage(_Stage):
+    """ColorJitter (vlatouch/imgaug.py): every frame that exists goes through it, an unjittered one with an empty operation list.  With `lift`
+    the stage also takes the brightness-lift decision, on the frame before the jitter, so the stage behind it runs without IMGPREP_BRIGHT and
+    no frame is lifted twice.  The table is this call's: the cached geometry with the call's parameters, through a pinned buffer."""
+
+    def __init__(self, lift: bool):
+        self.flags = _lib.COLORJITTER_LIFT if lift else 0
+        self.free: Optional[torch.cuda.Event] = None
+
+    def plan(self, items):
+        self.idx = [i for i, it in enumerate(items) if it is not None]
+        self.table = (_lib.ColorJitterFrame * len(self.idx))()
+        off = 0
+        for f, i in zip(self.table, self.idx):
+            f.src, f.h, f.w, f.pitch = items[i]
+            f.out_off = off
+            f.order[:] = [OP_NONE] * 4
+            f.brightness = f.contrast = f.saturation = 1.0
+            off += _align(3 * f.h * f.w, 16)
+        return off, int(_lib.lib().vt_colorjitter_workspace_bytes(len(self.idx))), [(i, f.out_off, f.h, f.w) for i, f in zip(self.idx, self.table)]
+
+    def bind(self, stager: FrameStager) -> None:
+        self.pin = torch.empty(C.sizeof(self.table), dtype=torch.uint8).pin_memory()
+        self.dev = torch.empty(C.sizeof(self.table), dtype=torch.uint8, device=stager.device)
+
+    def launch(self, wp, st, out, jitter, quality):
+        arr = type(self.table).from_buffer_copy(self.table)
+        for f, i in zip(arr, self.idx):
+            if jitter[i] is not None:
+                jitter[i].fill_record(f)
+        if self.free is not None:
+            self.free.synchronize()                                     # the previous call's copy has left the pinned table
+        self.pin.numpy()[:] = np.frombuffer(arr, dtype=np.uint8)
+        self.dev.copy_(self.pin, non_blocking=True)
+        self.free = torch.cuda.Event()
+        self.free.record(torch.cuda.current_stream(self.dev.device))
+        _lib.check(_lib.lib().vt_colorjitter(arr, _lib.ptr(self.dev), len(self.idx), self.flags, C.c_void_p(wp + self.out_off),
+                                             C.c_void_p(wp + self.ws_off), self.ws_bytes, st), "vt_colorjitter")
+
+
+class DevicePreprocessor:
+    """`preprocess_images` of one model configuration on one device.  image_size / pad / brightness as in the wrapper."""
+
+    def __init__(self, size: int, image_mean, image_std, device, dtype: torch.dtype = torch.float32, *, pad: bool = True,
+                 brightness: bool = False, image_size=None, rescale_factor: float = 1 / 255.0):
+        self.stager = FrameStager(device)
+        self.device = self.stager.device
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise _lib.VtError(f"DevicePreprocessor: fp32 or bf16 output, got {dtype}")
+        self.S, self.dtype, self.pad, self.brightness, self.image_size = int(size), dtype, bool(pad), bool(brightness), image_size
+        self.mean255 = tuple(int(x * 255) for x in image_mean)
+        self.fill = self.mean255[0] | self.mean255[1] << 8 | self.mean255[2] << 16
+        self.lut = norm_table(image_mean, image_std, dtype, rescale_factor).to(self.device)
+        self.flags = (_lib.IMGPREP_PAD if self.pad else 0) | (_lib.IMGPREP_BRIGHT if self.brightness else 0) | \
+                     (_lib.IMGPREP_OUT_BF16 if dtype == torch.bfloat16 else 0)
+        self.force_two_pass = False           # tests: run the two-launch form where the fused one would do
+        # a missing frame is the S x S fill image; the kernel writes it directly (item None) unless a pre-resize or a brightness lift could
+        # touch it: then it is a frame like the others, the background image
+        self._bg = self._missing = None
+        if image_size is not None or (self.brightness and sum(self.mean255) / (255.0 * 3) <= 0.15):
+            bg = np.ones((self.S, self.S, 3), dtype=np.uint8) * np.array(self.mean255, dtype=np.uint8).reshape(1, 1, 3)
+            self._bg = torch.from_numpy(bg).to(self.device)
+            self._missing = (self._bg.data_ptr(), self.S, self.S, 3 * self.S)
+        self._tables: dict = {}               # (in, out, filter) -> (device int32 table, ksize, rows_max)
+        self._plans: dict = {}
+        self._ws: Optional[torch.Tensor] = None
+        self._keepalive: list = []
+
+    # ---- tables
+    def _table(self, in_size: int, out_size: int, filt: int):
+        if in_size == out_size:
+            return None, 0, TILE_ROWS
+        key = (in_size, out_size, filt)
+        hit = self._tables.get(key)
+        if hit is None:
+            b, k = resample_coeffs(in_size, out_size, filt)
+            flat = np.concatenate([b.reshape(-1), k.reshape(-1)]).astype(np.int32)
+            hit = (torch.from_numpy(flat).to(self.device), int(k.shape[1]), tile_rows_max(b))
+            self._tables[key] = hit
+        return hit
+
     def _resized(self, h: int, w: int) -> Tuple[int, int]:
         sz = self.image_size
         if isinstance(sz, int):                           # transforms.Resize(int): shorter side -> sz
@@ -211,34 +330,19 @@ class DevicePreprocessor:
         return int(sz[0]), int(sz[1])
 
     # ---- planning: everything that depends only on geometry and addresses
-    def _stage(self, items, flags: int, S: int, out_sizes, filt: int):
-        n = len(items)
-        arr = (_lib.ImgprepFrame * n)()
-        off = 0
-        for i, it in enumerate(items):
-            if it is None:
-                continue
-            ptr, h, w, pitch = it
-            oh, ow = out_sizes[i]
-            ih, iw = (max(h, w), max(h, w)) if flags & _lib.IMGPREP_PAD else (h, w)
-            if ih > 100 * iw and oh < ih:
-                # recent Pillow resizes such a sliver vertically first (Image.resize), older ones do not: there is no single result to match
-                raise _lib.VtError(f"frame of {h} x {w} resized without padding: more than 100 times taller than wide is not supported "
-                                   "on the device (use preprocess_images)")
-            th, kh, _ = self._table(iw, ow, filt)
-            tv, kv, rows = self._table(ih, oh, filt)
-            f = arr[i]
-            f.src, f.pitch, f.h, f.w, f.out_h, f.out_w = ptr, pitch, h, w, oh, ow
-            f.coef_h = th.data_ptr() if th is not None else None
-            f.coef_v = tv.data_ptr() if tv is not None else None
-            f.ksize_h, f.ksize_v, f.rows_max = kh, kv, rows
-            f.out_off = off
-            off += _align(oh * ow * 3, 16)
-        L = _lib.lib()
-        ws_bytes = int(L.vt_imgprep_workspace_bytes(arr, n, S, flags))
-        if ws_bytes == 0:
-            raise _lib.VtError("vt_imgprep_workspace_bytes: " + L.vt_last_error().decode())
-        return arr, ws_bytes, off
+    def _stages(self, jit: bool, jpeg_idx: Optional[tuple]) -> list:
+        """The chain of one call, as the reference orders it: JPEG -> Resize -> (lift and) jitter -> pad, resize, normalise."""
+        stages = []
+        if jpeg_idx:
+            stages.append(_JpegStage(jpeg_idx))
+        if self.image_size is not None:
+            stages.append(_ResampleStage(self, _lib.IMGPREP_OUT_U8, final=False))
+        flags = self.flags | (_lib.IMGPREP_TWO_PASS if self.force_two_pass else 0)
+        if jit:
+            stages.append(_JitterStage(self.brightness))
+            flags &= ~_lib.IMGPREP_BRIGHT
+        stages.append(_ResampleStage(self, flags, final=True))
+        return stages
 
     def _plan(self, items, ws_ptr: Optional[int], jit: bool = False, jpeg_idx: Optional[tuple] = None):
         key = (tuple(items), ws_ptr, self.force_two_pass, jit, jpeg_idx)
@@ -247,72 +351,19 @@ class DevicePreprocessor:
             return plan
         if len(self._plans) >= 64:                        # plans a captured graph reads (their device tables) are never dropped
             self._plans = {k: v for k, v in self._plans.items() if v.get("captured")}
-        n = len(items)
-        flags = self.flags | (_lib.IMGPREP_TWO_PASS if self.force_two_pass else 0)
-        plan = {"pre": None, "jpeg": None}
-        total = 0
-        # every later stage's table needs addresses inside the workspace: sized first with a placeholder base
-        base = ws_ptr if ws_ptr is not None else 4096
-        if jpeg_idx:
-            # the JPEG round trip of the raw frames (vlatouch/jpegmap.py), ahead of everything else as in the reference: frames that exist
-            # are mapped into tight uint8 frames at the head of the workspace, which the next stage reads; a missing frame's fill is not
-            from .jpegmap import jpeg_table
-            jarr, jout, jws = jpeg_table([items[i] for i in jpeg_idx])
-            plan["jpeg"] = {"arr": jarr, "n": len(jpeg_idx), "out_off": 0, "ws_off": _align(jout, 256), "ws_bytes": jws}
-            if ws_ptr is not None:
-                plan["jpeg"]["dev"] = self._to_device(jarr)
-            total = _align(jout, 256) + _align(jws, 256)
+        base = ws_ptr if ws_ptr is not None else _SIZING_BASE
+        stages, off = self._stages(jit, jpeg_idx), 0
+        for st in stages:                                 # the workspace, carved: per stage its output, then its scratch, each 256-byte aligned
+            out_bytes, st.ws_bytes, outputs = st.plan(items)
+            st.out_off, st.ws_off = off, off + _align(out_bytes, 256)
             items = list(items)
-            for k, i in enumerate(jpeg_idx):
-                items[i] = (base + jarr[k].out_off, jarr[k].h, jarr[k].w, 3 * jarr[k].w)
-        if self.image_size is not None:                   # step 1: bilinear pre-resize into uint8 frames of the workspace
-            sizes = [self._resized(it[1], it[2]) for it in items]
-            arr1, ws1, out1 = self._stage(items, _lib.IMGPREP_OUT_U8, 0, sizes, BILINEAR)
-            plan["pre"] = {"arr": arr1, "out_off": total, "ws_off": total + _align(out1, 256), "ws_bytes": ws1}
-            mid = [(None, sizes[i][0], sizes[i][1], 3 * sizes[i][1], total + arr1[i].out_off) for i in range(n)]
-            total += _align(out1, 256) + _align(ws1, 256)
-        else:
-            mid = None
-        plan["flags"], plan["main_off"] = flags, total
-        main_items = items if mid is None else [(base + m[4], m[1], m[2], m[3]) for m in mid]
-        if jit:
-            # the jitter stage: every frame that exists goes through it (an unjittered one with an empty operation list) into tight uint8
-            # frames of the workspace, which the main stage reads; the stage also takes the lift decision, on the frame before the jitter,
-            # so the main stage runs without VT_IMGPREP_BRIGHT and no frame is lifted twice
-            idx = [i for i, it in enumerate(main_items) if it is not None]
-            jarr = (_lib.ColorJitterFrame * len(idx))()
-            joff = 0
-            for k, i in enumerate(idx):
-                f = jarr[k]
-                f.src, f.h, f.w, f.pitch = main_items[i]
-                f.out_off = joff
-                f.order[:] = [OP_NONE] * 4
-                f.brightness = f.contrast = f.saturation = 1.0
-                joff += _align(3 * f.h * f.w, 16)
-            jws = int(_lib.lib().vt_colorjitter_workspace_bytes(len(idx)))
-            jp = {"arr": jarr, "idx": idx, "out_off": total, "ws_off": total + _align(joff, 256), "ws_bytes": jws, "free": None}
+            for i, rel, h, w in outputs:
+                items[i] = (base + off + rel, h, w, 3 * w)
+            off = st.ws_off + _align(st.ws_bytes, 256)
             if ws_ptr is not None:
-                jp["pin"] = torch.empty(C.sizeof(jarr), dtype=torch.uint8).pin_memory()
-                jp["dev"] = torch.empty(C.sizeof(jarr), dtype=torch.uint8, device=self.device)
-            main_items = list(main_items)
-            for k, i in enumerate(idx):
-                main_items[i] = (base + total + jarr[k].out_off, jarr[k].h, jarr[k].w, 3 * jarr[k].w)
-            total += _align(joff, 256) + _align(jws, 256)
-            plan["jit"], plan["main_off"] = jp, total
-            flags &= ~_lib.IMGPREP_BRIGHT
-            plan["flags"] = flags
-        arr2, ws2, _ = self._stage(main_items, flags, self.S, [(self.S, self.S)] * n, BICUBIC)
-        plan["arr"], plan["ws_bytes_main"], plan["ws_bytes"] = arr2, ws2, total + ws2
-        if ws_ptr is not None:
-            plan["dev"] = self._to_device(arr2)
-            if plan["pre"] is not None:
-                plan["pre"]["dev"] = self._to_device(plan["pre"]["arr"])
-        self._plans[key] = plan
+                st.bind(self.stager)
+        plan = self._plans[key] = {"stages": stages, "ws_bytes": stages[-1].ws_off + stages[-1].ws_bytes}
         return plan
-
-    def _to_device(self, arr) -> torch.Tensor:
-        raw = np.frombuffer(bytes(memoryview(arr)), dtype=np.uint8).copy()
-        return torch.from_numpy(raw).to(self.device)
 
     @staticmethod
     def _jitter_list(images: Sequence, jitter):
@@ -343,7 +394,7 @@ class DevicePreprocessor:
     def workspace_bytes(self, images: Sequence, jitter=None, jpeg=None) -> int:
         """Bytes of workspace a call on these frames needs (geometry only, plus whether any frame is jittered or JPEG-mapped)."""
         jit = self._jitter_list(images, jitter) is not None
-        items, _ = self._gather(images)
+        items, _ = self.stager.gather(images, self._missing)
         return self._plan(items, None, jit, self._jpeg_idx(images, jpeg)[1])["ws_bytes"]
 
     @torch.no_grad()
@@ -365,7 +416,7 @@ class DevicePreprocessor:
         if jit and torch.cuda.is_current_stream_capturing():
             raise _lib.VtError("DevicePreprocessor: a call with jitter= cannot be captured in a graph")
         with torch.cuda.device(self.device):
-            items, keep = self._gather(images)
+            items, keep = self.stager.gather(images, self._missing)
             if workspace is None:
                 need = self._plan(items, None, jit, jpeg_idx)["ws_bytes"]
                 if self._ws is None or self._ws.numel() < need:
@@ -384,30 +435,7 @@ class DevicePreprocessor:
                 out = torch.empty((n, 3, S, S), dtype=self.dtype, device=self.device)
             elif out.shape != (n, 3, S, S) or out.dtype != self.dtype or not out.is_contiguous() or out.device != self.device:
                 raise _lib.VtError(f"out must be a contiguous {self.dtype} [{n}, 3, {S}, {S}] tensor on {self.device}")
-            L, st = _lib.lib(), _lib.stream_ptr(self.device)
-            wp = workspace.data_ptr()
-            jm = plan["jpeg"]
-            if jm is not None:
-                _lib.check(L.vt_jpegmap(jm["arr"], _lib.ptr(jm["dev"]), jm["n"], quality, _lib.JPEGMAP_CV2_ORDER, C.c_void_p(wp + jm["out_off"]),
-                                        C.c_void_p(wp + jm["ws_off"]), jm["ws_bytes"], st), "vt_jpegmap")
-            pre = plan["pre"]
-            if pre is not None:
-                _lib.check(L.vt_imgprep(pre["arr"], _lib.ptr(pre["dev"]), n, 0, None, 0, _lib.IMGPREP_OUT_U8, C.c_void_p(wp + pre["out_off"]),
-                                        C.c_void_p(wp + pre["ws_off"]), pre["ws_bytes"], st), "vt_imgprep (pre-resize)")
-            if jit:
-                jp = plan["jit"]
-                arr = type(jp["arr"]).from_buffer_copy(jp["arr"])          # the cached geometry; this call's parameters go into the copy
-                for k, i in enumerate(jp["idx"]):
-                    if jitter[i] is not None:
-                        jitter[i].fill_record(arr[k])
-                if jp["free"] is not None:
-                    jp["free"].synchronize()                                # the previous call's copy has left the pinned table
-                jp["pin"].numpy()[:] = np.frombuffer(arr, dtype=np.uint8)
-                jp["dev"].copy_(jp["pin"], non_blocking=True)
-                jp["free"] = torch.cuda.Event()
-                jp["free"].record(torch.cuda.current_stream(self.device))
-                _lib.check(L.vt_colorjitter(arr, _lib.ptr(jp["dev"]), len(jp["idx"]), _lib.COLORJITTER_LIFT if self.brightness else 0,
-                                            C.c_void_p(wp + jp["out_off"]), C.c_void_p(wp + jp["ws_off"]), jp["ws_bytes"], st), "vt_colorjitter")
-            _lib.check(L.vt_imgprep(plan["arr"], _lib.ptr(plan["dev"]), n, S, _lib.ptr(self.lut), self.fill, plan["flags"], _lib.ptr(out),
-                                    C.c_void_p(wp + plan["main_off"]), plan["ws_bytes_main"], st), "vt_imgprep")
+            wp, st = workspace.data_ptr(), _lib.stream_ptr(self.device)
+            for stage in plan["stages"]:
+                stage.launch(wp, st, out, jitter, quality)
         return out

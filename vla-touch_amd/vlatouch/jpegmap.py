@@ -3,7 +3,8 @@ align with training" (residual_controller/frank_inference_eef.py:84-87,131-132; 
 
   * `jpeg_mapping(img, quality, order)`: the CPU statement, through Pillow, whose libjpeg-turbo is the library cv2 wraps.
   * `jpeg_mapping_device(frames, ...)`: the same pixels from csrc/vt_jpegmap.hip, bit for bit, for frames of every kind
-    `preprocess_images_device` takes.  The SigLIP path reaches the kernel through `DevicePreprocessor(..., jpeg=quality)`; this function
+    `preprocess_images_device` takes, gathered by a `FrameStager` of its own.  The SigLIP path reaches the kernel through the JPEG stage of
+    `DevicePreprocessor.__call__(..., jpeg=quality)`, which builds its table with `jpeg_table` as this function does; this function
     serves consumers of the mapped frames themselves (the DINOv2 controller path reads the same frames on the robot).
 
 `order="cv2"`: channel 0 of the array plays blue's role, as cv2 treats whatever array it is given (the reference hands it RGB frames), i.e.
@@ -73,19 +74,18 @@ _stagers: dict = {}
 
 
 def _stager(device):
-    """One `DevicePreprocessor` per device, used for its frame gathering (host frames up in one copy, device views in place) only."""
-    from .imgprep import DevicePreprocessor
-    device = _lib.require_gpu(device)
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    st = _stagers.get(device)
+    """One `FrameStager` per device (host frames up in one copy, device views in place); a new one holds no memory until it gathers."""
+    st = _stagers.get(device)                 # the keys are devices with their index stated, as a frame's `.device` is
     if st is None:
-        st = _stagers[device] = DevicePreprocessor(16, (0.5,) * 3, (0.5,) * 3, device, pad=False)
+        from .imgprep import FrameStager
+        st = FrameStager(device)
+        st = _stagers.setdefault(st.device, st)
     return st
 
 
 def jpeg_table(items):
-    """[(ptr, h, w, pitch), ...] -> (the `vt_jpegmap_frame` table with out_off and ws_off set, output bytes, workspace bytes)."""
+    """[(ptr, h, w, pitch), ...] -> (the `vt_jpegmap_frame` table with out_off and ws_off set, output bytes, workspace bytes): the table
+    builder of the JPEG stage, for `jpeg_mapping_device` below and for the preprocessor's stage list (vlatouch/imgprep.py) alike."""
     arr = (_lib.JpegmapFrame * len(items))()
     off = 0
     for k, (ptr, h, w, pitch) in enumerate(items):
@@ -116,7 +116,7 @@ def jpeg_mapping_device(frames: Sequence, quality: int = 95, order: str = "cv2",
     if not idx:
         return res
     with torch.cuda.device(st.device):
-        items, _keep = st._gather([frames[i] for i in idx])      # _keep: contiguous copies of exotic views, alive until the launch is queued
+        items, _keep = st.gather([frames[i] for i in idx])       # _keep: contiguous copies of exotic views, alive until the launch is queued
         arr, out_bytes, ws_bytes = jpeg_table(items)
         for name, t, need in (("out", out, out_bytes), ("workspace", workspace, ws_bytes)):
             if t is not None and (t.dtype != torch.uint8 or not t.is_contiguous() or t.device != st.device or t.numel() < need):
@@ -125,7 +125,7 @@ def jpeg_mapping_device(frames: Sequence, quality: int = 95, order: str = "cv2",
             out = torch.empty(out_bytes, dtype=torch.uint8, device=st.device)
         if workspace is None:
             workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=st.device)
-        dev = st._to_device(arr)
+        dev = st.to_device(arr)
         _lib.check(_lib.lib().vt_jpegmap(arr, _lib.ptr(dev), len(idx), quality, _lib.JPEGMAP_CV2_ORDER if order == "cv2" else 0,
                                          _lib.ptr(out), _lib.ptr(workspace), ws_bytes, _lib.stream_ptr(st.device)), "vt_jpegmap")
     flat = out.view(-1)
