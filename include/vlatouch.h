@@ -233,6 +233,20 @@ size_t vt_t5_workspace_bytes(vt_t5_t h, int B, int L);
  * T5Attention._relative_position_bucket, bidirectional, computed on the host in fp32).  out: [B][L][d_model] of out_dt (0 fp32, 1 bf16). */
 int vt_t5_forward(vt_t5_t h, const int32_t* ids, const uint8_t* mask_or_null, int B, int L, const int8_t* bucket_tab, void* out, int out_dt,
                   void* workspace, vt_stream_t stream);
+/* The encoder's own two kernels as entries (tests call them alone; vt_t5_forward launches them through these and in no other way).
+ * vt_t5_attention: out = softmax(q k^T + rel_bias[bucket(j - i)][h], masked keys at -inf) v per (batch, head), head width 64, NO 1/sqrt(d)
+ * scale.  All pointers are DEVICE pointers.  qkv [B*L][3*H*64] (q | k | v, head h at column h*64 of its part), out [B*L][H*64], both of dt
+ * (0 fp32, 1 bf16); bucket_tab int8 [2047] as vt_t5_forward takes it (entries are clamped to 0 .. num_buckets-1); rel_bias fp32
+ * [num_buckets][H]; kmask_or_null uint8 [B][L], 1 = attend.  A sample without a valid key comes out as zeros (vt_t5_forward rejects one).
+ * Refused before any launch: a null required pointer, B, H or L < 1, B or H > 65535, L > 1024, num_buckets outside 1 .. 127 (-22); any
+ * other dt (-95).
+ * vt_t5_geglu: h[r][c] = gelu_tanh(g[r][c]) * g[r][F + c] for c < F (HF gelu_new on the first half, the gate), out of place, rows of g ldg
+ * elements apart and rows of h ldh apart, both DEVICE pointers aligned to 16 bytes, of dt (0 fp32, 1 bf16).  Refused before any launch: null
+ * g or h, rows < 1, F < 1, F, ldg or ldh that is not a multiple of the 16-byte vector (4 fp32 or 8 bf16 elements), ldg < 2 F, ldh < F (-22);
+ * any other dt (-95). */
+int vt_t5_attention(const void* qkv, void* out, const int8_t* bucket_tab, const float* rel_bias, const uint8_t* kmask_or_null,
+                    int B, int H, int L, int num_buckets, int dt, vt_stream_t stream);
+int vt_t5_geglu(const void* g, long ldg, void* h, long ldh, long rows, int F, int dt, vt_stream_t stream);
 
 /* ---------------------------------------------------------------- small MLP chain (state encoder / force encoder / heads)
  * y = L_n(...act(L_1(x))): replaces the nn.Sequential MLPs of bridge_controller.py:42-48 and

@@ -93,7 +93,7 @@ int vt_groupnorm(const void* params, vt_stream_t stream) {
 int vt_rownorm(const void* x, int xdt, long ldx, void* y, int ydt, long ldy, const float* w, const float* b, int rows, int D, float eps,
                int mode, vt_stream_t stream) {
   const int r = vt_k_rownorm(x, xdt, ldx, y, ydt, ldy, w, b, rows, D, eps, mode, (hipStream_t)stream);
-  if (r) vt_fail(r, "vt_rownorm: D must be a multiple of 4 and <= 2048");
+  if (r) vt_fail(r, "vt_rownorm: D must be a multiple of 4 and <= 2048 (<= 4096 from fp32 rows with ldx, ldy multiples of 4)");
   return r;
 }
 int vt_headnorm(void* x, int dt, long tok_stride, int heads, long tokens, const float* w, float eps, int mode, vt_stream_t stream) {

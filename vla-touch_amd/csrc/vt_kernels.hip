@@ -100,20 +100,31 @@ __global__ __launch_bounds__(256) void rownorm_block_kernel(const float* __restr
     return (red[0] + red[1]) + (red[2] + red[3]);
   };
   float mean = 0.f, var;
+  [[maybe_unused]] float corr = 0.f;
   if (mode == VT_NORM_RMS_MEANSQ) {
     var = block_sum(q) / (float)D;
   } else {
     mean = block_sum(s) / (float)D;
     float d2 = 0.f;
+    [[maybe_unused]] float r1 = 0.f;
 #pragma unroll
     for (int i = 0; i < NV; ++i)
       if (tid + 256 * i < nv) {
         const float a0 = v[i].x - mean, a1 = v[i].y - mean, a2 = v[i].z - mean, a3 = v[i].w - mean;
         d2 += (a0 * a0 + a1 * a1) + (a2 * a2 + a3 * a3);
+        if constexpr (NV == 4) r1 += (a0 + a1) + (a2 + a3);
       }
     d2 = block_sum(d2);
+    if constexpr (NV == 4) {
+      // The wide route only: what the fp32 mean missed.  A row whose mean is hundreds of standard deviations from zero has a mean good to an
+      // ulp or two of ITS magnitude (3e-5 at 400), which LayerNorm then carries into every output at 1e-5 of the row's scale.  x - mean is
+      // exact there, so the sum of the centred values is that error times D, to fp32's precision of the deviations.  (The narrower routes
+      // round the same way; their outputs are pinned bit for bit by tests/test_gpu_drivers_parent.py and stay as they are.)
+      corr = block_sum(r1) / (float)D;
+      d2 -= corr * corr * (float)D;
+    }
     var = (mode == VT_NORM_RMS_VAR) ? d2 / (float)(D - 1) : d2 / (float)D;
-    if (mode == VT_NORM_RMS_VAR) mean = 0.f;
+    if (mode == VT_NORM_RMS_VAR) { mean = 0.f; corr = 0.f; }
   }
   if (range_flag && tid == 0 && vt_nonfinite(var)) vt_range_note(range_flag, VT_RANGE_NONFINITE);     // an inf / NaN anywhere in the row makes its statistics non-finite
   const float rstd = rsqrtf(var + eps);
@@ -123,7 +134,9 @@ __global__ __launch_bounds__(256) void rownorm_block_kernel(const float* __restr
     const int c4 = tid + 256 * i;
     if (c4 < nv) {
       const float4 ww = *reinterpret_cast<const float4*>(w + c4 * 4);
-      float o[4] = {(v[i].x - mean) * rstd * ww.x, (v[i].y - mean) * rstd * ww.y, (v[i].z - mean) * rstd * ww.z, (v[i].w - mean) * rstd * ww.w};
+      float c[4] = {v[i].x - mean, v[i].y - mean, v[i].z - mean, v[i].w - mean};
+      if constexpr (NV == 4) { c[0] -= corr; c[1] -= corr; c[2] -= corr; c[3] -= corr; }
+      float o[4] = {c[0] * rstd * ww.x, c[1] * rstd * ww.y, c[2] * rstd * ww.z, c[3] * rstd * ww.w};
       if (b) { const float4 bb = *reinterpret_cast<const float4*>(b + c4 * 4); o[0] += bb.x; o[1] += bb.y; o[2] += bb.z; o[3] += bb.w; }
       if constexpr (sizeof(TO) == 4) *reinterpret_cast<float4*>(yr + c4 * 4) = make_float4(o[0], o[1], o[2], o[3]);
       else {

@@ -208,13 +208,41 @@ __global__ __launch_bounds__(256) void t5_attn_kernel(const T5AttnParams p) {
   }
 }
 
-template <typename T>
-int t5_attn_launch(const T5AttnParams& p, hipStream_t s) {
-  hipLaunchKernelGGL((t5_attn_kernel<T>), dim3((p.L + 63) / 64, p.H, p.B), dim3(256), 0, s, p);
+}  // namespace
+
+// ======================================================================================= the two kernels as entries of their own (include/vlatouch.h)
+// vt_t5_forward launches attention and the gate through these and nowhere else, so a test of either entry runs the engine's code.
+int vt_t5_attention(const void* qkv, void* out, const int8_t* bucket_tab, const float* rel_bias, const uint8_t* kmask, int B, int H, int L,
+                    int num_buckets, int dt, vt_stream_t stream) {
+  if (!qkv || !out || !bucket_tab || !rel_bias) return vt_fail(VT_ERR_ARG, "vt_t5_attention: null qkv, out, bucket_tab or rel_bias");
+  if (B < 1 || H < 1 || L < 1) return vt_fail(VT_ERR_ARG, "vt_t5_attention: bad sizes B=%d H=%d L=%d", B, H, L);
+  if (B > 65535 || H > 65535) return vt_fail(VT_ERR_ARG, "vt_t5_attention: B=%d or H=%d exceeds the grid's 65535", B, H);
+  if (L > T5_MAX_L) return vt_fail(VT_ERR_ARG, "vt_t5_attention: L = %d exceeds %d", L, T5_MAX_L);
+  if (num_buckets < 1 || num_buckets > 127) return vt_fail(VT_ERR_ARG, "vt_t5_attention: num_buckets = %d is outside 1 .. 127", num_buckets);
+  if (dt != VT_F32 && dt != VT_BF16) return vt_fail(VT_ERR_UNSUPPORTED, "vt_t5_attention: dt must be fp32 (0) or bf16 (1), got %d", dt);
+  T5AttnParams p;
+  p.qkv = qkv; p.out = out; p.bucket = bucket_tab; p.rel_bias = rel_bias; p.kmask = kmask;
+  p.B = B; p.H = H; p.L = L; p.inner = H * 64; p.num_buckets = num_buckets;
+  const dim3 grid((L + 63) / 64, H, B);
+  // chosen by hand between the two types a T5 handle admits: DISPATCH_T (vt_common.h) would also instantiate the kernel for half_t
+  if (dt == VT_BF16) hipLaunchKernelGGL((t5_attn_kernel<bf16_t>), grid, dim3(256), 0, (hipStream_t)stream, p);
+  else hipLaunchKernelGGL((t5_attn_kernel<float>), grid, dim3(256), 0, (hipStream_t)stream, p);
   return vt_check_launch();
 }
 
-}  // namespace
+int vt_t5_geglu(const void* g, long ldg, void* h, long ldh, long rows, int F, int dt, vt_stream_t stream) {
+  if (!g || !h) return vt_fail(VT_ERR_ARG, "vt_t5_geglu: null g or h");
+  if (dt != VT_F32 && dt != VT_BF16) return vt_fail(VT_ERR_UNSUPPORTED, "vt_t5_geglu: dt must be fp32 (0) or bf16 (1), got %d", dt);
+  const int V = 16 / vt_dt_bytes(dt);                       // elements of a lane's 16-byte vector
+  if (rows < 1 || F < 1) return vt_fail(VT_ERR_ARG, "vt_t5_geglu: bad sizes rows=%ld F=%d", rows, F);
+  if (F % V || ldg % V || ldh % V) return vt_fail(VT_ERR_ARG, "vt_t5_geglu: F=%d, ldg=%ld and ldh=%ld must be multiples of %d elements (16 bytes)", F, ldg, ldh, V);
+  if (ldg < 2L * F || ldh < F) return vt_fail(VT_ERR_ARG, "vt_t5_geglu: ldg=%ld < 2 F or ldh=%ld < F (F=%d)", ldg, ldh, F);
+  const long n = rows * (F / V);
+  if (n > 0x7fffffffL * 256) return vt_fail(VT_ERR_ARG, "vt_t5_geglu: rows=%ld x F=%d is more than one launch covers", rows, F);
+  if (dt == VT_BF16) hipLaunchKernelGGL((t5_geglu_kernel<bf16_t>), g1(n), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)g, ldg, (bf16_t*)h, ldh, rows, F);
+  else hipLaunchKernelGGL((t5_geglu_kernel<float>), g1(n), dim3(256), 0, (hipStream_t)stream, (const float*)g, ldg, (float*)h, ldh, rows, F);
+  return vt_check_launch();
+}
 
 // ======================================================================================= driver
 struct T5Layer { const float *ln1, *ln2; const void *qkv_w, *o_w, *wi_w, *wo_w; };
@@ -295,29 +323,24 @@ int vt_t5_forward(vt_t5_t h, const int32_t* ids, const uint8_t* mask, int B, int
   if (hipMemcpyAsync(ws + w.ids, ids, (size_t)M * 4, hipMemcpyHostToDevice, s) != hipSuccess) return vt_fail(VT_ERR_LAUNCH, "vt_t5_forward: id upload");
   if (mask && hipMemcpyAsync(ws + w.mask, mask, (size_t)M, hipMemcpyHostToDevice, s) != hipSuccess) return vt_fail(VT_ERR_LAUNCH, "vt_t5_forward: mask upload");
   float* tok = (float*)(ws + w.tok);
-  // the typed kernels (gather, attention, GEGLU gate) are chosen by hand between the two types `create` admits: DISPATCH_T (vt_common.h) would also
-  // instantiate them for half_t, which no T5 handle can ask for
+  // the typed gather is chosen by hand between the two types `create` admits: DISPATCH_T (vt_common.h) would also instantiate it for half_t,
+  // which no T5 handle can ask for
   if (cdt == VT_BF16) hipLaunchKernelGGL((t5_gather_kernel<bf16_t>), g1((long)M * D / 4), dim3(256), 0, s, (const int*)(ws + w.ids), (const bf16_t*)h->shared, tok, (long)M, D, d.vocab);
   else hipLaunchKernelGGL((t5_gather_kernel<float>), g1((long)M * D / 4), dim3(256), 0, s, (const int*)(ws + w.ids), (const float*)h->shared, tok, (long)M, D, d.vocab);
   CK(vt_wrap(vt_check_launch(), "t5 token gather"));
-  T5AttnParams ap;
-  ap.qkv = ws + w.qkv; ap.out = ws + w.att; ap.bucket = bucket_tab; ap.rel_bias = h->rel_bias;
-  ap.kmask = mask ? (const uint8_t*)(ws + w.mask) : nullptr;
-  ap.B = B; ap.H = d.heads; ap.L = L; ap.inner = I; ap.num_buckets = d.num_buckets;
+  const uint8_t* kmask = mask ? (const uint8_t*)(ws + w.mask) : nullptr;
   for (const T5Layer& Ly : h->L) {
     CK(vt_wrap(vt_k_rownorm(tok, VT_F32, D, ws + w.xn, adt, D, Ly.ln1, nullptr, M, D, d.eps, VT_NORM_RMS_MEANSQ, s), "t5 rms1"));
     { VtGemmParams p = vt_linear(ws + w.xn, adt, D, Ly.qkv_w, cdt, D, nullptr, ws + w.qkv, adt, 3 * I, M, 3 * I, D, VT_ACT_NONE);
       CK(vt_wrap(vt_gemm_launch(p, s), "t5 qkv")); }
-    CK(vt_wrap(adt == VT_BF16 ? t5_attn_launch<bf16_t>(ap, s) : t5_attn_launch<float>(ap, s), "t5 attention"));
+    CK(vt_wrap(vt_t5_attention(ws + w.qkv, ws + w.att, bucket_tab, h->rel_bias, kmask, B, d.heads, L, d.num_buckets, adt, stream), "t5 attention"));
     { VtGemmParams p = vt_linear(ws + w.att, adt, I, Ly.o_w, cdt, I, nullptr, tok, VT_F32, D, M, D, I, VT_ACT_NONE);
       p.residual = tok; p.ldr = D;
       CK(vt_wrap(vt_gemm_launch(p, s), "t5 o")); }
     CK(vt_wrap(vt_k_rownorm(tok, VT_F32, D, ws + w.xn, adt, D, Ly.ln2, nullptr, M, D, d.eps, VT_NORM_RMS_MEANSQ, s), "t5 rms2"));
     { VtGemmParams p = vt_linear(ws + w.xn, adt, D, Ly.wi_w, cdt, D, nullptr, ws + w.g, adt, 2 * F, M, 2 * F, D, VT_ACT_NONE);
       CK(vt_wrap(vt_gemm_launch(p, s), "t5 wi")); }
-    if (adt == VT_BF16) hipLaunchKernelGGL((t5_geglu_kernel<bf16_t>), g1((long)M * F / 8), dim3(256), 0, s, (const bf16_t*)(ws + w.g), (long)2 * F, (bf16_t*)(ws + w.hf), (long)F, (long)M, F);
-    else hipLaunchKernelGGL((t5_geglu_kernel<float>), g1((long)M * F / 4), dim3(256), 0, s, (const float*)(ws + w.g), (long)2 * F, (float*)(ws + w.hf), (long)F, (long)M, F);
-    CK(vt_wrap(vt_check_launch(), "t5 geglu gate"));
+    CK(vt_wrap(vt_t5_geglu(ws + w.g, (long)2 * F, ws + w.hf, (long)F, (long)M, F, adt, stream), "t5 geglu gate"));
     { VtGemmParams p = vt_linear(ws + w.hf, adt, F, Ly.wo_w, cdt, F, nullptr, tok, VT_F32, D, M, D, F, VT_ACT_NONE);
       p.residual = tok; p.ldr = D;
       CK(vt_wrap(vt_gemm_launch(p, s), "t5 wo")); }

@@ -244,6 +244,8 @@ SIGNATURES = {
     "vt_t5_num_weights": (_I, [_P]),
     "vt_t5_workspace_bytes": (_Z, [_P, _I, _I]),
     "vt_t5_forward": (_I, [_P, _P, _P, _I, _I, _P, _P, _I, _P, _P]),
+    "vt_t5_attention": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "vt_t5_geglu": (_I, [_P, _L, _P, _L, _L, _I, _I, _P]),
     "vt_mlp": (_I, [_P, _L, _I, _I, _P, _P, _P, _I, _P, _I, _L, _I, _I, _P, _P]),
     "vt_concat_obs": (_I, [_P, _P, _I, _P, _I, _P, _I, _P, _I, _L, _I, _P]),
     "vt_lstm_create": (_I, [_P, _P, _I, _P]),
