@@ -668,6 +668,55 @@ size_t vt_jpegmap_workspace_bytes(vt_jpegmap_frame* frames_host, int n);
 int vt_jpegmap(const vt_jpegmap_frame* frames_host, const void* frames_dev, int n, int quality, int flags, void* out, void* ws,
                size_t ws_bytes, vt_stream_t stream);
 
+/* ---- corruption of camera frames (train/image_corrupt.py: imgaug's Sequential([noise, blur], random_order=True)), restated in integers
+ * (UNPINNED against imgaug and cv2).  uint8 HWC in (pitched), uint8 HWC out, frame i tight (pitch 3 * w) at
+ * out + out_off; source and output must not overlap.  Per frame, in the stated order, either or both of
+ *   noise: v' = clamp(v + e, 0, 255), e = -255 + #{n in -255..254 : u >= C[n]} with C the frame's VT_CORRUPT_THRESHOLDS non-decreasing
+ *     thresholds (C[n] = floor(2^32 P(X <= n)), built by the host) and u = word idx & 3 of Philox4x32-10 at counter idx >> 2 under `key`;
+ *     idx = (y * w + x) * 3 + c with per_channel, y * w + x (one draw for the three bytes) without.  Behind a blur, (y, x) is the output
+ *     position; in front of it, the position of the source pixel, so a pixel reached through the border carries its own noise;
+ *   blur: GAUSSIAN, AVERAGE, MOTION: ntaps taps (dy, dx, W > 0) as int32 triples, |dy|, |dx| <= k / 2 <= VT_CORRUPT_MAX_RADIUS, tap_sum = D
+ *     = sum of W <= 2^24; per byte S = sum of W * p(y + dy, x + dx) over the periodic reflect-101 border (period 2 (n - 1); n = 1 reads
+ *     index 0), q, r = divmod(S, D), out = q + (2 r > D or (2 r == D and q odd)).  k: odd in 3..37, for AVERAGE 2..7.
+ *     MEDIAN: per channel the median of the k x k window over the replicate border, k odd in 3..11, exact.
+ * The thresholds and taps of all frames sit in one buffer of 32-bit words at noise_off / taps_off (in words); like the frame table it is
+ * passed as host memory (checked here) and as the same bytes in device memory (read by the kernel).
+ * One launch: a workgroup stages a 32 x 32 tile plus halo in LDS, blurs out of LDS, writes words.  No workspace, no atomics, no host read,
+ * allocation or synchronisation: a pure function of the inputs.  n < 1, a null source, h < 1, w < 1, pitch < 3 * w, an unknown kind or
+ * order, an even or out-of-range k, decreasing thresholds, an empty tap list, a tap beyond radius k / 2, a weight < 1, tap_sum that is not
+ * the taps' sum or lies outside 1..2^24, and a table that does not hold what a record points at return VT_ERR_ARG without a launch. */
+typedef struct {
+  const void* src;      /* uint8 HWC, device */
+  long pitch;           /* bytes between rows of src, >= 3 * w */
+  int h, w;             /* frame size */
+  long out_off;         /* byte offset of this frame's output in `out` */
+  unsigned long long key;   /* Philox key of the frame's noise */
+  int noise;            /* VT_CORRUPT_NOISE_*: which distribution the thresholds state (the device reads them only) */
+  int per_channel;      /* 0: one draw per pixel, shared by its three bytes */
+  int blur, k;          /* VT_CORRUPT_BLUR_*, and the kernel's side */
+  int order;            /* VT_CORRUPT_NOISE_FIRST / VT_CORRUPT_BLUR_FIRST */
+  int noise_off;        /* word offset of C[510] in the tables */
+  int taps_off, ntaps;  /* word offset of the int32 (dy, dx, W) triples, and their count */
+  unsigned tap_sum;     /* D */
+  unsigned reserved;
+} vt_corrupt_frame;
+#define VT_CORRUPT_NOISE_NONE 0
+#define VT_CORRUPT_NOISE_GAUSSIAN 1
+#define VT_CORRUPT_NOISE_LAPLACE 2
+#define VT_CORRUPT_NOISE_POISSON 3
+#define VT_CORRUPT_BLUR_NONE 0
+#define VT_CORRUPT_BLUR_GAUSSIAN 1
+#define VT_CORRUPT_BLUR_AVERAGE 2
+#define VT_CORRUPT_BLUR_MEDIAN 3
+#define VT_CORRUPT_BLUR_MOTION 4
+#define VT_CORRUPT_NOISE_FIRST 0
+#define VT_CORRUPT_BLUR_FIRST 1
+#define VT_CORRUPT_THRESHOLDS 510
+#define VT_CORRUPT_MAX_RADIUS 18
+#define VT_CORRUPT_MAX_TAP_SUM (1u << 24)
+int vt_corrupt(const vt_corrupt_frame* frames_host, const void* frames_dev, int n, const unsigned* tables_host, const void* tables_dev,
+               long table_words, void* out, vt_stream_t stream);
+
 /* ---- one fine-tuning micro-batch out of device-resident episodes (vlatouch/rdt_data.py).  Stands for, per sample,
  * UnifiedVLADataset.parse_file (data/unified_vla_dataset_episode.py:314-351: state row, action chunk from action_id = step_id + 2 padded
  * with its last row, the episode's std / norm, fill_in_state), VLAConsumerDataset.__getitem__ (train/dataset.py:327-344: control frequency,

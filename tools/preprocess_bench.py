@@ -7,6 +7,9 @@ path from host frames (one copy of raw bytes included, ending in a synchronise),
 Then the training-time colour jitter (`--image_aug`, tests/imgaug_ref.py / csrc/vt_colorjitter.hip) on the 6 frames, every frame jittered with all
 four operations: the PIL chain followed by `preprocess_images` against one `DevicePreprocessor` call with `jitter=`, beside the unjittered
 device call of the same run (key `c_jitter_6`).
+Then the training-time corruption (tests/corrupt_ref.py / csrc/vt_corrupt.hip) on the 6 frames, every frame corrupted, the two costliest
+blurs (median k = 11, motion k = 37) among them: one `DevicePreprocessor` call with `corrupt=` beside the call without it, alternated (key
+`d_corrupt_6`), `vt_corrupt` alone on device frames back to back, and the numpy statement once, for scale.
 Then `step()` at batch 1 from PIL frames (so400m tower + RDT-1B, synthetic weights) with `device_preprocess` off and on, alternated in
 this process, with the spread of the repeats.  A machine without a GPU fails: nothing here is measured on a CPU.  One JSON line.
 
@@ -65,7 +68,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=7, help="alternated off / on repeats of step()")
+    ap.add_argument("--no-plain", action="store_true", help="skip the two plain legs (a, b)")
     ap.add_argument("--no-jitter", action="store_true", help="skip the colour-jitter leg")
+    ap.add_argument("--no-corrupt", action="store_true", help="skip the corruption leg")
     ap.add_argument("--no-step", action="store_true", help="skip the step() comparison (it builds the so400m tower and RDT-1B)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -81,7 +86,7 @@ def main():
     pol = types.SimpleNamespace(eval=lambda: None)
     m = RoboticDiffusionTransformerModel(ARGS, device=DEV, dtype=torch.bfloat16, vision_model=vis, policy=pol)
     g = np.random.default_rng(0)
-    for tag, n in (("a_robot_step_6", 6), ("b_labelling_48", 48)):
+    for tag, n in () if a.no_plain else (("a_robot_step_6", 6), ("b_labelling_48", 48)):
         arrs = [(g.random((480, 640, 3)) * 256 * (0.2 if i % 5 == 4 else 1.0)).astype(np.uint8) for i in range(n)]       # every fifth frame is dark
         pil = [Image.fromarray(x) for x in arrs]
         dev = [torch.from_numpy(x).to(DEV) for x in arrs]
@@ -140,6 +145,60 @@ def main():
              "speedup_vs_host_chain": round(cpu[0] / hostf[0], 1)}
         res["c_jitter_6"] = r
         print("c_jitter_6", r, file=sys.stderr, flush=True)
+    if not a.no_corrupt:
+        import ctypes
+        from tests import corrupt_ref
+        from vlatouch import _lib
+        from vlatouch.imgaug import CorruptParams, image_corrupt_device, pack_corrupt
+        n = 6
+        arrs = [(g.random((480, 640, 3)) * 256).astype(np.uint8) for i in range(n)]      # no dark frame: the lift, which precedes the corruption, stays out
+        dev = [torch.from_numpy(x).to(DEV) for x in arrs]
+        cor = [CorruptParams(True, "gaussian", 9.0, True, 11, blur="median", k=11),
+               CorruptParams(False, "laplace", 6.0, False, 12, blur="motion", k=37, angle=37.0, direction=0.3),
+               CorruptParams(True, "poisson", 11.0, True, 13, blur="gaussian", sigma=2.9),
+               CorruptParams(False, "gaussian", 4.0, False, 14, blur="average", k=7),
+               CorruptParams(True, "laplace", 12.0, True, 15, blur="motion", k=15, angle=200.0, direction=-0.7),
+               CorruptParams(True, "poisson", 3.0, False, 16)]
+        out = torch.empty(n, 3, 384, 384, dtype=torch.bfloat16, device=DEV)
+        t0 = time.perf_counter()
+        want = [corrupt_ref.image_corrupt_np(x, p) for x, p in zip(arrs, cor)]
+        cpu_once = round((time.perf_counter() - t0) * 1e3, 1)
+        got = image_corrupt_device(dev, cor)
+        same = all(bool(torch.equal(t.cpu(), torch.from_numpy(w))) for t, w in zip(got, want))
+        same = same and bool(torch.equal(m.preprocess_images_device(arrs, corrupt=cor), m.preprocess_images_device(want)))
+        with_h, without_h, with_d, without_d = [], [], [], []
+        for _ in range(a.repeats):                       # alternated in one process: the host is shared with other work
+            without_h.append(host_ms(lambda: m.preprocess_images_device(arrs, out=out), a.iters)[0])
+            with_h.append(host_ms(lambda: m.preprocess_images_device(arrs, out=out, corrupt=cor), a.iters)[0])
+            without_d.append(host_ms(lambda: m.preprocess_images_device(dev, out=out), a.iters)[0])
+            with_d.append(host_ms(lambda: m.preprocess_images_device(dev, out=out, corrupt=cor), a.iters)[0])
+        spread = lambda ts: {"median": round(statistics.median(ts), 4), "min": round(min(ts), 4), "max": round(max(ts), 4)}
+
+        def kernel_ms(idx):
+            """vt_corrupt alone on the device frames `idx`, tables uploaded once, back-to-back launches between two events."""
+            arr = (_lib.CorruptFrame * len(idx))()
+            off = 0
+            for f, i in zip(arr, idx):
+                f.src, f.pitch, f.h, f.w, f.out_off = dev[i].data_ptr(), 3 * 640, 480, 640, off
+                off += 480 * 640 * 3
+            words = pack_corrupt(arr, [cor[i] for i in idx])
+            fd = torch.from_numpy(np.frombuffer(bytes(memoryview(arr)), dtype=np.uint8).copy()).to(DEV)
+            td = torch.from_numpy(np.concatenate([words, np.zeros(1, dtype=np.uint32)]).view(np.uint8).copy()).to(DEV)
+            buf = torch.empty(off, dtype=torch.uint8, device=DEV)
+            L, st = _lib.lib(), _lib.stream_ptr(torch.device(DEV))
+            call = lambda: _lib.check(L.vt_corrupt(arr, _lib.ptr(fd), len(idx), ctypes.c_void_p(words.ctypes.data), _lib.ptr(td), words.size,
+                                                   _lib.ptr(buf), st), "vt_corrupt")
+            return event_ms(call, 10 * a.iters)
+        r = {"n": n, "bit_identical": same, "blurs": [p.blur if p.blur != "median" and p.blur != "motion" else f"{p.blur} k={p.k}" for p in cor],
+             "repeats": a.repeats,
+             "device_corrupt_from_host_arrays_ms": spread(with_h), "device_uncorrupted_from_host_arrays_ms": spread(without_h),
+             "device_corrupt_from_device_frames_ms": spread(with_d), "device_uncorrupted_from_device_frames_ms": spread(without_d),
+             "corrupt_over_uncorrupted_from_host_arrays": round(statistics.median(with_h) / statistics.median(without_h), 2),
+             "vt_corrupt_back_to_back_ms": {"all_6": kernel_ms(range(n)), "median_k11_alone": kernel_ms([0]), "motion_k37_alone": kernel_ms([1]),
+                                            "noise_alone": kernel_ms([5])},
+             "numpy_statement_once_ms": cpu_once}
+        res["d_corrupt_6"] = r
+        print("d_corrupt_6", r, file=sys.stderr, flush=True)
     if not a.no_step:
         from models.multimodal_encoder.siglip_encoder import SiglipVisionTower
         from models.rdt_runner import RDTRunner

@@ -4,6 +4,7 @@
 #include "vt_kernels.h"
 #include "vt_host.h"
 #include "vt_gemm_route.h"
+#include "vt_philox.h"
 #include "vt_prof.h"
 #include "vt_unet_int.h"
 #include "../../include/vlatouch.h"
@@ -158,15 +159,6 @@ extern "C" int vt_selftest_mfma(float* out_err, vt_stream_t stream) {
 // (`state` = 2 x uint64: key, next counter) and is advanced by a one-thread kernel behind the draw, so a captured hipGraph yields fresh
 // noise on every replay without a host round trip.
 namespace {
-__device__ __forceinline__ void philox_round(uint32_t (&c)[4], const uint32_t k0, const uint32_t k1) {
-  const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-  const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1, n3 = (uint32_t)p0;
-  c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-}
-__device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) { philox_round(c, k0, k1); k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
-}
 // out[i] = N(0, 1) (optionally rounded to the bf16 grid: `noisy_action` lives in bf16 in the reference's bf16 mode), 4 values per thread
 __global__ void randn_kernel(float* __restrict__ out, const long n, const unsigned long long* __restrict__ state, const int round_bf16) {
   const long q = (long)blockIdx.x * blockDim.x + threadIdx.x;

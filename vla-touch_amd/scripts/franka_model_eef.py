@@ -177,13 +177,14 @@ class RoboticDiffusionTransformerModel(object):
             out.append(self.image_processor.preprocess(image, return_tensors="pt")["pixel_values"][0])
         return torch.stack(out, dim=0)
 
-    def preprocess_images_device(self, images, out=None, jitter=None, jpeg=None):
+    def preprocess_images_device(self, images, out=None, jitter=None, jpeg=None, corrupt=None):
         """`preprocess_images(images).to(self.device, self.dtype)`, bit for bit, computed on the card (csrc/vt_imgprep.hip): frames go up
         as raw bytes in one copy; device-resident uint8 [H, W, 3] tensors are used in place.  Per frame: PIL image, HxWx3 uint8 array,
         uint8 tensor (host or device) or None.  `jitter`: per frame None or a vlatouch.imgaug.ColorJitterParams, the training-time
         colour augmentation between the pre-resize / lift and the pad (train/dataset.py:385-391); not part of `preprocess_images`.
         `jpeg`: None or the quality of the reference's cv2 JPEG round trip of every frame that exists (vlatouch.jpegmap), ahead of all
-        else; equals `preprocess_images_device([jpeg_mapping(f, jpeg) ...])`."""
+        else; equals `preprocess_images_device([jpeg_mapping(f, jpeg) ...])`.  `corrupt`: per frame None or a vlatouch.imgaug.CorruptParams,
+        the training-time corruption directly behind the jitter (train/dataset.py:392-393)."""
         from vlatouch.imgprep import DevicePreprocessor
         p, d = self.image_processor, self.args["dataset"]
         size = p.size["height"]
@@ -197,7 +198,7 @@ class RoboticDiffusionTransformerModel(object):
             pp = DevicePreprocessor(size, p.image_mean, p.image_std, self.device, self.dtype, pad=key[6], brightness=key[7], image_size=sz,
                                     rescale_factor=p.rescale_factor)
             self._imgprep = {key: pp}
-        return pp(list(images), out=out, jitter=jitter, jpeg=jpeg)
+        return pp(list(images), out=out, jitter=jitter, jpeg=jpeg, corrupt=corrupt)
 
     @torch.no_grad()
     def step(self, proprio, images, text_embeds, jpeg_mapping=False):

@@ -169,6 +169,12 @@ class JpegmapFrame(C.Structure):     # vt_jpegmap_frame
 JPEGMAP_CV2_ORDER = 1
 
 
+class CorruptFrame(C.Structure):     # vt_corrupt_frame (kind ids: vlatouch/imgaug.py)
+    _fields_ = [("src", C.c_void_p), ("pitch", C.c_long), ("h", C.c_int), ("w", C.c_int), ("out_off", C.c_long), ("key", C.c_ulonglong),
+                ("noise", C.c_int), ("per_channel", C.c_int), ("blur", C.c_int), ("k", C.c_int), ("order", C.c_int), ("noise_off", C.c_int),
+                ("taps_off", C.c_int), ("ntaps", C.c_int), ("tap_sum", C.c_uint), ("reserved", C.c_uint)]
+
+
 class LstmDesc(C.Structure):
     _fields_ = [("state_dim", C.c_int), ("hidden", C.c_int), ("layers", C.c_int), ("force_dim", C.c_int),
                 ("force_pad", C.c_int), ("in_pad", C.c_int), ("cdt", C.c_int)]
@@ -327,6 +333,7 @@ SIGNATURES = {
     "vt_colorjitter": (_I, [_P, _P, _I, _I, _P, _P, _Z, _P]),
     "vt_jpegmap_workspace_bytes": (_Z, [_P, _I]),
     "vt_jpegmap": (_I, [_P, _P, _I, _I, _I, _P, _P, _Z, _P]),
+    "vt_corrupt": (_I, [_P, _P, _I, _P, _P, C.c_long, _P, _P]),
     "vt_rdt_batch": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, C.c_double, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vt_ctrl_batch": (_I, [_P, _P, _P, _P, _P, _P, _I, C.c_longlong, _I, _I, _I, C.c_longlong, _P, _F, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P,
                            _P, _P]),

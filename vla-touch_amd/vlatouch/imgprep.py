@@ -10,11 +10,13 @@ Host side of the feature:
   * `FrameStager`: frames of any accepted kind -> one pinned staging buffer -> one host-to-device copy of raw bytes; device-resident
     frames (pitched views included) are used in place.  `DevicePreprocessor` owns one, `jpeg_mapping_device` one per device.
   * `DevicePreprocessor`: the stager's frames -> a list of stages, each one driver call (`_JpegStage`, `_ResampleStage` for the pre-resize
-    and for the main pass, `_JitterStage`), planned in one loop that carves the workspace and launched in one loop.  With frames of an
-    already-seen geometry at already-seen addresses the call allocates nothing (given `out=`), copies nothing and never synchronises,
-    so it can be captured in a graph together with the tower.
+    and for the main pass, `_JitterStage`, `_CorruptStage`), planned in one loop that carves the workspace and launched in one loop.
+    With frames of an already-seen geometry at already-seen addresses the call allocates nothing (given `out=`), copies nothing and
+    never synchronises, so it can be captured in a graph together with the tower.
   * `jitter=`: the training-time ColorJitter (vlatouch/imgaug.py, csrc/vt_colorjitter.hip) between the `image_size` pre-resize and the
     pad, where the reference's dataset applies it (train/dataset.py:373-409): Resize -> lift -> jitter -> pad -> resize -> normalise.
+  * `corrupt=`: the training-time corruption (`image_corrupt`: noise and blur; vlatouch/imgaug.py, csrc/vt_corrupt.hip) directly behind the
+    jitter, as the reference orders it: Resize -> lift -> jitter -> corruption -> pad -> resize -> normalise.
   * `jpeg=`: the reference's cv2 JPEG round trip of the raw frames (vlatouch/jpegmap.py, csrc/vt_jpegmap.hip) ahead of all of the above,
     where the robot loop and the labeller apply it: JPEG -> Resize -> lift -> jitter -> pad -> resize -> normalise.
 
@@ -31,7 +33,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .imgaug import OP_NONE, ColorJitterParams
+from .imgaug import OP_NONE, TABLE_WORDS_MAX, ColorJitterParams, corrupt_list, pack_corrupt
 from .jpegmap import jpeg_table
 
 BILINEAR, BICUBIC = 1, 2
@@ -177,7 +179,7 @@ class FrameStager:
 # ---- the stages of a call.  Each kind answers the same two questions:
 #   plan(items) -> (output bytes, scratch bytes, [(frame index, offset in the output, h, w), ...]): builds `self.table` over the incoming items
 #       (ptr, h, w, pitch), None for a frame that is missing; the list names the tight uint8 frames it writes, which the next stage reads
-#   launch(wp, st, out, jitter, quality): enqueues on stream `st`, workspace at address `wp`, with this call's arguments
+#   launch(wp, st, out, jitter, quality, corrupt): enqueues on stream `st`, workspace at address `wp`, with this call's arguments
 # `_plan` places the output at `out_off` and the scratch at `ws_off` of the workspace and, once there is a workspace, calls bind().
 class _Stage:
     def bind(self, stager: FrameStager) -> None:
@@ -194,7 +196,7 @@ class _JpegStage(_Stage):
         self.table, out_bytes, ws_bytes = jpeg_table([items[i] for i in self.idx])
         return out_bytes, ws_bytes, [(i, f.out_off, f.h, f.w) for i, f in zip(self.idx, self.table)]
 
-    def launch(self, wp, st, out, jitter, quality):
+    def launch(self, wp, st, out, jitter, quality, corrupt):
         _lib.check(_lib.lib().vt_jpegmap(self.table, _lib.ptr(self.dev), len(self.idx), quality, _lib.JPEGMAP_CV2_ORDER, C.c_void_p(wp + self.out_off),
                                          C.c_void_p(wp + self.ws_off), self.ws_bytes, st), "vt_jpegmap")
 
@@ -236,7 +238,7 @@ class _ResampleStage(_Stage):
             raise _lib.VtError("vt_imgprep_workspace_bytes: " + L.vt_last_error().decode())
         return (0, ws_bytes, []) if self.final else (off, ws_bytes, outputs)
 
-    def launch(self, wp, st, out, jitter, quality):
+    def launch(self, wp, st, out, jitter, quality, corrupt):
         lut, fill, dst = (_lib.ptr(self.pp.lut), self.pp.fill, _lib.ptr(out)) if self.final else (None, 0, C.c_void_p(wp + self.out_off))
         _lib.check(_lib.lib().vt_imgprep(self.table, _lib.ptr(self.dev), len(self.table), self.S, lut, fill, self.flags, dst,
                                          C.c_void_p(wp + self.ws_off), self.ws_bytes, st), self.what)
@@ -267,10 +269,10 @@ class _JitterStage(_Stage):
         self.pin = torch.empty(C.sizeof(self.table), dtype=torch.uint8).pin_memory()
         self.dev = torch.empty(C.sizeof(self.table), dtype=torch.uint8, device=stager.device)
 
-    def launch(self, wp, st, out, jitter, quality):
+    def launch(self, wp, st, out, jitter, quality, corrupt):
         arr = type(self.table).from_buffer_copy(self.table)
         for f, i in zip(arr, self.idx):
-            if jitter[i] is not None:
+            if jitter is not None and jitter[i] is not None:      # no jitter list: the stage is here for the lift ahead of a corruption
                 jitter[i].fill_record(f)
         if self.free is not None:
             self.free.synchronize()                                     # the previous call's copy has left the pinned table
@@ -280,6 +282,46 @@ class _JitterStage(_Stage):
         self.free.record(torch.cuda.current_stream(self.dev.device))
         _lib.check(_lib.lib().vt_colorjitter(arr, _lib.ptr(self.dev), len(self.idx), self.flags, C.c_void_p(wp + self.out_off),
                                              C.c_void_p(wp + self.ws_off), self.ws_bytes, st), "vt_colorjitter")
+
+
+class _CorruptStage(_Stage):
+    """The corruption (vlatouch/imgaug.py, csrc/vt_corrupt.hip) directly behind the jitter: every frame that exists goes through it, an
+    uncorrupted one as a copy.  Records and tables are this call's: one pinned buffer holds the frame table and, behind it, room for
+    `TABLE_WORDS_MAX` words per frame, and goes up in one copy."""
+
+    def __init__(self):
+        self.free: Optional[torch.cuda.Event] = None
+
+    def plan(self, items):
+        self.idx = [i for i, it in enumerate(items) if it is not None]
+        self.table = (_lib.CorruptFrame * len(self.idx))()
+        off = 0
+        for f, i in zip(self.table, self.idx):
+            f.src, f.h, f.w, f.pitch = items[i]
+            f.out_off = off
+            off += _align(3 * f.h * f.w, 16)
+        self.rec_bytes = _align(C.sizeof(self.table), 16)
+        return off, 0, [(i, f.out_off, f.h, f.w) for i, f in zip(self.idx, self.table)]
+
+    def bind(self, stager: FrameStager) -> None:
+        nbytes = self.rec_bytes + 4 * TABLE_WORDS_MAX * len(self.idx)
+        self.pin = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
+        self.dev = torch.empty(nbytes, dtype=torch.uint8, device=stager.device)
+
+    def launch(self, wp, st, out, jitter, quality, corrupt):
+        arr = type(self.table).from_buffer_copy(self.table)
+        words = pack_corrupt(arr, [corrupt[i] for i in self.idx])
+        if self.free is not None:
+            self.free.synchronize()                                     # the previous call's copy has left the pinned buffer
+        pin, used = self.pin.numpy(), self.rec_bytes + 4 * words.size
+        pin[:C.sizeof(arr)] = np.frombuffer(arr, dtype=np.uint8)
+        pin[self.rec_bytes:used] = words.view(np.uint8)
+        self.dev[:used].copy_(self.pin[:used], non_blocking=True)
+        self.free = torch.cuda.Event()
+        self.free.record(torch.cuda.current_stream(self.dev.device))
+        _lib.check(_lib.lib().vt_corrupt(arr, _lib.ptr(self.dev), len(self.idx), words.ctypes.data if words.size else None,
+                                         C.c_void_p(self.dev.data_ptr() + self.rec_bytes), words.size, C.c_void_p(wp + self.out_off), st),
+                   "vt_corrupt")
 
 
 class DevicePreprocessor:
@@ -330,29 +372,32 @@ class DevicePreprocessor:
         return int(sz[0]), int(sz[1])
 
     # ---- planning: everything that depends only on geometry and addresses
-    def _stages(self, jit: bool, jpeg_idx: Optional[tuple]) -> list:
-        """The chain of one call, as the reference orders it: JPEG -> Resize -> (lift and) jitter -> pad, resize, normalise."""
+    def _stages(self, jit: bool, jpeg_idx: Optional[tuple], cor: bool = False) -> list:
+        """The chain of one call, as the reference orders it: JPEG -> Resize -> (lift and) jitter -> corruption -> pad, resize, normalise.
+        The lift precedes the corruption: with `brightness`, a corrupting call runs the jitter stage even where no frame is jittered."""
         stages = []
         if jpeg_idx:
             stages.append(_JpegStage(jpeg_idx))
         if self.image_size is not None:
             stages.append(_ResampleStage(self, _lib.IMGPREP_OUT_U8, final=False))
         flags = self.flags | (_lib.IMGPREP_TWO_PASS if self.force_two_pass else 0)
-        if jit:
+        if jit or (cor and self.brightness):
             stages.append(_JitterStage(self.brightness))
             flags &= ~_lib.IMGPREP_BRIGHT
+        if cor:
+            stages.append(_CorruptStage())
         stages.append(_ResampleStage(self, flags, final=True))
         return stages
 
-    def _plan(self, items, ws_ptr: Optional[int], jit: bool = False, jpeg_idx: Optional[tuple] = None):
-        key = (tuple(items), ws_ptr, self.force_two_pass, jit, jpeg_idx)
+    def _plan(self, items, ws_ptr: Optional[int], jit: bool = False, jpeg_idx: Optional[tuple] = None, cor: bool = False):
+        key = (tuple(items), ws_ptr, self.force_two_pass, jit, jpeg_idx, cor)
         plan = self._plans.get(key)
         if plan is not None:
             return plan
         if len(self._plans) >= 64:                        # plans a captured graph reads (their device tables) are never dropped
             self._plans = {k: v for k, v in self._plans.items() if v.get("captured")}
         base = ws_ptr if ws_ptr is not None else _SIZING_BASE
-        stages, off = self._stages(jit, jpeg_idx), 0
+        stages, off = self._stages(jit, jpeg_idx, cor), 0
         for st in stages:                                 # the workspace, carved: per stage its output, then its scratch, each 256-byte aligned
             out_bytes, st.ws_bytes, outputs = st.plan(items)
             st.out_off, st.ws_off = off, off + _align(out_bytes, 256)
@@ -391,21 +436,25 @@ class DevicePreprocessor:
             raise _lib.VtError(f"jpeg must be None or a quality in 1..100, got {jpeg!r}")
         return int(jpeg), tuple(i for i, im in enumerate(images) if im is not None)
 
-    def workspace_bytes(self, images: Sequence, jitter=None, jpeg=None) -> int:
-        """Bytes of workspace a call on these frames needs (geometry only, plus whether any frame is jittered or JPEG-mapped)."""
+    def workspace_bytes(self, images: Sequence, jitter=None, jpeg=None, corrupt=None) -> int:
+        """Bytes of workspace a call on these frames needs (geometry only, plus whether any frame is jittered, JPEG-mapped or corrupted)."""
         jit = self._jitter_list(images, jitter) is not None
+        cor = corrupt_list(images, corrupt, _lib.VtError) is not None
         items, _ = self.stager.gather(images, self._missing)
-        return self._plan(items, None, jit, self._jpeg_idx(images, jpeg)[1])["ws_bytes"]
+        return self._plan(items, None, jit, self._jpeg_idx(images, jpeg)[1], cor)["ws_bytes"]
 
     @torch.no_grad()
     def __call__(self, images: Sequence, out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None, jitter=None,
-                 jpeg=None) -> torch.Tensor:
+                 jpeg=None, corrupt=None) -> torch.Tensor:
         """-> pixel_values [n, 3, S, S].  `jitter`: None, or one entry per frame, each None or a `ColorJitterParams` (never on a missing
         frame).  Without it, or with every entry None, the call is the unjittered one: same launches, same bits, capturable in a graph.
         A call that jitters writes its parameters into a device table through a pinned buffer and waits for the previous such copy, so
         it is not capturable in a graph.
         `jpeg`: None, or the quality of the reference's cv2 JPEG round trip (vlatouch/jpegmap.py, order "cv2"), applied to every frame
-        that exists before anything else.  Its table is cached with the plan: the call stays as capturable as the plain one."""
+        that exists before anything else.  Its table is cached with the plan: the call stays as capturable as the plain one.
+        `corrupt`: None, or one entry per frame, each None or a `CorruptParams` (never on a missing frame): the training-time corruption
+        (vlatouch/imgaug.py), directly behind the jitter.  Without it, or with every entry None, the call is the one without it.  Like
+        a jittering call it uploads this call's tables through a pinned buffer, so it is not capturable in a graph."""
         n = len(images)
         if n < 1:
             raise _lib.VtError("DevicePreprocessor: no frames")
@@ -413,12 +462,16 @@ class DevicePreprocessor:
         jitter = self._jitter_list(images, jitter)
         jit = jitter is not None
         quality, jpeg_idx = self._jpeg_idx(images, jpeg)
+        corrupt = corrupt_list(images, corrupt, _lib.VtError)
+        cor = corrupt is not None
         if jit and torch.cuda.is_current_stream_capturing():
             raise _lib.VtError("DevicePreprocessor: a call with jitter= cannot be captured in a graph")
+        if cor and torch.cuda.is_current_stream_capturing():
+            raise _lib.VtError("DevicePreprocessor: a call with corrupt= cannot be captured in a graph")
         with torch.cuda.device(self.device):
             items, keep = self.stager.gather(images, self._missing)
             if workspace is None:
-                need = self._plan(items, None, jit, jpeg_idx)["ws_bytes"]
+                need = self._plan(items, None, jit, jpeg_idx, cor)["ws_bytes"]
                 if self._ws is None or self._ws.numel() < need:
                     if self._ws is not None and any(v.get("captured") for v in self._plans.values()):
                         self._keepalive.append(self._ws)          # a captured graph still works in the old one
@@ -426,7 +479,7 @@ class DevicePreprocessor:
                 workspace = self._ws
             elif workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.device != self.device:
                 raise _lib.VtError("workspace must be a contiguous uint8 tensor on the preprocessor's device")
-            plan = self._plan(items, workspace.data_ptr(), jit, jpeg_idx)
+            plan = self._plan(items, workspace.data_ptr(), jit, jpeg_idx, cor)
             if torch.cuda.is_current_stream_capturing():
                 plan["captured"] = True
             if workspace.numel() < plan["ws_bytes"]:
@@ -437,5 +490,5 @@ class DevicePreprocessor:
                 raise _lib.VtError(f"out must be a contiguous {self.dtype} [{n}, 3, {S}, {S}] tensor on {self.device}")
             wp, st = workspace.data_ptr(), _lib.stream_ptr(self.device)
             for stage in plan["stages"]:
-                stage.launch(wp, st, out, jitter, quality)
+                stage.launch(wp, st, out, jitter, quality, corrupt)
         return out

@@ -8,7 +8,7 @@ Replaces the reference's data path for `episode_*.h5` files (VLAConsumerDataset 
   * the random decisions of `get_item`, `parse_file` and `VLAConsumerDataset.__getitem__` (train/dataset.py:300-442) are `EpisodeStore.draw`,
     which consumes numpy's, `random`'s and torch's streams in the reference's order and returns small host records (`SamplePlan`);
   * the sample's arrays and the collator's stacks (train/dataset.py:460-533) are one vt_rdt_batch call (csrc/vt_rdt_data.hip) in
-    `EpisodeStore.assemble`, whose result is the mapping `prepare_batch` / `sample_eval` take, with raw `frames` and `jitter`.
+    `EpisodeStore.assemble`, whose result is the mapping `prepare_batch` / `sample_eval` take, with raw `frames`, `jitter` and `corrupt`.
 
 Only precomputed instruction embeddings are built (`instruct_embeddings[0]`, the reference's use_precomp_lang_embed); `input_ids` and the
 instruction masking draw are not.  Deviations from the reference are listed in INTEGRATION.md.  Everything except `upload` / `assemble` /
@@ -71,12 +71,12 @@ class SamplePlan:
     state_masked / elem_masked: the three condition masks; frame_idx [hist] and slot_valid [hist]: the frame each history slot shows and
     whether parse_file marks it valid; frame_valid [hist * cameras] (slot-major): valid, present and not masked, i.e. not the background;
     noise: the standard-normal draws at the state indices [S] or None, and noise_snr, the SNR in dB they are scaled for; jitter
-    [hist * cameras]: ColorJitterParams or None per frame."""
+    [hist * cameras]: ColorJitterParams or None per frame; corrupt [hist * cameras]: CorruptParams or None per frame."""
     __slots__ = ("episode", "step_id", "action_id", "ctrl_masked", "state_masked", "elem_masked", "frame_idx", "slot_valid", "frame_valid", "noise",
-                 "noise_snr", "jitter")
+                 "noise_snr", "jitter", "corrupt")
 
     def __init__(self, episode, step_id, ctrl_masked, state_masked, elem_masked, frame_idx, slot_valid, frame_valid, noise=None, jitter=None,
-                 action_id=None, noise_snr=None):
+                 action_id=None, noise_snr=None, corrupt=None):
         self.episode, self.step_id = int(episode), int(step_id)
         self.action_id = self.step_id + 2 if action_id is None else int(action_id)
         self.ctrl_masked, self.state_masked, self.elem_masked = bool(ctrl_masked), bool(state_masked), bool(elem_masked)
@@ -84,6 +84,7 @@ class SamplePlan:
         self.noise = None if noise is None else np.asarray(noise, dtype=np.float64)
         self.noise_snr = None if noise is None else noise_snr
         self.jitter = [None] * len(self.frame_valid) if jitter is None else list(jitter)
+        self.corrupt = [None] * len(self.frame_valid) if corrupt is None else list(corrupt)
 
     def flags(self) -> int:
         return (MASK_FREQ * self.ctrl_masked | MASK_STATE * self.state_masked | MASK_ELEM * self.elem_masked | NOISE * (self.noise is not None))
@@ -244,16 +245,22 @@ class EpisodeStore:
 
     # ---- the draws
     def draw(self, B: int, *, np_rng, rng, generator: Optional[torch.Generator] = None, cond_mask_prob: float = 0.1, cam_ext_mask_prob: float = -1.0,
-             state_noise_snr: Optional[float] = None, image_aug: bool = False) -> List[SamplePlan]:
+             state_noise_snr: Optional[float] = None, image_aug: bool = False, image_corrupt: bool = False, corrupt_rng=None) -> List[SamplePlan]:
         """B samples' decisions, one sample after the other, from np_rng (numpy's legacy interface: `np.random` or a RandomState), rng (`random`
         or a random.Random) and generator (torch; None = the global one), each consumed as the reference consumes its global stream:
         get_item's choice(p=weights), parse_file's randint(first_idx - 1, N - int(horizon / 2)), then __getitem__'s random() for ctrl_freq,
         normal(0, 1, (1, state_dim)) when state_noise_snr is set (all state_dim draws; the reference's normal(0, scale, shape) equals scale
         times these), random() for the state, random() for the element mask, one random() per frame that is valid and present (against
         cam_ext_mask_prob for camera 0 when that is >= 0, else cond_mask_prob) in slot-major order, and the augmentation draws
-        (vlatouch.imgaug.draw_image_aug) when image_aug."""
+        (vlatouch.imgaug.draw_image_aug) when image_aug.  image_corrupt (only with image_aug): the frames whose augmentation type asks for
+        it also get corruption parameters, drawn from corrupt_rng (a numpy `Generator`) alone, so every other decision and the three
+        streams above are the same with and without it."""
         if int(B) != B or B < 1:
             raise ValueError(f"draw: B must be an integer >= 1, got {B!r}")
+        if image_corrupt and not image_aug:
+            raise ValueError("draw: image_corrupt needs image_aug (the corruption is one of the augmentation types)")
+        if image_corrupt and corrupt_rng is None:
+            raise ValueError("draw: image_corrupt needs a corrupt_rng (a numpy Generator)")
         ncam, hist = len(self.cameras), self.hist
         mask_probs = [cond_mask_prob] * ncam
         if cam_ext_mask_prob >= 0.0:
@@ -277,9 +284,13 @@ class EpisodeStore:
             for i in range(hist):
                 for j in range(ncam):
                     frame_valid.append(bool(slot_valid[i] and ep.has_cam[j] and rng.random() > mask_probs[j]))
-            jitter = draw_image_aug(frame_valid, rng=rng, generator=generator) if image_aug else None
+            jitter = corrupt = None
+            if image_aug and image_corrupt:
+                jitter, corrupt = draw_image_aug(frame_valid, rng=rng, generator=generator, corrupt_rng=corrupt_rng)
+            elif image_aug:
+                jitter = draw_image_aug(frame_valid, rng=rng, generator=generator)
             plans.append(SamplePlan(e, step, ctrl_masked, state_masked, elem_masked, frame_idx, slot_valid, frame_valid, noise, jitter,
-                                    noise_snr=state_noise_snr))
+                                    noise_snr=state_noise_snr, corrupt=corrupt))
         return plans
 
     def check_plans(self, plans: Sequence[SamplePlan]) -> None:
@@ -302,8 +313,11 @@ class EpisodeStore:
                 raise ValueError(f"assemble: plan {k}: noise must hold {len(self.state_indices)} draws, got {p.noise.shape}")
             if p.noise is not None and (p.noise_snr is None or p.noise_snr != snrs.setdefault("snr", p.noise_snr)):
                 raise ValueError(f"assemble: plan {k}: noise draws need a noise_snr, the same for every noised plan of a batch (got {p.noise_snr!r})")
-            if len(p.frame_idx) != self.hist or len(p.frame_valid) != nfr or len(p.jitter) != nfr:
-                raise ValueError(f"assemble: plan {k}: {self.hist} frame indices and {nfr} frame flags / jitter entries expected")
+            if len(p.frame_idx) != self.hist or len(p.frame_valid) != nfr or len(p.jitter) != nfr or len(p.corrupt) != nfr:
+                raise ValueError(f"assemble: plan {k}: {self.hist} frame indices and {nfr} frame flags / jitter / corrupt entries expected")
+            for q, c in enumerate(p.corrupt):
+                if c is not None and not p.frame_valid[q]:
+                    raise ValueError(f"assemble: plan {k}: frame {q} is missing and cannot be corrupted")
             for i, fi in enumerate(p.frame_idx):
                 if not 0 <= fi < n:
                     raise ValueError(f"assemble: plan {k}: frame index {fi} of slot {i} is outside the episode")
@@ -363,7 +377,7 @@ class EpisodeStore:
         """plans -> the collator's mapping on the device: states [B, 1, A], actions [B, H, A], state_elem_mask [B, A], state_norm [B, A] (fp32),
         ctrl_freqs [B] int64, data_indices (list), lang_embeds [B, Lmax, D] zero padded, lang_attn_mask [B, Lmax] bool, frames (B lists of
         hist * cameras entries, slot-major: a uint8 [H, W, 3] view into the resident episode, a host array for an episode kept in pinned
-        memory, or None for the background) and jitter (B lists, or None when no plan carries any)."""
+        memory, or None for the background), jitter (B lists, or None when no plan carries any) and, where a plan carries any, corrupt."""
         plans = list(plans)
         self.check_plans(plans)
         snr = next((p.noise_snr for p in plans if p.noise is not None), None)
@@ -393,6 +407,8 @@ class EpisodeStore:
         out["data_indices"] = [self.data_idx] * B
         out["frames"] = [[d["frames"][p.episode][q % ncam][p.frame_idx[q // ncam]] if v else None for q, v in enumerate(p.frame_valid)] for p in plans]
         out["jitter"] = [list(p.jitter) for p in plans] if any(j is not None for p in plans for j in p.jitter) else None
+        if any(c is not None for p in plans for c in p.corrupt):
+            out["corrupt"] = [list(p.corrupt) for p in plans]
         return out
 
     def plan_batches(self, batch_size: int, rank: int = 0, world_size: int = 1, **draw_kwargs) -> Iterator[List[SamplePlan]]:

@@ -1105,10 +1105,10 @@ def latest_checkpoint(output_dir: str) -> Optional[str]:
     return max(dirs, key=lambda d: int(d.split("-", 1)[1])) if dirs else None
 
 
-def _batch_img_tokens(batch, B: int, who: str, vision_encoder, preprocessor, jitter):
+def _batch_img_tokens(batch, B: int, who: str, vision_encoder, preprocessor, jitter, corrupt=None):
     """The image tokens of a collator batch: ready `img_tokens`; `images` [B, N, C, H, W] through `vision_encoder` (train.py:420-423,
     sample.py:34-36); or `frames`, B lists of N raw frames (None = missing), through `preprocessor` (vlatouch.imgprep.DevicePreprocessor,
-    with the flat per-frame `jitter` list or B lists of N) and then `vision_encoder`."""
+    with the flat per-frame `jitter` and `corrupt` lists or B lists of N) and then `vision_encoder`."""
     if "img_tokens" in batch:
         return batch["img_tokens"]
     if vision_encoder is None:
@@ -1125,7 +1125,9 @@ def _batch_img_tokens(batch, B: int, who: str, vision_encoder, preprocessor, jit
         flat = [f for sample in frames for f in sample]
         if jitter is not None and len(jitter) == B and all(isinstance(j, (list, tuple)) for j in jitter):
             jitter = [p for sample in jitter for p in sample]
-        pixel_values = preprocessor(flat, jitter=jitter)
+        if corrupt is not None and len(corrupt) == B and all(isinstance(c, (list, tuple)) for c in corrupt):
+            corrupt = [p for sample in corrupt for p in sample]
+        pixel_values = preprocessor(flat, jitter=jitter) if corrupt is None else preprocessor(flat, jitter=jitter, corrupt=corrupt)
     return vision_encoder(pixel_values).detach().reshape(B, -1, vision_encoder.hidden_size)
 
 
@@ -1137,19 +1139,22 @@ def _batch_lang_tokens(batch, who: str, text_encoder):
     return text_encoder(input_ids=batch["input_ids"], attention_mask=batch["lang_attn_mask"])["last_hidden_state"].detach()
 
 
-def prepare_batch(batch, *, vision_encoder=None, text_encoder=None, preprocessor=None, jitter=None) -> dict:
+def prepare_batch(batch, *, vision_encoder=None, text_encoder=None, preprocessor=None, jitter=None, corrupt=None) -> dict:
     """What train.py:407-437 does between the loader and `rdt(...)`: the reference collator's mapping -> `train_step`'s keyword arguments.
     `states[:, -1:, :]` is the state token, `state_elem_mask.unsqueeze(1)` the action mask, `actions` the target, `ctrl_freqs` and
     `lang_attn_mask` pass as they are; the language is `lang_embeds` or `input_ids` through `text_encoder`; the image tokens are `img_tokens`,
     `images` through `vision_encoder`, or (not in the reference) raw `frames` through `preprocessor` and `vision_encoder`, with the colour
-    augmentation `jitter` (the argument, or the batch's key of that name; vlatouch.imgaug.draw_image_aug) applied on the device.  Optional
+    augmentation `jitter` and the corruption `corrupt` (the arguments, or the batch's keys of those names; vlatouch.imgaug.draw_image_aug)
+    applied on the device.  Optional
     `noise` / `timesteps` keys prescribe train_step's two random draws."""
     states = torch.as_tensor(batch["states"])
     B = states.shape[0]
     if jitter is None:
         jitter = batch.get("jitter")
+    if corrupt is None:
+        corrupt = batch.get("corrupt")
     kw = {"lang_tokens": _batch_lang_tokens(batch, "prepare_batch", text_encoder), "lang_attn_mask": batch["lang_attn_mask"],
-          "img_tokens": _batch_img_tokens(batch, B, "prepare_batch", vision_encoder, preprocessor, jitter),
+          "img_tokens": _batch_img_tokens(batch, B, "prepare_batch", vision_encoder, preprocessor, jitter, corrupt),
           "state_tokens": states[:, -1:, :], "action_gt": batch["actions"], "action_mask": torch.as_tensor(batch["state_elem_mask"]).unsqueeze(1),
           "ctrl_freqs": batch["ctrl_freqs"]}
     for key in ("noise", "timesteps"):                # train_step's two random draws, where a batch prescribes them (tests)
@@ -1222,7 +1227,7 @@ def sample_eval_sums(runner, batches, *, num_sample_batches: int, dataset_id2nam
         B, H, A = actions.shape
         if len(data_indices) != B or mask.shape != (B, A) or state_norm.shape != (B, A):
             raise ValueError("sample_eval: data_indices must hold B entries, state_elem_mask and state_norm must be [B, action_dim]")
-        img_tokens = _batch_img_tokens(batch, B, "sample_eval", vision_encoder, preprocessor, batch.get("jitter"))
+        img_tokens = _batch_img_tokens(batch, B, "sample_eval", vision_encoder, preprocessor, batch.get("jitter"), batch.get("corrupt"))
         lang_attn_mask = batch["lang_attn_mask"]
         lang_tokens = _batch_lang_tokens(batch, "sample_eval", text_encoder)
         kw = {"x_init": batch["x_init"]} if batch.get("x_init") is not None else {}
