@@ -203,12 +203,21 @@ int vt_dino_set_packed(vt_dino_t h, void* buf, vt_stream_t stream);
 int vt_dino_set_range_flag(vt_dino_t h, unsigned* word);      /* see vt_rdt_set_range_flag */
 /* imgs[ncams] device pointers; is_u8: uint8 pixels else fp32; nhwc: [B,H,W,3] else [B,3,H,W];
  * pre_scale: 1/255 when the caller passed a numpy array (visual_encoder.py:66) else 1;
- * norm_mode: 0 auto (reference behaviour), 1 force ImageNet-normalise, 2 never;
+ * norm_mode: 0 auto (reference behaviour), 1 force ImageNet-normalise, 2 never; in all three a camera batch whose largest value
+ *   (times pre_scale) exceeds 1 is divided by 255 (visual_encoder.py:78).  3 raw: scale = pre_scale, no such rule and no normalisation: the
+ *   pixel values reach the patch embedding as they are (the SigLIP tower, whose image processor has already rescaled and normalised them;
+ *   the statistics kernels still run and report max and mean);
  * pos_patch: [grid*grid][hidden] fp32 position embeddings already interpolated for `res`;
  * out: [ncams][B][hidden] fp32 pooler_output; flags_out (optional) [ncams][4] = {scale, normalised, max, mean}. */
 int vt_dino_forward(vt_dino_t h, const void* const* imgs, int ncams, int is_u8, int nhwc, float pre_scale,
                     int norm_mode, int B, int res, const float* pos_patch, float* out, float* flags_out,
                     void* workspace, vt_stream_t stream);
+/* The front end of vt_dino_forward alone, through the same code: statistics, patchify, patch-embed GEMM + position embedding, CLS row.
+ * Same image arguments and workspace (vt_dino_workspace_bytes); tokens: [ncams*B][tokens][hidden] fp32, the residual stream as the first
+ * block receives it, written straight into the caller's buffer; flags_out as above. */
+int vt_dino_embed(vt_dino_t h, const void* const* imgs, int ncams, int is_u8, int nhwc, float pre_scale,
+                  int norm_mode, int B, int res, const float* pos_patch, float* tokens, float* flags_out,
+                  void* workspace, vt_stream_t stream);
 
 /* ---------------------------------------------------------------- T5 v1.1 text encoder (csrc/vt_t5.hip)
  * Replaces HF T5EncoderModel (feed_forward_proj "gated-gelu") of models/multimodal_encoder/t5_encoder.py::T5Embedder, used by

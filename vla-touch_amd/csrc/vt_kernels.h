@@ -5,7 +5,7 @@
 #include "vt_gemm.h"
 
 enum { VT_NORM_LAYER = 0, VT_NORM_RMS_MEANSQ = 1, VT_NORM_RMS_VAR = 2 };
-enum { VT_IMGNORM_AUTO = 0, VT_IMGNORM_ON = 1, VT_IMGNORM_OFF = 2 };
+enum { VT_IMGNORM_AUTO = 0, VT_IMGNORM_ON = 1, VT_IMGNORM_OFF = 2, VT_IMGNORM_RAW = 3 };   // RAW: scale = pre_scale, no max > 1 rule, no normalisation
 
 struct VtGnParams {
   const float* P; int nslabs; long slab_stride; long p_gs; long ldp;   // fp32 partial slabs [slab][rows][ldp]

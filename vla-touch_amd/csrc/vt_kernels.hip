@@ -586,7 +586,7 @@ __global__ __launch_bounds__(64) void imgstat_final_kernel(const float* __restri
   if (threadIdx.x != 0) return;
   mx *= pre_scale;
   float scale = pre_scale;
-  if (mx > 1.0f) scale = pre_scale / 255.0f;
+  if (mx > 1.0f && norm_mode != VT_IMGNORM_RAW) scale = pre_scale / 255.0f;     // RAW: the caller's pixel values as they are (SigLIP's processor output)
   const float mean = (float)(sm / (double)n) * scale;
   flags[0] = scale;
   flags[1] = norm_mode == VT_IMGNORM_AUTO ? (mean < 0.5f ? 0.f : 1.f) : (norm_mode == VT_IMGNORM_ON ? 1.f : 0.f);

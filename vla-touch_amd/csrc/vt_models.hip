@@ -116,6 +116,41 @@ DWs dcarve(const vt_dino_s* h, int Bt, int res) {
 
 size_t vt_dino_workspace_bytes(vt_dino_t h, int B_total, int res) { return h ? dcarve(h, B_total, res).total : 0; }
 
+namespace {
+// Steps 1 and 2 of the ViT forward, shared by vt_dino_forward (tok = the workspace's residual stream) and vt_dino_embed (tok = the caller's buffer):
+// per-camera statistics -> branch flags, patchify with the camera's own decision, patch-embed GEMM + position embedding, CLS row.
+int dino_embed_steps(const vt_dino_s* h, const void* const* imgs, int ncams, int is_u8, int nhwc, float pre_scale, int norm_mode, int B, int res,
+                     const float* pos_patch, float* tok, float* flags_out, char* ws, const DWs& w, hipStream_t s) {
+  const vt_dino_desc& d = h->d;
+  const int g = res / d.patch, np = g * g, cls = d.no_cls ? 0 : 1, N = np + cls, D = d.hidden, Bt = ncams * B, a = vt_dt_bytes(d.adt);
+  // 1. per-camera statistics -> branch flags; patchify with the camera's own decision
+  for (int c = 0; c < ncams; ++c) {
+    float* part = (float*)(ws + w.part) + c * 512;
+    float* flags = (float*)(ws + w.flags) + c * 8;
+    const long n = (long)B * 3 * res * res;
+    CK(vt_wrap(vt_k_imgstats(imgs[c], is_u8, n, pre_scale, norm_mode, part, flags, s, flags_out ? flags_out + c * 4 : nullptr), "dino imgstats"));
+    CK(vt_wrap(vt_k_patchify(imgs[c], is_u8, nhwc, B, res, g, d.kpad, flags, ws + w.apatch + (size_t)c * B * np * d.kpad * a, d.adt, s), "dino patchify"));
+  }
+  // 2. patch-embed GEMM, one group per image, + position embedding (shared residual) -> fp32 tokens rows 1..np
+  VtGemmParams p = vt_linear(ws + w.apatch, d.adt, d.kpad, h->patch_w, d.cdt, d.kpad, h->patch_b, tok + (size_t)cls * D, VT_F32, D, np, D, d.kpad, VT_ACT_NONE);
+  p.groups = Bt; p.a_gs = (long)np * d.kpad; p.w_gs = 0; p.c_gs = (long)N * D; p.bias_gs = 0;
+  p.residual = pos_patch; p.ldr = D; p.r_gs = 0;
+  CK(vt_wrap(vt_gemm_launch(p, s), "dino patch embed"));
+  if (cls) CK(vt_k_bcast_row(h->cls_pos0, tok, (long)N * D, Bt, D, s));
+  return VT_OK;
+}
+}  // namespace
+
+int vt_dino_embed(vt_dino_t h, const void* const* imgs, int ncams, int is_u8, int nhwc, float pre_scale, int norm_mode, int B, int res,
+                  const float* pos_patch, float* tokens, float* flags_out, void* workspace, vt_stream_t stream) {
+  if (!h || !imgs || !pos_patch || !tokens || !workspace) return vt_fail(VT_ERR_ARG, "vt_dino_embed: null argument");
+  if (ncams < 1 || ncams > 8 || B < 1 || res < 14) return vt_fail(VT_ERR_ARG, "vt_dino_embed: bad sizes");
+  for (int c = 0; c < ncams; ++c)
+    if (!imgs[c]) return vt_fail(VT_ERR_ARG, "vt_dino_embed: null camera pointer");
+  return dino_embed_steps(h, imgs, ncams, is_u8, nhwc, pre_scale, norm_mode, B, res, pos_patch, tokens, flags_out, (char*)workspace,
+                          dcarve(h, ncams * B, res), (hipStream_t)stream);
+}
+
 int vt_dino_forward(vt_dino_t h, const void* const* imgs, int ncams, int is_u8, int nhwc, float pre_scale, int norm_mode, int B, int res,
                     const float* pos_patch, float* out, float* flags_out, void* workspace, vt_stream_t stream) {
   if (!h || !imgs || !pos_patch || !out || !workspace) return vt_fail(VT_ERR_ARG, "vt_dino_forward: null argument");
@@ -129,22 +164,8 @@ int vt_dino_forward(vt_dino_t h, const void* const* imgs, int ncams, int is_u8, 
   char* ws = (char*)workspace;
   const DWs w = dcarve(h, Bt, res);
   float* tok = (float*)(ws + w.tok);
-  // 1. per-camera statistics -> branch flags; patchify with the camera's own decision
-  for (int c = 0; c < ncams; ++c) {
-    float* part = (float*)(ws + w.part) + c * 512;
-    float* flags = (float*)(ws + w.flags) + c * 8;
-    const long n = (long)B * 3 * res * res;
-    CK(vt_wrap(vt_k_imgstats(imgs[c], is_u8, n, pre_scale, norm_mode, part, flags, s, flags_out ? flags_out + c * 4 : nullptr), "dino imgstats"));
-    CK(vt_wrap(vt_k_patchify(imgs[c], is_u8, nhwc, B, res, g, d.kpad, flags, ws + w.apatch + (size_t)c * B * np * d.kpad * a, d.adt, s), "dino patchify"));
-  }
-  // 2. patch-embed GEMM, one group per image, + position embedding (shared residual) -> fp32 tokens rows 1..np
-  {
-    VtGemmParams p = vt_linear(ws + w.apatch, d.adt, d.kpad, h->patch_w, d.cdt, d.kpad, h->patch_b, tok + (size_t)cls * D, VT_F32, D, np, D, d.kpad, VT_ACT_NONE);
-    p.groups = Bt; p.a_gs = (long)np * d.kpad; p.w_gs = 0; p.c_gs = (long)N * D; p.bias_gs = 0;
-    p.residual = pos_patch; p.ldr = D; p.r_gs = 0;
-    CK(vt_wrap(vt_gemm_launch(p, s), "dino patch embed"));
-    if (cls) CK(vt_k_bcast_row(h->cls_pos0, tok, (long)N * D, Bt, D, s));
-  }
+  // 1., 2. statistics, patchify, patch embed + position embedding, CLS row
+  CK(dino_embed_steps(h, imgs, ncams, is_u8, nhwc, pre_scale, norm_mode, B, res, pos_patch, tok, flags_out, ws, w, s));
   const int M = Bt * N;
   // The reference consumes only pooler_output = the CLS row of the last layer (visual_encoder.py:88-93): in the LAST block every token still feeds
   // K and V, but only the CLS row needs a query, the output projection, the MLP and the residual updates (SURVEY 2.1 "last layer prunes to the CLS

@@ -43,7 +43,7 @@ ACT_NONE, ACT_GELU_ERF, ACT_GELU_TANH, ACT_SILU, ACT_MISH, ACT_SWIGLU, ACT_GEGLU
 # vt_gemm_route_of (include/vlatouch.h, VT_ROUTE_*)
 ROUTE_NAMES = ("UNSUPPORTED", "BAD_ARG", "REG", "F32R", "GLDS", "PP", "PT", "PPK", "PW", "PWS", "ROWSPLIT")
 NORM_LAYER, NORM_RMS_MEANSQ, NORM_RMS_VAR = 0, 1, 2
-IMGNORM_AUTO, IMGNORM_ON, IMGNORM_OFF = 0, 1, 2
+IMGNORM_AUTO, IMGNORM_ON, IMGNORM_OFF, IMGNORM_RAW = 0, 1, 2, 3       # RAW: no max > 1 rule, no normalisation (include/vlatouch.h, vt_dino_forward)
 
 
 class VtError(RuntimeError):
@@ -245,6 +245,7 @@ SIGNATURES = {
     "vt_dino_set_packed": (_I, [_P, _P, _P]),
     "vt_dino_set_range_flag": (_I, [_P, _P]),
     "vt_dino_forward": (_I, [_P, _P, _I, _I, _I, _F, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "vt_dino_embed": (_I, [_P, _P, _I, _I, _I, _F, _I, _I, _I, _P, _P, _P, _P, _P]),
     "vt_t5_create": (_I, [_P, _P, _I, _P]),
     "vt_t5_destroy": (None, [_P]),
     "vt_t5_num_weights": (_I, [_P]),

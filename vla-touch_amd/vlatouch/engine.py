@@ -313,9 +313,10 @@ class UNetEngine(_Engine):
 
 # =========================================================================================== DINOv2
 class DinoEngine(_Engine, RangeGuard):
-    """HF Dinov2Model state dict -> CLS features (pooler_output)."""
+    """HF Dinov2Model state dict -> CLS features (pooler_output); with `out_all=True` every token of the final LayerNorm (last_hidden_state:
+    the last block then runs in full instead of pruned to the CLS query)."""
 
-    def __init__(self, sd: SD, *, heads: int, precision: str = "fp32", device="cuda", patch: int = 14, eps: float = 1e-6):
+    def __init__(self, sd: SD, *, heads: int, precision: str = "fp32", device="cuda", patch: int = 14, eps: float = 1e-6, out_all: bool = False):
         self.device = L.require_gpu(device)
         cdt, adt = precision_dtypes(precision)
         self.cdt, self.adt = cdt, adt
@@ -333,6 +334,24 @@ class DinoEngine(_Engine, RangeGuard):
         # dinov2-giant: gated FFN (HF Dinov2SwiGLUFFN: weights_in [2F, D] -> silu(x1) * x2 -> weights_out [D, F]); the others: fc1 / GELU / fc2
         self.swiglu = "encoder.layer.0.mlp.weights_in.weight" in sd
         fc1n, fc2n = ("mlp.weights_in", "mlp.weights_out") if self.swiglu else ("mlp.fc1", "mlp.fc2")
+        # HF's SwiGLU width is a multiple of 8 only (hidden 128 -> 344); the driver takes multiples of 16 and the 16-bit GEMM tiles K % 64: zero-pad
+        # x1 | x2 and weights_out's columns (silu(0) * 0 = 0 times zero columns: exact).  Giant's 4096 is left as it is.
+        F0 = sd[f"encoder.layer.0.{fc2n}.weight"].shape[1] if self.swiglu else 0
+        Fp = _pad_to(F0, 64)
+
+        def fc1_pad(w):           # [2F, D] or [2F] -> [2Fp, ...]: each half padded with zero rows
+            if not self.swiglu or Fp == F0:
+                return w
+            out = torch.zeros(2, Fp, *w.shape[1:])
+            out[:, :F0] = w.reshape(2, F0, *w.shape[1:])
+            return out.reshape(2 * Fp, *w.shape[1:])
+
+        def fc2_pad(w):           # [D, F] -> [D, Fp]
+            if not self.swiglu or Fp == F0:
+                return w
+            out = torch.zeros(w.shape[0], Fp)
+            out[:, :F0] = w
+            return out
         dev = self.device
         pwp = torch.zeros(D, self.kpad)
         pwp[:, : 3 * patch * patch] = pw.reshape(D, -1)
@@ -348,8 +367,8 @@ class DinoEngine(_Engine, RangeGuard):
                   g(f"{p}.attention.output.dense.weight").to(wdt).to(dev), g(f"{p}.attention.output.dense.bias").to(dev),
                   g(f"{p}.layer_scale1.lambda1").to(dev),
                   g(f"{p}.norm2.weight").to(dev), g(f"{p}.norm2.bias").to(dev),
-                  g(f"{p}.{fc1n}.weight").to(wdt).to(dev), g(f"{p}.{fc1n}.bias").to(dev),
-                  g(f"{p}.{fc2n}.weight").to(wdt).to(dev), g(f"{p}.{fc2n}.bias").to(dev),
+                  fc1_pad(g(f"{p}.{fc1n}.weight")).to(wdt).to(dev), fc1_pad(g(f"{p}.{fc1n}.bias")).to(dev),
+                  fc2_pad(g(f"{p}.{fc2n}.weight")).to(wdt).to(dev), g(f"{p}.{fc2n}.bias").to(dev),
                   g(f"{p}.layer_scale2.lambda1").to(dev)]
         W += [g("layernorm.weight").to(dev), g("layernorm.bias").to(dev)]
         W = [w.contiguous() for w in W]
@@ -358,7 +377,9 @@ class DinoEngine(_Engine, RangeGuard):
         desc.hidden, desc.layers, desc.heads, desc.patch, desc.kpad = D, layers, heads, patch, self.kpad
         desc.cdt, desc.adt, desc.eps = cdt, adt, eps
         if self.swiglu:
-            desc.act, desc.mlp_dim = L.ACT_SWIGLU, sd[f"encoder.layer.0.{fc2n}.weight"].shape[1]
+            desc.act, desc.mlp_dim = L.ACT_SWIGLU, Fp
+        self.out_all = bool(out_all)
+        desc.out_all = int(self.out_all)
         self._create("dino", desc, W)
         # fragment-packed second copies of the fc1 weights (16-bit GELU models): the rows a 256-row tiling of the token matrix leaves over, and the CLS-only last
         # block, run fc1 on the small-M packed-weight tile (csrc/vt_gemm_pws.hip)
@@ -383,34 +404,51 @@ class DinoEngine(_Engine, RangeGuard):
             self._pos_cache[grid] = pp[0].contiguous().to(self.device)
         return self._pos_cache[grid]
 
-    def forward(self, cams: Sequence[torch.Tensor], *, nhwc: bool, pre_scale: float = 1.0, norm_mode: int = L.IMGNORM_AUTO) -> torch.Tensor:
-        """cams: list of image batches (same shape/dtype, fp32 or uint8) -> [ncams, B, hidden] fp32.
-        Each camera batch gets its own max()/mean() decision (visual_encoder.py:78,100)."""
-        x0 = cams[0]
+    def _frames(self, what: str, cams: Sequence[torch.Tensor], nhwc: bool):
+        """The checks and conversions `forward` and `embed` share -> (device batches, is_u8, B, res)."""
         is_u8 = all(c.dtype == torch.uint8 for c in cams)      # one element type per call: mixed batches are read as fp32
         cams = [c.to(self.device).contiguous() if is_u8 else c.to(self.device, torch.float32).contiguous() for c in cams]
         B = cams[0].shape[0]
         res = cams[0].shape[1] if nhwc else cams[0].shape[2]
         for c in cams:
             if c.dim() != 4 or c.shape != cams[0].shape:
-                raise ValueError(f"DinoEngine.forward: every camera batch must be 4-D with one shape, got {[tuple(k.shape) for k in cams]}")
+                raise ValueError(f"DinoEngine.{what}: every camera batch must be 4-D with one shape, got {[tuple(k.shape) for k in cams]}")
             if (c.shape[-1] if nhwc else c.shape[1]) != 3:
-                raise ValueError(f"DinoEngine.forward: expected 3 colour channels, got shape {tuple(c.shape)} (nhwc={nhwc})")
+                raise ValueError(f"DinoEngine.{what}: expected 3 colour channels, got shape {tuple(c.shape)} (nhwc={nhwc})")
             if not ((c.shape[1] == c.shape[2]) if nhwc else (c.shape[2] == c.shape[3])):
-                raise ValueError(f"DinoEngine.forward: square frames only, got shape {tuple(c.shape)}")
+                raise ValueError(f"DinoEngine.{what}: square frames only, got shape {tuple(c.shape)}")
         if res < self.patch:
-            raise ValueError(f"DinoEngine.forward: frames of {res} px are smaller than one {self.patch}-px patch")
-        grid = res // self.patch
+            raise ValueError(f"DinoEngine.{what}: frames of {res} px are smaller than one {self.patch}-px patch")
+        return cams, is_u8, B, res
+
+    def _run(self, fn: str, cams, is_u8, nhwc, pre_scale, norm_mode, B, res, out: torch.Tensor) -> torch.Tensor:
         n = len(cams)
-        out = torch.empty(n, B, self.hidden, dtype=torch.float32, device=self.device)
         flags = torch.empty(n, 4, dtype=torch.float32, device=self.device)
         lib = L.lib()
         ws = self._ws.get(lib.vt_dino_workspace_bytes(self._h, n * B, res))
-        L.check(lib.vt_dino_forward(self._h, L.ptr_array(cams), n, int(is_u8), int(nhwc), C.c_float(pre_scale), norm_mode, B, res,
-                                    L.ptr(self.pos_patch(grid)), L.ptr(out), L.ptr(flags), L.ptr(ws), L.stream_ptr(self.device)),
-                "vt_dino_forward")
+        L.check(getattr(lib, fn)(self._h, L.ptr_array(cams), n, int(is_u8), int(nhwc), C.c_float(pre_scale), norm_mode, B, res,
+                                 L.ptr(self.pos_patch(res // self.patch)), L.ptr(out), L.ptr(flags), L.ptr(ws), L.stream_ptr(self.device)), fn)
         self.last_flags = flags
         return out
+
+    def forward(self, cams: Sequence[torch.Tensor], *, nhwc: bool, pre_scale: float = 1.0, norm_mode: int = L.IMGNORM_AUTO) -> torch.Tensor:
+        """cams: list of image batches (same shape/dtype, fp32 or uint8) -> [ncams, B, hidden] fp32 ([ncams, B, tokens, hidden] with out_all).
+        Each camera batch gets its own max()/mean() decision (visual_encoder.py:78,100)."""
+        cams, is_u8, B, res = self._frames("forward", cams, nhwc)
+        shape = (len(cams), B, (res // self.patch) ** 2 + 1, self.hidden) if self.out_all else (len(cams), B, self.hidden)
+        return self._run("vt_dino_forward", cams, is_u8, nhwc, pre_scale, norm_mode, B, res, torch.empty(shape, dtype=torch.float32, device=self.device))
+
+    def embed(self, cams: Sequence[torch.Tensor], *, nhwc: bool, pre_scale: float = 1.0, norm_mode: int = L.IMGNORM_AUTO,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The front end of `forward` alone (vt_dino_embed): [ncams, B, tokens, hidden] fp32 = CLS row + projected patches + position rows, the
+        residual stream as the first block receives it; `last_flags` as after `forward`.  `out`: write into the caller's buffer of that shape."""
+        cams, is_u8, B, res = self._frames("embed", cams, nhwc)
+        shape = (len(cams), B, (res // self.patch) ** 2 + 1, self.hidden)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        if tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != self.device:
+            raise ValueError(f"DinoEngine.embed: out must be a contiguous fp32 {shape} tensor on {self.device}")
+        return self._run("vt_dino_embed", cams, is_u8, nhwc, pre_scale, norm_mode, B, res, out)
 
 
 # =========================================================================================== SigLIP image tokens
@@ -499,20 +537,34 @@ class SiglipEngine(_Engine, RangeGuard):
     def num_patches(self) -> int:
         return self._pos.shape[0]
 
-    def forward(self, pixel_values: torch.Tensor) -> torch.Tensor:
-        """pixel_values [B, 3, res, res] (already rescaled + normalised by the image processor) -> [B, tokens, hidden] fp32."""
+    def _run(self, fn: str, pixel_values: torch.Tensor, out: Optional[torch.Tensor]) -> torch.Tensor:
         x = pixel_values.to(self.device, torch.float32).contiguous()
         B, _, res, res2 = x.shape
         grid = res // self.patch
         if res != res2 or grid * grid != self._pos.shape[0]:
             raise L.VtError(f"SiglipEngine: {res}x{res2} input does not match the {self._pos.shape[0]}-entry position table")
-        out = torch.empty(B, grid * grid, self.hidden, dtype=torch.float32, device=self.device)
+        shape = (B, grid * grid, self.hidden)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        if tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != self.device:
+            raise ValueError(f"SiglipEngine: out must be a contiguous fp32 {shape} tensor on {self.device}")
         flags = torch.empty(1, 4, dtype=torch.float32, device=self.device)
         lib = L.lib()
         ws = self._ws.get(lib.vt_dino_workspace_bytes(self._h, B, res))
-        L.check(lib.vt_dino_forward(self._h, L.ptr_array([x]), 1, 0, 0, C.c_float(1.0), L.IMGNORM_OFF, B, res, L.ptr(self._pos), L.ptr(out),
-                                    L.ptr(flags), L.ptr(ws), L.stream_ptr(self.device)), "vt_dino_forward (siglip)")
+        # IMGNORM_RAW: the processor's output reaches the patch embedding as it is (siglip_encoder.py:33-35 has no max > 1 rule; with ImageNet
+        # statistics the values reach 2.64)
+        L.check(getattr(lib, fn)(self._h, L.ptr_array([x]), 1, 0, 0, C.c_float(1.0), L.IMGNORM_RAW, B, res, L.ptr(self._pos), L.ptr(out),
+                                 L.ptr(flags), L.ptr(ws), L.stream_ptr(self.device)), f"{fn} (siglip)")
+        self.last_flags = flags
         return out
+
+    def forward(self, pixel_values: torch.Tensor) -> torch.Tensor:
+        """pixel_values [B, 3, res, res] (already rescaled + normalised by the image processor) -> [B, tokens, hidden] fp32."""
+        return self._run("vt_dino_forward", pixel_values, None)
+
+    def embed(self, pixel_values: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The front end of `forward` alone (vt_dino_embed): [B, tokens, hidden] fp32 = projected patches + position rows."""
+        return self._run("vt_dino_embed", pixel_values, out)
 
 
 # =========================================================================================== MLP chain
