@@ -1,4 +1,5 @@
-// vt_gemm_epilogue.h — shared epilogue of the LDS-DMA GEMM kernels (vt_gemm_fast.hip, vt_gemm_pp.hip).
+// vt_gemm_epilogue.h — shared epilogue of the LDS-DMA GEMM kernels: vt_gemm_epilogue of vt_gemm_fast.hip, vt_gemm_pp.hip and vt_gemm_ppk.hip; its row
+// segment (vt_epi_segment) also of vt_gemm_pw.hip and vt_gemm_pws.hip, which stage their tile themselves and load that side's parameters as here.
 // A wave owns (TM*16) rows x 64 columns; register layout: acc[i][j][r] = C[mrow0 + j*16 + l15][ncol0 + i*16 + g*4 + r].
 // + bias, optional per-head RMSNorm (q_norm / k_norm of timm Attention: the wave's 64 columns are exactly one head, the row's
 // 64 values live in the 4 lanes sharing lane&15 -> two shuffles), activation, column scale (LayerScale); then the sub-tile

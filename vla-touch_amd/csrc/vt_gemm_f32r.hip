@@ -67,7 +67,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32r_kernel(const VtGemmParams p)
 #pragma unroll
   for (int e = 0; e < 2; ++e) {
     const int r = (wave + 4 * e) * 8 + r_in;                     // tile row 0..63
-    const int c = pch ^ ((r >> 1) & 7);
+    const int c = swz(r, pch);
     const int m = min(m0 + r, p.M - 1);
     if (p.taps == 0) { a_base[e] = A + (long)m * p.lda + c * 4; a_t[e] = 0; }
     else {

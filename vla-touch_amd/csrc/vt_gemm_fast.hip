@@ -9,7 +9,7 @@
 // from the grid size, see vt_gemm_fast_launch): ONE LDS stage with 4 co-resident blocks per CU (latency hidden across
 // blocks; the default whenever the grid fills the 1024 block slots) or TWO stages at 2 blocks/CU (DMA of k-tile t+1 issued
 // before the MFMAs of tile t).  Blocks are dealt to XCDs in contiguous bands of tiles, and inside a band in super-rows of
-// GM m-tiles, so neighbouring tiles share operand panels in that XCD's private L2.
+// GM m-tiles, so neighbouring tiles share operand panels in that XCD's private L2 (vt_tile_of, vt_gemm_tile.h: the family's one tile order).
 // Operands are swapped (D = W_tile A_tile^T) so a lane ends with 4 consecutive n of one row m.
 // Epilogue: vt_gemm_epilogue.h (shared with the ping-pong kernels vt_gemm_pp.hip / vt_gemm_ppk.hip).
 // Dispatch: this file launches gemm_glds_kernel only.  Which large 16-bit GEMMs land here is decided in vt_gemm_route.hip (VT_GEMM_GLDS: what
@@ -17,6 +17,7 @@
 #include "vt_common.h"
 #include "vt_gemm_route.h"
 #include "vt_gemm_epilogue.h"
+#include "vt_gemm_tile.h"
 #include "vt_prof.h"
 
 namespace {
@@ -42,38 +43,22 @@ __global__ __launch_bounds__(2 * BN, MINW * (BN / 128)) void gemm_glds_kernel(co
   const int wm = wave / WN, wn = wave % WN;
   const int g = lane >> 4, l15 = lane & 15;
 
-  int bid = blockIdx.x;
-  if ((total_tiles & 7) == 0) bid = (bid & 7) * (total_tiles >> 3) + (bid >> 3);     // XCD b%8 gets a contiguous band
-  const int grp = bid / tiles_per_group;
-  const int t_in = bid - grp * tiles_per_group;
-  // tile order inside a group: super-rows of GM m-tiles; within a super-row n advances slowly and m fastest, so GM
-  // consecutive blocks share one W tile and the GM A panels stay L2-resident across all n (W is re-read tiles_m/GM times
-  // instead of tiles_m times; PMC FETCH showed 2.5x the algorithmic bytes with the plain n-fastest order).
-  const int tiles_m = tiles_per_group / tiles_n;
-  const int sr = t_in / (GM * tiles_n);
-  const int gm = min(GM, tiles_m - sr * GM);
-  const int r_in = t_in - sr * GM * tiles_n;
-  const int tn = r_in / gm, tm = sr * GM + (r_in - tn * gm);
-  const int m0 = tm * BM, n0 = tn * BN;
+  const VtTile t = vt_tile_of(blockIdx.x, total_tiles, tiles_n, tiles_per_group, GM);
+  const int grp = t.grp, m0 = t.tm * BM, n0 = t.tn * BN;
 
   const uint16_t* A = reinterpret_cast<const uint16_t*>(p.A) + (long)grp * p.a_gs;
   const uint16_t* W = reinterpret_cast<const uint16_t*>(p.W) + (long)grp * p.w_gs;
 
-  // DMA sources: instruction q of this wave fills 8 LDS rows; lane -> (row, chunk position); it fetches the chunk whose
-  // swizzled position is its own.  Rows beyond M / N are clamped (computed, never stored).
+  // DMA sources (vt_dma_src): instruction q of this wave fills 8 LDS rows
   const uint16_t* a_src[QA];
   const uint16_t* b_src[QB];
 #pragma unroll
   for (int q = 0; q < QA; ++q) {
-    const int r = (wave * QA + q) * 8 + (lane >> 3);
-    const int c = (lane & 7) ^ ((r >> 1) & 7);
-    a_src[q] = A + (long)min(m0 + r, p.M - 1) * p.lda + c * 8;
+    a_src[q] = vt_dma_src(A, m0, (wave * QA + q) * 8 + (lane >> 3), p.M, p.lda, lane);
   }
 #pragma unroll
   for (int q = 0; q < QB; ++q) {
-    const int r = (wave * QB + q) * 8 + (lane >> 3);
-    const int c = (lane & 7) ^ ((r >> 1) & 7);
-    b_src[q] = W + (long)min(n0 + r, p.N - 1) * p.ldw + c * 8;
+    b_src[q] = vt_dma_src(W, n0, (wave * QB + q) * 8 + (lane >> 3), p.N, p.ldw, lane);
   }
   auto stage = [&](int buf, int kt) {
     char* base = smem + buf * STAGE_BYTES;
@@ -135,8 +120,7 @@ bool vt_gemm_lds_fits(const VtGemmParams& p) {
   if (p.M < 128) return false;
   if (p.cmap && ((p.a_dtype != VT_BF16 && !(p.a_dtype == VT_F16 && p.cmap == 3)) || p.c_dtype == VT_F32 || p.N % 64 || p.residual || p.groups != 1 || (long)p.cmap_T * 64 < p.M)) return false;
   if (p.cmap == 3 && (p.N % 128)) return false;      // fused K|V: two halves of whole heads
-  const long tiles = (long)((p.M + 127) / 128) * ((p.N + 127) / 128) * p.groups;
-  return tiles >= 96;
+  return vt_tile_count(p, 128, 128) >= 96;
 }
 
 bool vt_gemm_can_fuse_headnorm(const VtGemmParams& p) { return vt_gemm_lds_fits(p) && (p.N % 64) == 0; }
@@ -151,32 +135,27 @@ static void launch_variant(int variant, dim3 grid, hipStream_t s, const VtGemmPa
 }
 
 int vt_gemm_fast_launch(const VtGemmParams& p, hipStream_t s) {
-  const long tiles128 = (long)((p.M + 127) / 128) * ((p.N + 127) / 128) * p.groups;
+  const long tiles128 = vt_tile_count(p, 128, 128);
   // Measured on MI355X (tools/gemm_bench.py).  128-column tiles: one LDS stage with 4 co-resident blocks per CU (1024 block
   // slots) beats in-block double buffering at 2 blocks/CU on every shape of this path (cond-K/V 561 -> 854 TF/s, K=768 DINOv2
   // GEMMs 330 -> 490) except when the grid cannot fill the slots, where the two-stage kernel hides latency inside the block;
   // 128-row tiles when they fill the slots, else 64-row tiles.
   const int bm = tiles128 < 1024 ? 64 : 128;
-  const int bn = 128;
-  const int tiles_n = (p.N + bn - 1) / bn, tiles_m = (p.M + bm - 1) / bm;
-  const int per_group = tiles_n * tiles_m, total = per_group * p.groups;
-  const int variant = total < 768 ? 22 : 14;   // 22 = two stages, 2 blocks/CU; 14 = one stage, 4 blocks/CU
+  const VtTiles t = vt_tiles(p, bm, 128);
+  const int variant = t.total < 768 ? 22 : 14;   // 22 = two stages, 2 blocks/CU; 14 = one stage, 4 blocks/CU
   VtProfScope prof(3, p, s);
-#define VT_FAST_GO(T16, TC, BMv) launch_variant<T16, TC, BMv, 0>(variant, dim3(total), s, p, tiles_n, per_group, total)
+#define VT_FAST_GO(T16, TC, BMv, CM) launch_variant<T16, TC, BMv, CM>(variant, dim3(t.total), s, p, t.n, t.per_group, t.total)
 #define VT_FAST_GO3(T16, TC) \
-  { if (bm == 128) VT_FAST_GO(T16, TC, 128); else VT_FAST_GO(T16, TC, 64); }
+  { if (bm == 128) VT_FAST_GO(T16, TC, 128, 0); else VT_FAST_GO(T16, TC, 64, 0); }
 #define VT_FAST_GO_CMAP(BMv) \
-  { if (p.a_dtype == VT_F16) launch_variant<half_t, half_t, BMv, 3>(variant, dim3(total), s, p, tiles_n, per_group, total);      /* fp16: the fused K|V form only */ \
-    else if (p.cmap == 1) launch_variant<bf16_t, bf16_t, BMv, 1>(variant, dim3(total), s, p, tiles_n, per_group, total); \
-    else if (p.cmap == 2) launch_variant<bf16_t, bf16_t, BMv, 2>(variant, dim3(total), s, p, tiles_n, per_group, total); \
-    else launch_variant<bf16_t, bf16_t, BMv, 3>(variant, dim3(total), s, p, tiles_n, per_group, total); }
-  const bool c16 = p.c_dtype != VT_F32;
+  { if (p.a_dtype == VT_F16) VT_FAST_GO(half_t, half_t, BMv, 3);      /* fp16: the fused K|V form only */ \
+    else if (p.cmap == 1) VT_FAST_GO(bf16_t, bf16_t, BMv, 1); \
+    else if (p.cmap == 2) VT_FAST_GO(bf16_t, bf16_t, BMv, 2); \
+    else VT_FAST_GO(bf16_t, bf16_t, BMv, 3); }
   if (p.cmap) {
     if (bm == 128) VT_FAST_GO_CMAP(128) else VT_FAST_GO_CMAP(64)
-  } else if (p.a_dtype == VT_BF16) {
-    if (c16) VT_FAST_GO3(bf16_t, bf16_t) else VT_FAST_GO3(bf16_t, float)
   } else {
-    if (c16) VT_FAST_GO3(half_t, half_t) else VT_FAST_GO3(half_t, float)
+    VT_DISPATCH_T16_TC(p, T16, TC, VT_FAST_GO3(T16, TC))
   }
 #undef VT_FAST_GO
 #undef VT_FAST_GO3

@@ -15,12 +15,13 @@
 //     s_barrier (a __syncthreads() would drain the DMA queue).  A unit is read one phase after the wait + barrier that retires it
 //     (RAW: the wait is per wave, the barrier makes it block-wide, also across the stagger).
 // LDS: 2 buffers x (A 256 x 128 B + B 256 x 128 B) = 128 KiB, rows XOR-swizzled exactly as in vt_gemm_fast.hip (lane-linear
-// DMA image, swizzle on the source address).  Tile order, XCD banding and the epilogue are shared with that kernel.
+// DMA image, swizzle on the source address: vt_dma_chunk).  Tile order and XCD banding are vt_tile_of's (vt_gemm_tile.h); the epilogue is shared with that kernel.
 // Dispatch: this file launches gemm_pp256d_kernel only.  vt_gemm_route.hip sends it the grids of vt_gemm_pp_fits (below) whose epilogue the persistent
 // form of the tile (vt_gemm_pt.hip) does not have, and all of them with vt_tune(8, 0).
 #include "vt_common.h"
 #include "vt_gemm_route.h"
 #include "vt_gemm_epilogue.h"
+#include "vt_gemm_tile.h"
 #include "vt_prof.h"
 
 namespace {
@@ -36,16 +37,8 @@ __global__ __launch_bounds__(512, 2) void gemm_pp256d_kernel(const VtGemmParams 
   const int wm = wave >> 2, wn = wave & 3;          // group (row half), column quarter
   const int g = lane >> 4, l15 = lane & 15;
 
-  int bid = blockIdx.x;
-  if ((total_tiles & 7) == 0) bid = (bid & 7) * (total_tiles >> 3) + (bid >> 3);     // XCD b%8 gets a contiguous band
-  const int grp = bid / tiles_per_group;
-  const int t_in = bid - grp * tiles_per_group;
-  const int tiles_m = tiles_per_group / tiles_n;
-  const int sr = t_in / (GM * tiles_n);
-  const int gmr = min(GM, tiles_m - sr * GM);
-  const int r_in = t_in - sr * GM * tiles_n;
-  const int tn = r_in / gmr, tm = sr * GM + (r_in - tn * gmr);
-  const int m0 = tm * BM, n0 = tn * BN;
+  const VtTile t = vt_tile_of(blockIdx.x, total_tiles, tiles_n, tiles_per_group, GM);
+  const int grp = t.grp, m0 = t.tm * BM, n0 = t.tn * BN;
 
   const uint16_t* A = reinterpret_cast<const uint16_t*>(p.A) + (long)grp * p.a_gs;
   const uint16_t* W = reinterpret_cast<const uint16_t*>(p.W) + (long)grp * p.w_gs;
@@ -53,7 +46,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp256d_kernel(const VtGemmParams 
   // DMA pieces: a unit is 128 tile rows = 16 pieces of 8 rows; this wave issues pieces 2*wave and 2*wave+1 of every unit.
   //   A units (U0: sel 0, U3: sel 1): rows with (r & 64) == sel*64 -> r = (q>>3)*128 + sel*64 + (q&7)*8 + lane/8
   //   B units (U1: sel 0, U2: sel 1): rows with (r & 32) == sel*32 -> r = (q>>2)*64  + sel*32 + (q&3)*8 + lane/8
-  // lane -> (row, chunk position); it fetches the chunk whose swizzled position is its own.  Rows beyond M / N are clamped.
+  // (spelled out here and in gemm_pt_kernel: behind a shared function hipcc's code for both kernels changes.)  Source of a piece: vt_gemm_tile.h.
   // The pieces are buffer loads (SGPR resource of the tile's A / W row block + one 32-bit VGPR offset per lane + the k offset in
   // an SGPR): the per-piece issue cost of the LDS-DMA is what bounds this kernel, and a 32-bit offset is half the address traffic
   // of a 64-bit flat pointer per lane.
@@ -70,8 +63,8 @@ __global__ __launch_bounds__(512, 2) void gemm_pp256d_kernel(const VtGemmParams 
       const int sel = (u == 2 || u == 3) ? 1 : 0;
       const int r8 = isA ? ((q >> 3) * 128 + sel * 64 + (q & 7) * 8) : ((q >> 2) * 64 + sel * 32 + (q & 3) * 8);
       const int r = r8 + (lane >> 3);
-      const int c = (lane & 7) ^ ((r >> 1) & 7);
-      src[u][e] = isA ? (int)(((long)(min(m0 + r, p.M - 1) - m0) * p.lda + c * 8) * 2) : (int)(((long)(min(n0 + r, p.N - 1) - n0) * p.ldw + c * 8) * 2);
+      const int c = vt_dma_chunk(r, lane);
+      src[u][e] = isA ? vt_dma_off(m0, r, p.M, p.lda, c) : vt_dma_off(n0, r, p.N, p.ldw, c);
       dst[u][e] = (isA ? 0 : BM * 128) + r8 * 128;
     }
   auto stage = [&](int u, int buf, int kt) {
@@ -184,25 +177,22 @@ __global__ __launch_bounds__(512, 2) void gemm_pp256d_kernel(const VtGemmParams 
 // the shapes gemm_pp256d_kernel is good at, inside the LDS-DMA family (vt_gemm_lds_fits); the persistent kernel of vt_gemm_pt.hip takes these and a few
 // more (vt_gemm_pt_one_round) — which of the two runs is vt_gemm_route.hip's decision
 bool vt_gemm_pp_fits(const VtGemmParams& p) {
-  const long tiles256 = (long)((p.M + 255) / 256) * ((p.N + 255) / 256) * p.groups;
-  if (p.lda >= (1 << 21) || p.ldw >= (1 << 21) || p.K >= (1 << 24)) return false;   // 32-bit buffer offsets inside a 256-row block
+  const long tiles256 = vt_tile_count(p, BM, BN);
+  if (!vt_gemm_sq256_offsets_fit(p)) return false;
   if (tiles256 >= 192 && tiles256 <= 256 && p.K >= 1024) return true;   // one well-filled round (RDT qkv: 9 x 24 tiles): 22 % faster than 128-col tiles
   return tiles256 >= 512 && p.K >= 512;            // at least two rounds of 256-square tiles over the 256 CUs
 }
 
 int vt_gemm_pp_launch(const VtGemmParams& p, hipStream_t s) {
-  const int tiles_n = (p.N + BN - 1) / BN, tiles_m = (p.M + BM - 1) / BM;
-  const int per_group = tiles_n * tiles_m, total = per_group * p.groups;
+  const VtTiles t = vt_tiles(p, BM, BN);
   const int gm = 8;
   VtProfScope prof(2, p, s);
-#define VT_PP_GO(T16, TC, CM) hipLaunchKernelGGL((gemm_pp256d_kernel<T16, TC, CM>), dim3(total), dim3(512), 0, s, p, tiles_n, per_group, total, gm)
-  const bool c16 = p.c_dtype != VT_F32;
+#define VT_PP_GO(T16, TC, CM) hipLaunchKernelGGL((gemm_pp256d_kernel<T16, TC, CM>), dim3(t.total), dim3(512), 0, s, p, t.n, t.per_group, t.total, gm)
   if (p.cmap == 3 && p.a_dtype == VT_F16) VT_PP_GO(half_t, half_t, 3);
   else if (p.cmap == 1) VT_PP_GO(bf16_t, bf16_t, 1);
   else if (p.cmap == 2) VT_PP_GO(bf16_t, bf16_t, 2);
   else if (p.cmap == 3) VT_PP_GO(bf16_t, bf16_t, 3);
-  else if (p.a_dtype == VT_BF16) { if (c16) VT_PP_GO(bf16_t, bf16_t, 0); else VT_PP_GO(bf16_t, float, 0); }
-  else { if (c16) VT_PP_GO(half_t, half_t, 0); else VT_PP_GO(half_t, float, 0); }
+  else VT_DISPATCH_T16_TC(p, T16, TC, VT_PP_GO(T16, TC, 0))
 #undef VT_PP_GO
   return vt_check_launch();
 }

@@ -16,6 +16,7 @@
 #include "vt_common.h"
 #include "vt_gemm_route.h"
 #include "vt_gemm_epilogue.h"
+#include "vt_gemm_tile.h"
 #include "vt_prof.h"
 
 namespace {
@@ -36,29 +37,20 @@ __global__ __launch_bounds__(512, 2) void gemm_ppk_kernel(const VtGemmParams p, 
   const int wm = wq >> 1, wn = wq & 1;
   const int g = lane >> 4, l15 = lane & 15;
 
-  int bid = blockIdx.x;
-  if ((total_tiles & 7) == 0) bid = (bid & 7) * (total_tiles >> 3) + (bid >> 3);     // XCD b%8 gets a contiguous band
-  const int grp = bid / tiles_per_group;
-  const int t_in = bid - grp * tiles_per_group;
-  const int tiles_m = tiles_per_group / tiles_n;
-  const int sr = t_in / (GM * tiles_n);
-  const int gmr = min(GM, tiles_m - sr * GM);
-  const int r_in = t_in - sr * GM * tiles_n;
-  const int tn = r_in / gmr, tm = sr * GM + (r_in - tn * gmr);
-  const int m0 = tm * BM, n0 = tn * BN;
+  const VtTile t = vt_tile_of(blockIdx.x, total_tiles, tiles_n, tiles_per_group, GM);
+  const int grp = t.grp, m0 = t.tm * BM, n0 = t.tn * BN;
 
   const uint16_t* A = reinterpret_cast<const uint16_t*>(p.A) + (long)grp * p.a_gs;
   const uint16_t* W = reinterpret_cast<const uint16_t*>(p.W) + (long)grp * p.w_gs;
 
   // DMA pieces of a k-tile: piece q = 8 tile rows (A rows for q < 20, then B rows); wave wq of the group issues q = wq, wq+4, ...
-  // lane -> (row, chunk position); it fetches the chunk whose swizzled position is its own.  Rows beyond M / N are clamped.
+  // (source of a piece: vt_dma_src)
   const uint16_t* src[9];
 #pragma unroll
   for (int e = 0; e < 9; ++e) {
     const int q = wq + 4 * e;
     const int r = (q < BM / 8 ? q * 8 : (q - BM / 8) * 8) + (lane >> 3);
-    const int c = (lane & 7) ^ ((r >> 1) & 7);
-    src[e] = q < BM / 8 ? A + (long)min(m0 + r, p.M - 1) * p.lda + c * 8 : W + (long)min(n0 + r, p.N - 1) * p.ldw + c * 8;
+    src[e] = q < BM / 8 ? vt_dma_src(A, m0, r, p.M, p.lda, lane) : vt_dma_src(W, n0, r, p.N, p.ldw, lane);
   }
   char* gbase = smem + grp_k * 2 * BUF_BYTES;
   auto stage = [&](int buf, int kt) {
@@ -165,19 +157,14 @@ __global__ __launch_bounds__(512, 2) void gemm_ppk_kernel(const VtGemmParams p, 
 
 bool vt_gemm_ppk_fits(const VtGemmParams& p) {      // inside the LDS-DMA family (vt_gemm_lds_fits)
   if (p.cmap) return false;
-  const long tiles = (long)((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN) * p.groups;
+  const long tiles = vt_tile_count(p, BM, BN);
   return tiles >= 100 && tiles <= 256 && p.K >= 512;     // one round of 160 x 128 tiles over the 256 CUs
 }
 
 int vt_gemm_ppk_launch(const VtGemmParams& p, hipStream_t s) {
-  const int tiles_n = (p.N + BN - 1) / BN, tiles_m = (p.M + BM - 1) / BM;
-  const int per_group = tiles_n * tiles_m, total = per_group * p.groups;
+  const VtTiles t = vt_tiles(p, BM, BN);
   const int gm = 4;
   VtProfScope prof(3, p, s);
-#define VT_PPK_GO(T16, TC) hipLaunchKernelGGL((gemm_ppk_kernel<T16, TC>), dim3(total), dim3(512), 0, s, p, tiles_n, per_group, total, gm)
-  const bool c16 = p.c_dtype != VT_F32;
-  if (p.a_dtype == VT_BF16) { if (c16) VT_PPK_GO(bf16_t, bf16_t); else VT_PPK_GO(bf16_t, float); }
-  else { if (c16) VT_PPK_GO(half_t, half_t); else VT_PPK_GO(half_t, float); }
-#undef VT_PPK_GO
+  VT_DISPATCH_T16_TC(p, T16, TC, hipLaunchKernelGGL((gemm_ppk_kernel<T16, TC>), dim3(t.total), dim3(512), 0, s, p, t.n, t.per_group, t.total, gm))
   return vt_check_launch();
 }

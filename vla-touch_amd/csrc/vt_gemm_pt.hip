@@ -34,6 +34,7 @@
 //   P16  bias (+ GELU erf / tanh) -> row-major 16-bit C  (ViT qkv / fc1, adaptor first layers)
 #include "vt_common.h"
 #include "vt_gemm_route.h"
+#include "vt_gemm_tile.h"
 #include "vt_kernels.h"
 #include "vt_prof.h"
 
@@ -144,11 +145,8 @@ __device__ __forceinline__ void pt_body(const VtGemmParams& p, char* smem, const
   int idx = banded ? (bx >> 3) : bx;
   if (idx >= bandn) return;
   auto decode = [&](int id) __attribute__((always_inline)) -> TileId {
-    const int sr = id / (GM * tiles_n);
-    const int gmr = min(GM, tiles_m - sr * GM);
-    const int r_in = id - sr * GM * tiles_n;
-    const int tn = r_in / gmr, tm = sr * GM + (r_in - tn * gmr);
-    return TileId{tm * BM, n_base + tn * BN};
+    const VtTileMN t = vt_tile_mn(id, tiles_m, tiles_n, GM);
+    return TileId{t.tm * BM, n_base + t.tn * BN};
   };
 
   // ---- staging context (of the tile whose units are being issued): buffer resources of its A / W row blocks + per-lane offsets.
@@ -182,8 +180,8 @@ __device__ __forceinline__ void pt_body(const VtGemmParams& p, char* smem, const
         const int sel = (u == 2 || u == 3) ? 1 : 0;
         const int r8 = isA ? ((q >> 3) * 128 + sel * 64 + (q & 7) * 8) : ((q >> 2) * 64 + sel * 32 + (q & 3) * 8);
         const int r = r8 + (ln >> 3);
-        const int c = (ln & 7) ^ ((r >> 1) & 7);
-        src[u][e] = isA ? (int)(((long)(min(t.m0 + r, p.M - 1) - t.m0) * p.lda + c * 8) * 2) : (int)(((long)(min(t.n0 + r, p.N - 1) - t.n0) * p.ldw + c * 8) * 2);
+        const int c = vt_dma_chunk(r, ln);
+        src[u][e] = isA ? vt_dma_off(t.m0, r, p.M, p.lda, c) : vt_dma_off(t.n0, r, p.N, p.ldw, c);
       }
   };
   auto stage = [&](int u, int buf, int kt) __attribute__((always_inline)) {
@@ -574,7 +572,7 @@ int g_pt_cus = 0;
 // epilogue kinds the persistent kernel has (anything else stays on gemm_pp256d_kernel)
 bool vt_gemm_pt_fits(const VtGemmParams& p) {
   if (p.groups != 1 || p.K < 4 * BK || !p.bias || (p.N % 64)) return false;
-  if (p.lda >= (1 << 21) || p.ldw >= (1 << 21) || p.K >= (1 << 24)) return false;   // 32-bit buffer offsets inside a 256-row block
+  if (!vt_gemm_sq256_offsets_fit(p)) return false;
   if (p.c_dtype == VT_F32)          // R32 kind: fp32 C = residual + colscale * (acc + bias)
     return p.residual && p.colscale && p.cmap == 0 && !p.hn_w0 && !p.hn_w1 && p.act == VT_ACT_NONE && (long)p.ldc * 4 * 128 < (1L << 31) && (long)p.ldr * 4 * 128 < (1L << 31);
   if (p.residual || p.colscale) return false;
@@ -589,7 +587,7 @@ bool vt_gemm_pt_fits(const VtGemmParams& p) {
 // tile per block, but the in-register epilogue is not).
 bool vt_gemm_pt_one_round(const VtGemmParams& p) {
   if (p.cmap != 0 || !vt_gemm_pt_fits(p)) return false;
-  const long tiles256 = (long)((p.M + 255) / 256) * ((p.N + 255) / 256);
+  const long tiles256 = vt_tile_count(p, BM, BN, false);
   return tiles256 >= 160 && tiles256 <= 256 && p.K >= 512;
 }
 
@@ -617,16 +615,13 @@ int vt_gemm_pt_launch(const VtGemmParams& p, hipStream_t s) {
   }
   VtProfScope prof(2, p, s);
 #define VT_PT_GO(T16, KIND, ACT) hipLaunchKernelGGL((gemm_pt_kernel<T16, KIND, ACT>), dim3(grid), dim3(512), 0, s, p, tiles_n, tiles_m, total, gm)
-  if (p.cmap == 3) { if (p.a_dtype == VT_BF16) VT_PT_GO(bf16_t, KIND_KV, VT_ACT_NONE); else VT_PT_GO(half_t, KIND_KV, VT_ACT_NONE); }
-  else if (p.c_dtype == VT_F32) { if (p.a_dtype == VT_BF16) VT_PT_GO(bf16_t, KIND_R32, VT_ACT_NONE); else VT_PT_GO(half_t, KIND_R32, VT_ACT_NONE); }
-  else if (p.a_dtype == VT_BF16) {
-    if (p.act == VT_ACT_NONE) VT_PT_GO(bf16_t, KIND_P16, VT_ACT_NONE);
-    else if (p.act == VT_ACT_GELU_ERF) VT_PT_GO(bf16_t, KIND_P16, VT_ACT_GELU_ERF);
-    else VT_PT_GO(bf16_t, KIND_P16, VT_ACT_GELU_TANH);
-  } else {
-    if (p.act == VT_ACT_NONE) VT_PT_GO(half_t, KIND_P16, VT_ACT_NONE);
-    else if (p.act == VT_ACT_GELU_ERF) VT_PT_GO(half_t, KIND_P16, VT_ACT_GELU_ERF);
-    else VT_PT_GO(half_t, KIND_P16, VT_ACT_GELU_TANH);
+  if (p.cmap == 3) { VT_DISPATCH_A16(p, T16, VT_PT_GO(T16, KIND_KV, VT_ACT_NONE)) }
+  else if (p.c_dtype == VT_F32) { VT_DISPATCH_A16(p, T16, VT_PT_GO(T16, KIND_R32, VT_ACT_NONE)) }
+  else {
+    VT_DISPATCH_A16(p, T16,
+      if (p.act == VT_ACT_NONE) VT_PT_GO(T16, KIND_P16, VT_ACT_NONE);
+      else if (p.act == VT_ACT_GELU_ERF) VT_PT_GO(T16, KIND_P16, VT_ACT_GELU_ERF);
+      else VT_PT_GO(T16, KIND_P16, VT_ACT_GELU_TANH))
   }
 #undef VT_PT_GO
   return vt_check_launch();

@@ -11,7 +11,8 @@
 //   * 4 waves, one per SIMD (up to 512 VGPRs: accumulators 80, NB weight buffers x 16, two fragment sets x 20); wave w owns the
 //     160 x 32 sub-tile at columns 32 w: 5 accumulators of v_mfma_f32_32x32x16 (D[n][m] = W-fragment x A-fragment, so a lane ends with
 //     4 consecutive n of one row m);
-//   * A k-tiles (160 rows x 128 B = 20 pieces of 1 KiB, XOR-swizzled on the SOURCE address like every LDS-DMA tile of this library)
+//   * A k-tiles (160 rows x 128 B = 20 pieces of 1 KiB, XOR-swizzled on the SOURCE address like every LDS-DMA tile of this library: vt_gemm_tile.h;
+//     blocks take their tiles in vt_tile_of's order)
 //     go HBM/L2 -> LDS by DMA into a ring of NB slots; tile t + NB - 1 is issued at the top of iteration t (5 DMA pieces + 4 weight
 //     loads per wave, always in this order), the end of iteration t waits — counted, `s_waitcnt vmcnt(9 (NB - 3))` — until tile t + 2
 //     has landed, one raw s_barrier per k-tile makes it block-visible;
@@ -25,6 +26,7 @@
 #include "vt_common.h"
 #include "vt_gemm_route.h"
 #include "vt_gemm_epilogue.h"
+#include "vt_gemm_tile.h"
 #include "vt_prof.h"
 #include "vt_host.h"
 #include "vt_kernels.h"
@@ -46,22 +48,15 @@ __global__ __launch_bounds__(256, 1) void gemm_pw_kernel(const VtGemmParams p, c
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, hk = lane >> 5;
 
-  int bid = blockIdx.x;
-  if ((total_tiles & 7) == 0) bid = (bid & 7) * (total_tiles >> 3) + (bid >> 3);     // XCD b%8 gets a contiguous band
-  const int grp = bid / tiles_per_group;
-  const int t_in = bid - grp * tiles_per_group;
-  const int tiles_m = tiles_per_group / tiles_n;
-  const int sr = t_in / (GM * tiles_n);
-  const int gmr = min(GM, tiles_m - sr * GM);
-  const int r_in = t_in - sr * GM * tiles_n;
-  const int tn = r_in / gmr, tm = sr * GM + (r_in - tn * gmr);
-  const int m0 = tm * BM, n0 = tn * BN;
+  const VtTile t_ = vt_tile_of(blockIdx.x, total_tiles, tiles_n, tiles_per_group, GM);
+  const int grp = t_.grp, tn = t_.tn, m0 = t_.tm * BM, n0 = tn * BN;
 
   const uint16_t* A = reinterpret_cast<const uint16_t*>(p.A) + (long)grp * p.a_gs;
   const int nk = p.K / BK;
 
   // activation DMA: piece q = 8 tile rows; wave w issues q = w, w+4, ..., w+16.  lane -> (row, chunk position); it fetches the
-  // chunk whose swizzled position is its own.  Rows beyond M are clamped (computed, never stored).
+  // chunk whose swizzled position is its own.  Rows beyond M are clamped (computed, never stored).  (vt_dma_chunk / vt_dma_off of
+  // vt_gemm_tile.h spelled out: called here, and in gemm_pws_kernel, they change hipcc's code for the kernel.)
   const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)(A + (long)m0 * p.lda), 0, 0x7fffffff, 0x00020000);
   int asrc[5];
 #pragma unroll
@@ -81,11 +76,7 @@ __global__ __launch_bounds__(256, 1) void gemm_pw_kernel(const VtGemmParams p, c
 #pragma unroll
     for (int e = 0; e < 5; ++e)
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_void*)(smem + b * A_TILE + (wave + 4 * e) * 1024), 16, asrc[e], kt * (BK * 2), 0, 0);
-    const char* sb = wbase + (long)kt * 4096;
-    wload<0, true>(wb[b][0], wvoff, sb);
-    wload<1024, false>(wb[b][1], wvoff, sb);
-    wload<2048, false>(wb[b][2], wvoff, sb);
-    wload<3072, false>(wb[b][3], wvoff, sb);
+    vt_pw_wload4<0>(wb[b], wvoff, wbase + (long)kt * 4096);
   };
 
   // fragment (32 rows x 16 k) of k-step s of the tile in slot b: lane reads row j*32 + l31, chunk s*2 + hk (swizzled by the row)
@@ -356,38 +347,31 @@ void vt_gemm_pw_tune(int ring) { g_vt_pw_nb = ring; }
 bool vt_gemm_pw_fits(const VtGemmParams& p) {       // inside the LDS-DMA family (vt_gemm_lds_fits)
   if (!p.Wp || p.cmap || p.groups != 1) return false;
   if (p.N % BN || p.K % (8 * BK) || p.lda >= (1 << 21)) return false;
-  const long tiles = (long)((p.M + BM - 1) / BM) * (p.N / BN) * p.groups;
+  const long tiles = vt_tile_count(p, BM, BN);
   // one round of the 256 CUs, or several rounds each at least 7/8 full
   const long rounds = (tiles + 255) / 256;
   return tiles >= 100 && tiles * 8 >= rounds * 256 * 7;
 }
 
 int vt_gemm_pw_launch(const VtGemmParams& p, hipStream_t s) {
-  const int tiles_n = p.N / BN, tiles_m = (p.M + BM - 1) / BM;
-  const int per_group = tiles_n * tiles_m, total = per_group * p.groups;
+  const VtTiles t = vt_tiles(p, BM, BN);
   const int gm = 4;
   VtProfScope prof(3, p, s);
   const bool c16 = p.c_dtype != VT_F32;
-#define VT_PW_GO(T16, TC) do { if (g_vt_pw_nb == 8) hipLaunchKernelGGL((gemm_pw_kernel<T16, TC, 8>), dim3(total), dim3(256), 0, s, p, tiles_n, per_group, total, gm); \
-                               else hipLaunchKernelGGL((gemm_pw_kernel<T16, TC, 4>), dim3(total), dim3(256), 0, s, p, tiles_n, per_group, total, gm); } while (0)
+#define VT_PW_GO(T16, TC, NB, FUSE) hipLaunchKernelGGL((gemm_pw_kernel<T16, TC, NB, FUSE>), dim3(t.total), dim3(256), 0, s, p, t.n, t.per_group, t.total, gm)
   if (p.xn_out || p.rs_part) {        // fused RMSNorm hand-off (vt_gemm.h): ring depth 4 only
-    const dim3 g(total), b(256);
     if (p.xn_out && (c16 || !p.residual || p.act != VT_ACT_NONE || p.hn_w0 || p.hn_w1)) return VT_ERR_UNSUPPORTED;
     if (p.xn_out && p.rs_part) return VT_ERR_UNSUPPORTED;
     if (p.xn_out) {
-      if (p.a_dtype == VT_BF16) hipLaunchKernelGGL((gemm_pw_kernel<bf16_t, float, 4, 1>), g, b, 0, s, p, tiles_n, per_group, total, gm);
-      else hipLaunchKernelGGL((gemm_pw_kernel<half_t, float, 4, 1>), g, b, 0, s, p, tiles_n, per_group, total, gm);
+      VT_DISPATCH_A16(p, T16, VT_PW_GO(T16, float, 4, 1))
     } else if (!c16) {
       return VT_ERR_UNSUPPORTED;        // consumers are the 16-bit-output Linears (qkv, cross q, fc1); an fp32-output consumer would need 260 VGPRs (no second block per CU)
-    } else if (p.a_dtype == VT_BF16) {
-      hipLaunchKernelGGL((gemm_pw_kernel<bf16_t, bf16_t, 4, 2>), g, b, 0, s, p, tiles_n, per_group, total, gm);
     } else {
-      hipLaunchKernelGGL((gemm_pw_kernel<half_t, half_t, 4, 2>), g, b, 0, s, p, tiles_n, per_group, total, gm);
+      VT_DISPATCH_A16(p, T16, VT_PW_GO(T16, T16, 4, 2))
     }
     return vt_check_launch();
   }
-  if (p.a_dtype == VT_BF16) { if (c16) VT_PW_GO(bf16_t, bf16_t); else VT_PW_GO(bf16_t, float); }
-  else { if (c16) VT_PW_GO(half_t, half_t); else VT_PW_GO(half_t, float); }
+  VT_DISPATCH_T16_TC(p, T16, TC, if (g_vt_pw_nb == 8) VT_PW_GO(T16, TC, 8, 0); else VT_PW_GO(T16, TC, 4, 0))
 #undef VT_PW_GO
   return vt_check_launch();
 }

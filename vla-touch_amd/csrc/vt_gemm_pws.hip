@@ -17,6 +17,7 @@
 #include "vt_common.h"
 #include "vt_gemm_route.h"
 #include "vt_gemm_epilogue.h"
+#include "vt_gemm_tile.h"
 #include "vt_prof.h"
 #include "vt_host.h"
 #include "../../include/vlatouch.h"
@@ -68,15 +69,8 @@ __global__ __launch_bounds__(256, 1) void gemm_pws_kernel(const VtGemmParams p, 
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_void*)(smem + b * CHUNK + kk * A_TILE + (wave + 4 * e) * 1024), 16, asrc[e],
                                                  (kt0 + c * CH + kk) * (BK * 2), 0, 0);
     const char* sb0 = wbase + (long)(kt0 + c * CH + wp) * 4096;         // this wave's k-tiles of the chunk: wp and wp + 2
-    wload<0, true>(wb[b][0], wvoff, sb0);
-    wload<1024, false>(wb[b][1], wvoff, sb0);
-    wload<2048, false>(wb[b][2], wvoff, sb0);
-    wload<3072, false>(wb[b][3], wvoff, sb0);
-    const char* sb1 = sb0 + 2 * 4096;
-    wload<0, true>(wb[b][4], wvoff, sb1);
-    wload<1024, false>(wb[b][5], wvoff, sb1);
-    wload<2048, false>(wb[b][6], wvoff, sb1);
-    wload<3072, false>(wb[b][7], wvoff, sb1);
+    vt_pw_wload4<0>(wb[b], wvoff, sb0);
+    vt_pw_wload4<4>(wb[b], wvoff, sb0 + 2 * 4096);
   };
 
   const int xr = (l31 >> 1) & 7;
@@ -233,7 +227,7 @@ void vt_gemm_pws_tune(int split) { g_vt_pws_s = split; }
 
 static int pws_split(const VtGemmParams& p) {
   if (p.splitk > 1) return p.splitk;
-  const long tiles = (long)((p.M + BM - 1) / BM) * (p.N / BN);
+  const long tiles = vt_tile_count(p, BM, BN, false);
   int S = 1;
   if (g_vt_pws_s < 0) while (tiles * S < 128 && S < 8 && (p.K / BK) % (2 * S * CH) == 0) S *= 2;      // knob 4 = -1: choose; default: no in-launch combine
   if (g_vt_pws_s > 0 && (p.K / BK) % (g_vt_pws_s * CH) == 0) S = g_vt_pws_s;
@@ -253,12 +247,8 @@ bool vt_gemm_pws_fits(const VtGemmParams& p) {
 
 int vt_gemm_pws_launch(const VtGemmParams& p, hipStream_t s) {
   const int S = pws_split(p);
-  const int tiles_n = p.N / BN, tiles_m = (p.M + BM - 1) / BM;
+  const VtTiles t = vt_tiles(p, BM, BN);             // groups == 1 (vt_gemm_pws_fits)
   VtProfScope prof(3, p, s);
-  const bool c16 = p.c_dtype != VT_F32;
-#define VT_PWS_GO(T16, TC) hipLaunchKernelGGL((gemm_pws_kernel<T16, TC>), dim3(tiles_n * tiles_m * S), dim3(256), 0, s, p, S, tiles_n)
-  if (p.a_dtype == VT_BF16) { if (c16) VT_PWS_GO(bf16_t, bf16_t); else VT_PWS_GO(bf16_t, float); }
-  else { if (c16) VT_PWS_GO(half_t, half_t); else VT_PWS_GO(half_t, float); }
-#undef VT_PWS_GO
+  VT_DISPATCH_T16_TC(p, T16, TC, hipLaunchKernelGGL((gemm_pws_kernel<T16, TC>), dim3(t.total * S), dim3(256), 0, s, p, S, t.n))
   return vt_check_launch();
 }

@@ -47,6 +47,28 @@ int vt_gemm_pt_launch(const VtGemmParams& p, hipStream_t s);     // gemm_pt_kern
 int vt_gemm_ppk_launch(const VtGemmParams& p, hipStream_t s);    // gemm_ppk_kernel
 int vt_gemm_pw_launch(const VtGemmParams& p, hipStream_t s);     // gemm_pw_kernel
 int vt_gemm_pws_launch(const VtGemmParams& p, hipStream_t s);    // gemm_pws_kernel
+
+// What the launchers of the 16-bit tiles share.  Template arguments from the block's types: the statement is compiled once per case with T16 = the
+// operand type (a_dtype: VT_BF16, else IEEE half; the router admits nothing else here) and, in the second form, TC = T16 or float (fp32 C).
+// (bf16_t, half_t and the dtype codes are vt_common.h's, which every launcher includes ahead of this file.)
+#define VT_DISPATCH_A16(p, T16, ...) \
+  if ((p).a_dtype == VT_BF16) { using T16 = bf16_t; __VA_ARGS__; } else { using T16 = half_t; __VA_ARGS__; }
+#define VT_DISPATCH_T16_TC(p, T16, TC, ...) \
+  VT_DISPATCH_A16(p, T16, if ((p).c_dtype != VT_F32) { using TC = T16; __VA_ARGS__; } else { using TC = float; __VA_ARGS__; })
+// BM x BN tiles over the output: of all groups (of one group: groups = false) for the *_fits predicates, and as a launcher passes them to its kernel
+inline long vt_tile_count(const VtGemmParams& p, int BM, int BN, bool groups = true) {
+  return (long)((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN) * (groups ? p.groups : 1);
+}
+struct VtTiles { int n, m, per_group, total; };
+inline VtTiles vt_tiles(const VtGemmParams& p, int BM, int BN) {
+  VtTiles t;
+  t.n = (p.N + BN - 1) / BN; t.m = (p.M + BM - 1) / BM;
+  t.per_group = t.n * t.m; t.total = t.per_group * p.groups;
+  return t;
+}
+// the 256-square tiles (PP, PT) address a 256-row block of A / W through a buffer resource with 32-bit byte offsets
+inline bool vt_gemm_sq256_offsets_fit(const VtGemmParams& p) { return p.lda < (1 << 21) && p.ldw < (1 << 21) && p.K < (1 << 24); }
+
 // launch details, not routing
 void vt_gemm_pw_tune(int ring);                            // vt_tune(1, .): ring depth 4 | 8, 0 = default
 void vt_gemm_pws_tune(int split);                          // vt_tune(4, .): split factor (0 = none, -1 = choose)
