@@ -665,8 +665,14 @@ class LstmEngine(_Engine):
         fpad, inpad = _pad_to(force_dim), _pad_to(H // 2 + state_dim)
         if H not in (128, 256, 384):
             raise L.VtError("LstmEngine: hidden_dim must be 128, 256 or 384 (each of the persistent kernel's 8 waves owns hidden/8 = whole 16-unit tiles)")
-        if state_dim > 16:
-            raise L.VtError("LstmEngine: state_dim <= 16")
+        if not 1 <= state_dim <= 16:
+            raise L.VtError(f"LstmEngine: state_dim must be 1..16 (one 16-row output tile), got {state_dim}")
+        if not 1 <= force_dim <= 32:
+            raise L.VtError(f"LstmEngine: force_dim must be 1..32 (the raw force is one 32-column k-step), got {force_dim}")
+        if not 1 <= layers <= 4:
+            raise L.VtError(f"LstmEngine: layers must be 1..4 (the persistent kernel is instantiated for 1 to 4 LSTM layers), got {layers}")
+        if H == 384 and layers == 4:
+            raise L.VtError("LstmEngine: hidden_dim 384 with 4 layers does not fit the CU's LDS (at most 3 layers at 384)")
         g = lambda m, k: mods[m][k].detach().float().cpu()
 
         def pack(w: torch.Tensor, row_starts, kpad: int) -> torch.Tensor:
