@@ -726,6 +726,37 @@ typedef struct {
 int vt_corrupt(const vt_corrupt_frame* frames_host, const void* frames_dev, int n, const unsigned* tables_host, const void* tables_dev,
                long table_words, void* out, vt_stream_t stream);
 
+/* ---- the reference's zero pad and area resize of camera frames (scripts/utils_eef.py:5-77, pad_and_resize_for_siglip: the frame centred
+ * on a zero square of side m = max(h, w), rows from (m - h) / 2 and columns from (m - w) / 2, both floored, then cv2.resize to
+ * (target, target) with INTER_AREA), restated from OpenCV 4.x modules/imgproc/src/resize.cpp (UNPINNED against cv2).
+ * uint8 HWC in (pitched), uint8 HWC out, frame i tight (pitch 3 * target) at out + out_off; source and output must not overlap.
+ * In fp64, inv = (double)target / m, scale = 1.0 / inv, iscale = (int)scale:
+ *   scale < 1 (a frame smaller than the target): cv2's fixed-point bilinear emulation, not built, refused;
+ *   |scale - iscale| < DBL_EPSILON (resizeAreaFast_): ntaps = 0.  s = the integer sum of the iscale x iscale cell; iscale 1 copies, iscale
+ *     2 gives (s + 2) >> 2, any other (float)s * (1.0f / (iscale * iscale)) rounded to nearest-even and clamped to 0..255;
+ *   otherwise (resizeArea_<uchar, float>): ntaps >= 1 and the axis table at tabs + tab_x (columns) and tabs + tab_y (rows), device memory
+ *     the host filled: [ntaps][target] pairs {int32 source index, fp32 weight} as computeResizeAreaTab lists them per output, the shorter
+ *     lists padded with zero weights.  Per vertical tap (sy, beta) in order: buf = 0, then buf += (float)S[sy][sx] * alpha over the
+ *     horizontal taps in order; sum = beta * buf for the first vertical tap, sum += beta * buf for the others; the output is sum rounded
+ *     to nearest-even and clamped.  Every product and every sum is rounded to fp32 on its own (no fused multiply-add).
+ * One launch over all frames, one output pixel per lane; the padded square is not made: a source position is clamped into the m x m
+ * canvas and reads 0 in the border, so no table content can make a lane read outside its frame.  A pure function of the inputs.  No host
+ * read, allocation or synchronisation.  n < 1, a null source, h < 1, w < 1, a side above 32768, pitch < 3 * w, target < 1, a frame
+ * smaller than the target, ntaps that does not fit the form (0 for an integer scale, 1 .. iscale + 3 otherwise), an integer scale above
+ * VT_AREA_MAX_ISCALE and a table offset that is negative, not a multiple of 8 or beyond tabs_bytes return VT_ERR_ARG without a launch. */
+typedef struct {
+  const void* src;      /* uint8 HWC, device */
+  long pitch;           /* bytes between rows of src, >= 3 * w */
+  int h, w;             /* frame size */
+  long out_off;         /* byte offset of this frame's target x target output in `out` */
+  int target;           /* output side */
+  int ntaps;            /* taps per output of the axis tables; 0: the integer-scale form */
+  long tab_x, tab_y;    /* byte offsets of the column and row tables in `tabs` (unused with ntaps = 0) */
+} vt_area_frame;
+#define VT_AREA_MAX_ISCALE 2048     /* 2048 * 2048 * 255 < 2^31 */
+int vt_area_resize(const vt_area_frame* frames_host, const void* frames_dev, int n, void* out, const void* tabs, size_t tabs_bytes,
+                   vt_stream_t stream);
+
 /* ---- one fine-tuning micro-batch out of device-resident episodes (vlatouch/rdt_data.py).  Stands for, per sample,
  * UnifiedVLADataset.parse_file (data/unified_vla_dataset_episode.py:314-351: state row, action chunk from action_id = step_id + 2 padded
  * with its last row, the episode's std / norm, fill_in_state), VLAConsumerDataset.__getitem__ (train/dataset.py:327-344: control frequency,

@@ -23,6 +23,7 @@ import torch
 
 from models.multimodal_encoder.siglip_encoder import SiglipVisionTower
 from models.rdt_runner import RDTRunner
+from vlatouch.imgprep import area_size, pad_and_resize_pil
 from vlatouch.jpegmap import jpeg_mapped_pil, jpeg_quality
 
 # eef_pos_x, eef_pos_y, eef_pos_z, eef_angle_0..5, right_gripper_open in upstream RDT's configs/state_vec.py [assumed-upstream]
@@ -177,14 +178,16 @@ class RoboticDiffusionTransformerModel(object):
             out.append(self.image_processor.preprocess(image, return_tensors="pt")["pixel_values"][0])
         return torch.stack(out, dim=0)
 
-    def preprocess_images_device(self, images, out=None, jitter=None, jpeg=None, corrupt=None):
+    def preprocess_images_device(self, images, out=None, jitter=None, jpeg=None, corrupt=None, area=None):
         """`preprocess_images(images).to(self.device, self.dtype)`, bit for bit, computed on the card (csrc/vt_imgprep.hip): frames go up
         as raw bytes in one copy; device-resident uint8 [H, W, 3] tensors are used in place.  Per frame: PIL image, HxWx3 uint8 array,
         uint8 tensor (host or device) or None.  `jitter`: per frame None or a vlatouch.imgaug.ColorJitterParams, the training-time
         colour augmentation between the pre-resize / lift and the pad (train/dataset.py:385-391); not part of `preprocess_images`.
         `jpeg`: None or the quality of the reference's cv2 JPEG round trip of every frame that exists (vlatouch.jpegmap), ahead of all
         else; equals `preprocess_images_device([jpeg_mapping(f, jpeg) ...])`.  `corrupt`: per frame None or a vlatouch.imgaug.CorruptParams,
-        the training-time corruption directly behind the jitter (train/dataset.py:392-393)."""
+        the training-time corruption directly behind the jitter (train/dataset.py:392-393).  `area`: None or the target size of the
+        reference's `pad_and_resize_for_siglip` of every frame that exists (vlatouch.imgprep), ahead of the JPEG mapping; equals
+        `preprocess_images_device([pad_and_resize_for_siglip(f, area) ...], jpeg=jpeg)`."""
         from vlatouch.imgprep import DevicePreprocessor
         p, d = self.image_processor, self.args["dataset"]
         size = p.size["height"]
@@ -198,20 +201,23 @@ class RoboticDiffusionTransformerModel(object):
             pp = DevicePreprocessor(size, p.image_mean, p.image_std, self.device, self.dtype, pad=key[6], brightness=key[7], image_size=sz,
                                     rescale_factor=p.rescale_factor)
             self._imgprep = {key: pp}
-        return pp(list(images), out=out, jitter=jitter, jpeg=jpeg, corrupt=corrupt)
+        return pp(list(images), out=out, jitter=jitter, jpeg=jpeg, corrupt=corrupt, area=area)
 
     @torch.no_grad()
-    def step(self, proprio, images, text_embeds, jpeg_mapping=False):
+    def step(self, proprio, images, text_embeds, jpeg_mapping=False, pad_and_resize=False):
         """proprio [1, 10]; images: [ext_{t-1}, right_wrist_{t-1}, left_wrist_{t-1}, ext_t, right_wrist_t, left_wrist_t] (PIL or
         None); text_embeds [1, L, lang_token_dim].  Returns the action chunk [1, horizon, 10] fp32 (gripper back in 0..255).
         `jpeg_mapping`: pass every frame through the JPEG round trip the reference's robot loop applies before it calls step
-        (frank_inference_eef.py:84-87; vlatouch.jpegmap): False, True (quality 95, cv2's default) or a quality."""
+        (frank_inference_eef.py:84-87; vlatouch.jpegmap): False, True (quality 95, cv2's default) or a quality.
+        `pad_and_resize`: give step the raw camera frames and let it apply `pad_and_resize_for_siglip` first, as the robot loop does ahead
+        of the mapping (frank_inference_eef.py:324-325; vlatouch.imgprep): False, True (the tower's size) or a target size."""
         device, dtype = self.device, self.dtype
         quality = jpeg_quality(jpeg_mapping)
+        target = area_size(pad_and_resize, self.image_processor.size["height"])
         if self.device_preprocess:
-            image_tensor = self.preprocess_images_device(images, jpeg=quality)
+            image_tensor = self.preprocess_images_device(images, jpeg=quality, area=target)
         else:
-            image_tensor = self.preprocess_images(jpeg_mapped_pil(images, quality)).to(device, dtype=dtype)
+            image_tensor = self.preprocess_images(jpeg_mapped_pil(pad_and_resize_pil(images, target), quality)).to(device, dtype=dtype)
         image_embeds = self.vision_model(image_tensor).detach()
         image_embeds = image_embeds.reshape(-1, self.vision_model.hidden_size).unsqueeze(0)
         joints = proprio.to(device).unsqueeze(0)

@@ -162,6 +162,11 @@ class ColorJitterFrame(C.Structure):     # vt_colorjitter_frame (operation ids: 
 COLORJITTER_LIFT = 1
 
 
+class AreaFrame(C.Structure):     # vt_area_frame
+    _fields_ = [("src", C.c_void_p), ("pitch", C.c_long), ("h", C.c_int), ("w", C.c_int), ("out_off", C.c_long), ("target", C.c_int),
+                ("ntaps", C.c_int), ("tab_x", C.c_long), ("tab_y", C.c_long)]
+
+
 class JpegmapFrame(C.Structure):     # vt_jpegmap_frame
     _fields_ = [("src", C.c_void_p), ("pitch", C.c_long), ("h", C.c_int), ("w", C.c_int), ("out_off", C.c_long), ("ws_off", C.c_long)]
 
@@ -335,6 +340,7 @@ SIGNATURES = {
     "vt_jpegmap_workspace_bytes": (_Z, [_P, _I]),
     "vt_jpegmap": (_I, [_P, _P, _I, _I, _I, _P, _P, _Z, _P]),
     "vt_corrupt": (_I, [_P, _P, _I, _P, _P, C.c_long, _P, _P]),
+    "vt_area_resize": (_I, [_P, _P, _I, _P, _P, _Z, _P]),
     "vt_rdt_batch": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, C.c_double, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vt_ctrl_batch": (_I, [_P, _P, _P, _P, _P, _P, _I, C.c_longlong, _I, _I, _I, C.c_longlong, _P, _F, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P,
                            _P, _P]),

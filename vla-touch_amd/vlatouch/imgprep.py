@@ -10,7 +10,7 @@ Host side of the feature:
   * `FrameStager`: frames of any accepted kind -> one pinned staging buffer -> one host-to-device copy of raw bytes; device-resident
     frames (pitched views included) are used in place.  `DevicePreprocessor` owns one, `jpeg_mapping_device` one per device.
   * `DevicePreprocessor`: the stager's frames -> a list of stages, each one driver call (`_JpegStage`, `_ResampleStage` for the pre-resize
-    and for the main pass, `_JitterStage`, `_CorruptStage`), planned in one loop that carves the workspace and launched in one loop.
+    and for the main pass, `_JitterStage`, `_CorruptStage`, `_AreaStage`), planned in one loop that carves the workspace and launched in one loop.
     With frames of an already-seen geometry at already-seen addresses the call allocates nothing (given `out=`), copies nothing and
     never synchronises, so it can be captured in a graph together with the tower.
   * `jitter=`: the training-time ColorJitter (vlatouch/imgaug.py, csrc/vt_colorjitter.hip) between the `image_size` pre-resize and the
@@ -19,6 +19,20 @@ Host side of the feature:
     jitter, as the reference orders it: Resize -> lift -> jitter -> corruption -> pad -> resize -> normalise.
   * `jpeg=`: the reference's cv2 JPEG round trip of the raw frames (vlatouch/jpegmap.py, csrc/vt_jpegmap.hip) ahead of all of the above,
     where the robot loop and the labeller apply it: JPEG -> Resize -> lift -> jitter -> pad -> resize -> normalise.
+  * `area=`: the reference's `pad_and_resize_for_siglip` (below; csrc/vt_area.hip) ahead of the JPEG mapping, where every consumer of the
+    reference applies it to the raw camera frame: area -> JPEG -> Resize -> lift -> jitter -> pad -> resize -> normalise.
+
+`pad_and_resize_for_siglip(images, target_size)` is the CPU statement of that first stage (scripts/utils_eef.py:5-77: a zero pad to a centred
+square, then `cv2.resize(..., interpolation=cv2.INTER_AREA)`), in numpy; `pad_and_resize_device` gives the same bytes from the kernel.
+UNPINNED against cv2, which is not available where this was written.  It is restated from OpenCV 4.x modules/imgproc/src/resize.cpp, and
+these parts rest on reading that source alone: that `resize` takes INTER_AREA with scale >= 1 to `resizeAreaFast_` when the fp64 scale is
+within DBL_EPSILON of an integer and to `resizeArea_<uchar, float>` with `computeResizeAreaTab` otherwise; the fast form's `(s + 2) >> 2`
+for a factor of 2 and `saturate_cast<uchar>(s * (1.f / area))` for the others; the table's 1e-3 thresholds and `cellWidth`; the loop order of
+the fractional form (buf over the horizontal taps per source row, sum over the rows) in fp32 without fused multiply-adds; and that
+`saturate_cast<uchar>(float)` rounds to nearest-even.  A build of cv2 that dispatches the call to another back end (IPP, OpenCL, a HAL) may
+differ.  What is checked here is independent of cv2: known answers of the cell sums, and the exact fp64 box integral of the padded canvas.
+A frame smaller than the target (scale < 1) takes cv2 to its fixed-point bilinear emulation, which is not built: the statement and the
+device refuse it.
 
 All launches go to the current stream; the staging buffers are reused from call to call on the assumption that calls are issued in
 stream order (the pinned buffer itself is guarded by an event).
@@ -99,6 +113,156 @@ def norm_table(image_mean, image_std, dtype: torch.dtype = torch.float32, rescal
     x = np.asarray(x, dtype=np.float32) * np.float32(rescale_factor)
     x = (x - np.asarray(image_mean, dtype=np.float32)) / np.asarray(image_std, dtype=np.float32)
     return torch.from_numpy(np.ascontiguousarray(x.T)).to(dtype)
+
+
+# ---- the zero pad and area resize of the raw frames
+DBL_EPSILON = float(np.finfo(np.float64).eps)
+AREA_MAX_ISCALE = 2048      # VT_AREA_MAX_ISCALE: the cell sum of the integer form is an int
+
+
+def area_scale(m: int, target: int) -> Tuple[float, int, bool]:
+    """cv2.resize's (scale, iscale, fast) of an axis m -> target, in fp64 as it computes them; refuses what is not built."""
+    if int(target) != target or target < 1 or m < 1:
+        raise ValueError(f"pad_and_resize_for_siglip: sizes must be positive integers, got {m} -> {target!r}")
+    inv = float(np.float64(target) / np.float64(m))
+    scale = 1.0 / inv
+    iscale = int(scale)
+    if scale < 1.0:
+        raise ValueError(f"pad_and_resize_for_siglip: a frame of side {m} is smaller than the target {target}: cv2's bilinear up-scale "
+                         "emulation is not built")
+    fast = abs(scale - iscale) < DBL_EPSILON
+    if fast and iscale > AREA_MAX_ISCALE:
+        raise ValueError(f"pad_and_resize_for_siglip: a reduction by {iscale} (at most {AREA_MAX_ISCALE})")
+    return scale, iscale, fast
+
+
+_area_cache: dict = {}
+
+
+def area_taps(m: int, target: int) -> Tuple[np.ndarray, np.ndarray]:
+    """computeResizeAreaTab of an axis m -> target (fractional scale >= 1): (source index [K, target] int32, weight [K, target] float32),
+    per output its taps in the table's order, the shorter lists padded to the longest K with (0, 0.0).  Cached per (m, target)."""
+    key = (int(m), int(target))
+    hit = _area_cache.get(key)
+    if hit is not None:
+        return hit
+    m, target = key
+    scale, _, fast = area_scale(m, target)
+    if fast:
+        raise ValueError(f"area_taps: {m} -> {target} is an integer scale and has no tap table")
+    taps = []
+    for dx in range(target):
+        fsx1 = dx * scale
+        fsx2 = fsx1 + scale
+        cell = min(scale, m - fsx1)
+        sx1, sx2 = math.ceil(fsx1), min(math.floor(fsx2), m - 1)
+        sx1 = min(sx1, sx2)
+        t = []
+        if sx1 - fsx1 > 1e-3:
+            t.append((sx1 - 1, np.float32((sx1 - fsx1) / cell)))
+        for sx in range(sx1, sx2):
+            t.append((sx, np.float32(1.0 / cell)))
+        if fsx2 - sx2 > 1e-3:
+            t.append((sx2, np.float32(min(min(fsx2 - sx2, 1.0), cell) / cell)))
+        taps.append(t)
+    K = max(1, max(len(t) for t in taps))
+    idx, wgt = np.zeros((K, target), dtype=np.int32), np.zeros((K, target), dtype=np.float32)
+    for dx, t in enumerate(taps):
+        for k, (si, a) in enumerate(t):
+            idx[k, dx], wgt[k, dx] = si, a
+    _area_cache[key] = (idx, wgt)
+    return idx, wgt
+
+
+def _area_one(img: np.ndarray, target: int) -> np.ndarray:
+    H, W = img.shape[:2]
+    m = max(H, W)
+    _, k, fast = area_scale(m, target)
+    canvas = np.zeros((m, m, 3), dtype=np.uint8)
+    top, left = (m - H) // 2, (m - W) // 2
+    canvas[top:top + H, left:left + W] = img
+    if fast:
+        if k == 1:
+            return canvas
+        s = canvas.reshape(target, k, target, k, 3).sum(axis=(1, 3), dtype=np.int64)
+        if k == 2:
+            return ((s + 2) >> 2).astype(np.uint8)
+        v = s.astype(np.float32) * (np.float32(1.0) / np.float32(k * k))
+        return np.clip(np.rint(v), 0, 255).astype(np.uint8)
+    idx, wgt = area_taps(m, target)
+    S = canvas.astype(np.float32)
+    buf = np.zeros((m, target, 3), dtype=np.float32)               # every source row's horizontal pass; fp32 products and sums, each rounded
+    for k in range(idx.shape[0]):
+        buf = buf + S[:, idx[k], :] * wgt[k][None, :, None]
+    total = wgt[0][:, None, None] * buf[idx[0]]
+    for k in range(1, idx.shape[0]):
+        total = total + wgt[k][:, None, None] * buf[idx[k]]
+    return np.clip(np.rint(total), 0, 255).astype(np.uint8)
+
+
+def pad_and_resize_for_siglip(images, target_size: int = 384) -> np.ndarray:
+    """The reference's `pad_and_resize_for_siglip` / `pad_and_resize_for_siglip_batch` (scripts/utils_eef.py:5-77): one uint8 [H, W, 3] frame
+    or a batch [n, H, W, 3] -> uint8 [.., target, target, 3]: the frame on a centred square of zeros, rows from (m - H) // 2 and columns from
+    (m - W) // 2 with m = max(H, W), then cv2's INTER_AREA resize as the module docstring states it (UNPINNED against cv2)."""
+    a = np.asarray(images)
+    if a.dtype != np.uint8 or a.ndim not in (3, 4) or a.shape[-1] != 3 or min(a.shape) < 1:
+        raise ValueError(f"pad_and_resize_for_siglip: frames must be uint8 [H, W, 3] or [n, H, W, 3], got {a.dtype} {a.shape}")
+    target = int(target_size)
+    area_scale(max(a.shape[-3], a.shape[-2]), target_size)
+    if a.ndim == 3:
+        return _area_one(a, target)
+    return np.stack([_area_one(f, target) for f in a], axis=0)
+
+
+def area_size(flag, tower_size: int) -> Optional[int]:
+    """The `pad_and_resize=` argument of the callers (step, encode_frames, label_episode) -> None or a target: False / None is off, True is
+    the tower's size, an integer is that size."""
+    if flag is None or flag is False:
+        return None
+    if flag is True:
+        return int(tower_size)
+    if int(flag) != flag or flag < 1:
+        raise ValueError(f"pad_and_resize must be False, True or a positive target size, got {flag!r}")
+    return int(flag)
+
+
+def pad_and_resize_pil(images: Sequence, target: Optional[int]) -> list:
+    """The CPU route of the callers: every frame that exists -> a PIL image of `pad_and_resize_for_siglip(frame, target)`; all as given
+    when `target` is None."""
+    from PIL import Image
+    if target is None:
+        return list(images)
+    rgb = lambda im: np.asarray(im if not isinstance(im, Image.Image) or im.mode == "RGB" else im.convert("RGB"))
+    return [None if im is None else Image.fromarray(pad_and_resize_for_siglip(rgb(im), target)) for im in images]
+
+
+def area_table(items, target: int, align: int = 1):
+    """[(ptr, h, w, pitch), ...] -> (the `vt_area_frame` table with out_off, ntaps and the table offsets set, output bytes, the tap tables'
+    bytes as one uint8 array): the table builder of the area stage, for `pad_and_resize_device` below and for the preprocessor's stage list
+    alike.  Frame k is written at k * stride, stride = 3 * target^2 rounded up to `align`; frames of one canvas side share one table, which
+    serves both axes."""
+    arr = (_lib.AreaFrame * len(items))()
+    tabs, offs = [], {}
+    stride = (3 * target * target + align - 1) // align * align
+    for k, (ptr, h, w, pitch) in enumerate(items):
+        m = max(h, w)
+        try:
+            _, _, fast = area_scale(m, target)
+        except ValueError as e:
+            raise _lib.VtError(f"frame {k} of {h} x {w}: {e}") from None
+        f = arr[k]
+        f.src, f.h, f.w, f.pitch, f.out_off, f.target = ptr, h, w, pitch, k * stride, target
+        if fast:
+            continue
+        if m not in offs:
+            idx, wgt = area_taps(m, target)
+            rec = np.empty(idx.shape, dtype=[("si", np.int32), ("alpha", np.float32)])
+            rec["si"], rec["alpha"] = idx, wgt
+            offs[m] = (sum(t.size for t in tabs), idx.shape[0])
+            tabs.append(rec.view(np.uint8).reshape(-1))
+        f.tab_x = f.tab_y = offs[m][0]
+        f.ntaps = offs[m][1]
+    return arr, len(items) * stride, (np.concatenate(tabs) if tabs else np.zeros(0, dtype=np.uint8))
 
 
 def _align(v: int, a: int) -> int:
@@ -184,6 +348,30 @@ class FrameStager:
 class _Stage:
     def bind(self, stager: FrameStager) -> None:
         self.dev = stager.to_device(self.table)
+
+
+class _AreaStage(_Stage):
+    """The zero pad and area resize of the raw frames `idx` (those that exist; a missing frame stays the fill image) to `target`.  The
+    records and, 16 bytes aligned behind them, the tap tables go up once with the plan: the call stays as capturable as the plain one."""
+
+    def __init__(self, idx, target: int):
+        self.idx, self.target = idx, target
+
+    def plan(self, items):
+        self.table, out_bytes, self.taps = area_table([items[i] for i in self.idx], self.target, 16)
+        self.rec_bytes = _align(C.sizeof(self.table), 16)
+        return out_bytes, 0, [(i, f.out_off, self.target, self.target) for i, f in zip(self.idx, self.table)]
+
+    def bind(self, stager: FrameStager) -> None:
+        host = np.zeros(self.rec_bytes + self.taps.size, dtype=np.uint8)
+        host[:C.sizeof(self.table)] = np.frombuffer(self.table, dtype=np.uint8)
+        host[self.rec_bytes:] = self.taps
+        self.dev = torch.from_numpy(host).to(stager.device)
+
+    def launch(self, wp, st, out, jitter, quality, corrupt):
+        _lib.check(_lib.lib().vt_area_resize(self.table, _lib.ptr(self.dev), len(self.idx), C.c_void_p(wp + self.out_off),
+                                             C.c_void_p(self.dev.data_ptr() + self.rec_bytes) if self.taps.size else None, self.taps.size, st),
+                   "vt_area_resize")
 
 
 class _JpegStage(_Stage):
@@ -372,10 +560,13 @@ class DevicePreprocessor:
         return int(sz[0]), int(sz[1])
 
     # ---- planning: everything that depends only on geometry and addresses
-    def _stages(self, jit: bool, jpeg_idx: Optional[tuple], cor: bool = False) -> list:
-        """The chain of one call, as the reference orders it: JPEG -> Resize -> (lift and) jitter -> corruption -> pad, resize, normalise.
-        The lift precedes the corruption: with `brightness`, a corrupting call runs the jitter stage even where no frame is jittered."""
+    def _stages(self, jit: bool, jpeg_idx: Optional[tuple], cor: bool = False, area: Optional[tuple] = None) -> list:
+        """The chain of one call, as the reference orders it: area -> JPEG -> Resize -> (lift and) jitter -> corruption -> pad, resize,
+        normalise.  The lift precedes the corruption: with `brightness`, a corrupting call runs the jitter stage even where no frame is
+        jittered.  `area`: None or (target, the indices of the frames that exist)."""
         stages = []
+        if area and area[1]:
+            stages.append(_AreaStage(area[1], area[0]))
         if jpeg_idx:
             stages.append(_JpegStage(jpeg_idx))
         if self.image_size is not None:
@@ -389,15 +580,16 @@ class DevicePreprocessor:
         stages.append(_ResampleStage(self, flags, final=True))
         return stages
 
-    def _plan(self, items, ws_ptr: Optional[int], jit: bool = False, jpeg_idx: Optional[tuple] = None, cor: bool = False):
-        key = (tuple(items), ws_ptr, self.force_two_pass, jit, jpeg_idx, cor)
+    def _plan(self, items, ws_ptr: Optional[int], jit: bool = False, jpeg_idx: Optional[tuple] = None, cor: bool = False,
+              area: Optional[tuple] = None):
+        key = (tuple(items), ws_ptr, self.force_two_pass, jit, jpeg_idx, cor, area)
         plan = self._plans.get(key)
         if plan is not None:
             return plan
         if len(self._plans) >= 64:                        # plans a captured graph reads (their device tables) are never dropped
             self._plans = {k: v for k, v in self._plans.items() if v.get("captured")}
         base = ws_ptr if ws_ptr is not None else _SIZING_BASE
-        stages, off = self._stages(jit, jpeg_idx, cor), 0
+        stages, off = self._stages(jit, jpeg_idx, cor, area), 0
         for st in stages:                                 # the workspace, carved: per stage its output, then its scratch, each 256-byte aligned
             out_bytes, st.ws_bytes, outputs = st.plan(items)
             st.out_off, st.ws_off = off, off + _align(out_bytes, 256)
@@ -436,16 +628,26 @@ class DevicePreprocessor:
             raise _lib.VtError(f"jpeg must be None or a quality in 1..100, got {jpeg!r}")
         return int(jpeg), tuple(i for i, im in enumerate(images) if im is not None)
 
-    def workspace_bytes(self, images: Sequence, jitter=None, jpeg=None, corrupt=None) -> int:
-        """Bytes of workspace a call on these frames needs (geometry only, plus whether any frame is jittered, JPEG-mapped or corrupted)."""
+    @staticmethod
+    def _area_idx(images: Sequence, area):
+        """`area` checked -> (target, the indices of the frames that exist) or None."""
+        if area is None:
+            return None
+        if isinstance(area, bool) or not isinstance(area, (int, np.integer)) or int(area) < 1:
+            raise _lib.VtError(f"area must be None or a positive target size, got {area!r}")
+        return int(area), tuple(i for i, im in enumerate(images) if im is not None)
+
+    def workspace_bytes(self, images: Sequence, jitter=None, jpeg=None, corrupt=None, area=None) -> int:
+        """Bytes of workspace a call on these frames needs (geometry only, plus whether any frame is jittered, JPEG-mapped, corrupted or
+        area-resized)."""
         jit = self._jitter_list(images, jitter) is not None
         cor = corrupt_list(images, corrupt, _lib.VtError) is not None
         items, _ = self.stager.gather(images, self._missing)
-        return self._plan(items, None, jit, self._jpeg_idx(images, jpeg)[1], cor)["ws_bytes"]
+        return self._plan(items, None, jit, self._jpeg_idx(images, jpeg)[1], cor, self._area_idx(images, area))["ws_bytes"]
 
     @torch.no_grad()
     def __call__(self, images: Sequence, out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None, jitter=None,
-                 jpeg=None, corrupt=None) -> torch.Tensor:
+                 jpeg=None, corrupt=None, area=None) -> torch.Tensor:
         """-> pixel_values [n, 3, S, S].  `jitter`: None, or one entry per frame, each None or a `ColorJitterParams` (never on a missing
         frame).  Without it, or with every entry None, the call is the unjittered one: same launches, same bits, capturable in a graph.
         A call that jitters writes its parameters into a device table through a pinned buffer and waits for the previous such copy, so
@@ -454,7 +656,10 @@ class DevicePreprocessor:
         that exists before anything else.  Its table is cached with the plan: the call stays as capturable as the plain one.
         `corrupt`: None, or one entry per frame, each None or a `CorruptParams` (never on a missing frame): the training-time corruption
         (vlatouch/imgaug.py), directly behind the jitter.  Without it, or with every entry None, the call is the one without it.  Like
-        a jittering call it uploads this call's tables through a pinned buffer, so it is not capturable in a graph."""
+        a jittering call it uploads this call's tables through a pinned buffer, so it is not capturable in a graph.
+        `area`: None, or the target size of the reference's `pad_and_resize_for_siglip` (zero pad to a square, cv2's INTER_AREA resize),
+        applied to every frame that exists before anything else, the JPEG mapping included; a missing frame stays the fill image.  Its
+        records and tap tables are cached with the plan: the call stays as capturable as the plain one."""
         n = len(images)
         if n < 1:
             raise _lib.VtError("DevicePreprocessor: no frames")
@@ -464,6 +669,7 @@ class DevicePreprocessor:
         quality, jpeg_idx = self._jpeg_idx(images, jpeg)
         corrupt = corrupt_list(images, corrupt, _lib.VtError)
         cor = corrupt is not None
+        area = self._area_idx(images, area)
         if jit and torch.cuda.is_current_stream_capturing():
             raise _lib.VtError("DevicePreprocessor: a call with jitter= cannot be captured in a graph")
         if cor and torch.cuda.is_current_stream_capturing():
@@ -471,7 +677,7 @@ class DevicePreprocessor:
         with torch.cuda.device(self.device):
             items, keep = self.stager.gather(images, self._missing)
             if workspace is None:
-                need = self._plan(items, None, jit, jpeg_idx, cor)["ws_bytes"]
+                need = self._plan(items, None, jit, jpeg_idx, cor, area)["ws_bytes"]
                 if self._ws is None or self._ws.numel() < need:
                     if self._ws is not None and any(v.get("captured") for v in self._plans.values()):
                         self._keepalive.append(self._ws)          # a captured graph still works in the old one
@@ -479,7 +685,7 @@ class DevicePreprocessor:
                 workspace = self._ws
             elif workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.device != self.device:
                 raise _lib.VtError("workspace must be a contiguous uint8 tensor on the preprocessor's device")
-            plan = self._plan(items, workspace.data_ptr(), jit, jpeg_idx, cor)
+            plan = self._plan(items, workspace.data_ptr(), jit, jpeg_idx, cor, area)
             if torch.cuda.is_current_stream_capturing():
                 plan["captured"] = True
             if workspace.numel() < plan["ws_bytes"]:
@@ -492,3 +698,38 @@ class DevicePreprocessor:
             for stage in plan["stages"]:
                 stage.launch(wp, st, out, jitter, quality, corrupt)
         return out
+
+
+@torch.no_grad()
+def pad_and_resize_device(frames: Sequence, target_size: int = 384, out: Optional[torch.Tensor] = None, device=None) -> torch.Tensor:
+    """`pad_and_resize_for_siglip` of every frame on the card (csrc/vt_area.hip), bit for bit: per frame a PIL image, uint8 [H, W, 3] array or
+    uint8 tensor (host or device, pitched views included), of mixed sizes; a `None` entry gives the canvas with nothing on it, all zeros.
+    Returns uint8 [n, target, target, 3] on the device: `out` (contiguous, of that shape) or a new tensor.  `device`: where to run when no
+    frame is a device tensor (default: the current one).  One launch, on the current stream."""
+    from .jpegmap import _stager
+    frames = list(frames)
+    target = area_size(target_size, 0)
+    if target is None or not frames:
+        raise _lib.VtError(f"pad_and_resize_device: a target size and at least one frame are needed, got {target_size!r} and {len(frames)} frames")
+    if device is None:
+        device = next((f.device for f in frames if isinstance(f, torch.Tensor) and f.is_cuda), "cuda")
+    st = _stager(device)
+    idx = [i for i, f in enumerate(frames) if f is not None]
+    shape = (len(frames), target, target, 3)
+    with torch.cuda.device(st.device):
+        items, _keep = st.gather([frames[i] for i in idx])       # _keep: contiguous copies of exotic views, alive until the launch is queued
+        arr, _, taps = area_table(items, target) if idx else (None, 0, None)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=st.device)
+        elif out.shape != shape or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != st.device:
+            raise _lib.VtError(f"out must be a contiguous uint8 {list(shape)} tensor on {st.device}")
+        if len(idx) < len(frames):
+            out.zero_()
+        if idx:
+            per = 3 * target * target
+            for f, i in zip(arr, idx):
+                f.out_off = i * per
+            dev, tabs = st.to_device(arr), (torch.from_numpy(taps).to(st.device) if taps.size else None)
+            _lib.check(_lib.lib().vt_area_resize(arr, _lib.ptr(dev), len(idx), _lib.ptr(out), _lib.ptr(tabs) if tabs is not None else None,
+                                                 taps.size, _lib.stream_ptr(st.device)), "vt_area_resize")
+    return out

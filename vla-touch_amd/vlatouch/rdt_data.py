@@ -106,11 +106,16 @@ class EpisodeStore:
     camera; the order is the reference's (camera1, camera2, the missing left wrist).  frames="device" keeps the frames in HBM, at most
     `max_device_bytes` of them: episodes are taken whole, in order, and the first one that does not fit and every one after it stay in pinned
     host memory; frames="host" keeps all of them there.  Host frames reach the preprocessor as host arrays, which it stages and uploads in one
-    copy per call (the staging copy is a host memcpy, so the store's pinning saves no copy, it only locks the pages)."""
+    copy per call (the staging copy is a host memcpy, so the store's pinning saves no copy, it only locks the pages).
+    pad_and_resize: None, or the target size of the reference's `pad_and_resize_for_siglip` (vlatouch.imgprep; parse_file applies it to every
+    frame it reads, data/unified_vla_dataset_episode.py:382-397): `upload` then resizes every camera frame once on the card
+    (csrc/vt_area.hip), in chunks, and the store keeps the target x target frames, on the device or in pinned host memory as above;
+    `max_device_bytes` counts the resized size, and `assemble` hands out the resized frames, so jitter and corruption act on them as
+    train/dataset.py does.  The stage precedes every random decision: `dataset_stat` and the draws are the same with and without it."""
 
     def __init__(self, paths_or_dir, *, dataset_name: str, dataset_names: Sequence[str], control_freq, horizon: int = 64, img_history_size: int = 2,
                  state_dim: int = 128, state_indices: Optional[Sequence[int]] = None, cameras: Sequence[Optional[str]] = ("camera1", "camera2", None),
-                 device="cuda", frames: str = "device", max_device_bytes: Optional[int] = None):
+                 device="cuda", frames: str = "device", max_device_bytes: Optional[int] = None, pad_and_resize: Optional[int] = None):
         if int(horizon) != horizon or horizon < 4:
             raise ValueError(f"EpisodeStore: horizon must be an integer >= 4, got {horizon!r} (below 4 the last drawable step has an empty action chunk)")
         if int(img_history_size) != img_history_size or img_history_size < 1:
@@ -122,6 +127,9 @@ class EpisodeStore:
             raise ValueError(f"EpisodeStore: frames must be 'device' or 'host', got {frames!r}")
         if max_device_bytes is not None and max_device_bytes < 0:
             raise ValueError("EpisodeStore: max_device_bytes must be >= 0")
+        if pad_and_resize is not None and (isinstance(pad_and_resize, bool) or int(pad_and_resize) != pad_and_resize or pad_and_resize < 1):
+            raise ValueError(f"EpisodeStore: pad_and_resize must be None or a positive target size, got {pad_and_resize!r}")
+        self.pad_and_resize = None if pad_and_resize is None else int(pad_and_resize)
         dataset_names = list(dataset_names)
         if dataset_name not in dataset_names:
             raise ValueError(f"EpisodeStore: dataset_name {dataset_name!r} is not in dataset_names {dataset_names}")
@@ -165,6 +173,9 @@ class EpisodeStore:
         a = np.asarray(node[...])
         if a.dtype != np.uint8 or a.ndim != 4 or a.shape[3] != 3:
             raise ValueError(f"EpisodeStore: camera {key!r} must be uint8 [N, H, W, 3], got {a.dtype} {a.shape}")
+        if self.pad_and_resize is not None:
+            from .imgprep import area_scale
+            area_scale(max(a.shape[1], a.shape[2]), self.pad_and_resize)      # refuses, by name, a frame smaller than the target
         return a
 
     def _load(self, path: str) -> None:
@@ -349,14 +360,26 @@ class EpisodeStore:
         self.resident_bytes = sum(t.numel() * t.element_size() for t in d.values())
         budget = 0 if self.frames_mode == "host" else self.max_device_bytes
         frames = []
+        T = self.pad_and_resize
+        kept = (lambda a: a.nbytes) if T is None else (lambda a: a.shape[0] * 3 * T * T)      # the bytes the store keeps of a camera's frames
         for e in eps:                                                  # decided per episode, in order: the first one past the cap and all after it stay on the host
-            need = sum(a.nbytes for a in e.frames if a is not None)
+            need = sum(kept(a) for a in e.frames if a is not None)
             if budget is not None:
                 budget = budget - need if need <= budget else -1      # -1: the cap is reached, nothing more goes to the device
             per_cam = []
             for a in e.frames:
                 if a is None:
                     per_cam.append(None)
+                elif T is not None:
+                    on_dev = budget is None or budget >= 0
+                    t = self._resized(a, T, dev, on_dev)
+                    if on_dev:
+                        per_cam.append(t)
+                        self.resident_bytes += kept(a)
+                    else:
+                        per_cam.append(t.numpy())
+                        d.setdefault("pinned", []).append(t)
+                        self.host_frame_bytes += kept(a)
                 elif budget is None or budget >= 0:
                     per_cam.append(torch.from_numpy(a).to(dev))
                     self.resident_bytes += a.nbytes
@@ -372,6 +395,21 @@ class EpisodeStore:
         d["frames"] = frames
         self._dev = d
         return self
+
+    @staticmethod
+    def _resized(a: np.ndarray, T: int, dev, on_dev: bool) -> torch.Tensor:
+        """`pad_and_resize_for_siglip` of a camera's frames [N, H, W, 3] on the card, in chunks of at most 64 MiB of raw frames -> uint8
+        [N, T, T, 3], on the device or (on_dev False) in pinned host memory."""
+        from .imgprep import pad_and_resize_device
+        n = a.shape[0]
+        out = torch.empty((n, T, T, 3), dtype=torch.uint8, device=dev) if on_dev else torch.empty((n, T, T, 3), dtype=torch.uint8).pin_memory()
+        chunk = max(1, (64 << 20) // max(1, a[0].nbytes))
+        for i in range(0, n, chunk):
+            raw = torch.from_numpy(a[i:i + chunk]).to(dev)
+            got = pad_and_resize_device(list(raw), T, out=out[i:i + chunk] if on_dev else None)
+            if not on_dev:
+                out[i:i + chunk].copy_(got)
+        return out
 
     def assemble(self, plans: Sequence[SamplePlan]) -> dict:
         """plans -> the collator's mapping on the device: states [B, 1, A], actions [B, H, A], state_elem_mask [B, A], state_norm [B, A] (fp32),
