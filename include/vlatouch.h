@@ -304,6 +304,11 @@ int vt_rdt_create(const vt_rdt_desc* desc, const void* const* weights, int n_wei
 void vt_rdt_destroy(vt_rdt_t h);
 int vt_rdt_num_weights(const vt_rdt_desc* desc);
 size_t vt_rdt_workspace_bytes(vt_rdt_t h, int B, int lang_len);
+/* The part of that workspace a caller driving vt_gemm itself needs for the small-M packed-weight tile (VtGemmParams.sk_ws / sk_cnt): bytes of
+ * fp32 slabs for Linears of at most M rows and N columns (0 above 512 rows: nothing splits there), and the number of int32 ticket counters
+ * (zeroed once by the caller, self-resetting afterwards).  Host only. */
+size_t vt_splitk_slab_bytes(int M, int N);
+int vt_splitk_counters(void);
 /* Optional fragment-packed second copies of the Linears of the denoise loop (vt_pack_w32 layout; bf16, hidden % 512 == 0): the caller
  * allocates vt_rdt_packed_bytes(h) bytes (0 = not applicable), vt_rdt_set_packed enqueues the packing kernels and keeps the pointers. */
 /* bounds[depth] (host): per block an upper bound of |q . k| * scale of its cross-attention (8 max|q_norm.weight| max|k_norm.weight| for the
@@ -524,6 +529,17 @@ typedef struct {
 int vt_gemm_tn_plan(int M, int N, int K, VtGemmTnPlan* plan);
 int vt_gemm_tn(const void* dy, long ld_dy, const void* x, long ld_x, int dt, int M, int N, int K, float* dw, float* db, void* ws, long ws_bytes, vt_stream_t stream);
 int vt_copy_cols_dt(const void* src, long lds, long off, void* dst, long ldd, long doff, long rows, long cols, int dt, vt_stream_t stream);
+/* vt_refresh16 (csrc/vt_refresh16.hip): the 16-bit trainer's weight refresh, one read of an fp32 master W [N][K] (row pitch ldw >= K elements)
+ *   writing whichever of four 16-bit forms (dt 1 bf16 / 3 fp16) are not null, in one launch:
+ *     w16  [N][K]   the bits of vt_cast(W) (round to nearest even),
+ *     w16t [K][Np]  vt_transpose_pad(w16), Np = N rounded up to 8, padding columns zero,
+ *     wp            vt_pack_w32(w16)  (N % 32 == 0 and K % 16 == 0),
+ *     wtp           vt_pack_w32 of w16t viewed [K][Np]  (K % 32 == 0 and Np % 16 == 0).
+ *   w16t, wp and wtp are 16-byte aligned; wp also wants a 16-byte aligned master and w16 and ldw % 4 == 0.  A null master, N or K below 1,
+ *   ldw < K, another dtype or a packed form asked for a shape vt_pack_w32 refuses returns VT_ERR_ARG before any launch and writes nothing;
+ *   an output that is null is never touched.  Stands where DeepSpeed's bf16 optimizer copies its fp32 partitions back into the 16-bit
+ *   parameters after a step; the transposed and packed forms are layouts of this engine's GEMM tiles. */
+int vt_refresh16(const float* W, long ldw, int N, int K, int dt, void* w16, void* w16t, void* wp, void* wtp, vt_stream_t stream);
 int vt_grad_clip_multi(const void* table, int ntensors, long total_chunks, float max_norm, float* chunk_part, float* norm_coef, vt_stream_t stream);
 int vt_mse_loss(const void* pred, const float* target, void* dpred, float* loss, long n, int dt, vt_stream_t stream);
 int vt_mse_loss_scaled(const void* pred, const float* target, void* dpred, float* loss, long n, int dt, float grad_scale, vt_stream_t stream);

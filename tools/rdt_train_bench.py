@@ -38,6 +38,13 @@ phase device-synchronised, medians with min / max; by device events the weight-g
 (`--img-len` x batch rows), a hidden x hidden product (67 x batch rows) and the timestep embedder's (batch rows), with the plan of each; peak device
 memory of a step of each trainer.  Added to `--out` under the key `weight_gradient_tn`; the other keys stay.
 
+`--small-batch-linear packed` measures the bf16 step (under `attention_backward="mfma"`, `weight_gradient="tn"`) with the packed-weight small-batch
+Linears and the one-pass refresh (`RdtTrainer(small_batch_linear="packed")`, csrc/vt_refresh16.hip) beside the default "gemm" trainer at every
+`--batch` size (4, 7 and 32 are the sizes of the record: the working point, the largest the path takes, and one it does not take), same method; by device
+events the refresh of all weights alone after every timed step under either setting, and one hidden x hidden Linear (67 x batch rows), forward and
+data gradient, on either route; how many launches were offered a packed copy and took the packed tile; the bytes of the packed copies and the scratch;
+peak device memory of a step of each trainer.  Added to `--out` under the key `small_batch_linear_packed`; the other keys stay.
+
 `--data-parallel fp32|bf16` measures the data-parallel step (`RdtTrainer(process_group=, comm_dtype=)`) at batch 4, bf16, `attention_backward="mfma"`
 over an RCCL ("nccl") process group of world size 1, which is all a one-GPU machine allows: NO SCALING NUMBER CAN BE PRODUCED ON A ONE-GPU BOX, and a
 world-size-1 all-reduce moves nothing between cards.  A grouped and an ungrouped trainer alternate in one process and swap who goes first; by device
@@ -430,6 +437,93 @@ def weight_gradient_run(a, c, sd, params, dev, B):
     return out
 
 
+def small_batch_linear_launches(a, c, B, dev):
+    """Device-event time of one hidden x hidden Linear at the step's row count (67 x batch), forward and data gradient, with and without the
+    packed copy (routes asked from the library), back to back and alternating -> dict."""
+    from vlatouch import ops
+    from vlatouch.rdt_train import PackedScratch, gemm_small_packed
+    D, M = c["hidden"], (c["horizon"] + 3) * B
+    g = torch.Generator(device=dev).manual_seed(5)
+    w = torch.randn(D, D, generator=g, device=dev) * 0.02
+    x, bias = torch.randn(M, D, generator=g, device=dev).bfloat16(), torch.zeros(D, device=dev)
+    forms = ops.refresh16(w, torch.bfloat16, ops.REFRESH16_FORMS)
+    scratch = PackedScratch(D, dev)
+    legs = {"forward": (forms["w16"], forms["wp"], bias), "data_gradient": (forms["w16t"], forms["wtp"], None)}
+    out = {"M": M, "N": D, "K": D}
+    for leg, (w16, wp, b) in legs.items():
+        calls = {"gemm": lambda: ops.gemm(x, w16, b), "packed": lambda: gemm_small_packed(x, w16, wp, scratch, b)}
+        routes = {"gemm": ops.gemm_route(ops.gemm_params(x, w16, b)[0]),
+                  "packed": ops.gemm_route(ops.gemm_params(x, w16, b, wp=wp, sk_ws=scratch.sk_ws, sk_cnt=scratch.sk_cnt)[0])}
+        ms = {"gemm": [], "packed": []}
+        for n in range(3 + 15):
+            for kind in (("gemm", "packed") if n % 2 == 0 else ("packed", "gemm")):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize(dev)
+                e0.record()
+                for _ in range(8):                      # eight launches back to back: one is below the resolution of an event pair
+                    res = calls[kind]()
+                e1.record()
+                torch.cuda.synchronize(dev)
+                if n >= 3:
+                    ms[kind].append(e0.elapsed_time(e1) / 8)
+        del res
+        out[leg] = {"route": routes, "gemm_ms": _stats(ms["gemm"]), "packed_ms": _stats(ms["packed"]),
+                    "packed_over_gemm": _stats(ms["packed"])["median"] / _stats(ms["gemm"])["median"]}
+    out["timing"] = ("device events around eight back-to-back launches of one Linear (output allocation from the caching allocator included), divided "
+                     "by eight; 3 warm-up + 15 timed, the two routes alternating; outside a step: the weights stay in L2 between the launches")
+    return out
+
+
+def small_batch_linear_run(a, c, sd, params, dev, B):
+    """The bf16 step (attention_backward="mfma", weight_gradient="tn") under small_batch_linear="packed" and "gemm", alternating in this process
+    at batch B, with the refresh phase of each timed alone by device events -> dict."""
+    from vlatouch.rdt_train import RdtTrainer
+    args, kw = inputs(a, B, dev)
+    kinds = ("packed", "gemm")
+    make = lambda kind: lambda: RdtTrainer(sd, heads=c["heads"], horizon=64, action_dim=128, lr=a.lr, precision="bf16", attention_backward="mfma",
+                                           weight_gradient="tn", small_batch_linear=kind, device=dev)
+    out = {"batch": B, "rows": (c["horizon"] + 3) * B, "precision": "bf16", "attention_backward": "mfma", "weight_gradient": "tn", "parameters": params,
+           "warmup": a.warmup, "timed_steps": a.steps}
+    refresh = {k: [] for k in kinds}
+    offered = {}
+
+    def each_step(kind, tr):                                  # the refresh alone, again, on the weights the step just wrote
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize(dev)
+        e0.record()
+        tr._refresh16()
+        e1.record()
+        torch.cuda.synchronize(dev)
+        refresh[kind].append(e0.elapsed_time(e1))
+        if kind == "packed" and not offered and tr.packed is not None:
+            tr.packed.log = []
+            tr.get_loss(*args, **kw)
+            routes = [r for _, _, r in tr.packed.log]
+            offered.update(launches_offered_a_packed_copy=len(routes), of_them_on_pws=routes.count("PWS"),
+                           weights_with_wp=len(tr.wp), weights_with_wtp=len(tr.wtp),
+                           packed_copies_gib=sum(t.numel() * 2 for d in (tr.wp, tr.wtp) for t in d.values()) / 2 ** 30,
+                           splitk_scratch_gib=tr.packed.sk_ws.numel() * 4 / 2 ** 30)
+            tr.packed.log = None
+
+    out.update(compare_steps(a, dev, args, kw, {kind: make(kind) for kind in kinds}, each_step))
+    for kind in kinds:
+        out[kind]["loss_decreases"] = bool(out[kind]["losses"][-1] < out[kind]["losses"][0])
+        out[kind]["refresh_ms"] = _stats(refresh[kind])
+    out["packed"].update(offered)
+    sp, sg = out["packed"]["step_ms"], out["gemm"]["step_ms"]
+    out["step_packed_over_gemm"] = sp["median"] / sg["median"]
+    spread = max(sp["max"] - sp["min"], sg["max"] - sg["min"])
+    out["step_gain_ms"], out["larger_min_max_spread_ms"] = sg["median"] - sp["median"], spread
+    out["step_faster_than_gemm_by_more_than_the_spread"] = bool(sg["median"] - sp["median"] > spread)
+    rp, rg = out["packed"]["refresh_ms"], out["gemm"]["refresh_ms"]
+    out["refresh_packed_over_gemm"] = rp["median"] / rg["median"]
+    out["refresh_no_slower_than_cast_plus_transpose"] = bool(rp["median"] - rg["median"] <= max(rp["max"] - rp["min"], rg["max"] - rg["min"]))
+    if out["rows"] <= 512:
+        out["linear_launches"] = small_batch_linear_launches(a, c, B, dev)
+    out["timing"] = STEP_TIMING + "; refresh_ms: device events around one _refresh16() call over all weights, after every timed step"
+    return out
+
+
 def fp16_attention_launches(a, c, B, dev):
     """Device-event time of the attention-backward launches alone in fp16 and in bf16, "wave" and "mfma", alternating, at the trainer's packed
     layouts and the three attention shapes of the step -> dict."""
@@ -574,7 +668,7 @@ def data_parallel_run(a, c, sd, params, dev):
     return out
 
 
-SECTIONS = ("accumulation", "adamw8bit", "attention_backward_mfma", "data_parallel", "fp16", "weight_gradient_tn")      # the modes' keys of --out
+SECTIONS = ("accumulation", "adamw8bit", "attention_backward_mfma", "data_parallel", "fp16", "small_batch_linear_packed", "weight_gradient_tn")      # the modes' keys of --out
 
 
 def merge_record(path, key, section, sub=None) -> None:
@@ -628,6 +722,10 @@ def main():
                     help="tn measures the bf16 step with the transpose-free weight-gradient GEMM beside the gemm path and adds it to --out")
     ap.add_argument("--step-weight-gradient", default="gemm", choices=["gemm", "tn"],
                     help="the weight gradient of the default run's trainer (a kernel trace of the step under \"tn\" uses this)")
+    ap.add_argument("--small-batch-linear", default="gemm", choices=["gemm", "packed"],
+                    help="packed measures the bf16 mfma / tn step with the packed small-batch Linears beside the gemm path and adds it to --out")
+    ap.add_argument("--step-small-batch-linear", default="gemm", choices=["gemm", "packed"],
+                    help="the small-batch Linear of the default run's trainer (a kernel trace of the step under \"packed\" uses this)")
     ap.add_argument("--data-parallel", default=None, choices=["fp32", "bf16"],
                     help="measures the data-parallel step over an RCCL group of world size 1 beside the ungrouped one and adds it to --out")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rdt_train_bench.json"))
@@ -636,8 +734,10 @@ def main():
         ap.error("--attention-backward mfma measures a 16-bit step")
     if "tn" in (a.weight_gradient, a.step_weight_gradient) and a.precision == "fp32":
         ap.error("weight_gradient tn is a 16-bit kernel")
+    if "packed" in (a.small_batch_linear, a.step_small_batch_linear) and a.precision == "fp32":
+        ap.error("small_batch_linear packed is a 16-bit path")
     if a.steps is None:
-        a.steps = 21 if a.attention_backward == "mfma" or a.weight_gradient == "tn" or a.precision == "fp16" else 10
+        a.steps = 21 if a.attention_backward == "mfma" or a.weight_gradient == "tn" or a.precision == "fp16" or a.small_batch_linear == "packed" else 10
     from vlatouch.rdt_train import RdtTrainer
     dev = torch.device("cuda:0")
     c = dict(hidden=a.hidden, depth=a.depth, heads=a.hidden // 64, horizon=64, action_dim=128, lang_token_dim=4096, img_token_dim=1152,
@@ -651,6 +751,9 @@ def main():
         section = dict(data_parallel_run(a, c, sd, params, dev), **meta)
         print(json.dumps(section))
         return merge_record(a.out, "data_parallel", section, sub=a.data_parallel)
+    if a.small_batch_linear == "packed":
+        runs = per_batch(small_batch_linear_run, a, c, sd, params, dev)
+        return merge_record(a.out, "small_batch_linear_packed", dict(runs=runs, **meta))
     if a.weight_gradient == "tn":
         runs = per_batch(weight_gradient_run, a, c, sd, params, dev)
         return merge_record(a.out, "weight_gradient_tn", dict(runs=runs, **meta, backward_faster_than_gemm_at_every_batch=all(r["backward_faster_than_gemm"] for r in runs)))
@@ -668,11 +771,13 @@ def main():
         rec["attention_backward"] = a.step_attention_backward
     if a.step_weight_gradient != "gemm":
         rec["weight_gradient"] = a.step_weight_gradient
+    if a.step_small_batch_linear != "gemm":
+        rec["small_batch_linear"] = a.step_small_batch_linear
     for B in a.batch:
         torch.cuda.empty_cache()
         torch.cuda.reset_peak_memory_stats(dev)
         tr = RdtTrainer(sd, heads=c["heads"], horizon=64, action_dim=128, lr=a.lr, precision=a.precision, attention_backward=a.step_attention_backward,
-                        weight_gradient=a.step_weight_gradient, device=dev)
+                        weight_gradient=a.step_weight_gradient, small_batch_linear=a.step_small_batch_linear, device=dev)
         args, kw = inputs(a, B, dev)
         t_f = t_fb = t_o = 0.0
         losses = []

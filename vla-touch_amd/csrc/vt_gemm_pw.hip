@@ -30,6 +30,7 @@
 #include "vt_prof.h"
 #include "vt_host.h"
 #include "vt_kernels.h"
+#include "vt_pack.h"
 #include "../../include/vlatouch.h"
 
 namespace {
@@ -325,17 +326,15 @@ __global__ __launch_bounds__(256, 1) void gemm_pw_kernel(const VtGemmParams p, c
   for (int i = 0; i < PFN; ++i) asm volatile("" :: "v"(pfv[i]));       // (the prefetch loads are not dead code)
 }
 
-// W [N][K] row-major (ldw) -> fragment order: out[((n/32 * K/16 + k/16) * 64 + (k%16)/8 * 32 + n%32) * 8 + k%8]; one thread per 16-byte chunk
+// W [N][K] row-major (ldw) -> fragment order (vt_pack.h); one thread per 16-byte chunk.  Thread i takes row (i % 32) of band i / (32 K/8) and
+// chunk (i / 32) % (K/8): a wave reads 32 rows x 32 B and its stores are the 1 KiB of one fragment, back to back.
 __global__ void pack_w32_kernel(const uint16_t* __restrict__ W, const long ldw, uint16_t* __restrict__ out, const int N, const int K) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;          // chunk index in the OUTPUT order
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long nchunks = (long)N * K / 8;
   if (i >= nchunks) return;
-  const int lane = (int)(i & 63);
-  const long frag = i >> 6;
-  const int ks = (int)(frag % (K / 16));
-  const int nt = (int)(frag / (K / 16));
-  const int n = nt * 32 + (lane & 31), k = ks * 16 + (lane >> 5) * 8;
-  *reinterpret_cast<uint4*>(out + i * 8) = *reinterpret_cast<const uint4*>(W + (long)n * ldw + k);
+  const long band = i / (4L * K), rem = i - band * 4L * K;            // 32 rows x K / 8 chunks = 4 K chunks per band
+  const int n = (int)band * 32 + (int)(rem & 31), c8 = (int)(rem >> 5);
+  *reinterpret_cast<uint4*>(out + vt_pack_w32_chunk(n, c8, K)) = *reinterpret_cast<const uint4*>(W + (long)n * ldw + c8 * 8);
 }
 
 }  // namespace
@@ -377,7 +376,7 @@ int vt_gemm_pw_launch(const VtGemmParams& p, hipStream_t s) {
 }
 
 extern "C" int vt_pack_w32(const void* W, long ldw, void* out, int N, int K, vt_stream_t stream) {
-  if (!W || !out || N <= 0 || K <= 0 || N % 32 || K % 16 || ldw % 8) return vt_fail(VT_ERR_ARG, "vt_pack_w32: N %% 32, K %% 16, ldw %% 8 must be 0");
+  if (!W || !out || !vt_pack_w32_shape_ok(N, K) || ldw % 8) return vt_fail(VT_ERR_ARG, "vt_pack_w32: N %% 32, K %% 16, ldw %% 8 must be 0");
   const long nchunks = (long)N * K / 8;
   hipLaunchKernelGGL(pack_w32_kernel, dim3((unsigned)((nchunks + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)W, ldw, (uint16_t*)out, N, K);
   return vt_check_launch();

@@ -178,6 +178,12 @@ namespace {
 inline int lpad64(int L) { return (L + 63) / 64 * 64; }
 constexpr int RDT_MAX_SPLITK = 16;
 constexpr int RDT_SK_CNT = 4096;
+}  // namespace
+// Split-K scratch of small-M Linears of at most M rows and N columns (rgemm's slab path and the in-launch split of vt_gemm_pws.hip): the fp32 slab
+// area, 0 above 512 rows where nothing splits, and the number of ticket counters.  Exported for callers that drive vt_gemm themselves (the RDT trainer).
+extern "C" size_t vt_splitk_slab_bytes(int M, int N) { return M >= 1 && M <= 512 && N >= 1 ? (size_t)RDT_MAX_SPLITK * M * N * 4 : 0; }
+extern "C" int vt_splitk_counters(void) { return RDT_SK_CNT; }
+namespace {
 struct RWs {
   size_t lang_c, img_c, tmpA, tmpB, state_tok, freq_emb, t_emb, emb_tmp, sin, kv_lang, kv_img, x, xn, qkv, q, att, hid, sa_in, sa_tmpA, sa_tmpB,
       out_tok, x0_cur, x0_prev, noisy, noisy_a, slab, sk_cnt, rs_part, kv_small, total;
@@ -221,7 +227,7 @@ RWs rcarve(const vt_rdt_s* h, int B, int L) {
   w.out_tok = cv.take(M * d.out_dim * 4);                 // (sized for the fp32 form of vt_rdt_sample's solver loop)
   w.x0_cur = cv.take((size_t)B * d.horizon * d.out_dim * 4); w.x0_prev = cv.take((size_t)B * d.horizon * d.out_dim * 4);
   w.noisy = cv.take((size_t)B * d.horizon * d.out_dim * 4); w.noisy_a = cv.take((size_t)B * d.horizon * d.out_dim * a);
-  w.slab_bytes = M <= 512 ? (size_t)RDT_MAX_SPLITK * M * 3 * D * 4 : 0;
+  w.slab_bytes = vt_splitk_slab_bytes((int)M, 3 * D);
   w.slab = cv.take(w.slab_bytes);
   w.sk_cnt = cv.take(RDT_SK_CNT * sizeof(int));    // ticket counters of the small-M tile (vt_gemm_pws.hip), zeroed once per call
   // cached cross-attention: B*H blocks stream a sample's whole key range each; below ~512 blocks split the range (flash-decoding)

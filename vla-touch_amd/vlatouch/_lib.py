@@ -270,6 +270,8 @@ SIGNATURES = {
     "vt_rdt_destroy": (None, [_P]),
     "vt_rdt_num_weights": (_I, [_P]),
     "vt_rdt_workspace_bytes": (_Z, [_P, _I, _I]),
+    "vt_splitk_slab_bytes": (_Z, [_I, _I]),
+    "vt_splitk_counters": (_I, []),
     "vt_rdt_set_score_bounds": (_I, [_P, _P, _I]),
     "vt_rdt_set_state_precision": (_I, [_P, _I]),
     "vt_rdt_set_io_dtype": (_I, [_P, _I]),
@@ -316,6 +318,7 @@ SIGNATURES = {
     "vt_timestep_embed": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "vt_add_rowvec_": (_I, [_P, _I, _P, _L, _L, _P]),
     "vt_transpose_pad": (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    "vt_refresh16": (_I, [_P, _L, _I, _I, _I, _P, _P, _P, _P, _P]),
     "vt_colsum_dt": (_I, [_P, _I, _L, _P, _I, _I, _P]),
     "vt_add_dt": (_I, [_P, _P, _L, _I, _P]),
     "vt_gemm_tn_plan": (_I, [_I, _I, _I, _P]),

@@ -14,17 +14,13 @@ def _es(t: torch.Tensor) -> int:
     return t.element_size()
 
 
-def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, *, act: int = L.ACT_NONE,
-         colscale: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
-         out: Optional[torch.Tensor] = None, out_dtype: Optional[torch.dtype] = None, splitk: int = 1,
-         headnorm=None, cmap=None, wp: Optional[torch.Tensor] = None, sk_ws: Optional[torch.Tensor] = None,
-         sk_cnt: Optional[torch.Tensor] = None, xn=None, rs=None) -> torch.Tensor:
-    """out[M,N] = residual + colscale * act(a[M,K] @ w[N,K]^T + bias).  splitk>1 returns the fp32 slabs [splitk,M,N].
-    headnorm = (w0[64], c0_end, w1[64] | None, c1_end, eps, mode): fused per-head RMSNorm (large bf16 GEMMs only).
-    cmap = (mode, T) with out= a [H, T, 2, 64, 64] tile stream (T = ceil(M/64)): the cached-condition K (mode 1) / Vt (mode 2) layout.
-    RMSNorm hand-off between two Linears on the weights-in-registers tile (csrc/vt_gemm.h): xn = (xn_out [M, N] 16-bit, gain [N] fp32, part [M, 2N/128, 2] fp32:
-    (sum of squares, sum) per 64 columns — with mode = NORM_RMS_VAR as a 4th entry: (second moment about the 64 columns' own mean, sum)) on the residual Linear (fp32 out), rs = (part, eps[, mode = NORM_RMS_MEANSQ | NORM_RMS_VAR]) on the Linear that reads
-    xn_out as `a`."""
+def gemm_params(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, *, act: int = L.ACT_NONE,
+                colscale: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
+                out: Optional[torch.Tensor] = None, out_dtype: Optional[torch.dtype] = None, splitk: int = 1,
+                headnorm=None, cmap=None, wp: Optional[torch.Tensor] = None, sk_ws: Optional[torch.Tensor] = None,
+                sk_cnt: Optional[torch.Tensor] = None, xn=None, rs=None):
+    """The parameter block `gemm` launches for the same arguments, and its output tensor: -> (block, out).  Nothing is launched, so a caller can
+    ask `gemm_route(block)` first and hand the block to `gemm_launch`."""
     assert a.dim() == 2 and w.dim() == 2 and a.shape[1] == w.shape[1]
     M, K = a.shape
     N = w.shape[0]
@@ -66,8 +62,24 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, 
         assert part.dtype == torch.float32 and part.shape[0] == M and part.dim() == 3 and part.shape[2] == 2 and part.is_contiguous()
         p.rs_part, p.rs_n, p.rs_inv_k, p.rs_eps = part.data_ptr(), part.shape[1], 1.0 / K, eps
         p.rs_mode = rs[2] if len(rs) > 2 else L.NORM_RMS_MEANSQ
-    L.check(L.lib().vt_gemm(C.byref(p), L.stream_ptr(a.device)), "vt_gemm")
+    return p, out
+
+
+def gemm_launch(p: L.GemmParams, out: torch.Tensor) -> torch.Tensor:
+    """Launch a block `gemm_params` built (its operands must still be alive) -> out."""
+    L.check(L.lib().vt_gemm(C.byref(p), L.stream_ptr(out.device)), "vt_gemm")
     return out
+
+
+def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, **fields) -> torch.Tensor:
+    """out[M,N] = residual + colscale * act(a[M,K] @ w[N,K]^T + bias).  splitk>1 returns the fp32 slabs [splitk,M,N].
+    Keywords (gemm_params): act, colscale, residual, out, out_dtype, splitk, wp, sk_ws, sk_cnt, and
+    headnorm = (w0[64], c0_end, w1[64] | None, c1_end, eps, mode): fused per-head RMSNorm (large bf16 GEMMs only).
+    cmap = (mode, T) with out= a [H, T, 2, 64, 64] tile stream (T = ceil(M/64)): the cached-condition K (mode 1) / Vt (mode 2) layout.
+    RMSNorm hand-off between two Linears on the weights-in-registers tile (csrc/vt_gemm.h): xn = (xn_out [M, N] 16-bit, gain [N] fp32, part [M, 2N/128, 2] fp32:
+    (sum of squares, sum) per 64 columns — with mode = NORM_RMS_VAR as a 4th entry: (second moment about the 64 columns' own mean, sum)) on the residual Linear (fp32 out), rs = (part, eps[, mode = NORM_RMS_MEANSQ | NORM_RMS_VAR]) on the Linear that reads
+    xn_out as `a`."""
+    return gemm_launch(*gemm_params(a, w, bias, **fields))
 
 
 def _grouped(t: torch.Tensor, grouped: bool, what: str):
@@ -203,6 +215,40 @@ def cast(x: torch.Tensor, dtype: torch.dtype, out: Optional[torch.Tensor] = None
     rows = x.numel() // cols
     L.check(L.lib().vt_cast(L.ptr(x), L.dt_code(x.dtype), cols, L.ptr(out), L.dt_code(dtype), cols, rows, cols, L.stream_ptr(x.device)), "vt_cast")
     return out
+
+
+REFRESH16_FORMS = ("w16", "w16t", "wp", "wtp")
+
+
+def refresh16(w: torch.Tensor, dtype: torch.dtype, forms=("w16", "w16t"), out: Optional[dict] = None) -> dict:
+    """w [N, K] fp32 master (unit inner stride, any row pitch) -> {form: tensor} for the requested `forms`, all written by ONE vt_refresh16
+    launch from one read of w: "w16" [N, K] = cast(w, dtype), "w16t" [K, Np] = its zero-padded transpose (Np = N rounded up to 8), "wp" =
+    pack_w32(w16), "wtp" = pack_w32(w16t) (flat, in MFMA fragment order).  `out` may hold tensors of earlier calls to overwrite in place."""
+    assert w.dim() == 2 and w.dtype == torch.float32 and w.stride(1) == 1 and all(f in REFRESH16_FORMS for f in forms)
+    N, K = w.shape
+    Np = (N + 7) // 8 * 8
+    shapes = {"w16": (N, K), "w16t": (K, Np), "wp": (N * K,), "wtp": (K * Np,)}
+    res = {}
+    for f in forms:
+        t = None if out is None else out.get(f)
+        if t is None:
+            t = torch.empty(shapes[f], dtype=dtype, device=w.device)
+        assert t.shape == shapes[f] and t.dtype == dtype and t.is_contiguous()
+        res[f] = t
+    L.check(L.lib().vt_refresh16(L.ptr(w), w.stride(0), N, K, L.dt_code(dtype), *(L.ptr(res.get(f)) for f in REFRESH16_FORMS), L.stream_ptr(w.device)),
+            "vt_refresh16")
+    return res
+
+
+def packed_route(M: int, N: int, K: int, dtype: torch.dtype, residual_dtype: Optional[torch.dtype] = None) -> str:
+    """The route vt_gemm takes for a plain Linear of M rows on contiguous 16-bit operands when a packed copy of its [N, K] weights travels with
+    it (host only, no memory is read): "PWS" means the small-M packed-weight tile takes it."""
+    p = L.GemmParams()
+    p.M, p.N, p.K, p.lda, p.ldw, p.ldc, p.ldr = M, N, K, K, K, N, N
+    p.groups = p.splitk = 1
+    p.a_dtype = p.w_dtype = p.c_dtype = L.dt_code(dtype)
+    p.Wp = 1                              # only tested against null by the dispatcher
+    return gemm_route(p)
 
 
 def pack_w32(w: torch.Tensor) -> torch.Tensor:

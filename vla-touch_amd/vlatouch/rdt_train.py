@@ -207,6 +207,35 @@ def copy_cols(src: torch.Tensor, off: int, dst: torch.Tensor, doff: int, cols: i
 
 
 WEIGHT_GRADIENTS = ("gemm", "tn")
+SMALL_BATCH_LINEARS = ("gemm", "packed")
+PACKED_MAX_ROWS = 512      # launches above it never get a packed pointer: the dispatcher would move them to another tile
+
+
+class PackedScratch:
+    """What the small-batch packed Linears of one trainer share: the split-K scratch of the small-M tile (fp32 slabs and zeroed, self-resetting
+    ticket counters, sized by the library as the inference engine's workspace sizes them) and, when `log` is a list, a record
+    (tag, rows, route) of every launch that was offered a packed copy."""
+
+    def __init__(self, max_cols: int, device):
+        lib = L.lib()
+        self.sk_ws = torch.empty(max(1, lib.vt_splitk_slab_bytes(PACKED_MAX_ROWS, max_cols) // 4), dtype=F32, device=device)
+        self.sk_cnt = torch.zeros(lib.vt_splitk_counters(), dtype=torch.int32, device=device)
+        self.log: Optional[list] = None
+
+
+def gemm_small_packed(x: torch.Tensor, w: torch.Tensor, wp: Optional[torch.Tensor], scratch: Optional[PackedScratch], bias=None, residual=None,
+                      tag: str = "") -> torch.Tensor:
+    """ops.gemm(x, w, bias, residual=residual), on the small-M packed-weight tile (csrc/vt_gemm_pws.hip) when `wp`, the fragment-packed copy of
+    w, exists, x has at most PACKED_MAX_ROWS rows and the library's dispatcher then routes the block there (ops.gemm_route on the block: the
+    predicate is not restated here).  Any other launch goes without the packed pointer, exactly as ops.gemm sends it."""
+    if wp is not None and scratch is not None and x.shape[0] <= PACKED_MAX_ROWS:
+        p, out = ops.gemm_params(x, w, bias, residual=residual, wp=wp, sk_ws=scratch.sk_ws, sk_cnt=scratch.sk_cnt)
+        route = ops.gemm_route(p)
+        if scratch.log is not None:
+            scratch.log.append((tag, x.shape[0], route))
+        if route == "PWS":
+            return ops.gemm_launch(p, out)
+    return ops.gemm(x, w, bias, residual=residual)
 
 
 def weight_grad_tn(dy: torch.Tensor, x: torch.Tensor, *, bias: bool = True):
@@ -229,11 +258,13 @@ def weight_grad_tn(dy: torch.Tensor, x: torch.Tensor, *, bias: bool = True):
     return dw, db
 
 
-def linear_bwd(x: torch.Tensor, w: torch.Tensor, dy: torch.Tensor, need_dx: bool = True, wt: Optional[torch.Tensor] = None, kernel: str = "gemm"):
+def linear_bwd(x: torch.Tensor, w: torch.Tensor, dy: torch.Tensor, need_dx: bool = True, wt: Optional[torch.Tensor] = None, kernel: str = "gemm",
+               wtp: Optional[torch.Tensor] = None, scratch: Optional[PackedScratch] = None, tag: str = ""):
     """y = x w^T + b -> (dx | None, dw fp32, db fp32).  fp32: exact-fp32 MFMA with the deterministic split-K of vlatouch.train.gemm;
     bf16 operands (w, or its cached transpose wt, in bf16): bf16 MFMA with fp32 accumulation, dx rounded to bf16, dw written in fp32.
     kernel="tn" (16-bit operands only) forms dw and db in one weight_grad_tn call instead of two transposes, a GEMM and a column sum; dx is the
-    same launch either way."""
+    same launch either way.  wtp (with wt and scratch): the fragment-packed copy of wt, which sends a dx of few rows to the small-M packed tile
+    (gemm_small_packed)."""
     if kernel not in WEIGHT_GRADIENTS:
         raise ValueError(f"linear_bwd: kernel must be one of {WEIGHT_GRADIENTS}, got {kernel!r}")
     if x.dtype == F32:
@@ -241,7 +272,7 @@ def linear_bwd(x: torch.Tensor, w: torch.Tensor, dy: torch.Tensor, need_dx: bool
             raise ValueError("linear_bwd: kernel='tn' is a 16-bit kernel, got fp32 operands")
         dx = T.gemm(dy, T.transpose(w)) if need_dx else None
         return dx, T.gemm(transpose_pad(dy), transpose_pad(x)), colsum(dy)
-    dx = ops.gemm(dy, wt if wt is not None else transpose_pad(w)) if need_dx else None
+    dx = gemm_small_packed(dy, wt if wt is not None else transpose_pad(w), wtp if wt is not None else None, scratch, tag=tag) if need_dx else None
     if kernel == "tn":
         return (dx, *weight_grad_tn(dy, x))
     return dx, ops.gemm(transpose_pad(dy), transpose_pad(x), out_dtype=F32), colsum(dy)
@@ -430,6 +461,13 @@ class RdtTrainer:
     not state: gradient bits change, checkpoints do not record it and resume under either setting.  Every 2-D weight must then have dimensions
     that are multiples of 8 (ValueError at construction, naming the tensor).
 
+    small_batch_linear="packed" (bf16 / fp16 only; the default "gemm" is the trainer as it was, launch for launch) keeps two more 16-bit copies of
+    the Linear weights, in MFMA fragment order (w and w^T), and sends the forward and data-gradient Linears of at most 512 rows to the small-M
+    packed-weight tile the denoise loop uses (csrc/vt_gemm_pws.hip) wherever the library's dispatcher takes them there; launches above 512 rows
+    get no packed pointer and keep their kernels and bits.  Every refresh of the 16-bit copies is then one vt_refresh16 launch per weight
+    (csrc/vt_refresh16.hip: one read of the fp32 master writes all four forms) instead of a cast and a transpose.  An execution choice like
+    attention_backward: output bits change (another summation order), checkpoints do not record it and resume under either setting.
+
     precision="fp16" with loss_scale= ("dynamic", a dict of GradScaler's init_scale / growth_factor / backoff_factor / growth_interval, or a
     positive number for a static scale) is torch.amp.GradScaler around the bf16 mode's step on IEEE half: dL/dpred is multiplied by the scale S
     (the loss is reported unscaled), the accumulators and the exchange hold scaled gradients, and optimizer_step unscales, checks and clips in
@@ -440,7 +478,7 @@ class RdtTrainer:
 
     process_group: a torch.distributed group of W ranks, one process per GPU, for data-parallel training with replicated state (None, the
     default, is the one-process trainer: same launches, same bits).  The constructor is then collective: the ranks compare parameter names and
-    shapes, gradient_accumulation_steps, precision, optimizer, comm_dtype, attention_backward and weight_gradient, every rank raising ValueError with the
+    shapes, gradient_accumulation_steps, precision, optimizer, comm_dtype, attention_backward, weight_gradient and small_batch_linear, every rank raising ValueError with the
     differing field if they disagree, and rank 0's master parameters are broadcast.  For any k the accumulators are views into one fp32
     arena (tensor i at first_chunk_i * MT_CHUNK, padding zeroed once); `accumulate` folds with scale 1 / (k W) and, after the window's last
     fold, sums the arena over the ranks in chunk-aligned slices of at most `comm_bucket_bytes`; comm_dtype="bf16" (an exchange format, allowed
@@ -451,7 +489,8 @@ class RdtTrainer:
                  num_train_timesteps: int = 1000, beta_schedule: str = "squaredcos_cap_v2", precision: str = "fp32", lr: float = 5e-6,
                  betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, max_grad_norm: float = 1.0, lr_scheduler: str = "constant",
                  lr_warmup_steps: int = 500, ema: Optional[dict] = None, config: Optional[dict] = None, gradient_accumulation_steps: int = 1,
-                 optimizer: str = "adamw", attention_backward: str = "wave", weight_gradient: str = "gemm", process_group=None,
+                 optimizer: str = "adamw", attention_backward: str = "wave", weight_gradient: str = "gemm", small_batch_linear: str = "gemm",
+                 process_group=None,
                  comm_dtype: str = "fp32", comm_bucket_bytes: int = 256 << 20, loss_scale=None, device="cuda"):
         if precision not in PRECISIONS:
             raise ValueError(f"precision must be one of {PRECISIONS}, got {precision!r}")
@@ -481,6 +520,10 @@ class RdtTrainer:
             for k, v in sd.items():
                 if k.endswith(".weight") and v.dim() == 2 and (v.shape[0] % 8 or v.shape[1] % 8):
                     raise ValueError(f"weight_gradient='tn' takes Linear weights whose dimensions are multiples of 8, {k} is {tuple(v.shape)}")
+        if small_batch_linear not in SMALL_BATCH_LINEARS:
+            raise ValueError(f"small_batch_linear must be one of {SMALL_BATCH_LINEARS}, got {small_batch_linear!r}")
+        if small_batch_linear == "packed" and precision == "fp32":
+            raise ValueError("small_batch_linear='packed' runs on a 16-bit kernel: it needs precision='bf16' or 'fp16' ('gemm' is the fp32 path)")
         if comm_dtype not in COMM_DTYPES:
             raise ValueError(f"comm_dtype must be one of {COMM_DTYPES}, got {comm_dtype!r} (the format of the gradient exchange, whatever the precision)")
         if int(comm_bucket_bytes) != comm_bucket_bytes or comm_bucket_bytes < 1:
@@ -503,10 +546,8 @@ class RdtTrainer:
             from . import dist as D
             self.world, self.rank = dist.get_world_size(process_group), dist.get_rank(process_group)
             digest = hashlib.sha256(repr([(k, tuple(v.shape)) for k, v in self.p.items()]).encode()).hexdigest()
-            diff = D.differing_field({"parameter names and shapes": digest, "gradient_accumulation_steps": int(gradient_accumulation_steps),
-                                      "precision": precision, "optimizer": optimizer, "comm_dtype": comm_dtype,
-                                      "attention_backward": attention_backward, "weight_gradient": weight_gradient,
-                                      **({} if scale_settings is None else {"loss_scale": repr(sorted(scale_settings.items()))})}, process_group)
+            diff = D.differing_field(self.group_fields(digest, gradient_accumulation_steps, precision, optimizer, comm_dtype, attention_backward,
+                                                       weight_gradient, small_batch_linear, scale_settings), process_group)
             if diff is not None:
                 raise ValueError(f"RdtTrainer: the ranks of the process group disagree on {diff[0]}: {diff[1]}")
             D.broadcast_tensors(self.p.values(), src=dist.get_global_rank(process_group, 0), group=process_group)
@@ -532,6 +573,13 @@ class RdtTrainer:
         self.last_step_skipped = False                                # the last optimizer_step found a non-finite gradient and took no step
         self.w16: Dict[str, torch.Tensor] = {}                        # 16-bit modes: copies of the Linear weights and of their transposes,
         self.w16t: Dict[str, torch.Tensor] = {}                       # refreshed after every optimizer step
+        self.small_batch_linear = small_batch_linear          # an execution choice too
+        self.wp: Dict[str, torch.Tensor] = {}                         # "packed": fragment-packed copies of w16 / w16t for the weights whose forward /
+        self.wtp: Dict[str, torch.Tensor] = {}                        # data-gradient Linear the small-M tile can take; refreshed with the others
+        self._forms: Dict[str, tuple] = {}                            # "packed": per 2-D weight, the forms vt_refresh16 writes for it
+        self.packed: Optional[PackedScratch] = None
+        if small_batch_linear == "packed":
+            self._plan_packed()
         self._refresh16()
         self.base_lr, self.lr, self.wd, self.betas, self.eps, self.max_grad_norm = lr, lr, weight_decay, betas, eps, max_grad_norm
         self.lr_scheduler, self.lr_warmup_steps = lr_scheduler, lr_warmup_steps
@@ -557,6 +605,15 @@ class RdtTrainer:
         self._sampler = None                                  # the RDTRunner `sampler` keeps, and the (source, its version) it was last refreshed at
         self._sampler_key = None
         self.sampler_repacks = 0                              # times `sampler` handed weights over (the first build included)
+
+    @staticmethod
+    def group_fields(shapes_digest, gradient_accumulation_steps, precision, optimizer, comm_dtype, attention_backward, weight_gradient,
+                     small_batch_linear, scale_settings) -> dict:
+        """What the ranks of a process group compare at construction (dist.differing_field names the first key that differs)."""
+        return {"parameter names and shapes": shapes_digest, "gradient_accumulation_steps": int(gradient_accumulation_steps),
+                "precision": precision, "optimizer": optimizer, "comm_dtype": comm_dtype,
+                "attention_backward": attention_backward, "weight_gradient": weight_gradient, "small_batch_linear": small_batch_linear,
+                **({} if scale_settings is None else {"loss_scale": repr(sorted(scale_settings.items()))})}
 
     def _adaptor_layers(self, name: str) -> List[str]:
         if f"{name}.weight" in self.p:
@@ -595,17 +652,39 @@ class RdtTrainer:
         """Global L2 norm of the gradients before clipping at the last optimizer_step (0-d device tensor; reading it synchronises)."""
         return self._norm_coef[0]
 
+    def _plan_packed(self) -> None:
+        """small_batch_linear="packed": which packed forms each 2-D weight gets, decided once by asking the dispatcher (ops.packed_route) whether a
+        one-row Linear with these weights and a packed copy goes to the small-M tile: w [N, K] for the forward, w^T [K, Np] for the data
+        gradient.  Then the tile's split-K scratch, wide enough for the widest of those Linears."""
+        widest = 0
+        for k, v in self.p.items():
+            if k.endswith(".weight") and v.dim() == 2:
+                (N, K), Np = v.shape, (v.shape[0] + 7) // 8 * 8
+                fwd, dgrad = ops.packed_route(1, N, K, self.adt) == "PWS", ops.packed_route(1, K, Np, self.adt) == "PWS"
+                self._forms[k] = ("w16", "w16t") + (("wp",) if fwd else ()) + (("wtp",) if dgrad else ())
+                widest = max(widest, N if fwd else 0, K if dgrad else 0)
+        if widest:
+            self.packed = PackedScratch(widest, self.device)
+
     def _refresh16(self) -> None:
         if self.adt == F32:
             return
+        stores = {"w16": self.w16, "w16t": self.w16t, "wp": self.wp, "wtp": self.wtp}
         for k, v in self.p.items():
             if k.endswith(".weight") and v.dim() == 2:
+                if self.small_batch_linear == "packed":           # one launch, one read of the master, every form in place
+                    for f, t in ops.refresh16(v, self.adt, self._forms[k], out={f: stores[f].get(k) for f in self._forms[k]}).items():
+                        stores[f][k] = t
+                    continue
                 self.w16[k] = ops.cast(v, self.adt, out=self.w16.get(k))
                 self.w16t[k] = transpose_pad(self.w16[k])
 
     # ---- layers
     def _linear(self, name, x, residual=None):
         b = self.p[f"{name}.bias"]
+        if self.packed is not None:
+            k = f"{name}.weight"
+            return gemm_small_packed(x, self.w16[k], self.wp.get(k), self.packed, b, residual, tag=f"{name}/forward")
         if self.adt != F32:
             return ops.gemm(x, self.w16[f"{name}.weight"], b, residual=residual)
         w = self.p[f"{name}.weight"]
@@ -614,7 +693,8 @@ class RdtTrainer:
     def _linear_bwd(self, name, x, dy, need_dx=True):
         k = f"{name}.weight"
         dx, self.g[k], self.g[f"{name}.bias"] = linear_bwd(x, self.w16.get(k, self.p[k]), dy, need_dx, self.w16t.get(k),
-                                                                 kernel=self.weight_gradient)
+                                                                 kernel=self.weight_gradient, wtp=self.wtp.get(k), scratch=self.packed,
+                                                                 tag=f"{name}/dgrad")
         return dx
 
     def _norm(self, name, x):
