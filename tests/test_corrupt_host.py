@@ -322,7 +322,6 @@ def full_params():
 
 def test_record_conversion():
     from vlatouch import _lib
-    assert C.sizeof(_lib.CorruptFrame) == 80
     arr = (_lib.CorruptFrame * 3)()
     ps = [full_params(), None, A.CorruptParams(True, None, blur="median", k=5)]
     words = A.pack_corrupt(arr, ps)

@@ -160,8 +160,7 @@ def test_record_conversion():
     from vlatouch import _lib
     from vlatouch.imgaug import OP_NONE, ColorJitterParams, hue_shift
     assert hue_shift(-0.03) == 249 and hue_shift(0.03) == 7 and hue_shift(0.0) == 0 and hue_shift(0.5) == 127 and hue_shift(-0.5) == 129
-    assert C.sizeof(_lib.ColorJitterFrame) == 64
-    rec = _lib.ColorJitterFrame()
+    rec =_lib.ColorJitterFrame()
     ColorJitterParams((3, 1, 0, 2), brightness=0.9, contrast=None, saturation=1.25, hue=-0.03).fill_record(rec)
     assert list(rec.order) == [3, OP_NONE, 0, 2]
     assert (rec.brightness, rec.saturation, rec.hue_shift) == (float(np.float32(0.9)), 1.25, 249)
@@ -171,18 +170,6 @@ def test_record_conversion():
         ColorJitterParams((0, 1, 2, 2))
     with pytest.raises(ValueError):
         ColorJitterParams((0, 1, 2, 3), hue=0.6)
-
-
-def test_header_declares_the_entry_points_and_the_ops():
-    import os
-    from vlatouch import _lib, imgaug
-    hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "vlatouch.h")).read()
-    for name in ("vt_colorjitter_workspace_bytes", "vt_colorjitter", "vt_colorjitter_frame"):
-        assert name in hdr
-    for name, val in (("BRIGHTNESS", imgaug.OP_BRIGHTNESS), ("CONTRAST", imgaug.OP_CONTRAST), ("SATURATION", imgaug.OP_SATURATION),
-                      ("HUE", imgaug.OP_HUE), ("NONE", imgaug.OP_NONE), ("LIFT", _lib.COLORJITTER_LIFT)):
-        assert f"#define VT_COLORJITTER_{name} {val}\n" in hdr
-    assert "vt_colorjitter" in _lib.SIGNATURES and "vt_colorjitter_workspace_bytes" in _lib.SIGNATURES
 
 
 def test_entry_point_rejects_bad_arguments_without_a_launch():

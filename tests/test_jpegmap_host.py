@@ -93,17 +93,11 @@ def test_bad_quality_raises(quality):
             jpeg_quality(quality)
 
 
-def test_entry_points_are_declared_bound_and_check_their_arguments():
+def test_entry_points_check_their_arguments():
     """Through the loaded library, without a device: every call below is refused before a launch, the pointers are never read."""
     import ctypes as C
-    import re
     from vlatouch import _lib as L
     lib = L.lib()
-    hdr = open(os.path.join(cases.ROOT, "include", "vlatouch.h")).read()
-    for name in ("vt_jpegmap", "vt_jpegmap_workspace_bytes"):
-        assert re.search(r"\b%s\s*\(" % name, hdr) and name in L.SIGNATURES and hasattr(lib, name)
-    assert re.search(r"#define VT_JPEGMAP_CV2_ORDER 1\b", hdr) and L.JPEGMAP_CV2_ORDER == 1
-    assert C.sizeof(L.JpegmapFrame) == 40
     dev = C.c_void_p(4096)
 
     def frame(h=480, w=640, pitch=None, src=4096, out_off=0):

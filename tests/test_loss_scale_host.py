@@ -1,17 +1,13 @@
 """fp16 fine-tuning's loss scaling on the host: the statement of tests/loss_scale_ref.py against torch.amp.GradScaler("cpu") and accelerate,
 the trainer's own LossScaler against that statement, the constructor's validation, unscale-then-clip against GradScaler.unscale_ +
-clip_grad_norm_ bit for bit, the fp16 statement of the MFMA attention backward against fp64, and the C interface's new names.  No GPU."""
+clip_grad_norm_ bit for bit, and the fp16 statement of the MFMA attention backward against fp64.  No GPU."""
 import math
-import os
-import re
 
 import pytest
 import torch
 
 from tests import attn_bwd_mfma16_ref as A16
 from tests import loss_scale_ref as S
-
-HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 def _bits(t):
@@ -215,16 +211,8 @@ def test_fp16_mfma_statement_against_fp64(case):
         assert all(float(got[i][1].abs().max()) == 0.0 for i in range(3))
 
 
-def test_header_declares_and_lib_binds_the_new_names():
-    from vlatouch import _lib as L
-    header = open(os.path.join(HERE, "..", "include", "vlatouch.h")).read()
-    for name, nargs in (("vt_mse_loss_scaled", 8), ("vt_grad_unscale_clip_multi", 9)):
-        m = re.search(r"\bint " + name + r"\(([^;]*)\);", header)
-        assert m, f"{name} is not declared in include/vlatouch.h"
-        assert len(m.group(1).split(",")) == nargs
-        assert name in L.SIGNATURES and len(L.SIGNATURES[name][1]) == nargs
+def test_inverse_of_the_largest_scale_is_finite():
     assert math.isfinite(S.inv_scale(2.0 ** 24))
-
 
 
 def test_recorded_fp16_oracle_errors_are_what_the_oracle_reaches():

@@ -1,34 +1,15 @@
 """vt_gemm_tn_plan (csrc/vt_gemm_tn.hip) without a GPU: the row splits of the transpose-free weight-gradient GEMM are a pure function of
 (M, N, K) that covers rows 0 .. M - 1 exactly once in order, in runs that are multiples of the kernel's m-step, with the workspace the header
-states; bad shapes are refused; both symbols are bound with the header's signatures."""
-import ctypes as C
-import os
-import re
-
+states; bad shapes are refused."""
 import pytest
 
 from tests import wgrad_tn_ref as W
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 VT_ERR_ARG = -22
 
 
 def _rows():
     return sorted({1, 3, 32, 33, 64, 127, 128, 129, 4374 * 4, 4374 * 32, 17496 * 4} | {67 * B for B in range(1, 33)} | set(range(1, 33)))
-
-
-def test_both_symbols_are_bound_with_the_headers_signatures():
-    from vlatouch import _lib as L
-    header = open(os.path.join(ROOT, "include", "vlatouch.h")).read()
-    assert re.search(r"int\s+vt_gemm_tn_plan\(int M, int N, int K, VtGemmTnPlan\* plan\);", header)
-    assert re.search(r"int\s+vt_gemm_tn\(const void\* dy, long ld_dy, const void\* x, long ld_x, int dt, int M, int N, int K, float\* dw, float\* db, "
-                     r"void\* ws, long ws_bytes, vt_stream_t stream\);", header)
-    assert re.search(r"int splits, rows_per_split, m_step;\s+long ws_bytes;\s+} VtGemmTnPlan;", header)
-    assert [n for n, _ in L.GemmTnPlan._fields_] == ["splits", "rows_per_split", "m_step", "ws_bytes"]
-    assert L.SIGNATURES["vt_gemm_tn_plan"] == (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p])
-    assert L.SIGNATURES["vt_gemm_tn"] == (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_long] + [C.c_int] * 4 + [C.c_void_p] * 3 + [C.c_long, C.c_void_p])
-    lib = L.lib()
-    assert lib.vt_gemm_tn_plan.restype is C.c_int and lib.vt_gemm_tn.restype is C.c_int
 
 
 def test_plan_over_the_trainers_shapes():

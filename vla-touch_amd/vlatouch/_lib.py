@@ -185,6 +185,12 @@ class LstmDesc(C.Structure):
                 ("force_pad", C.c_int), ("in_pad", C.c_int), ("cdt", C.c_int)]
 
 
+class RdtDesc(C.Structure):
+    _fields_ = [("hidden", C.c_int), ("depth", C.c_int), ("heads", C.c_int), ("horizon", C.c_int), ("out_dim", C.c_int),
+                ("state_dim", C.c_int), ("lang_dim", C.c_int), ("img_dim", C.c_int), ("max_lang_len", C.c_int), ("img_len", C.c_int),
+                ("n_lang", C.c_int), ("n_img", C.c_int), ("n_state", C.c_int), ("cdt", C.c_int), ("adt", C.c_int), ("rms_mode", C.c_int)]
+
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -210,7 +216,7 @@ def lib() -> C.CDLL:
 
 
 _P, _I, _L, _F, _Z = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_size_t
-# every entry point of include/vlatouch.h: name -> (restype, argtypes)
+# name -> (restype, argtypes); tests/test_abi_host.py holds this table, the structs above and the integer codes against the C headers
 SIGNATURES = {
     "vt_selftest_mfma": (_I, [_P, _P]),
     "vt_prof_enable": (_I, [_I]),
@@ -352,12 +358,6 @@ SIGNATURES = {
     "vt_marker_detect": (_I, [_P, _I, _I, _I, _I, _I, C.c_double, C.c_double, _I, _P, _P, _I, _P, _P, _P]),
     "vt_marker_displacement": (_I, [_P, _P, _I, _I, _P, _I, _P, _P, _P]),
 }
-
-
-class RdtDesc(C.Structure):
-    _fields_ = [("hidden", C.c_int), ("depth", C.c_int), ("heads", C.c_int), ("horizon", C.c_int), ("out_dim", C.c_int),
-                ("state_dim", C.c_int), ("lang_dim", C.c_int), ("img_dim", C.c_int), ("max_lang_len", C.c_int), ("img_len", C.c_int),
-                ("n_lang", C.c_int), ("n_img", C.c_int), ("n_state", C.c_int), ("cdt", C.c_int), ("adt", C.c_int), ("rms_mode", C.c_int)]
 
 
 def check(code: int, what: str = "") -> None:
