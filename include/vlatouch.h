@@ -693,6 +693,40 @@ size_t vt_jpegmap_workspace_bytes(vt_jpegmap_frame* frames_host, int n);
 int vt_jpegmap(const vt_jpegmap_frame* frames_host, const void* frames_dev, int n, int quality, int flags, void* out, void* ws,
                size_t ws_bytes, vt_stream_t stream);
 
+/* ---- baseline JPEG files decoded on the device (vlatouch/jpegdec.py; csrc/vt_jpegdec.hip), bit-identical to libjpeg's default decompress
+ * (islow inverse DCT, fancy h2v2 up-sampling, components at most 2 samples wide replicated): three components, 4:2:0 or 4:4:4, one
+ * interleaved scan.  The host parses the markers, un-stuffs FF 00 and removes the RSTn markers; the Huffman decoder, the dequantisation, the
+ * inverse DCT, the up-sampling and the conversion run here.  Output: uint8 HWC, frame i tight (pitch 3 * w) at out + out_off.
+ * A table is int64 [n][VT_JPEG_K], passed as host memory (checked here) and as the same bytes in device memory (read by the kernels).  A row:
+ *    0 stream     device pointer, 4-byte aligned: the un-stuffed entropy bytes, padded with FF to a multiple of 4
+ *    1 len        bytes of the stream before the padding (< 2^28)
+ *    2 h   3 w    frame size (1..32768)
+ *    4 sampling   VT_JPEG_444 or VT_JPEG_420
+ *    5 tables     device pointer, 4-byte aligned: a table set of VT_JPEG_TABLESET_BYTES (layout: csrc/vt_jpegdec.hip)
+ *    6 entries    device pointer, 16-byte aligned: int32 [ceil(mcus / interval)][4] = bit offset, DC predictors of Y, Cb, Cr
+ *    7 interval   MCUs per entry (1..mcus)
+ *    8 restart    the restart interval in MCUs, 0 = none
+ *    9 starts     device pointer, 4-byte aligned: int32 byte offset in the stream of every restart interval's start ([0] = 0)
+ *   10 out_off    byte offset of this frame's output in `out` (vt_jpeg_decode)
+ *   11 12         workspace offsets, WRITTEN by vt_jpeg_workspace_bytes, which returns the bytes vt_jpeg_decode needs (0 on a bad table)
+ *   13..15        reserved, 0
+ * vt_jpeg_index (once per upload) walks every stream, one lane per restart interval, and writes the entries.  vt_jpeg_decode decodes the n
+ * frames of the table: one lane per entry Huffman-decodes `interval` MCUs into int16 coefficients in the workspace; then dequantise +
+ * inverse DCT into decoded planes; then up-sampling and conversion.  status: int32 [n] on the device, zeroed by the caller; a lane that
+ * meets an undefined code, a run past coefficient 63 or the end of the stream before its MCUs are done stores 1 in its frame's word and
+ * zero-fills the rest of its MCUs.  Stream reads are clamped to the padded length (1-bits behind it, as libjpeg pads).  No atomics: a pure
+ * function of the inputs.  No host read, allocation or synchronisation.  A bad row (sizes, sampling code, null or misaligned pointers,
+ * interval, workspace offsets not the ones written), n < 1, a null buffer and a short or misaligned (16 bytes) workspace return
+ * VT_ERR_ARG without a launch. */
+#define VT_JPEG_K 16
+#define VT_JPEG_444 0
+#define VT_JPEG_420 1
+#define VT_JPEG_TABLESET_BYTES 6144
+size_t vt_jpeg_workspace_bytes(long long* table_host, int n);
+int vt_jpeg_index(const long long* table_host, const void* table_dev, int n, void* status, vt_stream_t stream);
+int vt_jpeg_decode(const long long* table_host, const void* table_dev, int n, void* out, void* ws, size_t ws_bytes, void* status,
+                   vt_stream_t stream);
+
 /* ---- corruption of camera frames (train/image_corrupt.py: imgaug's Sequential([noise, blur], random_order=True)), restated in integers
  * (UNPINNED against imgaug and cv2).  uint8 HWC in (pitched), uint8 HWC out, frame i tight (pitch 3 * w) at
  * out + out_off; source and output must not overlap.  Per frame, in the stated order, either or both of

@@ -14,17 +14,18 @@
 //                          both a permutation of the 32 banks over each 32-lane group.
 //   jpegmap_upsample_kernel  one lane = 2 rows x 4 columns of the output: Y', the clamped 3 x 4 neighbourhood of Cb' and Cr', the triangle
 //                          filter, the conversion, 12 bytes per row.  A launch of its own: the filter reads decoded chroma of neighbouring MCUs.
+// The inverse DCT pass, the plane layout and the up-sampling item are vt_jpeg.h's, shared with the decoder of stored files (vt_jpegdec.hip).
 // Workspace: per frame the planes Y' [H16][W16], Cb' and Cr' [H16 / 2][W16 / 2] of the frame padded to multiples of 16 (1.5 bytes per pixel).
 #include <stdint.h>
 #include "vt_common.h"
 #include "vt_frames.h"
+#include "vt_jpeg.h"
 #include "vt_pixel.h"
 #include "../../include/vlatouch.h"
 
 namespace {
 constexpr int kRow = 9;            // words per row of a block in LDS
 constexpr int kBlk = 8 * kRow;     // words per block
-constexpr int kHalf = 32768;       // ONE_HALF of the 16-bit fixed-point colour conversions
 constexpr int kNT = 256;           // threads per block of the up-sampling launch
 
 // Annex K of ITU-T T.81, natural order
@@ -33,17 +34,6 @@ __device__ const unsigned char kBase[2][64] = {
      18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99},
     {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
      99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99}};
-
-__device__ __forceinline__ int descale(const int x, const int n) { return (x + (1 << (n - 1))) >> n; }
-
-// the odd part that jfdctint and jidctint share: (t4, t5, t6, t7) -> the sums of out7 / 5 / 3 / 1 (forward) or tmp0..3 (inverse)
-__device__ __forceinline__ void odd_part(int& t4, int& t5, int& t6, int& t7) {
-  int z1 = t4 + t7, z2 = t5 + t6, z3 = t4 + t6, z4 = t5 + t7;
-  const int z5 = (z3 + z4) * 9633;
-  t4 *= 2446; t5 *= 16819; t6 *= 25172; t7 *= 12299;
-  z1 *= -7373; z2 *= -20995; z3 = z3 * -16069 + z5; z4 = z4 * -3196 + z5;
-  t4 += z1 + z3; t5 += z2 + z4; t6 += z2 + z3; t7 += z1 + z4;
-}
 
 // one pass of jfdctint on d[0..8): FIRST = the row pass (PASS1_BITS up-scaling), else the column pass
 template <bool FIRST> __device__ __forceinline__ void fdct8(int d[8]) {
@@ -58,32 +48,6 @@ template <bool FIRST> __device__ __forceinline__ void fdct8(int d[8]) {
   d[6] = descale(z1 - t12 * 15137, n);
   odd_part(t4, t5, t6, t7);
   d[7] = descale(t4, n); d[5] = descale(t5, n); d[3] = descale(t6, n); d[1] = descale(t7, n);
-}
-
-// one pass of jidctint on c[0..8), descaled by N bits
-template <int N> __device__ __forceinline__ void idct8(int c[8]) {
-  const int z1 = (c[2] + c[6]) * 4433;
-  const int t2 = z1 - c[6] * 15137, t3 = z1 + c[2] * 6270;
-  const int t0 = (c[0] + c[4]) << 13, t1 = (c[0] - c[4]) << 13;
-  const int t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
-  int o0 = c[7], o1 = c[5], o2 = c[3], o3 = c[1];
-  odd_part(o0, o1, o2, o3);
-  c[0] = descale(t10 + o3, N); c[7] = descale(t10 - o3, N);
-  c[1] = descale(t11 + o2, N); c[6] = descale(t11 - o2, N);
-  c[2] = descale(t12 + o1, N); c[5] = descale(t12 - o1, N);
-  c[3] = descale(t13 + o0, N); c[4] = descale(t13 - o0, N);
-}
-
-struct PlaneGeom {
-  int H16, W16;       // the frame padded to whole MCUs
-  long cb, cr;        // byte offsets of the chroma planes behind the frame's ws_off
-};
-__host__ __device__ inline PlaneGeom plane_geom(const int h, const int w) {
-  PlaneGeom g;
-  g.H16 = (h + 15) & ~15; g.W16 = (w + 15) & ~15;
-  g.cb = (long)g.H16 * g.W16;
-  g.cr = g.cb + g.cb / 4;
-  return g;
 }
 
 __global__ void __launch_bounds__(64) jpegmap_mcu_kernel(const vt_jpegmap_frame* __restrict__ frames, const int scale, const int flags,
@@ -117,9 +81,9 @@ __global__ void __launch_bounds__(64) jpegmap_mcu_kernel(const vt_jpegmap_frame*
     for (int j = 0; j < 4; ++j) {
       int R = px[j] & 255, G = (px[j] >> 8) & 255, B = px[j] >> 16;
       if (flags & VT_JPEGMAP_CV2_ORDER) { const int t = R; R = B; B = t; }
-      yb[j] = ((19595 * R + 38470 * G + 7471 * B + kHalf) >> 16) - 128;      // luma8(R, G, B) written out: through the helper this kernel came out 20 bytes shorter, and it is held to its size
-      cbv[j] = (-11059 * R - 21709 * G + 32768 * B + (128 << 16) + kHalf - 1) >> 16;
-      crv[j] = (32768 * R - 27439 * G - 5329 * B + (128 << 16) + kHalf - 1) >> 16;
+      yb[j] = ((19595 * R + 38470 * G + 7471 * B + kJpegHalf) >> 16) - 128;      // luma8(R, G, B) written out: through the helper this kernel came out 20 bytes shorter, and it is held to its size
+      cbv[j] = (-11059 * R - 21709 * G + 32768 * B + (128 << 16) + kJpegHalf - 1) >> 16;
+      crv[j] = (32768 * R - 27439 * G - 5329 * B + (128 << 16) + kJpegHalf - 1) >> 16;
     }
     hsum[0][r][xq >> 1] = cbv[0] + cbv[1]; hsum[0][r][(xq >> 1) + 1] = cbv[2] + cbv[3];
     hsum[1][r][xq >> 1] = crv[0] + crv[1]; hsum[1][r][(xq >> 1) + 1] = crv[2] + crv[3];
@@ -186,63 +150,13 @@ __global__ void __launch_bounds__(64) jpegmap_mcu_kernel(const vt_jpegmap_frame*
 __global__ void __launch_bounds__(kNT) jpegmap_upsample_kernel(const vt_jpegmap_frame* __restrict__ frames, const int flags,
                                                                const uint8_t* __restrict__ ws, uint8_t* __restrict__ out) {
   const vt_jpegmap_frame f = frames[blockIdx.y];
-  const PlaneGeom g = plane_geom(f.h, f.w);
-  const int ch = (f.h + 1) >> 1, cw = (f.w + 1) >> 1;
-  const int ipr = (cw + 1) >> 1;                     // items per chroma row: two chroma columns = four pixels each
-  const long it = (long)blockIdx.x * kNT + threadIdx.x;
-  if (it >= (long)ch * ipr) return;
-  const int j = (int)(it / ipr), i0 = (int)(it - (long)j * ipr) * 2;
-  const int cpitch = g.W16 >> 1;
-  const uint8_t* base = ws + f.ws_off;
-  const bool fancy = cw > 2;                         // jdsample.c: narrower components are replicated
-  const int jr[3] = {max(j - 1, 0), j, min(j + 1, ch - 1)};
-  int up[2][2][4];                                   // [Cb | Cr][row 2j + v][column 2 i0 + k]
-#pragma unroll
-  for (int c = 0; c < 2; ++c) {
-    const uint8_t* pl = base + (c ? g.cr : g.cb);
-    int C[3][4];                                     // rows j - 1, j, j + 1; columns i0 - 1 .. i0 + 2, all clamped into the ch x cw component
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-      for (int k = 0; k < 4; ++k) C[r][k] = pl[(long)jr[r] * cpitch + min(max(i0 - 1 + k, 0), cw - 1)];
-#pragma unroll
-    for (int v = 0; v < 2; ++v) {
-      int s[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) s[k] = 3 * C[1][k] + C[v ? 2 : 0][k];
-#pragma unroll
-      for (int q = 0; q < 2; ++q) {                  // chroma column i0 + q sits at C[.][q + 1]
-        up[c][v][2 * q] = fancy ? (3 * s[q + 1] + s[q] + 8) >> 4 : C[1][q + 1];
-        up[c][v][2 * q + 1] = fancy ? (3 * s[q + 1] + s[q + 2] + 7) >> 4 : C[1][q + 1];
-      }
-    }
-  }
-  const int x0 = i0 * 2, npx = min(4, f.w - x0);
-#pragma unroll
-  for (int v = 0; v < 2; ++v) {
-    const int y = 2 * j + v;
-    if (y >= f.h) break;
-    const uint32_t yw = *(const uint32_t*)(base + (long)y * g.W16 + x0);      // x0 is a multiple of 4 inside the padded plane
-    uint32_t px[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int Y = (yw >> (8 * k)) & 255, cb = up[0][v][k] - 128, cr = up[1][v][k] - 128;
-      int R = clip8(Y + ((91881 * cr + kHalf) >> 16));
-      const int G = clip8(Y + ((-22554 * cb + kHalf - 46802 * cr) >> 16));
-      int B = clip8(Y + ((116130 * cb + kHalf) >> 16));
-      if (flags & VT_JPEGMAP_CV2_ORDER) { const int t = R; R = B; B = t; }
-      px[k] = (uint32_t)R | ((uint32_t)G << 8) | ((uint32_t)B << 16);
-    }
-    store_px4(out + f.out_off + ((long)y * f.w + x0) * 3, px, npx);
-  }
+  jpeg_upsample_item(ws + f.ws_off, f.h, f.w, flags, (long)blockIdx.x * kNT + threadIdx.x, out + f.out_off);
 }
-
-constexpr int kMaxSide = 32768;
 
 // the checks of one record that both entry points make; 0 or VT_ERR_ARG with the message set
 int check_frame(const char* fn, const vt_jpegmap_frame& f, const int i) {
   CK(vt_frame_check(fn, f, i));
-  return (f.h > kMaxSide || f.w > kMaxSide) ? vt_fail(VT_ERR_ARG, "%s: frame %d of %d x %d is too large (at most %d a side)", fn, i, f.h, f.w, kMaxSide) : VT_OK;
+  return (f.h > kJpegMaxSide || f.w > kJpegMaxSide) ? vt_fail(VT_ERR_ARG, "%s: frame %d of %d x %d is too large (at most %d a side)", fn, i, f.h, f.w, kJpegMaxSide) : VT_OK;
 }
 inline size_t frame_ws_bytes(const vt_jpegmap_frame& f) {
   const PlaneGeom g = plane_geom(f.h, f.w);
@@ -274,7 +188,7 @@ extern "C" int vt_jpegmap(const vt_jpegmap_frame* frames_host, const void* frame
       return vt_fail(VT_ERR_ARG, "vt_jpegmap: frame %d: ws_off %ld is not the one vt_jpegmap_workspace_bytes writes", i, f.ws_off);
     const PlaneGeom g = plane_geom(f.h, f.w);
     const long mcus = (long)(g.H16 >> 4) * (g.W16 >> 4);
-    const long items = (long)((f.h + 1) >> 1) * ((((f.w + 1) >> 1) + 1) >> 1);
+    const long items = jpeg_upsample_items(f.h, f.w);
     max_mcus = mcus > max_mcus ? mcus : max_mcus;
     max_items = items > max_items ? items : max_items;
   }

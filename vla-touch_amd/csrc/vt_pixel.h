@@ -1,4 +1,4 @@
-// vt_pixel.h — the pixel idioms of the camera-frame kernels (vt_imgprep.hip, vt_colorjitter.hip, vt_jpegmap.hip), stated once: the byte clip,
+// vt_pixel.h — the pixel idioms of the camera-frame kernels (vt_imgprep.hip, vt_colorjitter.hip, vt_jpegmap.hip, vt_jpegdec.hip), stated once: the byte clip,
 // the brightness lift and its decision, the luma weights, four RGB pixels as three aligned words, and the per-block tail of an exact sum.
 // Integer arithmetic throughout, but for the lift decision: one quotient of products in double, no sum in it, so there is nothing a
 // floating-point contraction could fuse (vt_colorjitter.hip turns contraction off for its own expressions, behind its includes).

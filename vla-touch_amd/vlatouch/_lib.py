@@ -172,6 +172,7 @@ class JpegmapFrame(C.Structure):     # vt_jpegmap_frame
 
 
 JPEGMAP_CV2_ORDER = 1
+JPEG_K, JPEG_444, JPEG_420, JPEG_TABLESET_BYTES = 16, 0, 1, 6144       # vt_jpeg_index / vt_jpeg_decode: a table row is JPEG_K int64
 
 
 class CorruptFrame(C.Structure):     # vt_corrupt_frame (kind ids: vlatouch/imgaug.py)
@@ -348,6 +349,9 @@ SIGNATURES = {
     "vt_colorjitter": (_I, [_P, _P, _I, _I, _P, _P, _Z, _P]),
     "vt_jpegmap_workspace_bytes": (_Z, [_P, _I]),
     "vt_jpegmap": (_I, [_P, _P, _I, _I, _I, _P, _P, _Z, _P]),
+    "vt_jpeg_workspace_bytes": (_Z, [_P, _I]),
+    "vt_jpeg_index": (_I, [_P, _P, _I, _P, _P]),
+    "vt_jpeg_decode": (_I, [_P, _P, _I, _P, _P, _Z, _P, _P]),
     "vt_corrupt": (_I, [_P, _P, _I, _P, _P, C.c_long, _P, _P]),
     "vt_area_resize": (_I, [_P, _P, _I, _P, _P, _Z, _P]),
     "vt_rdt_batch": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, C.c_double, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P]),

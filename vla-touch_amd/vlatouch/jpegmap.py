@@ -13,7 +13,7 @@ align with training" (residual_controller/frank_inference_eef.py:84-87,131-132; 
 UNPINNED against cv2, which is not available where this was written: that `imencode('.jpg', a)` + `imdecode` is libjpeg with
 jpeg_set_defaults (quality 95, 4:2:0, islow DCT) and a default decompress (fancy up-sampling), the array read as BGR, rests on reading
 OpenCV's grfmt_jpeg.cpp.  The mapping is pinned to Pillow's libjpeg-turbo with the channel roles swapped.  Decoding stored JPEG files (the
-entropy coder) is not built.
+entropy coder in front of this file's inverse half) is vlatouch/jpegdec.py.
 """
 from __future__ import annotations
 

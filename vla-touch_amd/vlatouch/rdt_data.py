@@ -94,6 +94,15 @@ class SamplePlan:
                 f"elem {self.elem_masked}), frame_idx={self.frame_idx}, frame_valid={self.frame_valid}, noise={self.noise is not None})")
 
 
+class _JpegCamera:
+    """A camera's frames under frames="jpeg", on the host until upload(): the files' bytes and the one size and sampling they share."""
+    __slots__ = ("files", "shape", "sampling", "nbytes")
+
+    def __init__(self, files, h, w, sampling):
+        self.files, self.shape, self.sampling = files, (len(files), h, w, 3), sampling
+        self.nbytes = sum(len(f) for f in files)
+
+
 class _Episode:
     __slots__ = ("path", "qpos", "first_idx", "stats", "lang", "frames", "has_cam")      # frames: host arrays until upload() moves them
 
@@ -111,11 +120,20 @@ class EpisodeStore:
     frame it reads, data/unified_vla_dataset_episode.py:382-397): `upload` then resizes every camera frame once on the card
     (csrc/vt_area.hip), in chunks, and the store keeps the target x target frames, on the device or in pinned host memory as above;
     `max_device_bytes` counts the resized size, and `assemble` hands out the resized frames, so jitter and corruption act on them as
-    train/dataset.py does.  The stage precedes every random decision: `dataset_stat` and the draws are the same with and without it."""
+    train/dataset.py does.  The stage precedes every random decision: `dataset_stat` and the draws are the same with and without it.
+    frames="jpeg" reads episode files written by `convert_episode_to_hdf5(..., images="jpeg")` (a camera group holds `<camera>_jpeg` and
+    `<camera>_jpeg_offsets`) and keeps every camera as JPEG bitstreams in HBM, one `vlatouch.jpegdec.JpegFrames` per episode and camera;
+    all frames of a camera must share size and sampling.  `assemble` decodes exactly the frames its plans mark valid, in one vt_jpeg_decode
+    call per micro-batch (csrc/vt_jpegdec.hip, bit-identical to the Pillow decode the other modes store), and hands out views of that
+    buffer; with pad_and_resize the decoded frames go through `pad_and_resize_device` in the same call (decoded at full size, resized per
+    batch).  `max_device_bytes` counts the compressed size, and there is no pinned-host spill in this mode: an episode past the cap raises.
+    jpeg_index_interval: the `index_interval` of the `JpegFrames`.  Everything that works without a GPU is the same as for a store of the
+    decoded files."""
 
     def __init__(self, paths_or_dir, *, dataset_name: str, dataset_names: Sequence[str], control_freq, horizon: int = 64, img_history_size: int = 2,
                  state_dim: int = 128, state_indices: Optional[Sequence[int]] = None, cameras: Sequence[Optional[str]] = ("camera1", "camera2", None),
-                 device="cuda", frames: str = "device", max_device_bytes: Optional[int] = None, pad_and_resize: Optional[int] = None):
+                 device="cuda", frames: str = "device", max_device_bytes: Optional[int] = None, pad_and_resize: Optional[int] = None,
+                 jpeg_index_interval=None):
         if int(horizon) != horizon or horizon < 4:
             raise ValueError(f"EpisodeStore: horizon must be an integer >= 4, got {horizon!r} (below 4 the last drawable step has an empty action chunk)")
         if int(img_history_size) != img_history_size or img_history_size < 1:
@@ -123,8 +141,9 @@ class EpisodeStore:
         idx = tuple(int(i) for i in (DEFAULT_STATE_INDICES if state_indices is None else state_indices))
         if len(idx) != 10 or len(set(idx)) != 10 or min(idx) < 0 or max(idx) >= state_dim:
             raise ValueError(f"EpisodeStore: state_indices must be 10 distinct columns of the {state_dim}-wide unified vector, got {idx}")
-        if frames not in ("device", "host"):
-            raise ValueError(f"EpisodeStore: frames must be 'device' or 'host', got {frames!r}")
+        if frames not in ("device", "host", "jpeg"):
+            raise ValueError(f"EpisodeStore: frames must be 'device', 'host' or 'jpeg', got {frames!r}")
+        self.jpeg_index_interval = jpeg_index_interval
         if max_device_bytes is not None and max_device_bytes < 0:
             raise ValueError("EpisodeStore: max_device_bytes must be >= 0")
         if pad_and_resize is not None and (isinstance(pad_and_resize, bool) or int(pad_and_resize) != pad_and_resize or pad_and_resize < 1):
@@ -167,9 +186,14 @@ class EpisodeStore:
             return None
         node = f[key]
         if isinstance(node, h5lite.Group):
+            if self.frames_mode == "jpeg":
+                return self._jpeg_camera(node, key)
             if key not in node:
                 return None
             node = node[key]
+        if self.frames_mode == "jpeg":
+            raise ValueError(f"EpisodeStore: frames='jpeg' needs camera {key!r} as a group holding {key}_jpeg and {key}_jpeg_offsets "
+                             "(convert_episode_to_hdf5(..., images='jpeg'))")
         a = np.asarray(node[...])
         if a.dtype != np.uint8 or a.ndim != 4 or a.shape[3] != 3:
             raise ValueError(f"EpisodeStore: camera {key!r} must be uint8 [N, H, W, 3], got {a.dtype} {a.shape}")
@@ -177,6 +201,28 @@ class EpisodeStore:
             from .imgprep import area_scale
             area_scale(max(a.shape[1], a.shape[2]), self.pad_and_resize)      # refuses, by name, a frame smaller than the target
         return a
+
+    def _jpeg_camera(self, group, key):
+        """The two datasets `convert_episode_to_hdf5(..., images="jpeg")` writes -> a `_JpegCamera`; headers are parsed, nothing is decoded."""
+        from .jpegdec import SAMPLING_NAMES, parse_jpeg
+        if f"{key}_jpeg" not in group or f"{key}_jpeg_offsets" not in group:
+            if key in group:
+                raise ValueError(f"EpisodeStore: camera {key!r} holds decoded pixels; frames='jpeg' reads files converted with images='jpeg'")
+            return None
+        data, off = np.asarray(group[f"{key}_jpeg"][...]), np.asarray(group[f"{key}_jpeg_offsets"][...])
+        if data.dtype != np.uint8 or data.ndim != 1 or off.dtype != np.int64 or off.ndim != 1 or len(off) < 2 or off[0] != 0 or \
+                off[-1] != len(data) or np.any(np.diff(off) <= 0):
+            raise ValueError(f"EpisodeStore: camera {key!r}: {key}_jpeg must be uint8 [bytes] and {key}_jpeg_offsets int64 [N + 1], rising from 0 to its length")
+        files = [data[off[k]:off[k + 1]].tobytes() for k in range(len(off) - 1)]
+        kinds = {(r.h, r.w, r.sampling) for r in (parse_jpeg(f, k, header_only=True) for k, f in enumerate(files))}
+        if len(kinds) > 1:
+            raise ValueError(f"EpisodeStore: camera {key!r}: its frames differ in size or sampling: "
+                             f"{sorted((h, w, SAMPLING_NAMES[s]) for h, w, s in kinds)}")
+        (h, w, samp), = kinds
+        if self.pad_and_resize is not None:
+            from .imgprep import area_scale
+            area_scale(max(h, w), self.pad_and_resize)
+        return _JpegCamera(files, h, w, samp)
 
     def _load(self, path: str) -> None:
         with h5lite.File(path) as f:
@@ -358,6 +404,10 @@ class EpisodeStore:
             "lang_off": i32(np.concatenate([[0], np.cumsum([e.lang.shape[0] for e in eps])])),
         }
         self.resident_bytes = sum(t.numel() * t.element_size() for t in d.values())
+        if self.frames_mode == "jpeg":
+            d["frames"] = self._upload_jpeg(dev)
+            self._dev = d
+            return self
         budget = 0 if self.frames_mode == "host" else self.max_device_bytes
         frames = []
         T = self.pad_and_resize
@@ -396,6 +446,48 @@ class EpisodeStore:
         self._dev = d
         return self
 
+    def _upload_jpeg(self, dev) -> list:
+        """One `JpegFrames` per episode and camera; resident_bytes counts what each keeps (streams + index + tables)."""
+        from .jpegdec import DEFAULT_INDEX_INTERVAL, JpegFrames
+        iv = DEFAULT_INDEX_INTERVAL if self.jpeg_index_interval is None else self.jpeg_index_interval
+        frames, used = [], 0
+        for k, e in enumerate(self.episodes):
+            per_cam = []
+            for c, a in zip(self.cameras, e.frames):
+                if a is None:
+                    per_cam.append(None)
+                    continue
+                try:
+                    jf = JpegFrames(a.files, dev, iv)
+                except ValueError as err:
+                    raise ValueError(f"EpisodeStore: {os.path.basename(e.path)}, camera {c!r}: {err}") from None
+                used += jf.nbytes
+                if self.max_device_bytes is not None and used > self.max_device_bytes:
+                    raise ValueError(f"EpisodeStore: episode {k} ({os.path.basename(e.path)}) brings the compressed frames to {used} bytes, past "
+                                     f"max_device_bytes = {self.max_device_bytes}; frames='jpeg' has no pinned-host spill")
+                per_cam.append(jf)
+            frames.append(per_cam)
+            e.frames = None
+        self.resident_bytes += used
+        return frames
+
+    def _decoded_frames(self, plans) -> list:
+        """frames="jpeg": the frames the plans mark valid, decoded in one vt_jpeg_decode call (and resized in one vt_area_resize call under
+        pad_and_resize) -> B lists of hist * cameras entries, views of that call's buffer or None."""
+        from .jpegdec import decode_many
+        ncam, jfs = len(self.cameras), self._dev["frames"]
+        where = [(k, q) for k, p in enumerate(plans) for q, v in enumerate(p.frame_valid) if v]
+        res = [[None] * len(p.frame_valid) for p in plans]
+        if not where:
+            return res
+        got = decode_many([(jfs[plans[k].episode][q % ncam], plans[k].frame_idx[q // ncam]) for k, q in where])
+        if self.pad_and_resize is not None:
+            from .imgprep import pad_and_resize_device
+            got = pad_and_resize_device(got, self.pad_and_resize)
+        for (k, q), t in zip(where, got):
+            res[k][q] = t
+        return res
+
     @staticmethod
     def _resized(a: np.ndarray, T: int, dev, on_dev: bool) -> torch.Tensor:
         """`pad_and_resize_for_siglip` of a camera's frames [N, H, W, 3] on the card, in chunks of at most 64 MiB of raw frames -> uint8
@@ -414,8 +506,8 @@ class EpisodeStore:
     def assemble(self, plans: Sequence[SamplePlan]) -> dict:
         """plans -> the collator's mapping on the device: states [B, 1, A], actions [B, H, A], state_elem_mask [B, A], state_norm [B, A] (fp32),
         ctrl_freqs [B] int64, data_indices (list), lang_embeds [B, Lmax, D] zero padded, lang_attn_mask [B, Lmax] bool, frames (B lists of
-        hist * cameras entries, slot-major: a uint8 [H, W, 3] view into the resident episode, a host array for an episode kept in pinned
-        memory, or None for the background), jitter (B lists, or None when no plan carries any) and, where a plan carries any, corrupt."""
+        hist * cameras entries, slot-major: a uint8 [H, W, 3] view into the resident episode (frames="jpeg": into the buffer this call
+        decoded), a host array for an episode kept in pinned memory, or None for the background), jitter (B lists, or None when no plan carries any) and, where a plan carries any, corrupt."""
         plans = list(plans)
         self.check_plans(plans)
         snr = next((p.noise_snr for p in plans if p.noise is not None), None)
@@ -443,7 +535,7 @@ class EpisodeStore:
                                      L.stream_ptr(dev)), "vt_rdt_batch")
         ncam = len(self.cameras)
         out["data_indices"] = [self.data_idx] * B
-        out["frames"] = [[d["frames"][p.episode][q % ncam][p.frame_idx[q // ncam]] if v else None for q, v in enumerate(p.frame_valid)] for p in plans]
+        out["frames"] = self._decoded_frames(plans) if self.frames_mode == "jpeg" else [[d["frames"][p.episode][q % ncam][p.frame_idx[q // ncam]] if v else None for q, v in enumerate(p.frame_valid)] for p in plans]
         out["jitter"] = [list(p.jitter) for p in plans] if any(j is not None for p in plans for j in p.jitter) else None
         if any(c is not None for p in plans for c in p.corrupt):
             out["corrupt"] = [list(p.corrupt) for p in plans]
