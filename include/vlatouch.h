@@ -190,6 +190,14 @@ typedef struct {
   int mlp_dim;       /* 0: 4*hidden; else the (64-padded) FFN width */
   int out_all;       /* 0: out = [ncams][B][hidden] CLS rows; 1: out = [ncams][B][tokens][hidden] */
   float attn_scale;  /* 0: head_dim^-0.5 */
+  /* CLIP vision tower with deep visual prompts (Octopi's tactile encoder; all 0 = the variants above).  With act = 7 (VT_ACT_QUICK_GELU),
+   * ones for the two LayerScale slots and a zero patch bias this is HF CLIPVisionTransformer; out_all = 0 gives pooler_output. */
+  int pre_ln;        /* 1: LayerNorm of every embedded row (CLIP pre_layrnorm) before block 0; two weights (gain, bias) follow the final norm's */
+  int n_prompt;      /* n_ctx learnable prompt rows appended after the patch tokens of every image (needs a CLS token) */
+  int prompt_depth;  /* P: blocks 0 .. P-1 see the prompt rows, block P drops them; -1 = every block; 0 = no prompts (n_prompt is ignored).
+                        Weights after the pre_ln pair when P != 0 and n_prompt > 0: VPT [n][hidden] fp32, VPT_shallow_i [n][hidden] fp32 for
+                        1 <= i < P, then ONE fp32 array [layers] of the gates sigmoid(VPT_gamma_i) at index i (only 1 <= i < P, i != last are read) */
+  int image_size;    /* != 0: vt_dino_forward / vt_dino_embed refuse any other `res` (CLIP's position table is never interpolated) */
 } vt_dino_desc;
 int vt_dino_create(const vt_dino_desc* desc, const void* const* weights, int n_weights, vt_dino_t* out);
 void vt_dino_destroy(vt_dino_t h);
@@ -214,10 +222,42 @@ int vt_dino_forward(vt_dino_t h, const void* const* imgs, int ncams, int is_u8, 
                     void* workspace, vt_stream_t stream);
 /* The front end of vt_dino_forward alone, through the same code: statistics, patchify, patch-embed GEMM + position embedding, CLS row.
  * Same image arguments and workspace (vt_dino_workspace_bytes); tokens: [ncams*B][tokens][hidden] fp32, the residual stream as the first
- * block receives it, written straight into the caller's buffer; flags_out as above. */
+ * block receives it, written straight into the caller's buffer; flags_out as above.  For a CLIP handle `tokens` counts the prompt rows too:
+ * 1 + grid^2 + n_prompt rows per image when prompt_depth != 0 (VPT after the patch rows), every row after pre_layrnorm. */
 int vt_dino_embed(vt_dino_t h, const void* const* imgs, int ncams, int is_u8, int nhwc, float pre_scale,
                   int norm_mode, int B, int res, const float* pos_patch, float* tokens, float* flags_out,
                   void* workspace, vt_stream_t stream);
+
+/* ---------------------------------------------------------------- deep visual prompts of the CLIP tower (csrc/vt_prompt_seam.hip)
+ * The two launches vt_dino_forward issues between blocks when n_prompt > 0, as entries (tests call them alone).  Replaces the prompt steps
+ * of PromptLearningCLIPEncoderLayer.forward (octopi_s/utils/encoder.py:59-91, 108-124), vision branch.
+ * vt_prompt_seam: on the last n rows of each of the Bt images of the fp32 residual stream tok [Bt][rows][D], per element and in this order:
+ *   gate  (gate != null):    v = g * v + (1 - g) * before, g = *gate (DEVICE fp32 scalar), each product and the sum rounded to fp32;
+ *   save  (save != 0):       before = v;
+ *   overwrite (shallow != null): v = shallow [n][D];
+ * `before` is [Bt][n][D] fp32 and must be given when gate or save is.  Rows outside the tail are neither read nor written.
+ * tok, before and shallow are read and written as 16-byte vectors: they must be 16-byte aligned (as must src and dst of vt_prompt_compact).
+ * Refused (-22) before any launch: null tok, Bt / n / D < 1, n > rows, D % 4, gate or save without before, nothing to do, a misaligned pointer.
+ * vt_prompt_compact: [Bt][rows][D] -> [Bt][rows - n][D], the last n rows of every image dropped.  dst == src works in place (one workgroup
+ * walks the images front to back); otherwise the two buffers must not overlap.  Refused (-22): null pointer, Bt / D < 1, n < 1, n >= rows, D % 4, a misaligned pointer. */
+int vt_prompt_seam(float* tok, int Bt, int rows, int n, int D, const float* gate, float* before, int save, const float* shallow,
+                   vt_stream_t stream);
+int vt_prompt_compact(const float* src, float* dst, int Bt, int rows, int n, int D, vt_stream_t stream);
+
+/* ---------------------------------------------------------------- tactile video heads (csrc/vt_tactile_head.hip)
+ * Replaces ViFiCLIP.forward's video feature (encoder.py:401-411: mean over the l frames, then / L2 norm, no eps) and the retrieval of
+ * dataset.py:189-195 (nn.CosineSimilarity(dim=1, eps=1e-8) of a saved bank against it, then torch.topk), batched over b videos that all
+ * use the same bank.  pooled [b][l][D] fp32; video [b][D] fp32.  With bank != null ([R][D] fp32; bank_norm [R] fp32 = its rows' L2 norms,
+ * vt_tactile_bank_norms): sims [b][R] fp32 = bank_r . video / (max(|bank_r|, 1e-8) * max(|video|, 1e-8)), and with k > 0 topk_idx int32
+ * [b][k] / topk_val fp32 [b][k], the k largest similarities of each video in descending order; TIES GO TO THE LOWER INDEX.  Every sum is
+ * taken in fp32 in an order that depends on l, D and R only, so a video's results do not depend on b.  A video whose mean feature is zero
+ * has NaN for its feature and similarities (the reference divides without an eps); its top-k then lists the lowest indices 0 .. k-1 with NaN
+ * values, always valid indices.  bank and video are read as 16-byte vectors and must be 16-byte aligned.
+ * Refused (-22) before any launch: null pooled / video, b / l / D < 1, D % 4, a bank without bank_norm or sims, R < 1, k < 0, k > R, k > 16,
+ * k > 0 without topk_idx / topk_val, a misaligned bank or video. */
+int vt_tactile_bank_norms(const float* bank, int R, int D, float* bank_norm, vt_stream_t stream);
+int vt_tactile_head(const float* pooled, int b, int l, int D, const float* bank, const float* bank_norm, int R, int k,
+                    float* video, float* sims, int* topk_idx, float* topk_val, vt_stream_t stream);
 
 /* ---------------------------------------------------------------- T5 v1.1 text encoder (csrc/vt_t5.hip)
  * Replaces HF T5EncoderModel (feed_forward_proj "gated-gelu") of models/multimodal_encoder/t5_encoder.py::T5Embedder, used by

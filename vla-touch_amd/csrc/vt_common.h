@@ -34,7 +34,8 @@ typedef __attribute__((address_space(3))) short4_t lds_short4_t;
 enum { VT_F32 = 0, VT_BF16 = 1, VT_F32X3 = 2, VT_F16 = 3 };
 enum { VT_ACT_NONE = 0, VT_ACT_GELU_ERF = 1, VT_ACT_GELU_TANH = 2, VT_ACT_SILU = 3, VT_ACT_MISH = 4,
        VT_ACT_SWIGLU = 5,      // not an element-wise epilogue: a ViT FFN form (vt_dino_desc.act): fc1 -> [x1 | x2], silu(x1) * x2, fc2 (HF Dinov2SwiGLUFFN)
-       VT_ACT_GEGLU = 6 };     // likewise, the T5 v1.1 gated-gelu FFN (vt_t5.hip): wi_0 | wi_1 -> gelu_tanh(a) * b, wo (HF T5DenseGatedActDense)
+       VT_ACT_GEGLU = 6,       // likewise, the T5 v1.1 gated-gelu FFN (vt_t5.hip): wi_0 | wi_1 -> gelu_tanh(a) * b, wo (HF T5DenseGatedActDense)
+       VT_ACT_QUICK_GELU = 7 };   // element-wise: x * sigmoid(1.702 x) (HF "quick_gelu", the CLIP towers)
 
 __device__ __forceinline__ float bf2f(bf16_t h) { return __uint_as_float(((uint32_t)h) << 16); }
 typedef __attribute__((ext_vector_type(2))) float float2_t;
@@ -185,6 +186,7 @@ __device__ __forceinline__ float act_apply(float x, int act) {
       return x * __builtin_amdgcn_rcpf(1.0f + fast_exp(-u2));
     }
     case VT_ACT_SILU: return x * __builtin_amdgcn_rcpf(1.0f + fast_exp(-x));
+    case VT_ACT_QUICK_GELU: return x * __builtin_amdgcn_rcpf(1.0f + fast_exp(-1.702f * x));
     case VT_ACT_MISH: {
       // x tanh(log(1 + e^x)) == x w / (w + 2), w = e^x (e^x + 2)   (tanh(log s) = (s^2 - 1) / (s^2 + 1), s = 1 + e^x)
       if (x > 20.0f) return x;

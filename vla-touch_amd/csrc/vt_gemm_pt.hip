@@ -579,7 +579,7 @@ bool vt_gemm_pt_fits(const VtGemmParams& p) {
   if (p.cmap == 3) return (p.a_dtype == VT_BF16 || p.a_dtype == VT_F16) && (p.N % 512) == 0 && p.hn_c0_end == (p.N >> 1) && !p.hn_w1 && p.act == VT_ACT_NONE && p.hn_w0;
   if (p.cmap != 0 || p.hn_w0 || p.hn_w1) return false;
   if ((long)p.ldc * 2 * 128 >= (1L << 31)) return false;
-  return p.act == VT_ACT_NONE || p.act == VT_ACT_GELU_ERF || p.act == VT_ACT_GELU_TANH;
+  return p.act == VT_ACT_NONE || p.act == VT_ACT_GELU_ERF || p.act == VT_ACT_GELU_TANH || p.act == VT_ACT_QUICK_GELU;
 }
 
 // One round of 160 .. 256 tiles at K >= 512 (DINOv2-B out-projection: 64 x 3 tiles, K = 768): too short for gemm_pp256d_kernel to beat the 128-column
@@ -621,6 +621,7 @@ int vt_gemm_pt_launch(const VtGemmParams& p, hipStream_t s) {
     VT_DISPATCH_A16(p, T16,
       if (p.act == VT_ACT_NONE) VT_PT_GO(T16, KIND_P16, VT_ACT_NONE);
       else if (p.act == VT_ACT_GELU_ERF) VT_PT_GO(T16, KIND_P16, VT_ACT_GELU_ERF);
+      else if (p.act == VT_ACT_QUICK_GELU) VT_PT_GO(T16, KIND_P16, VT_ACT_QUICK_GELU);
       else VT_PT_GO(T16, KIND_P16, VT_ACT_GELU_TANH))
   }
 #undef VT_PT_GO

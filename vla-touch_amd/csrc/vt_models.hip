@@ -6,6 +6,8 @@
 //                           ln2_w ln2_b  fc1_w [4D][D] cdt  fc1_b  fc2_w [D][4D] cdt  fc2_b  ls2
 //                           (act = VT_ACT_SWIGLU, dinov2-giant: fc1_w = weights_in [2F][D], fc2_w = weights_out [D][F], F = mlp_dim)
 //   then  lnf_w  lnf_b
+//   CLIP (vt_dino_desc.pre_ln / n_prompt / prompt_depth, include/vlatouch.h), appended:  pre_w pre_b (pre_ln);  VPT [n][D], VPT_shallow_i [n][D] for
+//   1 <= i < P, gates [layers] = sigmoid(VPT_gamma_i) (n_prompt > 0 and P != 0), all fp32
 // The residual stream (tokens) is kept in fp32; normalised activations / QKV / MLP hidden are `adt`.
 //
 // (The LSTM residual head is one persistent kernel: vt_lstm.hip.)
@@ -28,10 +30,18 @@ struct vt_dino_s {
   vt_dino_desc d;
   const void* patch_w; const float *patch_b, *cls_pos0, *lnf_w, *lnf_b;
   DinoLayer L[48];
+  // CLIP with deep visual prompts: pre_layrnorm, VPT, VPT_shallow_i (1 <= i < P), the gates
+  const float *pre_w = nullptr, *pre_b = nullptr, *vpt = nullptr, *gates = nullptr;
+  const float* shallow[48] = {};
   unsigned* range_flag = nullptr;      // range guard word (vt_dino_set_range_flag)
 };
 
-int vt_dino_num_weights(const vt_dino_desc* d) { return 3 + 14 * d->layers + 2; }
+// prompt depth P (blocks 0 .. P-1 carry the prompt rows; -1 = all) and the number of prompt rows in the stream (0 when P == 0)
+static int dino_depth(const vt_dino_desc& d) { return d.n_prompt > 0 ? (d.prompt_depth < 0 ? d.layers : d.prompt_depth) : 0; }
+static int dino_nprompt(const vt_dino_desc& d) { return dino_depth(d) > 0 ? d.n_prompt : 0; }
+int vt_dino_num_weights(const vt_dino_desc* d) {
+  return 3 + 14 * d->layers + 2 + (d->pre_ln ? 2 : 0) + (dino_nprompt(*d) ? 1 + (dino_depth(*d) - 1) + 1 : 0);
+}
 int vt_dino_set_range_flag(vt_dino_t h, unsigned* word) {
   if (!h) return vt_fail(VT_ERR_ARG, "vt_dino_set_range_flag: null handle");
   h->range_flag = word;
@@ -45,6 +55,9 @@ int vt_dino_create(const vt_dino_desc* desc, const void* const* w, int n, vt_din
   if (d.layers < 1 || d.layers > 48 || d.hidden % 64 || (hd != 64 && hd != 96 && !(hd == 80 && d.adt != VT_F32)) || (hd == 64 && d.hidden / d.heads != 64) || d.patch != 14 ||
       d.kpad % 16 || d.kpad < 588 || (d.mlp_dim % 16))
     return vt_fail(VT_ERR_ARG, "vt_dino_create: unsupported config (head_dim 64 / 96, or 80 in a 16-bit mode; patch 14)");
+  if (d.n_prompt < 0 || d.prompt_depth < -1 || d.prompt_depth > d.layers || d.image_size < 0 || (d.image_size && d.image_size < d.patch))
+    return vt_fail(VT_ERR_ARG, "vt_dino_create: n_prompt >= 0, -1 <= prompt_depth <= layers and image_size 0 or >= patch are required");
+  if (d.n_prompt > 0 && d.no_cls) return vt_fail(VT_ERR_ARG, "vt_dino_create: prompt rows need a CLS token (n_prompt with no_cls)");
   VtWeights W;
   CK(W.open("vt_dino_create", w, n, vt_dino_num_weights(desc)));
   vt_dino_s* h = new (std::nothrow) vt_dino_s();
@@ -59,6 +72,12 @@ int vt_dino_create(const vt_dino_desc* desc, const void* const* w, int n, vt_din
     L.fc2_w = W.next(); L.fc2_b = W.next_f32(); L.ls2 = W.next_f32();
   }
   h->lnf_w = W.next_f32(); h->lnf_b = W.next_f32();
+  if (d.pre_ln) { h->pre_w = W.next_f32(); h->pre_b = W.next_f32(); }
+  if (dino_nprompt(d)) {
+    h->vpt = W.next_f32();
+    for (int l = 1; l < dino_depth(d); ++l) h->shallow[l] = W.next_f32();
+    h->gates = W.next_f32();
+  }
   *out = h;
   return VT_OK;
 }
@@ -93,10 +112,10 @@ int vt_dino_set_packed(vt_dino_t h, void* buf, vt_stream_t stream) {
 
 namespace {
 constexpr int DINO_SPLITK = 4, DINO_SPLIT_ROWS = 1100;
-struct DWs { size_t part, flags, apatch, tok, xn, qkv, att, h1, slab, slab_bytes, total; };
+struct DWs { size_t part, flags, apatch, tok, xn, qkv, att, h1, slab, slab_bytes, tok2, before, total; };
 DWs dcarve(const vt_dino_s* h, int Bt, int res) {
   const vt_dino_desc& d = h->d;
-  const int a = vt_dt_bytes(d.adt), g = res / d.patch, N = g * g + (d.no_cls ? 0 : 1), D = d.hidden;
+  const int a = vt_dt_bytes(d.adt), g = res / d.patch, n = dino_nprompt(d), N = g * g + (d.no_cls ? 0 : 1) + n, D = d.hidden;      // N: with the prompt rows
   const int Da = d.heads * (d.head_dim ? d.head_dim : 64), Dm = d.mlp_dim ? d.mlp_dim : 4 * D;
   DWs w; VtCarver cv;
   w.part = cv.take(512 * 4 * 8); w.flags = cv.take(8 * 4 * 8);
@@ -109,6 +128,11 @@ DWs dcarve(const vt_dino_s* h, int Bt, int res) {
   // split-K scratch of fc2 at a few images (batch 1 of the robot loop: 2 x 257 rows): DINO_SPLITK fp32 slabs of [rows][D]
   w.slab_bytes = (size_t)Bt * N <= DINO_SPLIT_ROWS ? (size_t)DINO_SPLITK * Bt * N * D * 4 : 0;
   w.slab = cv.take(w.slab_bytes);
+  // CLIP: a second residual stream (the embedded rows before pre_layrnorm; the compacted stream when block P drops the prompt rows) and the
+  // prompt rows as the gated block received them
+  w.tok2 = w.before = 0;
+  if (d.pre_ln || n) w.tok2 = cv.take((size_t)Bt * N * D * 4);
+  if (n) w.before = cv.take((size_t)Bt * n * D * 4);
   w.total = cv.o;
   return w;
 }
@@ -123,6 +147,9 @@ int dino_embed_steps(const vt_dino_s* h, const void* const* imgs, int ncams, int
                      const float* pos_patch, float* tok, float* flags_out, char* ws, const DWs& w, hipStream_t s) {
   const vt_dino_desc& d = h->d;
   const int g = res / d.patch, np = g * g, cls = d.no_cls ? 0 : 1, N = np + cls, D = d.hidden, Bt = ncams * B, a = vt_dt_bytes(d.adt);
+  const int n = dino_nprompt(d), Nt = N + n;                      // rows per image with the prompt rows
+  float* const dst = tok;
+  if (d.pre_ln) tok = (float*)(ws + w.tok2);                       // CLIP: the embedded rows go through pre_layrnorm into `dst`
   // 1. per-camera statistics -> branch flags; patchify with the camera's own decision
   for (int c = 0; c < ncams; ++c) {
     float* part = (float*)(ws + w.part) + c * 512;
@@ -133,10 +160,12 @@ int dino_embed_steps(const vt_dino_s* h, const void* const* imgs, int ncams, int
   }
   // 2. patch-embed GEMM, one group per image, + position embedding (shared residual) -> fp32 tokens rows 1..np
   VtGemmParams p = vt_linear(ws + w.apatch, d.adt, d.kpad, h->patch_w, d.cdt, d.kpad, h->patch_b, tok + (size_t)cls * D, VT_F32, D, np, D, d.kpad, VT_ACT_NONE);
-  p.groups = Bt; p.a_gs = (long)np * d.kpad; p.w_gs = 0; p.c_gs = (long)N * D; p.bias_gs = 0;
+  p.groups = Bt; p.a_gs = (long)np * d.kpad; p.w_gs = 0; p.c_gs = (long)Nt * D; p.bias_gs = 0;
   p.residual = pos_patch; p.ldr = D; p.r_gs = 0;
   CK(vt_wrap(vt_gemm_launch(p, s), "dino patch embed"));
-  if (cls) CK(vt_k_bcast_row(h->cls_pos0, tok, (long)N * D, Bt, D, s));
+  if (cls) CK(vt_k_bcast_row(h->cls_pos0, tok, (long)Nt * D, Bt, D, s));
+  if (n) CK(vt_k_bcast_row(h->vpt, tok + (size_t)N * D, (long)Nt * D, Bt, n * D, s));      // VPT after the patch tokens of every image
+  if (d.pre_ln) CK(vt_k_rownorm(tok, VT_F32, D, dst, VT_F32, D, h->pre_w, h->pre_b, Bt * Nt, D, d.eps, VT_NORM_LAYER, s));
   return VT_OK;
 }
 }  // namespace
@@ -145,6 +174,7 @@ int vt_dino_embed(vt_dino_t h, const void* const* imgs, int ncams, int is_u8, in
                   const float* pos_patch, float* tokens, float* flags_out, void* workspace, vt_stream_t stream) {
   if (!h || !imgs || !pos_patch || !tokens || !workspace) return vt_fail(VT_ERR_ARG, "vt_dino_embed: null argument");
   if (ncams < 1 || ncams > 8 || B < 1 || res < 14) return vt_fail(VT_ERR_ARG, "vt_dino_embed: bad sizes");
+  if (h->d.image_size && res != h->d.image_size) return vt_fail(VT_ERR_ARG, "vt_dino_embed: res %d is not the tower's image_size %d", res, h->d.image_size);
   for (int c = 0; c < ncams; ++c)
     if (!imgs[c]) return vt_fail(VT_ERR_ARG, "vt_dino_embed: null camera pointer");
   return dino_embed_steps(h, imgs, ncams, is_u8, nhwc, pre_scale, norm_mode, B, res, pos_patch, tokens, flags_out, (char*)workspace,
@@ -156,8 +186,11 @@ int vt_dino_forward(vt_dino_t h, const void* const* imgs, int ncams, int is_u8, 
   if (!h || !imgs || !pos_patch || !out || !workspace) return vt_fail(VT_ERR_ARG, "vt_dino_forward: null argument");
   if (ncams < 1 || ncams > 8 || B < 1 || res < 14) return vt_fail(VT_ERR_ARG, "vt_dino_forward: bad sizes");
   const vt_dino_desc& d = h->d;
+  if (d.image_size && res != d.image_size) return vt_fail(VT_ERR_ARG, "vt_dino_forward: res %d is not the tower's image_size %d", res, d.image_size);
   hipStream_t s = (hipStream_t)stream;
-  const int g = res / d.patch, np = g * g, cls = d.no_cls ? 0 : 1, N = np + cls, D = d.hidden, Bt = ncams * B, a = vt_dt_bytes(d.adt);
+  const int g = res / d.patch, np = g * g, cls = d.no_cls ? 0 : 1, D = d.hidden, Bt = ncams * B, a = vt_dt_bytes(d.adt);
+  const int n_pr = dino_nprompt(d), P = dino_depth(d), N0 = np + cls;      // N0: rows per image without the prompt rows
+  int N = N0 + n_pr;                                                       // rows per image now: block P drops the prompt rows
   const int hd = d.head_dim ? d.head_dim : 64, Da = d.heads * hd, Dm = d.mlp_dim ? d.mlp_dim : 4 * D;
   const int act = d.act ? d.act : VT_ACT_GELU_ERF;
   const float scale = d.attn_scale > 0.f ? d.attn_scale : 1.0f / sqrtf((float)hd);
@@ -166,7 +199,7 @@ int vt_dino_forward(vt_dino_t h, const void* const* imgs, int ncams, int is_u8, 
   float* tok = (float*)(ws + w.tok);
   // 1., 2. statistics, patchify, patch embed + position embedding, CLS row
   CK(dino_embed_steps(h, imgs, ncams, is_u8, nhwc, pre_scale, norm_mode, B, res, pos_patch, tok, flags_out, ws, w, s));
-  const int M = Bt * N;
+  int M = Bt * N;
   // The reference consumes only pooler_output = the CLS row of the last layer (visual_encoder.py:88-93): in the LAST block every token still feeds
   // K and V, but only the CLS row needs a query, the output projection, the MLP and the residual updates (SURVEY 2.1 "last layer prunes to the CLS
   // query").
@@ -199,6 +232,18 @@ int vt_dino_forward(vt_dino_t h, const void* const* imgs, int ncams, int is_u8, 
   for (int l = 0; l < d.layers; ++l) {
     const DinoLayer& L = h->L[l];
     const bool cls_only = cls && !d.out_all && l == d.layers - 1;
+    if (n_pr && l >= 1 && l < P) {
+      // between block l-1 and block l: the gate of block l-1 (it overwrote, and it is not the last: l-1 >= 1), `before` for block l's own gate
+      // (l is not the last), the rows block l sees
+      const bool gate = l - 1 >= 1, save = l != d.layers - 1;
+      CK(vt_wrap(vt_prompt_seam(tok, Bt, N, n_pr, D, gate ? h->gates + (l - 1) : nullptr, (float*)(ws + w.before), save, h->shallow[l], s), "dino prompt seam"));
+    } else if (n_pr && l == P) {
+      // block P drops the prompt rows (a gate of block P-1 would only touch them): compact into the second stream and go on there
+      float* t2 = (float*)(ws + w.tok2);
+      if (t2 == tok) t2 = (float*)(ws + w.tok);
+      CK(vt_wrap(vt_prompt_compact(tok, t2, Bt, N, n_pr, D, s), "dino prompt drop"));
+      tok = t2; N = N0; M = Bt * N;
+    }
     CK(vt_k_rownorm(tok, VT_F32, D, ws + w.xn, d.adt, D, L.ln1_w, L.ln1_b, M, D, d.eps, VT_NORM_LAYER, s));
     if (cls_only) {
       const long tstride = (long)N * D;                 // CLS row of image b = row b * N of the token matrix

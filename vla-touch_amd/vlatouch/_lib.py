@@ -40,6 +40,7 @@ def range_names(bits: int):
 
 F32, BF16, F32X3, F16 = 0, 1, 2, 3   # F32X3: fp32 storage, split-bf16 3-MFMA compute (GEMM weights only); F16: IEEE half
 ACT_NONE, ACT_GELU_ERF, ACT_GELU_TANH, ACT_SILU, ACT_MISH, ACT_SWIGLU, ACT_GEGLU = 0, 1, 2, 3, 4, 5, 6
+ACT_QUICK_GELU = 7                    # x * sigmoid(1.702 x): the CLIP towers (csrc/vt_common.h)
 # vt_gemm_route_of (include/vlatouch.h, VT_ROUTE_*)
 ROUTE_NAMES = ("UNSUPPORTED", "BAD_ARG", "REG", "F32R", "GLDS", "PP", "PT", "PPK", "PW", "PWS", "ROWSPLIT")
 NORM_LAYER, NORM_RMS_MEANSQ, NORM_RMS_VAR = 0, 1, 2
@@ -137,7 +138,8 @@ class DinoDesc(C.Structure):
     _fields_ = [("hidden", C.c_int), ("layers", C.c_int), ("heads", C.c_int), ("patch", C.c_int), ("kpad", C.c_int),
                 ("cdt", C.c_int), ("adt", C.c_int), ("eps", C.c_float),
                 ("no_cls", C.c_int), ("act", C.c_int), ("head_dim", C.c_int), ("mlp_dim", C.c_int), ("out_all", C.c_int),
-                ("attn_scale", C.c_float)]
+                ("attn_scale", C.c_float),
+                ("pre_ln", C.c_int), ("n_prompt", C.c_int), ("prompt_depth", C.c_int), ("image_size", C.c_int)]      # CLIP with deep visual prompts
 
 
 class T5Desc(C.Structure):
@@ -258,6 +260,10 @@ SIGNATURES = {
     "vt_dino_set_range_flag": (_I, [_P, _P]),
     "vt_dino_forward": (_I, [_P, _P, _I, _I, _I, _F, _I, _I, _I, _P, _P, _P, _P, _P]),
     "vt_dino_embed": (_I, [_P, _P, _I, _I, _I, _F, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "vt_prompt_seam": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _P, _P]),
+    "vt_prompt_compact": (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    "vt_tactile_bank_norms": (_I, [_P, _I, _I, _P, _P]),
+    "vt_tactile_head": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
     "vt_t5_create": (_I, [_P, _P, _I, _P]),
     "vt_t5_destroy": (None, [_P]),
     "vt_t5_num_weights": (_I, [_P]),

@@ -344,6 +344,75 @@ def siglip_shapes(hidden: int, layers: int, inter: int, image_size: int = 384, p
     return d
 
 
+# ------------------------------------------------------------------ CLIP vision tower with deep visual prompts (Octopi's tactile encoder)
+CLIP_CONFIGS = {
+    "vit-l14": dict(hidden=1024, layers=24, heads=16, inter=4096, image_size=224, n_ctx=8, prompt_depth=12),      # openai/clip-vit-large-patch14
+    "tiny": dict(hidden=128, layers=3, heads=2, inter=512, image_size=28, n_ctx=3, prompt_depth=2),
+}
+
+
+def clip_prompt_depth(layers: int, prompt_depth: int) -> int:
+    """prompt_depth_vision as the encoder reads it: -1 = every layer."""
+    return layers if prompt_depth == -1 else prompt_depth
+
+
+def clip_shapes(hidden: int, layers: int, inter: int, image_size: int = 224, patch: int = 14, n_ctx: int = 0, prompt_depth: int = 0,
+                **_) -> Dict[str, Tuple[int, ...]]:
+    """HF CLIPVisionModel key map below `vision_model.` plus the prompt-learning parameters of octopi_s/utils/encoder.py: `VPT` [n_ctx, D] when
+    prompt_depth != 0, `encoder.layers.{i}.VPT_shallow` [n_ctx, D] for 1 <= i < depth, `encoder.layers.{i}.VPT_gamma` (a scalar) for every
+    layer but the last."""
+    D = hidden
+    P = clip_prompt_depth(layers, prompt_depth)
+    d: Dict[str, Tuple[int, ...]] = {
+        "embeddings.class_embedding": (D,),
+        "embeddings.patch_embedding.weight": (D, 3, patch, patch),
+        "embeddings.position_embedding.weight": ((image_size // patch) ** 2 + 1, D),
+        "pre_layrnorm.weight": (D,),
+        "pre_layrnorm.bias": (D,),
+    }
+    if P != 0:
+        d["VPT"] = (n_ctx, D)
+    for i in range(layers):
+        p = f"encoder.layers.{i}"
+        d[f"{p}.layer_norm1.weight"] = (D,)
+        d[f"{p}.layer_norm1.bias"] = (D,)
+        for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
+            d[f"{p}.self_attn.{n}.weight"] = (D, D)
+            d[f"{p}.self_attn.{n}.bias"] = (D,)
+        d[f"{p}.layer_norm2.weight"] = (D,)
+        d[f"{p}.layer_norm2.bias"] = (D,)
+        d[f"{p}.mlp.fc1.weight"] = (inter, D)
+        d[f"{p}.mlp.fc1.bias"] = (inter,)
+        d[f"{p}.mlp.fc2.weight"] = (D, inter)
+        d[f"{p}.mlp.fc2.bias"] = (D,)
+        if 1 <= i < P:
+            d[f"{p}.VPT_shallow"] = (n_ctx, D)
+        if i != layers - 1:
+            d[f"{p}.VPT_gamma"] = ()
+    d["post_layernorm.weight"] = (D,)
+    d["post_layernorm.bias"] = (D,)
+    return d
+
+
+def clip_prompt_init(name: str, n_ctx: int, hidden: int) -> np.ndarray:
+    """A prompt parameter (VPT, VPT_shallow) a checkpoint lacks, as the reference's constructor draws it: 0.02 x standard normal, here from the
+    deterministic generator of `name`."""
+    return (0.02 * _rng("clip-prompt-init." + name).standard_normal((n_ctx, hidden), dtype=np.float32)).astype(np.float32)
+
+
+def tactile_head_shapes(hidden: int = 1024, llm_dim: int = 3584) -> Dict[str, Dict[str, Tuple[int, ...]]]:
+    """The heads around the tactile encoder, one key map per saved file (octopi_s/utils/encoder.py:441-495, llm.py:141-145): Adapter (`rfc` =
+    Linear(D, 512), GELU, Linear(512, D); no `align` when input and output sizes agree, as load_encoder builds it), PropertyClassifier
+    (D -> 512 -> 256 with GELU after each, then two 1-wide heads) and the LLM projector (`project` = Linear(D, E), GELU, Linear(E, E))."""
+    D, E = hidden, llm_dim
+    return {
+        "adapter": {"rfc.0.weight": (512, D), "rfc.0.bias": (512,), "rfc.2.weight": (D, 512), "rfc.2.bias": (D,)},
+        "property_classifier": {"fc.0.weight": (512, D), "fc.0.bias": (512,), "fc.2.weight": (256, 512), "fc.2.bias": (256,),
+                                "hardness_fc.weight": (1, 256), "hardness_fc.bias": (1,), "roughness_fc.weight": (1, 256), "roughness_fc.bias": (1,)},
+        "project": {"0.weight": (E, D), "0.bias": (E,), "2.weight": (E, E), "2.bias": (E,)},
+    }
+
+
 # ------------------------------------------------------------------ a synthetic controller (bench / smoke / tests)
 MODEL_ARGS = {
     'interpolant_type': 'linear', 'gamma_type': '2^0.5*t(t-1)', 'epsilon_type': '1-t', 'prior_policy': 'vla',
